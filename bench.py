@@ -7,7 +7,10 @@ pass of the hot path over one batch: ``DiffusionDenoiser.denoise`` of B images t
 For N > 1 it runs one rank per GPU (launched by torch.distributed.run; started bare, it launches those
 ranks itself as a child process); the batch is sharded (B per GPU fixed -> weak scaling) and one RCCL
 all-gather collects the outputs.
-Rank 0 prints ONE JSON line.
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the steps and prints the line (`metric`, `value`,
+`unit`, `ms_per_step`, ...); `--full` adds the legs that take passes of their own after the timed region (per-kernel
+roofline, batch-1 latency, CPU baseline with a parity spot check).  `--dump-outputs DIR` writes the images the last timed
+step returned as DIR/denoised.npy; inputs and weights are seeded, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -150,6 +153,27 @@ def self_launch(args):
     raise SystemExit(0)
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays, limit=DUMP_LIMIT_BYTES):
+    """Writes each array as out_dir/<name>.npy in float32.  When all of them together exceed `limit` bytes, every array
+    is replaced by a fixed sample (same seeded flat indices from run to run, in ascending order) of its share of the
+    limit, saved as <name>_sample.npy.  Returns {file name: shape written}."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    written = {}
+    for name, a in arrays.items():
+        if total > limit:
+            keep = max(1, limit * a.size // total)          # this array's share of the limit, in elements
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=keep, replace=False))
+            a, name = a.reshape(-1)[idx], name + "_sample"
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        written[name + ".npy"] = list(a.shape)
+    return written
+
+
 def baseline_config_label(Bp, S, noise_steps, n_iters):
     """Which BASELINE.json configuration a (per-GPU batch, size, schedule) corresponds to."""
     if (Bp, S, noise_steps, n_iters) == (8, 256, 50, 50):
@@ -178,7 +202,14 @@ def main():
                          "per-kernel averages cover the bench workload only)")
     ap.add_argument("--compute", default=None, choices=["f16x3", "f32"],
                     help="MFMA arithmetic: split-fp16 x3 (default) or fp32-input MFMA")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also run the roofline, batch-1 latency and CPU-baseline legs "
+                         "(--cpu-iters / --latency-reps size the last two); a plain run times the steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float32, at most 64 MB)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -227,6 +258,9 @@ def main():
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = float(tmax.item())
     assert out.shape[0] == Bp * world and torch.isfinite(out).all()
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path receives from its last step: the denoised batch, all ranks' images
+        dump_outputs(args.dump_outputs, {"denoised": out.cpu().numpy()})
 
     images = Bp * world * args.steps
     value = images / elapsed
@@ -246,87 +280,88 @@ def main():
     }
 
     if rank == 0:
-        # ---- roofline leg: per-kernel HIP-event timing of one more step on the same stream ----
-        model.profile_begin()
-        den.denoise(noisy, inference_steps=args.inference_steps)
-        prof = model.profile_end()
-        total_ms = sum(p["total_ms"] for p in prof)
-        dom = max((p for p in prof if p["flops"] > 0), key=lambda p: p["total_ms"])
-        achieved = dom["flops"] / (dom["total_ms"] * 1e-3)
-        if model.compute == "f16x3":
-            # every fp32-equivalent product costs three fp16 MFMA products (hi*hi + hi*lo + lo*hi), so the
-            # attainable ALGORITHMIC rate is the dense fp16 MFMA peak / 3
-            peak, peak_note = PEAK_MFMA_F16 / 3, "2.5 PFLOP/s dense fp16 MFMA / 3 split passes"
-        else:
-            peak, peak_note = PEAK_MFMA_F32, "fp32-input MFMA dense peak"
-        traffic, traffic_src = pmc_traffic(dom["name"]) if (Bp == 8 and S == 256) else (None, "profiled for the default workload only")
-        result["roofline"] = {
-            "bound": "mfma", "kernel": dom["name"], "achieved": achieved / 1e12, "peak": peak / 1e12,
-            "unit": "TFLOP/s", "frac": achieved / peak, "traffic": traffic, "traffic_source": traffic_src, "peak_note": peak_note,
-            "measured_under": "HIP events around each launch on the stream it goes to; the batch runs as two half-batch "
-                              "programs on two streams, so another kernel is usually co-resident during a span",
-            "launches": dom["launches"], "avg_launch_us": 1e3 * dom["total_ms"] / dom["launches"],
-            "alg_flops_per_launch": dom["flops"] / dom["launches"],
-            "alg_bytes_per_launch": dom["bytes"] / dom["launches"],
-            "alg_GBps": dom["bytes"] / (dom["total_ms"] * 1e-3) / 1e9,
-            "frac_hbm_peak": dom["bytes"] / (dom["total_ms"] * 1e-3) / PEAK_HBM,
-            "share_of_kernel_time": dom["total_ms"] / total_ms,
-        }
-        # the same fraction from the committed rocprofv3 --kernel-trace --stats summary of this command, when it describes
-        # the library that is running (source hash): the tracer's averages sit several % above the in-bench events
-        rp_us, rp_src = rocprof_avg_us(dom["name"]) if (Bp == 8 and S == 256) else (None, "profiled for the default workload only")
-        result["roofline"]["frac_rocprof"] = (dom["flops"] / dom["launches"] / (rp_us * 1e-6) / peak) if rp_us else None
-        result["roofline"]["rocprof_avg_launch_us"] = rp_us
-        result["roofline"]["rocprof_source"] = rp_src
-        # the same kernel with nothing else on the chip: one more pass as ONE program on one stream (MI_NO_SPLIT)
-        model.profile_begin()
-        model.run_sampler(noisy, timestep_list(args.noise_steps, args.inference_steps), den.beta, den.alpha, den.alpha_hat, clamp_eps=True, no_split=True)
-        alone = {p["name"]: p for p in model.profile_end()}
-        big = max((p for p in alone.values() if p["flops"] > 0), key=lambda p: p["total_ms"])
-        result["roofline"]["alone"] = {
-            "what": "the dominant kernel of the same batch run as one program on one stream (no co-resident kernel)",
-            "kernel": big["name"], "achieved": big["flops"] / (big["total_ms"] * 1e-3) / 1e12,
-            "frac": big["flops"] / (big["total_ms"] * 1e-3) / peak, "avg_launch_us": 1e3 * big["total_ms"] / big["launches"],
-            "launches": big["launches"]}
-        gf = GF_PER_IMAGE_STEP.get(S)
-        if gf:
-            per_gpu_rate = (value / world) * n_iters          # image-steps per second per GPU
-            result["whole_loop"] = {
-                "ref_graph_tflops": per_gpu_rate * gf / 1e12,
-                # fraction of the peak of the arithmetic this run computes in (never of a peak it does not use)
-                "frac_mfma_peak": per_gpu_rate * gf / peak, "mfma_peak_note": peak_note,
-                "alg_GBps": per_gpu_rate * BYTES_PER_IMAGE_STEP_F32[S] / 1e9,
-                "frac_hbm_peak": per_gpu_rate * BYTES_PER_IMAGE_STEP_F32[S] / PEAK_HBM,
+        if args.full:
+            # ---- roofline leg: per-kernel HIP-event timing of one more step on the same stream ----
+            model.profile_begin()
+            den.denoise(noisy, inference_steps=args.inference_steps)
+            prof = model.profile_end()
+            total_ms = sum(p["total_ms"] for p in prof)
+            dom = max((p for p in prof if p["flops"] > 0), key=lambda p: p["total_ms"])
+            achieved = dom["flops"] / (dom["total_ms"] * 1e-3)
+            if model.compute == "f16x3":
+                # every fp32-equivalent product costs three fp16 MFMA products (hi*hi + hi*lo + lo*hi), so the
+                # attainable ALGORITHMIC rate is the dense fp16 MFMA peak / 3
+                peak, peak_note = PEAK_MFMA_F16 / 3, "2.5 PFLOP/s dense fp16 MFMA / 3 split passes"
+            else:
+                peak, peak_note = PEAK_MFMA_F32, "fp32-input MFMA dense peak"
+            traffic, traffic_src = pmc_traffic(dom["name"]) if (Bp == 8 and S == 256) else (None, "profiled for the default workload only")
+            result["roofline"] = {
+                "bound": "mfma", "kernel": dom["name"], "achieved": achieved / 1e12, "peak": peak / 1e12,
+                "unit": "TFLOP/s", "frac": achieved / peak, "traffic": traffic, "traffic_source": traffic_src, "peak_note": peak_note,
+                "measured_under": "HIP events around each launch on the stream it goes to; the batch runs as two half-batch "
+                                  "programs on two streams, so another kernel is usually co-resident during a span",
+                "launches": dom["launches"], "avg_launch_us": 1e3 * dom["total_ms"] / dom["launches"],
+                "alg_flops_per_launch": dom["flops"] / dom["launches"],
+                "alg_bytes_per_launch": dom["bytes"] / dom["launches"],
+                "alg_GBps": dom["bytes"] / (dom["total_ms"] * 1e-3) / 1e9,
+                "frac_hbm_peak": dom["bytes"] / (dom["total_ms"] * 1e-3) / PEAK_HBM,
+                "share_of_kernel_time": dom["total_ms"] / total_ms,
             }
-        result["kernels"] = sorted(
-            [dict(name=p["name"], launches=p["launches"], ms=round(p["total_ms"], 3),
-                  tflops=round(p["flops"] / (p["total_ms"] * 1e-3) / 1e12, 2) if p["flops"] else None,
-                  GBps=round(p["bytes"] / (p["total_ms"] * 1e-3) / 1e9, 1)) for p in prof],
-            key=lambda d: -d["ms"])[:24]
+            # the same fraction from the committed rocprofv3 --kernel-trace --stats summary of this command, when it describes
+            # the library that is running (source hash): the tracer's averages sit several % above the in-bench events
+            rp_us, rp_src = rocprof_avg_us(dom["name"]) if (Bp == 8 and S == 256) else (None, "profiled for the default workload only")
+            result["roofline"]["frac_rocprof"] = (dom["flops"] / dom["launches"] / (rp_us * 1e-6) / peak) if rp_us else None
+            result["roofline"]["rocprof_avg_launch_us"] = rp_us
+            result["roofline"]["rocprof_source"] = rp_src
+            # the same kernel with nothing else on the chip: one more pass as ONE program on one stream (MI_NO_SPLIT)
+            model.profile_begin()
+            model.run_sampler(noisy, timestep_list(args.noise_steps, args.inference_steps), den.beta, den.alpha, den.alpha_hat, clamp_eps=True, no_split=True)
+            alone = {p["name"]: p for p in model.profile_end()}
+            big = max((p for p in alone.values() if p["flops"] > 0), key=lambda p: p["total_ms"])
+            result["roofline"]["alone"] = {
+                "what": "the dominant kernel of the same batch run as one program on one stream (no co-resident kernel)",
+                "kernel": big["name"], "achieved": big["flops"] / (big["total_ms"] * 1e-3) / 1e12,
+                "frac": big["flops"] / (big["total_ms"] * 1e-3) / peak, "avg_launch_us": 1e3 * big["total_ms"] / big["launches"],
+                "launches": big["launches"]}
+            gf = GF_PER_IMAGE_STEP.get(S)
+            if gf:
+                per_gpu_rate = (value / world) * n_iters          # image-steps per second per GPU
+                result["whole_loop"] = {
+                    "ref_graph_tflops": per_gpu_rate * gf / 1e12,
+                    # fraction of the peak of the arithmetic this run computes in (never of a peak it does not use)
+                    "frac_mfma_peak": per_gpu_rate * gf / peak, "mfma_peak_note": peak_note,
+                    "alg_GBps": per_gpu_rate * BYTES_PER_IMAGE_STEP_F32[S] / 1e9,
+                    "frac_hbm_peak": per_gpu_rate * BYTES_PER_IMAGE_STEP_F32[S] / PEAK_HBM,
+                }
+            result["kernels"] = sorted(
+                [dict(name=p["name"], launches=p["launches"], ms=round(p["total_ms"], 3),
+                      tflops=round(p["flops"] / (p["total_ms"] * 1e-3) / 1e12, 2) if p["flops"] else None,
+                      GBps=round(p["bytes"] / (p["total_ms"] * 1e-3) / 1e9, 1)) for p in prof],
+                key=lambda d: -d["ms"])[:24]
 
-        # ---- CPU baseline (rank 0, N = 1 only) + a parity spot check on the same sample ----
-        if world == 1 and args.latency_reps > 0:
-            # serving regime (run.py:107 denoises one image per request): latency of a single image
-            one = torch.from_numpy(synthetic_xray(1, S, S, seed=1234)).to(dev)
-            den.denoise(one, inference_steps=args.inference_steps)
-            torch.cuda.synchronize()
-            t1 = time.perf_counter()
-            for _ in range(args.latency_reps):
+            # ---- CPU baseline (rank 0, N = 1 only) + a parity spot check on the same sample ----
+            if world == 1 and args.latency_reps > 0:
+                # serving regime (run.py:107 denoises one image per request): latency of a single image
+                one = torch.from_numpy(synthetic_xray(1, S, S, seed=1234)).to(dev)
                 den.denoise(one, inference_steps=args.inference_steps)
-            torch.cuda.synchronize()
-            result["latency_batch1"] = {"ms_per_image": 1e3 * (time.perf_counter() - t1) / args.latency_reps, "iterations": n_iters, "image": [S, S]}
-        if world == 1 and args.cpu_iters > 0 and S <= 512:
-            x_cpu, steps, base = cpu_baseline(sd_np, cfg, S, args.noise_steps, args.cpu_iters, Bp)
-            result["cpu_baseline"] = base
-            # row 0 of the TIMED batch (image seed 1234, the oracle's sample) through the same iterations, computed IN the
-            # batch the number above was measured on (same execution programs: per-program batch, tiles, key split)
-            x_gpu = model.run_sampler(noisy, steps, den.beta, den.alpha, den.alpha_hat, clamp_eps=True)
-            result["parity_max_abs_err_vs_oracle"] = float((x_gpu[:1].cpu() - x_cpu).abs().max())
-            result["parity_sample"] = f"row 0 of the timed batch of {Bp}, first {len(steps)} iterations"
-            result["speedup_vs_cpu_baseline"] = value / base["value"]
+                torch.cuda.synchronize()
+                t1 = time.perf_counter()
+                for _ in range(args.latency_reps):
+                    den.denoise(one, inference_steps=args.inference_steps)
+                torch.cuda.synchronize()
+                result["latency_batch1"] = {"ms_per_image": 1e3 * (time.perf_counter() - t1) / args.latency_reps, "iterations": n_iters, "image": [S, S]}
+            if world == 1 and args.cpu_iters > 0 and S <= 512:
+                x_cpu, steps, base = cpu_baseline(sd_np, cfg, S, args.noise_steps, args.cpu_iters, Bp)
+                result["cpu_baseline"] = base
+                # row 0 of the TIMED batch (image seed 1234, the oracle's sample) through the same iterations, computed IN the
+                # batch the number above was measured on (same execution programs: per-program batch, tiles, key split)
+                x_gpu = model.run_sampler(noisy, steps, den.beta, den.alpha, den.alpha_hat, clamp_eps=True)
+                result["parity_max_abs_err_vs_oracle"] = float((x_gpu[:1].cpu() - x_cpu).abs().max())
+                result["parity_sample"] = f"row 0 of the timed batch of {Bp}, first {len(steps)} iterations"
+                result["speedup_vs_cpu_baseline"] = value / base["value"]
         print(json.dumps(result), flush=True)
     if world > 1:
-        dist.barrier()                      # rank 0's roofline leg runs after the timed region; leave together
+        dist.barrier()                      # rank 0's --full legs run after the timed region; leave together
         dist.destroy_process_group()
 
 

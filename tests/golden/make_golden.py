@@ -25,6 +25,7 @@ import midd_loader  # noqa: E402
 midd_loader.load()
 from midd_amd.config import UNetConfig, timestep_list  # noqa: E402
 from midd_amd.weights import make_state_dict, synthetic_xray  # noqa: E402
+from tests.golden import save  # noqa: E402
 from tests.golden.ref_import import import_reference  # noqa: E402
 
 SMALL = dict(model_channels=16, time_emb_dim=64)
@@ -137,7 +138,7 @@ def main():
         arrays.update(den_noisy=noisy.numpy(), den_steps=np.array(steps, np.int64),
                       den_inference_steps=np.int64(S), den_eps=np.stack(eps_log),
                       den_x=np.stack(x_log), den_out=xf)
-        np.savez_compressed(os.path.join(HERE, f"small_{variant}.npz"), **arrays)
+        save(f"small_{variant}", arrays)                # in parts below 1 MiB (tests/golden/__init__.py)
 
     # ---- 3. full-size DDIM UNet (12.8 M params, weights regenerated, not stored) ------
     cfg = UNetConfig()
@@ -154,7 +155,7 @@ def main():
                       den_x_after_1=x_log[0], den_x_after_5=x_log[4],
                       den_eps_first=eps_log[0], den_eps_last=eps_log[-1],
                       seed_image=np.int64(1234), seed_weights=np.int64(42))
-        np.savez_compressed(os.path.join(HERE, f"{tag}.npz"), **arrays)
+        save(tag, arrays)
         print(tag, "done", float(xf.mean()))
 
     # 9-iteration served setting (run.py:107 uses inference_steps=8) at 64x64, B=2

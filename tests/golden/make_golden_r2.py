@@ -31,6 +31,7 @@ import midd_loader  # noqa: E402
 midd_loader.load()
 from midd_amd.config import UNetConfig, timestep_list  # noqa: E402
 from midd_amd.weights import make_state_dict, synthetic_xray  # noqa: E402
+from tests.golden import save  # noqa: E402
 from tests.golden.make_golden import SMALL, build, traced_denoise  # noqa: E402
 from tests.golden.ref_import import import_reference, import_hybrid  # noqa: E402
 
@@ -98,8 +99,8 @@ def gen_c3(ref):
     noisy = torch.from_numpy(synthetic_xray(2, 256, 256, seed=5100))
     xf, eps_log, x_log = traced_denoise(den, noisy, 100)
     assert len(eps_log) == 100
-    np.savez_compressed(os.path.join(HERE, "full_ddim_256_n100.npz"), den_out=xf, den_eps_first=eps_log[0], den_eps_last=eps_log[-1],
-                        den_x_after_1=x_log[0], den_x_after_50=x_log[49], seed_image=np.int64(5100))
+    save("full_ddim_256_n100", dict(den_out=xf, den_eps_first=eps_log[0], den_eps_last=eps_log[-1],
+                                    den_x_after_1=x_log[0], den_x_after_50=x_log[49], seed_image=np.int64(5100)))
     print("c3 done", float(xf.mean()))
 
 
@@ -109,8 +110,8 @@ def gen_c5(ref):
     den = ref.ddim.DiffusionDenoiser(model, noise_steps=50)
     noisy = torch.from_numpy(synthetic_xray(1, 512, 512, seed=6200))
     xf, eps_log, x_log = traced_denoise(den, noisy, 50)
-    np.savez_compressed(os.path.join(HERE, "full_ddim_512.npz"), den_out=xf, den_eps_first=eps_log[0], den_eps_last=eps_log[-1],
-                        den_x_after_1=x_log[0], den_x_after_25=x_log[24], seed_image=np.int64(6200))
+    save("full_ddim_512", dict(den_out=xf, den_eps_first=eps_log[0], den_eps_last=eps_log[-1],
+                               den_x_after_1=x_log[0], den_x_after_25=x_log[24], seed_image=np.int64(6200)))
     print("c5 done", float(xf.mean()))
 
 

@@ -7,6 +7,7 @@ import subprocess
 import sys
 import types
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -62,3 +63,41 @@ def test_stale_pmc_profile_is_refused():
         assert traffic is None or traffic > 0
     else:
         assert traffic is None and "stale" in why
+
+
+def test_dump_outputs_writes_float32_arrays(tmp_path):
+    bench = _bench()
+    x = np.arange(2 * 1 * 4 * 5, dtype=np.float64).reshape(2, 1, 4, 5)
+    written = bench.dump_outputs(str(tmp_path / "out"), {"denoised": x})
+    assert written == {"denoised.npy": [2, 1, 4, 5]}
+    got = np.load(tmp_path / "out" / "denoised.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, x.astype(np.float32))
+
+
+def test_dump_outputs_samples_a_large_output_the_same_way_every_run(tmp_path):
+    bench = _bench()
+    x = np.random.default_rng(5).standard_normal((3, 1, 64, 64)).astype(np.float32)      # 48 KiB
+    limit = 16 << 10
+    a = bench.dump_outputs(str(tmp_path / "a"), {"denoised": x}, limit=limit)
+    b = bench.dump_outputs(str(tmp_path / "b"), {"denoised": x}, limit=limit)
+    assert a == b == {"denoised_sample.npy": [limit // 4]}
+    sa, sb = np.load(tmp_path / "a" / "denoised_sample.npy"), np.load(tmp_path / "b" / "denoised_sample.npy")
+    assert sa.nbytes <= limit and np.array_equal(sa, sb)
+    assert np.isin(sa, x.reshape(-1)).all()                    # values of the output itself, not a summary
+
+
+def test_plain_and_full_options_parse(monkeypatch):
+    """--full and --dump-outputs reach the ranks a bare multi-GPU run launches; --steps 0 is refused."""
+    bench = _bench()
+    seen = {}
+    monkeypatch.setattr(subprocess, "run", lambda cmd, **k: seen.setdefault("cmd", cmd) and types.SimpleNamespace(
+        returncode=0, stdout='{"metric": "m"}\n'))
+    monkeypatch.delenv("WORLD_SIZE", raising=False)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "2", "--full", "--dump-outputs", "d"])
+    with pytest.raises(SystemExit) as exc:
+        bench.main()
+    assert exc.value.code == 0 and seen["cmd"][-4:] == ["2", "--full", "--dump-outputs", "d"]
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "0"])
+    with pytest.raises(SystemExit) as exc:
+        bench.main()
+    assert exc.value.code == 2

@@ -4,7 +4,6 @@ All calls go through the C ABI (ctypes -> libmidd.so).  Tolerance: north_star st
 |delta| < 1e-3 per pixel in fp32 for the sampler output; per-layer and single-forward checks
 use tighter bounds (printed so regressions are visible long before the 1e-3 gate).
 """
-import os
 
 import numpy as np
 import pytest
@@ -14,10 +13,10 @@ from midd_amd import UNetDiffusion, DiffusionDenoiser, UNetConfig, topology, tim
 from midd_amd import native
 from midd_amd.weights import make_state_dict, synthetic_xray
 from oracle import ddim_oracle as orc
+from tests import golden
 
 pytestmark = pytest.mark.gpu
 
-G = os.path.join(os.path.dirname(__file__), "golden")
 SMALL = dict(model_channels=16, time_emb_dim=64)
 TOL_FINAL = 1e-3          # north_star: |delta| < 1e-3 fp32 per pixel
 TOL_LAYER = 2e-4          # per-module activations (values are O(1))
@@ -48,7 +47,7 @@ def full_model(request):
 @pytest.mark.parametrize("compute", COMPUTE_MODES)
 @pytest.mark.parametrize("variant", ["ddim", "cddpm"])
 def test_small_per_layer_vs_golden_and_oracle(variant, compute):
-    g = np.load(os.path.join(G, f"small_{variant}.npz"))
+    g = golden.load(f"small_{variant}")
     cfg = UNetConfig(variant=variant, **SMALL)
     sd = make_state_dict(cfg, seed=42, perturb_norm=True)
     model = _model(SMALL, sd, variant, compute)
@@ -82,7 +81,7 @@ def test_small_per_layer_vs_golden_and_oracle(variant, compute):
 @pytest.mark.parametrize("compute", COMPUTE_MODES)
 @pytest.mark.parametrize("variant", ["ddim", "cddpm"])
 def test_small_sampler_vs_golden(variant, compute):
-    g = np.load(os.path.join(G, f"small_{variant}.npz"))
+    g = golden.load(f"small_{variant}")
     cfg = UNetConfig(variant=variant, **SMALL)
     sd = make_state_dict(cfg, seed=42, perturb_norm=True)
     model = _model(SMALL, sd, variant, compute)
@@ -142,7 +141,7 @@ def test_sampler_schedules_and_batch_shapes_vs_oracle(case):
 # ------------------------------------------------------------------------------ full network
 def test_full_forward_64_vs_golden(full_model):
     cfg, sd, model = full_model
-    g = np.load(os.path.join(G, "full_ddim_64.npz"))
+    g = golden.load("full_ddim_64")
     noisy = torch.from_numpy(synthetic_xray(1, 64, 64, seed=1234)).cuda()
     eps = model(noisy, noisy, torch.tensor([49]))
     d = _maxdiff(eps.cpu().numpy(), g["fwd_eps_t49"])
@@ -166,7 +165,7 @@ def test_full_forward_64_vs_golden(full_model):
 
 def test_full_sampler_64_vs_golden(full_model):
     cfg, sd, model = full_model
-    g = np.load(os.path.join(G, "full_ddim_64.npz"))
+    g = golden.load("full_ddim_64")
     noisy = torch.from_numpy(synthetic_xray(1, 64, 64, seed=1234)).cuda()
     den = DiffusionDenoiser(model, noise_steps=50)
     for steps, key in ((50, "den_out"),):
@@ -175,12 +174,12 @@ def test_full_sampler_64_vs_golden(full_model):
         print(f"full 64 x 50 steps max|d| = {d:.2e}")
         assert d < TOL_FINAL
     # the served setting: inference_steps=8 -> 9 iterations (run.py:107)
-    g8 = np.load(os.path.join(G, "full_ddim_64_s8.npz"))
+    g8 = golden.load("full_ddim_64_s8")
     noisy2 = torch.from_numpy(synthetic_xray(2, 64, 64, seed=1234)).cuda()
     out = den.ddim_sample(noisy2, inference_steps=8)
     assert _maxdiff(out.cpu().numpy(), g8["den_out"]) < TOL_FINAL
     # noise_steps=100 (BASELINE.json config 3 needs DiffusionDenoiser(model, noise_steps=100))
-    g100 = np.load(os.path.join(G, "full_ddim_64_n100.npz"))
+    g100 = golden.load("full_ddim_64_n100")
     den100 = DiffusionDenoiser(model, noise_steps=100)
     noisy3 = torch.from_numpy(synthetic_xray(1, 64, 64, seed=4321)).cuda()
     out = den100.denoise(noisy3, inference_steps=100)
@@ -192,7 +191,7 @@ def test_full_sampler_64_vs_golden(full_model):
 def test_full_sampler_256_vs_golden(full_model):
     """BASELINE.json's resolution: 256x256, 50 steps, against the reference's own output."""
     cfg, sd, model = full_model
-    g = np.load(os.path.join(G, "full_ddim_256.npz"))
+    g = golden.load("full_ddim_256")
     noisy = torch.from_numpy(synthetic_xray(1, 256, 256, seed=1234)).cuda()
     eps = model(noisy, noisy, torch.tensor([49]))
     d0 = _maxdiff(eps.cpu().numpy(), g["den_eps_first"])

@@ -4,7 +4,6 @@ iterations), configs[3]'s shard (B=32 x 256^2 x 50), configs[4]'s shard (B=8 x 5
 GroupNorm-offset stress, weights reloaded into a live plan, two threads on two streams.
 
 All through the C ABI.  Tolerances as in test_gpu_parity.py (north_star: |delta| < 1e-3 on sampler outputs)."""
-import os
 import threading
 
 import numpy as np
@@ -14,10 +13,10 @@ import torch
 from midd_amd import UNetDiffusion, DiffusionDenoiser, UNetConfig, topology, timestep_list
 from midd_amd.weights import make_state_dict, synthetic_xray
 from oracle import ddim_oracle as orc
+from tests import golden
 
 pytestmark = pytest.mark.gpu
 
-G = os.path.join(os.path.dirname(__file__), "golden")
 SMALL = dict(model_channels=16, time_emb_dim=64)
 TOL_FINAL, TOL_EPS = 1e-3, 2e-4
 COMPUTE_MODES = ["f16x3", "f32"]
@@ -64,8 +63,8 @@ def test_every_iteration_eps_and_x(fixture, compute):
     """eps_i = model(x_{i-1}, noisy, t_i) against the reference's recorded (pre-clamp) eps of EVERY iteration, and x
     after k = 1..n iterations against its recorded x_k -- unsaturated pixels included, unlike the final image
     (DDIMModel.py:277-284; the clamp fixture has 46 % of |eps| beyond 5, so :278 is live)."""
-    base = np.load(os.path.join(G, "small_ddim.npz" if fixture == "small_ddim_clamp" else f"{fixture}.npz"))
-    g = np.load(os.path.join(G, f"{fixture}.npz"))
+    base = golden.load("small_ddim" if fixture == "small_ddim_clamp" else fixture)
+    g = golden.load(fixture)
     variant = "cddpm" if "cddpm" in fixture else "ddim"
     cfg = UNetConfig(variant=variant, **SMALL)
     sd = _clamp_sd(cfg, 42, True) if fixture.endswith("clamp") else make_state_dict(cfg, seed=42, perturb_norm=True)
@@ -96,7 +95,7 @@ def test_clamp_active_full_network(full_model):
     (Longer horizons are not a parity target for this fixture: with the x15 head the loop amplifies rounding
     differences -- the reference's own 50-iteration output moves by 9e-4 between 4 and 8 CPU threads.)"""
     cfg, _, ref_model = full_model
-    g = np.load(os.path.join(G, "full_ddim_64_clamp.npz"))
+    g = golden.load("full_ddim_64_clamp")
     model = _model({}, _clamp_sd(cfg, 42, False), compute=ref_model.compute)
     den = DiffusionDenoiser(model, noise_steps=50)
     noisy = torch.from_numpy(synthetic_xray(1, 64, 64, seed=1234)).cuda()
@@ -116,7 +115,7 @@ def test_clamp_active_full_network(full_model):
 def test_256_intermediate_states(full_model):
     """The 256x256 fixture's intermediate records (round 1 read only den_out and the first eps)."""
     cfg, sd, model = full_model
-    g = np.load(os.path.join(G, "full_ddim_256.npz"))
+    g = golden.load("full_ddim_256")
     den = DiffusionDenoiser(model, noise_steps=50)
     noisy = torch.from_numpy(synthetic_xray(1, 256, 256, seed=1234)).cuda()
     steps = timestep_list(50, 50)
@@ -141,7 +140,7 @@ def test_config3_b32_256_100_iterations(full_model):
     """configs[2]: batch 32, 256x256, noise_steps = inference_steps = 100; the two reference images sit at slots 5
     and 27, the other 30 rows are covered by determinism + slot-permutation equivariance (bit for bit)."""
     cfg, sd, model = full_model
-    g = np.load(os.path.join(G, "full_ddim_256_n100.npz"))
+    g = golden.load("full_ddim_256_n100")
     known = synthetic_xray(2, 256, 256, seed=int(g["seed_image"]))
     den = DiffusionDenoiser(model, noise_steps=100)
     noisy = _batch_with(known, (5, 27), 32, 256, seed0=9000)
@@ -161,7 +160,7 @@ def test_config3_b32_256_100_iterations(full_model):
 def test_config4_shard_b32_256_50_iterations(full_model):
     """configs[3]'s per-GPU shard: batch 32, 256x256, 50 iterations; reference image at slot 17."""
     cfg, sd, model = full_model
-    g = np.load(os.path.join(G, "full_ddim_256.npz"))
+    g = golden.load("full_ddim_256")
     known = synthetic_xray(1, 256, 256, seed=1234)
     den = DiffusionDenoiser(model, noise_steps=50)
     noisy = _batch_with(known, (17,), 32, 256, seed0=9100)
@@ -175,7 +174,7 @@ def test_config4_shard_b32_256_50_iterations(full_model):
 def test_config5_shard_b8_512_50_iterations(full_model):
     """configs[4]'s per-GPU shard: batch 8, 512x512 (N = 4096 attention), 50 iterations; reference image at slot 3."""
     cfg, sd, model = full_model
-    g = np.load(os.path.join(G, "full_ddim_512.npz"))
+    g = golden.load("full_ddim_512")
     known = synthetic_xray(1, 512, 512, seed=int(g["seed_image"]))
     den = DiffusionDenoiser(model, noise_steps=50)
     noisy = _batch_with(known, (3,), 8, 512, seed0=9200)
@@ -349,7 +348,7 @@ def test_batch_invariant_mode_is_bit_exact_across_batch_sizes(compute):
         t = torch.full((8,), 11, dtype=torch.long, device="cuda")
         e8 = m(x, x, t)
         assert torch.equal(m(x[2:3].contiguous(), x[2:3].contiguous(), t[2:3]), e8[2:3])
-    g = np.load(os.path.join(G, "full_ddim_64.npz"))          # 64x64, 50 iterations, weights seed 42 / image seed 1234
+    g = golden.load("full_ddim_64")          # 64x64, 50 iterations, weights seed 42 / image seed 1234
     out = den.denoise(torch.from_numpy(synthetic_xray(1, 64, 64, seed=1234)).cuda(), inference_steps=50)
     assert _maxdiff(out, g["den_out"]) < TOL_FINAL
 

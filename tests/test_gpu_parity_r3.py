@@ -7,7 +7,6 @@
   * non-finite activations are reported (mi_status), not silently turned into finite statistics.
 
 All through the C ABI.  Tolerances as in test_gpu_parity.py (north_star: |delta| < 1e-3 on sampler outputs)."""
-import os
 
 import numpy as np
 import pytest
@@ -16,10 +15,10 @@ import torch
 from midd_amd import UNetDiffusion, DiffusionDenoiser, UNetConfig, topology, timestep_list
 from midd_amd.weights import make_state_dict, synthetic_xray
 from oracle import ddim_oracle as orc
+from tests import golden
 
 pytestmark = pytest.mark.gpu
 
-G = os.path.join(os.path.dirname(__file__), "golden")
 TOL_FINAL, TOL_EPS = 1e-3, 2e-4
 COMPUTE_MODES = ["f16x3", "f32"]
 
@@ -50,7 +49,7 @@ def test_config2_b8_256_50_iterations(full_model):
     choice, persistent workgroups per sample, statistics copies and the attention key split all follow the per-program
     batch (4), which no other fixture test exercises."""
     cfg, sd, model = full_model
-    g = np.load(os.path.join(G, "full_ddim_256.npz"))
+    g = golden.load("full_ddim_256")
     known = synthetic_xray(1, 256, 256, seed=1234)
     x = synthetic_xray(8, 256, 256, seed=9300)
     x[6] = known[0]
@@ -252,7 +251,7 @@ def test_no_split_run_matches_fixture_and_default(full_model):
     programs that run alone) see 64x64 and 32x32 maps of a full batch.  Same image as the default two-stream run to
     rounding (the per-program batch changes tiles and partial-sum grouping), both within the gate of the reference fixture."""
     cfg, sd, model = full_model
-    g = np.load(os.path.join(G, "full_ddim_256.npz"))
+    g = golden.load("full_ddim_256")
     x = synthetic_xray(8, 256, 256, seed=9400)
     x[3] = synthetic_xray(1, 256, 256, seed=1234)[0]
     noisy = torch.from_numpy(x).cuda()

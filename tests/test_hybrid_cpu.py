@@ -1,5 +1,6 @@
 """Hybrid-router caller, the parts that need no GPU: state-dict compatibility with the
 reference's HybridDenoisingRouter (hybrid3diffusionspeed.py:560-600) and the fixture that pins it."""
+import json
 import os
 
 import numpy as np
@@ -9,12 +10,11 @@ import torch.nn as nn
 
 from midd_amd import UNetConfig, param_shapes
 from midd_amd.hybrid import HybridDenoisingRouter
-
-G = os.path.join(os.path.dirname(__file__), "golden")
+from tests import golden
 
 
 def test_router_state_dict_layout_matches_fixture():
-    g = np.load(os.path.join(G, "hybrid_ddim_64.npz"))
+    g = golden.load("hybrid_ddim_64")
     ours = HybridDenoisingRouter(nn.Identity(), nn.Identity(), nn.Identity())
     mine = {k: tuple(v.shape) for k, v in ours.state_dict().items() if k.startswith("diffusion_unet.")}
     theirs = {str(k): tuple(int(d) for d in str(s).split(",") if d) for k, s in zip(g["router_unet_keys"], g["router_unet_shapes"])}
@@ -26,25 +26,48 @@ def test_router_state_dict_layout_matches_fixture():
     assert ours.diffusion_wrapper.noise_steps == 50
 
 
-@pytest.mark.reference
+class _RecordedLayout(nn.Module):
+    """A side network (NAFNet, NoiseAnalyzer, FusionModule: ordinary torch modules, injected) with exactly the recorded
+    state-dict layout of the reference's own module; forward passes the image through."""
+
+    def __init__(self, entries):
+        super().__init__()
+        for name, shape, dtype, is_param in entries:
+            *path, leaf = name.split(".")
+            mod = self
+            for p in path:
+                if not hasattr(mod, p):
+                    mod.add_module(p, nn.Module())
+                mod = getattr(mod, p)
+            t = torch.zeros(shape, dtype=getattr(torch, dtype))
+            if is_param:
+                mod.register_parameter(leaf, nn.Parameter(t, requires_grad=t.is_floating_point()))
+            else:
+                mod.register_buffer(leaf, t)
+
+    def forward(self, x):
+        return x
+
+
 def test_reference_router_checkpoint_loads_strictly():
     """run.py:59-72: HybridDenoisingRouter(...).load_state_dict(ckpt['model_state_dict']) with the side networks being
-    the reference's own torch modules."""
-    from tests.golden.ref_import import import_hybrid
-    hyb = import_hybrid()
-    naf = dict(width=8, middle_blk_num=1, enc_blk_nums=[1, 1], dec_blk_nums=[1, 1])
-    theirs = hyb.HybridDenoisingRouter(naf, {"noise_steps": 50}, inference_diffusion_steps=7)
-    ours = HybridDenoisingRouter(
-        nafnet=hyb.EnhancedNAFNet(img_channel=1, width=8, middle_blk_num=1, enc_blk_nums=[1, 1], dec_blk_nums=[1, 1]),
-        router=hyb.NoiseAnalyzer(in_c=1, out_c=1, base_c=32), fusion=hyb.FusionModule(in_c=3, out_c=1, base_c=48),
-        diffusion_params={"noise_steps": 50}, inference_diffusion_steps=7)
-    sd = theirs.state_dict()
+    the reference's own torch modules -- here stand-ins with their recorded layout (tests/golden/make_golden_pins.py:
+    the reference router built with a width-8 NAFNet, NoiseAnalyzer(1, 1, 32), FusionModule(3, 1, 48), noise_steps 50)."""
+    with open(os.path.join(golden.HERE, "reference_pins.json")) as f:
+        layout = [(k, tuple(s), dt, p) for k, s, dt, p in json.load(f)["router"]]
+    side = {pre: _RecordedLayout([(k[len(pre) + 1:], s, dt, p) for k, s, dt, p in layout if k.startswith(pre + ".")])
+            for pre in ("nafnet", "router", "fusion")}
+    ours = HybridDenoisingRouter(nafnet=side["nafnet"], router=side["router"], fusion=side["fusion"],
+                                 diffusion_params={"noise_steps": 50}, inference_diffusion_steps=7)
+    gen = torch.Generator().manual_seed(3)
+    sd = {k: torch.randn(s, generator=gen).to(getattr(torch, dt)) for k, s, dt, _ in layout}      # the reference's keys, in order
     assert list(sd) == list(ours.state_dict())
     ours.load_state_dict(sd, strict=True)
     for k, v in ours.state_dict().items():
         assert torch.equal(v, sd[k]), k
     ours.inference_diffusion_steps = 8                                       # run.py:71-72
     ours.training_diffusion_steps = 8
-    assert torch.equal(ours.diffusion_wrapper.beta.cpu(), theirs.diffusion_wrapper.beta.cpu())
+    beta = golden.load("reference_pins")["router_beta"]                     # the reference router's diffusion_wrapper.beta
+    assert torch.equal(ours.diffusion_wrapper.beta.cpu(), torch.from_numpy(beta))
     with pytest.raises(RuntimeError):                                        # no CPU fallback for the diffusion branch
         ours.eval()(torch.rand(1, 1, 32, 32))

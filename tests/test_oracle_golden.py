@@ -1,7 +1,5 @@
 """Oracle vs the committed golden fixtures (outputs of the reference itself,
 tests/golden/make_golden.py).  CPU only; runs in the container and on the GPU box."""
-import os
-
 import numpy as np
 import pytest
 import torch
@@ -9,13 +7,13 @@ import torch
 from midd_amd.config import UNetConfig, topology, timestep_list
 from midd_amd.weights import make_state_dict, synthetic_xray
 from oracle import ddim_oracle as orc
+from tests import golden
 
-G = os.path.join(os.path.dirname(__file__), "golden")
 SMALL = dict(model_channels=16, time_emb_dim=64)
 
 
 def _load(name):
-    return np.load(os.path.join(G, name))
+    return golden.load(name[:-len(".npz")])
 
 
 def test_schedule_tables():

@@ -1,8 +1,11 @@
-"""Pins the oracle: the CPU restatement must equal the imported reference.
+"""Pins the oracle: the CPU restatement must equal the reference.
 
-Runs only in the build container (needs /root/reference).  The reference has no tests or
-golden vectors of its own, so this import is the pin.
+The reference has no tests or golden vectors of its own, so its outputs were recorded by importing
+it (tests/golden/make_golden_pins.py): state-dict layout, every top-level block of one forward, and two sampler runs.
 """
+import json
+import os
+
 import numpy as np
 import pytest
 import torch
@@ -10,40 +13,44 @@ import torch
 from midd_amd.config import UNetConfig, topology, param_shapes, timestep_list
 from midd_amd.weights import make_state_dict, synthetic_xray
 from oracle import ddim_oracle as orc
-
-pytestmark = pytest.mark.reference
+from tests import golden
 
 SMALL = dict(model_channels=16, time_emb_dim=32)
 
 
-def _load_ref(ref_mod, cfg, sd_np):
-    kw = dict(in_channels=cfg.in_channels, model_channels=cfg.model_channels,
-              channel_mult=cfg.channel_mult, num_res_blocks=cfg.num_res_blocks,
-              attention_resolutions=cfg.attention_resolutions, dropout=cfg.dropout,
-              time_emb_dim=cfg.time_emb_dim)
-    model = ref_mod.UNetDiffusion(**kw)
-    model.load_state_dict({k: torch.from_numpy(v.copy()) for k, v in sd_np.items()}, strict=True)
-    return model.eval()
+@pytest.fixture(autouse=True)
+def _recording_threads():
+    """The pins were recorded with 8 intra-op threads (make_golden_pins.py); a single-threaded CPU convolution rounds
+    differently by a few ulp, so the oracle runs with the recording's thread count."""
+    n = torch.get_num_threads()
+    torch.set_num_threads(8)
+    yield
+    torch.set_num_threads(n)
+
+
+def _pins():
+    with open(os.path.join(golden.HERE, "reference_pins.json")) as f:
+        return json.load(f)
 
 
 @pytest.mark.parametrize("variant", ["ddim", "cddpm"])
-def test_state_dict_names_and_shapes_match_reference(reference_module, variant):
+def test_state_dict_names_and_shapes_match_reference(variant):
     cfg = UNetConfig(variant=variant)
-    ref = getattr(reference_module, variant).UNetDiffusion()
-    ref_sd = ref.state_dict()
+    ref_sd = {n: tuple(s) for n, s in _pins()["state_dict"][variant]}      # the reference's UNetDiffusion().state_dict()
     ours = param_shapes(cfg)
     assert [n for n, _ in ours] == list(ref_sd.keys())
     for n, s in ours:
-        assert tuple(ref_sd[n].shape) == s, n
+        assert ref_sd[n] == s, n
     nparam = sum(int(np.prod(s)) for _, s in ours)
     assert nparam == (12_823_489 if variant == "ddim" else 12_526_273)    # SURVEY.md App. B
 
 
-def test_schedule_matches_reference(reference_module):
+def test_schedule_matches_reference():
+    g = golden.load("schedule")                       # the reference DiffusionDenoiser's beta / alpha / alpha_hat
     for steps in (50, 100):
-        d = reference_module.ddim.DiffusionDenoiser(None, noise_steps=steps)
         b, a, ah = orc.schedule(steps)
-        assert torch.equal(b, d.beta) and torch.equal(a, d.alpha) and torch.equal(ah, d.alpha_hat)
+        assert torch.equal(b, torch.from_numpy(g[f"beta_{steps}"])) and torch.equal(a, torch.from_numpy(g[f"alpha_{steps}"])) \
+            and torch.equal(ah, torch.from_numpy(g[f"alpha_hat_{steps}"]))
 
 
 def test_iteration_counts():
@@ -54,27 +61,18 @@ def test_iteration_counts():
 
 
 @pytest.mark.parametrize("variant", ["ddim", "cddpm"])
-def test_forward_blockwise_equal(reference_module, variant):
+def test_forward_blockwise_equal(variant):
     cfg = UNetConfig(variant=variant, **SMALL)
     topo = topology(cfg)
     sd_np = make_state_dict(cfg, seed=7, perturb_norm=True)
-    model = _load_ref(getattr(reference_module, variant), cfg, sd_np)
     sd = orc.to_torch(sd_np)
     x = torch.from_numpy(synthetic_xray(2, 32, 40, seed=3, kind="uniform"))
     cond = torch.from_numpy(synthetic_xray(2, 32, 40, seed=5))
     t = torch.tensor([13, 13])
 
-    captured = {}
-    hooks = []
-    for name, mod in model.named_modules():
-        top = (name.startswith(("downs.", "ups.")) and name.count(".") == 1) or \
-              name in ("mid_block1", "mid_attn", "mid_block2", "in_conv", "out_conv", "time_mlp")
-        if top:
-            hooks.append(mod.register_forward_hook(lambda m, i, o, n=name: captured.__setitem__(n, o.detach())))
-    with torch.no_grad():
-        ref_out = model(x, cond, t)
-    for h in hooks:
-        h.remove()
+    g = golden.load(f"forward_blocks_{variant}")      # forward hooks on the reference's top-level blocks, same inputs
+    captured = {k[len("layer/"):]: torch.from_numpy(g[k]) for k in g.files if k.startswith("layer/")}
+    ref_out = torch.from_numpy(g["out"])
 
     ours = {}
     with torch.no_grad():
@@ -85,30 +83,27 @@ def test_forward_blockwise_equal(reference_module, variant):
     torch.testing.assert_close(out, ref_out, rtol=0, atol=2e-6)
 
 
-def test_denoise_equal_ddim(reference_module):
+def test_denoise_equal_ddim():
     cfg = UNetConfig(**SMALL)
     topo = topology(cfg)
     sd_np = make_state_dict(cfg, seed=11, perturb_norm=True)
-    model = _load_ref(reference_module.ddim, cfg, sd_np)
-    den = reference_module.ddim.DiffusionDenoiser(model, noise_steps=50)
+    g = golden.load("reference_pins")
     noisy = torch.from_numpy(synthetic_xray(2, 32, 32, seed=21))
+    ref = torch.from_numpy(g["ddim_out"])             # the reference's denoise(noisy, inference_steps=8)
+    assert torch.equal(noisy, torch.from_numpy(g["ddim_noisy_after"]))      # the reference does not mutate its input
     keep = noisy.clone()
-    ref = den.denoise(noisy, inference_steps=8)
-    assert torch.equal(noisy, keep)                  # the reference does not mutate its input
     ours = orc.denoise(orc.to_torch(sd_np), topo, noisy, noise_steps=50, inference_steps=8)
+    assert torch.equal(noisy, keep)
     torch.testing.assert_close(ours, ref, rtol=0, atol=5e-6)
 
 
-def test_denoise_equal_cddpm(reference_module):
+def test_denoise_equal_cddpm():
     cfg = UNetConfig(variant="cddpm", **SMALL)
     topo = topology(cfg)
     sd_np = make_state_dict(cfg, seed=12, perturb_norm=True)
-    model = _load_ref(reference_module.cddpm, cfg, sd_np)
-    den = reference_module.cddpm.DiffusionDenoiser(model, noise_steps=50)
     noisy = torch.from_numpy(synthetic_xray(1, 32, 32, seed=22))
     steps = timestep_list(50, 5)
-    torch.manual_seed(1234)
-    ref = den.denoise(noisy, inference_steps=5)
+    ref = torch.from_numpy(golden.load("reference_pins")["cddpm_out"])     # torch.manual_seed(1234); denoise(noisy, 5)
     # replay the reference's RNG consumption: one randn_like per iteration with i > 0
     torch.manual_seed(1234)
     noises = [torch.randn_like(noisy) * 0.5 if i > 0 else None for i in steps]

@@ -7,7 +7,7 @@ OUT=$GRAFT_REPO_ROOT/gpurun_out/tpo_$NAME; mkdir -p $OUT
 cd /tmp; export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
 export MIDD_SPLIT=1 MIDD_PLAN_AS_SIDE=1
 [ -n "$3" ] && export MIDD_LIBRARY=$GRAFT_REPO_ROOT/$3
-CMD="python3 bench.py --steps 1 --warmup 0 --cpu-iters 0 --latency-reps 0 --inference-steps 2 --batch-per-gpu $B"
+CMD="python3 bench.py --full --steps 1 --warmup 0 --cpu-iters 0 --latency-reps 0 --inference-steps 2 --batch-per-gpu $B"
 timeout -k 10 300 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $OUT/pf -o pf --output-format csv -- $CMD > $OUT/pf.log 2>&1
 timeout -k 10 300 rocprofv3 --kernel-trace --pmc WRITE_SIZE -d $OUT/pw -o pw --output-format csv -- $CMD > $OUT/pw.log 2>&1
 python3 - <<PY
