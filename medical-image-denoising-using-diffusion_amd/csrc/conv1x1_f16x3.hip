@@ -13,7 +13,7 @@
 //     fetched once by LDS-DMA and reused for every pixel tile the persistent workgroup walks;
 //   * has no barrier in the K loop; the activation loads run two K-steps ahead in registers, across tile borders.
 // Epilogue and contract are those of conv_mfma_f16x3.hip (bias / time embedding / residual, GroupNorm partial
-// sums of the output per (workgroup, wave) row).  Weight pack: pack_conv_f16x3 (midd_api.hip), 32 channels per step.
+// sums of the output per (workgroup, wave) row).  Weight pack: pack_conv_f16x3 (midd_weights.hip), 32 channels per step.
 //
 // Attention hand-off (round 3: the attention block is three launches, qkv -> attention -> proj; it was five):
 //   ATT_QKV_OUT  the qkv projection writes what the attention kernel stages instead of an fp32 [B][N][3C] tensor that a
@@ -31,18 +31,23 @@ namespace midd {
 
 constexpr int C1_MAX_SPLIT = 8;                  // == A16_MAX_SPLIT (attention_f16x3.hip)
 
+// Geometry of the (mt, nt) tile (4 waves, 256 threads), written down once as plain integers: Conv1Geom<> hands it to the kernel as
+// constants, conv1x1_launch_info (which launch1 calls for its grid and LDS bytes) evaluates it at run time.
+struct Conv1Tile {
+    int mt, nt;
+    int bm = 4 * mt * 16;                            // pixels per tile
+    int wstep = nt * 2048;                           // bytes of one K-step's weights (hi + lo, nt cout tiles)
+    int stat_floats = 4 * 2 * nt * 16, add_floats = nt * 16;
+    int coef_floats = C1_MAX_SPLIT * 2 * bm;         // ATT_PART_IN: [split][head][pixel of the tile]
+    constexpr int weight_bytes(int cin) const { const int w = ((cin + 31) / 32) * wstep; return w < 4096 ? 4096 : w; }      // also the statistics scratch at the end
+    constexpr int lds_bytes(int cin, int att_mode) const {
+        return weight_bytes(cin) + (stat_floats + add_floats) * 4 + 2 * cin * 4 + 64 + (att_mode == ATT_PART_IN ? coef_floats * 4 : 0);
+    }
+};
 template <int MT, int NT>
 struct Conv1Geom {
-    static constexpr int NW = 4, NTHREADS = 256;
-    static constexpr int BM = NW * MT * 16;                  // pixels per tile
-    static constexpr int WSTEP = NT * 2048;                  // bytes of one K-step's weights (hi + lo, NT cout tiles)
-    static constexpr int STAT_FLOATS = NW * 2 * NT * 16;
-    static constexpr int ADD_FLOATS = NT * 16;
-    static constexpr int COEF_FLOATS = C1_MAX_SPLIT * 2 * BM;     // ATT_PART_IN: [split][head][pixel of the tile]
-    static int weight_bytes(int cin) { const int w = ((cin + 31) / 32) * WSTEP; return w < 4096 ? 4096 : w; }      // also the statistics scratch at the end
-    static int lds_bytes(int cin, int att_mode) {
-        return weight_bytes(cin) + (STAT_FLOATS + ADD_FLOATS) * 4 + 2 * cin * 4 + 64 + (att_mode == ATT_PART_IN ? COEF_FLOATS * 4 : 0);
-    }
+    static constexpr Conv1Tile g{MT, NT};
+    static constexpr int NW = 4, NTHREADS = 256, BM = g.bm, WSTEP = g.wstep, STAT_FLOATS = g.stat_floats, ADD_FLOATS = g.add_floats;
 };
 
 // (ATT_PART_IN keeps up to four splits' partials of two K steps in registers, and its launches never fill a CU three times:
@@ -364,21 +369,17 @@ void conv1x1_f16x3_kernel(const ConvArgs a) {
 
 template <int MT, int NT, int ATT>
 static hipError_t launch1(const ConvArgs& a0, hipStream_t s) {
-    using G = Conv1Geom<MT, NT>;
     ConvArgs a = a0;
-    const int HW = a.OH * a.OW;
-    a.tiles_x = (HW + G::BM - 1) / G::BM;
-    a.tiles_y = 1;
-    const int ny = a.Cout / (NT * 16);
-    a.wgs_per_img = conv16_wgs_per_img(a.tiles_x, a.B, ny, a.persist_wgs);
-    const int lds_bytes = G::lds_bytes(a.C0 + a.C1, ATT);
-    if (lds_bytes > 160 * 1024) return hipErrorInvalidValue;
+    ConvLaunchInfo li{};
+    (void)conv1x1_launch_info(a.C0 + a.C1, a.Cout, a.B, a.OH, a.OW, ConvTile{1, 1, 0, MT, NT, 4, 1}, a.persist_wgs, ATT, &li);
+    a.tiles_x = li.tiles_x; a.tiles_y = 1; a.wgs_per_img = li.wgs_per_img;
+    if (li.lds_bytes > 160 * 1024) return hipErrorInvalidValue;
     {
         static int raised[MIDD_MAX_DEVICES] = {};          // per instantiation and device
-        hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(&conv1x1_f16x3_kernel<MT, NT, ATT>), lds_bytes, raised);
+        hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(&conv1x1_f16x3_kernel<MT, NT, ATT>), li.lds_bytes, raised);
         if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL((conv1x1_f16x3_kernel<MT, NT, ATT>), dim3(a.B * a.wgs_per_img, ny), dim3(G::NTHREADS), lds_bytes, s, a);
+    hipLaunchKernelGGL((conv1x1_f16x3_kernel<MT, NT, ATT>), dim3(li.grid_x, li.grid_y), dim3(Conv1Geom<MT, NT>::NTHREADS), li.lds_bytes, s, a);
     return hipGetLastError();
 }
 
@@ -394,14 +395,13 @@ bool conv1x1_pick_tile(int Cin, int Cout, int B, int OH, int OW, ConvTile* t) {
 }
 
 bool conv1x1_launch_info(int Cin, int Cout, int B, int OH, int OW, const ConvTile& t, int persist_wgs, int att_mode, ConvLaunchInfo* o) {
-    const int bm = 4 * t.mt * 16, HW = OH * OW;
-    o->tiles_x = (HW + bm - 1) / bm; o->tiles_y = 1;
+    const Conv1Tile g{t.mt, t.nt};
+    o->tiles_x = (OH * OW + g.bm - 1) / g.bm; o->tiles_y = 1;
     o->grid_y = Cout / (t.nt * 16);
     o->wgs_per_img = conv16_wgs_per_img(o->tiles_x, B, o->grid_y, persist_wgs);
     o->grid_x = B * o->wgs_per_img;
     o->ring = 0; o->ppw = 0; o->apw = 0;
-    const int w = ((Cin + 31) / 32) * t.nt * 2048;
-    o->lds_bytes = (w < 4096 ? 4096 : w) + (4 * 2 * t.nt * 16 + t.nt * 16) * 4 + 2 * Cin * 4 + 64 + (att_mode == ATT_PART_IN ? C1_MAX_SPLIT * 2 * bm * 4 : 0);
+    o->lds_bytes = g.lds_bytes(Cin, att_mode);
     return true;
 }
 

@@ -38,57 +38,65 @@
 
 namespace midd {
 
-template <int KS, int STRIDE, int TW, int MT, int NT, int WM, int WN, int CBT = 0>
-struct Conv16Geom {
-    static constexpr int NW = WM * WN;
-    static constexpr int NTHREADS = NW * 64;
-    static constexpr int BM = WM * MT * 16;
-    static constexpr int TH = BM / TW;
-    static constexpr int IH = (TH - 1) * STRIDE + KS;
-    static constexpr int IW = (TW - 1) * STRIDE + KS;
-    static constexpr int NPIX = IH * IW;
-    static constexpr int CB = CBT ? CBT : conv16_cb(KS);            // 16-channel blocks per chunk (CBT = 2: the "wide" 3x3 variant)
-    static constexpr bool WIDE = (KS == 3 && CB == 2);
-    static constexpr int QPP = 4 * CB;                              // 16-byte slots per halo pixel and chunk
-    static constexpr int NSLOT = NPIX * QPP;
-    static constexpr int APW = (NSLOT + NTHREADS - 1) / NTHREADS;   // activation DMA pieces per wave and chunk
-    static constexpr int RAW_BYTES = APW * NTHREADS * 16;
-    static constexpr int PLANE = NPIX * 32;
-    static constexpr int IMG_BYTES = 2 * CB * PLANE;
-    static constexpr int WPIECES = WN * NT * 2;                     // 1 KiB weight pieces per step
-    static constexpr int PPW = (WPIECES + NW - 1) / NW;             // pieces per wave and step (duplicates pad)
-    static constexpr int WSLICE = WPIECES * 1024;
-    // epilogue state kept in LDS instead of registers (the K loop is register-bound): GroupNorm partial
-    // sums of the output, one row [2][NT*16] per wave, and the bias (+ time embedding) vector of the workgroup
-    static constexpr int STAT_FLOATS = NW * 2 * NT * 16;
-    static constexpr int ADD_FLOATS = WN * NT * 16;
-    static constexpr int EPI_BYTES = (STAT_FLOATS + ADD_FLOATS) * 4;
-    // GroupNorm scale/shift of the input, [2][Cin] floats, sized at launch (dynamic LDS); the ring is
-    // dimensioned for up to NOMINAL_CIN input channels (more still runs, possibly one workgroup per CU fewer)
-    static constexpr int NOMINAL_CIN = 384;
-    static constexpr int FIXED_BYTES = RAW_BYTES + IMG_BYTES + EPI_BYTES + 2 * NOMINAL_CIN * 4 + 64;
-    // weight steps resident in LDS (prefetch distance RING-1): L2->LDS latency is ~1-2k cycles under
-    // load, a step is only 150-600 MFMA cycles, so take as many slots as fit in half the LDS (two
-    // workgroups per CU), between 2 and 6.
 #ifndef MIDD_LDS_TARGET_KB
 #define MIDD_LDS_TARGET_KB 52
 #endif
 #ifndef MIDD_RING_MAX
 #define MIDD_RING_MAX 6
 #endif
+#ifndef MIDD_LDS_WIDE_KB
+#define MIDD_LDS_WIDE_KB 78
+#endif
+// Geometry of one tile of this kernel, written down once as plain integers: Conv16Tile{ks, stride, tw, mt, nt, wm, wn, cbt} derives
+// everything else.  Conv16Geom<> hands it to the kernel as constants; the tile picker and conv16_launch_info evaluate it at run time.
+struct Conv16Tile {
+    int ks, stride, tw, mt, nt, wm, wn;
+    int cbt = 0;                                             // 16-channel blocks per chunk: 0 = conv16_cb(ks), 2 = the "wide" 3x3 variant
+    int nw = wm * wn;
+    int nthreads = nw * 64;
+    int th = wm * mt * 16 / tw;
+    int ih = (th - 1) * stride + ks;
+    int iw = (tw - 1) * stride + ks;
+    int npix = ih * iw;
+    int cb = cbt ? cbt : conv16_cb(ks);
+    int qpp = 4 * cb;                                        // 16-byte slots per halo pixel and chunk
+    int nslot = npix * qpp;
+    int apw = (nslot + nthreads - 1) / nthreads;             // activation DMA pieces per wave and chunk
+    int raw_bytes = apw * nthreads * 16;
+    int plane = npix * 32;
+    int img_bytes = 2 * cb * plane;
+    int wpieces = wn * nt * 2;                               // 1 KiB weight pieces per step
+    int ppw = (wpieces + nw - 1) / nw;                       // pieces per wave and step (duplicates pad)
+    int wslice = wpieces * 1024;
+    // epilogue state kept in LDS instead of registers (the K loop is register-bound): GroupNorm partial
+    // sums of the output, one row [2][NT*16] per wave, and the bias (+ time embedding) vector of the workgroup
+    int stat_floats = nw * 2 * nt * 16;
+    int add_floats = wn * nt * 16;
+    // GroupNorm scale/shift of the input, [2][Cin] floats, sized at launch (dynamic LDS); the ring is
+    // dimensioned for up to NOMINAL_CIN input channels (more still runs, possibly one workgroup per CU fewer)
+    static constexpr int NOMINAL_CIN = 384;
+    int fixed_bytes = raw_bytes + img_bytes + (stat_floats + add_floats) * 4 + 2 * NOMINAL_CIN * 4 + 64;
+    // weight steps resident in LDS (prefetch distance RING-1): L2->LDS latency is ~1-2k cycles under
+    // load, a step is only 150-600 MFMA cycles, so take as many slots as fit in the LDS target, between 2 and MIDD_RING_MAX.
     // 52 KB: three workgroups per CU
     // (stride-2 tiles stage a 33x17 halo and run one workgroup per CU whatever the ring: they take a deep ring -- with two
     // slots the counted wait for a step's weights was 18-33 % of a wave's time, in-kernel stamps of round 3)
     // wide 3x3 chunks (launches that leave at most ~2 workgroups per CU anyway): two workgroups per CU
-#ifndef MIDD_LDS_WIDE_KB
-#define MIDD_LDS_WIDE_KB 78
-#endif
-    static constexpr int LDS_TARGET = (STRIDE == 2 ? 120 : WIDE ? MIDD_LDS_WIDE_KB : MIDD_LDS_TARGET_KB) * 1024;
-    static constexpr int ring_fit = (LDS_TARGET - FIXED_BYTES) / WSLICE;
-    static constexpr int RING = ring_fit < 2 ? 2 : (ring_fit > MIDD_RING_MAX ? MIDD_RING_MAX : ring_fit);
-    static constexpr int LDS_BYTES = FIXED_BYTES + RING * WSLICE;                 // at NOMINAL_CIN
-    static constexpr int lds_bytes(int cin) { return LDS_BYTES + 2 * (cin - NOMINAL_CIN) * 4; }   // incl. the 16 mean/rstd floats
-    static_assert(BM % TW == 0, "tile");
+    int lds_target = (stride == 2 ? 120 : (ks == 3 && cb == 2) ? MIDD_LDS_WIDE_KB : MIDD_LDS_TARGET_KB) * 1024;
+    int ring_fit = (lds_target - fixed_bytes) / wslice;
+    int ring = ring_fit < 2 ? 2 : (ring_fit > MIDD_RING_MAX ? MIDD_RING_MAX : ring_fit);
+    int lds_nominal = fixed_bytes + ring * wslice;           // at NOMINAL_CIN
+    bool fits = lds_nominal <= 160 * 1024 && (ring - 2) * ppw + apw <= 60;      // LDS of a CU; the vmcnt encoding.  Else never picked, never instantiated
+    constexpr int lds_bytes(int cin) const { return lds_nominal + 2 * (cin - NOMINAL_CIN) * 4; }   // incl. the 16 mean/rstd floats
+};
+
+template <int KS, int STRIDE, int TW, int MT, int NT, int WM, int WN, int CBT = 0>
+struct Conv16Geom {
+    static constexpr Conv16Tile g{KS, STRIDE, TW, MT, NT, WM, WN, CBT};
+    static constexpr int NW = g.nw, NTHREADS = g.nthreads, TH = g.th, IH = g.ih, IW = g.iw, CB = g.cb, QPP = g.qpp, NSLOT = g.nslot, APW = g.apw;
+    static constexpr int RAW_BYTES = g.raw_bytes, PLANE = g.plane, IMG_BYTES = g.img_bytes, WPIECES = g.wpieces, PPW = g.ppw, WSLICE = g.wslice;
+    static constexpr int STAT_FLOATS = g.stat_floats, ADD_FLOATS = g.add_floats, RING = g.ring;
+    static_assert((WM * MT * 16) % TW == 0, "tile");
 };
 
 // Diagnostic build only (-DMIDD_CONV_TIMING, tools/conv_timing.py): s_memtime stamps of wave 0 of every
@@ -873,8 +881,8 @@ static hipError_t launch16(const ConvArgs& a0, hipStream_t s) {
 #ifdef MIDD_CONV_TIMING
     a.dbg_slot = conv_timing_slot(KS, STRIDE, TW, MT * 10 + G::CB, NT, WM, WN, a.OH, a.C0 + a.C1, a.Cout, a.B, G::RING, (int)grid.x * (int)grid.y);
 #endif
-    if constexpr (G::LDS_BYTES <= 160 * 1024 && (G::RING - 2) * G::PPW + G::APW <= 60) {
-        const int lds_bytes = G::lds_bytes(a.C0 + a.C1);
+    if constexpr (G::g.fits) {
+        const int lds_bytes = G::g.lds_bytes(a.C0 + a.C1);
         if (lds_bytes > 160 * 1024) return hipErrorInvalidValue;
         {
             static int raised[MIDD_MAX_DEVICES] = {};      // per instantiation and device
@@ -919,22 +927,16 @@ static const Tile16 kTiles16[] = {
 #undef X
 };
 
-// run-time mirror of Conv16Geom::LDS_BYTES / the vmcnt-encoding limit, for the tile picker
-static bool tile16_fits(const Tile16& d, int ks, int stride, int cb = 0) {
-    const int nw = d.wm * d.wn, nthreads = nw * 64;
-    const int bm = d.wm * d.mt * 16, th = bm / d.tw;
-    const int ih = (th - 1) * stride + ks, iw = (d.tw - 1) * stride + ks;
-    if (cb == 0) cb = conv16_cb(ks);
-    const bool wide = ks == 3 && cb == 2;
-    const int npix = ih * iw, apw = (npix * 4 * cb + nthreads - 1) / nthreads;
-    const int wpieces = d.wn * d.nt * 2, ppw = (wpieces + nw - 1) / nw;
-    const long fixed = (long)apw * nthreads * 16 + 2L * cb * npix * 32 + (nw * 2 * d.nt * 16 + d.wn * d.nt * 16) * 4 + 2 * 384 * 4 + 64;
-    long ring = ((long)(stride == 2 ? 120 : wide ? MIDD_LDS_WIDE_KB : MIDD_LDS_TARGET_KB) * 1024 - fixed) / (wpieces * 1024);
-    ring = ring < 2 ? 2 : (ring > MIDD_RING_MAX ? MIDD_RING_MAX : ring);
-    const long lds = fixed + ring * wpieces * 1024;
-    return lds <= 160 * 1024 && (ring - 2) * ppw + apw <= 60;
-}
+// the kernel's constants are the run-time geometry, for every listed tile at the three kernel shapes
+#define X(tw, mt, nt, wm, wn)                                                                                     \
+    static_assert(Conv16Geom<3, 1, tw, mt, nt, wm, wn>::RING == Conv16Tile{3, 1, tw, mt, nt, wm, wn}.ring &&         \
+                  Conv16Geom<3, 2, tw, mt, nt, wm, wn>::APW == Conv16Tile{3, 2, tw, mt, nt, wm, wn}.apw &&           \
+                  Conv16Geom<1, 1, tw, mt, nt, wm, wn>::WSLICE == Conv16Tile{1, 1, tw, mt, nt, wm, wn}.wslice, "Conv16Geom");
+MIDD_CONV16_TILES(X)
+#undef X
 
+// the 4x1-wave 3x3 tiles (mt = 1, 2) have a wide-chunk variant
+static bool wide16_tile(const ConvTile& t) { return t.ks == 3 && t.stride == 1 && t.tw == 16 && t.nt == 3 && t.wm == 4 && t.wn == 1; }
 // Launches whose grid is at most this many workgroups take the wide-chunk variant of the 4x1-wave tiles (they would
 // leave the third workgroup slot of a CU empty anyway).
 #ifndef MIDD_WIDE_MAX_WGS
@@ -954,7 +956,7 @@ bool conv16_pick_tile(int Cin, int Cout, int B, int OH, int OW, int ks, int stri
         if (d.nt != nt) continue;
         const int nn_d = Cout / (16 * d.nt);              // cout slices of 16*nt; a workgroup takes wn of them
         if (nn_d % d.wn) continue;
-        if (!tile16_fits(d, ks, stride)) continue;
+        if (!Conv16Tile{ks, stride, d.tw, d.mt, d.nt, d.wm, d.wn}.fits) continue;
         const int bm = d.wm * d.mt * 16, th = bm / d.tw;
         const long tiles = (long)((OW + d.tw - 1) / d.tw) * ((OH + th - 1) / th);
         const long wgs = (long)B * tiles * (nn_d / d.wn);
@@ -970,44 +972,32 @@ bool conv16_pick_tile(int Cin, int Cout, int B, int OH, int OW, int ks, int stri
     }
     if (!best) return false;
     *t = ConvTile{ks, stride, best->tw, best->mt, best->nt, best->wm, best->wn};
-    if (allow_wide && ks == 3 && stride == 1 && best->tw == 16 && best->nt == 3 && best->wm == 4 && best->wn == 1 && Cin >= 32 &&
-        best_wgs <= MIDD_WIDE_MAX_WGS && tile16_fits(*best, ks, stride, 2))
+    if (allow_wide && wide16_tile(*t) && Cin >= 32 &&
+        best_wgs <= MIDD_WIDE_MAX_WGS && Conv16Tile{ks, stride, best->tw, best->mt, best->nt, best->wm, best->wn, 2}.fits)
         t->cb = 2;
     return true;
 }
 
-template <int KS, int STRIDE, int TW, int MT, int NT, int WM, int WN, int CBT = 0>
-static bool info16(int Cin, int Cout, int B, int OH, int OW, int persist_wgs, ConvLaunchInfo* o) {
-    using G = Conv16Geom<KS, STRIDE, TW, MT, NT, WM, WN, CBT>;
-    o->tiles_x = (OW + TW - 1) / TW; o->tiles_y = (OH + G::TH - 1) / G::TH;
-    o->grid_y = Cout / (WN * NT * 16);
+bool conv16_launch_info(int Cin, int Cout, int B, int OH, int OW, const ConvTile& t, int persist_wgs, ConvLaunchInfo* o) {
+    if (t.ks == 1 && t.tw == 0) return conv1x1_launch_info(Cin, Cout, B, OH, OW, t, persist_wgs, ATT_NONE, o);
+    // only what conv16_launch instantiates: a listed tile at 3x3 s1 / 3x3 s2 / 1x1, or one of the two wide tiles
+    bool listed = false;
+    if (t.cb == 2 ? wide16_tile(t) : ((t.ks == 3 && (t.stride == 1 || t.stride == 2)) || (t.ks == 1 && t.stride == 1)))
+        for (const Tile16& d : kTiles16) listed = listed || (d.tw == t.tw && d.mt == t.mt && d.nt == t.nt && d.wm == t.wm && d.wn == t.wn);
+    if (!listed) return false;
+    const Conv16Tile g{t.ks, t.stride, t.tw, t.mt, t.nt, t.wm, t.wn, t.cb == 2 ? 2 : 0};
+    o->tiles_x = (OW + t.tw - 1) / t.tw; o->tiles_y = (OH + g.th - 1) / g.th;
+    o->grid_y = Cout / (t.wn * t.nt * 16);
     o->wgs_per_img = conv16_wgs_per_img(o->tiles_x * o->tiles_y, B, o->grid_y, persist_wgs);
     o->grid_x = B * o->wgs_per_img;
-    o->ring = G::RING; o->ppw = G::PPW; o->apw = G::APW; o->lds_bytes = G::lds_bytes(Cin);
+    o->ring = g.ring; o->ppw = g.ppw; o->apw = g.apw; o->lds_bytes = g.lds_bytes(Cin);
     return true;
-}
-bool conv16_launch_info(int Cin, int Cout, int B, int OH, int OW, const ConvTile& t, int persist_wgs, ConvLaunchInfo* out) {
-    if (t.ks == 1 && t.tw == 0) return conv1x1_launch_info(Cin, Cout, B, OH, OW, t, persist_wgs, ATT_NONE, out);
-    if (t.cb == 2) {
-        if (t.mt == 2) return info16<3, 1, 16, 2, 3, 4, 1, 2>(Cin, Cout, B, OH, OW, persist_wgs, out);
-        if (t.mt == 1) return info16<3, 1, 16, 1, 3, 4, 1, 2>(Cin, Cout, B, OH, OW, persist_wgs, out);
-        return false;
-    }
-#define X(tw_, mt_, nt_, wm_, wn_)                                                            \
-    if (t.tw == tw_ && t.mt == mt_ && t.nt == nt_ && t.wm == wm_ && t.wn == wn_) {           \
-        if (t.ks == 3 && t.stride == 1) return info16<3, 1, tw_, mt_, nt_, wm_, wn_>(Cin, Cout, B, OH, OW, persist_wgs, out); \
-        if (t.ks == 3 && t.stride == 2) return info16<3, 2, tw_, mt_, nt_, wm_, wn_>(Cin, Cout, B, OH, OW, persist_wgs, out); \
-        if (t.ks == 1 && t.stride == 1) return info16<1, 1, tw_, mt_, nt_, wm_, wn_>(Cin, Cout, B, OH, OW, persist_wgs, out); \
-    }
-    MIDD_CONV16_TILES(X)
-#undef X
-    return false;
 }
 
 hipError_t conv16_launch(const ConvArgs& a, const ConvTile& t, hipStream_t s) {
     if (t.ks == 1 && t.tw == 0) return conv1x1_launch(a, t, s);
     if (t.cb == 2) {          // wide chunks: the two 4x1-wave tiles the picker marks (conv16_pick_tile)
-        if (!(t.ks == 3 && t.stride == 1 && t.tw == 16 && t.nt == 3 && t.wm == 4 && t.wn == 1)) return hipErrorInvalidValue;
+        if (!wide16_tile(t)) return hipErrorInvalidValue;
         if (t.mt == 2) return a.res_steps > 0 ? launch16<3, 1, 16, 2, 3, 4, 1, true, 2>(a, s) : launch16<3, 1, 16, 2, 3, 4, 1, false, 2>(a, s);
         if (t.mt == 1) return a.res_steps > 0 ? launch16<3, 1, 16, 1, 3, 4, 1, true, 2>(a, s) : launch16<3, 1, 16, 1, 3, 4, 1, false, 2>(a, s);
         return hipErrorInvalidValue;

@@ -15,7 +15,7 @@
 //   K is walked in chunks of 16 input channels; within a chunk the four k-steps of the
 //   16x16x4 MFMA take channel 4*kq+j in step j (kq = lane>>4), so one ds_read_b128 /
 //   global dwordx4 feeds four MFMAs.  The weight tensor is pre-packed on the host in
-//   exactly that fragment order (midd_api.hip: pack_conv_weights).
+//   exactly that fragment order (midd_weights.hip: pack_conv_f32).
 //
 // Workgroup = WM x WN waves.  A TH x TW output tile (BM = WM*MT*16 pixels) with its halo is
 // staged once per 16-channel chunk into LDS ([halo pixel][16 ch] = 64 B per pixel, so a

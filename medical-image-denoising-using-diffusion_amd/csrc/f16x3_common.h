@@ -8,9 +8,9 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 typedef _Float16 half4 __attribute__((ext_vector_type(4)));
 
-constexpr float ACT_PRESCALE = 16.0f;             // 2^s, s = 4, of GroupNorm-ed operands (see header); must match midd_api.hip
+constexpr float ACT_PRESCALE = 16.0f;             // 2^s, s = 4, of GroupNorm-ed operands (see header); must match ACT_PRESCALE_H (midd_host.h)
 // GroupNorm + SiLU operands of the 3x3 kernel: the transform forms t = -log2(e) y and u = 16 t / (1 + 2^t) = -16 log2(e) silu(y);
-// the packed weights of those convolutions carry the factor -ln 2 that makes w'' . u = 16 w . silu(y) (midd_api.hip).
+// the packed weights of those convolutions carry the factor -ln 2 that makes w'' . u = 16 w . silu(y) (midd_weights.hip: SILU_WEIGHT_FACTOR_H).
 constexpr float SILU_ARG_FACTOR = -1.4426950408889634f;
 constexpr float SILU_WEIGHT_FACTOR = -0.6931471805599453f;
 constexpr float RAW_PRESCALE = 1.0f;              // raw operands without statistics of their own (none on the default networks)

@@ -107,7 +107,6 @@ struct ConvTile {           // which template instance to launch
     int cb = 0;             // f16x3 3x3: 16-channel blocks per K chunk (0: conv16_cb(ks)); selects the weight packing too
 };
 
-enum ComputeMode { MODE_F32 = 0, MODE_F16X3 = 1 };
 enum AttMode { ATT_NONE = 0, ATT_QKV_OUT = 1, ATT_PART_IN = 2 };
 enum StatusBits { STATUS_NONFINITE = 1, STATUS_FP16_RANGE = 2,          // == MI_STATUS_* (include/midd.h)
                   STATUS_DMA_EARLY = 4 };      // diagnostic builds only (-DMIDD_DMA_CHECK, tools/dma_check.sh): data used before its counted wait had covered it

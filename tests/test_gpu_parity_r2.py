@@ -370,3 +370,19 @@ def test_launched_kernels():
     # 100 in round 2 (88 ops, an attention op being prep + attention + combine); round 3: every op is ONE launch, the 15
     # res_conv launches are K steps of their block's conv2 and an attention block is qkv -> attention -> proj: 73
     assert sum(p["launches"] for p in prof) == 73
+
+
+def test_finalized_plan_dumps_as_the_unfinalized_plan():
+    """The planner decides from the plan alone (which convs have a wide-chunk weight copy included): `mi_debug_plan_dump` of a
+    finalized plan -- the programs that run -- equals the dump of a plan of the same configuration that never saw a weight, which
+    is what tests/test_plan_dump_cpu.py inspects without a GPU."""
+    import os
+    import sys
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
+    import plan_dump as pd
+    model = _model({}, make_state_dict(UNetConfig(), seed=42))
+    finalized, fresh = model._ensure_plan(), pd.make_plan({}, "f16x3")
+    for B in (1, 8):
+        for side in (0, 1):
+            text = pd.dump(finalized, B, 256, 256, side)
+            assert "ops=73" in text and text == pd.dump(fresh, B, 256, 256, side), (B, side)

@@ -7,8 +7,8 @@ ROOT=$(cd "$(dirname "$0")/.." && pwd); CSRC=$ROOT/medical-image-denoising-using
 mkdir -p $CSRC/build_$NAME
 hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -Wall -Wno-unused-function $FLAGS -c $CSRC/$SRC -o $CSRC/build_$NAME/${SRC%.hip}.o
 OBJS=""
-for f in midd_api conv_mfma_f32 conv_mfma_f16x3 conv1x1_f16x3 groupnorm attention_f32 attention_f16x3 pointwise prepost; do
-  if [ "$f.hip" == "$SRC" ]; then OBJS="$OBJS $CSRC/build_$NAME/$f.o"; else OBJS="$OBJS $CSRC/build/$f.o"; fi
+for o in $(make -s -C $CSRC print-OBJS); do      # the Makefile's object list (build/NAME.o), with the one variant object swapped in
+  if [ "$(basename $o .o).hip" == "$SRC" ]; then OBJS="$OBJS $CSRC/build_$NAME/$(basename $o)"; else OBJS="$OBJS $CSRC/$o"; fi
 done
 hipcc --offload-arch=gfx950 -shared -fPIC -o $ROOT/libmidd_$NAME.so $OBJS
 echo "built $ROOT/libmidd_$NAME.so"
