@@ -41,7 +41,7 @@ extern "C" {
 
 /* bits of the status word (mi_status) */
 #define MI_STATUS_NONFINITE   1   /* NaN / Inf activations reached a GroupNorm statistic or a raw conv operand */
-#define MI_STATUS_FP16_RANGE  2   /* split-fp16 mode: an attention operand (q, k, v) beyond +-4094 */
+#define MI_STATUS_FP16_RANGE  2   /* fp16-MFMA modes (f16x3, f16): an attention operand (q, k, v) beyond +-4094 */
 
 #define MI_MAX_LEVELS    8
 
@@ -52,6 +52,10 @@ extern "C" {
 #define MI_COMPUTE_F32   0   /* fp32-input MFMA: bit-for-bit an fp32 fma chain */
 #define MI_COMPUTE_F16X3 1   /* fp32 operands split into two fp16 halves, three fp16 MFMAs, fp32 accumulate
                                 (~2^-21 relative per product; same parity gate) — about 5x the MFMA rate */
+#define MI_COMPUTE_F16   2   /* every MFMA multiplicand rounded ONCE to fp16 (the hi half of the split above, same
+                                prescales), one fp16 MFMA per product, fp32 accumulate; activations, statistics, softmax
+                                sums and epilogues stay fp32.  NOT a parity mode: ~2^-11 relative per operand, judged
+                                against the reference under autocast; same operand-range rule */
 /* OR into compute_mode: results of a sample do not depend on the batch it is computed in, bit for bit
  * (denoise(x[:k]) == denoise(x)[:k]; SURVEY.md section 8e "sharded == single-GPU").  Tiles, persistent workgroups per
  * sample, chunk width and the attention key split are then chosen as the default plan of a 4-sample sub-batch chooses
@@ -160,6 +164,10 @@ int mi_debug_plan_dump(mi_plan* plan, int B, int H, int W, int side_by_side, cha
  * these numbers for every instantiated tile and checks every hand-counted `s_waitcnt vmcnt(N)`.  MI_EINVAL: not instantiated. */
 int mi_debug_conv16_geometry(int ks, int stride, int tw, int mt, int nt, int wm, int wn, int cb,
                              int* ring, int* ppw, int* apw, int* lds_bytes);
+/* The same for `planes` fp16 planes per operand: 2 = the split-fp16 kernel (identical to the call above), 1 = the one-product
+ * kernel of MI_COMPUTE_F16 (halved image and weight slices: other ring depths and pieces per wave). */
+int mi_debug_conv16_geometry_planes(int ks, int stride, int tw, int mt, int nt, int wm, int wn, int cb, int planes,
+                                    int* ring, int* ppw, int* apw, int* lds_bytes);
 
 /* First 16 hex digits of the sha256 over the kernel sources (csrc/ *.h, *.hip) this library was BUILT from, embedded at
  * build time: what bench.py / tools/pmc_traffic.py compare profiles against (not the working tree). */

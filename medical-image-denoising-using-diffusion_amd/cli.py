@@ -28,10 +28,11 @@ from .sampler import DiffusionDenoiser
 
 def denoise_image_diffusion(model_path: Optional[str], test_image_path: str, device_type: str = "cuda",
                             img_size: int = 512, inference_steps: int = 50, variant: str = "cddpm",
-                            step_noise: Optional[torch.Tensor] = None) -> Image.Image:
+                            step_noise: Optional[torch.Tensor] = None, compute: Optional[str] = None) -> Image.Image:
+    """compute (not a reference argument): arithmetic of the network, see UNetDiffusion -- None keeps the default."""
     device = torch.device(device_type)
     model = UNetDiffusion(in_channels=1, model_channels=48, channel_mult=(1, 2, 3, 4), num_res_blocks=2,
-                          attention_resolutions=(3,), dropout=0.0, time_emb_dim=192, variant=variant)
+                          attention_resolutions=(3,), dropout=0.0, time_emb_dim=192, variant=variant, compute=compute)
     checkpoint = {}
     if model_path:
         checkpoint = torch.load(model_path, map_location="cpu", weights_only=True)

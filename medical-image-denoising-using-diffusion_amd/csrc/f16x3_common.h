@@ -1,4 +1,5 @@
-// Device helpers shared by the f16x3 convolution kernels (conv_mfma_f16x3.hip, conv1x1_f16x3.hip).
+// Device helpers shared by the fp16-MFMA convolution kernels (conv_mfma_f16x3.hip, conv1x1_f16x3.hip), both arithmetic modes:
+// split-fp16 ("f16x3", two planes per operand) and one-product fp16 ("f16", one plane).
 #pragma once
 #include "midd_internal.h"
 
@@ -52,6 +53,20 @@ __device__ __forceinline__ void split_pair(float x0, float x1, unsigned& hi, uns
     hi = __builtin_bit_cast(unsigned, h);
     asm("v_fma_mixlo_f16 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(lo) : "v"(hi), "v"(x0));
     asm("v_fma_mixhi_f16 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "+v"(lo) : "v"(hi), "v"(x1));
+}
+
+// The operand planes of a pair of fp32 values for PL planes: PL = 2 the split above; PL = 1 (compute "f16") the fp16 rounding
+// alone (round to nearest even, v_cvt_pk_f16_f32) -- the same `hi` the split produces, no lo half (lo reads as 0, unused).
+template <int PL>
+__device__ __forceinline__ void planes_pair(float x0, float x1, unsigned& hi, unsigned& lo) {
+    if constexpr (PL == 2) split_pair(x0, x1, hi, lo);
+    else {
+        typedef _Float16 h2 __attribute__((ext_vector_type(2)));
+        h2 h;
+        h[0] = (_Float16)x0; h[1] = (_Float16)x1;
+        hi = __builtin_bit_cast(unsigned, h);
+        lo = 0u;
+    }
 }
 
 // Wait until at most N of this wave's vector-memory operations (all of them LDS-DMA inside the

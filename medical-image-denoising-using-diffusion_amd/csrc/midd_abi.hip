@@ -59,7 +59,7 @@ extern "C" int mi_image_metrics(const void* target, const void* pred, int n, int
 
 // ------------------------------------------------------------------------------ C ABI: create / load
 extern "C" const char* mi_last_error(void) { return g_err; }
-extern "C" const char* mi_version(void) { return "midd 0.4 gfx950 (fp32 MFMA | split-fp16 x3 MFMA; GroupNorm statistics in the producers; device pre/post-processing)"; }
+extern "C" const char* mi_version(void) { return "midd 0.4 gfx950 (fp32 MFMA | split-fp16 x3 MFMA | fp16 MFMA; GroupNorm statistics in the producers; device pre/post-processing)"; }
 
 #ifndef MIDD_SOURCE_HASH
 #define MIDD_SOURCE_HASH "unknown"
@@ -82,7 +82,7 @@ extern "C" int mi_unet_plan_create(const mi_unet_cfg* cfg, mi_plan** out) {
     if (cfg->time_emb_dim < 1) return fail(MI_EINVAL, "time_emb_dim must be >= 1");
     if (cfg->variant != MI_VARIANT_DDIM && cfg->variant != MI_VARIANT_CDDPM) return fail(MI_EINVAL, "unknown variant %d", cfg->variant);
     const int arith = cfg->compute_mode & ~MI_COMPUTE_BATCH_INVARIANT;
-    if (arith != MI_COMPUTE_F32 && arith != MI_COMPUTE_F16X3) return fail(MI_EINVAL, "unknown compute_mode %d", cfg->compute_mode);
+    if (arith != MI_COMPUTE_F32 && arith != MI_COMPUTE_F16X3 && arith != MI_COMPUTE_F16) return fail(MI_EINVAL, "unknown compute_mode %d", cfg->compute_mode);
     for (int i = 0; i < cfg->num_levels; ++i)
         if (cfg->channel_mult[i] < 1) return fail(MI_EINVAL, "channel_mult[%d] must be >= 1", i);
     for (int i = 0; i < cfg->num_attention_levels; ++i) {
@@ -148,6 +148,16 @@ extern "C" int mi_status(const void* workspace, void* stream, int* flags) {
 extern "C" int mi_debug_conv16_geometry(int ks, int stride, int tw, int mt, int nt, int wm, int wn, int cb, int* ring, int* ppw, int* apw, int* lds_bytes) {
     if (!ring || !ppw || !apw || !lds_bytes) return fail(MI_EINVAL, "null argument");
     ConvTile t{ks, stride, tw, mt, nt, wm, wn, cb};
+    ConvLaunchInfo li{};
+    if (!conv16_launch_info(384, 16 * nt * wn, 1, 64, 64, t, 0, &li)) return fail(MI_EINVAL, "tile (%d,%d,%d,%d,%d) ks %d stride %d cb %d is not instantiated", tw, mt, nt, wm, wn, ks, stride, cb);
+    *ring = li.ring; *ppw = li.ppw; *apw = li.apw; *lds_bytes = li.lds_bytes;
+    return MI_OK;
+}
+extern "C" int mi_debug_conv16_geometry_planes(int ks, int stride, int tw, int mt, int nt, int wm, int wn, int cb, int planes,
+                                               int* ring, int* ppw, int* apw, int* lds_bytes) {
+    if (!ring || !ppw || !apw || !lds_bytes) return fail(MI_EINVAL, "null argument");
+    if (planes != 1 && planes != 2) return fail(MI_EINVAL, "planes must be 1 (f16) or 2 (f16x3), got %d", planes);
+    ConvTile t{ks, stride, tw, mt, nt, wm, wn, cb, planes};
     ConvLaunchInfo li{};
     if (!conv16_launch_info(384, 16 * nt * wn, 1, 64, 64, t, 0, &li)) return fail(MI_EINVAL, "tile (%d,%d,%d,%d,%d) ks %d stride %d cb %d is not instantiated", tw, mt, nt, wm, wn, ks, stride, cb);
     *ring = li.ring; *ppw = li.ppw; *apw = li.apw; *lds_bytes = li.lds_bytes;

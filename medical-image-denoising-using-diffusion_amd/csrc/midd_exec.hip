@@ -18,7 +18,8 @@ static int run_program(mi_plan* p, Program* g, const StepIO& io, char* ws, int* 
     // every tensor's GroupNorm totals start the forward at zero (producers accumulate with atomics)
     if (hipMemsetAsync(ws + g->stats_off, 0, g->stats_bytes, s) != hipSuccess) return fail(MI_EHIP, "clearing the statistics arena failed");
     // split-fp16 plans keep their activations channel-blocked, [B][C/16][H][W][16] (midd_internal.h); fp32-MFMA plans NHWC
-    const int blocked = p->cfg.compute_mode == MI_COMPUTE_F16X3 ? 1 : 0;
+    const int blocked = fp16_mfma(p->cfg) ? 1 : 0;
+    const int planes = operand_planes(p->cfg);
     for (const Op& o : g->ops) {
         hipError_t e = hipSuccess;
         hipEvent_t ev_a = nullptr, ev_b = nullptr;
@@ -59,7 +60,7 @@ static int run_program(mi_plan* p, Program* g, const StepIO& io, char* ws, int* 
                     }
                 }
                 if (o.att_mode != ATT_NONE) {
-                    const Att16Layout lay = attention16_layout(B, o.dst.H * o.dst.W, o.att_mode == ATT_QKV_OUT ? o.dst.C / 3 : o.dst.C);
+                    const Att16Layout lay = attention16_layout(B, o.dst.H * o.dst.W, o.att_mode == ATT_QKV_OUT ? o.dst.C / 3 : o.dst.C, planes);
                     a.att_mode = o.att_mode; a.att_heads = ATTN_HEADS_ABI; a.att_D = (o.att_mode == ATT_QKV_OUT ? o.dst.C / 3 : o.dst.C) / ATTN_HEADS_ABI;
                     a.att_npad = lay.npad; a.att_ksplit = o.att_ksplit;
                     a.att_k = reinterpret_cast<_Float16*>(ws + o.partial_off + lay.k_off); a.att_v = reinterpret_cast<_Float16*>(ws + o.partial_off + lay.v_off);
@@ -78,17 +79,17 @@ static int run_program(mi_plan* p, Program* g, const StepIO& io, char* ws, int* 
                 a.out = F(o.dst.off); a.out_scale = o.out_scale;
                 if (o.want_stats) { a.stat_tot = T(o.dst.tot_off); a.stat_bs = o.dst.stat_bs; }
                 a.persist_wgs = g->persist_wgs;
-                e = (p->cfg.compute_mode == MI_COMPUTE_F16X3) ? conv16_launch(a, o.tile, s) : conv_launch(a, o.tile, s);
+                e = fp16_mfma(p->cfg) ? conv16_launch(a, o.tile, s) : conv_launch(a, o.tile, s);      // (the tile carries the planes)
                 break;
             }
             case OP_ATTN:
-                if (p->cfg.compute_mode == MI_COMPUTE_F16X3) {
+                if (fp16_mfma(p->cfg)) {
                     const int N = o.dst.H * o.dst.W, C = o.dst.C;
-                    const Att16Layout lay = attention16_layout(B, N, C);
+                    const Att16Layout lay = attention16_layout(B, N, C, planes);
                     char* sc = ws + o.partial_off;
                     e = attention16_launch(F(o.s0.off), reinterpret_cast<const _Float16*>(sc + lay.k_off), reinterpret_cast<const _Float16*>(sc + lay.v_off),
                                            reinterpret_cast<float*>(sc + lay.po_off), reinterpret_cast<float*>(sc + lay.ml_off),
-                                           B, o.att_ksplit, o.att_tps, N, C, ATTN_HEADS_ABI, s);
+                                           B, o.att_ksplit, o.att_tps, N, C, ATTN_HEADS_ABI, s, planes);
                 } else {
                     e = attention_launch(F(o.s0.off), F(o.dst.off), B, o.dst.H * o.dst.W, o.dst.C, 2, s);
                 }
@@ -257,7 +258,7 @@ extern "C" int mi_debug_fetch(mi_plan* plan, const char* module_name, int B, int
     if (dst) {
         if (!workspace) return fail(MI_EINVAL, "null workspace");
         hipError_t e = nhwc_to_nchw_launch(reinterpret_cast<const float*>((const char*)workspace + t.off), dst, B, t.H, t.W, t.C,
-                                           plan->cfg.compute_mode == MI_COMPUTE_F16X3 ? 1 : 0, (hipStream_t)stream);
+                                           fp16_mfma(plan->cfg) ? 1 : 0, (hipStream_t)stream);
         if (e != hipSuccess) return fail(MI_EHIP, "nhwc_to_nchw: %s", hipGetErrorString(e));
     }
     return MI_OK;

@@ -96,7 +96,11 @@ struct Program {
 
 // f16x3 plans keep a second, wide-chunk copy (conv16_pick_tile: cb = 2) of a residual block's two 3x3 weights and of a folded
 // up-conv's, when the conv has at least one 32-channel chunk: what mi_unet_finalize packs and what the planner may pick
-inline bool packs_wide_copy(const mi_unet_cfg& cfg, int Cin) { return cfg.compute_mode == MI_COMPUTE_F16X3 && Cin >= 32; }
+inline bool packs_wide_copy(const mi_unet_cfg& cfg, int Cin) { return cfg.compute_mode != MI_COMPUTE_F32 && Cin >= 32; }
+// The two fp16-MFMA modes share planner, layouts (channel-blocked activations) and kernels' structure; they differ in the fp16
+// planes every MFMA operand has: 2 = hi | lo, three products (MI_COMPUTE_F16X3); 1 = the rounded value, one product (MI_COMPUTE_F16)
+inline bool fp16_mfma(const mi_unet_cfg& cfg) { return cfg.compute_mode == MI_COMPUTE_F16X3 || cfg.compute_mode == MI_COMPUTE_F16; }
+inline int operand_planes(const mi_unet_cfg& cfg) { return cfg.compute_mode == MI_COMPUTE_F16 ? 1 : 2; }
 
 int build_topology(mi_plan* p);                                                                   // midd_weights.hip
 int get_program(mi_plan* p, int B, int H, int W, Program** out, bool side_by_side = false);       // midd_planner.hip

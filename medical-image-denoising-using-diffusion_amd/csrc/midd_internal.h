@@ -105,6 +105,7 @@ struct ConvArgs {          // (activation pointers: NHWC for the fp32-MFMA kerne
 struct ConvTile {           // which template instance to launch
     int ks, stride, tw, mt, nt, wm, wn;
     int cb = 0;             // f16x3 3x3: 16-channel blocks per K chunk (0: conv16_cb(ks)); selects the weight packing too
+    int pl = 2;             // fp16-MFMA kernels: planes per operand, 2 = split-fp16 ("f16x3"), 1 = one-product fp16 ("f16"); selects kernel and packing
 };
 
 enum AttMode { ATT_NONE = 0, ATT_QKV_OUT = 1, ATT_PART_IN = 2 };
@@ -116,7 +117,7 @@ bool conv_pick_tile(int Cout, int B, int OH, int OW, int ks, int stride, ConvTil
 hipError_t conv_launch(const ConvArgs& a, const ConvTile& t, hipStream_t s);
 
 // split-fp16 variant (conv_mfma_f16x3.hip): same arguments, weights packed by pack_conv_f16x3
-bool conv16_pick_tile(int Cin, int Cout, int B, int OH, int OW, int ks, int stride, ConvTile* t, bool allow_wide = false);
+bool conv16_pick_tile(int Cin, int Cout, int B, int OH, int OW, int ks, int stride, ConvTile* t, bool allow_wide = false, int planes = 2);
 int conv16_wgs_per_img(int tiles, int B, int ny, int target = 0);   // target 0: 768
 bool conv1x1_pick_tile(int Cin, int Cout, int B, int OH, int OW, ConvTile* t);   // ConvTile::tw == 0 marks it
 hipError_t conv1x1_launch(const ConvArgs& a, const ConvTile& t, hipStream_t s);      // persistent workgroups per sample (f16x3 kernels)
@@ -165,10 +166,10 @@ hipError_t attention_launch(const float* qkv, float* out, int B, int N, int C, i
 // [B][N][C]) and the split-fp16 images of k and v, the attention kernel leaves key-split partials, the output projection
 // combines them while it loads its operand.  Scratch layout (attention16_layout): K image, V image, partial O, partial (m, l).
 struct Att16Layout { size_t k_off, v_off, po_off, ml_off, bytes; int npad; };
-Att16Layout attention16_layout(int B, int N, int C);
+Att16Layout attention16_layout(int B, int N, int C, int planes = 2);      // planes: fp16 planes of the K / V images (2 = f16x3, 1 = f16)
 // split_B: the batch the key split is chosen for (B, or 1 for batch-invariant plans)
 hipError_t attention16_launch(const float* q, const _Float16* Kp, const _Float16* Vp, float* part_o, float* part_ml,
-                              int B, int ksplit, int tiles_per_split, int N, int C, int heads, hipStream_t s);
+                              int B, int ksplit, int tiles_per_split, int N, int C, int heads, hipStream_t s, int planes = 2);
 // key split of the f16x3 attention for N keys: splits and 32-key tiles per split (every split owns >= 1 tile)
 void attention16_split(int N, int heads, int split_B, int* ksplit, int* tiles_per_split);
 bool attention_supported(int head_dim);

@@ -51,7 +51,7 @@ struct Builder {
     int conv(const ConvSpec& c) {
         const TensorRef &s0 = *c.s0, *s1 = c.s1; TensorRef& dst = *c.dst;
         const int cin = s0.C + (s1 ? s1->C : 0);
-        const bool f16 = p->cfg.compute_mode == MI_COMPUTE_F16X3;
+        const bool f16 = fp16_mfma(p->cfg);
         Op o{}; o.kind = OP_CONV; o.att_mode = c.att_mode; o.partial_off = c.att_scratch; o.att_ksplit = c.att_ksplit; o.s0 = s0; if (s1) { o.s1 = *s1; o.has_s1 = true; }
         // wscale = 2^-k / 2^s undoes the weight and the activation prescale; a raw operand's own prescale (per sample from
         // its statistics, or raw_scale_fixed) is divided out inside the kernel
@@ -67,7 +67,7 @@ struct Builder {
             o.res_scale = c.res_wscale * ACT_PRESCALE_H;         // 2^-k of the res_conv weights
         }
         const int Bp = p->batch_invariant ? INVARIANT_B : B; // batch-invariant plans tile as for the canonical batch
-        const bool ok = f16 ? conv16_pick_tile(cin, dst.C, Bp, dst.H, dst.W, c.ks, c.stride, &o.tile, g->wide_chunks && c.wide && packs_wide_copy(p->cfg, cin))
+        const bool ok = f16 ? conv16_pick_tile(cin, dst.C, Bp, dst.H, dst.W, c.ks, c.stride, &o.tile, g->wide_chunks && c.wide && packs_wide_copy(p->cfg, cin), operand_planes(p->cfg))
                             : conv_pick_tile(dst.C, Bp, dst.H, dst.W, c.ks, c.stride, &o.tile);
         if (!ok) return fail(MI_EINVAL, "no conv tile for Cout=%d ks=%d stride=%d", dst.C, c.ks, c.stride);
         if (o.tile.cb == 2) o.w = c.w_wide;                  // the launch walks K in the wide order
@@ -104,7 +104,7 @@ static int build_program(mi_plan* p, int B, int H, int W, Program* g) {
         if ((rc = bld.conv(c1))) return rc;
         ConvSpec c2{&h1, nullptr, &o, m.w2, m.b2, m.s2};
         c2.wide = true; c2.w_wide = m.w2x; c2.prologue = PRO_GN_SILU; c2.gn = GnRef{m.g2, m.be2, true};
-        if (m.in_c != m.out_c && p->cfg.compute_mode == MI_COMPUTE_F16X3) {
+        if (m.in_c != m.out_c && fp16_mfma(p->cfg)) {
             // res_conv(x) inside conv2's launch: extra K steps over the block input after each tile's 3x3 steps (SURVEY 2.1;
             // round 2 ran it as a launch of its own that wrote the tensor conv2 then re-read as its residual operand)
             c2.b = m.b2r; c2.res0 = &s0; c2.res1 = s1; c2.res_wscale = m.sr;
@@ -124,13 +124,13 @@ static int build_program(mi_plan* p, int B, int H, int W, Program* g) {
     };
     auto run_attn = [&](const Mod& m, const TensorRef& x, TensorRef* out) -> int {
         const int C = x.C, N = x.H * x.W;
-        const bool f16 = p->cfg.compute_mode == MI_COMPUTE_F16X3;
+        const bool f16 = fp16_mfma(p->cfg);
         TensorRef y = bld.alloc(C, x.H, x.W);
         // fp32 MFMA mode: qkv tensor -> attention -> att tensor -> proj.
         // split-fp16 mode, three launches: the qkv projection's epilogue writes q (fp32 [B][N][C], the head of `qkv`'s buffer)
         // and the split-fp16 K / V images into the scratch; the attention kernel leaves key-split partials there; the
         // output projection combines them while it loads its operand
-        const Att16Layout lay = attention16_layout(B, N, C);
+        const Att16Layout lay = attention16_layout(B, N, C, operand_planes(p->cfg));
         const size_t scratch = f16 ? bld.take(lay.bytes) : 0;
         int ksplit = 1, tps = 1;
         if (f16) attention16_split(N, ATTN_HEADS_ABI, p->batch_invariant ? INVARIANT_B : B, &ksplit, &tps);
@@ -299,14 +299,16 @@ void midd::op_work(mi_plan* p, Program* g, const Op& o, std::string* name, doubl
             break;
         case OP_CHAN_TOT: *name = "midd::chan_total_kernel"; *flops = 0; *bytes = 4.0 * elems(o.s0); break;
         case OP_CONV: {
-            if (p->cfg.compute_mode == MI_COMPUTE_F16X3 && o.tile.ks == 1 && o.tile.tw == 0)
-                snprintf(buf, sizeof(buf), "midd::conv1x1_f16x3_kernel<%d, %d, %d>", o.tile.mt, o.tile.nt, o.att_mode);
+            // the kernel that really runs: "f16x3" = two planes / three products, "f16" = one plane / one product
+            const char* mode = p->cfg.compute_mode == MI_COMPUTE_F16X3 ? "f16x3" : p->cfg.compute_mode == MI_COMPUTE_F16 ? "f16" : "f32";
+            if (fp16_mfma(p->cfg) && o.tile.ks == 1 && o.tile.tw == 0)
+                snprintf(buf, sizeof(buf), "midd::conv1x1_%s_kernel<%d, %d, %d>", mode, o.tile.mt, o.tile.nt, o.att_mode);
             else {
-                char tail[32] = "";         // f16x3: the RES flag and the chunk width (template arguments 8 and 9)
-                if (p->cfg.compute_mode == MI_COMPUTE_F16X3)
+                char tail[32] = "";         // fp16 MFMA: the RES flag and the chunk width (template arguments 8 and 9)
+                if (fp16_mfma(p->cfg))
                     snprintf(tail, sizeof(tail), ", %s, %d", (o.res_steps > 0 && o.tile.stride == 1 && o.tile.ks == 3) ? "true" : "false", o.tile.cb);
                 snprintf(buf, sizeof(buf), "midd::conv_mfma_%s_kernel<%d, %d, %d, %d, %d, %d, %d%s>",
-                         p->cfg.compute_mode == MI_COMPUTE_F16X3 ? "f16x3" : "f32", o.tile.ks, o.tile.stride,
+                         mode, o.tile.ks, o.tile.stride,
                          o.tile.tw, o.tile.mt, o.tile.nt, o.tile.wm, o.tile.wn, tail);
             }
             *name = buf;
@@ -320,7 +322,7 @@ void midd::op_work(mi_plan* p, Program* g, const Op& o, std::string* name, doubl
         }
         case OP_ATTN: {
             const double N = (double)o.dst.H * o.dst.W;
-            snprintf(buf, sizeof(buf), "midd::attention_%s_kernel<%d>", p->cfg.compute_mode == MI_COMPUTE_F16X3 ? "f16x3" : "f32", o.dst.C / 2);
+            snprintf(buf, sizeof(buf), "midd::attention_%s_kernel<%d>", p->cfg.compute_mode == MI_COMPUTE_F16X3 ? "f16x3" : p->cfg.compute_mode == MI_COMPUTE_F16 ? "f16" : "f32", o.dst.C / 2);
             *name = buf;
             *flops = 4.0 * B * N * N * o.dst.C;              // QK^T + PV over both heads
             *bytes = 4.0 * (elems(o.s0) + elems(o.dst));
@@ -365,7 +367,7 @@ int midd::dump_program(mi_plan* p, int B, int H, int W, bool side_by_side, std::
                 (int)(&o - g.ops.data()), kinds[o.kind], o.dst.H ? o.dst.H : H, o.dst.W ? o.dst.W : W, o.s0.C, o.has_s1 ? o.s1.C : 0, o.dst.C, o.ks, o.stride,
                 o.prologue, o.res_steps, o.att_mode, o.att_ksplit, o.att_tps, o.s0.stat_bs, o.has_s1 ? o.s1.stat_bs : 0, o.dst.stat_bs, name.c_str());
         ConvLaunchInfo li{};
-        if (o.kind == OP_CONV && p->cfg.compute_mode == MI_COMPUTE_F16X3 &&
+        if (o.kind == OP_CONV && fp16_mfma(p->cfg) &&
             conv16_launch_info(o.s0.C + (o.has_s1 ? o.s1.C : 0), o.dst.C, B, o.dst.H, o.dst.W, o.tile, g.persist_wgs, &li))
             appendf(" | grid %dx%d wgs/img %d tiles %dx%d ring %d ppw %d apw %d lds %d", li.grid_x, li.grid_y, li.wgs_per_img,
                     li.tiles_x, li.tiles_y, li.ring, li.ppw, li.apw, li.lds_bytes);

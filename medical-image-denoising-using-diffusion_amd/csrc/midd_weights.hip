@@ -138,7 +138,8 @@ static std::vector<float> pack_conv_f32(const float* w, int Cout, int Cin, int K
     return out;
 }
 
-// Split-fp16 packing for conv_mfma_f16x3.hip:  [step][Cout/16][hi|lo][lane 64][8 fp16].
+// Split-fp16 packing for conv_mfma_f16x3.hip:  [step][Cout/16][hi|lo][lane 64][8 fp16]  (planes == 2; planes == 1, compute
+// "f16": the hi plane alone, [step][Cout/16][lane 64][8 fp16] -- fp16(w') of the same w').
 // Steps walk 32 input channels (blocks 2c, 2c+1) per tap; a trailing single block pairs two
 // taps per step.  lane = kq*16 + n; element j is W[16*tile+n][cin][tap] with
 //   full chunk : cin = 16*(2c + (kq>>1)) + 8*(kq&1) + j, tap = step's tap
@@ -146,7 +147,7 @@ static std::vector<float> pack_conv_f32(const float* w, int Cout, int Cin, int K
 // w' = w * 2^k (k per layer, max|w'| in [2^13,2^14)); hi = fp16(w'), lo = fp16(w' - hi).
 // *out_scale = 2^-k / ACT_PRESCALE.  Returned as raw 32-bit words (two fp16 each).
 static const float SILU_WEIGHT_FACTOR_H = -0.6931471805599453f;     // == SILU_WEIGHT_FACTOR (f16x3_common.h): see conv_mfma_f16x3.hip, transform
-static std::vector<float> pack_conv_f16x3(const float* w_in, int Cout, int Cin, int KS, float* out_scale, float wmul = 1.0f, int cb = 0) {
+static std::vector<float> pack_conv_f16x3(const float* w_in, int Cout, int Cin, int KS, float* out_scale, int planes, float wmul = 1.0f, int cb = 0) {
     if (cb == 0) cb = conv16_cb(KS);                     // blocks per K chunk: the K order of the steps (midd_internal.h)
     // wmul: constant folded into the weights (fp32 product, rounded once): -ln 2 for the convolutions behind GroupNorm + SiLU,
     // whose operand the kernel forms as -16 log2(e) silu(y)
@@ -166,7 +167,7 @@ static std::vector<float> pack_conv_f16x3(const float* w_in, int Cout, int Cin, 
     const int k = 14 - e;                                // max|w * 2^k| in [2^13, 2^14)
     const float wscale = std::ldexp(1.0f, k);
     *out_scale = std::ldexp(1.0f, -k) / ACT_PRESCALE_H;
-    std::vector<_Float16> out((size_t)steps * ntile * 2 * 64 * 8);
+    std::vector<_Float16> out((size_t)steps * ntile * planes * 64 * 8);
     int step = 0;
     auto emit = [&](int blk_of_kq0, int blk_of_kq2, int tap_of_kq0, int tap_of_kq2) {
         for (int nt = 0; nt < ntile; ++nt)
@@ -182,9 +183,9 @@ static std::vector<float> pack_conv_f16x3(const float* w_in, int Cout, int Cin, 
                     }
                     const _Float16 hi = (_Float16)v;
                     const _Float16 lo = (_Float16)(v - (float)hi);
-                    const size_t base = (((size_t)step * ntile + nt) * 2) * 64 * 8;
+                    const size_t base = (((size_t)step * ntile + nt) * planes) * 64 * 8;
                     out[base + (size_t)lane * 8 + j] = hi;
-                    out[base + 64 * 8 + (size_t)lane * 8 + j] = lo;
+                    if (planes == 2) out[base + 64 * 8 + (size_t)lane * 8 + j] = lo;
                 }
             }
         ++step;
@@ -280,16 +281,17 @@ extern "C" int mi_unet_finalize(mi_plan* plan, int time_rows) {
         if (!getw(plan, k)) return fail(MI_ESTATE, "missing key in state_dict: \"%s\"", k.c_str());
 
     Packer pk;
-    const bool f16 = plan->cfg.compute_mode == MI_COMPUTE_F16X3;
+    const bool f16 = fp16_mfma(plan->cfg);               // either fp16-MFMA mode
+    const int planes = operand_planes(plan->cfg);
     auto pack_conv = [&](const float* w, int Cout, int Cin, int KS, float* scale, bool behind_silu = false) {
         *scale = 1.0f;
-        return f16 ? pack_conv_f16x3(w, Cout, Cin, KS, scale, behind_silu ? SILU_WEIGHT_FACTOR_H : 1.0f) : pack_conv_f32(w, Cout, Cin, KS);
+        return f16 ? pack_conv_f16x3(w, Cout, Cin, KS, scale, planes, behind_silu ? SILU_WEIGHT_FACTOR_H : 1.0f) : pack_conv_f32(w, Cout, Cin, KS);
     };
     // second copy of a 3x3's weights in the wide-chunk K order (same values, same scale); the planner picks per launch
     auto pack_wide = [&](const float* w, int Cout, int Cin, bool behind_silu, const std::vector<float>* tail = nullptr) -> size_t {
         if (!packs_wide_copy(plan->cfg, Cin)) return (size_t)-1;
         float scale;
-        std::vector<float> v = pack_conv_f16x3(w, Cout, Cin, 3, &scale, behind_silu ? SILU_WEIGHT_FACTOR_H : 1.0f, 2);
+        std::vector<float> v = pack_conv_f16x3(w, Cout, Cin, 3, &scale, planes, behind_silu ? SILU_WEIGHT_FACTOR_H : 1.0f, 2);
         if (tail) v.insert(v.end(), tail->begin(), tail->end());
         return pk.put(v);
     };

@@ -64,8 +64,16 @@ class UNetDiffusion(nn.Module):
         # batch it is computed in, bit for bit (denoise(x[:k]) == denoise(x)[:k]) -- every launch is planned as for a batch of
         # one, which costs throughput at large batches.  Default off: results are then reproducible per (batch size, image size).
         self.batch_invariant = bool(int(os.environ.get("MIDD_BATCH_INVARIANT", "0"))) if batch_invariant is None else bool(batch_invariant)
-        # arithmetic of the MFMA contractions: "f16x3" (split-fp16, default) or "f32" (fp32-input MFMA)
-        self.compute = compute or os.environ.get("MIDD_COMPUTE", "f16x3")
+        # arithmetic of the MFMA contractions: "f16x3" (split-fp16, default) or "f32" (fp32-input MFMA) -- the two parity modes --
+        # or "f16": every MFMA operand rounded once to fp16, one product, fp32 accumulate (the precision of the reference under
+        # autocast, not parity: DESIGN.md section 4).  "f16" is opt-in BY ARGUMENT only: the environment may select between the
+        # parity modes, never the reduced-precision one (a run must not change its numerics, or a benchmark line its meaning,
+        # through a variable nobody sees in the code).
+        env_compute = os.environ.get("MIDD_COMPUTE")
+        if compute is None and env_compute == "f16":
+            raise ValueError('MIDD_COMPUTE=f16 is not accepted: the reduced-precision mode is selected by argument only, '
+                             'UNetDiffusion(compute="f16")')
+        self.compute = compute or env_compute or "f16x3"
         if self.compute not in native.MI_COMPUTE:
             raise ValueError(f"compute must be one of {sorted(native.MI_COMPUTE)}")
         self.cfg = UNetConfig(in_channels, model_channels, tuple(channel_mult), num_res_blocks,
@@ -83,7 +91,7 @@ class UNetDiffusion(nn.Module):
         self._lock = threading.RLock()
         self._workspaces: Dict[Tuple[int, int, int, int, int], torch.Tensor] = {}
         # After every native call the status word of its workspace is read back (mi_status: one 4-byte copy, synchronises the
-        # stream): NaN / Inf activations or an operand beyond the split-fp16 range raise MiddError instead of returning garbage.
+        # stream): NaN / Inf activations or an operand beyond the fp16 range (f16x3, f16) raise MiddError instead of returning garbage.
         # Set to False (env MIDD_CHECK_STATUS=0) to keep forward() / denoise() asynchronous; the output is NaN then, as torch's.
         self.check_status = bool(int(os.environ.get("MIDD_CHECK_STATUS", "1")))
         # Debug / test knob (env MIDD_POISON_WS = a byte value 0..255, e.g. 255: every float reads as NaN, every statistics limb

@@ -17,7 +17,7 @@ MI_MAX_LEVELS = 8
 MI_VARIANT = {"ddim": 0, "cddpm": 1}
 MI_CLAMP_EPS = 1
 MI_NO_SPLIT = 2
-MI_COMPUTE = {"f32": 0, "f16x3": 1}
+MI_COMPUTE = {"f32": 0, "f16x3": 1, "f16": 2}
 MI_STATUS_NONFINITE, MI_STATUS_FP16_RANGE = 1, 2
 MI_COMPUTE_BATCH_INVARIANT = 0x100          # include/midd.h: OR into compute_mode
 
@@ -63,6 +63,7 @@ SYMBOLS = [
     ("mi_debug_attention_split", C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("mi_debug_plan_dump", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_size_t]),
     ("mi_debug_conv16_geometry", C.c_int, [C.c_int] * 8 + [C.POINTER(C.c_int)] * 4),
+    ("mi_debug_conv16_geometry_planes", C.c_int, [C.c_int] * 9 + [C.POINTER(C.c_int)] * 4),
     ("mi_source_hash", C.c_char_p, []),
     ("mi_profile_begin", C.c_int, [C.c_void_p]),
     ("mi_profile_end", C.c_int, [C.c_void_p, C.POINTER(ProfileEntry), C.c_int, C.POINTER(C.c_int)]),

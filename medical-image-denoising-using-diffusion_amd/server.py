@@ -98,7 +98,8 @@ class DiffusionService:
     """Counterpart of ModelManager's diffusion members (run.py:20-42,103-111)."""
 
     def __init__(self, checkpoint: Optional[str] = None, device: Optional[torch.device] = None,
-                 denoise_fn: Optional[Callable[[torch.Tensor], torch.Tensor]] = None):
+                 denoise_fn: Optional[Callable[[torch.Tensor], torch.Tensor]] = None, compute: Optional[str] = None):
+        self.compute = compute                 # arithmetic of the network (UNetDiffusion); None: the default
         self.device = device or torch.device("cuda" if torch.cuda.is_available() else "cpu")
         self.checkpoint = checkpoint
         self.diffusion_model = None
@@ -108,7 +109,7 @@ class DiffusionService:
 
     def load_models(self) -> None:
         model = UNetDiffusion(in_channels=1, model_channels=48, channel_mult=(1, 2, 3, 4), num_res_blocks=2,
-                              attention_resolutions=(3,), dropout=0.0, time_emb_dim=192)
+                              attention_resolutions=(3,), dropout=0.0, time_emb_dim=192, compute=self.compute)
         noise_steps = 50
         if self.checkpoint:
             ckpt = torch.load(self.checkpoint, map_location="cpu", weights_only=True)
