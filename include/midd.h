@@ -133,6 +133,36 @@ int mi_denoise(mi_plan* plan, const float* noisy, float* x_out, int B, int H, in
                const float* step_noise, int flags,
                void* workspace, size_t workspace_bytes, void* stream);
 
+/* mi_denoise for the cddpm variant with the step noise drawn ON THE DEVICE, inside the fused update, from a seeded counter-based
+ * generator (the reference draws torch.randn_like(x) per iteration, cddpmModels.py:297-302; its generator stream is not
+ * reproduced).  No noise tensor exists.  Same arguments as mi_denoise without `step_noise`, plus
+ *   seed           any 64-bit value
+ *   sample_offset  global index of sample 0 of this call (>= 0): a caller that splits a batch over calls, streams or GPUs passes
+ *                  each part its offset and gets the noise the whole batch would have got, bit for bit.  The two-stream split
+ *                  inside the call does the same (sub-batch h of `parts` passes sample_offset + h * B / parts).
+ * Every value is a pure function of (seed, global sample index, iteration index i, element index): it does not depend on B,
+ * on MI_NO_SPLIT, on the stream or on the device.  THE SPECIFICATION (fixed):
+ *   Philox4x32-10 as in Random123: multipliers 0xD2511F53, 0xCD9E8D57; key increments 0x9E3779B9, 0xBB67AE85; ten rounds
+ *   counter  c0 = element index inside the sample's [C,H,W] block (C*H*W < 2^32, else MI_EINVAL), c1 = low 32 bits of
+ *            sample_offset + b, c2 = i (position in t_list), c3 = 0 (reserved: stream id);   key  k0, k1 = low, high word of seed
+ *   one Philox call per element, outputs x0 and x1 used:
+ *   u1 = ((x0 >> 8) + 1) * 2^-24 in (0, 1],   u2 = (x1 >> 8) * 2^-24 in [0, 1)   (exact in fp32)
+ *   z  = sqrtf(-2 * logf(u1)) * cospif(2 * u2)   (accurate fp32 library functions, each product rounded once; |z| <= 5.77)
+ *   x += sqrt(beta_t) * (0.5 * z)   for t_list[i] > 0, where mi_denoise adds sqrt(beta_t) * step_noise[i]; nothing is drawn at t == 0
+ * With the DDIM variant's flags the call works too and simply adds the term; the host shims never seed that variant. */
+int mi_denoise_seeded(mi_plan* plan, const float* noisy, float* x_out, int B, int H, int W,
+                      const int32_t* t_list, int n_iters,
+                      const float* beta, const float* alpha, const float* alpha_hat, int noise_steps,
+                      uint64_t seed, int64_t sample_offset, int flags,
+                      void* workspace, size_t workspace_bytes, void* stream);
+
+/* The values mi_denoise_seeded draws, as a tensor (no plan needed): dst device fp32 [n_iters,B,C,H,W] <- 0.5 * z of
+ * (seed, sample_offset + b, i, element), i.e. already 0.5-scaled as mi_denoise's `step_noise` expects.  Replay and export:
+ * mi_denoise with this tensor equals mi_denoise_seeded bit for bit.  Every iteration is filled (the t == 0 entry is ignored
+ * by mi_denoise).  MI_EINVAL: sample_offset < 0, C*H*W >= 2^32, B or n_iters > 65535.  Asynchronous on `stream`. */
+int mi_step_noise_fill(float* dst, int n_iters, int B, int C, int H, int W,
+                       uint64_t seed, int64_t sample_offset, void* stream);
+
 /* Status of the last mi_unet_forward / mi_denoise call that used `workspace` (its first word; the calls clear it when they
  * start).  SYNCHRONISES `stream` (one 4-byte device-to-host copy).  Returns MI_OK with *flags == 0, or MI_ERANGE with the
  * MI_STATUS_* bits in *flags: the kernels never turn a NaN / Inf activation or an operand beyond the split-fp16 range into

@@ -5,7 +5,7 @@
 img_size -> sampler -> uint8 -> bicubic resize back -> PNG, with the reference's timing print.
 
     python -m midd_amd.cli --image in.png --out out.png [--checkpoint ckpt.pth] [--variant cddpm|ddim]
-                           [--img-size 512] [--inference-steps 25]
+                           [--img-size 512] [--inference-steps 25] [--seed N]
 
 Without a checkpoint (the trained weights are not distributed with the reference) the network is
 random-init, which exercises the path but does not denoise.  The reference helper has a latent
@@ -28,8 +28,11 @@ from .sampler import DiffusionDenoiser
 
 def denoise_image_diffusion(model_path: Optional[str], test_image_path: str, device_type: str = "cuda",
                             img_size: int = 512, inference_steps: int = 50, variant: str = "cddpm",
-                            step_noise: Optional[torch.Tensor] = None, compute: Optional[str] = None) -> Image.Image:
-    """compute (not a reference argument): arithmetic of the network, see UNetDiffusion -- None keeps the default."""
+                            step_noise: Optional[torch.Tensor] = None, compute: Optional[str] = None,
+                            seed: Optional[int] = None) -> Image.Image:
+    """compute (not a reference argument): arithmetic of the network, see UNetDiffusion -- None keeps the default.
+    seed (not a reference argument; cddpm): the stochastic sampler's noise is drawn on the device from this seed, so the same
+    call gives the same image again (DiffusionDenoiser.denoise); None: torch.randn, as the reference."""
     device = torch.device(device_type)
     model = UNetDiffusion(in_channels=1, model_channels=48, channel_mult=(1, 2, 3, 4), num_res_blocks=2,
                           attention_resolutions=(3,), dropout=0.0, time_emb_dim=192, variant=variant, compute=compute)
@@ -53,6 +56,8 @@ def denoise_image_diffusion(model_path: Optional[str], test_image_path: str, dev
 
     start_time = time.time()
     kw = {"step_noise": step_noise} if step_noise is not None else {}
+    if seed is not None:
+        kw["seed"] = seed
     denoised = diffusion.denoise(input_tensor, inference_steps=inference_steps, **kw)
     if device.type == "cuda":
         torch.cuda.synchronize(device)
@@ -75,9 +80,11 @@ def main(argv=None) -> None:
     ap.add_argument("--img-size", type=int, default=512)
     ap.add_argument("--inference-steps", type=int, default=25)
     ap.add_argument("--device", default="cuda")
+    ap.add_argument("--seed", type=int, default=None,
+                    help="cddpm: draw the sampler's noise on the device from this seed (reproducible); default: torch.randn")
     args = ap.parse_args(argv)
     restored = denoise_image_diffusion(args.checkpoint, args.image, device_type=args.device, img_size=args.img_size,
-                                       inference_steps=args.inference_steps, variant=args.variant)
+                                       inference_steps=args.inference_steps, variant=args.variant, seed=args.seed)
     restored.save(args.out, quality=95)
     print(f"\nResult saved: {args.out}")
 

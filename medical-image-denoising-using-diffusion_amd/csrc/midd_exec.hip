@@ -6,6 +6,9 @@ using namespace midd;
 struct StepIO {
     const float* x; const float* cond; float* eps_out;
     float* x_update; const float* noise; float c1, c2, c3; int clamp_eps;
+    // seeded != 0: the update draws its noise term (step_noise_common.h) for iteration `iter`, sample 0 of this program being
+    // global sample `sample_offset`
+    int seeded; int iter; uint64_t seed; int64_t sample_offset;
 };
 
 // status: the call's status word (first word of the CALLER's workspace, whichever sub-batch program runs)
@@ -107,6 +110,7 @@ static int run_program(mi_plan* p, Program* g, const StepIO& io, char* ws, int* 
                 a.B = B; a.H = g->H; a.W = g->W; a.C = o.s0.C; a.ic = p->cfg.in_channels;
                 a.eps_out = io.eps_out; a.x = io.x_update; a.noise = io.noise;
                 a.c1 = io.c1; a.c2 = io.c2; a.c3 = io.c3; a.clamp_eps = io.clamp_eps;
+                a.seeded = io.seeded; a.iter = io.iter; a.seed = io.seed; a.sample_offset = io.sample_offset;
                 e = out_conv_launch(a, s);
                 break;
             }
@@ -120,6 +124,8 @@ static int run_program(mi_plan* p, Program* g, const StepIO& io, char* ws, int* 
             (void)hipEventRecord(ev_b, s);
             mi_plan::Span sp; sp.a = ev_a; sp.b = ev_b;
             op_work(p, g, o, &sp.name, &sp.flops, &sp.bytes);
+            const size_t oc_at = sp.name.find("out_conv_kernel");
+            if (o.kind == OP_OUT && io.seeded && oc_at != std::string::npos) sp.name.replace(oc_at, 15, "out_conv_seeded_kernel");      // the symbol that ran
             static const bool per_op = getenv("MIDD_PROFILE_PER_OP") != nullptr;      // one entry per op instead of per symbol
             if (per_op) {
                 char tag[96];
@@ -158,15 +164,19 @@ extern "C" int mi_unet_forward(mi_plan* plan, const float* x, const float* condi
     HIPCHK(hipMemsetAsync(ws, 0, 256, s));                  // status word
     hipError_t e = fill_i32_launch(reinterpret_cast<int*>(ws + g->trow_off), t, B, s);
     if (e != hipSuccess) return fail(MI_EHIP, "fill timesteps: %s", hipGetErrorString(e));
-    StepIO io{x, condition, eps, nullptr, nullptr, 0.f, 0.f, 0.f, 0};
+    StepIO io{};
+    io.x = x; io.cond = condition; io.eps_out = eps;
     return run_program(plan, g, io, ws, reinterpret_cast<int*>(ws), s);
 }
 
-extern "C" int mi_denoise(mi_plan* plan, const float* noisy, float* x_out, int B, int H, int W,
-                          const int32_t* t_list, int n_iters,
-                          const float* beta, const float* alpha, const float* alpha_hat, int noise_steps,
-                          const float* step_noise, int flags,
-                          void* workspace, size_t workspace_bytes, void* stream) {
+// The noise term of the cddpm update: none, a caller's tensor (mi_denoise), or drawn in the update (mi_denoise_seeded)
+struct StepNoise { const float* tensor = nullptr; bool seeded = false; uint64_t seed = 0; int64_t sample_offset = 0; };
+
+static int denoise_run(mi_plan* plan, const float* noisy, float* x_out, int B, int H, int W,
+                       const int32_t* t_list, int n_iters,
+                       const float* beta, const float* alpha, const float* alpha_hat, int noise_steps,
+                       const StepNoise& sn, int flags,
+                       void* workspace, size_t workspace_bytes, void* stream) {
     Program* g = nullptr;
     int rc = check_call(plan, B, H, W, workspace, workspace_bytes, &g);
     if (rc) return rc;
@@ -222,7 +232,11 @@ extern "C" int mi_denoise(mi_plan* plan, const float* noisy, float* x_out, int B
                 io.c1 = 1.0f / sqrtf(alpha[t]);                  // fp32 arithmetic in the reference's order (DDIMModel.py:280-283)
                 io.c2 = (1.0f - alpha[t]) / sqrtf(1.0f - alpha_hat[t]);
                 io.c3 = sqrtf(beta[t]);
-                io.noise = (step_noise && t > 0) ? step_noise + (size_t)i * img_elems + h * part : nullptr;      // cddpmModels.py:297-300
+                io.noise = (sn.tensor && t > 0) ? sn.tensor + (size_t)i * img_elems + h * part : nullptr;      // cddpmModels.py:297-300
+                if (sn.seeded && t > 0) {                        // nothing is drawn at t == 0
+                    io.seeded = 1; io.iter = i; io.seed = sn.seed;
+                    io.sample_offset = sn.sample_offset + (int64_t)h * (B / parts);
+                }
                 io.clamp_eps = (flags & MI_CLAMP_EPS) ? 1 : 0;
                 if (i == 0 && h > 0) HIPCHK(hipStreamWaitEvent(sh, plan->sev_phase[h - 1], 0));      // phase offset (re-establishing it every n-th
                                                                                                       // iteration measured -2 %: round 4; the streams run freely)
@@ -243,6 +257,52 @@ extern "C" int mi_denoise(mi_plan* plan, const float* noisy, float* x_out, int B
         }
     }
     return rc;
+}
+
+extern "C" int mi_denoise(mi_plan* plan, const float* noisy, float* x_out, int B, int H, int W,
+                          const int32_t* t_list, int n_iters,
+                          const float* beta, const float* alpha, const float* alpha_hat, int noise_steps,
+                          const float* step_noise, int flags,
+                          void* workspace, size_t workspace_bytes, void* stream) {
+    StepNoise sn;
+    sn.tensor = step_noise;
+    return denoise_run(plan, noisy, x_out, B, H, W, t_list, n_iters, beta, alpha, alpha_hat, noise_steps, sn, flags,
+                       workspace, workspace_bytes, stream);
+}
+
+// the generator's counter words: element index and sample index (step_noise_common.h)
+static int check_step_noise_range(int64_t C, int64_t H, int64_t W, int64_t sample_offset) {
+    if (sample_offset < 0) return fail(MI_EINVAL, "sample_offset %lld is negative: the global sample index starts at 0", (long long)sample_offset);
+    if (C < 1 || H < 1 || W < 1) return fail(MI_EINVAL, "bad image shape %lldx%lldx%lld", (long long)C, (long long)H, (long long)W);
+    // (three factors below 2^31 each: the product of two fits 64 bits, the third is compared by division)
+    if (C * H > (int64_t)0xFFFFFFFFll / W)
+        return fail(MI_EINVAL, "C*H*W = %lld*%lld*%lld reaches 2^32: the element index of the seeded step noise is one 32-bit counter word "
+                    "(limit: C*H*W < 4294967296)", (long long)C, (long long)H, (long long)W);
+    return MI_OK;
+}
+
+extern "C" int mi_denoise_seeded(mi_plan* plan, const float* noisy, float* x_out, int B, int H, int W,
+                                 const int32_t* t_list, int n_iters,
+                                 const float* beta, const float* alpha, const float* alpha_hat, int noise_steps,
+                                 uint64_t seed, int64_t sample_offset, int flags,
+                                 void* workspace, size_t workspace_bytes, void* stream) {
+    if (!plan) return fail(MI_EINVAL, "null plan");
+    if (int rc = check_step_noise_range(plan->cfg.in_channels, H, W, sample_offset)) return rc;
+    StepNoise sn;
+    sn.seeded = true; sn.seed = seed; sn.sample_offset = sample_offset;
+    return denoise_run(plan, noisy, x_out, B, H, W, t_list, n_iters, beta, alpha, alpha_hat, noise_steps, sn, flags,
+                       workspace, workspace_bytes, stream);
+}
+
+extern "C" int mi_step_noise_fill(float* dst, int n_iters, int B, int C, int H, int W,
+                                  uint64_t seed, int64_t sample_offset, void* stream) {
+    if (int rc = check_step_noise_range(C, H, W, sample_offset)) return rc;
+    if (n_iters < 0 || B < 0 || n_iters > 65535 || B > 65535) return fail(MI_EINVAL, "n_iters %d / B %d outside [0, 65535]", n_iters, B);
+    if (n_iters == 0 || B == 0) return MI_OK;
+    if (!dst) return fail(MI_EINVAL, "null argument");
+    const hipError_t e = step_noise_fill_launch(dst, n_iters, B, (unsigned long long)C * H * W, seed, sample_offset, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(MI_EHIP, "step_noise_fill: %s", hipGetErrorString(e));
+    return MI_OK;
 }
 
 extern "C" int mi_debug_fetch(mi_plan* plan, const char* module_name, int B, int H, int W, const void* workspace,

@@ -193,8 +193,16 @@ struct OutConvArgs {
     const float* noise;     // NCHW or null
     float c1, c2, c3;
     int clamp_eps;
+    // seeded != 0 (needs x): the noise term is drawn in the update instead of read from `noise` (step_noise_common.h):
+    // value = f(seed, sample_offset + b, iter, element index inside the sample) -- out_conv_seeded_kernel
+    int seeded;
+    int iter;                       // position in t_list
+    unsigned long long seed;
+    long long sample_offset;        // global index of this launch's sample 0
 };
 hipError_t out_conv_launch(const OutConvArgs& a, hipStream_t s);
+// dst [n_iters][B][chw] <- the 0.5-scaled seeded step noise (step_noise_common.h); chw < 2^32, B and n_iters <= 65535
+hipError_t step_noise_fill_launch(float* dst, int n_iters, int B, unsigned long long chw, unsigned long long seed, long long sample_offset, hipStream_t s);
 
 // bilinear resize of an activation tensor, either layout (align_corners=False), any size ratio
 hipError_t resize_bilinear_launch(const float* src, float* dst, stat_word* tot, int rep, int bs, int B, int H, int W, int C, int OH, int OW, int blocked, hipStream_t s);

@@ -1,0 +1,128 @@
+// The out_conv kernel's text (pointwise.hip), compiled twice: MIDD_OUT_KERNEL = out_conv_kernel with MIDD_OUT_SEEDED 0 (the noise
+// term of the sampler update, if any, is read from a.noise) and out_conv_seeded_kernel with MIDD_OUT_SEEDED 1 (the term is drawn
+// in the update from a.seed / a.sample_offset / a.iter: step_noise_common.h -- no noise tensor exists, 4 bytes per pixel less
+// are read).  Two kernels from one text rather than one template argument more: the unseeded kernels keep their symbols
+// (mi_profile_end, plan dumps) and compile to exactly what they were (instruction mix, registers: profiles/step_noise_isa.txt).
+template <int IC>
+__global__ __launch_bounds__(256)
+void MIDD_OUT_KERNEL(const OutConvArgs a, const float* __restrict__ wglob /* == a.w: a restrict parameter of its own, so that uniform reads become scalar loads */) {
+    __shared__ __attribute__((aligned(16))) float tile[OC_I * OC_I * OC_PS];
+    extern __shared__ __attribute__((aligned(16))) float wl[];       // [ic][9][C], then [2][C] GroupNorm scale / shift of this sample
+    const int ic = IC ? IC : a.ic;
+    const int tid = threadIdx.x;
+    const int tx = tid & 15, ty = tid >> 4;
+    float* const gnp = wl + ic * 9 * a.C;
+    const int tiles_x = (a.W + OC_T - 1) / OC_T, tiles_y = (a.H + OC_T - 1) / OC_T;
+    const int b = blockIdx.x / (tiles_x * tiles_y);
+    const int trem = blockIdx.x - b * tiles_x * tiles_y;
+    const int oy0 = (trem / tiles_x) * OC_T, ox0 = (trem % tiles_x) * OC_T;
+    const int C = a.C;
+    if constexpr (IC == 0) for (int i = tid; i < ic * 9 * C; i += 256) wl[i] = a.w[i];     // (IC > 0 reads the weights through scalar loads)
+
+    float acc[4] = {0.f, 0.f, 0.f, 0.f};          // ic <= 4 output channels
+    // Staging, round 3: a thread's slots (halo pixel, channel quad) are the same for every 16-channel chunk, so their
+    // addresses are formed once, branch-free (clamped; out-of-image and surplus slots load a valid dummy and store
+    // zeros), and the NEXT chunk's quads are requested before this chunk's taps: the loads fly under the arithmetic.
+    constexpr int NSL = (OC_I * OC_I * 4 + 255) / 256;
+    unsigned soff[NSL];                           // float offset of the slot's quad from the chunk's base
+    unsigned live = 0;                            // bit s: slot exists and lies in the image
+#pragma unroll
+    for (int s = 0; s < NSL; ++s) {
+        const int slot = min(tid + s * 256, OC_I * OC_I * 4 - 1);
+        const int pix = slot >> 2, q = slot & 3;
+        const int iy = pix / OC_I, ix = pix - iy * OC_I;
+        const int gy = oy0 + iy - 1, gx = ox0 + ix - 1;
+        const int cy = min(max(gy, 0), a.H - 1), cx = min(max(gx, 0), a.W - 1);
+        if (tid + s * 256 < OC_I * OC_I * 4 && gy == cy && gx == cx) live |= 1u << s;
+        soff[s] = (unsigned)((size_t)(cy * a.W + cx) * (a.blocked ? 16 : C) + q * 4);       // inside the sample (NHWC) / inside a block plane
+    }
+    const size_t plane = (size_t)a.H * a.W;
+    auto chunk_base = [&](int c0) {               // first element of the sample's 16-channel chunk c0
+        return a.blocked ? ((size_t)b * (C >> 4) + (c0 >> 4)) * plane * 16 : (size_t)b * plane * C + c0;
+    };
+    f32x4 pre[NSL];
+    auto prefetch = [&](int c0) {
+#pragma unroll
+        for (int s = 0; s < NSL; ++s) {
+#if defined(PW_ABL) && PW_ABL == 11     // ablation (tools/mb/pw_abl.hip, wrong results): no input loads
+            pre[s] = (f32x4){(float)soff[s], 1.f, 2.f, 3.f};
+#else
+            pre[s] = *reinterpret_cast<const f32x4*>(a.src + chunk_base(c0) + soff[s]);
+#endif
+        }
+    };
+    prefetch(0);                                  // the first chunk's quads fly while the GroupNorm scale / shift are derived
+    // (second source: C1 = 0, never read; a literal nullptr there crashes hipcc 7.2's inliner)
+    gn_prologue_lds(a.gn_tot, C, a.gn_bs, a.gn_tot, 0, 1, a.stat_rep, a.gn_gamma, a.gn_beta, a.gn_eps, 1.0 / ((double)a.H * a.W * (C / GN_GROUPS_C)), b, 1.0f, gnp, tid, 256);
+    for (int c0 = 0; c0 < C; c0 += 16) {
+        __syncthreads();                          // the previous chunk's taps are done with the tile
+#pragma unroll
+        for (int s = 0; s < NSL; ++s) {
+            const int slot = tid + s * 256;
+            if (slot < OC_I * OC_I * 4) {
+                const int q = slot & 3;
+                const f32x4 sc = *reinterpret_cast<const f32x4*>(gnp + c0 + q * 4);
+                const f32x4 sh = *reinterpret_cast<const f32x4*>(gnp + C + c0 + q * 4);
+                f32x4 v = pre[s] * sc + sh;
+#if !(defined(PW_ABL) && PW_ABL == 12)  // ablation: no SiLU
+                v.x = silu_pw(v.x); v.y = silu_pw(v.y); v.z = silu_pw(v.z); v.w = silu_pw(v.w);
+#endif
+                if (!((live >> s) & 1u)) v = (f32x4){0.f, 0.f, 0.f, 0.f};      // the conv's zero padding
+                *reinterpret_cast<f32x4*>(&tile[(slot >> 2) * OC_PS + q * 4]) = v;
+            }
+        }
+        if (c0 + 16 < C) prefetch(c0 + 16);
+        __syncthreads();
+#if defined(PW_ABL) && PW_ABL == 13     // ablation: no taps
+        acc[0] += tile[(ty * OC_I + tx) * OC_PS];
+#else
+#pragma unroll
+        for (int tap = 0; tap < 9; ++tap) {
+            const int dy = tap / 3, dx = tap - dy * 3;
+            const float* px = &tile[((ty + dy) * OC_I + tx + dx) * OC_PS];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const f32x4 v = *reinterpret_cast<const f32x4*>(px + q * 4);
+                if constexpr (IC > 0) {
+#pragma unroll
+                    for (int oc = 0; oc < IC; ++oc) {
+                        // uniform address: scalar loads, the weights are SGPR operands (no LDS read, no register)
+                        const f32x4 wv = *reinterpret_cast<const f32x4*>(wglob + (((oc * 9 + tap) * (C >> 4)) << 4) + c0 + q * 4);
+                        acc[oc] = __builtin_fmaf(v.x, wv.x, __builtin_fmaf(v.y, wv.y, __builtin_fmaf(v.z, wv.z, __builtin_fmaf(v.w, wv.w, acc[oc]))));
+                    }
+                } else {
+                    for (int oc = 0; oc < ic; ++oc) {
+                        const f32x4 wv = *reinterpret_cast<const f32x4*>(&wl[(oc * 9 + tap) * C + c0 + q * 4]);
+                        acc[oc] += v.x * wv.x + v.y * wv.y + v.z * wv.z + v.w * wv.w;
+                    }
+                }
+            }
+        }
+#endif
+    }
+    const int oy = oy0 + ty, ox = ox0 + tx;
+    if (oy >= a.H || ox >= a.W) return;
+#pragma unroll
+    for (int oc = 0; oc < (IC ? IC : 4); ++oc) {
+        if (oc >= ic) break;
+        const size_t o = (((size_t)b * ic + oc) * a.H + oy) * a.W + ox;
+        float eps = acc[oc] + a.bias[oc];
+        if (a.eps_out) a.eps_out[o] = eps;
+        if (a.x) {
+            const float c1 = a.c1, c2 = a.c2, c3 = a.c3;
+            const float* noise = a.noise;
+            // x <- clamp( (1/sqrt(alpha)) * (x - ((1-alpha)/sqrt(1-alpha_hat)) * eps) [+ sqrt(beta)*noise], 0, 1 )
+            // evaluated with the reference's operation order and no fused multiply-add.
+            if (a.clamp_eps) eps = fminf(fmaxf(eps, -5.0f), 5.0f);
+            float xn = __fmul_rn(c1, __fsub_rn(a.x[o], __fmul_rn(c2, eps)));
+            if constexpr (MIDD_OUT_SEEDED) {
+                // element index inside the sample's [ic,H,W] block (the host refuses ic*H*W >= 2^32)
+                const uint32_t elem = (uint32_t)(((size_t)oc * a.H + oy) * a.W + ox);
+                xn = __fadd_rn(xn, __fmul_rn(c3, step_noise_value(a.seed, a.sample_offset + b, a.iter, elem)));
+            } else {
+                if (noise) xn = __fadd_rn(xn, __fmul_rn(c3, noise[o]));
+            }
+            a.x[o] = fminf(fmaxf(xn, 0.0f), 1.0f);
+        }
+    }
+}

@@ -226,8 +226,16 @@ class UNetDiffusion(nn.Module):
     @torch.no_grad()
     def run_sampler(self, noisy: torch.Tensor, t_list, beta: torch.Tensor, alpha: torch.Tensor,
                     alpha_hat: torch.Tensor, clamp_eps: bool, step_noise: Optional[torch.Tensor] = None,
-                    no_split: bool = False) -> torch.Tensor:
-        """The whole reverse loop in one native call (used by DiffusionDenoiser.denoise)."""
+                    no_split: bool = False, seed: Optional[int] = None, sample_offset: int = 0) -> torch.Tensor:
+        """The whole reverse loop in one native call (used by DiffusionDenoiser.denoise).
+
+        seed: the noise term of every t > 0 update is drawn on the device from (seed, sample_offset + b, iteration, element)
+        (mi_denoise_seeded) instead of read from ``step_noise``; the two are exclusive."""
+        if seed is not None:
+            if step_noise is not None:
+                raise ValueError("pass either seed or step_noise, not both")
+            from .sampler import check_seed
+            seed, sample_offset = check_seed(seed, sample_offset)
         self._check_image(noisy, "noisy_img")
         B, _, H, W = noisy.shape
         steps = np.ascontiguousarray(np.asarray(list(t_list), dtype=np.int32))
@@ -249,11 +257,14 @@ class UNetDiffusion(nn.Module):
             wptr, wbytes = self._aligned_ptr(ws)
             stream = torch.cuda.current_stream(noisy.device).cuda_stream
             fp = C.POINTER(C.c_float)
-            native.check(native.lib().mi_denoise(
-                plan, src.data_ptr(), out.data_ptr(), B, H, W,
-                steps.ctypes.data_as(C.POINTER(C.c_int32)), len(steps),
-                tabs[0].ctypes.data_as(fp), tabs[1].ctypes.data_as(fp), tabs[2].ctypes.data_as(fp), noise_steps,
-                nptr, (native.MI_CLAMP_EPS if clamp_eps else 0) | (native.MI_NO_SPLIT if no_split else 0), wptr, wbytes, stream))
+            head = (plan, src.data_ptr(), out.data_ptr(), B, H, W,
+                    steps.ctypes.data_as(C.POINTER(C.c_int32)), len(steps),
+                    tabs[0].ctypes.data_as(fp), tabs[1].ctypes.data_as(fp), tabs[2].ctypes.data_as(fp), noise_steps)
+            tail = ((native.MI_CLAMP_EPS if clamp_eps else 0) | (native.MI_NO_SPLIT if no_split else 0), wptr, wbytes, stream)
+            if seed is not None:
+                native.check(native.lib().mi_denoise_seeded(*head, C.c_uint64(seed), C.c_int64(sample_offset), *tail))
+            else:
+                native.check(native.lib().mi_denoise(*head, nptr, *tail))
             self._raise_on_status(wptr, stream)
         return out
 

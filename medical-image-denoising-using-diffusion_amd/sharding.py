@@ -2,7 +2,11 @@
 
 The reference is single-device; the path shards trivially because
 images never interact: GroupNorm and attention are per sample (DDIMModel.py:116,146), ``t`` is
-the same for the whole batch (:275) and the DDIM variant draws no random numbers.  Rank r of W
+the same for the whole batch (:275) and the DDIM variant draws no random numbers.  The stochastic
+cddpm variant shards too when it is SEEDED: ``denoise(..., seed=s, sample_offset=lo)`` draws a
+sample's noise from its global index (``denoise_sharded(..., pass_offset=True)`` hands every rank
+its ``lo``), so the gathered batch is the single-GPU one (bit for bit with ``batch_invariant=True``).
+Unseeded, every rank draws from its own torch generator and the run is not reproducible.  Rank r of W
 takes the contiguous block ``[r*B/W, (r+1)*B/W)``, runs every step with zero communication,
 and ONE all-gather (RCCL over xGMI when the backend is "nccl") collects the outputs.
 """
@@ -35,10 +39,15 @@ def gather_outputs(local: torch.Tensor, group: Optional[dist.ProcessGroup] = Non
     return full
 
 
-def denoise_sharded(denoise_fn: Callable[[torch.Tensor], torch.Tensor], noisy_full: torch.Tensor,
-                    group: Optional[dist.ProcessGroup] = None) -> torch.Tensor:
-    """Every rank holds the full batch; each denoises its block, one all-gather at the end."""
+def denoise_sharded(denoise_fn: Callable[..., torch.Tensor], noisy_full: torch.Tensor,
+                    group: Optional[dist.ProcessGroup] = None, pass_offset: bool = False) -> torch.Tensor:
+    """Every rank holds the full batch; each denoises its block, one all-gather at the end.
+
+    pass_offset: ``denoise_fn`` is also given ``sample_offset=lo``, the global index of its block's first image (0 without
+    a process group) -- what a seeded cddpm run needs, e.g.
+    ``lambda x, sample_offset: d.denoise(x, 50, seed=s, sample_offset=sample_offset)``."""
     if not (dist.is_available() and dist.is_initialized()):
-        return denoise_fn(noisy_full)
+        return denoise_fn(noisy_full, sample_offset=0) if pass_offset else denoise_fn(noisy_full)
     lo, hi = shard_bounds(noisy_full.shape[0], dist.get_world_size(group), dist.get_rank(group))
-    return gather_outputs(denoise_fn(noisy_full[lo:hi]), group)
+    local = denoise_fn(noisy_full[lo:hi], sample_offset=lo) if pass_offset else denoise_fn(noisy_full[lo:hi])
+    return gather_outputs(local, group)
