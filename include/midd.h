@@ -140,11 +140,13 @@ int mi_denoise(mi_plan* plan, const float* noisy, float* x_out, int B, int H, in
  *   sample_offset  global index of sample 0 of this call (>= 0): a caller that splits a batch over calls, streams or GPUs passes
  *                  each part its offset and gets the noise the whole batch would have got, bit for bit.  The two-stream split
  *                  inside the call does the same (sub-batch h of `parts` passes sample_offset + h * B / parts).
- * Every value is a pure function of (seed, global sample index, iteration index i, element index): it does not depend on B,
- * on MI_NO_SPLIT, on the stream or on the device.  THE SPECIFICATION (fixed):
+ * Every value is a pure function of (seed, global sample index, iteration index i, element index, member index): it does not
+ * depend on B, on MI_NO_SPLIT, on the stream or on the device.  THE SPECIFICATION (fixed):
  *   Philox4x32-10 as in Random123: multipliers 0xD2511F53, 0xCD9E8D57; key increments 0x9E3779B9, 0xBB67AE85; ten rounds
  *   counter  c0 = element index inside the sample's [C,H,W] block (C*H*W < 2^32, else MI_EINVAL), c1 = low 32 bits of
- *            sample_offset + b, c2 = i (position in t_list), c3 = 0 (reserved: stream id);   key  k0, k1 = low, high word of seed
+ *            sample_offset + b (the global IMAGE index), c2 = i (position in t_list), c3 = member index; 0 for mi_denoise_seeded
+ *            (mi_denoise_ensemble numbers the draws of one image member_offset, member_offset + 1, ...);
+ *            key  k0, k1 = low, high word of seed
  *   one Philox call per element, outputs x0 and x1 used:
  *   u1 = ((x0 >> 8) + 1) * 2^-24 in (0, 1],   u2 = (x1 >> 8) * 2^-24 in [0, 1)   (exact in fp32)
  *   z  = sqrtf(-2 * logf(u1)) * cospif(2 * u2)   (accurate fp32 library functions, each product rounded once; |z| <= 5.77)
@@ -162,6 +164,59 @@ int mi_denoise_seeded(mi_plan* plan, const float* noisy, float* x_out, int B, in
  * by mi_denoise).  MI_EINVAL: sample_offset < 0, C*H*W >= 2^32, B or n_iters > 65535.  Asynchronous on `stream`. */
 int mi_step_noise_fill(float* dst, int n_iters, int B, int C, int H, int W,
                        uint64_t seed, int64_t sample_offset, void* stream);
+/* The same for ensemble member `member` (0 <= member < 2^32, else MI_EINVAL) of every image: counter word c3 = member.
+ * member == 0 is mi_step_noise_fill.  mi_denoise with this tensor replays member `member` of mi_denoise_ensemble. */
+int mi_step_noise_fill_member(float* dst, int n_iters, int B, int C, int H, int W,
+                              uint64_t seed, int64_t sample_offset, int64_t member, void* stream);
+
+/* ENSEMBLES of the stochastic (cddpm) sampler: `members` seeded draws per image in one call, their per-pixel mean and
+ * unbiased standard deviation (the reference returns one draw, cddpmModels.py:281-308; a caller who wants several loops).
+ * A "virtual sample" is one (image b, member m) pair; the virtual batch is image-major, v = b * members + m, so the member
+ * outputs [B,members,C,H,W] ARE the virtual batch.  Virtual sample v draws the step noise of the specification above with
+ *   global image index  sample_offset + v / members        (counter word c1)
+ *   member index        member_offset + v % members        (counter word c3)
+ * so member 0 of image b is what mi_denoise_seeded computes for that image, and -- with a batch-invariant plan -- every member
+ * output is a function of (seed, image, member) alone: not of B, members, pass_samples or the stream.
+ * The B * members virtual samples run through mi_denoise's sampler loop in passes of at most pass_samples consecutive virtual
+ * samples (the last pass may be shorter); each pass is split over two streams as a mi_denoise batch of that size is.  One
+ * reduce launch (mi_ensemble_reduce) follows the last pass.
+ *   noisy        device fp32 [B,C,H,W]; never written
+ *   mean_out     device fp32 [B,C,H,W] or NULL
+ *   std_out      device fp32 [B,C,H,W] or NULL; needs members >= 2
+ *   samples_out  device fp32 [B,members,C,H,W] or NULL: the member outputs (NULL: they live in the workspace)
+ *   seed, sample_offset   as mi_denoise_seeded (sample_offset counts IMAGES)
+ *   member_offset  member index of member 0 of this call.  members == 1, member_offset = m, samples_out = x, mean_out =
+ *                std_out = NULL is "run member m only": the single-member form
+ *   pass_samples  virtual samples per pass (>= 1); the workspace grows with it (mi_ensemble_workspace_bytes)
+ *   flags        as mi_denoise (MI_NO_SPLIT: every pass as one program)
+ * MI_EINVAL before any GPU work, with the limit named in mi_last_error: members < 1; member_offset < 0; member_offset +
+ * members > 2^32 (4294967296: the member index is one 32-bit counter word); pass_samples < 1; no output pointer; std_out with
+ * members < 2; any two of noisy, mean_out, std_out, samples_out overlapping; sample_offset < 0; C*H*W >= 2^32; B > 65535 or B * members > 2^31 - 1 (2147483647:
+ * grid of the reduce kernel, 32-bit virtual index).
+ * The status word (mi_status) is cleared once per call and accumulates over the passes.  Allocates nothing; asynchronous. */
+int mi_denoise_ensemble(mi_plan* plan, const float* noisy, float* mean_out, float* std_out, float* samples_out,
+                        int B, int members, int H, int W,
+                        const int32_t* t_list, int n_iters,
+                        const float* beta, const float* alpha, const float* alpha_hat, int noise_steps,
+                        uint64_t seed, int64_t sample_offset, int64_t member_offset, int pass_samples, int flags,
+                        void* workspace, size_t workspace_bytes, void* stream);
+
+/* Bytes of workspace mi_denoise_ensemble needs: the sampler workspace of a pass (>= mi_workspace_bytes of pass_samples
+ * virtual samples) + the pass's condition images + -- unless samples_external != 0, i.e. samples_out is given -- the member
+ * outputs, B * members * C*H*W * 4 bytes.  Host only, and answered from the planner alone: it works before mi_unet_finalize
+ * too.  0 on bad arguments (mi_last_error says which). */
+size_t mi_ensemble_workspace_bytes(mi_plan* plan, int B, int members, int H, int W, int pass_samples, int samples_external);
+
+/* The reduction of mi_denoise_ensemble on its own (no plan needed; a caller who gathered members from several GPUs reduces
+ * them with the same arithmetic): samples device fp32 [B,members,chw] -> mean_out [B,chw] and, if not NULL, std_out [B,chw]
+ * (members >= 2).  THE ARITHMETIC (fixed, per pixel, independent of the launch geometry): in double precision, every operation
+ * rounded to nearest on its own, no fused multiply-add,
+ *   s = 0; for m = 0 .. members-1: s += (double)x[m];      mean64 = s / members
+ *   q = 0; for m = 0 .. members-1: d = (double)x[m] - mean64; q += d * d
+ *   mean = (float)mean64        std = (float)sqrt(q / (members - 1))       (unbiased)
+ * MI_EINVAL: B outside [1, 65535], members < 1, chw outside [1, 2^32), null samples / mean_out, std_out with members < 2.
+ * samples, mean_out and std_out must not overlap (the kernel reads the samples while it writes the other two). */
+int mi_ensemble_reduce(const float* samples, int B, int members, int64_t chw, float* mean_out, float* std_out, void* stream);
 
 /* Status of the last mi_unet_forward / mi_denoise call that used `workspace` (its first word; the calls clear it when they
  * start).  SYNCHRONISES `stream` (one 4-byte device-to-host copy).  Returns MI_OK with *flags == 0, or MI_ERANGE with the

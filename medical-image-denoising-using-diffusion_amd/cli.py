@@ -5,7 +5,7 @@
 img_size -> sampler -> uint8 -> bicubic resize back -> PNG, with the reference's timing print.
 
     python -m midd_amd.cli --image in.png --out out.png [--checkpoint ckpt.pth] [--variant cddpm|ddim]
-                           [--img-size 512] [--inference-steps 25] [--seed N]
+                           [--img-size 512] [--inference-steps 25] [--seed N] [--samples K [--std-out std.npy]]
 
 Without a checkpoint (the trained weights are not distributed with the reference) the network is
 random-init, which exercises the path but does not denoise.  The reference helper has a latent
@@ -29,10 +29,20 @@ from .sampler import DiffusionDenoiser
 def denoise_image_diffusion(model_path: Optional[str], test_image_path: str, device_type: str = "cuda",
                             img_size: int = 512, inference_steps: int = 50, variant: str = "cddpm",
                             step_noise: Optional[torch.Tensor] = None, compute: Optional[str] = None,
-                            seed: Optional[int] = None) -> Image.Image:
+                            seed: Optional[int] = None, samples: Optional[int] = None,
+                            std_out: Optional[str] = None) -> Image.Image:
     """compute (not a reference argument): arithmetic of the network, see UNetDiffusion -- None keeps the default.
     seed (not a reference argument; cddpm): the stochastic sampler's noise is drawn on the device from this seed, so the same
-    call gives the same image again (DiffusionDenoiser.denoise); None: torch.randn, as the reference."""
+    call gives the same image again (DiffusionDenoiser.denoise); None: torch.randn, as the reference.
+    samples (not a reference argument; cddpm): the returned image is the MEAN of this many seeded draws
+    (DiffusionDenoiser.denoise_ensemble; seed None: a seed is drawn and printed) through the same recipe; std_out: path of a
+    .npy file that receives their per-pixel standard deviation, float32 [img_size, img_size] (needs samples >= 2)."""
+    if samples is not None and variant != "cddpm":
+        raise ValueError("--samples needs the stochastic (cddpm) variant: a deterministic sampler has no ensemble")
+    if std_out is not None and (samples is None or samples < 2):
+        raise ValueError("--std-out needs --samples K with K >= 2")
+    if samples is not None and step_noise is not None:
+        raise ValueError("samples draws its noise from the seed: step_noise cannot be given as well")
     device = torch.device(device_type)
     model = UNetDiffusion(in_channels=1, model_channels=48, channel_mult=(1, 2, 3, 4), num_res_blocks=2,
                           attention_resolutions=(3,), dropout=0.0, time_emb_dim=192, variant=variant, compute=compute)
@@ -58,7 +68,14 @@ def denoise_image_diffusion(model_path: Optional[str], test_image_path: str, dev
     kw = {"step_noise": step_noise} if step_noise is not None else {}
     if seed is not None:
         kw["seed"] = seed
-    denoised = diffusion.denoise(input_tensor, inference_steps=inference_steps, **kw)
+    if samples is not None:
+        ens = diffusion.denoise_ensemble(input_tensor, inference_steps=inference_steps, members=samples, seed=seed)
+        denoised = ens.mean                               # a mean of values in [0, 1]: in [0, 1]
+        print(f"Ensemble of {samples} samples, seed {ens.seed}")
+        if std_out is not None:
+            np.save(std_out, ens.std.reshape(img_size, img_size).cpu().numpy())
+    else:
+        denoised = diffusion.denoise(input_tensor, inference_steps=inference_steps, **kw)
     if device.type == "cuda":
         torch.cuda.synchronize(device)
     print(f"Inference time: {time.time() - start_time:.2f} seconds")
@@ -82,9 +99,18 @@ def main(argv=None) -> None:
     ap.add_argument("--device", default="cuda")
     ap.add_argument("--seed", type=int, default=None,
                     help="cddpm: draw the sampler's noise on the device from this seed (reproducible); default: torch.randn")
+    ap.add_argument("--samples", type=int, default=None,
+                    help="cddpm: save the mean of this many seeded samples of the image (with --seed: reproducible)")
+    ap.add_argument("--std-out", default=None, metavar="PATH.npy",
+                    help="with --samples K >= 2: write the per-pixel standard deviation of the samples (float32, model resolution)")
     args = ap.parse_args(argv)
+    if args.samples is not None and (args.samples < 1 or args.variant != "cddpm"):
+        ap.error("--samples needs K >= 1 and --variant cddpm")
+    if args.std_out is not None and (args.samples is None or args.samples < 2):
+        ap.error("--std-out needs --samples K with K >= 2")
     restored = denoise_image_diffusion(args.checkpoint, args.image, device_type=args.device, img_size=args.img_size,
-                                       inference_steps=args.inference_steps, variant=args.variant, seed=args.seed)
+                                       inference_steps=args.inference_steps, variant=args.variant, seed=args.seed,
+                                       samples=args.samples, std_out=args.std_out)
     restored.save(args.out, quality=95)
     print(f"\nResult saved: {args.out}")
 

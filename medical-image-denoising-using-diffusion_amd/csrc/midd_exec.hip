@@ -6,9 +6,10 @@ using namespace midd;
 struct StepIO {
     const float* x; const float* cond; float* eps_out;
     float* x_update; const float* noise; float c1, c2, c3; int clamp_eps;
-    // seeded != 0: the update draws its noise term (step_noise_common.h) for iteration `iter`, sample 0 of this program being
-    // global sample `sample_offset`
-    int seeded; int iter; uint64_t seed; int64_t sample_offset;
+    // seeded != 0: the update draws its noise term (step_noise_common.h) for iteration `iter`; sample 0 of this program is
+    // virtual sample `v0` of a call whose image 0 is global image `sample_offset`, with `members` draws per image numbered from
+    // `member_offset` (OutConvArgs, midd_internal.h)
+    int seeded; int iter; uint64_t seed; int64_t sample_offset; int v0; int members; uint32_t member_offset;
 };
 
 // status: the call's status word (first word of the CALLER's workspace, whichever sub-batch program runs)
@@ -111,6 +112,7 @@ static int run_program(mi_plan* p, Program* g, const StepIO& io, char* ws, int* 
                 a.eps_out = io.eps_out; a.x = io.x_update; a.noise = io.noise;
                 a.c1 = io.c1; a.c2 = io.c2; a.c3 = io.c3; a.clamp_eps = io.clamp_eps;
                 a.seeded = io.seeded; a.iter = io.iter; a.seed = io.seed; a.sample_offset = io.sample_offset;
+                a.v0 = io.v0; a.members = io.members > 0 ? io.members : 1; a.member_offset = io.member_offset;
                 e = out_conv_launch(a, s);
                 break;
             }
@@ -139,15 +141,30 @@ static int run_program(mi_plan* p, Program* g, const StepIO& io, char* ws, int* 
     return MI_OK;
 }
 
+static int check_device(mi_plan* plan) {
+    int dev = -1;
+    if (hipGetDevice(&dev) != hipSuccess || dev != plan->device)
+        return fail(MI_ESTATE, "plan was finalized on device %d but current device is %d", plan->device, dev);
+    return MI_OK;
+}
+
 static int check_call(mi_plan* plan, int B, int H, int W, void* ws, size_t ws_bytes, Program** g) {
     if (!plan) return fail(MI_EINVAL, "null plan");
     int rc = get_program(plan, B, H, W, g);
     if (rc) return rc;
     if (!ws || ws_bytes < (*g)->bytes) return fail(MI_ENOMEM, "workspace too small: need %zu bytes, got %zu", (*g)->bytes, ws_bytes);
     if (((uintptr_t)ws) & 255) return fail(MI_EINVAL, "workspace must be 256-byte aligned");
-    int dev = -1;
-    if (hipGetDevice(&dev) != hipSuccess || dev != plan->device)
-        return fail(MI_ESTATE, "plan was finalized on device %d but current device is %d", plan->device, dev);
+    return check_device(plan);
+}
+
+// the sampler's host-side arguments (mi_denoise*, and mi_denoise_ensemble before its first pass)
+static int check_schedule(mi_plan* plan, const int32_t* t_list, int n_iters, const float* beta, const float* alpha, const float* alpha_hat,
+                          int noise_steps) {
+    if ((n_iters > 0 && !t_list) || !beta || !alpha || !alpha_hat) return fail(MI_EINVAL, "null argument");
+    if (n_iters < 0 || noise_steps < 1 || noise_steps > plan->time_rows)
+        return fail(MI_EINVAL, "noise_steps %d exceeds the precomputed time table (%d rows)", noise_steps, plan->time_rows);
+    for (int i = 0; i < n_iters; ++i)
+        if (t_list[i] < 0 || t_list[i] >= noise_steps) return fail(MI_EINVAL, "t_list[%d]=%d outside [0,%d)", i, t_list[i], noise_steps);
     return MI_OK;
 }
 
@@ -169,28 +186,37 @@ extern "C" int mi_unet_forward(mi_plan* plan, const float* x, const float* condi
     return run_program(plan, g, io, ws, reinterpret_cast<int*>(ws), s);
 }
 
-// The noise term of the cddpm update: none, a caller's tensor (mi_denoise), or drawn in the update (mi_denoise_seeded)
-struct StepNoise { const float* tensor = nullptr; bool seeded = false; uint64_t seed = 0; int64_t sample_offset = 0; };
+// The noise term of the cddpm update: none, a caller's tensor (mi_denoise), or drawn in the update (mi_denoise_seeded,
+// mi_denoise_ensemble).  Seeded: the B samples of the run are the virtual samples v0 .. v0 + B - 1 of an image-major
+// (image, member) batch with `members` draws per image; a plain seeded run is members = 1, v0 = 0.
+struct StepNoise {
+    const float* tensor = nullptr; bool seeded = false; uint64_t seed = 0; int64_t sample_offset = 0;
+    int v0 = 0; int members = 1; uint32_t member_offset = 0;
+};
 
-static int denoise_run(mi_plan* plan, const float* noisy, float* x_out, int B, int H, int W,
-                       const int32_t* t_list, int n_iters,
-                       const float* beta, const float* alpha, const float* alpha_hat, int noise_steps,
-                       const StepNoise& sn, int flags,
-                       void* workspace, size_t workspace_bytes, void* stream) {
-    Program* g = nullptr;
-    int rc = check_call(plan, B, H, W, workspace, workspace_bytes, &g);
+// One batch through the sampler loop, in two steps: check_run judges the arguments (no GPU work), enqueue_run enqueues the
+// batch.  enqueue_run neither takes the plan's side-stream mutex nor clears the status word: its caller does both, once per
+// C call -- denoise_run for mi_denoise / mi_denoise_seeded, mi_denoise_ensemble once for all its passes, so that the word
+// accumulates over them.
+static int check_run(mi_plan* plan, const float* noisy, const float* x_out, int B, int H, int W,
+                     const int32_t* t_list, int n_iters, const float* beta, const float* alpha, const float* alpha_hat, int noise_steps,
+                     void* workspace, size_t workspace_bytes, Program** g) {
+    int rc = check_call(plan, B, H, W, workspace, workspace_bytes, g);
     if (rc) return rc;
-    if (!noisy || !x_out || (n_iters > 0 && !t_list) || !beta || !alpha || !alpha_hat) return fail(MI_EINVAL, "null argument");
+    if (!noisy || !x_out) return fail(MI_EINVAL, "null argument");
+    if ((rc = check_schedule(plan, t_list, n_iters, beta, alpha, alpha_hat, noise_steps))) return rc;
     if (noisy == x_out) return fail(MI_EINVAL, "x_out must not alias noisy (the condition image is read every step)");
-    if (n_iters < 0 || noise_steps < 1 || noise_steps > plan->time_rows)
-        return fail(MI_EINVAL, "noise_steps %d exceeds the precomputed time table (%d rows)", noise_steps, plan->time_rows);
-    for (int i = 0; i < n_iters; ++i)
-        if (t_list[i] < 0 || t_list[i] >= noise_steps) return fail(MI_EINVAL, "t_list[%d]=%d outside [0,%d)", i, t_list[i], noise_steps);
+    return MI_OK;
+}
+
+// (the caller holds plan->side_mu and has cleared the status word at the head of `workspace`)
+static int enqueue_run(mi_plan* plan, Program* g, const float* noisy, float* x_out, int B, int H, int W,
+                       const int32_t* t_list, int n_iters, const float* beta, const float* alpha, const float* alpha_hat,
+                       const StepNoise& sn, int flags, void* workspace, size_t workspace_bytes, void* stream) {
+    int rc = MI_OK;
     hipStream_t s = (hipStream_t)stream;
     char* ws = (char*)workspace;
     const size_t img_elems = (size_t)B * plan->cfg.in_channels * H * W;
-    std::lock_guard<std::mutex> side_lk(plan->side_mu);      // the side streams and their events are per plan: one enqueue at a time
-    HIPCHK(hipMemsetAsync(ws, 0, 256, s));                  // status word (before the side streams fork)
     HIPCHK(hipMemcpyAsync(x_out, noisy, img_elems * sizeof(float), hipMemcpyDeviceToDevice, s));   // x = noisy_img.clone()
     // Images are independent: the batch runs as `parts` sub-batches on as many streams, each started
     // 1/parts of a forward after the previous one, so that one part's latency-bound low-resolution
@@ -235,7 +261,8 @@ static int denoise_run(mi_plan* plan, const float* noisy, float* x_out, int B, i
                 io.noise = (sn.tensor && t > 0) ? sn.tensor + (size_t)i * img_elems + h * part : nullptr;      // cddpmModels.py:297-300
                 if (sn.seeded && t > 0) {                        // nothing is drawn at t == 0
                     io.seeded = 1; io.iter = i; io.seed = sn.seed;
-                    io.sample_offset = sn.sample_offset + (int64_t)h * (B / parts);
+                    io.sample_offset = sn.sample_offset; io.v0 = sn.v0 + h * (B / parts);      // sub-batch h: its first virtual index
+                    io.members = sn.members; io.member_offset = sn.member_offset;
                 }
                 io.clamp_eps = (flags & MI_CLAMP_EPS) ? 1 : 0;
                 if (i == 0 && h > 0) HIPCHK(hipStreamWaitEvent(sh, plan->sev_phase[h - 1], 0));      // phase offset (re-establishing it every n-th
@@ -257,6 +284,20 @@ static int denoise_run(mi_plan* plan, const float* noisy, float* x_out, int B, i
         }
     }
     return rc;
+}
+
+// a sampler call of its own: arguments, the plan's side-stream mutex, the status word, the batch
+static int denoise_run(mi_plan* plan, const float* noisy, float* x_out, int B, int H, int W,
+                       const int32_t* t_list, int n_iters,
+                       const float* beta, const float* alpha, const float* alpha_hat, int noise_steps,
+                       const StepNoise& sn, int flags,
+                       void* workspace, size_t workspace_bytes, void* stream) {
+    Program* g = nullptr;
+    if (int rc = check_run(plan, noisy, x_out, B, H, W, t_list, n_iters, beta, alpha, alpha_hat, noise_steps, workspace, workspace_bytes, &g))
+        return rc;
+    std::lock_guard<std::mutex> side_lk(plan->side_mu);      // the side streams and their events are per plan: one enqueue at a time
+    HIPCHK(hipMemsetAsync(workspace, 0, 256, (hipStream_t)stream));      // status word (before the side streams fork)
+    return enqueue_run(plan, g, noisy, x_out, B, H, W, t_list, n_iters, beta, alpha, alpha_hat, sn, flags, workspace, workspace_bytes, stream);
 }
 
 extern "C" int mi_denoise(mi_plan* plan, const float* noisy, float* x_out, int B, int H, int W,
@@ -294,14 +335,119 @@ extern "C" int mi_denoise_seeded(mi_plan* plan, const float* noisy, float* x_out
                        workspace, workspace_bytes, stream);
 }
 
-extern "C" int mi_step_noise_fill(float* dst, int n_iters, int B, int C, int H, int W,
-                                  uint64_t seed, int64_t sample_offset, void* stream) {
+extern "C" int mi_step_noise_fill_member(float* dst, int n_iters, int B, int C, int H, int W,
+                                         uint64_t seed, int64_t sample_offset, int64_t member, void* stream) {
     if (int rc = check_step_noise_range(C, H, W, sample_offset)) return rc;
+    if (member < 0 || member >= ((int64_t)1 << 32))
+        return fail(MI_EINVAL, "member %lld outside [0, 2^32): the member index is one 32-bit counter word (limit: member < 4294967296)", (long long)member);
     if (n_iters < 0 || B < 0 || n_iters > 65535 || B > 65535) return fail(MI_EINVAL, "n_iters %d / B %d outside [0, 65535]", n_iters, B);
     if (n_iters == 0 || B == 0) return MI_OK;
     if (!dst) return fail(MI_EINVAL, "null argument");
-    const hipError_t e = step_noise_fill_launch(dst, n_iters, B, (unsigned long long)C * H * W, seed, sample_offset, (hipStream_t)stream);
+    const hipError_t e = step_noise_fill_launch(dst, n_iters, B, (unsigned long long)C * H * W, seed, sample_offset, (uint32_t)member, (hipStream_t)stream);
     if (e != hipSuccess) return fail(MI_EHIP, "step_noise_fill: %s", hipGetErrorString(e));
+    return MI_OK;
+}
+
+extern "C" int mi_step_noise_fill(float* dst, int n_iters, int B, int C, int H, int W,
+                                  uint64_t seed, int64_t sample_offset, void* stream) {
+    return mi_step_noise_fill_member(dst, n_iters, B, C, H, W, seed, sample_offset, 0, stream);
+}
+
+// ---------------------------------------------------------------------------- ensembles of the stochastic sampler
+constexpr int64_t MEMBER_WORDS = (int64_t)1 << 32;      // the member index is one 32-bit counter word
+
+static int check_members(int members, int64_t member_offset) {
+    if (members < 1) return fail(MI_EINVAL, "members %d: an ensemble has at least one member (limit: members >= 1)", members);
+    if (member_offset < 0) return fail(MI_EINVAL, "member_offset %lld is negative: member indices start at 0", (long long)member_offset);
+    if (member_offset > MEMBER_WORDS - members)
+        return fail(MI_EINVAL, "member_offset %lld + members %d exceeds 2^32: the member index of the seeded step noise is one 32-bit "
+                    "counter word (limit: member_offset + members <= 4294967296)", (long long)member_offset, members);
+    return MI_OK;
+}
+
+// B images x members draws: what the reduce kernel's grid (B in grid.y) and the 32-bit virtual index can hold
+static int check_ensemble_size(int B, int members) {
+    if (B < 1 || B > 65535) return fail(MI_EINVAL, "B %d outside [1, 65535] (limit of the reduce kernel's grid)", B);
+    if ((int64_t)B * members > 2147483647ll)
+        return fail(MI_EINVAL, "B * members = %d * %d exceeds 2^31 - 1: the virtual sample index is a 32-bit int (limit: B * members <= 2147483647)", B, members);
+    return MI_OK;
+}
+
+int midd::check_ensemble_args(mi_plan* plan, int B, int members, int H, int W, int64_t sample_offset, int64_t member_offset, int pass_samples) {
+    if (!plan) return fail(MI_EINVAL, "null plan");
+    if (int rc = check_members(members, member_offset)) return rc;
+    if (pass_samples < 1) return fail(MI_EINVAL, "pass_samples %d: a pass holds at least one virtual sample (limit: pass_samples >= 1)", pass_samples);
+    if (int rc = check_ensemble_size(B, members)) return rc;
+    return check_step_noise_range(plan->cfg.in_channels, H, W, sample_offset);
+}
+
+extern "C" int mi_ensemble_reduce(const float* samples, int B, int members, int64_t chw, float* mean_out, float* std_out, void* stream) {
+    if (members < 1) return fail(MI_EINVAL, "members %d: an ensemble has at least one member (limit: members >= 1)", members);
+    if (B < 1 || B > 65535) return fail(MI_EINVAL, "B %d outside [1, 65535] (limit of the reduce kernel's grid)", B);
+    if (chw < 1 || chw >= MEMBER_WORDS) return fail(MI_EINVAL, "chw %lld outside [1, 2^32) (limit: C*H*W < 4294967296)", (long long)chw);
+    if (std_out && members < 2) return fail(MI_EINVAL, "std_out needs members >= 2: the unbiased standard deviation of one value is undefined");
+    if (!samples || !mean_out) return fail(MI_EINVAL, "null argument");
+    const hipError_t e = ensemble_reduce_launch(samples, B, members, (unsigned long long)chw, mean_out, std_out, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(MI_EHIP, "ensemble_reduce: %s", hipGetErrorString(e));
+    return MI_OK;
+}
+
+extern "C" int mi_denoise_ensemble(mi_plan* plan, const float* noisy, float* mean_out, float* std_out, float* samples_out,
+                                   int B, int members, int H, int W,
+                                   const int32_t* t_list, int n_iters,
+                                   const float* beta, const float* alpha, const float* alpha_hat, int noise_steps,
+                                   uint64_t seed, int64_t sample_offset, int64_t member_offset, int pass_samples, int flags,
+                                   void* workspace, size_t workspace_bytes, void* stream) {
+    if (int rc = check_ensemble_args(plan, B, members, H, W, sample_offset, member_offset, pass_samples)) return rc;
+    if (!mean_out && !std_out && !samples_out) return fail(MI_EINVAL, "no output: give at least one of mean_out, std_out, samples_out");
+    if (std_out && members < 2) return fail(MI_EINVAL, "std_out needs members >= 2: the unbiased standard deviation of one value is undefined");
+    {   // noisy is read every step and the reduce reads the samples while it writes mean and std: no two of the four may overlap
+        const size_t img = (size_t)plan->cfg.in_channels * H * W * sizeof(float);
+        const struct { const void* p; size_t n; const char* name; } buf[4] = {
+            {noisy, (size_t)B * img, "noisy"}, {mean_out, (size_t)B * img, "mean_out"}, {std_out, (size_t)B * img, "std_out"},
+            {samples_out, (size_t)B * members * img, "samples_out"}};
+        for (int i = 0; i < 4; ++i)
+            for (int j = i + 1; j < 4; ++j) {
+                const uintptr_t a = (uintptr_t)buf[i].p, b = (uintptr_t)buf[j].p;
+                if (a && b && a < b + buf[j].n && b < a + buf[i].n)
+                    return fail(MI_EINVAL, "%s and %s alias (overlap): noisy is read every step and the reduce reads samples_out while it "
+                                "writes mean_out and std_out", buf[i].name, buf[j].name);
+            }
+    }
+    if (!plan->finalized) return fail(MI_ESTATE, "mi_unet_finalize has not been called (or weights changed since)");
+    EnsembleLayout L{};
+    if (int rc = ensemble_layout(plan, B, members, H, W, pass_samples, samples_out != nullptr, &L)) return rc;
+    if (!workspace || workspace_bytes < L.bytes) return fail(MI_ENOMEM, "workspace too small: need %zu bytes, got %zu", L.bytes, workspace_bytes);
+    if (((uintptr_t)workspace) & 255) return fail(MI_EINVAL, "workspace must be 256-byte aligned");
+    if (!noisy) return fail(MI_EINVAL, "null argument");
+    // what a pass would refuse is refused here, before anything is enqueued
+    if (int rc = check_schedule(plan, t_list, n_iters, beta, alpha, alpha_hat, noise_steps)) return rc;
+    if (int rc = check_device(plan)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    char* ws = (char*)workspace;
+    const size_t chw = (size_t)plan->cfg.in_channels * H * W;
+    float* cond = reinterpret_cast<float*>(ws + L.cond_off);
+    float* samples = samples_out ? samples_out : reinterpret_cast<float*>(ws + L.samples_off);
+    const int64_t V = (int64_t)B * members;
+    std::lock_guard<std::mutex> side_lk(plan->side_mu);     // held over all passes: the side streams are per plan
+    HIPCHK(hipMemsetAsync(ws, 0, 256, s));                  // status word: once per call, the passes accumulate into it
+    StepNoise sn;
+    sn.seeded = true; sn.seed = seed; sn.sample_offset = sample_offset; sn.members = members; sn.member_offset = (uint32_t)member_offset;
+    for (int64_t v0 = 0; v0 < V; v0 += L.pass) {
+        const int n = (int)(V - v0 < L.pass ? V - v0 : L.pass);
+        const hipError_t e = ensemble_broadcast_launch(noisy, cond, (int)v0, n, members, chw, s);
+        if (e != hipSuccess) return fail(MI_EHIP, "ensemble_broadcast: %s", hipGetErrorString(e));
+        sn.v0 = (int)v0;
+        // (every pass joins its side streams before it returns, on success and on failure: enqueue_run)
+        Program* g = nullptr;
+        float* x = samples + (size_t)v0 * chw;
+        if (int rc = check_run(plan, cond, x, n, H, W, t_list, n_iters, beta, alpha, alpha_hat, noise_steps, ws, L.run_bytes, &g)) return rc;
+        if (int rc = enqueue_run(plan, g, cond, x, n, H, W, t_list, n_iters, beta, alpha, alpha_hat, sn, flags, ws, L.run_bytes, stream)) return rc;
+    }
+    if (mean_out || std_out) {
+        const hipError_t e = ensemble_reduce_launch(samples, B, members, chw, mean_out, std_out, s);
+        if (e != hipSuccess) return fail(MI_EHIP, "ensemble_reduce: %s", hipGetErrorString(e));
+    }
     return MI_OK;
 }
 

@@ -107,6 +107,11 @@ int get_program(mi_plan* p, int B, int H, int W, Program** out, bool side_by_sid
 int split_parts(int B);
 void op_work(mi_plan* p, Program* g, const Op& o, std::string* name, double* flops, double* bytes);
 int dump_program(mi_plan* p, int B, int H, int W, bool side_by_side, std::string* out);
+// mi_denoise_ensemble.  Layout of its workspace: [sampler workspace of a pass | condition images of a pass | member outputs
+// (unless the caller gives samples_out)]; pass = virtual samples per pass, tail = those of the last pass when it is shorter (else 0)
+struct EnsembleLayout { int pass, tail; size_t run_bytes, cond_off, samples_off, bytes; };
+int ensemble_layout(mi_plan* p, int B, int members, int H, int W, int pass_samples, bool samples_external, EnsembleLayout* L);   // midd_planner.hip
+int check_ensemble_args(mi_plan* p, int B, int members, int H, int W, int64_t sample_offset, int64_t member_offset, int pass_samples);   // midd_exec.hip
 }  // namespace midd
 
 struct mi_plan {

@@ -194,15 +194,27 @@ struct OutConvArgs {
     float c1, c2, c3;
     int clamp_eps;
     // seeded != 0 (needs x): the noise term is drawn in the update instead of read from `noise` (step_noise_common.h):
-    // value = f(seed, sample_offset + b, iter, element index inside the sample) -- out_conv_seeded_kernel
+    // value = f(seed, image, iter, element index inside the sample, member) -- out_conv_seeded_kernel.  Sample b of the launch is
+    // VIRTUAL sample v = v0 + b of an image-major (image, member) batch with `members` draws per image:
+    // image = sample_offset + v / members, member = member_offset + v % members.  A plain seeded run is members == 1,
+    // member_offset == 0: image = sample_offset + v0 + b, member 0.
     int seeded;
     int iter;                       // position in t_list
     unsigned long long seed;
-    long long sample_offset;        // global index of this launch's sample 0
+    long long sample_offset;        // global index of the call's image 0
+    int v0;                         // virtual index of this launch's sample 0 inside the call
+    int members;                    // >= 1
+    unsigned member_offset;         // member index of the call's member 0 (member_offset + members <= 2^32)
 };
 hipError_t out_conv_launch(const OutConvArgs& a, hipStream_t s);
-// dst [n_iters][B][chw] <- the 0.5-scaled seeded step noise (step_noise_common.h); chw < 2^32, B and n_iters <= 65535
-hipError_t step_noise_fill_launch(float* dst, int n_iters, int B, unsigned long long chw, unsigned long long seed, long long sample_offset, hipStream_t s);
+// dst [n_iters][B][chw] <- the 0.5-scaled seeded step noise of `member` (step_noise_common.h); chw < 2^32, B and n_iters <= 65535
+hipError_t step_noise_fill_launch(float* dst, int n_iters, int B, unsigned long long chw, unsigned long long seed, long long sample_offset,
+                                  unsigned member, hipStream_t s);
+// samples [B][K][chw] -> mean [B][chw] and, when std != null (K >= 2), the unbiased std [B][chw]; fixed double-precision
+// arithmetic per pixel (pointwise.hip: ensemble_reduce_kernel).  B <= 65535, K >= 1
+hipError_t ensemble_reduce_launch(const float* samples, int B, int K, unsigned long long chw, float* mean, float* std, hipStream_t s);
+// dst [n][chw] <- noisy[(v0 + j) / K]: the condition image of the n consecutive virtual samples from v0 (one pass of an ensemble)
+hipError_t ensemble_broadcast_launch(const float* noisy, float* dst, int v0, int n, int K, unsigned long long chw, hipStream_t s);
 
 // bilinear resize of an activation tensor, either layout (align_corners=False), any size ratio
 hipError_t resize_bilinear_launch(const float* src, float* dst, stat_word* tot, int rep, int bs, int B, int H, int W, int C, int OH, int OW, int blocked, hipStream_t s);

@@ -245,12 +245,16 @@ static void setup_program(const mi_plan* p, int B, bool side_by_side, Program* g
     g->wide_chunks = !side_by_side && !p->batch_invariant;
 }
 
+static bool plan_as_side() {
+    static const bool on = getenv("MIDD_PLAN_AS_SIDE") != nullptr;
+    return on;
+}
+
 int midd::get_program(mi_plan* p, int B, int H, int W, Program** out, bool side_by_side) {
     if (!p->finalized) return fail(MI_ESTATE, "mi_unet_finalize has not been called (or weights changed since)");
     // development knob (tools/profile_round.sh): plan a program that runs alone exactly as a side-by-side sub-batch program is
     // planned, so that counter passes can measure the default run's launches without the other stream's traffic in their windows
-    static const bool plan_as_side = getenv("MIDD_PLAN_AS_SIDE") != nullptr;
-    side_by_side = side_by_side || plan_as_side;
+    side_by_side = side_by_side || plan_as_side();
     const uint64_t key = ((uint64_t)(side_by_side ? 1 : 0) << 63) ^ ((uint64_t)B << 40) ^ ((uint64_t)H << 20) ^ (uint64_t)W;
     std::lock_guard<std::mutex> lk(p->mu);
     auto it = p->programs.find(key);
@@ -273,17 +277,59 @@ int midd::split_parts(int B) {
     return parts;
 }
 
-extern "C" size_t mi_workspace_bytes(mi_plan* plan, int B, int H, int W) {
-    Program* g = nullptr;
-    if (!plan || get_program(plan, B, H, W, &g)) return 0;
-    size_t need = g->bytes;
+// Workspace bytes of one forward / sampler run at batch B: the whole-batch program, or the sub-batch programs mi_denoise runs
+// side by side when the batch splits.  The ONE place that knows this (mi_workspace_bytes, mi_ensemble_workspace_bytes).
+// A finalized plan answers from its cached programs; an unfinalized one plans a throw-away program (host only, as
+// mi_debug_plan_dump does).  0: unsupported shape (mi_last_error)
+static size_t sampler_bytes(mi_plan* p, int B, int H, int W) {
+    auto bytes_of = [&](int b, bool side) -> size_t {
+        if (p->finalized) { Program* g = nullptr; return get_program(p, b, H, W, &g, side) ? 0 : g->bytes; }
+        Program g;
+        setup_program(p, b, side || plan_as_side(), &g);
+        std::lock_guard<std::mutex> lk(p->mu);
+        return build_program(p, b, H, W, &g) ? 0 : g.bytes;
+    };
+    size_t need = bytes_of(B, false);
     const int parts = split_parts(B);            // mi_denoise runs sub-batches side by side
-    if (parts > 1) {
-        Program* gh = nullptr;
-        if (get_program(plan, B / parts, H, W, &gh, true)) return 0;
-        if (parts * gh->bytes > need) need = parts * gh->bytes;
+    if (need && parts > 1) {
+        const size_t part = bytes_of(B / parts, true);
+        if (!part) return 0;
+        if (parts * part > need) need = parts * part;
     }
     return need;
+}
+
+extern "C" size_t mi_workspace_bytes(mi_plan* plan, int B, int H, int W) {
+    Program* g = nullptr;
+    if (!plan || get_program(plan, B, H, W, &g)) return 0;      // (needs a finalized plan, as before)
+    return sampler_bytes(plan, B, H, W);
+}
+
+int midd::ensemble_layout(mi_plan* p, int B, int members, int H, int W, int pass_samples, bool samples_external, EnsembleLayout* L) {
+    auto round256 = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    const int64_t V = (int64_t)B * members;
+    L->pass = (int)(V < pass_samples ? V : pass_samples);
+    if (L->pass > 65535) L->pass = 65535;                // "at most pass_samples": the broadcast kernel's grid holds this many
+    L->tail = (int)(V % L->pass);
+    L->run_bytes = sampler_bytes(p, L->pass, H, W);
+    if (!L->run_bytes) return MI_EINVAL;                 // (mi_last_error holds the planner's message)
+    if (L->tail) {                                       // (a smaller batch may plan wider tiles: take the larger of the two)
+        const size_t t = sampler_bytes(p, L->tail, H, W);
+        if (!t) return MI_EINVAL;
+        if (t > L->run_bytes) L->run_bytes = t;
+    }
+    const size_t chw = (size_t)p->cfg.in_channels * H * W;
+    L->cond_off = round256(L->run_bytes);
+    L->samples_off = L->cond_off + round256((size_t)L->pass * chw * sizeof(float));
+    L->bytes = L->samples_off + (samples_external ? 0 : (size_t)V * chw * sizeof(float));
+    return MI_OK;
+}
+
+extern "C" size_t mi_ensemble_workspace_bytes(mi_plan* plan, int B, int members, int H, int W, int pass_samples, int samples_external) {
+    if (check_ensemble_args(plan, B, members, H, W, 0, 0, pass_samples)) return 0;
+    EnsembleLayout L{};
+    if (ensemble_layout(plan, B, members, H, W, pass_samples, samples_external != 0, &L)) return 0;
+    return L.bytes;
 }
 
 // Kernel symbol + algorithmic work of one op (for mi_profile_*).

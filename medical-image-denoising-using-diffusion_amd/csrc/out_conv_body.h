@@ -1,8 +1,9 @@
-// The out_conv kernel's text (pointwise.hip), compiled twice: MIDD_OUT_KERNEL = out_conv_kernel with MIDD_OUT_SEEDED 0 (the noise
-// term of the sampler update, if any, is read from a.noise) and out_conv_seeded_kernel with MIDD_OUT_SEEDED 1 (the term is drawn
-// in the update from a.seed / a.sample_offset / a.iter: step_noise_common.h -- no noise tensor exists, 4 bytes per pixel less
-// are read).  Two kernels from one text rather than one template argument more: the unseeded kernels keep their symbols
-// (mi_profile_end, plan dumps) and compile to exactly what they were (instruction mix, registers: profiles/step_noise_isa.txt).
+// The out_conv kernel's text (pointwise.hip), compiled twice: MIDD_OUT_KERNEL = out_conv_kernel with MIDD_OUT_SEEDED 0 (the
+// noise term of the sampler update, if any, is read from a.noise) and out_conv_seeded_kernel with MIDD_OUT_SEEDED 1 (the term is
+// drawn in the update from a.seed / a.sample_offset / a.iter: step_noise_common.h -- no noise tensor exists, 4 bytes per pixel
+// less are read; sample b of the launch is virtual sample a.v0 + b of an ensemble of a.members draws per image, image-major).
+// Two kernels from one text rather than one template argument more: the unseeded kernels keep their symbols (mi_profile_end,
+// plan dumps) and compile to exactly what they were (instruction mix, registers: profiles/step_noise_isa.txt).
 template <int IC>
 __global__ __launch_bounds__(256)
 void MIDD_OUT_KERNEL(const OutConvArgs a, const float* __restrict__ wglob /* == a.w: a restrict parameter of its own, so that uniform reads become scalar loads */) {
@@ -118,7 +119,14 @@ void MIDD_OUT_KERNEL(const OutConvArgs a, const float* __restrict__ wglob /* == 
             if constexpr (MIDD_OUT_SEEDED) {
                 // element index inside the sample's [ic,H,W] block (the host refuses ic*H*W >= 2^32)
                 const uint32_t elem = (uint32_t)(((size_t)oc * a.H + oy) * a.W + ox);
-                xn = __fadd_rn(xn, __fmul_rn(c3, step_noise_value(a.seed, a.sample_offset + b, a.iter, elem)));
+                // virtual sample -> (image, member): b is uniform in the workgroup, so this is one scalar division per workgroup
+                const uint32_t v = (uint32_t)a.v0 + (uint32_t)b, vi = v / (uint32_t)a.members;
+                // The term is added as ONE fused multiply-add, because that is what the unseeded twin below compiles to (hipcc's
+                // __fmul_rn / __fadd_rn are the plain operators and it contracts them: v_fmac_f32, profiles/step_noise_isa.txt) and a
+                // seeded run must replay through the noise tensor bit for bit.  Left to the compiler, this side's contraction
+                // depends on the code around it (with the division above it became v_pk_mul_f32 + v_add_f32).
+                xn = __builtin_fmaf(c3, step_noise_value(a.seed, a.sample_offset + vi, a.iter, elem,
+                                                         a.member_offset + (v - vi * (uint32_t)a.members)), xn);
             } else {
                 if (noise) xn = __fadd_rn(xn, __fmul_rn(c3, noise[o]));
             }

@@ -6,6 +6,8 @@
 //                      (DDIMModel.py:278-284; cddpm noise term cddpmModels.py:297-303)
 //   out_conv_seeded_kernel : the same with the noise term drawn in the update (step_noise_common.h)
 //   step_noise_fill_kernel : the same noise values as a [n_iters,B,C,H,W] tensor (replay / export)
+//   ensemble_reduce_kernel : mean and unbiased std over the members of an ensemble of stochastic samples
+//   ensemble_broadcast_kernel : the condition image of an ensemble pass's virtual samples
 //   resize_bilinear  : F.interpolate(mode='bilinear', align_corners=False) (DDIMModel.py:242)
 //   conv_transpose   : ConvTranspose2d(C,C,4,2,1) (DDIMModel.py:211) for topologies where the
 //                      planner cannot fold it into a 3x3 (never on the default networks)
@@ -365,7 +367,7 @@ hipError_t out_conv_launch(const OutConvArgs& a, hipStream_t s) {
     const size_t lds = ((size_t)a.ic * 9 * a.C + 2 * a.C) * sizeof(float);
     const int tiles = ((a.W + OC_T - 1) / OC_T) * ((a.H + OC_T - 1) / OC_T);
     if (a.seeded) {
-        if (!a.x || (unsigned long long)a.ic * a.H * a.W >= (1ull << 32)) return hipErrorInvalidValue;
+        if (!a.x || (unsigned long long)a.ic * a.H * a.W >= (1ull << 32) || a.members < 1 || a.v0 < 0) return hipErrorInvalidValue;
         if (a.ic == 1) hipLaunchKernelGGL(out_conv_seeded_kernel<1>, dim3(a.B * tiles), dim3(256), lds, s, a, a.w);
         else hipLaunchKernelGGL(out_conv_seeded_kernel<0>, dim3(a.B * tiles), dim3(256), lds, s, a, a.w);
     } else if (a.ic == 1) hipLaunchKernelGGL(out_conv_kernel<1>, dim3(a.B * tiles), dim3(256), lds, s, a, a.w);
@@ -374,20 +376,122 @@ hipError_t out_conv_launch(const OutConvArgs& a, hipStream_t s) {
 }
 
 // ------------------------------------------------------------------------------ seeded step noise as a tensor
-// dst [n_iters][B][chw] <- step_noise_value(seed, sample_offset + b, iteration, element): what out_conv_seeded_kernel draws for
-// the same (seed, sample, iteration, element), so a seeded run replays through mi_denoise's `step_noise`.  grid (chunks of 256
-// elements, B, n_iters)
+// dst [n_iters][B][chw] <- step_noise_value(seed, sample_offset + b, iteration, element, member): what out_conv_seeded_kernel
+// draws for the same (seed, image, iteration, element, member), so a seeded run -- or one member of an ensemble -- replays through
+// mi_denoise's `step_noise`.  grid (chunks of 256 elements, B, n_iters)
 __global__ __launch_bounds__(256)
-void step_noise_fill_kernel(float* __restrict__ dst, unsigned long long chw, unsigned long long seed, long long sample_offset) {
+void step_noise_fill_kernel(float* __restrict__ dst, unsigned long long chw, unsigned long long seed, long long sample_offset, unsigned member) {
     const unsigned long long e = (unsigned long long)blockIdx.x * 256 + threadIdx.x;
     if (e >= chw) return;
     const int b = blockIdx.y, it = blockIdx.z;
-    dst[((size_t)it * gridDim.y + b) * chw + e] = step_noise_value(seed, sample_offset + b, it, (uint32_t)e);
+    dst[((size_t)it * gridDim.y + b) * chw + e] = step_noise_value(seed, sample_offset + b, it, (uint32_t)e, member);
 }
 
-hipError_t step_noise_fill_launch(float* dst, int n_iters, int B, unsigned long long chw, unsigned long long seed, long long sample_offset, hipStream_t s) {
+hipError_t step_noise_fill_launch(float* dst, int n_iters, int B, unsigned long long chw, unsigned long long seed, long long sample_offset,
+                                  unsigned member, hipStream_t s) {
     if (n_iters < 1 || B < 1 || chw < 1 || chw >= (1ull << 32) || n_iters > 65535 || B > 65535) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(step_noise_fill_kernel, dim3((unsigned)((chw + 255) / 256), B, n_iters), dim3(256), 0, s, dst, chw, seed, sample_offset);
+    hipLaunchKernelGGL(step_noise_fill_kernel, dim3((unsigned)((chw + 255) / 256), B, n_iters), dim3(256), 0, s, dst, chw, seed, sample_offset, member);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------ ensembles of stochastic samples
+// samples [B][K][chw] -> mean [B][chw], unbiased std [B][chw] over the K members of every pixel.  A thread owns V
+// neighbouring pixels (V = 4: one 16-byte load per member, 1 KiB per wave instruction, when chw is a multiple of 4 and the
+// pointers are 16-byte aligned; V = 1 otherwise) and walks the K member planes chw floats apart, twice (sum; deviations from
+// the mean), one load in flight per walk step.  The algorithm needs (K + 2) * 4 bytes per pixel; what the kernel reaches
+// against them, at a cache-resident and at a 512 MiB shape, is measured by tools/ensemble_ab.py.
+// THE ARITHMETIC IS FIXED (include/midd.h: mi_ensemble_reduce) and per pixel, so neither V nor the grid shows
+// in the result: double precision, members in index order, every operation rounded to nearest on its own.  hipcc's
+// __dadd_rn / __dmul_rn are the plain operators, which -ffp-contract=fast fuses (q += d * d became one v_fmac_f64), so the
+// three operations are functions of this file compiled with contraction off; division and square root are the correctly
+// rounded library ones (the FMAs left in the ISA are inside those two).
+__device__ __forceinline__ double add_rn64(double a, double b) {
+#pragma clang fp contract(off)
+    return a + b;
+}
+__device__ __forceinline__ double sub_rn64(double a, double b) {
+#pragma clang fp contract(off)
+    return a - b;
+}
+__device__ __forceinline__ double mul_rn64(double a, double b) {
+#pragma clang fp contract(off)
+    return a * b;
+}
+
+template <int V>
+__global__ __launch_bounds__(256)
+void ensemble_reduce_kernel(const float* __restrict__ samples, int K, unsigned long long chw, float* __restrict__ mean, float* __restrict__ stdv) {
+    const unsigned long long e = ((unsigned long long)blockIdx.x * 256 + threadIdx.x) * V;
+    if (e >= chw) return;                                   // (V == 4: chw % 4 == 0, so e + 3 < chw)
+    const size_t b = blockIdx.y;
+    const float* src = samples + b * (size_t)K * chw + e;
+    float x[V];
+    auto load = [&](int m) {
+        if constexpr (V == 4) { const f32x4 v = *reinterpret_cast<const f32x4*>(src + (size_t)m * chw); x[0] = v.x; x[1] = v.y; x[2] = v.z; x[3] = v.w; }
+        else x[0] = src[(size_t)m * chw];
+    };
+    double sum[V], m64[V];
+#pragma unroll
+    for (int j = 0; j < V; ++j) sum[j] = 0.0;
+    for (int m = 0; m < K; ++m) {
+        load(m);
+#pragma unroll
+        for (int j = 0; j < V; ++j) sum[j] = add_rn64(sum[j], (double)x[j]);
+    }
+#pragma unroll
+    for (int j = 0; j < V; ++j) m64[j] = __ddiv_rn(sum[j], (double)K);
+    float out[V];
+    if (mean) {
+#pragma unroll
+        for (int j = 0; j < V; ++j) out[j] = __double2float_rn(m64[j]);
+        if constexpr (V == 4) *reinterpret_cast<f32x4*>(mean + b * chw + e) = (f32x4){out[0], out[1], out[2], out[3]};
+        else mean[b * chw + e] = out[0];
+    }
+    if (stdv) {
+        double q[V];
+#pragma unroll
+        for (int j = 0; j < V; ++j) q[j] = 0.0;
+        for (int m = 0; m < K; ++m) {
+            load(m);
+#pragma unroll
+            for (int j = 0; j < V; ++j) { const double d = sub_rn64((double)x[j], m64[j]); q[j] = add_rn64(q[j], mul_rn64(d, d)); }
+        }
+#pragma unroll
+        for (int j = 0; j < V; ++j) out[j] = __double2float_rn(__dsqrt_rn(__ddiv_rn(q[j], (double)(K - 1))));
+        if constexpr (V == 4) *reinterpret_cast<f32x4*>(stdv + b * chw + e) = (f32x4){out[0], out[1], out[2], out[3]};
+        else stdv[b * chw + e] = out[0];
+    }
+}
+
+static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+hipError_t ensemble_reduce_launch(const float* samples, int B, int K, unsigned long long chw, float* mean, float* stdv, hipStream_t s) {
+    if (B < 1 || B > 65535 || K < 1 || chw < 1 || chw >= (1ull << 32) || (!mean && !stdv) || (stdv && K < 2)) return hipErrorInvalidValue;
+    if (chw % 4 == 0 && aligned16(samples) && aligned16(mean) && aligned16(stdv))
+        hipLaunchKernelGGL(ensemble_reduce_kernel<4>, dim3((unsigned)((chw / 4 + 255) / 256), B), dim3(256), 0, s, samples, K, chw, mean, stdv);
+    else
+        hipLaunchKernelGGL(ensemble_reduce_kernel<1>, dim3((unsigned)((chw + 255) / 256), B), dim3(256), 0, s, samples, K, chw, mean, stdv);
+    return hipGetLastError();
+}
+
+// dst [n][chw] <- noisy[(v0 + j) / K]: the condition image of every virtual sample of one ensemble pass (the K members of an
+// image share it).  grid (chunks of 256 * V elements, n); 8 bytes per element
+template <int V>
+__global__ __launch_bounds__(256)
+void ensemble_broadcast_kernel(const float* __restrict__ noisy, float* __restrict__ dst, int v0, int K, unsigned long long chw) {
+    const unsigned long long e = ((unsigned long long)blockIdx.x * 256 + threadIdx.x) * V;
+    if (e >= chw) return;
+    const size_t j = blockIdx.y, img = (size_t)((unsigned)v0 + blockIdx.y) / (unsigned)K;
+    if constexpr (V == 4) *reinterpret_cast<f32x4*>(dst + j * chw + e) = *reinterpret_cast<const f32x4*>(noisy + img * chw + e);
+    else dst[j * chw + e] = noisy[img * chw + e];
+}
+
+hipError_t ensemble_broadcast_launch(const float* noisy, float* dst, int v0, int n, int K, unsigned long long chw, hipStream_t s) {
+    if (v0 < 0 || n < 1 || n > 65535 || K < 1 || chw < 1 || chw >= (1ull << 32)) return hipErrorInvalidValue;
+    if (chw % 4 == 0 && aligned16(noisy) && aligned16(dst))
+        hipLaunchKernelGGL(ensemble_broadcast_kernel<4>, dim3((unsigned)((chw / 4 + 255) / 256), n), dim3(256), 0, s, noisy, dst, v0, K, chw);
+    else
+        hipLaunchKernelGGL(ensemble_broadcast_kernel<1>, dim3((unsigned)((chw + 255) / 256), n), dim3(256), 0, s, noisy, dst, v0, K, chw);
     return hipGetLastError();
 }
 

@@ -1,10 +1,12 @@
 // Seeded step noise of the stochastic sampler (cddpmModels.py:297-302: x += sqrt(beta_t) * 0.5 * randn_like(x) for t > 0) as a
-// counter-based generator: every value is a pure function of (seed, global sample index, iteration index, element index), so it
-// does not depend on the batch a sample is computed in, on the two-stream split, on the stream or on the GPU that holds the sample.
+// counter-based generator: every value is a pure function of (seed, global sample index, iteration index, element index, member
+// index), so it does not depend on the batch a sample is computed in, on the two-stream split, on the stream or on the GPU that
+// holds the sample.  The member index separates the draws of an ensemble (mi_denoise_ensemble): member 0 is the single seeded run.
 // The specification (include/midd.h; tests/step_noise_reference.py restates it in numpy):
 //   Philox4x32-10 as in Random123: multipliers 0xD2511F53 / 0xCD9E8D57, key increments 0x9E3779B9 / 0xBB67AE85, ten rounds
 //   counter  c0 = element index inside the sample's [C,H,W] block (C*H*W < 2^32), c1 = low word of the global sample index
-//            (sample_offset + b), c2 = iteration index (position in t_list), c3 = 0 (reserved: stream id)
+//            (the IMAGE's: sample_offset + b), c2 = iteration index (position in t_list), c3 = member index (0 for
+//            mi_denoise_seeded and mi_step_noise_fill; the ensemble calls number an image's draws 0, 1, 2, ...)
 //   key      k0 = low word of the seed, k1 = high word
 //   one call per element; outputs x0, x1 are used:
 //   u1 = ((x0 >> 8) + 1) * 2^-24  in (0, 1]      u2 = (x1 >> 8) * 2^-24  in [0, 1)      (both exact in fp32)
@@ -32,9 +34,9 @@ __device__ __forceinline__ Philox4 philox4x32_10(uint32_t c0, uint32_t c1, uint3
     return Philox4{c0, c1, c2, c3};
 }
 
-// the standard normal z of (seed, sample, iteration, element), times 0.5: the value the `step_noise` tensors carry
-__device__ __forceinline__ float step_noise_value(unsigned long long seed, long long sample, int iter, uint32_t elem) {
-    const Philox4 r = philox4x32_10(elem, (uint32_t)(unsigned long long)sample, (uint32_t)iter, 0u,
+// the standard normal z of (seed, sample, iteration, element, member), times 0.5: the value the `step_noise` tensors carry
+__device__ __forceinline__ float step_noise_value(unsigned long long seed, long long sample, int iter, uint32_t elem, uint32_t member) {
+    const Philox4 r = philox4x32_10(elem, (uint32_t)(unsigned long long)sample, (uint32_t)iter, member,
                                     (uint32_t)seed, (uint32_t)(seed >> 32));
     constexpr float TWO_M24 = 5.9604644775390625e-08f;
     const float u1 = __fmul_rn((float)((r.x0 >> 8) + 1u), TWO_M24);

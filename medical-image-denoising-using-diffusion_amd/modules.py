@@ -90,6 +90,7 @@ class UNetDiffusion(nn.Module):
         self._time_rows = DEFAULT_TIME_ROWS
         self._lock = threading.RLock()
         self._workspaces: Dict[Tuple[int, int, int, int, int], torch.Tensor] = {}
+        self._ensemble_ws: Optional[Tuple[tuple, torch.Tensor]] = None      # the one resident run_ensemble workspace: (key, tensor)
         # After every native call the status word of its workspace is read back (mi_status: one 4-byte copy, synchronises the
         # stream): NaN / Inf activations or an operand beyond the fp16 range (f16x3, f16) raise MiddError instead of returning garbage.
         # Set to False (env MIDD_CHECK_STATUS=0) to keep forward() / denoise() asynchronous; the output is NaN then, as torch's.
@@ -154,6 +155,7 @@ class UNetDiffusion(nn.Module):
             native.check(lib.mi_unet_finalize(self._plan, self._time_rows))
         self._stamp = stamp
         self._workspaces.clear()
+        self._ensemble_ws = None
         return self._plan
 
     MAX_WORKSPACES = 4       # resident (shape, stream) workspaces; least recently used is dropped first
@@ -174,6 +176,21 @@ class UNetDiffusion(nn.Module):
                 self._workspaces.pop(next(iter(self._workspaces)))
             ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=dev)
         self._workspaces[key] = ws                # most recently used last
+        return ws
+
+    def _ensemble_workspace(self, B: int, K: int, H: int, W: int, pass_samples: int, external: bool, dev: torch.device) -> torch.Tensor:
+        """Scratch of one run_ensemble call: ONE resident entry of its own, beside the (shape, stream) cache above, so that an
+        ensemble call -- whose workspace holds the activations of a whole pass and, unless the caller takes them, every member's
+        output -- evicts none of the sampler workspaces, and a second ensemble shape replaces the first."""
+        key = (B, K, H, W, pass_samples, external, dev.index, torch.cuda.current_stream(dev).cuda_stream)
+        if self._ensemble_ws is not None and self._ensemble_ws[0] == key:
+            return self._ensemble_ws[1]
+        nbytes = native.lib().mi_ensemble_workspace_bytes(self._plan, B, K, H, W, pass_samples, 1 if external else 0)
+        if nbytes == 0:
+            native.check(-1)
+        self._ensemble_ws = None                  # (free the old one before the new one is allocated)
+        ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=dev)
+        self._ensemble_ws = (key, ws)
         return ws
 
     @staticmethod
@@ -226,16 +243,26 @@ class UNetDiffusion(nn.Module):
     @torch.no_grad()
     def run_sampler(self, noisy: torch.Tensor, t_list, beta: torch.Tensor, alpha: torch.Tensor,
                     alpha_hat: torch.Tensor, clamp_eps: bool, step_noise: Optional[torch.Tensor] = None,
-                    no_split: bool = False, seed: Optional[int] = None, sample_offset: int = 0) -> torch.Tensor:
+                    no_split: bool = False, seed: Optional[int] = None, sample_offset: int = 0, member: int = 0) -> torch.Tensor:
         """The whole reverse loop in one native call (used by DiffusionDenoiser.denoise).
 
         seed: the noise term of every t > 0 update is drawn on the device from (seed, sample_offset + b, iteration, element)
-        (mi_denoise_seeded) instead of read from ``step_noise``; the two are exclusive."""
+        (mi_denoise_seeded) instead of read from ``step_noise``; the two are exclusive.
+        member (with seed): which draw of every image; 0 is the plain seeded run, m > 0 is member m of an ensemble, run alone
+        through mi_denoise_ensemble's single-member form."""
+        from .sampler import check_member, check_seed
+        member = check_member(member)
         if seed is not None:
             if step_noise is not None:
                 raise ValueError("pass either seed or step_noise, not both")
-            from .sampler import check_seed
             seed, sample_offset = check_seed(seed, sample_offset)
+            if member:
+                _, _, samples = self.run_ensemble(noisy, t_list, beta, alpha, alpha_hat, clamp_eps, members=1, seed=seed,
+                                                  sample_offset=sample_offset, member_offset=member, max_batch=max(1, noisy.shape[0]),
+                                                  want_mean=False, want_std=False, want_samples=True, no_split=no_split)
+                return samples[:, 0]
+        elif member:
+            raise ValueError("member selects a draw of the seeded generator: pass seed as well")
         self._check_image(noisy, "noisy_img")
         B, _, H, W = noisy.shape
         steps = np.ascontiguousarray(np.asarray(list(t_list), dtype=np.int32))
@@ -267,6 +294,57 @@ class UNetDiffusion(nn.Module):
                 native.check(native.lib().mi_denoise(*head, nptr, *tail))
             self._raise_on_status(wptr, stream)
         return out
+
+    @torch.no_grad()
+    def run_ensemble(self, noisy: torch.Tensor, t_list, beta: torch.Tensor, alpha: torch.Tensor, alpha_hat: torch.Tensor,
+                     clamp_eps: bool, members: int, seed: int, sample_offset: int = 0, member_offset: int = 0,
+                     max_batch: int = 16, want_mean: bool = True, want_std: bool = True, want_samples: bool = False,
+                     no_split: bool = False):
+        """``members`` seeded draws per image in one native call (mi_denoise_ensemble) -> (mean, std, samples), each None when
+        not asked for.  The B * members (image, member) pairs run through the sampler loop in passes of at most ``max_batch``;
+        samples is [B, members, C, H, W]."""
+        from .sampler import check_member, check_seed
+        seed, sample_offset = check_seed(seed, sample_offset)
+        members, member_offset = check_member(members, "members", low=1), check_member(member_offset, "member_offset")
+        max_batch = check_member(max_batch, "max_batch", low=1)
+        if member_offset + members > 1 << 32:
+            raise ValueError(f"member_offset + members must be <= 2**32 (got {member_offset} + {members})")
+        want_std = want_std and members >= 2
+        if not (want_mean or want_std or want_samples):
+            raise ValueError("nothing to return: ask for the mean, the std or the samples")
+        self._check_image(noisy, "noisy_img")
+        B, Cc, H, W = noisy.shape
+        steps = np.ascontiguousarray(np.asarray(list(t_list), dtype=np.int32))
+        tabs = [np.ascontiguousarray(v.detach().to("cpu", torch.float32).numpy()) for v in (beta, alpha, alpha_hat)]
+        noise_steps = int(tabs[0].shape[0])
+        with self._lock, torch.cuda.device(noisy.device):
+            plan = self._ensure_plan(time_rows=noise_steps)
+            src = noisy.contiguous()
+            mean = torch.empty_like(src) if want_mean else None
+            std = torch.empty_like(src) if want_std else None
+            samples = torch.empty((B, members, Cc, H, W), dtype=torch.float32, device=src.device) if want_samples else None
+            pass_samples = min(max_batch, max(1, B * members))
+            ws = self._ensemble_workspace(B, members, H, W, pass_samples, want_samples, noisy.device)
+            if self.poison_workspace is not None:
+                ws.fill_(self.poison_workspace)
+            wptr, wbytes = self._aligned_ptr(ws)
+            stream = torch.cuda.current_stream(noisy.device).cuda_stream
+            fp = C.POINTER(C.c_float)
+            ptr = lambda t: None if t is None else t.data_ptr()      # noqa: E731
+            native.check(native.lib().mi_denoise_ensemble(
+                plan, src.data_ptr(), ptr(mean), ptr(std), ptr(samples), B, members, H, W,
+                steps.ctypes.data_as(C.POINTER(C.c_int32)), len(steps),
+                tabs[0].ctypes.data_as(fp), tabs[1].ctypes.data_as(fp), tabs[2].ctypes.data_as(fp), noise_steps,
+                C.c_uint64(seed), C.c_int64(sample_offset), C.c_int64(member_offset), pass_samples,
+                (native.MI_CLAMP_EPS if clamp_eps else 0) | (native.MI_NO_SPLIT if no_split else 0), wptr, wbytes, stream))
+            self._raise_on_status(wptr, stream)
+        return mean, std, samples
+
+    def ensemble_workspace_bytes(self, B: int, members: int, H: int, W: int, max_batch: int = 16, samples_external: bool = False) -> int:
+        with self._lock, torch.cuda.device(self._device()):
+            self._ensure_plan()
+            return int(native.lib().mi_ensemble_workspace_bytes(self._plan, B, members, H, W, min(max_batch, max(1, B * members)),
+                                                                1 if samples_external else 0))
 
     @torch.no_grad()
     def debug_fetch(self, module_name: str, B: int, H: int, W: int) -> torch.Tensor:
