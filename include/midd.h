@@ -20,7 +20,7 @@
  *   - a plan is immutable after mi_unet_finalize and may be shared by threads; concurrent
  *     calls must use distinct workspaces (run.py:85-91 calls the sampler from a worker thread).
  *   - images are fp32, contiguous [B, in_channels, H, W] exactly as the reference passes
- *     them (DDIMModel.py:219, :269); H and W must be multiples of 2^(levels-1) (8).
+ *     them (DDIMModel.py:219, :269); H and W must be multiples of 2^(levels-1) (8) -- mi_denoise_tiled lifts that for images.
  */
 #ifndef MIDD_H
 #define MIDD_H
@@ -146,6 +146,9 @@ int mi_denoise(mi_plan* plan, const float* noisy, float* x_out, int B, int H, in
  *   counter  c0 = element index inside the sample's [C,H,W] block (C*H*W < 2^32, else MI_EINVAL), c1 = low 32 bits of
  *            sample_offset + b (the global IMAGE index), c2 = i (position in t_list), c3 = member index; 0 for mi_denoise_seeded
  *            (mi_denoise_ensemble numbers the draws of one image member_offset, member_offset + 1, ...);
+ *            in general c0 = c * plane + y * pitch + x + origin with (pitch, plane, origin) = (W, H*W, 0) for every call above;
+ *            a TILE of mi_denoise_tiled at (y0, x0) of an image [C,H_img,W_img] uses (W_img, H_img*W_img, y0*W_img + x0), i.e.
+ *            c0 = (c*H_img + y0 + y)*W_img + x0 + x, the pixel's index in the WHOLE image (C*H_img*W_img < 2^32), c3 = 0;
  *            key  k0, k1 = low, high word of seed
  *   one Philox call per element, outputs x0 and x1 used:
  *   u1 = ((x0 >> 8) + 1) * 2^-24 in (0, 1],   u2 = (x1 >> 8) * 2^-24 in [0, 1)   (exact in fp32)
@@ -217,6 +220,61 @@ size_t mi_ensemble_workspace_bytes(mi_plan* plan, int B, int members, int H, int
  * MI_EINVAL: B outside [1, 65535], members < 1, chw outside [1, 2^32), null samples / mean_out, std_out with members < 2.
  * samples, mean_out and std_out must not overlap (the kernel reads the samples while it writes the other two). */
 int mi_ensemble_reduce(const float* samples, int B, int members, int64_t chw, float* mean_out, float* std_out, void* stream);
+
+/* TILED DENOISING: images of any size >= the tile, at their own resolution, as overlapping network-sized tiles (the reference
+ * resizes every image to the training size first, Backend/run.py denoise_image_diffusion(..., img_size); nothing there tiles).
+ * THE GEOMETRY (fixed), per axis with image length L, tile T, minimum overlap O, T <= L, 0 <= O <= T/2:
+ *   n = 1 if L == T, else max(2, ceil((L - O) / (T - O)));   origin o_i = (i * (L - T)) / (n - 1) in integer division (o_0 = 0)
+ *   window of position r in [0, T):  w(r) = min(r + 1, T - r, O + 1)  (integer);  a tile's weight at a pixel is wy * wx
+ * Tiles of an image are numbered k = ky * nx + kx; virtual sample v = b * (ny * nx) + k is one (image, tile) pair.
+ * mi_tile_geometry: host only, no plan: *n <- the tile count, origins[0 .. min(n, cap)) <- the origins (origins may be NULL).
+ *   MI_EINVAL: T < 1, T > L, O < 0, O > T/2. */
+int mi_tile_geometry(int L, int T, int O, int* n, int* origins, int cap);
+
+/* dst device fp32 [n][C][th][tw] <- the tiles of virtual samples v0 .. v0 + n - 1 of noisy [B][C][H][W] (no plan needed; any
+ * H, W, th, tw >= 1 with th <= H, tw <= W; n <= 65535 per call).  A copy: bit for bit the slices of the image. */
+int mi_tile_extract(const float* noisy, int B, int C, int H, int W, int th, int tw, int oy, int ox, int v0, int n,
+                    float* dst, void* stream);
+
+/* out device fp32 [B][C][H][W] <- the blend of tiles [B][ny*nx][C][th][tw] (no plan needed).  THE ARITHMETIC (fixed, per pixel,
+ * independent of the launch geometry, no atomics): over the tiles that cover the pixel, in ascending (ky, kx), in double
+ * precision, every operation rounded to nearest on its own, no fused multiply-add,
+ *   num += (double)(wy * wx) * (double)v;   den += (double)(wy * wx);   out = (float)(num / den)
+ * A pixel under one tile gets that tile's value exactly.  tiles and out must not overlap.
+ * MI_EINVAL: the geometry rules above, C*H*W >= 2^32, B * tiles > 2^31 - 1, overlap > 46339. */
+int mi_tile_blend(const float* tiles, int B, int C, int H, int W, int th, int tw, int oy, int ox, float* out, void* stream);
+
+/* Denoises B images [B,C,H,W] of any H >= th, W >= tw at their own size: every image is cut into ny * nx overlapping th x tw
+ * tiles (th, tw: a shape the plan accepts), the B * ny * nx virtual samples run through mi_denoise's sampler loop in passes of
+ * at most pass_samples consecutive virtual samples (extract, then the loop -- each pass split over two streams as a mi_denoise
+ * batch of that size is, MI_NO_SPLIT honoured), and ONE blend launch follows the last pass.
+ *   noisy      device fp32 [B,C,H,W]; never written
+ *   image_out  device fp32 [B,C,H,W]
+ *   tiles_out  device fp32 [B,ny*nx,C,th,tw] or NULL: the denoised tiles (NULL: they live in the workspace)
+ *   t_list .. noise_steps   as mi_denoise
+ *   seeded     0: no noise term (the DDIM variant);  != 0: the term is drawn as mi_denoise_seeded draws it, with the counter word
+ *              c0 of a tile taken in the WHOLE image (specification above): the noise field belongs to the image, not to the
+ *              tiling -- overlapping tiles see the same noise at the same pixel, a tile's noise is the crop of
+ *              mi_step_noise_fill(.., B, C, H, W, seed, sample_offset), and th == H, tw == W is mi_denoise_seeded bit for bit
+ *   seed, sample_offset   as mi_denoise_seeded (sample_offset counts IMAGES); c3 is 0
+ *   pass_samples  virtual samples per pass (>= 1); the workspace grows with it (mi_tiled_workspace_bytes)
+ *   flags      as mi_denoise
+ * With a batch-invariant plan every tile output is a function of its crop (and, seeded, of seed, image and position) alone.
+ * MI_EINVAL before any GPU work, with the limit named in mi_last_error: a tile that is no positive multiple of 2^(levels-1);
+ * tile > image; overlap < 0 or > tile / 2; pass_samples < 1; any two of noisy, image_out, tiles_out overlapping;
+ * sample_offset < 0; C*H*W >= 2^32; B * tiles > 2^31 - 1 (2147483647).
+ * The status word (mi_status) is cleared once per call and accumulates over the passes.  Allocates nothing; asynchronous. */
+int mi_denoise_tiled(mi_plan* plan, const float* noisy, float* image_out, float* tiles_out,
+                     int B, int H, int W, int th, int tw, int oy, int ox,
+                     const int32_t* t_list, int n_iters,
+                     const float* beta, const float* alpha, const float* alpha_hat, int noise_steps,
+                     int seeded, uint64_t seed, int64_t sample_offset, int pass_samples, int flags,
+                     void* workspace, size_t workspace_bytes, void* stream);
+
+/* Bytes of workspace mi_denoise_tiled needs: the sampler workspace of a pass of tiles + the pass's condition tiles + -- unless
+ * tiles_external != 0, i.e. tiles_out is given -- the tile outputs, B * ny*nx * C*th*tw * 4 bytes.  Host only, answered from the
+ * planner alone: it works before mi_unet_finalize too.  0 on bad arguments (mi_last_error says which). */
+size_t mi_tiled_workspace_bytes(mi_plan* plan, int B, int H, int W, int th, int tw, int oy, int ox, int pass_samples, int tiles_external);
 
 /* Status of the last mi_unet_forward / mi_denoise call that used `workspace` (its first word; the calls clear it when they
  * start).  SYNCHRONISES `stream` (one 4-byte device-to-host copy).  Returns MI_OK with *flags == 0, or MI_ERANGE with the

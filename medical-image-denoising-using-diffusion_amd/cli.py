@@ -6,6 +6,7 @@ img_size -> sampler -> uint8 -> bicubic resize back -> PNG, with the reference's
 
     python -m midd_amd.cli --image in.png --out out.png [--checkpoint ckpt.pth] [--variant cddpm|ddim]
                            [--img-size 512] [--inference-steps 25] [--seed N] [--samples K [--std-out std.npy]]
+                           [--tile N [--overlap O]]
 
 Without a checkpoint (the trained weights are not distributed with the reference) the network is
 random-init, which exercises the path but does not denoise.  The reference helper has a latent
@@ -30,13 +31,17 @@ def denoise_image_diffusion(model_path: Optional[str], test_image_path: str, dev
                             img_size: int = 512, inference_steps: int = 50, variant: str = "cddpm",
                             step_noise: Optional[torch.Tensor] = None, compute: Optional[str] = None,
                             seed: Optional[int] = None, samples: Optional[int] = None,
-                            std_out: Optional[str] = None) -> Image.Image:
+                            std_out: Optional[str] = None, tile: Optional[int] = None, overlap: int = 32) -> Image.Image:
     """compute (not a reference argument): arithmetic of the network, see UNetDiffusion -- None keeps the default.
     seed (not a reference argument; cddpm): the stochastic sampler's noise is drawn on the device from this seed, so the same
     call gives the same image again (DiffusionDenoiser.denoise); None: torch.randn, as the reference.
     samples (not a reference argument; cddpm): the returned image is the MEAN of this many seeded draws
     (DiffusionDenoiser.denoise_ensemble; seed None: a seed is drawn and printed) through the same recipe; std_out: path of a
-    .npy file that receives their per-pixel standard deviation, float32 [img_size, img_size] (needs samples >= 2)."""
+    .npy file that receives their per-pixel standard deviation, float32 [img_size, img_size] (needs samples >= 2).
+    tile (not a reference argument): the image is denoised at its OWN size as blended overlapping tile x tile crops with at least
+    `overlap` shared pixels (DiffusionDenoiser.denoise_tiled) -- no resize to img_size and back; both sides must be >= tile."""
+    if tile is not None and (samples is not None or step_noise is not None):
+        raise ValueError("--tile cannot be combined with --samples or a step_noise tensor")
     if samples is not None and variant != "cddpm":
         raise ValueError("--samples needs the stochastic (cddpm) variant: a deterministic sampler has no ensemble")
     if std_out is not None and (samples is None or samples < 2):
@@ -56,6 +61,18 @@ def denoise_image_diffusion(model_path: Optional[str], test_image_path: str, dev
 
     img = Image.open(test_image_path).convert("L")
     on_gpu = device.type == "cuda"
+    if tile is not None:
+        if min(img.size) < tile:
+            raise ValueError(f"the image is {img.size[1]}x{img.size[0]}: a side is shorter than the tile ({tile}); use a smaller "
+                             "--tile, or leave it out so that the image is resized to img_size")
+        input_tensor = torch.from_numpy(np.asarray(img, np.uint8).astype(np.float32) / 255.0)[None, None].to(device)   # ToTensor
+        start_time = time.time()
+        res = diffusion.denoise_tiled(input_tensor, inference_steps=inference_steps, tile=tile, overlap=overlap, seed=seed)
+        if on_gpu:
+            torch.cuda.synchronize(device)
+        print(f"Tiled: {len(res.origins_y)} x {len(res.origins_x)} tiles of {tile}" + (f", seed {res.seed}" if res.seed is not None else ""))
+        print(f"Inference time: {time.time() - start_time:.2f} seconds")
+        return Image.fromarray((res.image[0, 0].cpu().numpy() * 255).astype(np.uint8), mode="L")      # already clamped to [0, 1]
     if on_gpu:      # resize + ToTensor scaling on the device (prepost: bit-identical to the PIL / numpy recipe below)
         from . import prepost
         raw = torch.from_numpy(np.asarray(img, np.uint8).copy()).to(device)
@@ -103,14 +120,19 @@ def main(argv=None) -> None:
                     help="cddpm: save the mean of this many seeded samples of the image (with --seed: reproducible)")
     ap.add_argument("--std-out", default=None, metavar="PATH.npy",
                     help="with --samples K >= 2: write the per-pixel standard deviation of the samples (float32, model resolution)")
+    ap.add_argument("--tile", type=int, default=None, metavar="N",
+                    help="denoise the image at its own size as blended overlapping N x N tiles (N: a multiple of 8) instead of resizing it to --img-size")
+    ap.add_argument("--overlap", type=int, default=32, help="with --tile: minimum overlap of neighbouring tiles (<= N / 2)")
     args = ap.parse_args(argv)
+    if args.tile is not None and (args.tile < 1 or args.samples is not None):
+        ap.error("--tile needs N >= 1 and cannot be combined with --samples")
     if args.samples is not None and (args.samples < 1 or args.variant != "cddpm"):
         ap.error("--samples needs K >= 1 and --variant cddpm")
     if args.std_out is not None and (args.samples is None or args.samples < 2):
         ap.error("--std-out needs --samples K with K >= 2")
     restored = denoise_image_diffusion(args.checkpoint, args.image, device_type=args.device, img_size=args.img_size,
                                        inference_steps=args.inference_steps, variant=args.variant, seed=args.seed,
-                                       samples=args.samples, std_out=args.std_out)
+                                       samples=args.samples, std_out=args.std_out, tile=args.tile, overlap=args.overlap)
     restored.save(args.out, quality=95)
     print(f"\nResult saved: {args.out}")
 

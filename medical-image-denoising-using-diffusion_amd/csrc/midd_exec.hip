@@ -1,5 +1,6 @@
 // Executor: walks a Program's launch list (mi_unet_forward), the sampler loop (mi_denoise), debug fetch and per-op profiling.
 #include "midd_host.h"
+#include "tile_geometry.h"
 
 using namespace midd;
 
@@ -10,6 +11,8 @@ struct StepIO {
     // virtual sample `v0` of a call whose image 0 is global image `sample_offset`, with `members` draws per image numbered from
     // `member_offset` (OutConvArgs, midd_internal.h)
     int seeded; int iter; uint64_t seed; int64_t sample_offset; int v0; int members; uint32_t member_offset;
+    // tiles_x != 0: the virtual samples are (image, tile) pairs of a tiles_y x tiles_x tiling of img_H x img_W images (mi_denoise_tiled)
+    int tiles_x, tiles_y, img_H, img_W;
 };
 
 // status: the call's status word (first word of the CALLER's workspace, whichever sub-batch program runs)
@@ -113,6 +116,7 @@ static int run_program(mi_plan* p, Program* g, const StepIO& io, char* ws, int* 
                 a.c1 = io.c1; a.c2 = io.c2; a.c3 = io.c3; a.clamp_eps = io.clamp_eps;
                 a.seeded = io.seeded; a.iter = io.iter; a.seed = io.seed; a.sample_offset = io.sample_offset;
                 a.v0 = io.v0; a.members = io.members > 0 ? io.members : 1; a.member_offset = io.member_offset;
+                a.tiles_x = io.tiles_x; a.tiles_y = io.tiles_y; a.img_H = io.img_H; a.img_W = io.img_W;
                 e = out_conv_launch(a, s);
                 break;
             }
@@ -192,6 +196,9 @@ extern "C" int mi_unet_forward(mi_plan* plan, const float* x, const float* condi
 struct StepNoise {
     const float* tensor = nullptr; bool seeded = false; uint64_t seed = 0; int64_t sample_offset = 0;
     int v0 = 0; int members = 1; uint32_t member_offset = 0;
+    // mi_denoise_tiled: the virtual samples are (image, tile) pairs, members = tiles_y * tiles_x, and the noise is indexed by the
+    // pixel's place in the whole img_H x img_W image (OutConvArgs)
+    int tiles_x = 0, tiles_y = 0, img_H = 0, img_W = 0;
 };
 
 // One batch through the sampler loop, in two steps: check_run judges the arguments (no GPU work), enqueue_run enqueues the
@@ -263,6 +270,7 @@ static int enqueue_run(mi_plan* plan, Program* g, const float* noisy, float* x_o
                     io.seeded = 1; io.iter = i; io.seed = sn.seed;
                     io.sample_offset = sn.sample_offset; io.v0 = sn.v0 + h * (B / parts);      // sub-batch h: its first virtual index
                     io.members = sn.members; io.member_offset = sn.member_offset;
+                    io.tiles_x = sn.tiles_x; io.tiles_y = sn.tiles_y; io.img_H = sn.img_H; io.img_W = sn.img_W;
                 }
                 io.clamp_eps = (flags & MI_CLAMP_EPS) ? 1 : 0;
                 if (i == 0 && h > 0) HIPCHK(hipStreamWaitEvent(sh, plan->sev_phase[h - 1], 0));      // phase offset (re-establishing it every n-th
@@ -448,6 +456,133 @@ extern "C" int mi_denoise_ensemble(mi_plan* plan, const float* noisy, float* mea
         const hipError_t e = ensemble_reduce_launch(samples, B, members, chw, mean_out, std_out, s);
         if (e != hipSuccess) return fail(MI_EHIP, "ensemble_reduce: %s", hipGetErrorString(e));
     }
+    return MI_OK;
+}
+
+// ---------------------------------------------------------------------------- tiled denoising of full-resolution images
+static int check_tile_axis(const char* axis, int L, int T, int O) {
+    if (T < 1) return fail(MI_EINVAL, "tile %s %d must be positive", axis, T);
+    if (T > L) return fail(MI_EINVAL, "tile %s %d exceeds the image %s %d (limit: tile <= image; resize a smaller image up, or use a smaller tile)", axis, T, axis, L);
+    if (O < 0 || O > T / 2) return fail(MI_EINVAL, "overlap %d of tile %s %d outside [0, %d] (limit: 0 <= overlap <= tile / 2)", O, axis, T, T / 2);
+    return MI_OK;
+}
+
+extern "C" int mi_tile_geometry(int L, int T, int O, int* n, int* origins, int cap) {
+    if (int rc = check_tile_axis("length", L, T, O)) return rc;
+    if (!n) return fail(MI_EINVAL, "null argument");
+    *n = tile_count(L, T, O);
+    for (int i = 0; origins && i < *n && i < cap; ++i) origins[i] = tile_origin(i, L, T, *n);
+    return MI_OK;
+}
+
+static int fill_tile_geom(int C, int H, int W, int th, int tw, int oy, int ox, TileGeom* g) {
+    if (int rc = check_tile_axis("height", H, th, oy)) return rc;
+    if (int rc = check_tile_axis("width", W, tw, ox)) return rc;
+    if (oy > 46339 || ox > 46339) return fail(MI_EINVAL, "overlap %dx%d: the window product must fit 32 bits (limit: overlap <= 46339)", oy, ox);
+    *g = TileGeom{C, H, W, th, tw, oy, ox, tile_count(H, th, oy), tile_count(W, tw, ox)};
+    return MI_OK;
+}
+
+static int check_tile_count(int B, const TileGeom& g) {
+    if (B < 1) return fail(MI_EINVAL, "B %d must be positive", B);
+    if ((int64_t)B * g.ny * g.nx > 2147483647ll)
+        return fail(MI_EINVAL, "B * tiles = %d * %d * %d exceeds 2^31 - 1: the virtual sample index is a 32-bit int (limit: B * tiles <= 2147483647)", B, g.ny, g.nx);
+    return MI_OK;
+}
+
+int midd::check_tiled_args(mi_plan* plan, int B, int H, int W, int th, int tw, int oy, int ox, int64_t sample_offset, int pass_samples, TileGeom* g) {
+    if (!plan) return fail(MI_EINVAL, "null plan");
+    const int div = 1 << (plan->levels - 1);
+    if (th < div || tw < div || th % div || tw % div)
+        return fail(MI_EINVAL, "tile %dx%d: the network takes positive multiples of %d only (limit of the plan; the IMAGE may have any size >= the tile)", th, tw, div);
+    if (int rc = fill_tile_geom(plan->cfg.in_channels, H, W, th, tw, oy, ox, g)) return rc;
+    if (pass_samples < 1) return fail(MI_EINVAL, "pass_samples %d: a pass holds at least one tile (limit: pass_samples >= 1)", pass_samples);
+    if (int rc = check_step_noise_range(plan->cfg.in_channels, H, W, sample_offset)) return rc;
+    return check_tile_count(B, *g);
+}
+
+extern "C" int mi_tile_extract(const float* noisy, int B, int C, int H, int W, int th, int tw, int oy, int ox, int v0, int n,
+                               float* dst, void* stream) {
+    TileGeom g{};
+    if (C < 1) return fail(MI_EINVAL, "C %d must be positive", C);
+    if (int rc = fill_tile_geom(C, H, W, th, tw, oy, ox, &g)) return rc;
+    if (int rc = check_tile_count(B, g)) return rc;
+    if (v0 < 0 || n < 0 || n > 65535 || (int64_t)v0 + n > (int64_t)B * g.ny * g.nx)
+        return fail(MI_EINVAL, "tiles [%d, %d + %d) outside the %d * %d * %d tiles of the batch (limit per call: n <= 65535)", v0, v0, n, B, g.ny, g.nx);
+    if ((int64_t)C * th * tw > 2147483647ll) return fail(MI_EINVAL, "C*th*tw = %d*%d*%d exceeds 2^31 - 1", C, th, tw);
+    if (n == 0) return MI_OK;
+    if (!noisy || !dst) return fail(MI_EINVAL, "null argument");
+    const hipError_t e = tile_extract_launch(noisy, dst, g, v0, n, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(MI_EHIP, "tile_extract: %s", hipGetErrorString(e));
+    return MI_OK;
+}
+
+extern "C" int mi_tile_blend(const float* tiles, int B, int C, int H, int W, int th, int tw, int oy, int ox, float* out, void* stream) {
+    TileGeom g{};
+    if (C < 1) return fail(MI_EINVAL, "C %d must be positive", C);
+    if (int rc = fill_tile_geom(C, H, W, th, tw, oy, ox, &g)) return rc;
+    if (int rc = check_tile_count(B, g)) return rc;
+    if (int rc = check_step_noise_range(C, H, W, 0)) return rc;
+    if (!tiles || !out) return fail(MI_EINVAL, "null argument");
+    const hipError_t e = tile_blend_launch(tiles, out, B, g, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(MI_EHIP, "tile_blend: %s", hipGetErrorString(e));
+    return MI_OK;
+}
+
+extern "C" int mi_denoise_tiled(mi_plan* plan, const float* noisy, float* image_out, float* tiles_out,
+                                int B, int H, int W, int th, int tw, int oy, int ox,
+                                const int32_t* t_list, int n_iters,
+                                const float* beta, const float* alpha, const float* alpha_hat, int noise_steps,
+                                int seeded, uint64_t seed, int64_t sample_offset, int pass_samples, int flags,
+                                void* workspace, size_t workspace_bytes, void* stream) {
+    TileGeom tg{};
+    if (int rc = check_tiled_args(plan, B, H, W, th, tw, oy, ox, sample_offset, pass_samples, &tg)) return rc;
+    const int K = tg.ny * tg.nx;
+    const size_t chw = (size_t)tg.C * th * tw;
+    {   // noisy is read by every pass and the blend reads the tiles while it writes the image: no two of the three may overlap
+        const struct { const void* p; size_t n; const char* name; } buf[3] = {
+            {noisy, (size_t)B * tg.C * H * W * sizeof(float), "noisy"}, {image_out, (size_t)B * tg.C * H * W * sizeof(float), "image_out"},
+            {tiles_out, (size_t)B * K * chw * sizeof(float), "tiles_out"}};
+        for (int i = 0; i < 3; ++i)
+            for (int j = i + 1; j < 3; ++j) {
+                const uintptr_t a = (uintptr_t)buf[i].p, b = (uintptr_t)buf[j].p;
+                if (a && b && a < b + buf[j].n && b < a + buf[i].n)
+                    return fail(MI_EINVAL, "%s and %s alias (overlap): noisy is read by every pass and the blend reads the tiles while it "
+                                "writes image_out", buf[i].name, buf[j].name);
+            }
+    }
+    if (!plan->finalized) return fail(MI_ESTATE, "mi_unet_finalize has not been called (or weights changed since)");
+    EnsembleLayout L{};
+    if (int rc = ensemble_layout(plan, B, K, th, tw, pass_samples, tiles_out != nullptr, &L)) return rc;
+    if (!workspace || workspace_bytes < L.bytes) return fail(MI_ENOMEM, "workspace too small: need %zu bytes, got %zu", L.bytes, workspace_bytes);
+    if (((uintptr_t)workspace) & 255) return fail(MI_EINVAL, "workspace must be 256-byte aligned");
+    if (!noisy || !image_out) return fail(MI_EINVAL, "null argument");
+    if (int rc = check_schedule(plan, t_list, n_iters, beta, alpha, alpha_hat, noise_steps)) return rc;
+    if (int rc = check_device(plan)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    char* ws = (char*)workspace;
+    float* cond = reinterpret_cast<float*>(ws + L.cond_off);
+    float* tiles = tiles_out ? tiles_out : reinterpret_cast<float*>(ws + L.samples_off);
+    const int64_t V = (int64_t)B * K;
+    std::lock_guard<std::mutex> side_lk(plan->side_mu);     // held over all passes: the side streams are per plan
+    HIPCHK(hipMemsetAsync(ws, 0, 256, s));                  // status word: once per call, the passes accumulate into it
+    StepNoise sn;
+    if (seeded) {
+        sn.seeded = true; sn.seed = seed; sn.sample_offset = sample_offset; sn.members = K;
+        sn.tiles_x = tg.nx; sn.tiles_y = tg.ny; sn.img_H = H; sn.img_W = W;
+    }
+    for (int64_t v0 = 0; v0 < V; v0 += L.pass) {
+        const int n = (int)(V - v0 < L.pass ? V - v0 : L.pass);
+        const hipError_t e = tile_extract_launch(noisy, cond, tg, (int)v0, n, s);
+        if (e != hipSuccess) return fail(MI_EHIP, "tile_extract: %s", hipGetErrorString(e));
+        sn.v0 = (int)v0;
+        Program* g = nullptr;
+        float* x = tiles + (size_t)v0 * chw;
+        if (int rc = check_run(plan, cond, x, n, th, tw, t_list, n_iters, beta, alpha, alpha_hat, noise_steps, ws, L.run_bytes, &g)) return rc;
+        if (int rc = enqueue_run(plan, g, cond, x, n, th, tw, t_list, n_iters, beta, alpha, alpha_hat, sn, flags, ws, L.run_bytes, stream)) return rc;
+    }
+    const hipError_t e = tile_blend_launch(tiles, image_out, B, tg, s);
+    if (e != hipSuccess) return fail(MI_EHIP, "tile_blend: %s", hipGetErrorString(e));
     return MI_OK;
 }
 

@@ -112,6 +112,9 @@ int dump_program(mi_plan* p, int B, int H, int W, bool side_by_side, std::string
 struct EnsembleLayout { int pass, tail; size_t run_bytes, cond_off, samples_off, bytes; };
 int ensemble_layout(mi_plan* p, int B, int members, int H, int W, int pass_samples, bool samples_external, EnsembleLayout* L);   // midd_planner.hip
 int check_ensemble_args(mi_plan* p, int B, int members, int H, int W, int64_t sample_offset, int64_t member_offset, int pass_samples);   // midd_exec.hip
+// mi_denoise_tiled: its argument rules (no GPU work) -> the geometry; its workspace is an EnsembleLayout with members = tiles per
+// image at the tile's shape: [sampler workspace of a pass | condition tiles of a pass | tile outputs (unless tiles_out is given)]
+int check_tiled_args(mi_plan* p, int B, int H, int W, int th, int tw, int oy, int ox, int64_t sample_offset, int pass_samples, TileGeom* g);   // midd_exec.hip
 }  // namespace midd
 
 struct mi_plan {

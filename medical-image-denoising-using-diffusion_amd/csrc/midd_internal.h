@@ -205,6 +205,11 @@ struct OutConvArgs {
     int v0;                         // virtual index of this launch's sample 0 inside the call
     int members;                    // >= 1
     unsigned member_offset;         // member index of the call's member 0 (member_offset + members <= 2^32)
+    // tiles_x != 0 (mi_denoise_tiled): the virtual batch is (image, tile) instead -- `members` = tiles_y * tiles_x tiles per
+    // image, tile k = v % members = ky * tiles_x + kx, every draw is member `member_offset` -- and the element index is the
+    // pixel's index in the WHOLE image [ic, img_H, img_W] at the tile's origin (tile_geometry.h: tile_origin of ky / kx with
+    // this launch's H, W as the tile): the noise field belongs to the image, not to the tiling.  0: pitch W, plane H*W, origin 0
+    int tiles_x, tiles_y, img_H, img_W;
 };
 hipError_t out_conv_launch(const OutConvArgs& a, hipStream_t s);
 // dst [n_iters][B][chw] <- the 0.5-scaled seeded step noise of `member` (step_noise_common.h); chw < 2^32, B and n_iters <= 65535
@@ -215,6 +220,13 @@ hipError_t step_noise_fill_launch(float* dst, int n_iters, int B, unsigned long 
 hipError_t ensemble_reduce_launch(const float* samples, int B, int K, unsigned long long chw, float* mean, float* std, hipStream_t s);
 // dst [n][chw] <- noisy[(v0 + j) / K]: the condition image of the n consecutive virtual samples from v0 (one pass of an ensemble)
 hipError_t ensemble_broadcast_launch(const float* noisy, float* dst, int v0, int n, int K, unsigned long long chw, hipStream_t s);
+
+// Tiled denoising (tile_geometry.h).  An image [C,H,W] is cut into ny x nx tiles of th x tw with minimum overlaps oy, ox.
+struct TileGeom { int C, H, W, th, tw, oy, ox, ny, nx; };
+// dst [n][C][th][tw] <- the tiles of the virtual samples v0 .. v0 + n - 1 (v = image * ny*nx + ky * nx + kx) of noisy [B][C][H][W]; n <= 65535
+hipError_t tile_extract_launch(const float* noisy, float* dst, const TileGeom& g, int v0, int n, hipStream_t s);
+// out [B][C][H][W] <- the window-weighted mean of the tiles [B][ny*nx][C][th][tw] over every pixel; fixed double arithmetic
+hipError_t tile_blend_launch(const float* tiles, float* out, int B, const TileGeom& g, hipStream_t s);
 
 // bilinear resize of an activation tensor, either layout (align_corners=False), any size ratio
 hipError_t resize_bilinear_launch(const float* src, float* dst, stat_word* tot, int rep, int bs, int B, int H, int W, int C, int OH, int OW, int blocked, hipStream_t s);

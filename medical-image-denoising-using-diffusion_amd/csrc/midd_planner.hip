@@ -332,6 +332,14 @@ extern "C" size_t mi_ensemble_workspace_bytes(mi_plan* plan, int B, int members,
     return L.bytes;
 }
 
+extern "C" size_t mi_tiled_workspace_bytes(mi_plan* plan, int B, int H, int W, int th, int tw, int oy, int ox, int pass_samples, int tiles_external) {
+    TileGeom g{};
+    if (check_tiled_args(plan, B, H, W, th, tw, oy, ox, 0, pass_samples, &g)) return 0;
+    EnsembleLayout L{};
+    if (ensemble_layout(plan, B, g.ny * g.nx, th, tw, pass_samples, tiles_external != 0, &L)) return 0;
+    return L.bytes;
+}
+
 // Kernel symbol + algorithmic work of one op (for mi_profile_*).
 void midd::op_work(mi_plan* p, Program* g, const Op& o, std::string* name, double* flops, double* bytes) {
     const double B = g->B;

@@ -1,7 +1,8 @@
 // The out_conv kernel's text (pointwise.hip), compiled twice: MIDD_OUT_KERNEL = out_conv_kernel with MIDD_OUT_SEEDED 0 (the
 // noise term of the sampler update, if any, is read from a.noise) and out_conv_seeded_kernel with MIDD_OUT_SEEDED 1 (the term is
 // drawn in the update from a.seed / a.sample_offset / a.iter: step_noise_common.h -- no noise tensor exists, 4 bytes per pixel
-// less are read; sample b of the launch is virtual sample a.v0 + b of an ensemble of a.members draws per image, image-major).
+// less are read; sample b of the launch is virtual sample a.v0 + b of an ensemble of a.members draws per image, image-major, or
+// -- a.tiles_x != 0 -- of a.members tiles per image, whose noise is indexed by the pixel's place in the whole image).
 // Two kernels from one text rather than one template argument more: the unseeded kernels keep their symbols (mi_profile_end,
 // plan dumps) and compile to exactly what they were (instruction mix, registers: profiles/step_noise_isa.txt).
 template <int IC>
@@ -117,16 +118,24 @@ void MIDD_OUT_KERNEL(const OutConvArgs a, const float* __restrict__ wglob /* == 
             if (a.clamp_eps) eps = fminf(fmaxf(eps, -5.0f), 5.0f);
             float xn = __fmul_rn(c1, __fsub_rn(a.x[o], __fmul_rn(c2, eps)));
             if constexpr (MIDD_OUT_SEEDED) {
-                // element index inside the sample's [ic,H,W] block (the host refuses ic*H*W >= 2^32)
-                const uint32_t elem = (uint32_t)(((size_t)oc * a.H + oy) * a.W + ox);
                 // virtual sample -> (image, member): b is uniform in the workgroup, so this is one scalar division per workgroup
                 const uint32_t v = (uint32_t)a.v0 + (uint32_t)b, vi = v / (uint32_t)a.members;
+                // element index oc * plane + y * pitch + x + origin: inside the sample's [ic,H,W] block (W, H*W, 0), or -- a tile
+                // of mi_denoise_tiled -- inside the whole image at the tile's origin (the host refuses ic * plane >= 2^32).
+                // Uniform in the workgroup: scalar arithmetic
+                uint32_t pitch = (uint32_t)a.W, plane = (uint32_t)a.H * (uint32_t)a.W, origin = 0, member = v - vi * (uint32_t)a.members;
+                if (a.tiles_x) {
+                    const int ky = (int)member / a.tiles_x, kx = (int)member - ky * a.tiles_x;
+                    pitch = (uint32_t)a.img_W; plane = (uint32_t)a.img_H * (uint32_t)a.img_W;
+                    origin = (uint32_t)tile_origin(ky, a.img_H, a.H, a.tiles_y) * pitch + (uint32_t)tile_origin(kx, a.img_W, a.W, a.tiles_x);
+                    member = 0;
+                }
+                const uint32_t elem = (uint32_t)oc * plane + (uint32_t)oy * pitch + (uint32_t)ox + origin;
                 // The term is added as ONE fused multiply-add, because that is what the unseeded twin below compiles to (hipcc's
                 // __fmul_rn / __fadd_rn are the plain operators and it contracts them: v_fmac_f32, profiles/step_noise_isa.txt) and a
                 // seeded run must replay through the noise tensor bit for bit.  Left to the compiler, this side's contraction
                 // depends on the code around it (with the division above it became v_pk_mul_f32 + v_add_f32).
-                xn = __builtin_fmaf(c3, step_noise_value(a.seed, a.sample_offset + vi, a.iter, elem,
-                                                         a.member_offset + (v - vi * (uint32_t)a.members)), xn);
+                xn = __builtin_fmaf(c3, step_noise_value(a.seed, a.sample_offset + vi, a.iter, elem, a.member_offset + member), xn);
             } else {
                 if (noise) xn = __fadd_rn(xn, __fmul_rn(c3, noise[o]));
             }

@@ -8,6 +8,7 @@
 //   step_noise_fill_kernel : the same noise values as a [n_iters,B,C,H,W] tensor (replay / export)
 //   ensemble_reduce_kernel : mean and unbiased std over the members of an ensemble of stochastic samples
 //   ensemble_broadcast_kernel : the condition image of an ensemble pass's virtual samples
+//   tile_extract_kernel / tile_blend_kernel : overlapping network-sized tiles of a larger image, and their blend (mi_denoise_tiled)
 //   resize_bilinear  : F.interpolate(mode='bilinear', align_corners=False) (DDIMModel.py:242)
 //   conv_transpose   : ConvTranspose2d(C,C,4,2,1) (DDIMModel.py:211) for topologies where the
 //                      planner cannot fold it into a 3x3 (never on the default networks)
@@ -15,6 +16,7 @@
 // against the HBM roofline.
 #include "midd_internal.h"
 #include "step_noise_common.h"
+#include "tile_geometry.h"
 
 namespace midd {
 
@@ -368,6 +370,8 @@ hipError_t out_conv_launch(const OutConvArgs& a, hipStream_t s) {
     const int tiles = ((a.W + OC_T - 1) / OC_T) * ((a.H + OC_T - 1) / OC_T);
     if (a.seeded) {
         if (!a.x || (unsigned long long)a.ic * a.H * a.W >= (1ull << 32) || a.members < 1 || a.v0 < 0) return hipErrorInvalidValue;
+        if (a.tiles_x && (a.tiles_x < 1 || a.tiles_y < 1 || a.members != a.tiles_x * a.tiles_y || a.img_H < a.H || a.img_W < a.W ||
+                          (unsigned long long)a.ic * a.img_H * a.img_W >= (1ull << 32))) return hipErrorInvalidValue;
         if (a.ic == 1) hipLaunchKernelGGL(out_conv_seeded_kernel<1>, dim3(a.B * tiles), dim3(256), lds, s, a, a.w);
         else hipLaunchKernelGGL(out_conv_seeded_kernel<0>, dim3(a.B * tiles), dim3(256), lds, s, a, a.w);
     } else if (a.ic == 1) hipLaunchKernelGGL(out_conv_kernel<1>, dim3(a.B * tiles), dim3(256), lds, s, a, a.w);
@@ -492,6 +496,93 @@ hipError_t ensemble_broadcast_launch(const float* noisy, float* dst, int v0, int
         hipLaunchKernelGGL(ensemble_broadcast_kernel<4>, dim3((unsigned)((chw / 4 + 255) / 256), n), dim3(256), 0, s, noisy, dst, v0, K, chw);
     else
         hipLaunchKernelGGL(ensemble_broadcast_kernel<1>, dim3((unsigned)((chw + 255) / 256), n), dim3(256), 0, s, noisy, dst, v0, K, chw);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------ tiled denoising: extract and blend
+// Both are HBM-bound streams over the image (tile_geometry.h holds the geometry; origins come from its formula, no table in
+// memory).  Extract: grid (chunks of 256 threads over C * th * tw / V, n virtual samples); the tile is uniform in the
+// workgroup, so its origin is scalar arithmetic.  V = 4: a thread moves four neighbouring pixels of one tile row and stores them
+// as 16 bytes (tw % 4 == 0, dst 16-byte aligned); it LOADS them as 16 bytes when the source address allows (row pitch W % 4 == 0,
+// noisy 16-byte aligned -- `vload` -- and this tile's x0 % 4 == 0), else as four dwords.  V = 1: one dword per thread, any shape.
+template <int V>
+__global__ __launch_bounds__(256)
+void tile_extract_kernel(const float* __restrict__ noisy, float* __restrict__ dst, TileGeom g, int v0, int vload) {
+    const unsigned e = (blockIdx.x * 256u + threadIdx.x) * V;                 // element inside the tile block [C][th][tw]
+    const unsigned tile_elems = (unsigned)g.C * g.th * g.tw;
+    if (e >= tile_elems) return;
+    const unsigned v = (unsigned)v0 + blockIdx.y, K = (unsigned)(g.ny * g.nx);
+    const unsigned img = v / K, k = v - img * K;
+    const int ky = (int)k / g.nx, kx = (int)k - ky * g.nx;
+    const int y0 = tile_origin(ky, g.H, g.th, g.ny), x0 = tile_origin(kx, g.W, g.tw, g.nx);
+    const unsigned x = e % (unsigned)g.tw, cy = e / (unsigned)g.tw;
+    const unsigned y = cy % (unsigned)g.th, c = cy / (unsigned)g.th;
+    const float* src = noisy + (((size_t)img * g.C + c) * g.H + (y0 + y)) * (size_t)g.W + x0 + x;
+    float* out = dst + (size_t)blockIdx.y * tile_elems + e;
+    if constexpr (V == 4) {
+        f32x4 r;
+        if (vload && (x0 & 3) == 0) r = *reinterpret_cast<const f32x4*>(src);
+        else r = (f32x4){src[0], src[1], src[2], src[3]};
+        *reinterpret_cast<f32x4*>(out) = r;
+    } else {
+        *out = *src;
+    }
+}
+
+hipError_t tile_extract_launch(const float* noisy, float* dst, const TileGeom& g, int v0, int n, hipStream_t s) {
+    if (v0 < 0 || n < 1 || n > 65535 || g.C < 1 || g.ny < 1 || g.nx < 1 || g.th < 1 || g.tw < 1 || g.th > g.H || g.tw > g.W ||
+        (unsigned long long)g.C * g.th * g.tw >= (1ull << 31)) return hipErrorInvalidValue;
+    const unsigned tile_elems = (unsigned)g.C * g.th * g.tw;
+    if (g.tw % 4 == 0 && aligned16(dst))
+        hipLaunchKernelGGL(tile_extract_kernel<4>, dim3((tile_elems / 4 + 255) / 256, n), dim3(256), 0, s, noisy, dst, g, v0,
+                           (g.W % 4 == 0 && aligned16(noisy)) ? 1 : 0);
+    else
+        hipLaunchKernelGGL(tile_extract_kernel<1>, dim3((tile_elems + 255) / 256, n), dim3(256), 0, s, noisy, dst, g, v0, 0);
+    return hipGetLastError();
+}
+
+// Blend, as a gather: a thread owns ONE output pixel, finds the tiles that cover it from the origin formula (tile_cover: at most
+// three per axis for every geometry the host accepts, but the loop does not rely on it) and walks them in ascending (ky, kx).
+// THE ARITHMETIC IS FIXED (include/midd.h: mi_tile_blend) and per pixel: in double, every operation rounded on its own,
+//   num += (double)(wy * wx) * (double)v;   den += (double)(wy * wx);   out = (float)(num / den)
+// with the integer windows of tile_geometry.h.  No atomics, nothing depends on the launch geometry; a pixel under one tile gets
+// that tile's value back exactly (w * v is exact in double, and so is the quotient).  Neighbouring threads read neighbouring
+// floats of the same tile row: every wave instruction is a contiguous run (broken once where a tile boundary crosses the wave).
+// grid (chunks of 256 pixels of a [C][H][W] block, images -- folded over grid.y when B > 65535)
+__global__ __launch_bounds__(256)
+void tile_blend_kernel(const float* __restrict__ tiles, float* __restrict__ out, int B, TileGeom g) {
+    const unsigned long long e = (unsigned long long)blockIdx.x * 256 + threadIdx.x;
+    const unsigned long long chw = (unsigned long long)g.C * g.H * g.W;
+    if (e >= chw) return;
+    const int x = (int)(e % (unsigned)g.W);
+    const unsigned long long cy = e / (unsigned)g.W;
+    const int y = (int)(cy % (unsigned)g.H), c = (int)(cy / (unsigned)g.H);
+    int ky0, ky1, kx0, kx1;
+    tile_cover(y, g.H, g.th, g.ny, &ky0, &ky1);
+    tile_cover(x, g.W, g.tw, g.nx, &kx0, &kx1);
+    const size_t tile_plane = (size_t)g.th * g.tw, K = (size_t)g.ny * g.nx;
+    for (size_t b = blockIdx.y; b < (size_t)B; b += gridDim.y) {
+        double num = 0.0, den = 0.0;
+        for (int ky = ky0; ky <= ky1; ++ky) {
+            const int ry = y - tile_origin(ky, g.H, g.th, g.ny);
+            const int wy = tile_window(ry, g.th, g.oy);
+            for (int kx = kx0; kx <= kx1; ++kx) {
+                const int rx = x - tile_origin(kx, g.W, g.tw, g.nx);
+                const double w = (double)(wy * tile_window(rx, g.tw, g.ox));
+                const float v = tiles[((b * K + (size_t)ky * g.nx + kx) * g.C + c) * tile_plane + (size_t)ry * g.tw + rx];
+                num = add_rn64(num, mul_rn64(w, (double)v));
+                den = add_rn64(den, w);
+            }
+        }
+        out[b * chw + e] = __double2float_rn(__ddiv_rn(num, den));
+    }
+}
+
+hipError_t tile_blend_launch(const float* tiles, float* out, int B, const TileGeom& g, hipStream_t s) {
+    const unsigned long long chw = (unsigned long long)g.C * g.H * g.W;
+    if (B < 1 || g.C < 1 || g.ny < 1 || g.nx < 1 || g.th < 1 || g.tw < 1 || g.th > g.H || g.tw > g.W || chw >= (1ull << 32) ||
+        g.oy < 0 || g.ox < 0 || (long long)g.oy + 1 > 46340 || (long long)g.ox + 1 > 46340) return hipErrorInvalidValue;      // wy * wx fits an int
+    hipLaunchKernelGGL(tile_blend_kernel, dim3((unsigned)((chw + 255) / 256), B < 65535 ? B : 65535), dim3(256), 0, s, tiles, out, B, g);
     return hipGetLastError();
 }
 

@@ -7,6 +7,7 @@
 //   counter  c0 = element index inside the sample's [C,H,W] block (C*H*W < 2^32), c1 = low word of the global sample index
 //            (the IMAGE's: sample_offset + b), c2 = iteration index (position in t_list), c3 = member index (0 for
 //            mi_denoise_seeded and mi_step_noise_fill; the ensemble calls number an image's draws 0, 1, 2, ...)
+//            tiles of mi_denoise_tiled: c0 = the pixel's index in the WHOLE image, (c * H_img + y0 + y) * W_img + x0 + x
 //   key      k0 = low word of the seed, k1 = high word
 //   one call per element; outputs x0, x1 are used:
 //   u1 = ((x0 >> 8) + 1) * 2^-24  in (0, 1]      u2 = (x1 >> 8) * 2^-24  in [0, 1)      (both exact in fp32)

@@ -97,6 +97,89 @@ def ensemble_reduce(samples: torch.Tensor) -> Tuple[torch.Tensor, Optional[torch
     return mean, std
 
 
+class TiledResult(NamedTuple):
+    """What ``DiffusionDenoiser.denoise_tiled`` returns."""
+    image: torch.Tensor                   # [B, C, H, W]: the blended image, at the input's own size
+    tiles: Optional[torch.Tensor]         # [B, ny * nx, C, th, tw] with return_tiles=True: the denoised tiles, k = ky * nx + kx
+    origins_y: Tuple[int, ...]            # row origin of every tile row
+    origins_x: Tuple[int, ...]            # column origin of every tile column
+    seed: Optional[int]                   # cddpm: the seed of the run (drawn when the call had seed=None); None for DDIM
+
+
+class TilePlan(NamedTuple):
+    """What ``tile_plan`` returns: the tiling of an H x W image (include/midd.h: mi_tile_geometry)."""
+    tile: Tuple[int, int]                 # (th, tw)
+    overlap: Tuple[int, int]              # (oy, ox): the minimum overlap of neighbouring tiles
+    origins_y: Tuple[int, ...]
+    origins_x: Tuple[int, ...]
+
+
+def _pair(v, what: str, low: int) -> Tuple[int, int]:
+    a, b = (v if isinstance(v, (tuple, list)) and len(v) == 2 else (v, v))
+    return _integer(a, what, 1 << 31, low), _integer(b, what, 1 << 31, low)
+
+
+def _axis(L: int, T: int, O: int) -> Tuple[int, ...]:
+    lib = native.lib()
+    n = C.c_int()
+    native.check(lib.mi_tile_geometry(L, T, O, C.byref(n), None, 0))
+    origins = (C.c_int * n.value)()
+    native.check(lib.mi_tile_geometry(L, T, O, C.byref(n), origins, n.value))
+    return tuple(origins)
+
+
+def tile_plan(H: int, W: int, tile, overlap=32) -> TilePlan:
+    """The tiling ``denoise_tiled`` uses for an H x W image (host only): ``tile`` and ``overlap`` are ints or (y, x) pairs.
+    Raises MiddError for a tile larger than the image or an overlap outside [0, tile / 2]."""
+    (th, tw), (oy, ox) = _pair(tile, "tile", 1), _pair(overlap, "overlap", 0)
+    H, W = _integer(H, "H", 1 << 31, 1), _integer(W, "W", 1 << 31, 1)
+    return TilePlan((th, tw), (oy, ox), _axis(H, th, oy), _axis(W, tw, ox))
+
+
+def _tile_tensor(x, what: str, dims: int) -> torch.Tensor:
+    if not isinstance(x, torch.Tensor) or x.dim() != dims or min(x.shape) < 1:
+        raise ValueError(f"{what} must be a {dims}-dimensional non-empty tensor")
+    if x.device.type != "cuda":
+        raise RuntimeError(f"{what} is on {x.device}: tiling runs only on a ROCm GPU, there is no CPU fallback")
+    if x.dtype != torch.float32:
+        raise TypeError(f"{what} must be float32 (got {x.dtype})")
+    return x.contiguous()
+
+
+@torch.no_grad()
+def tile_extract(images: torch.Tensor, tile, overlap=32) -> torch.Tensor:
+    """[B, C, H, W] -> its tiles [B, ny * nx, C, th, tw] (mi_tile_extract): what ``denoise_tiled`` feeds the sampler."""
+    src = _tile_tensor(images, "images", 4)
+    B, Cc, H, W = src.shape
+    plan = tile_plan(H, W, tile, overlap)
+    (th, tw), (oy, ox), K = plan.tile, plan.overlap, len(plan.origins_y) * len(plan.origins_x)
+    with torch.cuda.device(src.device):
+        out = torch.empty((B, K, Cc, th, tw), dtype=torch.float32, device=src.device)
+        stream = torch.cuda.current_stream(src.device).cuda_stream
+        for v0 in range(0, B * K, 65535):
+            n = min(65535, B * K - v0)
+            native.check(native.lib().mi_tile_extract(src.data_ptr(), B, Cc, H, W, th, tw, oy, ox, v0, n,
+                                                      out.data_ptr() + v0 * Cc * th * tw * 4, stream))
+    return out
+
+
+@torch.no_grad()
+def tile_blend(tiles: torch.Tensor, H: int, W: int, overlap=32) -> torch.Tensor:
+    """tiles [B, ny * nx, C, th, tw] of an H x W tiling -> the blended images [B, C, H, W] with the arithmetic of
+    ``denoise_tiled`` (mi_tile_blend: integer ramp windows, double precision, tiles in index order)."""
+    src = _tile_tensor(tiles, "tiles", 5)
+    B, K, Cc, th, tw = src.shape
+    plan = tile_plan(H, W, (th, tw), overlap)
+    if K != len(plan.origins_y) * len(plan.origins_x):
+        raise ValueError(f"tiles has {K} tiles per image; a {H}x{W} image with tile {th}x{tw} and overlap {plan.overlap} has "
+                         f"{len(plan.origins_y)} x {len(plan.origins_x)}")
+    with torch.cuda.device(src.device):
+        out = torch.empty((B, Cc, int(H), int(W)), dtype=torch.float32, device=src.device)
+        native.check(native.lib().mi_tile_blend(src.data_ptr(), B, Cc, int(H), int(W), th, tw, plan.overlap[0], plan.overlap[1],
+                                                out.data_ptr(), torch.cuda.current_stream(src.device).cuda_stream))
+    return out
+
+
 class DiffusionDenoiser:
     def __init__(self, model, noise_steps=50, beta_start=1e-4, beta_end=0.02):
         self.model = model
@@ -176,6 +259,39 @@ class DiffusionDenoiser:
                                                      members=members, seed=seed, sample_offset=sample_offset,
                                                      member_offset=member_offset, max_batch=max_batch, want_samples=return_samples)
         return EnsembleResult(mean, std, samples, seed)
+
+    @torch.no_grad()
+    def denoise_tiled(self, noisy_img: torch.Tensor, inference_steps: int = 25, tile=256, overlap=32, max_batch: int = 16,
+                      seed: Optional[int] = None, sample_offset: int = 0, return_tiles: bool = False,
+                      step_noise: None = None) -> TiledResult:
+        """Denoises images of ANY size >= the tile at their own resolution (not a reference call: the reference resizes every
+        image to the training size first): every image is cut into overlapping ``tile`` x ``tile`` crops (``tile``: an int or
+        (th, tw), a shape the network takes, i.e. multiples of 8; ``overlap``: an int or (oy, ox), at most tile / 2), the
+        B * tiles crops run through the sampler as batches of at most ``max_batch``, and a window-weighted blend with fixed
+        arithmetic puts them back (``tile_plan`` / ``tile_blend``; include/midd.h: mi_denoise_tiled).  H and W need not be
+        multiples of 8.
+
+        cddpm: the step noise is the seeded generator's, indexed by the pixel's place in the WHOLE image -- the noise field
+        belongs to the image, overlapping tiles see the same noise -- so ``tile == image size`` is ``denoise(x, seed=s)`` bit
+        for bit; ``seed=None`` draws a seed as ``denoise_ensemble`` does and returns it.  A caller's ``step_noise`` tensor is
+        not supported here (the argument exists to say so: anything but None raises ValueError).  DDIM: ``seed`` must be None."""
+        if step_noise is not None:
+            raise ValueError("denoise_tiled does not take a step_noise tensor: its noise is the seeded generator's, indexed by "
+                             "image position (pass seed; midd_amd.step_noise(seed, n, x.shape) exports the same values)")
+        stochastic = getattr(self.model, "variant", "ddim") == "cddpm"
+        if not stochastic and seed is not None:
+            raise ValueError("seed selects the step noise of the stochastic (cddpm) variant: the DDIM variant takes seed=None")
+        if stochastic:
+            if seed is None:
+                hi, lo = torch.randint(0, 1 << 32, (2,), dtype=torch.int64).tolist()
+                seed = (hi << 32) | lo
+            seed, sample_offset = check_seed(seed, sample_offset)
+        self.model.eval()
+        steps = timestep_list(self.noise_steps, inference_steps)
+        image, tiles, plan = self.model.run_tiled(noisy_img, steps, self.beta, self.alpha, self.alpha_hat, clamp_eps=not stochastic,
+                                                  tile=tile, overlap=overlap, seed=seed, sample_offset=sample_offset,
+                                                  max_batch=max_batch, want_tiles=return_tiles)
+        return TiledResult(image, tiles, plan.origins_y, plan.origins_x, seed)
 
     # north_star's wording for the same call
     ddim_sample = denoise
