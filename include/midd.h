@@ -161,6 +161,36 @@ int mi_denoise_seeded(mi_plan* plan, const float* noisy, float* x_out, int B, in
                       uint64_t seed, int64_t sample_offset, int flags,
                       void* workspace, size_t workspace_bytes, void* stream);
 
+/* CONTINUOUS BATCHING: the sampler loop with per-slot timesteps.  The B samples of the call are independent SLOTS: each has its
+ * own condition image, its own timestep in every row and its own noise counter words.  Row i runs ONE forward over all B slots
+ * with t_rows[i][b] as slot b's timestep, then the update of mi_denoise / mi_denoise_seeded per slot (same operation order, same
+ * rounding: a table whose columns all equal a t_list gives, with x preset to the condition, mi_denoise's bits at the same B).
+ *   cond          device fp32 [B,C,H,W]: the slots' condition images, read by every row
+ *   x             device fp32 [B,C,H,W], IN/OUT and NOT initialised by the call: a caller starting a slot copies its condition
+ *                 image into it; a slot continues across calls.  Must not overlap cond
+ *   t_rows        HOST int32 [n_rows][B]; -1 = idle: x[b] keeps its bits, nothing is drawn or written for it (the network still
+ *                 runs over the slot at time row 0, so its cond and x must hold finite values).  Within a call a slot is active
+ *                 on a prefix of the rows: a new image joins at a call boundary
+ *   iter_base     HOST int32 [B] or NULL (all 0): rows of slot b already run in earlier calls
+ *   sample_index  HOST int64 [B] or NULL (0 .. B-1): the global image index of slot b
+ *   step_noise    device fp32 [n_rows,B,C,H,W] (0.5-scaled, as mi_denoise's) or NULL; entries of idle rows and of t == 0 are ignored
+ *   seeded != 0   the noise term of every active t > 0 update is drawn as mi_denoise_seeded draws it, with counter words
+ *                 c1 = low 32 bits of sample_index[b], c2 = iter_base[b] + i, c3 = 0, c0 and the key as specified above
+ *   flags         MI_CLAMP_EPS, MI_NO_SPLIT as in mi_denoise.  The batch splits exactly as there: same sub-batches, same phase
+ *                 offset, joined before the call returns; sub-batch h takes columns [h*B/parts, (h+1)*B/parts) of every table
+ * The per-row coefficients are computed on the host in fp32 in the reference's order and reach the device, with the counter
+ * words and the active flag, as kernel arguments of a small launch per row (<= 32 slots each) that writes them into the
+ * workspace: the host tables are not read after the call returns, and the loop has no host synchronisation.
+ * workspace: mi_workspace_bytes(B, H, W).  The status word is cleared once per call.  n_rows == 0: MI_OK, nothing is enqueued.
+ * MI_EINVAL before any GPU work (mi_last_error names the limit): a null argument; n_rows < 0; a timestep outside
+ * [-1, noise_steps); a slot active again after an idle row; iter_base[b] < 0 or iter_base[b] + n_rows > 2^31 - 1;
+ * sample_index[b] < 0; seeded with C*H*W >= 2^32; seeded together with step_noise; x overlapping (or equal to) cond. */
+int mi_denoise_slots(mi_plan* plan, const float* cond, float* x, int B, int H, int W,
+                     const int32_t* t_rows, int n_rows, const int32_t* iter_base, const int64_t* sample_index,
+                     const float* beta, const float* alpha, const float* alpha_hat, int noise_steps,
+                     const float* step_noise, int seeded, uint64_t seed, int flags,
+                     void* workspace, size_t workspace_bytes, void* stream);
+
 /* The values mi_denoise_seeded draws, as a tensor (no plan needed): dst device fp32 [n_iters,B,C,H,W] <- 0.5 * z of
  * (seed, sample_offset + b, i, element), i.e. already 0.5-scaled as mi_denoise's `step_noise` expects.  Replay and export:
  * mi_denoise with this tensor equals mi_denoise_seeded bit for bit.  Every iteration is filled (the t == 0 entry is ignored

@@ -11,3 +11,4 @@ from .config import UNetConfig, topology, param_shapes, timestep_list  # noqa: F
 from .modules import UNetDiffusion  # noqa: F401
 from .sampler import (DiffusionDenoiser, EnsembleResult, TilePlan, TiledResult, device, ensemble_reduce, step_noise,  # noqa: F401
                       tile_blend, tile_extract, tile_plan)
+from .session import SamplerSession, Ticket  # noqa: F401

@@ -13,6 +13,9 @@ struct StepIO {
     int seeded; int iter; uint64_t seed; int64_t sample_offset; int v0; int members; uint32_t member_offset;
     // tiles_x != 0: the virtual samples are (image, tile) pairs of a tiles_y x tiles_x tiling of img_H x img_W images (mi_denoise_tiled)
     int tiles_x, tiles_y, img_H, img_W;
+    // slots != null (mi_denoise_slots): every sample is updated from its record of this row (device, [B]) by out_conv_slots_kernel;
+    // of the fields above the update reads x_update, noise, clamp_eps, seeded and seed only
+    const SlotRec* slots;
 };
 
 // status: the call's status word (first word of the CALLER's workspace, whichever sub-batch program runs)
@@ -117,7 +120,7 @@ static int run_program(mi_plan* p, Program* g, const StepIO& io, char* ws, int* 
                 a.seeded = io.seeded; a.iter = io.iter; a.seed = io.seed; a.sample_offset = io.sample_offset;
                 a.v0 = io.v0; a.members = io.members > 0 ? io.members : 1; a.member_offset = io.member_offset;
                 a.tiles_x = io.tiles_x; a.tiles_y = io.tiles_y; a.img_H = io.img_H; a.img_W = io.img_W;
-                e = out_conv_launch(a, s);
+                e = io.slots ? out_conv_slots_launch(a, io.slots, s) : out_conv_launch(a, s);
                 break;
             }
         }
@@ -131,7 +134,8 @@ static int run_program(mi_plan* p, Program* g, const StepIO& io, char* ws, int* 
             mi_plan::Span sp; sp.a = ev_a; sp.b = ev_b;
             op_work(p, g, o, &sp.name, &sp.flops, &sp.bytes);
             const size_t oc_at = sp.name.find("out_conv_kernel");
-            if (o.kind == OP_OUT && io.seeded && oc_at != std::string::npos) sp.name.replace(oc_at, 15, "out_conv_seeded_kernel");      // the symbol that ran
+            if (o.kind == OP_OUT && (io.seeded || io.slots) && oc_at != std::string::npos)      // the symbol that ran
+                sp.name.replace(oc_at, 15, io.slots ? "out_conv_slots_kernel" : "out_conv_seeded_kernel");
             static const bool per_op = getenv("MIDD_PROFILE_PER_OP") != nullptr;      // one entry per op instead of per symbol
             if (per_op) {
                 char tag[96];
@@ -216,15 +220,26 @@ static int check_run(mi_plan* plan, const float* noisy, const float* x_out, int 
     return MI_OK;
 }
 
+// The rows of a sampler call.  Uniform (mi_denoise and its siblings): row i puts every sample at t[i], x starts as a copy of the
+// condition images.  Slots (mi_denoise_slots): t is a table [n][B], sample b is at t[i * B + b] in row i or idle (-1), its noise
+// counter words are (sample_index[b], iter_base[b] + i), and x is the caller's: it is not initialised.
+struct RunRows {
+    const int32_t* t = nullptr; int n = 0;
+    bool slots = false;
+    const int32_t* iter_base = nullptr;         // slots: [B] or null (all 0)
+    const int64_t* sample_index = nullptr;      // slots: [B] or null (0 .. B-1)
+};
+
 // (the caller holds plan->side_mu and has cleared the status word at the head of `workspace`)
 static int enqueue_run(mi_plan* plan, Program* g, const float* noisy, float* x_out, int B, int H, int W,
-                       const int32_t* t_list, int n_iters, const float* beta, const float* alpha, const float* alpha_hat,
+                       const RunRows& rows, const float* beta, const float* alpha, const float* alpha_hat,
                        const StepNoise& sn, int flags, void* workspace, size_t workspace_bytes, void* stream) {
+    const int n_iters = rows.n;
     int rc = MI_OK;
     hipStream_t s = (hipStream_t)stream;
     char* ws = (char*)workspace;
     const size_t img_elems = (size_t)B * plan->cfg.in_channels * H * W;
-    HIPCHK(hipMemcpyAsync(x_out, noisy, img_elems * sizeof(float), hipMemcpyDeviceToDevice, s));   // x = noisy_img.clone()
+    if (!rows.slots) HIPCHK(hipMemcpyAsync(x_out, noisy, img_elems * sizeof(float), hipMemcpyDeviceToDevice, s));   // x = noisy_img.clone()
     // Images are independent: the batch runs as `parts` sub-batches on as many streams, each started
     // 1/parts of a forward after the previous one, so that one part's latency-bound low-resolution
     // layers (one workgroup per CU at B=8) share the chip with another part's HBM-bound high-resolution
@@ -254,23 +269,53 @@ static int enqueue_run(mi_plan* plan, Program* g, const float* noisy, float* x_o
     // From here on the side streams may hold work on x_out and the workspace: whatever happens in the loop,
     // the caller's stream waits for them before this call returns (the caller frees / reuses both).
     auto enqueue_all = [&]() -> int {
+        const int Bh = B / parts;
         for (int i = 0; i < n_iters; ++i) {
-            const int t = t_list[i];
             for (int h = 0; h < parts; ++h) {
                 hipStream_t sh = h ? plan->sstream[h] : s;
                 char* wsh = ws + (size_t)h * gh->bytes;
-                HIPCHK(hipMemsetD32Async((hipDeviceptr_t)(wsh + gh->trow_off), t, B / parts, sh));          // t = full((B,), i)
                 StepIO io{};
                 io.x = x_out + h * part; io.cond = noisy + h * part; io.eps_out = nullptr; io.x_update = x_out + h * part;
-                io.c1 = 1.0f / sqrtf(alpha[t]);                  // fp32 arithmetic in the reference's order (DDIMModel.py:280-283)
-                io.c2 = (1.0f - alpha[t]) / sqrtf(1.0f - alpha_hat[t]);
-                io.c3 = sqrtf(beta[t]);
-                io.noise = (sn.tensor && t > 0) ? sn.tensor + (size_t)i * img_elems + h * part : nullptr;      // cddpmModels.py:297-300
-                if (sn.seeded && t > 0) {                        // nothing is drawn at t == 0
-                    io.seeded = 1; io.iter = i; io.seed = sn.seed;
-                    io.sample_offset = sn.sample_offset; io.v0 = sn.v0 + h * (B / parts);      // sub-batch h: its first virtual index
-                    io.members = sn.members; io.member_offset = sn.member_offset;
-                    io.tiles_x = sn.tiles_x; io.tiles_y = sn.tiles_y; io.img_H = sn.img_H; io.img_W = sn.img_W;
+                // fp32 arithmetic in the reference's order (DDIMModel.py:280-283)
+                auto coeffs = [&](int t, float* c1, float* c2, float* c3) {
+                    *c1 = 1.0f / sqrtf(alpha[t]);
+                    *c2 = (1.0f - alpha[t]) / sqrtf(1.0f - alpha_hat[t]);
+                    *c3 = sqrtf(beta[t]);
+                };
+                if (rows.slots) {
+                    // sub-batch h takes columns [h * Bh, (h + 1) * Bh) of every table; the records leave as kernel arguments
+                    int* trow = reinterpret_cast<int*>(wsh + gh->trow_off);
+                    SlotRec* recs = reinterpret_cast<SlotRec*>(wsh + gh->slot_off);
+                    for (int c0 = 0; c0 < Bh; c0 += SLOTS_PER_LAUNCH) {
+                        SlotRecs r{};
+                        const int m = Bh - c0 < SLOTS_PER_LAUNCH ? Bh - c0 : SLOTS_PER_LAUNCH;
+                        for (int j = 0; j < m; ++j) {
+                            const int col = h * Bh + c0 + j, t = rows.t[(size_t)i * B + col];
+                            if (t < 0) continue;                             // idle: active 0, time row 0
+                            SlotRec& q = r.v[j];
+                            coeffs(t, &q.c1, &q.c2, &q.c3);
+                            q.active = SLOT_ACTIVE | ((t > 0 && (sn.seeded || sn.tensor)) ? SLOT_NOISE : 0);      // nothing is drawn at t == 0
+                            q.iter = (unsigned)((rows.iter_base ? rows.iter_base[col] : 0) + i);
+                            q.image = (unsigned)(uint64_t)(rows.sample_index ? rows.sample_index[col] : (int64_t)col);
+                            q.trow = t;
+                        }
+                        const hipError_t e = slot_fill_launch(trow + c0, recs + c0, r, m, sh);
+                        if (e != hipSuccess) return fail(MI_EHIP, "slot records: %s", hipGetErrorString(e));
+                    }
+                    io.slots = recs;
+                    io.noise = sn.tensor ? sn.tensor + (size_t)i * img_elems + h * part : nullptr;
+                    io.seeded = sn.seeded ? 1 : 0; io.seed = sn.seed;
+                } else {
+                    const int t = rows.t[i];
+                    HIPCHK(hipMemsetD32Async((hipDeviceptr_t)(wsh + gh->trow_off), t, Bh, sh));          // t = full((B,), i)
+                    coeffs(t, &io.c1, &io.c2, &io.c3);
+                    io.noise = (sn.tensor && t > 0) ? sn.tensor + (size_t)i * img_elems + h * part : nullptr;      // cddpmModels.py:297-300
+                    if (sn.seeded && t > 0) {                        // nothing is drawn at t == 0
+                        io.seeded = 1; io.iter = i; io.seed = sn.seed;
+                        io.sample_offset = sn.sample_offset; io.v0 = sn.v0 + h * Bh;      // sub-batch h: its first virtual index
+                        io.members = sn.members; io.member_offset = sn.member_offset;
+                        io.tiles_x = sn.tiles_x; io.tiles_y = sn.tiles_y; io.img_H = sn.img_H; io.img_W = sn.img_W;
+                    }
                 }
                 io.clamp_eps = (flags & MI_CLAMP_EPS) ? 1 : 0;
                 if (i == 0 && h > 0) HIPCHK(hipStreamWaitEvent(sh, plan->sev_phase[h - 1], 0));      // phase offset (re-establishing it every n-th
@@ -305,7 +350,8 @@ static int denoise_run(mi_plan* plan, const float* noisy, float* x_out, int B, i
         return rc;
     std::lock_guard<std::mutex> side_lk(plan->side_mu);      // the side streams and their events are per plan: one enqueue at a time
     HIPCHK(hipMemsetAsync(workspace, 0, 256, (hipStream_t)stream));      // status word (before the side streams fork)
-    return enqueue_run(plan, g, noisy, x_out, B, H, W, t_list, n_iters, beta, alpha, alpha_hat, sn, flags, workspace, workspace_bytes, stream);
+    RunRows rows; rows.t = t_list; rows.n = n_iters;
+    return enqueue_run(plan, g, noisy, x_out, B, H, W, rows, beta, alpha, alpha_hat, sn, flags, workspace, workspace_bytes, stream);
 }
 
 extern "C" int mi_denoise(mi_plan* plan, const float* noisy, float* x_out, int B, int H, int W,
@@ -341,6 +387,58 @@ extern "C" int mi_denoise_seeded(mi_plan* plan, const float* noisy, float* x_out
     sn.seeded = true; sn.seed = seed; sn.sample_offset = sample_offset;
     return denoise_run(plan, noisy, x_out, B, H, W, t_list, n_iters, beta, alpha, alpha_hat, noise_steps, sn, flags,
                        workspace, workspace_bytes, stream);
+}
+
+// ---------------------------------------------------------------------------- per-slot timesteps (continuous batching)
+extern "C" int mi_denoise_slots(mi_plan* plan, const float* cond, float* x, int B, int H, int W,
+                                const int32_t* t_rows, int n_rows, const int32_t* iter_base, const int64_t* sample_index,
+                                const float* beta, const float* alpha, const float* alpha_hat, int noise_steps,
+                                const float* step_noise, int seeded, uint64_t seed, int flags,
+                                void* workspace, size_t workspace_bytes, void* stream) {
+    if (!plan) return fail(MI_EINVAL, "null plan");
+    if (!cond || !x || !beta || !alpha || !alpha_hat || (n_rows > 0 && !t_rows)) return fail(MI_EINVAL, "null argument");
+    if (n_rows < 0) return fail(MI_EINVAL, "n_rows %d is negative (limit: n_rows >= 0)", n_rows);
+    if (B < 1 || H < 1 || W < 1) return fail(MI_EINVAL, "bad shape B %d, %dx%d (limit: B >= 1, H >= 1, W >= 1)", B, H, W);
+    if (noise_steps < 1) return fail(MI_EINVAL, "noise_steps %d: a schedule has at least one step (limit: noise_steps >= 1)", noise_steps);
+    for (int b = 0; b < B; ++b) {
+        bool idle = false;                                       // within a call a slot is active on a prefix of the rows
+        for (int i = 0; i < n_rows; ++i) {
+            const int t = t_rows[(size_t)i * B + b];
+            if (t < -1 || t >= noise_steps)
+                return fail(MI_EINVAL, "t_rows[%d][%d]=%d outside [-1,%d) (-1 = idle)", i, b, t, noise_steps);
+            if (t >= 0 && idle)
+                return fail(MI_EINVAL, "t_rows[%d][%d]=%d: slot %d is active again after an idle row (limit: a slot is active on a prefix "
+                            "of the rows; a new image joins at the next call)", i, b, t, b);
+            idle = t < 0;
+        }
+        if (iter_base && (iter_base[b] < 0 || (int64_t)iter_base[b] + n_rows > 2147483647ll))
+            return fail(MI_EINVAL, "iter_base[%d]=%d with %d rows: the iteration index is one 32-bit counter word, kept below 2^31 "
+                        "(limit: 0 <= iter_base, iter_base + n_rows <= 2147483647)", b, iter_base[b], n_rows);
+        if (sample_index && sample_index[b] < 0)
+            return fail(MI_EINVAL, "sample_index[%d]=%lld is negative: the global sample index starts at 0", b, (long long)sample_index[b]);
+    }
+    if (seeded) {
+        if (step_noise) return fail(MI_EINVAL, "seeded together with step_noise: the noise term is drawn or read, not both");
+        if (int rc = check_step_noise_range(plan->cfg.in_channels, H, W, 0)) return rc;
+    }
+    {   // cond is read by every row while x is updated in place
+        const size_t n = (size_t)B * plan->cfg.in_channels * H * W * sizeof(float);
+        const uintptr_t a = (uintptr_t)cond, b = (uintptr_t)x;
+        if (a < b + n && b < a + n)
+            return fail(MI_EINVAL, "x and cond alias (overlap): the condition images are read by every row while x is updated in place");
+    }
+    if (!plan->finalized) return fail(MI_ESTATE, "mi_unet_finalize has not been called (or weights changed since)");
+    if (noise_steps > plan->time_rows)
+        return fail(MI_EINVAL, "noise_steps %d exceeds the precomputed time table (%d rows)", noise_steps, plan->time_rows);
+    Program* g = nullptr;
+    if (int rc = check_call(plan, B, H, W, workspace, workspace_bytes, &g)) return rc;
+    if (n_rows == 0) return MI_OK;
+    StepNoise sn;
+    sn.tensor = step_noise; sn.seeded = seeded != 0; sn.seed = seed;
+    RunRows rows; rows.t = t_rows; rows.n = n_rows; rows.slots = true; rows.iter_base = iter_base; rows.sample_index = sample_index;
+    std::lock_guard<std::mutex> side_lk(plan->side_mu);
+    HIPCHK(hipMemsetAsync(workspace, 0, 256, (hipStream_t)stream));      // status word: once per call
+    return enqueue_run(plan, g, cond, x, B, H, W, rows, beta, alpha, alpha_hat, sn, flags, workspace, workspace_bytes, stream);
 }
 
 extern "C" int mi_step_noise_fill_member(float* dst, int n_iters, int B, int C, int H, int W,
@@ -441,6 +539,7 @@ extern "C" int mi_denoise_ensemble(mi_plan* plan, const float* noisy, float* mea
     HIPCHK(hipMemsetAsync(ws, 0, 256, s));                  // status word: once per call, the passes accumulate into it
     StepNoise sn;
     sn.seeded = true; sn.seed = seed; sn.sample_offset = sample_offset; sn.members = members; sn.member_offset = (uint32_t)member_offset;
+    RunRows rows; rows.t = t_list; rows.n = n_iters;
     for (int64_t v0 = 0; v0 < V; v0 += L.pass) {
         const int n = (int)(V - v0 < L.pass ? V - v0 : L.pass);
         const hipError_t e = ensemble_broadcast_launch(noisy, cond, (int)v0, n, members, chw, s);
@@ -450,7 +549,7 @@ extern "C" int mi_denoise_ensemble(mi_plan* plan, const float* noisy, float* mea
         Program* g = nullptr;
         float* x = samples + (size_t)v0 * chw;
         if (int rc = check_run(plan, cond, x, n, H, W, t_list, n_iters, beta, alpha, alpha_hat, noise_steps, ws, L.run_bytes, &g)) return rc;
-        if (int rc = enqueue_run(plan, g, cond, x, n, H, W, t_list, n_iters, beta, alpha, alpha_hat, sn, flags, ws, L.run_bytes, stream)) return rc;
+        if (int rc = enqueue_run(plan, g, cond, x, n, H, W, rows, beta, alpha, alpha_hat, sn, flags, ws, L.run_bytes, stream)) return rc;
     }
     if (mean_out || std_out) {
         const hipError_t e = ensemble_reduce_launch(samples, B, members, chw, mean_out, std_out, s);
@@ -571,6 +670,7 @@ extern "C" int mi_denoise_tiled(mi_plan* plan, const float* noisy, float* image_
         sn.seeded = true; sn.seed = seed; sn.sample_offset = sample_offset; sn.members = K;
         sn.tiles_x = tg.nx; sn.tiles_y = tg.ny; sn.img_H = H; sn.img_W = W;
     }
+    RunRows rows; rows.t = t_list; rows.n = n_iters;
     for (int64_t v0 = 0; v0 < V; v0 += L.pass) {
         const int n = (int)(V - v0 < L.pass ? V - v0 : L.pass);
         const hipError_t e = tile_extract_launch(noisy, cond, tg, (int)v0, n, s);
@@ -579,7 +679,7 @@ extern "C" int mi_denoise_tiled(mi_plan* plan, const float* noisy, float* image_
         Program* g = nullptr;
         float* x = tiles + (size_t)v0 * chw;
         if (int rc = check_run(plan, cond, x, n, th, tw, t_list, n_iters, beta, alpha, alpha_hat, noise_steps, ws, L.run_bytes, &g)) return rc;
-        if (int rc = enqueue_run(plan, g, cond, x, n, th, tw, t_list, n_iters, beta, alpha, alpha_hat, sn, flags, ws, L.run_bytes, stream)) return rc;
+        if (int rc = enqueue_run(plan, g, cond, x, n, th, tw, rows, beta, alpha, alpha_hat, sn, flags, ws, L.run_bytes, stream)) return rc;
     }
     const hipError_t e = tile_blend_launch(tiles, image_out, B, tg, s);
     if (e != hipSuccess) return fail(MI_EHIP, "tile_blend: %s", hipGetErrorString(e));

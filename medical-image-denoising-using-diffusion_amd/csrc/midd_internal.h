@@ -212,6 +212,21 @@ struct OutConvArgs {
     int tiles_x, tiles_y, img_H, img_W;
 };
 hipError_t out_conv_launch(const OutConvArgs& a, hipStream_t s);
+// mi_denoise_slots: every sample of a launch is a SLOT at its own timestep.  One record per sample and row of the loop, written
+// by the host for this row (slot_fill_launch) and read by out_conv_slots_kernel through scalar loads (b is per workgroup).
+enum SlotBits { SLOT_ACTIVE = 1, SLOT_NOISE = 2 };      // NOISE: t > 0 and the call has a noise term (seeded or a tensor)
+struct SlotRec {
+    float c1, c2, c3;               // x <- clamp(c1 * (x - c2 * eps) + c3 * noise, 0, 1) at the slot's timestep
+    int active;                     // SlotBits; 0 = idle: x keeps its bits, nothing is drawn or written
+    unsigned iter;                  // noise counter word c2: iter_base + row
+    unsigned image;                 // noise counter word c1: low word of the slot's global sample index
+    int trow;                       // the slot's time-table row (0 when idle)
+    int pad;
+};
+constexpr int SLOTS_PER_LAUNCH = 32;
+struct SlotRecs { SlotRec v[SLOTS_PER_LAUNCH]; };      // 1 KiB of kernel arguments
+hipError_t slot_fill_launch(int* trow, SlotRec* dst, const SlotRecs& recs, int n, hipStream_t s);
+hipError_t out_conv_slots_launch(const OutConvArgs& a, const SlotRec* slots, hipStream_t s);
 // dst [n_iters][B][chw] <- the 0.5-scaled seeded step noise of `member` (step_noise_common.h); chw < 2^32, B and n_iters <= 65535
 hipError_t step_noise_fill_launch(float* dst, int n_iters, int B, unsigned long long chw, unsigned long long seed, long long sample_offset,
                                   unsigned member, hipStream_t s);

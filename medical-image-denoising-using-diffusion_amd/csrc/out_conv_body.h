@@ -5,9 +5,17 @@
 // -- a.tiles_x != 0 -- of a.members tiles per image, whose noise is indexed by the pixel's place in the whole image).
 // Two kernels from one text rather than one template argument more: the unseeded kernels keep their symbols (mi_profile_end,
 // plan dumps) and compile to exactly what they were (instruction mix, registers: profiles/step_noise_isa.txt).
+// A third compile, MIDD_OUT_SLOTS 1 = out_conv_slots_kernel (mi_denoise_slots): the update's coefficients, the noise counter words
+// and whether the sample is updated at all come from the sample's SlotRec (midd_internal.h) instead of the arguments -- every
+// sample of the launch is at its own timestep.  b is per workgroup, so the record is read with scalar loads; the workgroups of
+// an idle slot leave at once: nothing is staged, drawn or written.  The other two compiles do not see a token of it.
 template <int IC>
 __global__ __launch_bounds__(256)
-void MIDD_OUT_KERNEL(const OutConvArgs a, const float* __restrict__ wglob /* == a.w: a restrict parameter of its own, so that uniform reads become scalar loads */) {
+void MIDD_OUT_KERNEL(const OutConvArgs a, const float* __restrict__ wglob /* == a.w: a restrict parameter of its own, so that uniform reads become scalar loads */
+#if MIDD_OUT_SLOTS
+                     , const SlotRec* __restrict__ slots /* [a.B] */
+#endif
+                     ) {
     __shared__ __attribute__((aligned(16))) float tile[OC_I * OC_I * OC_PS];
     extern __shared__ __attribute__((aligned(16))) float wl[];       // [ic][9][C], then [2][C] GroupNorm scale / shift of this sample
     const int ic = IC ? IC : a.ic;
@@ -19,6 +27,10 @@ void MIDD_OUT_KERNEL(const OutConvArgs a, const float* __restrict__ wglob /* == 
     const int trem = blockIdx.x - b * tiles_x * tiles_y;
     const int oy0 = (trem / tiles_x) * OC_T, ox0 = (trem % tiles_x) * OC_T;
     const int C = a.C;
+#if MIDD_OUT_SLOTS
+    const SlotRec rec = slots[b];
+    if (!rec.active) return;                      // idle slot: x[b] keeps its bits (whole workgroup, before any barrier)
+#endif
     if constexpr (IC == 0) for (int i = tid; i < ic * 9 * C; i += 256) wl[i] = a.w[i];     // (IC > 0 reads the weights through scalar loads)
 
     float acc[4] = {0.f, 0.f, 0.f, 0.f};          // ic <= 4 output channels
@@ -110,6 +122,25 @@ void MIDD_OUT_KERNEL(const OutConvArgs a, const float* __restrict__ wglob /* == 
         const size_t o = (((size_t)b * ic + oc) * a.H + oy) * a.W + ox;
         float eps = acc[oc] + a.bias[oc];
         if (a.eps_out) a.eps_out[o] = eps;
+#if MIDD_OUT_SLOTS
+        if (a.x) {
+            // The update of the two kernels above with the record's coefficients, every contraction written out as hipcc makes it
+            // there (profiles/step_noise_isa.txt, profiles/slots_isa.txt): v_fma_f32 (-c2, eps, x), v_mul_f32 by c1, one fused
+            // multiply-add for the noise term, clamp.  A uniform table must give mi_denoise's bits (tests/test_gpu_slots.py, G1).
+#pragma clang fp contract(off)
+            if (a.clamp_eps) eps = fminf(fmaxf(eps, -5.0f), 5.0f);
+            float xn = rec.c1 * __builtin_fmaf(-rec.c2, eps, a.x[o]);
+            if (rec.active & SLOT_NOISE) {        // (t > 0 and the call has a noise term)
+                if (a.seeded) {
+                    const uint32_t elem = (uint32_t)oc * ((uint32_t)a.H * (uint32_t)a.W) + (uint32_t)oy * (uint32_t)a.W + (uint32_t)ox;
+                    xn = __builtin_fmaf(rec.c3, step_noise_value(a.seed, (long long)rec.image, (int)rec.iter, elem, 0u), xn);
+                } else if (a.noise) {
+                    xn = __builtin_fmaf(rec.c3, a.noise[o], xn);
+                }
+            }
+            a.x[o] = fminf(fmaxf(xn, 0.0f), 1.0f);
+        }
+#else
         if (a.x) {
             const float c1 = a.c1, c2 = a.c2, c3 = a.c3;
             const float* noise = a.noise;
@@ -141,5 +172,6 @@ void MIDD_OUT_KERNEL(const OutConvArgs a, const float* __restrict__ wglob /* == 
             }
             a.x[o] = fminf(fmaxf(xn, 0.0f), 1.0f);
         }
+#endif
     }
 }

@@ -5,6 +5,8 @@
 //                      fused with the sampler update of DiffusionDenoiser.denoise
 //                      (DDIMModel.py:278-284; cddpm noise term cddpmModels.py:297-303)
 //   out_conv_seeded_kernel : the same with the noise term drawn in the update (step_noise_common.h)
+//   out_conv_slots_kernel  : the same with every sample at its own timestep: coefficients, counter words and the active
+//                      flag from the sample's SlotRec (mi_denoise_slots); slot_fill_kernel writes a row's records
 //   step_noise_fill_kernel : the same noise values as a [n_iters,B,C,H,W] tensor (replay / export)
 //   ensemble_reduce_kernel : mean and unbiased std over the members of an ensemble of stochastic samples
 //   ensemble_broadcast_kernel : the condition image of an ensemble pass's virtual samples
@@ -353,6 +355,7 @@ constexpr int OC_PS = 20;         // padded pixel stride in floats
 // IC: output channels at compile time (1: the reference's grayscale case; 0: a.ic at run time, <= 4).  With the count
 // only known at run time hipcc indexes the accumulators through select chains and splits the 16-byte LDS reads:
 // 7 340 instructions, 989 v_cndmask among them, for a loop of 432 multiply-adds (round 3; tools/isa_count.py).
+#define MIDD_OUT_SLOTS 0
 #define MIDD_OUT_KERNEL out_conv_kernel
 #define MIDD_OUT_SEEDED 0
 #include "out_conv_body.h"
@@ -363,6 +366,15 @@ constexpr int OC_PS = 20;         // padded pixel stride in floats
 #include "out_conv_body.h"
 #undef MIDD_OUT_KERNEL
 #undef MIDD_OUT_SEEDED
+#undef MIDD_OUT_SLOTS
+// per-slot update (mi_denoise_slots): coefficients, counter words and the active flag from the sample's SlotRec
+#define MIDD_OUT_SLOTS 1
+#define MIDD_OUT_KERNEL out_conv_slots_kernel
+#define MIDD_OUT_SEEDED 0
+#include "out_conv_body.h"
+#undef MIDD_OUT_KERNEL
+#undef MIDD_OUT_SEEDED
+#undef MIDD_OUT_SLOTS
 
 hipError_t out_conv_launch(const OutConvArgs& a, hipStream_t s) {
     if (a.ic > 4 || a.C % 16) return hipErrorInvalidValue;
@@ -376,6 +388,18 @@ hipError_t out_conv_launch(const OutConvArgs& a, hipStream_t s) {
         else hipLaunchKernelGGL(out_conv_seeded_kernel<0>, dim3(a.B * tiles), dim3(256), lds, s, a, a.w);
     } else if (a.ic == 1) hipLaunchKernelGGL(out_conv_kernel<1>, dim3(a.B * tiles), dim3(256), lds, s, a, a.w);
     else hipLaunchKernelGGL(out_conv_kernel<0>, dim3(a.B * tiles), dim3(256), lds, s, a, a.w);
+    return hipGetLastError();
+}
+
+// a.seeded != 0: the noise term of the slots with SLOT_NOISE is drawn from (a.seed, rec.image, rec.iter, element, member 0); else it
+// is read from a.noise when that is given.  a.c1 .. a.c3, a.iter, a.sample_offset, a.v0, a.members and the tile fields are not read.
+hipError_t out_conv_slots_launch(const OutConvArgs& a, const SlotRec* slots, hipStream_t s) {
+    if (a.ic > 4 || a.C % 16 || !slots || !a.x) return hipErrorInvalidValue;
+    if (a.seeded && (a.noise || (unsigned long long)a.ic * a.H * a.W >= (1ull << 32))) return hipErrorInvalidValue;
+    const size_t lds = ((size_t)a.ic * 9 * a.C + 2 * a.C) * sizeof(float);
+    const int tiles = ((a.W + OC_T - 1) / OC_T) * ((a.H + OC_T - 1) / OC_T);
+    if (a.ic == 1) hipLaunchKernelGGL(out_conv_slots_kernel<1>, dim3(a.B * tiles), dim3(256), lds, s, a, a.w, slots);
+    else hipLaunchKernelGGL(out_conv_slots_kernel<0>, dim3(a.B * tiles), dim3(256), lds, s, a, a.w, slots);
     return hipGetLastError();
 }
 
@@ -745,6 +769,19 @@ hipError_t nhwc_to_nchw_launch(const float* src, float* dst, int B, int H, int W
 struct I32x32 { int v[32]; };
 __global__ void fill_i32_kernel(int* dst, I32x32 vals, int n) {
     if ((int)threadIdx.x < n) dst[threadIdx.x] = vals.v[threadIdx.x];
+}
+
+// One row of mi_denoise_slots for n <= SLOTS_PER_LAUNCH samples: their records travel as kernel arguments (copied when the launch
+// is enqueued: nothing on the device ever reads the caller's host tables) into the program's record region, and every sample's
+// time-table row into trow (0 for an idle slot: the network kernels still run over it).
+__global__ void slot_fill_kernel(int* trow, SlotRec* dst, SlotRecs recs, int n) {
+    if ((int)threadIdx.x < n) { trow[threadIdx.x] = recs.v[threadIdx.x].trow; dst[threadIdx.x] = recs.v[threadIdx.x]; }
+}
+
+hipError_t slot_fill_launch(int* trow, SlotRec* dst, const SlotRecs& recs, int n, hipStream_t s) {
+    if (n < 1 || n > SLOTS_PER_LAUNCH) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(slot_fill_kernel, dim3(1), dim3(SLOTS_PER_LAUNCH), 0, s, trow, dst, recs, n);
+    return hipGetLastError();
 }
 
 hipError_t fill_i32_launch(int* dst, const int* host_vals, int n, hipStream_t s) {

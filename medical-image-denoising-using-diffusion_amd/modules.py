@@ -91,6 +91,7 @@ class UNetDiffusion(nn.Module):
         self._lock = threading.RLock()
         self._workspaces: Dict[Tuple[int, int, int, int, int], torch.Tensor] = {}
         self._ensemble_ws: Optional[Tuple[tuple, torch.Tensor]] = None      # the one resident run_ensemble workspace: (key, tensor)
+        self._slots_ws: Optional[Tuple[tuple, torch.Tensor]] = None         # the one resident workspace of a session's run_slots calls
         # After every native call the status word of its workspace is read back (mi_status: one 4-byte copy, synchronises the
         # stream): NaN / Inf activations or an operand beyond the fp16 range (f16x3, f16) raise MiddError instead of returning garbage.
         # Set to False (env MIDD_CHECK_STATUS=0) to keep forward() / denoise() asynchronous; the output is NaN then, as torch's.
@@ -156,6 +157,7 @@ class UNetDiffusion(nn.Module):
         self._stamp = stamp
         self._workspaces.clear()
         self._ensemble_ws = None
+        self._slots_ws = None
         return self._plan
 
     MAX_WORKSPACES = 4       # resident (shape, stream) workspaces; least recently used is dropped first
@@ -294,6 +296,76 @@ class UNetDiffusion(nn.Module):
                 native.check(native.lib().mi_denoise(*head, nptr, *tail))
             self._raise_on_status(wptr, stream)
         return out
+
+    @torch.no_grad()
+    def run_slots(self, cond: torch.Tensor, x: torch.Tensor, t_rows, beta: torch.Tensor, alpha: torch.Tensor, alpha_hat: torch.Tensor,
+                  clamp_eps: bool, iter_base=None, sample_index=None, step_noise: Optional[torch.Tensor] = None,
+                  seed: Optional[int] = None, no_split: bool = False, max_slots: Optional[int] = None) -> torch.Tensor:
+        """The sampler loop with per-slot timesteps (mi_denoise_slots): ``t_rows`` [n_rows][B] holds every slot's timestep per row,
+        -1 = idle.  ``x`` [B,C,H,W] is updated IN PLACE (and returned) and is not initialised: a caller starting a slot copies its
+        condition image into it; both tensors must be contiguous.  ``iter_base`` [B]: rows a slot has already run;
+        ``sample_index`` [B]: its global image index (seeded noise).  ``max_slots``: the workspace is sized for every batch up to
+        this many slots and kept, so that a session whose batch changes from call to call allocates once."""
+        from .sampler import check_seed
+        if seed is not None:
+            if step_noise is not None:
+                raise ValueError("pass either seed or step_noise, not both")
+            seed, _ = check_seed(seed, 0)
+        self._check_image(cond, "cond")
+        self._check_image(x, "x")
+        if x.shape != cond.shape or x.device != cond.device or not x.is_contiguous() or not cond.is_contiguous():
+            raise ValueError("x must match cond in shape and device, and both must be contiguous (x is updated in place)")
+        B, _, H, W = cond.shape
+        rows = np.ascontiguousarray(np.asarray(t_rows, dtype=np.int32).reshape(-1, B) if B else np.zeros((0, 0), np.int32))
+        n_rows = int(rows.shape[0])
+        ib = None if iter_base is None else np.ascontiguousarray(np.asarray(iter_base, dtype=np.int64))
+        si = None if sample_index is None else np.ascontiguousarray(np.asarray(sample_index, dtype=np.int64))
+        for v, what in ((ib, "iter_base"), (si, "sample_index")):
+            if v is not None and v.shape != (B,):
+                raise ValueError(f"{what} must have one entry per slot ({B})")
+        if ib is not None:
+            if ib.size and (ib.min() < -(1 << 31) or ib.max() >= 1 << 31):
+                raise ValueError("iter_base must fit 32 bits")
+            ib = ib.astype(np.int32)
+        tabs = [np.ascontiguousarray(v.detach().to("cpu", torch.float32).numpy()) for v in (beta, alpha, alpha_hat)]
+        noise_steps = int(tabs[0].shape[0])
+        with self._lock, torch.cuda.device(cond.device):
+            plan = self._ensure_plan(time_rows=noise_steps)
+            nptr = None
+            if step_noise is not None:
+                if step_noise.shape != (n_rows,) + tuple(cond.shape) or step_noise.device != cond.device:
+                    raise ValueError("step_noise must be [n_rows,B,C,H,W] on the image's device")
+                step_noise = step_noise.to(torch.float32).contiguous()
+                nptr = step_noise.data_ptr()
+            ws = self._workspace(B, H, W, cond.device) if not max_slots else self._slots_workspace(max(int(max_slots), B), H, W, cond.device)
+            if self.poison_workspace is not None:
+                ws.fill_(self.poison_workspace)
+            wptr, wbytes = self._aligned_ptr(ws)
+            stream = torch.cuda.current_stream(cond.device).cuda_stream
+            fp = C.POINTER(C.c_float)
+            native.check(native.lib().mi_denoise_slots(
+                plan, cond.data_ptr(), x.data_ptr(), B, H, W, rows.ctypes.data_as(C.POINTER(C.c_int32)), n_rows,
+                None if ib is None else ib.ctypes.data_as(C.POINTER(C.c_int32)),
+                None if si is None else si.ctypes.data_as(C.POINTER(C.c_int64)),
+                tabs[0].ctypes.data_as(fp), tabs[1].ctypes.data_as(fp), tabs[2].ctypes.data_as(fp), noise_steps,
+                nptr, 0 if seed is None else 1, C.c_uint64(seed or 0),
+                (native.MI_CLAMP_EPS if clamp_eps else 0) | (native.MI_NO_SPLIT if no_split else 0), wptr, wbytes, stream))
+            self._raise_on_status(wptr, stream)
+        return x
+
+    def _slots_workspace(self, max_slots: int, H: int, W: int, dev: torch.device) -> torch.Tensor:
+        """Scratch of the run_slots calls of one session: large enough for every batch of 1 .. max_slots slots, one resident entry
+        beside the (shape, stream) cache, so a batch that changes from call to call neither allocates nor evicts."""
+        key = (max_slots, H, W, dev.index, torch.cuda.current_stream(dev).cuda_stream)
+        if self._slots_ws is not None and self._slots_ws[0] == key:
+            return self._slots_ws[1]
+        sizes = [native.lib().mi_workspace_bytes(self._plan, b, H, W) for b in range(1, max_slots + 1)]
+        if min(sizes) == 0:
+            native.check(-1)
+        self._slots_ws = None                     # (free the old one before the new one is allocated)
+        ws = torch.empty(max(sizes) + 256, dtype=torch.uint8, device=dev)
+        self._slots_ws = (key, ws)
+        return ws
 
     @torch.no_grad()
     def run_ensemble(self, noisy: torch.Tensor, t_list, beta: torch.Tensor, alpha: torch.Tensor, alpha_hat: torch.Tensor,

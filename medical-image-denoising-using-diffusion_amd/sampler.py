@@ -293,5 +293,36 @@ class DiffusionDenoiser:
                                                   max_batch=max_batch, want_tiles=return_tiles)
         return TiledResult(image, tiles, plan.origins_y, plan.origins_x, seed)
 
+    def _draw_seed(self) -> int:
+        hi, lo = torch.randint(0, 1 << 32, (2,), dtype=torch.int64).tolist()
+        return (hi << 32) | lo
+
+    @torch.no_grad()
+    def denoise_ragged(self, noisy_img: torch.Tensor, inference_steps: Sequence[int], seed: Optional[int] = None,
+                       sample_offset: int = 0) -> torch.Tensor:
+        """Every image of the batch with its OWN step count, in one native call (mi_denoise_slots; not a reference call):
+        image b is ``denoise(noisy_img[b:b+1], inference_steps[b], seed=seed, sample_offset=sample_offset + b)`` -- bit for bit
+        with ``batch_invariant=True``, within the parity gate otherwise.  The loop runs max(iterations) rows; an image whose
+        list has ended idles (its pixels are not touched again).  cddpm: always seeded; ``seed=None`` draws one as
+        ``denoise_ensemble`` does (the run then cannot be repeated: pass a seed to keep it).  DDIM ignores ``seed``."""
+        counts = list(inference_steps)
+        if not isinstance(noisy_img, torch.Tensor) or noisy_img.dim() != 4 or len(counts) != noisy_img.shape[0]:
+            raise ValueError(f"inference_steps must hold one step count per image ({len(counts)} for a batch of "
+                             f"{noisy_img.shape[0] if isinstance(noisy_img, torch.Tensor) and noisy_img.dim() else '?'})")
+        stochastic = getattr(self.model, "variant", "ddim") == "cddpm"
+        if stochastic:
+            seed, sample_offset = check_seed(self._draw_seed() if seed is None else seed, sample_offset)
+        else:
+            seed = None
+            _, sample_offset = check_seed(0, sample_offset)
+        self.model.eval()
+        lists = [timestep_list(self.noise_steps, _integer(k, "inference_steps", 1 << 31)) for k in counts]
+        n_rows = max((len(t) for t in lists), default=0)
+        rows = [[t[i] if i < len(t) else -1 for t in lists] for i in range(n_rows)]
+        cond = noisy_img.contiguous()
+        x = cond.clone()
+        return self.model.run_slots(cond, x, rows, self.beta, self.alpha, self.alpha_hat, clamp_eps=not stochastic,
+                                    sample_index=[sample_offset + b for b in range(len(counts))], seed=seed)
+
     # north_star's wording for the same call
     ddim_sample = denoise

@@ -16,6 +16,10 @@ The sampler call runs in a worker thread (``asyncio.to_thread``, as run.py:85) o
 resizes, the ToTensor scaling and the uint8 conversion also run on the device (``prepost``; bit-identical to the
 PIL / numpy recipe, which stays as ``preprocess`` / ``tensor_to_base64`` for CPU tensors and tests).
 
+Not in the reference: ``DiffusionService(batch_slots=N)`` (or ``MIDD_BATCH_SLOTS=N``), N > 0, runs the sampler calls of concurrent
+requests as the slots of ONE ``SamplerSession`` owned by one worker thread (continuous batching, session.py) instead of one
+batch-1 call per request.  0, the default, is the path above, unchanged.
+
 ``python-multipart`` is not available in this image, so the multipart body is parsed with the
 standard library instead of FastAPI's ``UploadFile``; the wire format is the same.
 """
@@ -24,6 +28,8 @@ standard library instead of FastAPI's ``UploadFile``; the wire format is the sam
 import asyncio
 import base64
 import io
+import os
+import threading
 import time
 from email.parser import BytesParser
 from email.policy import HTTP
@@ -98,8 +104,19 @@ class DiffusionService:
     """Counterpart of ModelManager's diffusion members (run.py:20-42,103-111)."""
 
     def __init__(self, checkpoint: Optional[str] = None, device: Optional[torch.device] = None,
-                 denoise_fn: Optional[Callable[[torch.Tensor], torch.Tensor]] = None, compute: Optional[str] = None):
+                 denoise_fn: Optional[Callable[[torch.Tensor], torch.Tensor]] = None, compute: Optional[str] = None,
+                 batch_slots: Optional[int] = None, batch_invariant: Optional[bool] = None, session_factory=None):
         self.compute = compute                 # arithmetic of the network (UNetDiffusion); None: the default
+        self.batch_invariant = batch_invariant # UNetDiffusion's argument; None: its default
+        # > 0: concurrent requests share one SamplerSession of this many slots, run by one worker thread; 0: one call per request
+        self.batch_slots = int(os.environ.get("MIDD_BATCH_SLOTS", "0")) if batch_slots is None else int(batch_slots)
+        if self.batch_slots < 0:
+            raise ValueError("batch_slots must be >= 0")
+        self._session_factory = session_factory    # tests inject a stand-in: (service) -> an object with submit / step / pending / fail_pending
+        self._session = None
+        self._worker: Optional[threading.Thread] = None
+        self._wake = threading.Condition()
+        self._stopping = False
         self.device = device or torch.device("cuda" if torch.cuda.is_available() else "cpu")
         self.checkpoint = checkpoint
         self.diffusion_model = None
@@ -109,7 +126,8 @@ class DiffusionService:
 
     def load_models(self) -> None:
         model = UNetDiffusion(in_channels=1, model_channels=48, channel_mult=(1, 2, 3, 4), num_res_blocks=2,
-                              attention_resolutions=(3,), dropout=0.0, time_emb_dim=192, compute=self.compute)
+                              attention_resolutions=(3,), dropout=0.0, time_emb_dim=192, compute=self.compute,
+                              batch_invariant=self.batch_invariant)
         noise_steps = 50
         if self.checkpoint:
             ckpt = torch.load(self.checkpoint, map_location="cpu", weights_only=True)
@@ -126,12 +144,65 @@ class DiffusionService:
         with torch.no_grad():
             if self._denoise_fn is not None:
                 output = self._denoise_fn(input_tensor)
+            elif self.batch_slots > 0:
+                output = self._submit(input_tensor).result()      # raises what the worker met: the route then answers null
             else:
                 output = self.diffusion_denoiser.denoise(input_tensor, inference_steps=SERVE_INFERENCE_STEPS)
             output = torch.clamp(output, 0, 1)
             result = (tensor_to_base64_device if output.is_cuda else tensor_to_base64)(output, original_size)
         print(f"  Diffusion: {time.time() - start:.2f}s")
         return result
+
+    # ---- batch_slots > 0: one worker thread owns the session; requests submit and wait on their ticket
+    def _make_session(self):
+        if self._session_factory is not None:
+            return self._session_factory(self)
+        from .session import SamplerSession
+        return SamplerSession(self.diffusion_denoiser, SERVE_SIZE[0], SERVE_SIZE[1], slots=self.batch_slots)
+
+    def _submit(self, input_tensor: torch.Tensor):
+        with self._wake:
+            if self._worker is None or not self._worker.is_alive():      # first request, or the thread is gone: start it
+                if self._session is None:
+                    self._session = self._make_session()
+                self._stopping = False
+                self._worker = threading.Thread(target=self._work, name="midd-batch-worker", daemon=True)
+                self._worker.start()
+            ticket = self._session.submit(input_tensor, SERVE_INFERENCE_STEPS)
+            self._wake.notify()
+        return ticket
+
+    def _work(self) -> None:
+        """The worker: steps the session while anything is pending, sleeps on the condition otherwise.  An exception of a step
+        fails the requests that wait (they answer "diffusion": null) and the loop goes on: the worker never dies silently."""
+        session = self._session
+        while True:
+            with self._wake:
+                while not self._stopping and not session.pending():
+                    self._wake.wait()
+                if self._stopping:
+                    return
+            try:
+                with torch.no_grad():
+                    session.step()
+            except BaseException as exc:          # noqa: BLE001 -- reported through every waiting ticket
+                print(f"  batch worker: {type(exc).__name__}: {exc}")
+                try:
+                    session.fail_pending(exc)
+                except BaseException as exc2:     # noqa: BLE001
+                    print(f"  batch worker: could not fail the pending requests: {exc2}")
+
+    def close(self) -> None:
+        """Stops the batch worker (if any); waiting requests fail."""
+        with self._wake:
+            self._stopping = True
+            self._wake.notify_all()
+        if self._worker is not None:
+            self._worker.join(timeout=30)
+            self._worker = None
+        if self._session is not None:
+            self._session.fail_pending(RuntimeError("the service was closed"))
+            self._session = None
 
     async def process_all_models(self, input_tensor: torch.Tensor, original_size: Tuple[int, int]) -> dict:
         """run.py:80-101 with the three out-of-scope branches reported as null."""
@@ -168,6 +239,7 @@ def create_app(service: Optional[DiffusionService] = None, checkpoint: Optional[
         if svc.diffusion_model is None and svc._denoise_fn is None:
             svc.load_models()
         yield
+        svc.close()
 
     app = FastAPI(title="X-Ray Denoising API", description="diffusion branch on MI355X", version="2.0.0", lifespan=lifespan)
     app.add_middleware(CORSMiddleware, allow_origins=["*"], allow_credentials=True, allow_methods=["*"], allow_headers=["*"])
@@ -192,7 +264,7 @@ def create_app(service: Optional[DiffusionService] = None, checkpoint: Optional[
 
     @app.get("/health")
     async def health_check():
-        return {"status": "healthy", "device": str(svc.device),
+        return {"status": "healthy", "device": str(svc.device), "batch_slots": svc.batch_slots,
                 "models_loaded": {"diffusion": svc.diffusion_model is not None or svc._denoise_fn is not None,
                                   "nafnet": False, "expert": False, "hybrid": False}}
 
