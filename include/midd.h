@@ -306,6 +306,62 @@ int mi_denoise_tiled(mi_plan* plan, const float* noisy, float* image_out, float*
  * planner alone: it works before mi_unet_finalize too.  0 on bad arguments (mi_last_error says which). */
 size_t mi_tiled_workspace_bytes(mi_plan* plan, int B, int H, int W, int th, int tw, int oy, int ox, int pass_samples, int tiles_external);
 
+/* ENSEMBLES OF TILED RUNS: `members` seeded draws of B full-resolution images, their per-pixel mean and unbiased standard
+ * deviation at the images' own size.  Member m is mi_denoise_tiled's seeded run with the counter word c3 = member_offset + m
+ * (c0: the pixel's index in the whole image, c1: sample_offset + image, as there), so member 0 at member_offset 0 IS that run,
+ * bit for bit, and a tile of member m is mi_denoise of its crop with the crop of mi_step_noise_fill_member of member
+ * member_offset + m.
+ * Members are the OUTER loop: inside a member the B * ny * nx (image, tile) virtual samples run exactly as mi_denoise_tiled runs
+ * them -- extract, then the sampler loop, in passes of at most pass_samples consecutive virtual samples, each pass split over two
+ * streams as a mi_denoise batch of that size is (MI_NO_SPLIT honoured).  A pass never spans two members (the member word is a
+ * launch constant of the update), so a member whose B * ny * nx is no multiple of pass_samples ends in a shorter pass.  ONE
+ * mi_tile_blend_reduce launch follows the last pass of the last member.
+ *   noisy        device fp32 [B,C,H,W]; never written
+ *   mean_out     device fp32 [B,C,H,W] or NULL
+ *   std_out      device fp32 [B,C,H,W] or NULL; needs members >= 2
+ *   samples_out  device fp32 [B,members,C,H,W] or NULL: the blended image of every member
+ *   tiles_out    device fp32 [members,B,ny*nx,C,th,tw] or NULL: the denoised tiles in run order -- slice m is the tiles_out of
+ *                mi_denoise_tiled for member m (NULL: they live in the workspace).  At least one of the four outputs is given
+ *   t_list .. noise_steps   as mi_denoise
+ *   seed, sample_offset     as mi_denoise_seeded (sample_offset counts IMAGES)
+ *   member_offset  member index of member 0 of this call, as in mi_denoise_ensemble
+ *   pass_samples, flags     as mi_denoise_tiled
+ * There is no unseeded form and no `seeded` switch: a deterministic sampler has no ensemble.  With a batch-invariant plan every tile output is a function of its crop and of (seed,
+ * image, position, member) alone: not of B, members, pass_samples or the stream.
+ * MI_EINVAL before any GPU work, with the limit named in mi_last_error: everything mi_denoise_tiled refuses; members < 1;
+ * member_offset < 0; member_offset + members > 2^32 (4294967296); B * members * tiles > 2^31 - 1 (2147483647); no output pointer;
+ * std_out with members < 2; any two of noisy, mean_out, std_out, samples_out, tiles_out overlapping.
+ * The status word (mi_status) is cleared once per call and accumulates over the passes of every member.  Allocates nothing;
+ * asynchronous. */
+int mi_denoise_tiled_ensemble(mi_plan* plan, const float* noisy, float* mean_out, float* std_out, float* samples_out, float* tiles_out,
+                              int B, int members, int H, int W, int th, int tw, int oy, int ox,
+                              const int32_t* t_list, int n_iters,
+                              const float* beta, const float* alpha, const float* alpha_hat, int noise_steps,
+                              uint64_t seed, int64_t sample_offset, int64_t member_offset, int pass_samples, int flags,
+                              void* workspace, size_t workspace_bytes, void* stream);
+
+/* Bytes of workspace mi_denoise_tiled_ensemble needs: what mi_tiled_workspace_bytes answers for the same pass with
+ * tiles_external != 0 (the sampler workspace of a pass of tiles + the pass's condition tiles; the passes of one member are those of
+ * mi_denoise_tiled) + -- unless tiles_external != 0, i.e. tiles_out is given -- the tile outputs of every member,
+ * members * B * ny*nx * C*th*tw * 4 bytes.  Host only, answered from the planner alone: it works before mi_unet_finalize too.
+ * 0 on bad arguments (mi_last_error says which). */
+size_t mi_tiled_ensemble_workspace_bytes(mi_plan* plan, int B, int members, int H, int W, int th, int tw, int oy, int ox,
+                                         int pass_samples, int tiles_external);
+
+/* The reduction of mi_denoise_tiled_ensemble on its own (no plan needed): tiles device fp32 [members][B][ny*nx][C][th][tw] ->
+ * mean_out [B][C][H][W], std_out [B][C][H][W] or NULL (members >= 2) and samples_out [B][members][C][H][W] or NULL, the blended image
+ * of every member.  One kernel; a thread owns one output element of one image.  THE ARITHMETIC (fixed, per pixel, independent of
+ * the launch geometry, no atomics, no fused multiply-add) is the composition of the two specifications above, bit for bit:
+ *   for m = 0 .. members-1:  v_m = the pixel of mi_tile_blend over tiles[m][b]  (a float: (float)(num / den))
+ *   (mean, std) = the arithmetic of mi_ensemble_reduce over v_0 .. v_{members-1}, in index order
+ * so the outputs equal mi_tile_blend of every member followed by mi_ensemble_reduce, and are the same bits with and without
+ * samples_out (the v_m are formed again from the tiles for the deviations; nothing is read back).
+ * MI_EINVAL: the cases of mi_tile_blend (geometry rules, C*H*W >= 2^32, B * tiles > 2^31 - 1, overlap > 46339) and of
+ * mi_ensemble_reduce (B outside [1, 65535], members < 1, null tiles / mean_out, std_out with members < 2), and
+ * B * members * tiles > 2^31 - 1.  tiles and the three outputs must not overlap. */
+int mi_tile_blend_reduce(const float* tiles, int B, int members, int C, int H, int W, int th, int tw, int oy, int ox,
+                         float* mean_out, float* std_out, float* samples_out, void* stream);
+
 /* Status of the last mi_unet_forward / mi_denoise call that used `workspace` (its first word; the calls clear it when they
  * start).  SYNCHRONISES `stream` (one 4-byte device-to-host copy).  Returns MI_OK with *flags == 0, or MI_ERANGE with the
  * MI_STATUS_* bits in *flags: the kernels never turn a NaN / Inf activation or an operand beyond the split-fp16 range into

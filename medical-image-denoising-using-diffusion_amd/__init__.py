@@ -9,6 +9,6 @@ the C ABI declared in ``include/midd.h``.  There is no CPU fallback: without the
 """
 from .config import UNetConfig, topology, param_shapes, timestep_list  # noqa: F401
 from .modules import UNetDiffusion  # noqa: F401
-from .sampler import (DiffusionDenoiser, EnsembleResult, TilePlan, TiledResult, device, ensemble_reduce, step_noise,  # noqa: F401
-                      tile_blend, tile_extract, tile_plan)
+from .sampler import (DiffusionDenoiser, EnsembleResult, TilePlan, TiledEnsembleResult, TiledResult, device, ensemble_reduce,  # noqa: F401
+                      step_noise, tile_blend, tile_blend_reduce, tile_extract, tile_plan)
 from .session import SamplerSession, Ticket  # noqa: F401

@@ -686,6 +686,106 @@ extern "C" int mi_denoise_tiled(mi_plan* plan, const float* noisy, float* image_
     return MI_OK;
 }
 
+// ---------------------------------------------------------------------------- ensembles of tiled runs
+// members x B images x tiles: the tile storage is indexed by a 32-bit int (check_tile_count has judged B * tiles)
+static int check_tiled_ensemble_size(int B, int members, const TileGeom& g) {
+    if ((int64_t)B * g.ny * g.nx * members > 2147483647ll)
+        return fail(MI_EINVAL, "B * members * tiles = %d * %d * %d * %d exceeds 2^31 - 1: the tile index of the member storage is a 32-bit int "
+                    "(limit: B * members * tiles <= 2147483647)", B, members, g.ny, g.nx);
+    return MI_OK;
+}
+
+int midd::check_tiled_ensemble_args(mi_plan* plan, int B, int members, int H, int W, int th, int tw, int oy, int ox,
+                                    int64_t sample_offset, int64_t member_offset, int pass_samples, TileGeom* g) {
+    if (int rc = check_tiled_args(plan, B, H, W, th, tw, oy, ox, sample_offset, pass_samples, g)) return rc;
+    if (int rc = check_members(members, member_offset)) return rc;
+    return check_tiled_ensemble_size(B, members, *g);
+}
+
+extern "C" int mi_tile_blend_reduce(const float* tiles, int B, int members, int C, int H, int W, int th, int tw, int oy, int ox,
+                                    float* mean_out, float* std_out, float* samples_out, void* stream) {
+    TileGeom g{};
+    if (C < 1) return fail(MI_EINVAL, "C %d must be positive", C);
+    if (int rc = fill_tile_geom(C, H, W, th, tw, oy, ox, &g)) return rc;
+    if (int rc = check_tile_count(B, g)) return rc;
+    if (int rc = check_step_noise_range(C, H, W, 0)) return rc;
+    if (members < 1) return fail(MI_EINVAL, "members %d: an ensemble has at least one member (limit: members >= 1)", members);
+    if (B > 65535) return fail(MI_EINVAL, "B %d outside [1, 65535] (the limit of mi_ensemble_reduce, whose arithmetic this call composes)", B);
+    if (int rc = check_tiled_ensemble_size(B, members, g)) return rc;
+    if (std_out && members < 2) return fail(MI_EINVAL, "std_out needs members >= 2: the unbiased standard deviation of one value is undefined");
+    if (!tiles || !mean_out) return fail(MI_EINVAL, "null argument");
+    const hipError_t e = tile_blend_reduce_launch(tiles, B, members, g, mean_out, std_out, samples_out, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(MI_EHIP, "tile_blend_reduce: %s", hipGetErrorString(e));
+    return MI_OK;
+}
+
+// Members are the outer loop: member m is mi_denoise_tiled's seeded pass structure with counter word c3 = member_offset + m, a
+// launch constant of the update kernel, so no pass spans two members.  Its tiles are slice m of the storage [members][B][tiles].
+extern "C" int mi_denoise_tiled_ensemble(mi_plan* plan, const float* noisy, float* mean_out, float* std_out, float* samples_out, float* tiles_out,
+                                         int B, int members, int H, int W, int th, int tw, int oy, int ox,
+                                         const int32_t* t_list, int n_iters,
+                                         const float* beta, const float* alpha, const float* alpha_hat, int noise_steps,
+                                         uint64_t seed, int64_t sample_offset, int64_t member_offset, int pass_samples, int flags,
+                                         void* workspace, size_t workspace_bytes, void* stream) {
+    TileGeom tg{};
+    if (int rc = check_tiled_ensemble_args(plan, B, members, H, W, th, tw, oy, ox, sample_offset, member_offset, pass_samples, &tg)) return rc;
+    if (!mean_out && !std_out && !samples_out && !tiles_out)
+        return fail(MI_EINVAL, "no output: give at least one of mean_out, std_out, samples_out, tiles_out");
+    if (std_out && members < 2) return fail(MI_EINVAL, "std_out needs members >= 2: the unbiased standard deviation of one value is undefined");
+    const int K = tg.ny * tg.nx;
+    const size_t chw = (size_t)tg.C * th * tw;
+    {   // noisy is read by every pass and the reduce reads the tiles while it writes the other three: no two of the five may overlap
+        const size_t img = (size_t)tg.C * H * W * sizeof(float);
+        const struct { const void* p; size_t n; const char* name; } buf[5] = {
+            {noisy, (size_t)B * img, "noisy"}, {mean_out, (size_t)B * img, "mean_out"}, {std_out, (size_t)B * img, "std_out"},
+            {samples_out, (size_t)B * members * img, "samples_out"}, {tiles_out, (size_t)members * B * K * chw * sizeof(float), "tiles_out"}};
+        for (int i = 0; i < 5; ++i)
+            for (int j = i + 1; j < 5; ++j) {
+                const uintptr_t a = (uintptr_t)buf[i].p, b = (uintptr_t)buf[j].p;
+                if (a && b && a < b + buf[j].n && b < a + buf[i].n)
+                    return fail(MI_EINVAL, "%s and %s alias (overlap): noisy is read by every pass and the reduce reads the tiles while it "
+                                "writes mean_out, std_out and samples_out", buf[i].name, buf[j].name);
+            }
+    }
+    if (!plan->finalized) return fail(MI_ESTATE, "mi_unet_finalize has not been called (or weights changed since)");
+    EnsembleLayout L{};
+    if (int rc = tiled_ensemble_layout(plan, B, members, K, th, tw, pass_samples, tiles_out != nullptr, &L)) return rc;
+    if (!workspace || workspace_bytes < L.bytes) return fail(MI_ENOMEM, "workspace too small: need %zu bytes, got %zu", L.bytes, workspace_bytes);
+    if (((uintptr_t)workspace) & 255) return fail(MI_EINVAL, "workspace must be 256-byte aligned");
+    if (!noisy) return fail(MI_EINVAL, "null argument");
+    if (int rc = check_schedule(plan, t_list, n_iters, beta, alpha, alpha_hat, noise_steps)) return rc;
+    if (int rc = check_device(plan)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    char* ws = (char*)workspace;
+    float* cond = reinterpret_cast<float*>(ws + L.cond_off);
+    float* tiles = tiles_out ? tiles_out : reinterpret_cast<float*>(ws + L.samples_off);
+    const int64_t V = (int64_t)B * K;                       // virtual samples of ONE member
+    std::lock_guard<std::mutex> side_lk(plan->side_mu);     // held over all passes: the side streams are per plan
+    HIPCHK(hipMemsetAsync(ws, 0, 256, s));                  // status word: once per call, the passes of every member accumulate into it
+    StepNoise sn;
+    sn.seeded = true; sn.seed = seed; sn.sample_offset = sample_offset; sn.members = K;
+    sn.tiles_x = tg.nx; sn.tiles_y = tg.ny; sn.img_H = H; sn.img_W = W;
+    RunRows rows; rows.t = t_list; rows.n = n_iters;
+    for (int m = 0; m < members; ++m) {
+        sn.member_offset = (uint32_t)(member_offset + m);
+        for (int64_t v0 = 0; v0 < V; v0 += L.pass) {
+            const int n = (int)(V - v0 < L.pass ? V - v0 : L.pass);
+            const hipError_t e = tile_extract_launch(noisy, cond, tg, (int)v0, n, s);
+            if (e != hipSuccess) return fail(MI_EHIP, "tile_extract: %s", hipGetErrorString(e));
+            sn.v0 = (int)v0;
+            Program* g = nullptr;
+            float* x = tiles + ((size_t)m * V + (size_t)v0) * chw;
+            if (int rc = check_run(plan, cond, x, n, th, tw, t_list, n_iters, beta, alpha, alpha_hat, noise_steps, ws, L.run_bytes, &g)) return rc;
+            if (int rc = enqueue_run(plan, g, cond, x, n, th, tw, rows, beta, alpha, alpha_hat, sn, flags, ws, L.run_bytes, stream)) return rc;
+        }
+    }
+    if (mean_out || std_out || samples_out) {
+        const hipError_t e = tile_blend_reduce_launch(tiles, B, members, tg, mean_out, std_out, samples_out, s);
+        if (e != hipSuccess) return fail(MI_EHIP, "tile_blend_reduce: %s", hipGetErrorString(e));
+    }
+    return MI_OK;
+}
+
 extern "C" int mi_debug_fetch(mi_plan* plan, const char* module_name, int B, int H, int W, const void* workspace,
                               float* dst, int* C, int* h, int* w, void* stream) {
     if (!plan || !module_name) return fail(MI_EINVAL, "null argument");

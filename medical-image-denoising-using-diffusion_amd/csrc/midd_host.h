@@ -116,6 +116,12 @@ int check_ensemble_args(mi_plan* p, int B, int members, int H, int W, int64_t sa
 // mi_denoise_tiled: its argument rules (no GPU work) -> the geometry; its workspace is an EnsembleLayout with members = tiles per
 // image at the tile's shape: [sampler workspace of a pass | condition tiles of a pass | tile outputs (unless tiles_out is given)]
 int check_tiled_args(mi_plan* p, int B, int H, int W, int th, int tw, int oy, int ox, int64_t sample_offset, int pass_samples, TileGeom* g);   // midd_exec.hip
+// mi_denoise_tiled_ensemble: the rules of mi_denoise_tiled and of an ensemble's members (no GPU work) -> the geometry; its workspace
+// is mi_denoise_tiled's -- a pass never spans two members -- with the tile outputs of every member: [sampler workspace of a pass |
+// condition tiles of a pass | tile outputs [members][B][tiles] (unless tiles_out is given)]
+int check_tiled_ensemble_args(mi_plan* p, int B, int members, int H, int W, int th, int tw, int oy, int ox, int64_t sample_offset,
+                              int64_t member_offset, int pass_samples, TileGeom* g);   // midd_exec.hip
+int tiled_ensemble_layout(mi_plan* p, int B, int members, int tiles, int th, int tw, int pass_samples, bool tiles_external, EnsembleLayout* L);   // midd_planner.hip
 }  // namespace midd
 
 struct mi_plan {

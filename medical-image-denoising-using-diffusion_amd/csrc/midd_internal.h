@@ -242,6 +242,10 @@ struct TileGeom { int C, H, W, th, tw, oy, ox, ny, nx; };
 hipError_t tile_extract_launch(const float* noisy, float* dst, const TileGeom& g, int v0, int n, hipStream_t s);
 // out [B][C][H][W] <- the window-weighted mean of the tiles [B][ny*nx][C][th][tw] over every pixel; fixed double arithmetic
 hipError_t tile_blend_launch(const float* tiles, float* out, int B, const TileGeom& g, hipStream_t s);
+// tiles [M][B][ny*nx][C][th][tw] -> mean, unbiased std [B][C][H][W] over the M blended members and the blended members themselves,
+// samples [B][M][C][H][W]; each of the three may be null (not all; std needs M >= 2).  The arithmetic of tile_blend_launch per
+// member, then of ensemble_reduce_launch over the members.  B * M * ny*nx <= 2^31 - 1
+hipError_t tile_blend_reduce_launch(const float* tiles, int B, int M, const TileGeom& g, float* mean, float* std, float* samples, hipStream_t s);
 
 // bilinear resize of an activation tensor, either layout (align_corners=False), any size ratio
 hipError_t resize_bilinear_launch(const float* src, float* dst, stat_word* tot, int rep, int bs, int B, int H, int W, int C, int OH, int OW, int blocked, hipStream_t s);

@@ -341,6 +341,21 @@ extern "C" size_t mi_tiled_workspace_bytes(mi_plan* plan, int B, int H, int W, i
     return L.bytes;
 }
 
+int midd::tiled_ensemble_layout(mi_plan* p, int B, int members, int tiles, int th, int tw, int pass_samples, bool tiles_external, EnsembleLayout* L) {
+    if (int rc = ensemble_layout(p, B, tiles, th, tw, pass_samples, true, L)) return rc;      // the passes of one member
+    if (!tiles_external) L->bytes += (size_t)members * B * tiles * p->cfg.in_channels * th * tw * sizeof(float);
+    return MI_OK;
+}
+
+extern "C" size_t mi_tiled_ensemble_workspace_bytes(mi_plan* plan, int B, int members, int H, int W, int th, int tw, int oy, int ox,
+                                                    int pass_samples, int tiles_external) {
+    TileGeom g{};
+    if (check_tiled_ensemble_args(plan, B, members, H, W, th, tw, oy, ox, 0, 0, pass_samples, &g)) return 0;
+    EnsembleLayout L{};
+    if (tiled_ensemble_layout(plan, B, members, g.ny * g.nx, th, tw, pass_samples, tiles_external != 0, &L)) return 0;
+    return L.bytes;
+}
+
 // Kernel symbol + algorithmic work of one op (for mi_profile_*).
 void midd::op_work(mi_plan* p, Program* g, const Op& o, std::string* name, double* flops, double* bytes) {
     const double B = g->B;

@@ -11,6 +11,7 @@
 //   ensemble_reduce_kernel : mean and unbiased std over the members of an ensemble of stochastic samples
 //   ensemble_broadcast_kernel : the condition image of an ensemble pass's virtual samples
 //   tile_extract_kernel / tile_blend_kernel : overlapping network-sized tiles of a larger image, and their blend (mi_denoise_tiled)
+//   tile_blend_reduce_kernel : blend of every member's tiles and mean / std over the blended members (mi_denoise_tiled_ensemble)
 //   resize_bilinear  : F.interpolate(mode='bilinear', align_corners=False) (DDIMModel.py:242)
 //   conv_transpose   : ConvTranspose2d(C,C,4,2,1) (DDIMModel.py:211) for topologies where the
 //                      planner cannot fold it into a 3x3 (never on the default networks)
@@ -607,6 +608,79 @@ hipError_t tile_blend_launch(const float* tiles, float* out, int B, const TileGe
     if (B < 1 || g.C < 1 || g.ny < 1 || g.nx < 1 || g.th < 1 || g.tw < 1 || g.th > g.H || g.tw > g.W || chw >= (1ull << 32) ||
         g.oy < 0 || g.ox < 0 || (long long)g.oy + 1 > 46340 || (long long)g.ox + 1 > 46340) return hipErrorInvalidValue;      // wy * wx fits an int
     hipLaunchKernelGGL(tile_blend_kernel, dim3((unsigned)((chw + 255) / 256), B < 65535 ? B : 65535), dim3(256), 0, s, tiles, out, B, g);
+    return hipGetLastError();
+}
+
+// Blend and reduce in one pass over the image (mi_denoise_tiled_ensemble): tiles [M][B][ny*nx][C][th][tw], the tile outputs of M
+// members in run order, -> mean / unbiased std [B][C][H][W] over the members' BLENDED images and, if asked for, those images
+// themselves, samples [B][M][C][H][W].  A thread owns ONE output element of one image, as in tile_blend_kernel, whose addressing
+// this keeps (member m, image b is the tile block m * B + b).  THE ARITHMETIC IS FIXED (include/midd.h: mi_tile_blend_reduce):
+// the composition of the two kernels above, bit for bit --
+//   v_m = (float)(num / den) of member m, formed as tile_blend_kernel forms it;  then over v_0 .. v_{M-1}, in index order, the
+//   sums of ensemble_reduce_kernel: mean64 = (sum (double)v_m) / M,  q = sum d * d with d = (double)v_m - mean64
+// M is a run-time value, so the v_m are not kept: the second walk (std only) blends them again from the tiles -- the same loads
+// and the same operations, hence the same bits, whether or not samples is written; nothing is read back from samples.  The
+// blended members never exist in memory unless the caller wants them: per pixel (1 or 2) * M * cover tile reads and 1-2 writes,
+// against M * cover reads + M writes + 2 * M reads + 2 writes of blend-then-reduce.  No atomics, nothing depends on the grid.
+// grid (chunks of 256 elements of a [C][H][W] block, images -- folded over grid.y when B > 65535)
+__global__ __launch_bounds__(256)
+void tile_blend_reduce_kernel(const float* __restrict__ tiles, float* __restrict__ mean, float* __restrict__ stdv,
+                              float* __restrict__ samples, int B, int M, TileGeom g) {
+    const unsigned long long e = (unsigned long long)blockIdx.x * 256 + threadIdx.x;
+    const unsigned long long chw = (unsigned long long)g.C * g.H * g.W;
+    if (e >= chw) return;
+    const int x = (int)(e % (unsigned)g.W);
+    const unsigned long long cy = e / (unsigned)g.W;
+    const int y = (int)(cy % (unsigned)g.H), c = (int)(cy / (unsigned)g.H);
+    int ky0, ky1, kx0, kx1;
+    tile_cover(y, g.H, g.th, g.ny, &ky0, &ky1);
+    tile_cover(x, g.W, g.tw, g.nx, &kx0, &kx1);
+    const size_t tile_plane = (size_t)g.th * g.tw, K = (size_t)g.ny * g.nx;
+    for (size_t b = blockIdx.y; b < (size_t)B; b += gridDim.y) {
+        auto blended = [&](int m) -> float {                       // tile_blend_kernel's pixel, of tile block m * B + b
+            const size_t mb = (size_t)m * B + b;
+            double num = 0.0, den = 0.0;
+            for (int ky = ky0; ky <= ky1; ++ky) {
+                const int ry = y - tile_origin(ky, g.H, g.th, g.ny);
+                const int wy = tile_window(ry, g.th, g.oy);
+                for (int kx = kx0; kx <= kx1; ++kx) {
+                    const int rx = x - tile_origin(kx, g.W, g.tw, g.nx);
+                    const double w = (double)(wy * tile_window(rx, g.tw, g.ox));
+                    const float v = tiles[((mb * K + (size_t)ky * g.nx + kx) * g.C + c) * tile_plane + (size_t)ry * g.tw + rx];
+                    num = add_rn64(num, mul_rn64(w, (double)v));
+                    den = add_rn64(den, w);
+                }
+            }
+            return __double2float_rn(__ddiv_rn(num, den));
+        };
+        double sum = 0.0;
+        for (int m = 0; m < M; ++m) {
+            const float v = blended(m);
+            if (samples) samples[(b * (size_t)M + m) * chw + e] = v;
+            sum = add_rn64(sum, (double)v);
+        }
+        const double m64 = __ddiv_rn(sum, (double)M);
+        if (mean) mean[b * chw + e] = __double2float_rn(m64);
+        if (stdv) {
+            double q = 0.0;
+            for (int m = 0; m < M; ++m) {
+                const double d = sub_rn64((double)blended(m), m64);
+                q = add_rn64(q, mul_rn64(d, d));
+            }
+            stdv[b * chw + e] = __double2float_rn(__dsqrt_rn(__ddiv_rn(q, (double)(M - 1))));
+        }
+    }
+}
+
+hipError_t tile_blend_reduce_launch(const float* tiles, int B, int M, const TileGeom& g, float* mean, float* stdv, float* samples, hipStream_t s) {
+    const unsigned long long chw = (unsigned long long)g.C * g.H * g.W;
+    if (B < 1 || M < 1 || g.C < 1 || g.ny < 1 || g.nx < 1 || g.th < 1 || g.tw < 1 || g.th > g.H || g.tw > g.W || chw >= (1ull << 32) ||
+        g.oy < 0 || g.ox < 0 || (long long)g.oy + 1 > 46340 || (long long)g.ox + 1 > 46340 ||                          // wy * wx fits an int
+        (!mean && !stdv && !samples) || (stdv && M < 2)) return hipErrorInvalidValue;
+    const long long BK = (long long)B * ((long long)g.ny * g.nx);            // (ny * nx <= H * W < 2^32: no overflow in either product)
+    if (BK > 2147483647ll || BK * M > 2147483647ll) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(tile_blend_reduce_kernel, dim3((unsigned)((chw + 255) / 256), B < 65535 ? B : 65535), dim3(256), 0, s,
+                       tiles, mean, stdv, samples, B, M, g);
     return hipGetLastError();
 }
 

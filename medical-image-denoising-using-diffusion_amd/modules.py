@@ -451,13 +451,64 @@ class UNetDiffusion(nn.Module):
             self._raise_on_status(wptr, stream)
         return image, tiles, plan_t
 
-    def _tiled_workspace(self, args: tuple, dev: torch.device) -> torch.Tensor:
-        """Scratch of one run_tiled call; shares the one resident entry of the ensemble calls (a pass of tiles is as large as a
-        pass of members), so it evicts none of the sampler workspaces either."""
-        key = ("tiled",) + args + (dev.index, torch.cuda.current_stream(dev).cuda_stream)
+    @torch.no_grad()
+    def run_tiled_ensemble(self, noisy: torch.Tensor, t_list, beta: torch.Tensor, alpha: torch.Tensor, alpha_hat: torch.Tensor,
+                           clamp_eps: bool, tile, overlap, members: int, seed: int, sample_offset: int = 0, member_offset: int = 0,
+                           max_batch: int = 16, want_mean: bool = True, want_std: bool = True, want_samples: bool = False,
+                           want_tiles: bool = False, no_split: bool = False):
+        """``members`` seeded draws of images of any size >= the tile in one native call (mi_denoise_tiled_ensemble) ->
+        (mean, std, samples, tiles, TilePlan), each tensor None when not asked for.  Members are the outer loop; inside a member
+        the B * tiles crops run in passes of at most ``max_batch``, as run_tiled runs them.  samples is [B, members, C, H, W],
+        tiles [members, B, ny * nx, C, th, tw]."""
+        from .sampler import check_member, check_seed, tile_plan
+        seed, sample_offset = check_seed(seed, sample_offset)
+        members, member_offset = check_member(members, "members", low=1), check_member(member_offset, "member_offset")
+        max_batch = check_member(max_batch, "max_batch", low=1)
+        if member_offset + members > 1 << 32:
+            raise ValueError(f"member_offset + members must be <= 2**32 (got {member_offset} + {members})")
+        want_std = want_std and members >= 2
+        if not (want_mean or want_std or want_samples or want_tiles):
+            raise ValueError("nothing to return: ask for the mean, the std, the samples or the tiles")
+        self._check_image(noisy, "noisy_img")
+        B, Cc, H, W = noisy.shape
+        plan_t = tile_plan(H, W, tile, overlap)
+        (th, tw), (oy, ox) = plan_t.tile, plan_t.overlap
+        K = len(plan_t.origins_y) * len(plan_t.origins_x)
+        steps = np.ascontiguousarray(np.asarray(list(t_list), dtype=np.int32))
+        tabs = [np.ascontiguousarray(v.detach().to("cpu", torch.float32).numpy()) for v in (beta, alpha, alpha_hat)]
+        noise_steps = int(tabs[0].shape[0])
+        with self._lock, torch.cuda.device(noisy.device):
+            plan = self._ensure_plan(time_rows=noise_steps)
+            src = noisy.contiguous()
+            mean = torch.empty_like(src) if want_mean else None
+            std = torch.empty_like(src) if want_std else None
+            samples = torch.empty((B, members, Cc, H, W), dtype=torch.float32, device=src.device) if want_samples else None
+            tiles = torch.empty((members, B, K, Cc, th, tw), dtype=torch.float32, device=src.device) if want_tiles else None
+            pass_samples = min(max_batch, max(1, B * K))
+            ws = self._tiled_workspace((B, members, H, W, th, tw, oy, ox, pass_samples, 1 if want_tiles else 0), noisy.device, ensemble=True)
+            if self.poison_workspace is not None:
+                ws.fill_(self.poison_workspace)
+            wptr, wbytes = self._aligned_ptr(ws)
+            stream = torch.cuda.current_stream(noisy.device).cuda_stream
+            fp = C.POINTER(C.c_float)
+            ptr = lambda t: None if t is None else t.data_ptr()      # noqa: E731
+            native.check(native.lib().mi_denoise_tiled_ensemble(
+                plan, src.data_ptr(), ptr(mean), ptr(std), ptr(samples), ptr(tiles), B, members, H, W, th, tw, oy, ox,
+                steps.ctypes.data_as(C.POINTER(C.c_int32)), len(steps),
+                tabs[0].ctypes.data_as(fp), tabs[1].ctypes.data_as(fp), tabs[2].ctypes.data_as(fp), noise_steps,
+                C.c_uint64(seed), C.c_int64(sample_offset), C.c_int64(member_offset), pass_samples,
+                (native.MI_CLAMP_EPS if clamp_eps else 0) | (native.MI_NO_SPLIT if no_split else 0), wptr, wbytes, stream))
+            self._raise_on_status(wptr, stream)
+        return mean, std, samples, tiles, plan_t
+
+    def _tiled_workspace(self, args: tuple, dev: torch.device, ensemble: bool = False) -> torch.Tensor:
+        """Scratch of one run_tiled (or, ``ensemble``, run_tiled_ensemble) call; shares the one resident entry of the ensemble
+        calls (a pass of tiles is as large as a pass of members), so it evicts none of the sampler workspaces either."""
+        key = ("tiled_ensemble" if ensemble else "tiled",) + args + (dev.index, torch.cuda.current_stream(dev).cuda_stream)
         if self._ensemble_ws is not None and self._ensemble_ws[0] == key:
             return self._ensemble_ws[1]
-        nbytes = native.lib().mi_tiled_workspace_bytes(self._plan, *args)
+        query = native.lib().mi_tiled_ensemble_workspace_bytes if ensemble else native.lib().mi_tiled_workspace_bytes
+        nbytes = query(self._plan, *args)
         if nbytes == 0:
             native.check(-1)
         self._ensemble_ws = None                  # (free the old one before the new one is allocated)
@@ -473,6 +524,16 @@ class UNetDiffusion(nn.Module):
             self._ensure_plan()
             return int(native.lib().mi_tiled_workspace_bytes(self._plan, B, H, W, p.tile[0], p.tile[1], p.overlap[0], p.overlap[1],
                                                              min(max_batch, max(1, B * K)), 1 if tiles_external else 0))
+
+    def tiled_ensemble_workspace_bytes(self, B: int, members: int, H: int, W: int, tile, overlap=32, max_batch: int = 16,
+                                       tiles_external: bool = False) -> int:
+        from .sampler import tile_plan
+        p = tile_plan(H, W, tile, overlap)
+        K = len(p.origins_y) * len(p.origins_x)
+        with self._lock, torch.cuda.device(self._device()):
+            self._ensure_plan()
+            return int(native.lib().mi_tiled_ensemble_workspace_bytes(self._plan, B, members, H, W, p.tile[0], p.tile[1], p.overlap[0], p.overlap[1],
+                                                                      min(max_batch, max(1, B * K)), 1 if tiles_external else 0))
 
     def ensemble_workspace_bytes(self, B: int, members: int, H: int, W: int, max_batch: int = 16, samples_external: bool = False) -> int:
         with self._lock, torch.cuda.device(self._device()):

@@ -82,6 +82,11 @@ SYMBOLS = [
                                   [C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int,
                                    C.c_int, C.c_uint64, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
     ("mi_tiled_workspace_bytes", C.c_size_t, [C.c_void_p] + [C.c_int] * 9),
+    ("mi_denoise_tiled_ensemble", C.c_int, [C.c_void_p] * 6 + [C.c_int] * 8 +
+                                           [C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int,
+                                            C.c_uint64, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
+    ("mi_tiled_ensemble_workspace_bytes", C.c_size_t, [C.c_void_p] + [C.c_int] * 10),
+    ("mi_tile_blend_reduce", C.c_int, [C.c_void_p] + [C.c_int] * 9 + [C.c_void_p] * 4),
     ("mi_debug_fetch", C.c_int, [C.c_void_p, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                  C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p]),
     ("mi_status", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]),

@@ -106,6 +106,17 @@ class TiledResult(NamedTuple):
     seed: Optional[int]                   # cddpm: the seed of the run (drawn when the call had seed=None); None for DDIM
 
 
+class TiledEnsembleResult(NamedTuple):
+    """What ``DiffusionDenoiser.denoise_tiled_ensemble`` returns."""
+    mean: torch.Tensor                    # [B, C, H, W]: per-pixel mean of the members' blended images, at the input's own size
+    std: Optional[torch.Tensor]           # [B, C, H, W]: unbiased per-pixel standard deviation; None for one member
+    samples: Optional[torch.Tensor]       # [B, members, C, H, W] with return_samples=True: every member's blended image
+    tiles: Optional[torch.Tensor]         # [members, B, ny * nx, C, th, tw] with return_tiles=True: tiles[m] is a TiledResult.tiles
+    origins_y: Tuple[int, ...]            # row origin of every tile row
+    origins_x: Tuple[int, ...]            # column origin of every tile column
+    seed: int                             # the seed of the run (drawn when the call had seed=None): pass it to repeat the run
+
+
 class TilePlan(NamedTuple):
     """What ``tile_plan`` returns: the tiling of an H x W image (include/midd.h: mi_tile_geometry)."""
     tile: Tuple[int, int]                 # (th, tw)
@@ -178,6 +189,30 @@ def tile_blend(tiles: torch.Tensor, H: int, W: int, overlap=32) -> torch.Tensor:
         native.check(native.lib().mi_tile_blend(src.data_ptr(), B, Cc, int(H), int(W), th, tw, plan.overlap[0], plan.overlap[1],
                                                 out.data_ptr(), torch.cuda.current_stream(src.device).cuda_stream))
     return out
+
+
+@torch.no_grad()
+def tile_blend_reduce(tiles: torch.Tensor, H: int, W: int, overlap=32,
+                      return_samples: bool = False) -> Tuple[torch.Tensor, Optional[torch.Tensor], Optional[torch.Tensor]]:
+    """tiles [members, B, ny * nx, C, th, tw] of an H x W tiling -> (mean, std, samples): per-pixel mean and unbiased std
+    [B, C, H, W] over the members' blended images and, with ``return_samples``, those images [B, members, C, H, W], in one kernel
+    with the arithmetic of ``denoise_tiled_ensemble`` (mi_tile_blend_reduce: ``tile_blend`` per member, then ``ensemble_reduce``
+    over the members, bit for bit).  std is None for one member."""
+    src = _tile_tensor(tiles, "tiles", 6)
+    M, B, K, Cc, th, tw = src.shape
+    plan = tile_plan(H, W, (th, tw), overlap)
+    if K != len(plan.origins_y) * len(plan.origins_x):
+        raise ValueError(f"tiles has {K} tiles per image; a {H}x{W} image with tile {th}x{tw} and overlap {plan.overlap} has "
+                         f"{len(plan.origins_y)} x {len(plan.origins_x)}")
+    with torch.cuda.device(src.device):
+        mean = torch.empty((B, Cc, int(H), int(W)), dtype=torch.float32, device=src.device)
+        std = torch.empty_like(mean) if M >= 2 else None
+        samples = torch.empty((B, M, Cc, int(H), int(W)), dtype=torch.float32, device=src.device) if return_samples else None
+        native.check(native.lib().mi_tile_blend_reduce(src.data_ptr(), B, M, Cc, int(H), int(W), th, tw, plan.overlap[0], plan.overlap[1],
+                                                       mean.data_ptr(), None if std is None else std.data_ptr(),
+                                                       None if samples is None else samples.data_ptr(),
+                                                       torch.cuda.current_stream(src.device).cuda_stream))
+    return mean, std, samples
 
 
 class DiffusionDenoiser:
@@ -292,6 +327,41 @@ class DiffusionDenoiser:
                                                   tile=tile, overlap=overlap, seed=seed, sample_offset=sample_offset,
                                                   max_batch=max_batch, want_tiles=return_tiles)
         return TiledResult(image, tiles, plan.origins_y, plan.origins_x, seed)
+
+    @torch.no_grad()
+    def denoise_tiled_ensemble(self, noisy_img: torch.Tensor, inference_steps: int = 25, members: int = 8, tile=256, overlap=32,
+                               max_batch: int = 16, seed: Optional[int] = None, sample_offset: int = 0, member_offset: int = 0,
+                               return_samples: bool = False, return_tiles: bool = False,
+                               step_noise: None = None) -> TiledEnsembleResult:
+        """``denoise_ensemble`` for images of ANY size >= the tile: ``members`` stochastic (cddpm) draws of every image as blended
+        overlapping tiles in one native call, their per-pixel mean and unbiased standard deviation at the image's own resolution
+        (not a reference call; include/midd.h: mi_denoise_tiled_ensemble).
+
+        Member m is ``denoise_tiled(x, seed=seed, sample_offset=sample_offset)`` with the member word ``member_offset + m`` of the
+        seeded step noise: with one member at offset 0, ``mean`` is that call's image bit for bit, and a tile of member m is
+        ``denoise(crop, step_noise=crop of midd_amd.step_noise(seed, n, x.shape, sample_offset, member=member_offset + m))``.
+        Members run one after the other; inside a member the B * tiles crops run as batches of at most ``max_batch`` (the pass
+        size is min(max_batch, B * tiles); a batch never mixes members).  ``mean`` and ``std`` are ``ensemble_reduce`` of the
+        members' ``tile_blend`` images, computed by one kernel that never stores those images unless ``return_samples=True``
+        (``samples``: [B, members, C, H, W]).  ``tiles`` ([members, B, ny * nx, C, th, tw], ``return_tiles=True``): ``tiles[m]`` is
+        what ``denoise_tiled(..., return_tiles=True).tiles`` is for member m.  ``std`` is None for one member.  ``seed=None`` draws
+        a 64-bit seed and returns it.  A DDIM model raises ValueError (a deterministic sampler has no ensemble); a ``step_noise``
+        tensor is not supported (anything but None raises ValueError)."""
+        if step_noise is not None:
+            raise ValueError("denoise_tiled_ensemble does not take a step_noise tensor: its noise is the seeded generator's, indexed by "
+                             "image position and member (pass seed; midd_amd.step_noise(seed, n, x.shape, member=m) exports the same values)")
+        if getattr(self.model, "variant", "ddim") != "cddpm":
+            raise ValueError("denoise_tiled_ensemble needs the stochastic (cddpm) variant: a deterministic sampler has no ensemble")
+        if seed is None:
+            seed = self._draw_seed()
+        seed, _ = check_seed(seed, 0)             # (everything else is judged by run_tiled_ensemble, before any GPU work)
+        self.model.eval()
+        steps = timestep_list(self.noise_steps, inference_steps)
+        mean, std, samples, tiles, plan = self.model.run_tiled_ensemble(
+            noisy_img, steps, self.beta, self.alpha, self.alpha_hat, clamp_eps=False, tile=tile, overlap=overlap, members=members,
+            seed=seed, sample_offset=sample_offset, member_offset=member_offset, max_batch=max_batch,
+            want_samples=return_samples, want_tiles=return_tiles)
+        return TiledEnsembleResult(mean, std, samples, tiles, plan.origins_y, plan.origins_x, seed)
 
     def _draw_seed(self) -> int:
         hi, lo = torch.randint(0, 1 << 32, (2,), dtype=torch.int64).tolist()
