@@ -4,19 +4,36 @@
 
 using namespace midd;
 
+// The noise term of the cddpm update: none, a caller's tensor (mi_denoise), or drawn in the update (mi_denoise_seeded,
+// mi_denoise_ensemble).  Seeded: the B samples of the run are the virtual samples v0 .. v0 + B - 1 of an image-major
+// (image, member) batch with `members` draws per image numbered from `member_offset`, image 0 being global image
+// `sample_offset`; a plain seeded run is members = 1, v0 = 0 (OutConvArgs, midd_internal.h).
+struct StepNoise {
+    const float* tensor = nullptr; bool seeded = false; uint64_t seed = 0; int64_t sample_offset = 0;
+    int v0 = 0; int members = 1; uint32_t member_offset = 0;
+    // mi_denoise_tiled: the virtual samples are (image, tile) pairs, members = tiles_y * tiles_x, and the noise is indexed by the
+    // pixel's place in the whole img_H x img_W image (OutConvArgs)
+    int tiles_x = 0, tiles_y = 0, img_H = 0, img_W = 0;
+};
+
+// the sampler's schedule as a caller gives it: the timestep rows (uniform: t[n]; mi_denoise_slots: a table t[n][B]) and the tables
+struct Schedule { const int32_t* t; int n; const float *beta, *alpha, *alpha_hat; int noise_steps; };
+
 struct StepIO {
     const float* x; const float* cond; float* eps_out;
     float* x_update; const float* noise; float c1, c2, c3; int clamp_eps;
-    // seeded != 0: the update draws its noise term (step_noise_common.h) for iteration `iter`; sample 0 of this program is
-    // virtual sample `v0` of a call whose image 0 is global image `sample_offset`, with `members` draws per image numbered from
-    // `member_offset` (OutConvArgs, midd_internal.h)
-    int seeded; int iter; uint64_t seed; int64_t sample_offset; int v0; int members; uint32_t member_offset;
-    // tiles_x != 0: the virtual samples are (image, tile) pairs of a tiles_y x tiles_x tiling of img_H x img_W images (mi_denoise_tiled)
-    int tiles_x, tiles_y, img_H, img_W;
+    // sn.seeded: the update draws its noise term (step_noise_common.h) for iteration `iter`, sample 0 of THIS program being virtual
+    // sample sn.v0; a step that draws nothing keeps the defaults (sn.tensor is not read: `noise` is this step's slice of it)
+    int iter; StepNoise sn;
     // slots != null (mi_denoise_slots): every sample is updated from its record of this row (device, [B]) by out_conv_slots_kernel;
-    // of the fields above the update reads x_update, noise, clamp_eps, seeded and seed only
+    // of the fields above the update reads x_update, noise, clamp_eps, sn.seeded and sn.seed only
     const SlotRec* slots;
 };
+
+// the rc of a launch wrapper's hipError_t
+static int launched(hipError_t e, const char* what) {
+    return e == hipSuccess ? MI_OK : fail(MI_EHIP, "%s: %s", what, hipGetErrorString(e));
+}
 
 // status: the call's status word (first word of the CALLER's workspace, whichever sub-batch program runs)
 static int run_program(mi_plan* p, Program* g, const StepIO& io, char* ws, int* status, hipStream_t s,
@@ -117,9 +134,10 @@ static int run_program(mi_plan* p, Program* g, const StepIO& io, char* ws, int* 
                 a.B = B; a.H = g->H; a.W = g->W; a.C = o.s0.C; a.ic = p->cfg.in_channels;
                 a.eps_out = io.eps_out; a.x = io.x_update; a.noise = io.noise;
                 a.c1 = io.c1; a.c2 = io.c2; a.c3 = io.c3; a.clamp_eps = io.clamp_eps;
-                a.seeded = io.seeded; a.iter = io.iter; a.seed = io.seed; a.sample_offset = io.sample_offset;
-                a.v0 = io.v0; a.members = io.members > 0 ? io.members : 1; a.member_offset = io.member_offset;
-                a.tiles_x = io.tiles_x; a.tiles_y = io.tiles_y; a.img_H = io.img_H; a.img_W = io.img_W;
+                const StepNoise& n = io.sn;
+                a.seeded = n.seeded; a.iter = io.iter; a.seed = n.seed; a.sample_offset = n.sample_offset;
+                a.v0 = n.v0; a.members = n.members > 0 ? n.members : 1; a.member_offset = n.member_offset;
+                a.tiles_x = n.tiles_x; a.tiles_y = n.tiles_y; a.img_H = n.img_H; a.img_W = n.img_W;
                 e = io.slots ? out_conv_slots_launch(a, io.slots, s) : out_conv_launch(a, s);
                 break;
             }
@@ -134,7 +152,7 @@ static int run_program(mi_plan* p, Program* g, const StepIO& io, char* ws, int* 
             mi_plan::Span sp; sp.a = ev_a; sp.b = ev_b;
             op_work(p, g, o, &sp.name, &sp.flops, &sp.bytes);
             const size_t oc_at = sp.name.find("out_conv_kernel");
-            if (o.kind == OP_OUT && (io.seeded || io.slots) && oc_at != std::string::npos)      // the symbol that ran
+            if (o.kind == OP_OUT && (io.sn.seeded || io.slots) && oc_at != std::string::npos)      // the symbol that ran
                 sp.name.replace(oc_at, 15, io.slots ? "out_conv_slots_kernel" : "out_conv_seeded_kernel");
             static const bool per_op = getenv("MIDD_PROFILE_PER_OP") != nullptr;      // one entry per op instead of per symbol
             if (per_op) {
@@ -156,23 +174,42 @@ static int check_device(mi_plan* plan) {
     return MI_OK;
 }
 
+static int check_finalized(mi_plan* plan) {
+    return plan->finalized ? MI_OK : fail(MI_ESTATE, "mi_unet_finalize has not been called (or weights changed since)");
+}
+
+static int check_workspace(const void* ws, size_t got, size_t need) {
+    if (!ws || got < need) return fail(MI_ENOMEM, "workspace too small: need %zu bytes, got %zu", need, got);
+    if (((uintptr_t)ws) & 255) return fail(MI_EINVAL, "workspace must be 256-byte aligned");
+    return MI_OK;
+}
+
 static int check_call(mi_plan* plan, int B, int H, int W, void* ws, size_t ws_bytes, Program** g) {
     if (!plan) return fail(MI_EINVAL, "null plan");
-    int rc = get_program(plan, B, H, W, g);
-    if (rc) return rc;
-    if (!ws || ws_bytes < (*g)->bytes) return fail(MI_ENOMEM, "workspace too small: need %zu bytes, got %zu", (*g)->bytes, ws_bytes);
-    if (((uintptr_t)ws) & 255) return fail(MI_EINVAL, "workspace must be 256-byte aligned");
+    if (int rc = get_program(plan, B, H, W, g)) return rc;
+    if (int rc = check_workspace(ws, ws_bytes, (*g)->bytes)) return rc;
     return check_device(plan);
 }
 
-// the sampler's host-side arguments (mi_denoise*, and mi_denoise_ensemble before its first pass)
-static int check_schedule(mi_plan* plan, const int32_t* t_list, int n_iters, const float* beta, const float* alpha, const float* alpha_hat,
-                          int noise_steps) {
-    if ((n_iters > 0 && !t_list) || !beta || !alpha || !alpha_hat) return fail(MI_EINVAL, "null argument");
-    if (n_iters < 0 || noise_steps < 1 || noise_steps > plan->time_rows)
-        return fail(MI_EINVAL, "noise_steps %d exceeds the precomputed time table (%d rows)", noise_steps, plan->time_rows);
-    for (int i = 0; i < n_iters; ++i)
-        if (t_list[i] < 0 || t_list[i] >= noise_steps) return fail(MI_EINVAL, "t_list[%d]=%d outside [0,%d)", i, t_list[i], noise_steps);
+// the sampler's host-side arguments (mi_denoise*, and the batched calls before their first pass)
+static int check_schedule(mi_plan* plan, const Schedule& sc) {
+    if ((sc.n > 0 && !sc.t) || !sc.beta || !sc.alpha || !sc.alpha_hat) return fail(MI_EINVAL, "null argument");
+    if (sc.n < 0 || sc.noise_steps < 1 || sc.noise_steps > plan->time_rows)
+        return fail(MI_EINVAL, "noise_steps %d exceeds the precomputed time table (%d rows)", sc.noise_steps, plan->time_rows);
+    for (int i = 0; i < sc.n; ++i)
+        if (sc.t[i] < 0 || sc.t[i] >= sc.noise_steps) return fail(MI_EINVAL, "t_list[%d]=%d outside [0,%d)", i, sc.t[i], sc.noise_steps);
+    return MI_OK;
+}
+
+// no two of the n buffers may overlap (a null one is absent); `why` is the call's sentence on who reads and who writes
+struct Buf { const void* p; size_t bytes; const char* name; };
+static int check_no_overlap(const Buf* b, int n, const char* why) {
+    for (int i = 0; i < n; ++i)
+        for (int j = i + 1; j < n; ++j) {
+            const uintptr_t a = (uintptr_t)b[i].p, c = (uintptr_t)b[j].p;
+            if (a && c && a < c + b[j].bytes && c < a + b[i].bytes)
+                return fail(MI_EINVAL, "%s and %s alias (overlap): %s", b[i].name, b[j].name, why);
+        }
     return MI_OK;
 }
 
@@ -187,59 +224,45 @@ extern "C" int mi_unet_forward(mi_plan* plan, const float* x, const float* condi
     hipStream_t s = (hipStream_t)stream;
     char* ws = (char*)workspace;
     HIPCHK(hipMemsetAsync(ws, 0, 256, s));                  // status word
-    hipError_t e = fill_i32_launch(reinterpret_cast<int*>(ws + g->trow_off), t, B, s);
-    if (e != hipSuccess) return fail(MI_EHIP, "fill timesteps: %s", hipGetErrorString(e));
+    if ((rc = launched(fill_i32_launch(reinterpret_cast<int*>(ws + g->trow_off), t, B, s), "fill timesteps"))) return rc;
     StepIO io{};
     io.x = x; io.cond = condition; io.eps_out = eps;
     return run_program(plan, g, io, ws, reinterpret_cast<int*>(ws), s);
 }
 
-// The noise term of the cddpm update: none, a caller's tensor (mi_denoise), or drawn in the update (mi_denoise_seeded,
-// mi_denoise_ensemble).  Seeded: the B samples of the run are the virtual samples v0 .. v0 + B - 1 of an image-major
-// (image, member) batch with `members` draws per image; a plain seeded run is members = 1, v0 = 0.
-struct StepNoise {
-    const float* tensor = nullptr; bool seeded = false; uint64_t seed = 0; int64_t sample_offset = 0;
-    int v0 = 0; int members = 1; uint32_t member_offset = 0;
-    // mi_denoise_tiled: the virtual samples are (image, tile) pairs, members = tiles_y * tiles_x, and the noise is indexed by the
-    // pixel's place in the whole img_H x img_W image (OutConvArgs)
-    int tiles_x = 0, tiles_y = 0, img_H = 0, img_W = 0;
-};
-
 // One batch through the sampler loop, in two steps: check_run judges the arguments (no GPU work), enqueue_run enqueues the
 // batch.  enqueue_run neither takes the plan's side-stream mutex nor clears the status word: its caller does both, once per
-// C call -- denoise_run for mi_denoise / mi_denoise_seeded, mi_denoise_ensemble once for all its passes, so that the word
-// accumulates over them.
-static int check_run(mi_plan* plan, const float* noisy, const float* x_out, int B, int H, int W,
-                     const int32_t* t_list, int n_iters, const float* beta, const float* alpha, const float* alpha_hat, int noise_steps,
+// C call -- denoise_run for mi_denoise / mi_denoise_seeded, a batched call once for all its passes (run_passes), so that the
+// word accumulates over them.
+static int check_run(mi_plan* plan, const float* noisy, const float* x_out, int B, int H, int W, const Schedule& sc,
                      void* workspace, size_t workspace_bytes, Program** g) {
     int rc = check_call(plan, B, H, W, workspace, workspace_bytes, g);
     if (rc) return rc;
     if (!noisy || !x_out) return fail(MI_EINVAL, "null argument");
-    if ((rc = check_schedule(plan, t_list, n_iters, beta, alpha, alpha_hat, noise_steps))) return rc;
+    if ((rc = check_schedule(plan, sc))) return rc;
     if (noisy == x_out) return fail(MI_EINVAL, "x_out must not alias noisy (the condition image is read every step)");
     return MI_OK;
 }
 
-// The rows of a sampler call.  Uniform (mi_denoise and its siblings): row i puts every sample at t[i], x starts as a copy of the
-// condition images.  Slots (mi_denoise_slots): t is a table [n][B], sample b is at t[i * B + b] in row i or idle (-1), its noise
-// counter words are (sample_index[b], iter_base[b] + i), and x is the caller's: it is not initialised.
-struct RunRows {
-    const int32_t* t = nullptr; int n = 0;
-    bool slots = false;
-    const int32_t* iter_base = nullptr;         // slots: [B] or null (all 0)
-    const int64_t* sample_index = nullptr;      // slots: [B] or null (0 .. B-1)
+// The rows of a sampler call.  Uniform (mi_denoise and its siblings, slots == null): row i puts every sample at sc.t[i], x starts
+// as a copy of the condition images.  Slots (mi_denoise_slots): sc.t is a table [n][B], sample b is at t[i * B + b] in row i or
+// idle (-1), its noise counter words are (sample_index[b], iter_base[b] + i), and x is the caller's: it is not initialised.
+struct SlotRows {
+    const int32_t* iter_base;         // [B] or null (all 0)
+    const int64_t* sample_index;      // [B] or null (0 .. B-1)
 };
 
 // (the caller holds plan->side_mu and has cleared the status word at the head of `workspace`)
 static int enqueue_run(mi_plan* plan, Program* g, const float* noisy, float* x_out, int B, int H, int W,
-                       const RunRows& rows, const float* beta, const float* alpha, const float* alpha_hat,
-                       const StepNoise& sn, int flags, void* workspace, size_t workspace_bytes, void* stream) {
-    const int n_iters = rows.n;
+                       const Schedule& sc, const SlotRows* slots, const StepNoise& sn, int flags,
+                       void* workspace, size_t workspace_bytes, void* stream) {
+    const int n_iters = sc.n;
+    const float *beta = sc.beta, *alpha = sc.alpha, *alpha_hat = sc.alpha_hat;
     int rc = MI_OK;
     hipStream_t s = (hipStream_t)stream;
     char* ws = (char*)workspace;
     const size_t img_elems = (size_t)B * plan->cfg.in_channels * H * W;
-    if (!rows.slots) HIPCHK(hipMemcpyAsync(x_out, noisy, img_elems * sizeof(float), hipMemcpyDeviceToDevice, s));   // x = noisy_img.clone()
+    if (!slots) HIPCHK(hipMemcpyAsync(x_out, noisy, img_elems * sizeof(float), hipMemcpyDeviceToDevice, s));   // x = noisy_img.clone()
     // Images are independent: the batch runs as `parts` sub-batches on as many streams, each started
     // 1/parts of a forward after the previous one, so that one part's latency-bound low-resolution
     // layers (one workgroup per CU at B=8) share the chip with another part's HBM-bound high-resolution
@@ -282,7 +305,7 @@ static int enqueue_run(mi_plan* plan, Program* g, const float* noisy, float* x_o
                     *c2 = (1.0f - alpha[t]) / sqrtf(1.0f - alpha_hat[t]);
                     *c3 = sqrtf(beta[t]);
                 };
-                if (rows.slots) {
+                if (slots) {
                     // sub-batch h takes columns [h * Bh, (h + 1) * Bh) of every table; the records leave as kernel arguments
                     int* trow = reinterpret_cast<int*>(wsh + gh->trow_off);
                     SlotRec* recs = reinterpret_cast<SlotRec*>(wsh + gh->slot_off);
@@ -290,31 +313,28 @@ static int enqueue_run(mi_plan* plan, Program* g, const float* noisy, float* x_o
                         SlotRecs r{};
                         const int m = Bh - c0 < SLOTS_PER_LAUNCH ? Bh - c0 : SLOTS_PER_LAUNCH;
                         for (int j = 0; j < m; ++j) {
-                            const int col = h * Bh + c0 + j, t = rows.t[(size_t)i * B + col];
+                            const int col = h * Bh + c0 + j, t = sc.t[(size_t)i * B + col];
                             if (t < 0) continue;                             // idle: active 0, time row 0
                             SlotRec& q = r.v[j];
                             coeffs(t, &q.c1, &q.c2, &q.c3);
                             q.active = SLOT_ACTIVE | ((t > 0 && (sn.seeded || sn.tensor)) ? SLOT_NOISE : 0);      // nothing is drawn at t == 0
-                            q.iter = (unsigned)((rows.iter_base ? rows.iter_base[col] : 0) + i);
-                            q.image = (unsigned)(uint64_t)(rows.sample_index ? rows.sample_index[col] : (int64_t)col);
+                            q.iter = (unsigned)((slots->iter_base ? slots->iter_base[col] : 0) + i);
+                            q.image = (unsigned)(uint64_t)(slots->sample_index ? slots->sample_index[col] : (int64_t)col);
                             q.trow = t;
                         }
-                        const hipError_t e = slot_fill_launch(trow + c0, recs + c0, r, m, sh);
-                        if (e != hipSuccess) return fail(MI_EHIP, "slot records: %s", hipGetErrorString(e));
+                        if (int rc2 = launched(slot_fill_launch(trow + c0, recs + c0, r, m, sh), "slot records")) return rc2;
                     }
                     io.slots = recs;
                     io.noise = sn.tensor ? sn.tensor + (size_t)i * img_elems + h * part : nullptr;
-                    io.seeded = sn.seeded ? 1 : 0; io.seed = sn.seed;
+                    io.sn.seeded = sn.seeded; io.sn.seed = sn.seed;
                 } else {
-                    const int t = rows.t[i];
+                    const int t = sc.t[i];
                     HIPCHK(hipMemsetD32Async((hipDeviceptr_t)(wsh + gh->trow_off), t, Bh, sh));          // t = full((B,), i)
                     coeffs(t, &io.c1, &io.c2, &io.c3);
                     io.noise = (sn.tensor && t > 0) ? sn.tensor + (size_t)i * img_elems + h * part : nullptr;      // cddpmModels.py:297-300
                     if (sn.seeded && t > 0) {                        // nothing is drawn at t == 0
-                        io.seeded = 1; io.iter = i; io.seed = sn.seed;
-                        io.sample_offset = sn.sample_offset; io.v0 = sn.v0 + h * Bh;      // sub-batch h: its first virtual index
-                        io.members = sn.members; io.member_offset = sn.member_offset;
-                        io.tiles_x = sn.tiles_x; io.tiles_y = sn.tiles_y; io.img_H = sn.img_H; io.img_W = sn.img_W;
+                        io.iter = i; io.sn = sn;
+                        io.sn.v0 += h * Bh;                          // sub-batch h: its first virtual index
                     }
                 }
                 io.clamp_eps = (flags & MI_CLAMP_EPS) ? 1 : 0;
@@ -340,18 +360,13 @@ static int enqueue_run(mi_plan* plan, Program* g, const float* noisy, float* x_o
 }
 
 // a sampler call of its own: arguments, the plan's side-stream mutex, the status word, the batch
-static int denoise_run(mi_plan* plan, const float* noisy, float* x_out, int B, int H, int W,
-                       const int32_t* t_list, int n_iters,
-                       const float* beta, const float* alpha, const float* alpha_hat, int noise_steps,
-                       const StepNoise& sn, int flags,
-                       void* workspace, size_t workspace_bytes, void* stream) {
+static int denoise_run(mi_plan* plan, const float* noisy, float* x_out, int B, int H, int W, const Schedule& sc,
+                       const StepNoise& sn, int flags, void* workspace, size_t workspace_bytes, void* stream) {
     Program* g = nullptr;
-    if (int rc = check_run(plan, noisy, x_out, B, H, W, t_list, n_iters, beta, alpha, alpha_hat, noise_steps, workspace, workspace_bytes, &g))
-        return rc;
+    if (int rc = check_run(plan, noisy, x_out, B, H, W, sc, workspace, workspace_bytes, &g)) return rc;
     std::lock_guard<std::mutex> side_lk(plan->side_mu);      // the side streams and their events are per plan: one enqueue at a time
     HIPCHK(hipMemsetAsync(workspace, 0, 256, (hipStream_t)stream));      // status word (before the side streams fork)
-    RunRows rows; rows.t = t_list; rows.n = n_iters;
-    return enqueue_run(plan, g, noisy, x_out, B, H, W, rows, beta, alpha, alpha_hat, sn, flags, workspace, workspace_bytes, stream);
+    return enqueue_run(plan, g, noisy, x_out, B, H, W, sc, nullptr, sn, flags, workspace, workspace_bytes, stream);
 }
 
 extern "C" int mi_denoise(mi_plan* plan, const float* noisy, float* x_out, int B, int H, int W,
@@ -361,7 +376,7 @@ extern "C" int mi_denoise(mi_plan* plan, const float* noisy, float* x_out, int B
                           void* workspace, size_t workspace_bytes, void* stream) {
     StepNoise sn;
     sn.tensor = step_noise;
-    return denoise_run(plan, noisy, x_out, B, H, W, t_list, n_iters, beta, alpha, alpha_hat, noise_steps, sn, flags,
+    return denoise_run(plan, noisy, x_out, B, H, W, Schedule{t_list, n_iters, beta, alpha, alpha_hat, noise_steps}, sn, flags,
                        workspace, workspace_bytes, stream);
 }
 
@@ -385,7 +400,7 @@ extern "C" int mi_denoise_seeded(mi_plan* plan, const float* noisy, float* x_out
     if (int rc = check_step_noise_range(plan->cfg.in_channels, H, W, sample_offset)) return rc;
     StepNoise sn;
     sn.seeded = true; sn.seed = seed; sn.sample_offset = sample_offset;
-    return denoise_run(plan, noisy, x_out, B, H, W, t_list, n_iters, beta, alpha, alpha_hat, noise_steps, sn, flags,
+    return denoise_run(plan, noisy, x_out, B, H, W, Schedule{t_list, n_iters, beta, alpha, alpha_hat, noise_steps}, sn, flags,
                        workspace, workspace_bytes, stream);
 }
 
@@ -421,13 +436,10 @@ extern "C" int mi_denoise_slots(mi_plan* plan, const float* cond, float* x, int 
         if (step_noise) return fail(MI_EINVAL, "seeded together with step_noise: the noise term is drawn or read, not both");
         if (int rc = check_step_noise_range(plan->cfg.in_channels, H, W, 0)) return rc;
     }
-    {   // cond is read by every row while x is updated in place
-        const size_t n = (size_t)B * plan->cfg.in_channels * H * W * sizeof(float);
-        const uintptr_t a = (uintptr_t)cond, b = (uintptr_t)x;
-        if (a < b + n && b < a + n)
-            return fail(MI_EINVAL, "x and cond alias (overlap): the condition images are read by every row while x is updated in place");
-    }
-    if (!plan->finalized) return fail(MI_ESTATE, "mi_unet_finalize has not been called (or weights changed since)");
+    const size_t batch_bytes = (size_t)B * plan->cfg.in_channels * H * W * sizeof(float);
+    const Buf buf[2] = {{x, batch_bytes, "x"}, {cond, batch_bytes, "cond"}};
+    if (int rc = check_no_overlap(buf, 2, "the condition images are read by every row while x is updated in place")) return rc;
+    if (int rc = check_finalized(plan)) return rc;
     if (noise_steps > plan->time_rows)
         return fail(MI_EINVAL, "noise_steps %d exceeds the precomputed time table (%d rows)", noise_steps, plan->time_rows);
     Program* g = nullptr;
@@ -435,10 +447,11 @@ extern "C" int mi_denoise_slots(mi_plan* plan, const float* cond, float* x, int 
     if (n_rows == 0) return MI_OK;
     StepNoise sn;
     sn.tensor = step_noise; sn.seeded = seeded != 0; sn.seed = seed;
-    RunRows rows; rows.t = t_rows; rows.n = n_rows; rows.slots = true; rows.iter_base = iter_base; rows.sample_index = sample_index;
+    const SlotRows slots{iter_base, sample_index};
     std::lock_guard<std::mutex> side_lk(plan->side_mu);
     HIPCHK(hipMemsetAsync(workspace, 0, 256, (hipStream_t)stream));      // status word: once per call
-    return enqueue_run(plan, g, cond, x, B, H, W, rows, beta, alpha, alpha_hat, sn, flags, workspace, workspace_bytes, stream);
+    return enqueue_run(plan, g, cond, x, B, H, W, Schedule{t_rows, n_rows, beta, alpha, alpha_hat, noise_steps}, &slots, sn, flags,
+                       workspace, workspace_bytes, stream);
 }
 
 extern "C" int mi_step_noise_fill_member(float* dst, int n_iters, int B, int C, int H, int W,
@@ -449,9 +462,8 @@ extern "C" int mi_step_noise_fill_member(float* dst, int n_iters, int B, int C, 
     if (n_iters < 0 || B < 0 || n_iters > 65535 || B > 65535) return fail(MI_EINVAL, "n_iters %d / B %d outside [0, 65535]", n_iters, B);
     if (n_iters == 0 || B == 0) return MI_OK;
     if (!dst) return fail(MI_EINVAL, "null argument");
-    const hipError_t e = step_noise_fill_launch(dst, n_iters, B, (unsigned long long)C * H * W, seed, sample_offset, (uint32_t)member, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(MI_EHIP, "step_noise_fill: %s", hipGetErrorString(e));
-    return MI_OK;
+    return launched(step_noise_fill_launch(dst, n_iters, B, (unsigned long long)C * H * W, seed, sample_offset, (uint32_t)member, (hipStream_t)stream),
+                    "step_noise_fill");
 }
 
 extern "C" int mi_step_noise_fill(float* dst, int n_iters, int B, int C, int H, int W,
@@ -462,8 +474,22 @@ extern "C" int mi_step_noise_fill(float* dst, int n_iters, int B, int C, int H, 
 // ---------------------------------------------------------------------------- ensembles of the stochastic sampler
 constexpr int64_t MEMBER_WORDS = (int64_t)1 << 32;      // the member index is one 32-bit counter word
 
+static int check_members_min(int members) {
+    return members >= 1 ? MI_OK : fail(MI_EINVAL, "members %d: an ensemble has at least one member (limit: members >= 1)", members);
+}
+
+static int check_std_members(const float* std_out, int members) {
+    if (std_out && members < 2) return fail(MI_EINVAL, "std_out needs members >= 2: the unbiased standard deviation of one value is undefined");
+    return MI_OK;
+}
+
+// B is grid.y of the reduce kernel
+static int check_reduce_batch(int B, const char* why = "limit of the reduce kernel's grid") {
+    return (B >= 1 && B <= 65535) ? MI_OK : fail(MI_EINVAL, "B %d outside [1, 65535] (%s)", B, why);
+}
+
 static int check_members(int members, int64_t member_offset) {
-    if (members < 1) return fail(MI_EINVAL, "members %d: an ensemble has at least one member (limit: members >= 1)", members);
+    if (int rc = check_members_min(members)) return rc;
     if (member_offset < 0) return fail(MI_EINVAL, "member_offset %lld is negative: member indices start at 0", (long long)member_offset);
     if (member_offset > MEMBER_WORDS - members)
         return fail(MI_EINVAL, "member_offset %lld + members %d exceeds 2^32: the member index of the seeded step noise is one 32-bit "
@@ -473,7 +499,7 @@ static int check_members(int members, int64_t member_offset) {
 
 // B images x members draws: what the reduce kernel's grid (B in grid.y) and the 32-bit virtual index can hold
 static int check_ensemble_size(int B, int members) {
-    if (B < 1 || B > 65535) return fail(MI_EINVAL, "B %d outside [1, 65535] (limit of the reduce kernel's grid)", B);
+    if (int rc = check_reduce_batch(B)) return rc;
     if ((int64_t)B * members > 2147483647ll)
         return fail(MI_EINVAL, "B * members = %d * %d exceeds 2^31 - 1: the virtual sample index is a 32-bit int (limit: B * members <= 2147483647)", B, members);
     return MI_OK;
@@ -488,13 +514,56 @@ int midd::check_ensemble_args(mi_plan* plan, int B, int members, int H, int W, i
 }
 
 extern "C" int mi_ensemble_reduce(const float* samples, int B, int members, int64_t chw, float* mean_out, float* std_out, void* stream) {
-    if (members < 1) return fail(MI_EINVAL, "members %d: an ensemble has at least one member (limit: members >= 1)", members);
-    if (B < 1 || B > 65535) return fail(MI_EINVAL, "B %d outside [1, 65535] (limit of the reduce kernel's grid)", B);
+    if (int rc = check_members_min(members)) return rc;
+    if (int rc = check_reduce_batch(B)) return rc;
     if (chw < 1 || chw >= MEMBER_WORDS) return fail(MI_EINVAL, "chw %lld outside [1, 2^32) (limit: C*H*W < 4294967296)", (long long)chw);
-    if (std_out && members < 2) return fail(MI_EINVAL, "std_out needs members >= 2: the unbiased standard deviation of one value is undefined");
+    if (int rc = check_std_members(std_out, members)) return rc;
     if (!samples || !mean_out) return fail(MI_EINVAL, "null argument");
-    const hipError_t e = ensemble_reduce_launch(samples, B, members, (unsigned long long)chw, mean_out, std_out, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(MI_EHIP, "ensemble_reduce: %s", hipGetErrorString(e));
+    return launched(ensemble_reduce_launch(samples, B, members, (unsigned long long)chw, mean_out, std_out, (hipStream_t)stream), "ensemble_reduce");
+}
+
+// ---------------------------------------------------------------------------- the batched calls: virtual samples in passes
+// mi_denoise_ensemble, mi_denoise_tiled and mi_denoise_tiled_ensemble run `rounds` x V virtual samples of h x w each through the
+// sampler loop in passes of L.pass.  Each judges its own argument rules and its table of buffers (check_no_overlap), then shares
+// check_batched_call and run_passes, and ends with its own reduce / blend launch.
+
+// What lies between a batched call's own rules and its first launch, in the order in which it is reported: the plan's state, the
+// workspace layout (the caller's ensemble_layout / tiled_ensemble_layout call: its rc and result), the workspace's size and
+// alignment, the pointers that must not be null, the schedule -- what a pass would refuse is refused here, before anything is
+// enqueued -- and the device.
+static int check_batched_call(mi_plan* plan, int layout_rc, const EnsembleLayout& L, const void* ws, size_t ws_bytes,
+                              std::initializer_list<const void*> required, const Schedule& sc) {
+    if (int rc = check_finalized(plan)) return rc;
+    if (layout_rc) return layout_rc;                     // (mi_last_error holds the planner's message)
+    if (int rc = check_workspace(ws, ws_bytes, L.bytes)) return rc;
+    for (const void* p : required)
+        if (!p) return fail(MI_EINVAL, "null argument");
+    if (int rc = check_schedule(plan, sc)) return rc;
+    return check_device(plan);
+}
+
+// The one pass loop.  Round m (a member of the tiled ensemble, whose member word is a launch constant; else the only round) runs
+// the virtual samples [0, V) in passes: fill(cond, v0, n) writes the pass's condition images, the sampler loop leaves its
+// samples at store[m][v0 ..].  The caller holds plan->side_mu and has cleared the status word, so the word accumulates over the
+// passes; every pass joins its side streams before it returns, on success and on failure (enqueue_run), and the first failing
+// pass ends the call.
+template <class Fill>
+static int run_passes(mi_plan* plan, Fill fill, float* store, int64_t V, int rounds, int h, int w, size_t chw, const EnsembleLayout& L,
+                      StepNoise sn, const Schedule& sc, int flags, char* ws, void* stream) {
+    float* cond = reinterpret_cast<float*>(ws + L.cond_off);
+    const uint32_t member_base = sn.member_offset;
+    for (int m = 0; m < rounds; ++m) {
+        sn.member_offset = member_base + m;
+        for (int64_t v0 = 0; v0 < V; v0 += L.pass) {
+            const int n = (int)(V - v0 < L.pass ? V - v0 : L.pass);
+            if (int rc = fill(cond, (int)v0, n)) return rc;
+            sn.v0 = (int)v0;
+            Program* g = nullptr;
+            float* x = store + ((size_t)m * V + (size_t)v0) * chw;
+            if (int rc = check_run(plan, cond, x, n, h, w, sc, ws, L.run_bytes, &g)) return rc;
+            if (int rc = enqueue_run(plan, g, cond, x, n, h, w, sc, nullptr, sn, flags, ws, L.run_bytes, stream)) return rc;
+        }
+    }
     return MI_OK;
 }
 
@@ -506,55 +575,27 @@ extern "C" int mi_denoise_ensemble(mi_plan* plan, const float* noisy, float* mea
                                    void* workspace, size_t workspace_bytes, void* stream) {
     if (int rc = check_ensemble_args(plan, B, members, H, W, sample_offset, member_offset, pass_samples)) return rc;
     if (!mean_out && !std_out && !samples_out) return fail(MI_EINVAL, "no output: give at least one of mean_out, std_out, samples_out");
-    if (std_out && members < 2) return fail(MI_EINVAL, "std_out needs members >= 2: the unbiased standard deviation of one value is undefined");
-    {   // noisy is read every step and the reduce reads the samples while it writes mean and std: no two of the four may overlap
-        const size_t img = (size_t)plan->cfg.in_channels * H * W * sizeof(float);
-        const struct { const void* p; size_t n; const char* name; } buf[4] = {
-            {noisy, (size_t)B * img, "noisy"}, {mean_out, (size_t)B * img, "mean_out"}, {std_out, (size_t)B * img, "std_out"},
-            {samples_out, (size_t)B * members * img, "samples_out"}};
-        for (int i = 0; i < 4; ++i)
-            for (int j = i + 1; j < 4; ++j) {
-                const uintptr_t a = (uintptr_t)buf[i].p, b = (uintptr_t)buf[j].p;
-                if (a && b && a < b + buf[j].n && b < a + buf[i].n)
-                    return fail(MI_EINVAL, "%s and %s alias (overlap): noisy is read every step and the reduce reads samples_out while it "
-                                "writes mean_out and std_out", buf[i].name, buf[j].name);
-            }
-    }
-    if (!plan->finalized) return fail(MI_ESTATE, "mi_unet_finalize has not been called (or weights changed since)");
+    if (int rc = check_std_members(std_out, members)) return rc;
+    const size_t chw = (size_t)plan->cfg.in_channels * H * W, img = chw * sizeof(float);
+    const Buf buf[4] = {{noisy, (size_t)B * img, "noisy"}, {mean_out, (size_t)B * img, "mean_out"}, {std_out, (size_t)B * img, "std_out"},
+                        {samples_out, (size_t)B * members * img, "samples_out"}};
+    if (int rc = check_no_overlap(buf, 4, "noisy is read every step and the reduce reads samples_out while it writes mean_out and std_out"))
+        return rc;
+    const Schedule sc{t_list, n_iters, beta, alpha, alpha_hat, noise_steps};
     EnsembleLayout L{};
-    if (int rc = ensemble_layout(plan, B, members, H, W, pass_samples, samples_out != nullptr, &L)) return rc;
-    if (!workspace || workspace_bytes < L.bytes) return fail(MI_ENOMEM, "workspace too small: need %zu bytes, got %zu", L.bytes, workspace_bytes);
-    if (((uintptr_t)workspace) & 255) return fail(MI_EINVAL, "workspace must be 256-byte aligned");
-    if (!noisy) return fail(MI_EINVAL, "null argument");
-    // what a pass would refuse is refused here, before anything is enqueued
-    if (int rc = check_schedule(plan, t_list, n_iters, beta, alpha, alpha_hat, noise_steps)) return rc;
-    if (int rc = check_device(plan)) return rc;
+    // (evaluated before the state check, reported after it: check_batched_call; host arithmetic only, as in the *_workspace_bytes queries)
+    const int layout_rc = ensemble_layout(plan, B, members, H, W, pass_samples, samples_out != nullptr, &L);
+    if (int rc = check_batched_call(plan, layout_rc, L, workspace, workspace_bytes, {noisy}, sc)) return rc;
     hipStream_t s = (hipStream_t)stream;
     char* ws = (char*)workspace;
-    const size_t chw = (size_t)plan->cfg.in_channels * H * W;
-    float* cond = reinterpret_cast<float*>(ws + L.cond_off);
     float* samples = samples_out ? samples_out : reinterpret_cast<float*>(ws + L.samples_off);
-    const int64_t V = (int64_t)B * members;
     std::lock_guard<std::mutex> side_lk(plan->side_mu);     // held over all passes: the side streams are per plan
     HIPCHK(hipMemsetAsync(ws, 0, 256, s));                  // status word: once per call, the passes accumulate into it
     StepNoise sn;
     sn.seeded = true; sn.seed = seed; sn.sample_offset = sample_offset; sn.members = members; sn.member_offset = (uint32_t)member_offset;
-    RunRows rows; rows.t = t_list; rows.n = n_iters;
-    for (int64_t v0 = 0; v0 < V; v0 += L.pass) {
-        const int n = (int)(V - v0 < L.pass ? V - v0 : L.pass);
-        const hipError_t e = ensemble_broadcast_launch(noisy, cond, (int)v0, n, members, chw, s);
-        if (e != hipSuccess) return fail(MI_EHIP, "ensemble_broadcast: %s", hipGetErrorString(e));
-        sn.v0 = (int)v0;
-        // (every pass joins its side streams before it returns, on success and on failure: enqueue_run)
-        Program* g = nullptr;
-        float* x = samples + (size_t)v0 * chw;
-        if (int rc = check_run(plan, cond, x, n, H, W, t_list, n_iters, beta, alpha, alpha_hat, noise_steps, ws, L.run_bytes, &g)) return rc;
-        if (int rc = enqueue_run(plan, g, cond, x, n, H, W, rows, beta, alpha, alpha_hat, sn, flags, ws, L.run_bytes, stream)) return rc;
-    }
-    if (mean_out || std_out) {
-        const hipError_t e = ensemble_reduce_launch(samples, B, members, chw, mean_out, std_out, s);
-        if (e != hipSuccess) return fail(MI_EHIP, "ensemble_reduce: %s", hipGetErrorString(e));
-    }
+    auto broadcast = [&](float* cond, int v0, int n) { return launched(ensemble_broadcast_launch(noisy, cond, v0, n, members, chw, s), "ensemble_broadcast"); };
+    if (int rc = run_passes(plan, broadcast, samples, (int64_t)B * members, 1, H, W, chw, L, sn, sc, flags, ws, stream)) return rc;
+    if (mean_out || std_out) return launched(ensemble_reduce_launch(samples, B, members, chw, mean_out, std_out, s), "ensemble_reduce");
     return MI_OK;
 }
 
@@ -611,9 +652,7 @@ extern "C" int mi_tile_extract(const float* noisy, int B, int C, int H, int W, i
     if ((int64_t)C * th * tw > 2147483647ll) return fail(MI_EINVAL, "C*th*tw = %d*%d*%d exceeds 2^31 - 1", C, th, tw);
     if (n == 0) return MI_OK;
     if (!noisy || !dst) return fail(MI_EINVAL, "null argument");
-    const hipError_t e = tile_extract_launch(noisy, dst, g, v0, n, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(MI_EHIP, "tile_extract: %s", hipGetErrorString(e));
-    return MI_OK;
+    return launched(tile_extract_launch(noisy, dst, g, v0, n, (hipStream_t)stream), "tile_extract");
 }
 
 extern "C" int mi_tile_blend(const float* tiles, int B, int C, int H, int W, int th, int tw, int oy, int ox, float* out, void* stream) {
@@ -623,9 +662,7 @@ extern "C" int mi_tile_blend(const float* tiles, int B, int C, int H, int W, int
     if (int rc = check_tile_count(B, g)) return rc;
     if (int rc = check_step_noise_range(C, H, W, 0)) return rc;
     if (!tiles || !out) return fail(MI_EINVAL, "null argument");
-    const hipError_t e = tile_blend_launch(tiles, out, B, g, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(MI_EHIP, "tile_blend: %s", hipGetErrorString(e));
-    return MI_OK;
+    return launched(tile_blend_launch(tiles, out, B, g, (hipStream_t)stream), "tile_blend");
 }
 
 extern "C" int mi_denoise_tiled(mi_plan* plan, const float* noisy, float* image_out, float* tiles_out,
@@ -637,32 +674,18 @@ extern "C" int mi_denoise_tiled(mi_plan* plan, const float* noisy, float* image_
     TileGeom tg{};
     if (int rc = check_tiled_args(plan, B, H, W, th, tw, oy, ox, sample_offset, pass_samples, &tg)) return rc;
     const int K = tg.ny * tg.nx;
-    const size_t chw = (size_t)tg.C * th * tw;
-    {   // noisy is read by every pass and the blend reads the tiles while it writes the image: no two of the three may overlap
-        const struct { const void* p; size_t n; const char* name; } buf[3] = {
-            {noisy, (size_t)B * tg.C * H * W * sizeof(float), "noisy"}, {image_out, (size_t)B * tg.C * H * W * sizeof(float), "image_out"},
-            {tiles_out, (size_t)B * K * chw * sizeof(float), "tiles_out"}};
-        for (int i = 0; i < 3; ++i)
-            for (int j = i + 1; j < 3; ++j) {
-                const uintptr_t a = (uintptr_t)buf[i].p, b = (uintptr_t)buf[j].p;
-                if (a && b && a < b + buf[j].n && b < a + buf[i].n)
-                    return fail(MI_EINVAL, "%s and %s alias (overlap): noisy is read by every pass and the blend reads the tiles while it "
-                                "writes image_out", buf[i].name, buf[j].name);
-            }
-    }
-    if (!plan->finalized) return fail(MI_ESTATE, "mi_unet_finalize has not been called (or weights changed since)");
+    const size_t chw = (size_t)tg.C * th * tw, img = (size_t)tg.C * H * W * sizeof(float);
+    const Buf buf[3] = {{noisy, (size_t)B * img, "noisy"}, {image_out, (size_t)B * img, "image_out"},
+                        {tiles_out, (size_t)B * K * chw * sizeof(float), "tiles_out"}};
+    if (int rc = check_no_overlap(buf, 3, "noisy is read by every pass and the blend reads the tiles while it writes image_out")) return rc;
+    const Schedule sc{t_list, n_iters, beta, alpha, alpha_hat, noise_steps};
     EnsembleLayout L{};
-    if (int rc = ensemble_layout(plan, B, K, th, tw, pass_samples, tiles_out != nullptr, &L)) return rc;
-    if (!workspace || workspace_bytes < L.bytes) return fail(MI_ENOMEM, "workspace too small: need %zu bytes, got %zu", L.bytes, workspace_bytes);
-    if (((uintptr_t)workspace) & 255) return fail(MI_EINVAL, "workspace must be 256-byte aligned");
-    if (!noisy || !image_out) return fail(MI_EINVAL, "null argument");
-    if (int rc = check_schedule(plan, t_list, n_iters, beta, alpha, alpha_hat, noise_steps)) return rc;
-    if (int rc = check_device(plan)) return rc;
+    // (evaluated before the state check, reported after it: check_batched_call; host arithmetic only, as in the *_workspace_bytes queries)
+    const int layout_rc = ensemble_layout(plan, B, K, th, tw, pass_samples, tiles_out != nullptr, &L);
+    if (int rc = check_batched_call(plan, layout_rc, L, workspace, workspace_bytes, {noisy, image_out}, sc)) return rc;
     hipStream_t s = (hipStream_t)stream;
     char* ws = (char*)workspace;
-    float* cond = reinterpret_cast<float*>(ws + L.cond_off);
     float* tiles = tiles_out ? tiles_out : reinterpret_cast<float*>(ws + L.samples_off);
-    const int64_t V = (int64_t)B * K;
     std::lock_guard<std::mutex> side_lk(plan->side_mu);     // held over all passes: the side streams are per plan
     HIPCHK(hipMemsetAsync(ws, 0, 256, s));                  // status word: once per call, the passes accumulate into it
     StepNoise sn;
@@ -670,20 +693,9 @@ extern "C" int mi_denoise_tiled(mi_plan* plan, const float* noisy, float* image_
         sn.seeded = true; sn.seed = seed; sn.sample_offset = sample_offset; sn.members = K;
         sn.tiles_x = tg.nx; sn.tiles_y = tg.ny; sn.img_H = H; sn.img_W = W;
     }
-    RunRows rows; rows.t = t_list; rows.n = n_iters;
-    for (int64_t v0 = 0; v0 < V; v0 += L.pass) {
-        const int n = (int)(V - v0 < L.pass ? V - v0 : L.pass);
-        const hipError_t e = tile_extract_launch(noisy, cond, tg, (int)v0, n, s);
-        if (e != hipSuccess) return fail(MI_EHIP, "tile_extract: %s", hipGetErrorString(e));
-        sn.v0 = (int)v0;
-        Program* g = nullptr;
-        float* x = tiles + (size_t)v0 * chw;
-        if (int rc = check_run(plan, cond, x, n, th, tw, t_list, n_iters, beta, alpha, alpha_hat, noise_steps, ws, L.run_bytes, &g)) return rc;
-        if (int rc = enqueue_run(plan, g, cond, x, n, th, tw, rows, beta, alpha, alpha_hat, sn, flags, ws, L.run_bytes, stream)) return rc;
-    }
-    const hipError_t e = tile_blend_launch(tiles, image_out, B, tg, s);
-    if (e != hipSuccess) return fail(MI_EHIP, "tile_blend: %s", hipGetErrorString(e));
-    return MI_OK;
+    auto extract = [&](float* cond, int v0, int n) { return launched(tile_extract_launch(noisy, cond, tg, v0, n, s), "tile_extract"); };
+    if (int rc = run_passes(plan, extract, tiles, (int64_t)B * K, 1, th, tw, chw, L, sn, sc, flags, ws, stream)) return rc;
+    return launched(tile_blend_launch(tiles, image_out, B, tg, s), "tile_blend");
 }
 
 // ---------------------------------------------------------------------------- ensembles of tiled runs
@@ -709,14 +721,12 @@ extern "C" int mi_tile_blend_reduce(const float* tiles, int B, int members, int 
     if (int rc = fill_tile_geom(C, H, W, th, tw, oy, ox, &g)) return rc;
     if (int rc = check_tile_count(B, g)) return rc;
     if (int rc = check_step_noise_range(C, H, W, 0)) return rc;
-    if (members < 1) return fail(MI_EINVAL, "members %d: an ensemble has at least one member (limit: members >= 1)", members);
-    if (B > 65535) return fail(MI_EINVAL, "B %d outside [1, 65535] (the limit of mi_ensemble_reduce, whose arithmetic this call composes)", B);
+    if (int rc = check_members_min(members)) return rc;
+    if (int rc = check_reduce_batch(B, "the limit of mi_ensemble_reduce, whose arithmetic this call composes")) return rc;      // (B >= 1: check_tile_count)
     if (int rc = check_tiled_ensemble_size(B, members, g)) return rc;
-    if (std_out && members < 2) return fail(MI_EINVAL, "std_out needs members >= 2: the unbiased standard deviation of one value is undefined");
+    if (int rc = check_std_members(std_out, members)) return rc;
     if (!tiles || !mean_out) return fail(MI_EINVAL, "null argument");
-    const hipError_t e = tile_blend_reduce_launch(tiles, B, members, g, mean_out, std_out, samples_out, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(MI_EHIP, "tile_blend_reduce: %s", hipGetErrorString(e));
-    return MI_OK;
+    return launched(tile_blend_reduce_launch(tiles, B, members, g, mean_out, std_out, samples_out, (hipStream_t)stream), "tile_blend_reduce");
 }
 
 // Members are the outer loop: member m is mi_denoise_tiled's seeded pass structure with counter word c3 = member_offset + m, a
@@ -731,58 +741,31 @@ extern "C" int mi_denoise_tiled_ensemble(mi_plan* plan, const float* noisy, floa
     if (int rc = check_tiled_ensemble_args(plan, B, members, H, W, th, tw, oy, ox, sample_offset, member_offset, pass_samples, &tg)) return rc;
     if (!mean_out && !std_out && !samples_out && !tiles_out)
         return fail(MI_EINVAL, "no output: give at least one of mean_out, std_out, samples_out, tiles_out");
-    if (std_out && members < 2) return fail(MI_EINVAL, "std_out needs members >= 2: the unbiased standard deviation of one value is undefined");
+    if (int rc = check_std_members(std_out, members)) return rc;
     const int K = tg.ny * tg.nx;
-    const size_t chw = (size_t)tg.C * th * tw;
-    {   // noisy is read by every pass and the reduce reads the tiles while it writes the other three: no two of the five may overlap
-        const size_t img = (size_t)tg.C * H * W * sizeof(float);
-        const struct { const void* p; size_t n; const char* name; } buf[5] = {
-            {noisy, (size_t)B * img, "noisy"}, {mean_out, (size_t)B * img, "mean_out"}, {std_out, (size_t)B * img, "std_out"},
-            {samples_out, (size_t)B * members * img, "samples_out"}, {tiles_out, (size_t)members * B * K * chw * sizeof(float), "tiles_out"}};
-        for (int i = 0; i < 5; ++i)
-            for (int j = i + 1; j < 5; ++j) {
-                const uintptr_t a = (uintptr_t)buf[i].p, b = (uintptr_t)buf[j].p;
-                if (a && b && a < b + buf[j].n && b < a + buf[i].n)
-                    return fail(MI_EINVAL, "%s and %s alias (overlap): noisy is read by every pass and the reduce reads the tiles while it "
-                                "writes mean_out, std_out and samples_out", buf[i].name, buf[j].name);
-            }
-    }
-    if (!plan->finalized) return fail(MI_ESTATE, "mi_unet_finalize has not been called (or weights changed since)");
+    const size_t chw = (size_t)tg.C * th * tw, img = (size_t)tg.C * H * W * sizeof(float);
+    const Buf buf[5] = {{noisy, (size_t)B * img, "noisy"}, {mean_out, (size_t)B * img, "mean_out"}, {std_out, (size_t)B * img, "std_out"},
+                        {samples_out, (size_t)B * members * img, "samples_out"},
+                        {tiles_out, (size_t)members * B * K * chw * sizeof(float), "tiles_out"}};
+    if (int rc = check_no_overlap(buf, 5, "noisy is read by every pass and the reduce reads the tiles while it writes mean_out, std_out and samples_out"))
+        return rc;
+    const Schedule sc{t_list, n_iters, beta, alpha, alpha_hat, noise_steps};
     EnsembleLayout L{};
-    if (int rc = tiled_ensemble_layout(plan, B, members, K, th, tw, pass_samples, tiles_out != nullptr, &L)) return rc;
-    if (!workspace || workspace_bytes < L.bytes) return fail(MI_ENOMEM, "workspace too small: need %zu bytes, got %zu", L.bytes, workspace_bytes);
-    if (((uintptr_t)workspace) & 255) return fail(MI_EINVAL, "workspace must be 256-byte aligned");
-    if (!noisy) return fail(MI_EINVAL, "null argument");
-    if (int rc = check_schedule(plan, t_list, n_iters, beta, alpha, alpha_hat, noise_steps)) return rc;
-    if (int rc = check_device(plan)) return rc;
+    // (evaluated before the state check, reported after it: check_batched_call; host arithmetic only, as in the *_workspace_bytes queries)
+    const int layout_rc = tiled_ensemble_layout(plan, B, members, K, th, tw, pass_samples, tiles_out != nullptr, &L);
+    if (int rc = check_batched_call(plan, layout_rc, L, workspace, workspace_bytes, {noisy}, sc)) return rc;
     hipStream_t s = (hipStream_t)stream;
     char* ws = (char*)workspace;
-    float* cond = reinterpret_cast<float*>(ws + L.cond_off);
     float* tiles = tiles_out ? tiles_out : reinterpret_cast<float*>(ws + L.samples_off);
-    const int64_t V = (int64_t)B * K;                       // virtual samples of ONE member
     std::lock_guard<std::mutex> side_lk(plan->side_mu);     // held over all passes: the side streams are per plan
     HIPCHK(hipMemsetAsync(ws, 0, 256, s));                  // status word: once per call, the passes of every member accumulate into it
     StepNoise sn;
-    sn.seeded = true; sn.seed = seed; sn.sample_offset = sample_offset; sn.members = K;
+    sn.seeded = true; sn.seed = seed; sn.sample_offset = sample_offset; sn.members = K; sn.member_offset = (uint32_t)member_offset;
     sn.tiles_x = tg.nx; sn.tiles_y = tg.ny; sn.img_H = H; sn.img_W = W;
-    RunRows rows; rows.t = t_list; rows.n = n_iters;
-    for (int m = 0; m < members; ++m) {
-        sn.member_offset = (uint32_t)(member_offset + m);
-        for (int64_t v0 = 0; v0 < V; v0 += L.pass) {
-            const int n = (int)(V - v0 < L.pass ? V - v0 : L.pass);
-            const hipError_t e = tile_extract_launch(noisy, cond, tg, (int)v0, n, s);
-            if (e != hipSuccess) return fail(MI_EHIP, "tile_extract: %s", hipGetErrorString(e));
-            sn.v0 = (int)v0;
-            Program* g = nullptr;
-            float* x = tiles + ((size_t)m * V + (size_t)v0) * chw;
-            if (int rc = check_run(plan, cond, x, n, th, tw, t_list, n_iters, beta, alpha, alpha_hat, noise_steps, ws, L.run_bytes, &g)) return rc;
-            if (int rc = enqueue_run(plan, g, cond, x, n, th, tw, rows, beta, alpha, alpha_hat, sn, flags, ws, L.run_bytes, stream)) return rc;
-        }
-    }
-    if (mean_out || std_out || samples_out) {
-        const hipError_t e = tile_blend_reduce_launch(tiles, B, members, tg, mean_out, std_out, samples_out, s);
-        if (e != hipSuccess) return fail(MI_EHIP, "tile_blend_reduce: %s", hipGetErrorString(e));
-    }
+    auto extract = [&](float* cond, int v0, int n) { return launched(tile_extract_launch(noisy, cond, tg, v0, n, s), "tile_extract"); };
+    if (int rc = run_passes(plan, extract, tiles, (int64_t)B * K, members, th, tw, chw, L, sn, sc, flags, ws, stream)) return rc;      // V: ONE member's
+    if (mean_out || std_out || samples_out)
+        return launched(tile_blend_reduce_launch(tiles, B, members, tg, mean_out, std_out, samples_out, s), "tile_blend_reduce");
     return MI_OK;
 }
 
@@ -798,9 +781,8 @@ extern "C" int mi_debug_fetch(mi_plan* plan, const char* module_name, int B, int
     if (C) *C = t.C; if (h) *h = t.H; if (w) *w = t.W;
     if (dst) {
         if (!workspace) return fail(MI_EINVAL, "null workspace");
-        hipError_t e = nhwc_to_nchw_launch(reinterpret_cast<const float*>((const char*)workspace + t.off), dst, B, t.H, t.W, t.C,
-                                           fp16_mfma(plan->cfg) ? 1 : 0, (hipStream_t)stream);
-        if (e != hipSuccess) return fail(MI_EHIP, "nhwc_to_nchw: %s", hipGetErrorString(e));
+        return launched(nhwc_to_nchw_launch(reinterpret_cast<const float*>((const char*)workspace + t.off), dst, B, t.H, t.W, t.C,
+                                            fp16_mfma(plan->cfg) ? 1 : 0, (hipStream_t)stream), "nhwc_to_nchw");
     }
     return MI_OK;
 }

@@ -55,6 +55,10 @@ def _default_init(name: str, shape: Tuple[int, ...], all_shapes: Dict[str, Tuple
     return torch.empty(shape).uniform_(-bound, bound)
 
 
+def _ptr(t: Optional[torch.Tensor]):
+    return None if t is None else t.data_ptr()
+
+
 class UNetDiffusion(nn.Module):
     def __init__(self, in_channels=1, model_channels=48, channel_mult=(1, 2, 3, 4), num_res_blocks=2,
                  attention_resolutions=(3,), dropout=0.0, time_emb_dim=192, variant="ddim", compute=None,
@@ -180,19 +184,22 @@ class UNetDiffusion(nn.Module):
         self._workspaces[key] = ws                # most recently used last
         return ws
 
-    def _ensemble_workspace(self, B: int, K: int, H: int, W: int, pass_samples: int, external: bool, dev: torch.device) -> torch.Tensor:
-        """Scratch of one run_ensemble call: ONE resident entry of its own, beside the (shape, stream) cache above, so that an
-        ensemble call -- whose workspace holds the activations of a whole pass and, unless the caller takes them, every member's
-        output -- evicts none of the sampler workspaces, and a second ensemble shape replaces the first."""
-        key = (B, K, H, W, pass_samples, external, dev.index, torch.cuda.current_stream(dev).cuda_stream)
-        if self._ensemble_ws is not None and self._ensemble_ws[0] == key:
-            return self._ensemble_ws[1]
-        nbytes = native.lib().mi_ensemble_workspace_bytes(self._plan, B, K, H, W, pass_samples, 1 if external else 0)
-        if nbytes == 0:
+    def _resident_workspace(self, attr: str, key: tuple, query_bytes, dev: torch.device) -> torch.Tensor:
+        """Scratch of the batched calls: ONE resident (key, tensor) entry in ``attr``, beside the (shape, stream) cache above, so
+        that a call whose workspace holds the activations of a whole pass and, unless the caller takes them, every sample's output
+        evicts none of the sampler workspaces, and a second shape replaces the first.  ``_ensemble_ws`` serves run_ensemble,
+        run_tiled and run_tiled_ensemble (a pass of tiles is as large as a pass of members), ``_slots_ws`` a session's run_slots
+        calls.  ``query_bytes()`` is asked on a miss only; 0 is the library's refusal (mi_last_error)."""
+        held = getattr(self, attr)
+        if held is not None and held[0] == key:
+            return held[1]
+        n = query_bytes()
+        if n == 0:
             native.check(-1)
-        self._ensemble_ws = None                  # (free the old one before the new one is allocated)
-        ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=dev)
-        self._ensemble_ws = (key, ws)
+        held = None                               # (free the old one before the new one is allocated: this name and the
+        setattr(self, attr, None)                 #  attribute hold the only references to it)
+        ws = torch.empty(n + 256, dtype=torch.uint8, device=dev)
+        setattr(self, attr, (key, ws))
         return ws
 
     @staticmethod
@@ -214,6 +221,33 @@ class UNetDiffusion(nn.Module):
             flags = C.c_int()
             native.check(native.lib().mi_status(wptr, stream, C.byref(flags)))
 
+    @staticmethod
+    def _table_args(beta, alpha, alpha_hat):
+        """-> (host arrays to keep alive over the call, (beta, alpha, alpha_hat, noise_steps) as the native calls take them)"""
+        tabs = [np.ascontiguousarray(v.detach().to("cpu", torch.float32).numpy()) for v in (beta, alpha, alpha_hat)]
+        return tabs, tuple(t.ctypes.data_as(C.POINTER(C.c_float)) for t in tabs) + (int(tabs[0].shape[0]),)
+
+    @staticmethod
+    def _schedule_args(t_list, beta, alpha, alpha_hat):
+        """-> (host arrays to keep alive over the call, (t_list, n_iters, beta, alpha, alpha_hat, noise_steps) of a uniform schedule)"""
+        steps = np.ascontiguousarray(np.asarray(list(t_list), dtype=np.int32))
+        tabs, tail = UNetDiffusion._table_args(beta, alpha, alpha_hat)
+        return [steps] + tabs, (steps.ctypes.data_as(C.POINTER(C.c_int32)), len(steps)) + tail
+
+    @staticmethod
+    def _call_flags(clamp_eps: bool, no_split: bool) -> int:
+        return (native.MI_CLAMP_EPS if clamp_eps else 0) | (native.MI_NO_SPLIT if no_split else 0)
+
+    def _invoke(self, fn, head: tuple, ws: torch.Tensor, dev: torch.device) -> None:
+        """One native call ``fn(*head, workspace, workspace_bytes, stream)`` on the current stream, then its status word.  Runs
+        inside the caller's ``with self._lock, torch.cuda.device(dev)`` block."""
+        if self.poison_workspace is not None:
+            ws.fill_(self.poison_workspace)
+        wptr, wbytes = self._aligned_ptr(ws)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        native.check(fn(*head, wptr, wbytes, stream))
+        self._raise_on_status(wptr, stream)
+
     # ------------------------------------------------------------------ reference interface
     @torch.no_grad()
     def forward(self, x: torch.Tensor, condition: torch.Tensor, t: torch.Tensor) -> torch.Tensor:
@@ -231,15 +265,9 @@ class UNetDiffusion(nn.Module):
             plan = self._ensure_plan(time_rows=int(t_host.max()) + 1 if B else None)
             xc, cc = x.contiguous(), condition.contiguous()
             eps = torch.empty_like(xc)
-            ws = self._workspace(B, H, W, x.device)
-            if self.poison_workspace is not None:
-                ws.fill_(self.poison_workspace)
-            wptr, wbytes = self._aligned_ptr(ws)
-            stream = torch.cuda.current_stream(x.device).cuda_stream
-            native.check(native.lib().mi_unet_forward(
-                plan, xc.data_ptr(), cc.data_ptr(), t_host.ctypes.data_as(C.POINTER(C.c_int32)), eps.data_ptr(),
-                B, H, W, wptr, wbytes, stream))
-            self._raise_on_status(wptr, stream)
+            self._invoke(native.lib().mi_unet_forward,
+                         (plan, xc.data_ptr(), cc.data_ptr(), t_host.ctypes.data_as(C.POINTER(C.c_int32)), eps.data_ptr(), B, H, W),
+                         self._workspace(B, H, W, x.device), x.device)
         return eps
 
     @torch.no_grad()
@@ -267,35 +295,29 @@ class UNetDiffusion(nn.Module):
             raise ValueError("member selects a draw of the seeded generator: pass seed as well")
         self._check_image(noisy, "noisy_img")
         B, _, H, W = noisy.shape
-        steps = np.ascontiguousarray(np.asarray(list(t_list), dtype=np.int32))
-        tabs = [np.ascontiguousarray(v.detach().to("cpu", torch.float32).numpy()) for v in (beta, alpha, alpha_hat)]
-        noise_steps = int(tabs[0].shape[0])
+        keep, sched = self._schedule_args(t_list, beta, alpha, alpha_hat)
         with self._lock, torch.cuda.device(noisy.device):
-            plan = self._ensure_plan(time_rows=noise_steps)
+            plan = self._ensure_plan(time_rows=sched[-1])
             src = noisy.contiguous()
             out = torch.empty_like(src)
-            nptr = None
-            if step_noise is not None:
-                if step_noise.shape != (len(steps),) + tuple(src.shape) or step_noise.device != src.device:
-                    raise ValueError("step_noise must be [n_iters,B,C,H,W] on the image's device")
-                step_noise = step_noise.to(torch.float32).contiguous()
-                nptr = step_noise.data_ptr()
-            ws = self._workspace(B, H, W, noisy.device)
-            if self.poison_workspace is not None:
-                ws.fill_(self.poison_workspace)
-            wptr, wbytes = self._aligned_ptr(ws)
-            stream = torch.cuda.current_stream(noisy.device).cuda_stream
-            fp = C.POINTER(C.c_float)
-            head = (plan, src.data_ptr(), out.data_ptr(), B, H, W,
-                    steps.ctypes.data_as(C.POINTER(C.c_int32)), len(steps),
-                    tabs[0].ctypes.data_as(fp), tabs[1].ctypes.data_as(fp), tabs[2].ctypes.data_as(fp), noise_steps)
-            tail = ((native.MI_CLAMP_EPS if clamp_eps else 0) | (native.MI_NO_SPLIT if no_split else 0), wptr, wbytes, stream)
+            head = (plan, src.data_ptr(), out.data_ptr(), B, H, W) + sched
+            flags = self._call_flags(clamp_eps, no_split)
             if seed is not None:
-                native.check(native.lib().mi_denoise_seeded(*head, C.c_uint64(seed), C.c_int64(sample_offset), *tail))
+                fn, head = native.lib().mi_denoise_seeded, head + (C.c_uint64(seed), C.c_int64(sample_offset), flags)
             else:
-                native.check(native.lib().mi_denoise(*head, nptr, *tail))
-            self._raise_on_status(wptr, stream)
+                step_noise = self._step_noise(step_noise, sched[1], src, "n_iters")
+                fn, head = native.lib().mi_denoise, head + (_ptr(step_noise), flags)
+            self._invoke(fn, head, self._workspace(B, H, W, noisy.device), noisy.device)
         return out
+
+    @staticmethod
+    def _step_noise(step_noise: Optional[torch.Tensor], n: int, images: torch.Tensor, rows: str) -> Optional[torch.Tensor]:
+        """The caller's noise tensor [n, B, C, H, W] as the native calls read it (the caller keeps the result alive over the call)."""
+        if step_noise is None:
+            return None
+        if step_noise.shape != (n,) + tuple(images.shape) or step_noise.device != images.device:
+            raise ValueError(f"step_noise must be [{rows},B,C,H,W] on the image's device")
+        return step_noise.to(torch.float32).contiguous()
 
     @torch.no_grad()
     def run_slots(self, cond: torch.Tensor, x: torch.Tensor, t_rows, beta: torch.Tensor, alpha: torch.Tensor, alpha_hat: torch.Tensor,
@@ -327,45 +349,26 @@ class UNetDiffusion(nn.Module):
             if ib.size and (ib.min() < -(1 << 31) or ib.max() >= 1 << 31):
                 raise ValueError("iter_base must fit 32 bits")
             ib = ib.astype(np.int32)
-        tabs = [np.ascontiguousarray(v.detach().to("cpu", torch.float32).numpy()) for v in (beta, alpha, alpha_hat)]
-        noise_steps = int(tabs[0].shape[0])
-        with self._lock, torch.cuda.device(cond.device):
-            plan = self._ensure_plan(time_rows=noise_steps)
-            nptr = None
-            if step_noise is not None:
-                if step_noise.shape != (n_rows,) + tuple(cond.shape) or step_noise.device != cond.device:
-                    raise ValueError("step_noise must be [n_rows,B,C,H,W] on the image's device")
-                step_noise = step_noise.to(torch.float32).contiguous()
-                nptr = step_noise.data_ptr()
-            ws = self._workspace(B, H, W, cond.device) if not max_slots else self._slots_workspace(max(int(max_slots), B), H, W, cond.device)
-            if self.poison_workspace is not None:
-                ws.fill_(self.poison_workspace)
-            wptr, wbytes = self._aligned_ptr(ws)
-            stream = torch.cuda.current_stream(cond.device).cuda_stream
-            fp = C.POINTER(C.c_float)
-            native.check(native.lib().mi_denoise_slots(
-                plan, cond.data_ptr(), x.data_ptr(), B, H, W, rows.ctypes.data_as(C.POINTER(C.c_int32)), n_rows,
-                None if ib is None else ib.ctypes.data_as(C.POINTER(C.c_int32)),
-                None if si is None else si.ctypes.data_as(C.POINTER(C.c_int64)),
-                tabs[0].ctypes.data_as(fp), tabs[1].ctypes.data_as(fp), tabs[2].ctypes.data_as(fp), noise_steps,
-                nptr, 0 if seed is None else 1, C.c_uint64(seed or 0),
-                (native.MI_CLAMP_EPS if clamp_eps else 0) | (native.MI_NO_SPLIT if no_split else 0), wptr, wbytes, stream))
-            self._raise_on_status(wptr, stream)
+        keep, tables = self._table_args(beta, alpha, alpha_hat)
+        dev = cond.device
+        with self._lock, torch.cuda.device(dev):
+            plan = self._ensure_plan(time_rows=tables[-1])
+            step_noise = self._step_noise(step_noise, n_rows, cond, "n_rows")
+            ws = self._workspace(B, H, W, dev) if not max_slots else self._slots_workspace(max(int(max_slots), B), H, W, dev)
+            self._invoke(native.lib().mi_denoise_slots,
+                         (plan, cond.data_ptr(), x.data_ptr(), B, H, W, rows.ctypes.data_as(C.POINTER(C.c_int32)), n_rows,
+                          None if ib is None else ib.ctypes.data_as(C.POINTER(C.c_int32)),
+                          None if si is None else si.ctypes.data_as(C.POINTER(C.c_int64))) + tables
+                         + (_ptr(step_noise), 0 if seed is None else 1, C.c_uint64(seed or 0), self._call_flags(clamp_eps, no_split)), ws, dev)
         return x
 
     def _slots_workspace(self, max_slots: int, H: int, W: int, dev: torch.device) -> torch.Tensor:
-        """Scratch of the run_slots calls of one session: large enough for every batch of 1 .. max_slots slots, one resident entry
-        beside the (shape, stream) cache, so a batch that changes from call to call neither allocates nor evicts."""
-        key = (max_slots, H, W, dev.index, torch.cuda.current_stream(dev).cuda_stream)
-        if self._slots_ws is not None and self._slots_ws[0] == key:
-            return self._slots_ws[1]
-        sizes = [native.lib().mi_workspace_bytes(self._plan, b, H, W) for b in range(1, max_slots + 1)]
-        if min(sizes) == 0:
-            native.check(-1)
-        self._slots_ws = None                     # (free the old one before the new one is allocated)
-        ws = torch.empty(max(sizes) + 256, dtype=torch.uint8, device=dev)
-        self._slots_ws = (key, ws)
-        return ws
+        """Scratch of the run_slots calls of one session: large enough for every batch of 1 .. max_slots slots, so a batch that
+        changes from call to call neither allocates nor evicts."""
+        def query_bytes():
+            sizes = [native.lib().mi_workspace_bytes(self._plan, b, H, W) for b in range(1, max_slots + 1)]
+            return 0 if min(sizes) == 0 else max(sizes)
+        return self._resident_workspace("_slots_ws", (max_slots, H, W, dev.index, torch.cuda.current_stream(dev).cuda_stream), query_bytes, dev)
 
     @torch.no_grad()
     def run_ensemble(self, noisy: torch.Tensor, t_list, beta: torch.Tensor, alpha: torch.Tensor, alpha_hat: torch.Tensor,
@@ -375,41 +378,30 @@ class UNetDiffusion(nn.Module):
         """``members`` seeded draws per image in one native call (mi_denoise_ensemble) -> (mean, std, samples), each None when
         not asked for.  The B * members (image, member) pairs run through the sampler loop in passes of at most ``max_batch``;
         samples is [B, members, C, H, W]."""
-        from .sampler import check_member, check_seed
+        from .sampler import check_members, check_seed
         seed, sample_offset = check_seed(seed, sample_offset)
-        members, member_offset = check_member(members, "members", low=1), check_member(member_offset, "member_offset")
-        max_batch = check_member(max_batch, "max_batch", low=1)
-        if member_offset + members > 1 << 32:
-            raise ValueError(f"member_offset + members must be <= 2**32 (got {member_offset} + {members})")
+        members, member_offset, max_batch = check_members(members, member_offset, max_batch)
         want_std = want_std and members >= 2
         if not (want_mean or want_std or want_samples):
             raise ValueError("nothing to return: ask for the mean, the std or the samples")
         self._check_image(noisy, "noisy_img")
         B, Cc, H, W = noisy.shape
-        steps = np.ascontiguousarray(np.asarray(list(t_list), dtype=np.int32))
-        tabs = [np.ascontiguousarray(v.detach().to("cpu", torch.float32).numpy()) for v in (beta, alpha, alpha_hat)]
-        noise_steps = int(tabs[0].shape[0])
-        with self._lock, torch.cuda.device(noisy.device):
-            plan = self._ensure_plan(time_rows=noise_steps)
+        keep, sched = self._schedule_args(t_list, beta, alpha, alpha_hat)
+        dev = noisy.device
+        with self._lock, torch.cuda.device(dev):
+            plan = self._ensure_plan(time_rows=sched[-1])
             src = noisy.contiguous()
             mean = torch.empty_like(src) if want_mean else None
             std = torch.empty_like(src) if want_std else None
-            samples = torch.empty((B, members, Cc, H, W), dtype=torch.float32, device=src.device) if want_samples else None
+            samples = torch.empty((B, members, Cc, H, W), dtype=torch.float32, device=dev) if want_samples else None
             pass_samples = min(max_batch, max(1, B * members))
-            ws = self._ensemble_workspace(B, members, H, W, pass_samples, want_samples, noisy.device)
-            if self.poison_workspace is not None:
-                ws.fill_(self.poison_workspace)
-            wptr, wbytes = self._aligned_ptr(ws)
-            stream = torch.cuda.current_stream(noisy.device).cuda_stream
-            fp = C.POINTER(C.c_float)
-            ptr = lambda t: None if t is None else t.data_ptr()      # noqa: E731
-            native.check(native.lib().mi_denoise_ensemble(
-                plan, src.data_ptr(), ptr(mean), ptr(std), ptr(samples), B, members, H, W,
-                steps.ctypes.data_as(C.POINTER(C.c_int32)), len(steps),
-                tabs[0].ctypes.data_as(fp), tabs[1].ctypes.data_as(fp), tabs[2].ctypes.data_as(fp), noise_steps,
-                C.c_uint64(seed), C.c_int64(sample_offset), C.c_int64(member_offset), pass_samples,
-                (native.MI_CLAMP_EPS if clamp_eps else 0) | (native.MI_NO_SPLIT if no_split else 0), wptr, wbytes, stream))
-            self._raise_on_status(wptr, stream)
+            size = (B, members, H, W, pass_samples)
+            ws = self._resident_workspace("_ensemble_ws", size + (want_samples, dev.index, torch.cuda.current_stream(dev).cuda_stream),
+                                          lambda: native.lib().mi_ensemble_workspace_bytes(self._plan, *size, 1 if want_samples else 0), dev)
+            self._invoke(native.lib().mi_denoise_ensemble,
+                         (plan, src.data_ptr(), _ptr(mean), _ptr(std), _ptr(samples), B, members, H, W) + sched
+                         + (C.c_uint64(seed), C.c_int64(sample_offset), C.c_int64(member_offset), pass_samples,
+                            self._call_flags(clamp_eps, no_split)), ws, dev)
         return mean, std, samples
 
     @torch.no_grad()
@@ -418,37 +410,26 @@ class UNetDiffusion(nn.Module):
                   want_tiles: bool = False, no_split: bool = False):
         """Images of any size >= the tile as blended overlapping tiles in one native call (mi_denoise_tiled) ->
         (image, tiles or None, TilePlan).  seed None: no noise term (DDIM)."""
-        from .sampler import check_member, check_seed, tile_plan
+        from .sampler import check_member, check_seed, tiling
         if seed is not None:
             seed, sample_offset = check_seed(seed, sample_offset)
         max_batch = check_member(max_batch, "max_batch", low=1)
         self._check_image(noisy, "noisy_img")
         B, Cc, H, W = noisy.shape
-        plan_t = tile_plan(H, W, tile, overlap)
-        (th, tw), (oy, ox) = plan_t.tile, plan_t.overlap
-        K = len(plan_t.origins_y) * len(plan_t.origins_x)
-        steps = np.ascontiguousarray(np.asarray(list(t_list), dtype=np.int32))
-        tabs = [np.ascontiguousarray(v.detach().to("cpu", torch.float32).numpy()) for v in (beta, alpha, alpha_hat)]
-        noise_steps = int(tabs[0].shape[0])
-        with self._lock, torch.cuda.device(noisy.device):
-            plan = self._ensure_plan(time_rows=noise_steps)
+        plan_t, th, tw, oy, ox, K = tiling(H, W, tile, overlap)
+        keep, sched = self._schedule_args(t_list, beta, alpha, alpha_hat)
+        dev = noisy.device
+        with self._lock, torch.cuda.device(dev):
+            plan = self._ensure_plan(time_rows=sched[-1])
             src = noisy.contiguous()
             image = torch.empty_like(src)
-            tiles = torch.empty((B, K, Cc, th, tw), dtype=torch.float32, device=src.device) if want_tiles else None
+            tiles = torch.empty((B, K, Cc, th, tw), dtype=torch.float32, device=dev) if want_tiles else None
             pass_samples = min(max_batch, max(1, B * K))
-            ws = self._tiled_workspace((B, H, W, th, tw, oy, ox, pass_samples, 1 if want_tiles else 0), noisy.device)
-            if self.poison_workspace is not None:
-                ws.fill_(self.poison_workspace)
-            wptr, wbytes = self._aligned_ptr(ws)
-            stream = torch.cuda.current_stream(noisy.device).cuda_stream
-            fp = C.POINTER(C.c_float)
-            native.check(native.lib().mi_denoise_tiled(
-                plan, src.data_ptr(), image.data_ptr(), None if tiles is None else tiles.data_ptr(), B, H, W, th, tw, oy, ox,
-                steps.ctypes.data_as(C.POINTER(C.c_int32)), len(steps),
-                tabs[0].ctypes.data_as(fp), tabs[1].ctypes.data_as(fp), tabs[2].ctypes.data_as(fp), noise_steps,
-                0 if seed is None else 1, C.c_uint64(seed or 0), C.c_int64(sample_offset), pass_samples,
-                (native.MI_CLAMP_EPS if clamp_eps else 0) | (native.MI_NO_SPLIT if no_split else 0), wptr, wbytes, stream))
-            self._raise_on_status(wptr, stream)
+            ws = self._tiled_workspace((B, H, W, th, tw, oy, ox, pass_samples, 1 if want_tiles else 0), dev)
+            self._invoke(native.lib().mi_denoise_tiled,
+                         (plan, src.data_ptr(), image.data_ptr(), _ptr(tiles), B, H, W, th, tw, oy, ox) + sched
+                         + (0 if seed is None else 1, C.c_uint64(seed or 0), C.c_int64(sample_offset), pass_samples,
+                            self._call_flags(clamp_eps, no_split)), ws, dev)
         return image, tiles, plan_t
 
     @torch.no_grad()
@@ -460,79 +441,53 @@ class UNetDiffusion(nn.Module):
         (mean, std, samples, tiles, TilePlan), each tensor None when not asked for.  Members are the outer loop; inside a member
         the B * tiles crops run in passes of at most ``max_batch``, as run_tiled runs them.  samples is [B, members, C, H, W],
         tiles [members, B, ny * nx, C, th, tw]."""
-        from .sampler import check_member, check_seed, tile_plan
+        from .sampler import check_members, check_seed, tiling
         seed, sample_offset = check_seed(seed, sample_offset)
-        members, member_offset = check_member(members, "members", low=1), check_member(member_offset, "member_offset")
-        max_batch = check_member(max_batch, "max_batch", low=1)
-        if member_offset + members > 1 << 32:
-            raise ValueError(f"member_offset + members must be <= 2**32 (got {member_offset} + {members})")
+        members, member_offset, max_batch = check_members(members, member_offset, max_batch)
         want_std = want_std and members >= 2
         if not (want_mean or want_std or want_samples or want_tiles):
             raise ValueError("nothing to return: ask for the mean, the std, the samples or the tiles")
         self._check_image(noisy, "noisy_img")
         B, Cc, H, W = noisy.shape
-        plan_t = tile_plan(H, W, tile, overlap)
-        (th, tw), (oy, ox) = plan_t.tile, plan_t.overlap
-        K = len(plan_t.origins_y) * len(plan_t.origins_x)
-        steps = np.ascontiguousarray(np.asarray(list(t_list), dtype=np.int32))
-        tabs = [np.ascontiguousarray(v.detach().to("cpu", torch.float32).numpy()) for v in (beta, alpha, alpha_hat)]
-        noise_steps = int(tabs[0].shape[0])
-        with self._lock, torch.cuda.device(noisy.device):
-            plan = self._ensure_plan(time_rows=noise_steps)
+        plan_t, th, tw, oy, ox, K = tiling(H, W, tile, overlap)
+        keep, sched = self._schedule_args(t_list, beta, alpha, alpha_hat)
+        dev = noisy.device
+        with self._lock, torch.cuda.device(dev):
+            plan = self._ensure_plan(time_rows=sched[-1])
             src = noisy.contiguous()
             mean = torch.empty_like(src) if want_mean else None
             std = torch.empty_like(src) if want_std else None
-            samples = torch.empty((B, members, Cc, H, W), dtype=torch.float32, device=src.device) if want_samples else None
-            tiles = torch.empty((members, B, K, Cc, th, tw), dtype=torch.float32, device=src.device) if want_tiles else None
+            samples = torch.empty((B, members, Cc, H, W), dtype=torch.float32, device=dev) if want_samples else None
+            tiles = torch.empty((members, B, K, Cc, th, tw), dtype=torch.float32, device=dev) if want_tiles else None
             pass_samples = min(max_batch, max(1, B * K))
-            ws = self._tiled_workspace((B, members, H, W, th, tw, oy, ox, pass_samples, 1 if want_tiles else 0), noisy.device, ensemble=True)
-            if self.poison_workspace is not None:
-                ws.fill_(self.poison_workspace)
-            wptr, wbytes = self._aligned_ptr(ws)
-            stream = torch.cuda.current_stream(noisy.device).cuda_stream
-            fp = C.POINTER(C.c_float)
-            ptr = lambda t: None if t is None else t.data_ptr()      # noqa: E731
-            native.check(native.lib().mi_denoise_tiled_ensemble(
-                plan, src.data_ptr(), ptr(mean), ptr(std), ptr(samples), ptr(tiles), B, members, H, W, th, tw, oy, ox,
-                steps.ctypes.data_as(C.POINTER(C.c_int32)), len(steps),
-                tabs[0].ctypes.data_as(fp), tabs[1].ctypes.data_as(fp), tabs[2].ctypes.data_as(fp), noise_steps,
-                C.c_uint64(seed), C.c_int64(sample_offset), C.c_int64(member_offset), pass_samples,
-                (native.MI_CLAMP_EPS if clamp_eps else 0) | (native.MI_NO_SPLIT if no_split else 0), wptr, wbytes, stream))
-            self._raise_on_status(wptr, stream)
+            ws = self._tiled_workspace((B, members, H, W, th, tw, oy, ox, pass_samples, 1 if want_tiles else 0), dev, ensemble=True)
+            self._invoke(native.lib().mi_denoise_tiled_ensemble,
+                         (plan, src.data_ptr(), _ptr(mean), _ptr(std), _ptr(samples), _ptr(tiles), B, members, H, W, th, tw, oy, ox) + sched
+                         + (C.c_uint64(seed), C.c_int64(sample_offset), C.c_int64(member_offset), pass_samples,
+                            self._call_flags(clamp_eps, no_split)), ws, dev)
         return mean, std, samples, tiles, plan_t
 
     def _tiled_workspace(self, args: tuple, dev: torch.device, ensemble: bool = False) -> torch.Tensor:
-        """Scratch of one run_tiled (or, ``ensemble``, run_tiled_ensemble) call; shares the one resident entry of the ensemble
-        calls (a pass of tiles is as large as a pass of members), so it evicts none of the sampler workspaces either."""
-        key = ("tiled_ensemble" if ensemble else "tiled",) + args + (dev.index, torch.cuda.current_stream(dev).cuda_stream)
-        if self._ensemble_ws is not None and self._ensemble_ws[0] == key:
-            return self._ensemble_ws[1]
+        """Scratch of one run_tiled (or, ``ensemble``, run_tiled_ensemble) call: the resident entry of the ensemble calls."""
         query = native.lib().mi_tiled_ensemble_workspace_bytes if ensemble else native.lib().mi_tiled_workspace_bytes
-        nbytes = query(self._plan, *args)
-        if nbytes == 0:
-            native.check(-1)
-        self._ensemble_ws = None                  # (free the old one before the new one is allocated)
-        ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=dev)
-        self._ensemble_ws = (key, ws)
-        return ws
+        key = ("tiled_ensemble" if ensemble else "tiled",) + args + (dev.index, torch.cuda.current_stream(dev).cuda_stream)
+        return self._resident_workspace("_ensemble_ws", key, lambda: query(self._plan, *args), dev)
 
     def tiled_workspace_bytes(self, B: int, H: int, W: int, tile, overlap=32, max_batch: int = 16, tiles_external: bool = False) -> int:
-        from .sampler import tile_plan
-        p = tile_plan(H, W, tile, overlap)
-        K = len(p.origins_y) * len(p.origins_x)
+        from .sampler import tiling
+        _, th, tw, oy, ox, K = tiling(H, W, tile, overlap)
         with self._lock, torch.cuda.device(self._device()):
             self._ensure_plan()
-            return int(native.lib().mi_tiled_workspace_bytes(self._plan, B, H, W, p.tile[0], p.tile[1], p.overlap[0], p.overlap[1],
-                                                             min(max_batch, max(1, B * K)), 1 if tiles_external else 0))
+            return int(native.lib().mi_tiled_workspace_bytes(self._plan, B, H, W, th, tw, oy, ox, min(max_batch, max(1, B * K)),
+                                                             1 if tiles_external else 0))
 
     def tiled_ensemble_workspace_bytes(self, B: int, members: int, H: int, W: int, tile, overlap=32, max_batch: int = 16,
                                        tiles_external: bool = False) -> int:
-        from .sampler import tile_plan
-        p = tile_plan(H, W, tile, overlap)
-        K = len(p.origins_y) * len(p.origins_x)
+        from .sampler import tiling
+        _, th, tw, oy, ox, K = tiling(H, W, tile, overlap)
         with self._lock, torch.cuda.device(self._device()):
             self._ensure_plan()
-            return int(native.lib().mi_tiled_ensemble_workspace_bytes(self._plan, B, members, H, W, p.tile[0], p.tile[1], p.overlap[0], p.overlap[1],
+            return int(native.lib().mi_tiled_ensemble_workspace_bytes(self._plan, B, members, H, W, th, tw, oy, ox,
                                                                       min(max_batch, max(1, B * K)), 1 if tiles_external else 0))
 
     def ensemble_workspace_bytes(self, B: int, members: int, H: int, W: int, max_batch: int = 16, samples_external: bool = False) -> int:

@@ -43,6 +43,15 @@ def check_member(member, what: str = "member", low: int = 0) -> int:
     return _integer(member, what, 1 << 32 if low == 0 else 1 << 31, low)
 
 
+def check_members(members, member_offset, max_batch) -> Tuple[int, int, int]:
+    """Argument rules of an ensemble call (include/midd.h: mi_denoise_ensemble) -> (members, member_offset, max_batch)."""
+    members, member_offset = check_member(members, "members", low=1), check_member(member_offset, "member_offset")
+    max_batch = check_member(max_batch, "max_batch", low=1)
+    if member_offset + members > 1 << 32:
+        raise ValueError(f"member_offset + members must be <= 2**32 (got {member_offset} + {members})")
+    return members, member_offset, max_batch
+
+
 class EnsembleResult(NamedTuple):
     """What ``DiffusionDenoiser.denoise_ensemble`` returns."""
     mean: torch.Tensor                    # [B, C, H, W]: per-pixel mean of the members
@@ -147,6 +156,12 @@ def tile_plan(H: int, W: int, tile, overlap=32) -> TilePlan:
     return TilePlan((th, tw), (oy, ox), _axis(H, th, oy), _axis(W, tw, ox))
 
 
+def tiling(H: int, W: int, tile, overlap=32) -> Tuple[TilePlan, int, int, int, int, int]:
+    """``tile_plan`` with what the native calls take: (plan, th, tw, oy, ox, tiles per image)."""
+    plan = tile_plan(H, W, tile, overlap)
+    return (plan,) + plan.tile + plan.overlap + (len(plan.origins_y) * len(plan.origins_x),)
+
+
 def _tile_tensor(x, what: str, dims: int) -> torch.Tensor:
     if not isinstance(x, torch.Tensor) or x.dim() != dims or min(x.shape) < 1:
         raise ValueError(f"{what} must be a {dims}-dimensional non-empty tensor")
@@ -162,8 +177,7 @@ def tile_extract(images: torch.Tensor, tile, overlap=32) -> torch.Tensor:
     """[B, C, H, W] -> its tiles [B, ny * nx, C, th, tw] (mi_tile_extract): what ``denoise_tiled`` feeds the sampler."""
     src = _tile_tensor(images, "images", 4)
     B, Cc, H, W = src.shape
-    plan = tile_plan(H, W, tile, overlap)
-    (th, tw), (oy, ox), K = plan.tile, plan.overlap, len(plan.origins_y) * len(plan.origins_x)
+    _, th, tw, oy, ox, K = tiling(H, W, tile, overlap)
     with torch.cuda.device(src.device):
         out = torch.empty((B, K, Cc, th, tw), dtype=torch.float32, device=src.device)
         stream = torch.cuda.current_stream(src.device).cuda_stream
@@ -284,10 +298,7 @@ class DiffusionDenoiser:
         has no ensemble."""
         if getattr(self.model, "variant", "ddim") != "cddpm":
             raise ValueError("denoise_ensemble needs the stochastic (cddpm) variant: a deterministic sampler has no ensemble")
-        if seed is None:
-            hi, lo = torch.randint(0, 1 << 32, (2,), dtype=torch.int64).tolist()
-            seed = (hi << 32) | lo
-        seed, _ = check_seed(seed, 0)             # (everything else is judged by run_ensemble, before any GPU work)
+        seed, _ = check_seed(self._draw_seed() if seed is None else seed, 0)      # (everything else is judged by run_ensemble, before any GPU work)
         self.model.eval()
         steps = timestep_list(self.noise_steps, inference_steps)
         mean, std, samples = self.model.run_ensemble(noisy_img, steps, self.beta, self.alpha, self.alpha_hat, clamp_eps=False,
@@ -317,10 +328,7 @@ class DiffusionDenoiser:
         if not stochastic and seed is not None:
             raise ValueError("seed selects the step noise of the stochastic (cddpm) variant: the DDIM variant takes seed=None")
         if stochastic:
-            if seed is None:
-                hi, lo = torch.randint(0, 1 << 32, (2,), dtype=torch.int64).tolist()
-                seed = (hi << 32) | lo
-            seed, sample_offset = check_seed(seed, sample_offset)
+            seed, sample_offset = check_seed(self._draw_seed() if seed is None else seed, sample_offset)
         self.model.eval()
         steps = timestep_list(self.noise_steps, inference_steps)
         image, tiles, plan = self.model.run_tiled(noisy_img, steps, self.beta, self.alpha, self.alpha_hat, clamp_eps=not stochastic,
@@ -352,9 +360,7 @@ class DiffusionDenoiser:
                              "image position and member (pass seed; midd_amd.step_noise(seed, n, x.shape, member=m) exports the same values)")
         if getattr(self.model, "variant", "ddim") != "cddpm":
             raise ValueError("denoise_tiled_ensemble needs the stochastic (cddpm) variant: a deterministic sampler has no ensemble")
-        if seed is None:
-            seed = self._draw_seed()
-        seed, _ = check_seed(seed, 0)             # (everything else is judged by run_tiled_ensemble, before any GPU work)
+        seed, _ = check_seed(self._draw_seed() if seed is None else seed, 0)      # (everything else is judged by run_tiled_ensemble, before any GPU work)
         self.model.eval()
         steps = timestep_list(self.noise_steps, inference_steps)
         mean, std, samples, tiles, plan = self.model.run_tiled_ensemble(
