@@ -397,6 +397,11 @@ int mi_debug_conv16_geometry(int ks, int stride, int tw, int mt, int nt, int wm,
  * kernel of MI_COMPUTE_F16 (halved image and weight slices: other ring depths and pieces per wave). */
 int mi_debug_conv16_geometry_planes(int ks, int stride, int tw, int mt, int nt, int wm, int wn, int cb, int planes,
                                     int* ring, int* ppw, int* apw, int* lds_bytes);
+/* Debug/test hook, host only: the number of 32-wide K steps per tile the fp16-MFMA convolution kernel walks, and the packed
+ * weights hold, for (Cin, ks) with cb 16-channel blocks per chunk (0: the default of the kernel size; 2: the wide 3x3 chunks).
+ * The one function kernel, packer and planner share (conv16_num_steps); the folded res_conv's steps are not included.
+ * 3x3, 16-channel chunks: the pair walk, (nblk / 2) * 9 + (nblk & 1) * 5 with nblk = Cin / 16.  Negative MI_E* on bad arguments. */
+int mi_debug_conv16_steps(int Cin, int ks, int cb);
 
 /* First 16 hex digits of the sha256 over the kernel sources (csrc/ *.h, *.hip) this library was BUILT from, embedded at
  * build time: what bench.py / tools/pmc_traffic.py compare profiles against (not the working tree). */

@@ -24,8 +24,10 @@
 //     the slots it fetched itself (norm, SiLU, 2^s prescale, hi/lo split) into the MFMA image
 //     [block 0/1][hi|lo][halo pixel][16 fp16] (32 B per pixel and plane: a fragment read is
 //     2 x 512 contiguous bytes, conflict-free).
-// K walk: 32 input channels (two 16-channel blocks) per step and tap; a trailing single block
-// (Cin = 48, 144) pairs two TAPS per step instead.
+// K walk, wide chunks (CB = 2) and 1x1: 32 input channels (two 16-channel blocks) per step and tap; a trailing single
+// block (Cin = 48, 144) pairs two TAPS per step instead.  16-channel chunks of a 3x3 (CB = 1, the default): two taps per
+// step, and two chunks share the step that the ninth tap would leave half empty -- 4 + 5 steps per pair of chunks, the
+// "pair walk" (conv_mfma_f16x3_body.h; conv16_num_steps in midd_internal.h is the one place that counts the steps).
 #include "f16x3_common.h"
 #include <cstdlib>
 #include <type_traits>

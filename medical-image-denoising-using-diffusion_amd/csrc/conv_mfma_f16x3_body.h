@@ -119,9 +119,13 @@ __global__ MIDD_CONV16_BOUNDS void MIDD_CONV16_KERNEL(const ConvArgs a) {
     auto set_tile = [&](int t) {
         const int iy0 = (t / a.tiles_x) * TH * STRIDE - PAD, ix0 = (t % a.tiles_x) * TW * STRIDE - PAD;
         tile_pad = iy0 < 0 || ix0 < 0 || iy0 + G::IH > a.H || ix0 + IW > a.W;
+        // opaque copy of the thread index: a slot's halo row / column is worked out HERE, once per tile (a handful of
+        // instructions), instead of being hoisted into 2 * APW registers that stay live across the whole K loop
+        int tid_ = tid;
+        asm volatile("" : "+v"(tid_));
 #pragma unroll
         for (int s = 0; s < APW; ++s) {
-            const int slot = tid + s * NTHREADS;
+            const int slot = tid_ + s * NTHREADS;
             int off = -2;
             if (slot < NSLOT) {
                 const int pix = slot / QPP;
@@ -256,7 +260,23 @@ __global__ MIDD_CONV16_BOUNDS void MIDD_CONV16_KERNEL(const ConvArgs a) {
     //   N = (D-1)*PPW [+ APW].   At the chunk end the groups younger than A(c+1) are the
     // min(nsteps-1, D) weight groups issued after it.  The slot refilled after the barrier of step
     // s, (s+D)%RING == (s-1)%RING, was last read before that barrier by every wave.
+    //
+    // Pair walk (PAIR: 3x3, 16-channel chunks).  Chunks of a tile are taken in pairs (c even, c + 1): 4 steps, taps (0|1)
+    // (2|3) (4|5) (6|7) of block c, then 5 steps, (tap 8 of block c | tap 0 of block c + 1), (1|2) (3|4) (5|6) (7|8) of block
+    // c + 1; an unpaired last chunk keeps 5 steps with a zero-weight upper half.  One image buffer: after its fourth step the
+    // even chunk reads its tap-8 fragments into xh / xl (dead until the next step), the chunk end's lgkmcnt(0) + barrier
+    // retire them before transform(c + 1) rewrites the image, and the odd chunk's first step loads tap 0 of the new image
+    // into lanes kq >= 2 only.  Per step nothing changes: none of the counts above depends on the chunk's length S
+    // (step j of a chunk waits for W(s0+j); A(c+1) follows W(s0+D) in program order, so it is younger for 1 <= j <= D
+    // whatever S is, and from the chunk end on it has landed).  What does depend on S is the chunk end: the groups younger
+    // than A(c+1) are the S-1 weight groups of steps 1..S-1 plus those of the res steps (the res phase's own loads have all
+    // been awaited inside it, and operations retire in order), `after` in all, of which at most D can still be outstanding:
+    //   vmcnt(min(after, D) * PPW)     for EVERY after in 0..D -- S = 4 gives after = 3, which with a five- or six-slot
+    // ring (D = 4, 5) is neither >= D nor 1: the former ladder (>= D, == 1, else 0) would have drained the ring there.
     constexpr int D = RING - 1;
+    constexpr bool PAIR = conv16_pair_walk(TAPS, CB);
+    static_assert(D <= 5, "the chunk-end wait has one arm per after = 1 .. 4 below D (MIDD_RING_MAX 6)");
+    constexpr auto cmin = [](int x, int y) { return x < y ? x : y; };
     const int ntile0 = ntile_wg + wn * NT;
     TS_DECL
     issue_a(0);
@@ -316,13 +336,69 @@ __global__ MIDD_CONV16_BOUNDS void MIDD_CONV16_KERNEL(const ConvArgs a) {
     }
 
     TS(TS_PROLOGUE)
+    // 16-channel chunks pair two taps per step: lanes kq >= 2 read the tap AFTER the one lanes kq < 2 read, which is 32 bytes
+    // further in the halo row (frag_next) or, from a row's last tap to the next row's first, (IW - 2) * 32 (frag_wrap).  With
+    // these two per-lane bases every fragment address of every walk is base + an immediate offset (one base per step and row
+    // held in a register cost 10 registers per 16-pixel row once the pair walk had 15 distinct steps).
+    // (formed here, behind the prologue: four registers fewer across the GroupNorm set-up)
+    int frag_next[MT], frag_wrap[MT];
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt) {
+        frag_next[mt] = frag_base[mt] + (kq >> 1) * 32;
+        frag_wrap[mt] = frag_base[mt] + (kq >> 1) * ((IW - KS + 1) * 32);
+    }
     int rd_slot = 0;
     half8 xh[MT], xl[MT];
-    auto load_x = [&](const int (&xo)[MT]) {
+    auto load_x = [&](const int (&xo)[MT], int off) {       // off: a constant once the step loops are unrolled
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt) {
-            xh[mt] = *reinterpret_cast<const half8*>(img + xo[mt]);
-            if constexpr (PL == 2) xl[mt] = *reinterpret_cast<const half8*>(img + xo[mt] + PLANE);
+            xh[mt] = *reinterpret_cast<const half8*>(img + xo[mt] + off);
+            if constexpr (PL == 2) xl[mt] = *reinterpret_cast<const half8*>(img + xo[mt] + off + PLANE);
+        }
+    };
+    // lower lanes tap t0, upper lanes tap t0 + 1 (or, `single`, every lane tap t0: the upper half meets zero weights or is not used)
+    auto tap_off = [](int t) { return ((t / KS) * IW + (t % KS)) * 32; };
+    // Pair walk: the fragment registers carry a value from one chunk to the next only from the even to the odd chunk of a pair.
+    // Everywhere else they are dead at a chunk's end, which the compiler cannot see (the odd chunk's masked load reads them):
+    // an empty statement that "defines" them ends their live range there -- no instruction, and no 4*PL*MT registers held
+    // through the epilogue.
+    auto kill_x = [&]() {
+        if constexpr (PAIR) {
+#pragma unroll
+            for (int mt = 0; mt < MT; ++mt) {
+                asm volatile("" : "=v"(xh[mt]));
+                if constexpr (PL == 2) asm volatile("" : "=v"(xl[mt]));
+            }
+        }
+    };
+    // The tap-8 fragments an even chunk leaves for the next chunk's first step.  Only lanes kq < 2 of them are used, so with
+    // MT == 2 both 16-pixel rows share ONE register set across the transform: lanes kq >= 2 read row 1's fragment for lanes
+    // kq - 2 (same address pattern: a fragment offset depends on kq & 1 only), and v_permlane32_swap moves that half down
+    // into xh[1] / xl[1] right before the masked load of the new image.  4 * PL registers held across the transform, not 4 * PL * MT.
+    auto load_stash = [&]() {
+        constexpr int T8 = (((TAPS - 1) / KS) * IW + (TAPS - 1) % KS) * 32;
+        if constexpr (MT == 2) {
+            const int so = (kq >> 1) ? frag_base[1] : frag_base[0];
+            xh[0] = *reinterpret_cast<const half8*>(img + so + T8);
+            if constexpr (PL == 2) xl[0] = *reinterpret_cast<const half8*>(img + so + T8 + PLANE);
+        } else {
+            load_x(frag_base, T8);
+        }
+    };
+    auto unpack_stash = [&]() {
+        if constexpr (MT == 2) {
+            typedef unsigned u32x4_ __attribute__((ext_vector_type(4)));
+            auto unpack = [](half8& lo, half8& hi) {       // hi[lanes 0..31] <- lo[lanes 32..63]; lo keeps its lanes 0..31
+                u32x4_ a = __builtin_bit_cast(u32x4_, lo), b = __builtin_bit_cast(u32x4_, hi);
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const auto sw = __builtin_amdgcn_permlane32_swap(a[r], b[r], false, false);
+                    a[r] = sw[0]; b[r] = sw[1];
+                }
+                lo = __builtin_bit_cast(half8, a); hi = __builtin_bit_cast(half8, b);
+            };
+            unpack(xh[0], xh[1]);
+            if constexpr (PL == 2) unpack(xl[0], xl[1]);
         }
     };
     auto mfma_step = [&]() {
@@ -366,8 +442,16 @@ __global__ MIDD_CONV16_BOUNDS void MIDD_CONV16_KERNEL(const ConvArgs a) {
     // boundary), not on the step's barrier: they are requested first, so their LDS latency overlaps the wait.
     // `first` = first step of a chunk: its barrier is also the one that publishes the freshly transformed
     // image, so the fragments are read after it (WM == 1 has a dedicated barrier after the transform).
-    auto k_step = [&](auto with_a, bool first, bool first_with_more, int next_chunk, const int (&xo)[MT]) {
+    // `merge` (pair walk, first step of an odd chunk): lanes kq < 2 keep the tap-8 fragments of the previous image that the
+    // even chunk left in xh / xl; only lanes kq >= 2 read the new image (a divergent load: the LDS instruction count, which
+    // the lgkmcnt below counts on, is the same).
+    auto k_step = [&](auto with_a, auto merge, bool first, bool first_with_more, int next_chunk, const int (&xo)[MT], int xoff) {
         constexpr bool WITH_A = decltype(with_a)::value;
+        constexpr bool MERGE = decltype(merge)::value;
+        auto load_frag = [&]() {
+            if constexpr (MERGE) { unpack_stash(); if (kq >= 2) load_x(xo, xoff); }
+            else load_x(xo, xoff);
+        };
 #ifdef MIDD_DMA_CHECK_BREAK                // the checker's own test: a wait that is one weight step too permissive must be reported
         constexpr int N = D * PPW + (WITH_A ? APW : 0);
 #else
@@ -383,7 +467,7 @@ __global__ MIDD_CONV16_BOUNDS void MIDD_CONV16_KERNEL(const ConvArgs a) {
             // refill could land first -- rare wrong tiles, other ones every run, on the MI355X.  (The two-plane kernel is
             // compiled from the same text; its schedule is left as it is: its ISA is pinned against the parent's.)
             if constexpr (PL == 1) __builtin_amdgcn_sched_barrier(0);
-            load_x(xo);
+            load_frag();
             // LDS operations retire in order: "at most PL*MT outstanding" = everything older than the
             // fragment reads just issued (the previous step's weight reads) is done
             asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(%1)" ::"n"(N), "n"(PL * MT) : "memory");
@@ -398,7 +482,7 @@ __global__ MIDD_CONV16_BOUNDS void MIDD_CONV16_KERNEL(const ConvArgs a) {
 #ifdef MIDD_CONV_TIMING
         if (ts_after_epi) { TS(TS_FIRSTWAIT) ts_after_epi = false; } else { TS(TS_WAIT) }
 #endif
-        if (!early) load_x(xo);
+        if (!early) load_frag();
         issue_w();
         if (first_with_more) issue_a(next_chunk);  // each thread already consumed its own raw slots
         TS(TS_ISSUE)
@@ -534,6 +618,7 @@ __global__ MIDD_CONV16_BOUNDS void MIDD_CONV16_KERNEL(const ConvArgs a) {
                         if (r + i < res_steps) res_mfma(std::false_type{}, rxh[i], rxl[i]);
                 }
             }
+            kill_x();
         }
     };
 
@@ -659,40 +744,65 @@ __global__ MIDD_CONV16_BOUNDS void MIDD_CONV16_KERNEL(const ConvArgs a) {
             // the staging geometry switches to the next tile right before its first chunk is requested
             // (every transform of the current tile is done by then; the epilogue does not use it)
             if (!more_in_tile && has_next_tile) set_tile(next_tile);
-            auto run_chunk = [&](auto more_t) {
+            // pair walk: 0 = a chunk of its own (5 steps), 1 = the even chunk of a pair (4 steps + the tap-8 stash), 2 = the odd one
+            const int walk = !PAIR ? 0 : (c & 1) ? 2 : more_in_tile ? 1 : 0;
+            auto run_chunk = [&](auto more_t, auto walk_t) {
                 constexpr bool MORE = decltype(more_t)::value;
+                constexpr int WALK = decltype(walk_t)::value;
+                if constexpr (WALK != 0) {
+#pragma unroll
+                    for (int j = 0; j < (WALK == 1 ? HSTEPS - 1 : HSTEPS); ++j) {
+                        // even: taps (2j | 2j+1) of this block; odd: (8 of the previous block, in registers | 0), then (2j-1 | 2j)
+                        const int t0 = (WALK == 1) ? 2 * j : 2 * j - 1;
+                        if (j == 0 && WALK == 2)         k_step(std::false_type{}, std::true_type{}, true, MORE, next_chunk, frag_base, tap_off(0));
+                        else if (MORE && j >= 1 && j <= D) k_step(std::true_type{}, std::false_type{}, false, false, next_chunk, t0 % KS == KS - 1 ? frag_wrap : frag_next, tap_off(t0));
+                        else                             k_step(std::false_type{}, std::false_type{}, j == 0, MORE && j == 0, next_chunk, t0 % KS == KS - 1 ? frag_wrap : frag_next, tap_off(t0));
+                    }
+                    if constexpr (WALK == 1) {            // tap 8 of this image, for the next chunk's first step (all lanes read; kq < 2 keep it)
+                        load_stash();
+                    }
+                    if constexpr (WALK == 2) kill_x();
+                    return;
+                }
                 if (full) {
 #pragma unroll
                     for (int tap = 0; tap < TAPS; ++tap) {
                         const int dy = tap / KS, dx = tap - dy * KS;
-                        int xo[MT];
-#pragma unroll
-                        for (int mt = 0; mt < MT; ++mt) xo[mt] = frag_full[mt] + (dy * IW + dx) * 32;
-                        if (MORE && tap >= 1 && tap <= D) k_step(std::true_type{}, false, false, next_chunk, xo);
-                        else                              k_step(std::false_type{}, tap == 0, MORE && tap == 0, next_chunk, xo);
+                        const int xoff = (dy * IW + dx) * 32;
+                        if (MORE && tap >= 1 && tap <= D) k_step(std::true_type{}, std::false_type{}, false, false, next_chunk, frag_full, xoff);
+                        else                              k_step(std::false_type{}, std::false_type{}, tap == 0, MORE && tap == 0, next_chunk, frag_full, xoff);
                     }
                 } else {
 #pragma unroll
                     for (int hs = 0; hs < HSTEPS; ++hs) {
-                        const int t0 = 2 * hs, t1 = (2 * hs + 1 < TAPS) ? 2 * hs + 1 : 0;   // padded half has zero weights
-                        const int o0 = ((t0 / KS) * IW + (t0 % KS)) * 32, o1 = ((t1 / KS) * IW + (t1 % KS)) * 32;
-                        const int to = (kq >> 1) ? o1 : o0;
-                        int xo[MT];
-#pragma unroll
-                        for (int mt = 0; mt < MT; ++mt) xo[mt] = frag_base[mt] + to;
-                        if (MORE && hs >= 1 && hs <= D) k_step(std::true_type{}, false, false, next_chunk, xo);
-                        else                            k_step(std::false_type{}, hs == 0, MORE && hs == 0, next_chunk, xo);
+                        // taps (2 hs | 2 hs + 1); the padded half of the last step has zero weights: every lane reads the last tap
+                        const int t0 = 2 * hs;
+                        const int (&xb)[MT] = (t0 + 1 >= TAPS) ? frag_base : (t0 % KS == KS - 1) ? frag_wrap : frag_next;
+                        if (MORE && hs >= 1 && hs <= D) k_step(std::true_type{}, std::false_type{}, false, false, next_chunk, xb, tap_off(t0));
+                        else                            k_step(std::false_type{}, std::false_type{}, hs == 0, MORE && hs == 0, next_chunk, xb, tap_off(t0));
                     }
                 }
+                kill_x();
             };
             if (more) {
-                run_chunk(std::true_type{});
+                if constexpr (PAIR) {
+                    if (walk == 1)      run_chunk(std::true_type{}, std::integral_constant<int, 1>{});
+                    else if (walk == 2) run_chunk(std::true_type{}, std::integral_constant<int, 2>{});
+                    else                run_chunk(std::true_type{}, std::integral_constant<int, 0>{});
+                } else {
+                    run_chunk(std::true_type{}, std::integral_constant<int, 0>{});
+                }
                 if (!more_in_tile) { res_phase(); TS(TS_RES) }         // the tile's 3x3 steps are done: the folded res_conv's steps
                 // every wave is done reading the image, and A(next) (older than the last min(steps after it, D)
                 // weight groups) has landed, before the image is rewritten
-                const int after = (full ? TAPS : HSTEPS) - 1 + (more_in_tile ? 0 : res_steps);
+                // vmcnt(min(after, D) * PPW), derived at the head of the K loop; an `after` that cannot occur below D costs nothing
+                const int after = (full ? TAPS : walk == 1 ? HSTEPS - 1 : HSTEPS) - 1 + (more_in_tile ? 0 : res_steps);
+                // (one arm per value below D; tests/test_pair_walk_cpu.py reads these arms and replays them)
                 if (after >= D) wait_vm_and_barrier<D * PPW>();
-                else if (after == 1) wait_vm_and_barrier<PPW>();
+                else if (after == 4) wait_vm_and_barrier<cmin(4, D) * PPW>();
+                else if (after == 3) wait_vm_and_barrier<cmin(3, D) * PPW>();
+                else if (after == 2) wait_vm_and_barrier<cmin(2, D) * PPW>();
+                else if (after == 1) wait_vm_and_barrier<cmin(1, D) * PPW>();
                 else wait_vm_and_barrier<0>();
                 TS(TS_CHUNK_WAIT)
                 if (!more_in_tile) {                    // tile finished: store it, move to the next one
@@ -714,7 +824,12 @@ __global__ MIDD_CONV16_BOUNDS void MIDD_CONV16_KERNEL(const ConvArgs a) {
                     asm volatile("" ::: "memory");
                 }
             } else {
-                run_chunk(std::false_type{});
+                if constexpr (PAIR) {               // (the even chunk of a pair is never a tile's last)
+                    if (walk == 2) run_chunk(std::false_type{}, std::integral_constant<int, 2>{});
+                    else           run_chunk(std::false_type{}, std::integral_constant<int, 0>{});
+                } else {
+                    run_chunk(std::false_type{}, std::integral_constant<int, 0>{});
+                }
                 res_phase();
                 TS(TS_RES)
             }

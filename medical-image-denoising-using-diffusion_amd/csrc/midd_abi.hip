@@ -163,6 +163,12 @@ extern "C" int mi_debug_conv16_geometry_planes(int ks, int stride, int tw, int m
     *ring = li.ring; *ppw = li.ppw; *apw = li.apw; *lds_bytes = li.lds_bytes;
     return MI_OK;
 }
+extern "C" int mi_debug_conv16_steps(int Cin, int ks, int cb) {
+    if (Cin < 16 || Cin % 16) return fail(MI_EINVAL, "Cin %d: a positive multiple of 16", Cin);
+    if (ks != 1 && ks != 3) return fail(MI_EINVAL, "ks %d: 1 or 3", ks);
+    if (cb < 0 || cb > 2 || (ks == 1 && cb == 1)) return fail(MI_EINVAL, "cb %d: 0 (default), 1 (3x3) or 2", cb);
+    return conv16_num_steps(Cin, ks * ks, cb);
+}
 extern "C" int mi_debug_plan_dump(mi_plan* plan, int B, int H, int W, int side_by_side, char* buf, size_t cap) {
     if (!plan) return fail(MI_EINVAL, "null plan");
     std::string text;

@@ -127,8 +127,10 @@ struct ConvLaunchInfo { int grid_x, grid_y, wgs_per_img, tiles_x, tiles_y, ring,
 bool conv16_launch_info(int Cin, int Cout, int B, int OH, int OW, const ConvTile& t, int persist_wgs, ConvLaunchInfo* out);
 bool conv1x1_launch_info(int Cin, int Cout, int B, int OH, int OW, const ConvTile& t, int persist_wgs, int att_mode, ConvLaunchInfo* out);
 // 16-channel blocks staged per K chunk of the f16x3 kernel (shared with the host packer).
-//   3x3: 1 -> 16 channels per chunk, two taps per MFMA step (10 % padded MFMA slots, but half the
-//             activation LDS of a 32-channel chunk, i.e. three resident workgroups per CU)
+//   3x3: 1 -> 16 channels per chunk, two taps per MFMA step, half the activation LDS of a 32-channel chunk, i.e. three
+//             resident workgroups per CU.  Nine taps leave one half step over per block: blocks are walked in PAIRS
+//             (c even, c + 1) of 4 + 5 steps, the first step of block c + 1 carrying tap 8 of block c in its lower half
+//             (conv16_pair_walk); only an unpaired last block (Cin = 48, 144) keeps a zero-weight half step
 //   1x1: 2 -> 32 channels per chunk and step (no halo, so the image is small; halves the number of
 //             chunk hand-overs, which dominate a 1x1)
 //   3x3, "wide" (cb = 2, picked per launch where the grid leaves at most ~2 workgroups per CU anyway: the 32x32 / 64x64 maps
@@ -136,10 +138,14 @@ bool conv1x1_launch_info(int Cin, int Cout, int B, int OH, int OW, const ConvTil
 //             half step) and half the chunk hand-overs; weights packed in that K order as a second copy (pack_conv_f16x3)
 __host__ __device__ constexpr int conv16_cb(int ks) { return ks == 1 ? 2 : 1; }
 // number of 32-wide K steps the f16x3 kernel walks for (Cin, taps) with cb blocks per chunk (0: the default of the kernel size)
+// (the ONE place that says how many steps a K order has: the kernel, the weight packer and the mi_debug_conv16_steps hook
+// ask here; the planner and the plan dump do not count K steps.  cb == 1 exists for the 3x3 only.)
+__host__ __device__ constexpr bool conv16_pair_walk(int taps, int cb) { return cb == 1 && taps == 9; }
 __host__ __device__ inline int conv16_num_steps(int Cin, int taps, int cb = 0) {
     const int nblk = Cin / 16;
     if (cb == 0) cb = conv16_cb(taps == 1 ? 1 : 3);
-    if (cb == 1) return nblk * ((taps + 1) / 2);
+    // wide chunks: a pair of blocks is `taps` full steps; pair walk: a pair of blocks is 4 + 5 steps.  Either way an
+    // unpaired last block takes (taps + 1) / 2 steps, the last one half empty
     const int full = nblk / 2, half = nblk & 1;
     return full * taps + half * ((taps + 1) / 2);
 }

@@ -144,6 +144,7 @@ static std::vector<float> pack_conv_f32(const float* w, int Cout, int Cin, int K
 // taps per step.  lane = kq*16 + n; element j is W[16*tile+n][cin][tap] with
 //   full chunk : cin = 16*(2c + (kq>>1)) + 8*(kq&1) + j, tap = step's tap
 //   half chunk : cin = 16*(2c) + 8*(kq&1) + j,           tap = 2*hs + (kq>>1)  (zero when >= taps)
+//   16-channel chunks of a 3x3 (cb == 1): the pair walk of conv16_pair_walk (midd_internal.h), spelled out below
 // w' = w * 2^k (k per layer, max|w'| in [2^13,2^14)); hi = fp16(w'), lo = fp16(w' - hi).
 // *out_scale = 2^-k / ACT_PRESCALE.  Returned as raw 32-bit words (two fp16 each).
 static const float SILU_WEIGHT_FACTOR_H = -0.6931471805599453f;     // == SILU_WEIGHT_FACTOR (f16x3_common.h): see conv_mfma_f16x3.hip, transform
@@ -190,7 +191,19 @@ static std::vector<float> pack_conv_f16x3(const float* w_in, int Cout, int Cin, 
             }
         ++step;
     };
-    if (cb == 1) {
+    if (conv16_pair_walk(taps, cb)) {
+        // pair walk: block c (even) in 4 steps, taps (0|1) (2|3) (4|5) (6|7); block c + 1 in 5: (tap 8 of block c | tap 0),
+        // (1|2) (3|4) (5|6) (7|8).  An unpaired last block: 5 steps, the last one's upper half zero.
+        for (int blk = 0; blk < nblk; blk += 2) {
+            if (blk + 1 < nblk) {
+                for (int hs = 0; hs < taps / 2; ++hs) emit(blk, blk, 2 * hs, 2 * hs + 1);
+                emit(blk, blk + 1, taps - 1, 0);
+                for (int hs = 0; hs < taps / 2; ++hs) emit(blk + 1, blk + 1, 2 * hs + 1, 2 * hs + 2);
+            } else {
+                for (int hs = 0; hs < (taps + 1) / 2; ++hs) emit(blk, blk, 2 * hs, 2 * hs + 1);
+            }
+        }
+    } else if (cb == 1) {
         for (int blk = 0; blk < nblk; ++blk)
             for (int hs = 0; hs < (taps + 1) / 2; ++hs) emit(blk, blk, 2 * hs, 2 * hs + 1);
     } else {
