@@ -251,6 +251,33 @@ size_t mi_ensemble_workspace_bytes(mi_plan* plan, int B, int members, int H, int
  * samples, mean_out and std_out must not overlap (the kernel reads the samples while it writes the other two). */
 int mi_ensemble_reduce(const float* samples, int B, int members, int64_t chw, float* mean_out, float* std_out, void* stream);
 
+/* QUANTILE MAPS over the members of an ensemble (no plan needed): samples device fp32 [B,members,chw] -> out [B,nq,chw], per pixel
+ * the nq quantiles q[0 .. nq-1] (host doubles in [0, 1]) of its members.  Every member of this network is clamped to [0, 1], so
+ * the per-pixel distribution is skewed and piles up at the clamp: a median and an interval (0.05 .. 0.95) describe it where
+ * mean +- std does not.  THE ARITHMETIC (fixed, per pixel, independent of the launch geometry, the vector width and the alignment
+ * path), over the member values x_0 .. x_{K-1}, K = members:
+ *   NaN          if any x_m is NaN, every quantile of the pixel is the canonical quiet NaN 0x7FC00000 (numpy's rule: nothing is
+ *                silently dropped)
+ *   sort         else ascending in the total order of the unsigned key  k = bits ^ (sign ? 0xFFFFFFFF : 0x80000000):
+ *                -inf < ... < -0.0 < +0.0 < ... < +inf; ties carry identical bits, so the sorted s_0 .. s_{K-1} is unique
+ *   interpolate  per level q, in double precision, every operation rounded to nearest on its own, no fused multiply-add:
+ *                  pos = q * (double)(K-1);  lo = (int)floor(pos);  hi = min(lo+1, K-1);  g = pos - (double)lo
+ *                  out = (float)( (double)s_lo + g * ((double)s_hi - (double)s_lo) )
+ *                K == 1: every quantile is x_0, bit for bit.  A NaN the formula itself makes of infinite members (inf - inf,
+ *                0 * inf) is stored as 0x7FC00000 too.
+ * So, for finite members, q = 0 is the minimum and q = 1 the maximum, a q whose pos is an integer returns a member's value (equal in
+ * value, not always in bits: g = 0 turns a -0.0 into +0.0 when K > 1), and the levels of a pixel are non-decreasing in q.  An
+ * infinite member at or next to the position makes 0 * inf or inf - inf, i.e. NaN: q = 0 over a pixel with a -inf member is NaN.
+ * None of this arises for outputs clamped to [0, 1].  This is numpy.quantile(x.astype(float64), q) ("linear") up to its different rounding of the
+ * interpolation: within 1 fp32 ulp of it for members in [0, 1) (tests/test_quantiles_cpu.py).
+ * The kernel sorts a pixel's members in registers: members <= 64 (mean and std have no such limit).  The levels travel as kernel
+ * arguments: 1 <= nq <= 8; the call allocates nothing and is asynchronous.
+ * MI_EINVAL before any GPU work, the rule named in mi_last_error: B outside [1, 65535], members < 1, chw outside [1, 2^32),
+ * members > 64, nq outside [1, 8], null q / samples / out, a q[i] that is NaN or outside [0, 1].
+ * samples and out must not overlap. */
+int mi_ensemble_quantiles(const float* samples, int B, int members, int64_t chw,
+                          const double* q, int nq, float* out, void* stream);
+
 /* TILED DENOISING: images of any size >= the tile, at their own resolution, as overlapping network-sized tiles (the reference
  * resizes every image to the training size first, Backend/run.py denoise_image_diffusion(..., img_size); nothing there tiles).
  * THE GEOMETRY (fixed), per axis with image length L, tile T, minimum overlap O, T <= L, 0 <= O <= T/2:
@@ -361,6 +388,20 @@ size_t mi_tiled_ensemble_workspace_bytes(mi_plan* plan, int B, int members, int 
  * B * members * tiles > 2^31 - 1.  tiles and the three outputs must not overlap. */
 int mi_tile_blend_reduce(const float* tiles, int B, int members, int C, int H, int W, int th, int tw, int oy, int ox,
                          float* mean_out, float* std_out, float* samples_out, void* stream);
+
+/* The quantile maps of an ensemble of tiled runs (no plan needed): tiles device fp32 [members][B][ny*nx][C][th][tw], as
+ * mi_denoise_tiled_ensemble's tiles_out holds them, -> out [B][nq][C][H][W].  One kernel; a thread owns one output element of one
+ * image with the addressing of mi_tile_blend_reduce.  THE ARITHMETIC (fixed, per pixel, no atomics, no fused multiply-add) is the
+ * composition of two specifications above, bit for bit:
+ *   for m = 0 .. members-1:  v_m = the pixel of mi_tile_blend over tiles[m][b]  (a float: (float)(num / den)), formed once
+ *   out = the arithmetic of mi_ensemble_quantiles over v_0 .. v_{members-1}
+ * so the output equals mi_tile_blend of every member followed by mi_ensemble_quantiles, and the blended members never exist in
+ * memory.
+ * MI_EINVAL: the cases of mi_tile_blend_reduce for the arguments the two share (geometry rules, C*H*W >= 2^32, B outside
+ * [1, 65535], B * tiles and B * members * tiles > 2^31 - 1, overlap > 46339, members < 1) and of mi_ensemble_quantiles
+ * (members > 64, nq outside [1, 8], null q / tiles / out, a level that is NaN or outside [0, 1]).  tiles and out must not overlap. */
+int mi_tile_blend_quantiles(const float* tiles, int B, int members, int C, int H, int W, int th, int tw, int oy, int ox,
+                            const double* q, int nq, float* out, void* stream);
 
 /* Status of the last mi_unet_forward / mi_denoise call that used `workspace` (its first word; the calls clear it when they
  * start).  SYNCHRONISES `stream` (one 4-byte device-to-host copy).  Returns MI_OK with *flags == 0, or MI_ERANGE with the

@@ -5,7 +5,8 @@
 img_size -> sampler -> uint8 -> bicubic resize back -> PNG, with the reference's timing print.
 
     python -m midd_amd.cli --image in.png --out out.png [--checkpoint ckpt.pth] [--variant cddpm|ddim]
-                           [--img-size 512] [--inference-steps 25] [--seed N] [--samples K [--std-out std.npy]]
+                           [--img-size 512] [--inference-steps 25] [--seed N] [--samples K [--std-out std.npy]
+                           [--quantiles 0.05,0.5,0.95 --quantiles-out q.npy]]
                            [--tile N [--overlap O]]
 
 Without a checkpoint (the trained weights are not distributed with the reference) the network is
@@ -17,27 +18,31 @@ from __future__ import annotations
 
 import argparse
 import time
-from typing import Optional
+from typing import Optional, Sequence
 
 import numpy as np
 import torch
 from PIL import Image
 
 from .modules import UNetDiffusion
-from .sampler import DiffusionDenoiser
+from .sampler import MAX_QUANTILE_MEMBERS, DiffusionDenoiser, check_levels
 
 
 def denoise_image_diffusion(model_path: Optional[str], test_image_path: str, device_type: str = "cuda",
                             img_size: int = 512, inference_steps: int = 50, variant: str = "cddpm",
                             step_noise: Optional[torch.Tensor] = None, compute: Optional[str] = None,
                             seed: Optional[int] = None, samples: Optional[int] = None,
-                            std_out: Optional[str] = None, tile: Optional[int] = None, overlap: int = 32) -> Image.Image:
+                            std_out: Optional[str] = None, tile: Optional[int] = None, overlap: int = 32,
+                            quantiles: Optional[Sequence[float]] = None, quantiles_out: Optional[str] = None) -> Image.Image:
     """compute (not a reference argument): arithmetic of the network, see UNetDiffusion -- None keeps the default.
     seed (not a reference argument; cddpm): the stochastic sampler's noise is drawn on the device from this seed, so the same
     call gives the same image again (DiffusionDenoiser.denoise); None: torch.randn, as the reference.
     samples (not a reference argument; cddpm): the returned image is the MEAN of this many seeded draws
     (DiffusionDenoiser.denoise_ensemble; seed None: a seed is drawn and printed) through the same recipe; std_out: path of a
     .npy file that receives their per-pixel standard deviation, float32 [img_size, img_size] (needs samples >= 2).
+    quantiles, quantiles_out (not reference arguments; cddpm, with samples <= 64): the per-pixel quantile maps of the draws at these
+    levels (numbers in [0, 1], at most 8) are written to the .npy file quantiles_out, float32 [len(quantiles), img_size, img_size];
+    the two come together.
     tile (not a reference argument): the image is denoised at its OWN size as blended overlapping tile x tile crops with at least
     `overlap` shared pixels (DiffusionDenoiser.denoise_tiled) -- no resize to img_size and back; both sides must be >= tile."""
     if tile is not None and (samples is not None or step_noise is not None):
@@ -46,6 +51,12 @@ def denoise_image_diffusion(model_path: Optional[str], test_image_path: str, dev
         raise ValueError("--samples needs the stochastic (cddpm) variant: a deterministic sampler has no ensemble")
     if std_out is not None and (samples is None or samples < 2):
         raise ValueError("--std-out needs --samples K with K >= 2")
+    if (quantiles is None) != (quantiles_out is None):
+        raise ValueError("--quantiles and --quantiles-out come together")
+    if quantiles is not None:
+        if samples is None or samples > MAX_QUANTILE_MEMBERS:
+            raise ValueError(f"--quantiles needs --samples K with K <= {MAX_QUANTILE_MEMBERS}")
+        quantiles = check_levels(quantiles)
     if samples is not None and step_noise is not None:
         raise ValueError("samples draws its noise from the seed: step_noise cannot be given as well")
     device = torch.device(device_type)
@@ -86,11 +97,13 @@ def denoise_image_diffusion(model_path: Optional[str], test_image_path: str, dev
     if seed is not None:
         kw["seed"] = seed
     if samples is not None:
-        ens = diffusion.denoise_ensemble(input_tensor, inference_steps=inference_steps, members=samples, seed=seed)
+        ens = diffusion.denoise_ensemble(input_tensor, inference_steps=inference_steps, members=samples, seed=seed, quantiles=quantiles)
         denoised = ens.mean                               # a mean of values in [0, 1]: in [0, 1]
         print(f"Ensemble of {samples} samples, seed {ens.seed}")
         if std_out is not None:
             np.save(std_out, ens.std.reshape(img_size, img_size).cpu().numpy())
+        if quantiles is not None:
+            np.save(quantiles_out, ens.quantiles.reshape(len(quantiles), img_size, img_size).cpu().numpy())
     else:
         denoised = diffusion.denoise(input_tensor, inference_steps=inference_steps, **kw)
     if device.type == "cuda":
@@ -120,6 +133,10 @@ def main(argv=None) -> None:
                     help="cddpm: save the mean of this many seeded samples of the image (with --seed: reproducible)")
     ap.add_argument("--std-out", default=None, metavar="PATH.npy",
                     help="with --samples K >= 2: write the per-pixel standard deviation of the samples (float32, model resolution)")
+    ap.add_argument("--quantiles", default=None, metavar="Q,Q,...",
+                    help="with --samples K <= 64 and --quantiles-out: per-pixel quantile maps of the samples at these levels in [0, 1] (at most 8)")
+    ap.add_argument("--quantiles-out", default=None, metavar="PATH.npy",
+                    help="with --quantiles: write the quantile maps (float32 [levels, H, W], model resolution)")
     ap.add_argument("--tile", type=int, default=None, metavar="N",
                     help="denoise the image at its own size as blended overlapping N x N tiles (N: a multiple of 8) instead of resizing it to --img-size")
     ap.add_argument("--overlap", type=int, default=32, help="with --tile: minimum overlap of neighbouring tiles (<= N / 2)")
@@ -130,9 +147,20 @@ def main(argv=None) -> None:
         ap.error("--samples needs K >= 1 and --variant cddpm")
     if args.std_out is not None and (args.samples is None or args.samples < 2):
         ap.error("--std-out needs --samples K with K >= 2")
+    levels = None
+    if (args.quantiles is None) != (args.quantiles_out is None):
+        ap.error("--quantiles and --quantiles-out come together")
+    if args.quantiles is not None:
+        if args.samples is None or args.samples > MAX_QUANTILE_MEMBERS:
+            ap.error(f"--quantiles needs --samples K with K <= {MAX_QUANTILE_MEMBERS}")
+        try:
+            levels = check_levels([float(v) for v in args.quantiles.split(",")])
+        except ValueError as exc:
+            ap.error(f"--quantiles needs up to 8 comma-separated levels in [0, 1]: {exc}")
     restored = denoise_image_diffusion(args.checkpoint, args.image, device_type=args.device, img_size=args.img_size,
                                        inference_steps=args.inference_steps, variant=args.variant, seed=args.seed,
-                                       samples=args.samples, std_out=args.std_out, tile=args.tile, overlap=args.overlap)
+                                       samples=args.samples, std_out=args.std_out, tile=args.tile, overlap=args.overlap,
+                                       quantiles=levels, quantiles_out=args.quantiles_out)
     restored.save(args.out, quality=95)
     print(f"\nResult saved: {args.out}")
 

@@ -522,6 +522,39 @@ extern "C" int mi_ensemble_reduce(const float* samples, int B, int members, int6
     return launched(ensemble_reduce_launch(samples, B, members, (unsigned long long)chw, mean_out, std_out, (hipStream_t)stream), "ensemble_reduce");
 }
 
+// the members of a pixel are sorted in registers (pointwise.hip: ensemble_quantiles_kernel): at most QUANTILE_MAX_MEMBERS of them
+static int check_quantile_members(int members) {
+    if (members > QUANTILE_MAX_MEMBERS)
+        return fail(MI_EINVAL, "members %d: the quantile kernels sort a pixel's members in registers (limit: members <= %d; mean and std have no such limit)",
+                    members, QUANTILE_MAX_MEMBERS);
+    return MI_OK;
+}
+
+// the levels of a quantile call, host doubles -> the kernel argument
+static int check_quantile_levels(const double* q, int nq, QuantileLevels* ql) {
+    if (nq < 1 || nq > QUANTILE_MAX_LEVELS)
+        return fail(MI_EINVAL, "nq %d outside [1, %d]: the levels travel as kernel arguments (limit: 1 <= nq <= %d)", nq, QUANTILE_MAX_LEVELS, QUANTILE_MAX_LEVELS);
+    if (!q) return fail(MI_EINVAL, "null argument");
+    *ql = QuantileLevels{};
+    ql->nq = nq;
+    for (int i = 0; i < nq; ++i) {
+        if (!(q[i] >= 0.0 && q[i] <= 1.0)) return fail(MI_EINVAL, "q[%d] = %.17g outside [0, 1] (limit: 0 <= q <= 1, not NaN)", i, q[i]);
+        ql->q[i] = q[i];
+    }
+    return MI_OK;
+}
+
+extern "C" int mi_ensemble_quantiles(const float* samples, int B, int members, int64_t chw, const double* q, int nq, float* out, void* stream) {
+    if (int rc = check_members_min(members)) return rc;
+    if (int rc = check_reduce_batch(B)) return rc;
+    if (chw < 1 || chw >= MEMBER_WORDS) return fail(MI_EINVAL, "chw %lld outside [1, 2^32) (limit: C*H*W < 4294967296)", (long long)chw);
+    if (int rc = check_quantile_members(members)) return rc;
+    QuantileLevels ql;
+    if (int rc = check_quantile_levels(q, nq, &ql)) return rc;
+    if (!samples || !out) return fail(MI_EINVAL, "null argument");
+    return launched(ensemble_quantiles_launch(samples, B, members, (unsigned long long)chw, ql, out, (hipStream_t)stream), "ensemble_quantiles");
+}
+
 // ---------------------------------------------------------------------------- the batched calls: virtual samples in passes
 // mi_denoise_ensemble, mi_denoise_tiled and mi_denoise_tiled_ensemble run `rounds` x V virtual samples of h x w each through the
 // sampler loop in passes of L.pass.  Each judges its own argument rules and its table of buffers (check_no_overlap), then shares
@@ -727,6 +760,23 @@ extern "C" int mi_tile_blend_reduce(const float* tiles, int B, int members, int 
     if (int rc = check_std_members(std_out, members)) return rc;
     if (!tiles || !mean_out) return fail(MI_EINVAL, "null argument");
     return launched(tile_blend_reduce_launch(tiles, B, members, g, mean_out, std_out, samples_out, (hipStream_t)stream), "tile_blend_reduce");
+}
+
+extern "C" int mi_tile_blend_quantiles(const float* tiles, int B, int members, int C, int H, int W, int th, int tw, int oy, int ox,
+                                       const double* q, int nq, float* out, void* stream) {
+    TileGeom g{};
+    if (C < 1) return fail(MI_EINVAL, "C %d must be positive", C);
+    if (int rc = fill_tile_geom(C, H, W, th, tw, oy, ox, &g)) return rc;
+    if (int rc = check_tile_count(B, g)) return rc;
+    if (int rc = check_step_noise_range(C, H, W, 0)) return rc;
+    if (int rc = check_members_min(members)) return rc;
+    if (int rc = check_reduce_batch(B, "the limit of mi_ensemble_quantiles, whose arithmetic this call composes")) return rc;      // (B >= 1: check_tile_count)
+    if (int rc = check_tiled_ensemble_size(B, members, g)) return rc;
+    if (int rc = check_quantile_members(members)) return rc;
+    QuantileLevels ql;
+    if (int rc = check_quantile_levels(q, nq, &ql)) return rc;
+    if (!tiles || !out) return fail(MI_EINVAL, "null argument");
+    return launched(tile_blend_quantiles_launch(tiles, B, members, g, ql, out, (hipStream_t)stream), "tile_blend_quantiles");
 }
 
 // Members are the outer loop: member m is mi_denoise_tiled's seeded pass structure with counter word c3 = member_offset + m, a

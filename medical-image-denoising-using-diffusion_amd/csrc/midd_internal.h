@@ -253,6 +253,16 @@ hipError_t tile_blend_launch(const float* tiles, float* out, int B, const TileGe
 // member, then of ensemble_reduce_launch over the members.  B * M * ny*nx <= 2^31 - 1
 hipError_t tile_blend_reduce_launch(const float* tiles, int B, int M, const TileGeom& g, float* mean, float* std, float* samples, hipStream_t s);
 
+// Per-pixel quantile maps over the members (quantile_common.h; include/midd.h: mi_ensemble_quantiles).  The levels travel as kernel
+// arguments; the members of a pixel are sorted in registers, hence the member limit.
+constexpr int QUANTILE_MAX_MEMBERS = 64, QUANTILE_MAX_LEVELS = 8;
+struct QuantileLevels { double q[QUANTILE_MAX_LEVELS]; int nq; };
+// samples [B][K][chw] -> out [B][nq][chw].  B <= 65535, 1 <= K <= 64, 1 <= nq <= 8, every level in [0, 1]
+hipError_t ensemble_quantiles_launch(const float* samples, int B, int K, unsigned long long chw, const QuantileLevels& ql, float* out, hipStream_t s);
+// tiles [M][B][ny*nx][C][th][tw] -> out [B][nq][C][H][W]: the quantiles of the M blended members (the arithmetic of tile_blend_launch
+// per member, then of ensemble_quantiles_launch).  The limits of tile_blend_reduce_launch and of the call above
+hipError_t tile_blend_quantiles_launch(const float* tiles, int B, int M, const TileGeom& g, const QuantileLevels& ql, float* out, hipStream_t s);
+
 // bilinear resize of an activation tensor, either layout (align_corners=False), any size ratio
 hipError_t resize_bilinear_launch(const float* src, float* dst, stat_word* tot, int rep, int bs, int B, int H, int W, int C, int OH, int OW, int blocked, hipStream_t s);
 // ConvTranspose2d(C,C,4,stride=2,padding=1) direct (only used by topologies where it cannot be folded)

@@ -12,6 +12,7 @@
 //   ensemble_broadcast_kernel : the condition image of an ensemble pass's virtual samples
 //   tile_extract_kernel / tile_blend_kernel : overlapping network-sized tiles of a larger image, and their blend (mi_denoise_tiled)
 //   tile_blend_reduce_kernel : blend of every member's tiles and mean / std over the blended members (mi_denoise_tiled_ensemble)
+//   ensemble_quantiles_kernel / tile_blend_quantiles_kernel : per-pixel quantiles over the members, plain and blended from tiles
 //   resize_bilinear  : F.interpolate(mode='bilinear', align_corners=False) (DDIMModel.py:242)
 //   conv_transpose   : ConvTranspose2d(C,C,4,2,1) (DDIMModel.py:211) for topologies where the
 //                      planner cannot fold it into a 3x3 (never on the default networks)
@@ -20,6 +21,7 @@
 #include "midd_internal.h"
 #include "step_noise_common.h"
 #include "tile_geometry.h"
+#include "quantile_common.h"
 
 namespace midd {
 
@@ -681,6 +683,184 @@ hipError_t tile_blend_reduce_launch(const float* tiles, int B, int M, const Tile
     if (BK > 2147483647ll || BK * M > 2147483647ll) return hipErrorInvalidValue;
     hipLaunchKernelGGL(tile_blend_reduce_kernel, dim3((unsigned)((chw + 255) / 256), B < 65535 ? B : 65535), dim3(256), 0, s,
                        tiles, mean, stdv, samples, B, M, g);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------ quantile maps over the members
+// samples [B][K][chw] -> out [B][nq][chw]: per pixel the nq quantiles of its K members.  THE ARITHMETIC IS FIXED (include/midd.h:
+// mi_ensemble_quantiles) and per pixel, so neither V, the alignment path nor the grid shows in the result: the members are sorted
+// by their order keys (quantile_common.h), then per level, in double, every operation rounded on its own,
+//   pos = q * (K - 1);  lo = floor(pos);  hi = min(lo + 1, K - 1);  g = pos - lo;  out = (float)(s_lo + g * (s_hi - s_lo))
+// A thread owns V neighbouring pixels as ensemble_reduce_kernel does (V = 4: 16-byte loads and stores), loads its K members ONCE,
+// keeps the KP >= K keys (K padded to a power of two with keys above +inf) in registers and sorts them with the unrolled network:
+// every register index is a compile-time constant.  lo and hi are the same for every pixel (they depend on q and K alone), but
+// they are run-time values: s_lo and s_hi are picked by a chain of selects, not by indexing the array, so nothing goes to scratch
+// (tests/test_quantiles_cpu.py holds every instantiation to a private segment of 0 bytes).  The levels are kernel arguments.
+// A pixel with a NaN member, and a NaN that the interpolation itself makes of infinite members, is the canonical quiet NaN.
+struct QuantilePos { int lo, hi; double g; };
+
+__device__ __forceinline__ QuantilePos quantile_pos(double q, int K) {
+    const double pos = mul_rn64(q, (double)(K - 1));
+    QuantilePos p;
+    p.lo = (int)floor(pos);
+    p.hi = min(p.lo + 1, K - 1);
+    p.g = sub_rn64(pos, (double)p.lo);
+    return p;
+}
+
+template <int KP>
+__device__ __forceinline__ float quantile_of_sorted(const uint32_t (&key)[KP], const QuantilePos& p, int K, bool has_nan) {
+    const float s_lo = __uint_as_float(order_bits(pick_key(key, p.lo)));
+    const float s_hi = __uint_as_float(order_bits(pick_key(key, p.hi)));
+    const float r = __double2float_rn(add_rn64((double)s_lo, mul_rn64(p.g, sub_rn64((double)s_hi, (double)s_lo))));
+    const float v = (K == 1) ? s_lo : r;                    // one member: every quantile is that member, bit for bit
+    return (has_nan || v != v) ? __uint_as_float(0x7FC00000u) : v;
+}
+
+__device__ __forceinline__ bool is_nan_bits(uint32_t bits) { return (bits & 0x7FFFFFFFu) > 0x7F800000u; }
+
+template <int KP, int V>
+__global__ __launch_bounds__(256)
+void ensemble_quantiles_kernel(const float* __restrict__ samples, int K, unsigned long long chw, QuantileLevels ql, float* __restrict__ out) {
+    const unsigned long long e = ((unsigned long long)blockIdx.x * 256 + threadIdx.x) * V;
+    if (e >= chw) return;                                   // (V == 4: chw % 4 == 0, so e + 3 < chw)
+    const size_t b = blockIdx.y;
+    const float* src = samples + b * (size_t)K * chw + e;
+    uint32_t key[V][KP];
+    bool has_nan[V];
+#pragma unroll
+    for (int j = 0; j < V; ++j) has_nan[j] = false;
+#pragma unroll
+    for (int m = 0; m < KP; ++m) {
+        if (m < K) {
+            uint32_t x[V];
+            if constexpr (V == 4) {
+                const f32x4 v = *reinterpret_cast<const f32x4*>(src + (size_t)m * chw);
+                x[0] = __float_as_uint(v.x); x[1] = __float_as_uint(v.y); x[2] = __float_as_uint(v.z); x[3] = __float_as_uint(v.w);
+            } else {
+                x[0] = __float_as_uint(src[(size_t)m * chw]);
+            }
+#pragma unroll
+            for (int j = 0; j < V; ++j) { key[j][m] = order_key(x[j]); has_nan[j] = has_nan[j] || is_nan_bits(x[j]); }
+        } else {
+#pragma unroll
+            for (int j = 0; j < V; ++j) key[j][m] = ORDER_KEY_PAD;
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < V; ++j) sort_keys<KP>(key[j]);
+    float* dst = out + b * (size_t)ql.nq * chw + e;
+    for (int i = 0; i < ql.nq; ++i) {
+        const QuantilePos p = quantile_pos(ql.q[i], K);
+        float r[V];
+#pragma unroll
+        for (int j = 0; j < V; ++j) r[j] = quantile_of_sorted<KP>(key[j], p, K, has_nan[j]);
+        if constexpr (V == 4) *reinterpret_cast<f32x4*>(dst + (size_t)i * chw) = (f32x4){r[0], r[1], r[2], r[3]};
+        else dst[(size_t)i * chw] = r[0];
+    }
+}
+
+static bool quantile_levels_ok(const QuantileLevels& ql) {
+    if (ql.nq < 1 || ql.nq > QUANTILE_MAX_LEVELS) return false;
+    for (int i = 0; i < ql.nq; ++i)
+        if (!(ql.q[i] >= 0.0 && ql.q[i] <= 1.0)) return false;
+    return true;
+}
+
+template <int KP>
+static void ensemble_quantiles_dispatch(const float* samples, int B, int K, unsigned long long chw, const QuantileLevels& ql, float* out, hipStream_t s) {
+    if (chw % 4 == 0 && aligned16(samples) && aligned16(out))
+        hipLaunchKernelGGL((ensemble_quantiles_kernel<KP, 4>), dim3((unsigned)((chw / 4 + 255) / 256), B), dim3(256), 0, s, samples, K, chw, ql, out);
+    else
+        hipLaunchKernelGGL((ensemble_quantiles_kernel<KP, 1>), dim3((unsigned)((chw + 255) / 256), B), dim3(256), 0, s, samples, K, chw, ql, out);
+}
+
+hipError_t ensemble_quantiles_launch(const float* samples, int B, int K, unsigned long long chw, const QuantileLevels& ql, float* out, hipStream_t s) {
+    if (B < 1 || B > 65535 || K < 1 || K > QUANTILE_MAX_MEMBERS || chw < 1 || chw >= (1ull << 32) || !samples || !out || !quantile_levels_ok(ql))
+        return hipErrorInvalidValue;
+    if (K <= 2) ensemble_quantiles_dispatch<2>(samples, B, K, chw, ql, out, s);
+    else if (K <= 4) ensemble_quantiles_dispatch<4>(samples, B, K, chw, ql, out, s);
+    else if (K <= 8) ensemble_quantiles_dispatch<8>(samples, B, K, chw, ql, out, s);
+    else if (K <= 16) ensemble_quantiles_dispatch<16>(samples, B, K, chw, ql, out, s);
+    else if (K <= 32) ensemble_quantiles_dispatch<32>(samples, B, K, chw, ql, out, s);
+    else ensemble_quantiles_dispatch<64>(samples, B, K, chw, ql, out, s);
+    return hipGetLastError();
+}
+
+// Blend and quantiles in one pass over the image (mi_tile_blend_quantiles): tiles [M][B][ny*nx][C][th][tw] -> out [B][nq][C][H][W],
+// the quantiles over the members' BLENDED images, which never exist in memory.  A thread owns ONE output element of one image
+// with the addressing of tile_blend_reduce_kernel.  THE ARITHMETIC IS FIXED: v_m = (float)(num_m / den) exactly as
+// tile_blend_kernel forms it -- the covering tiles in ascending (ky, kx), num_m += (double)(wy * wx) * (double)v -- for every member
+// once, then the sort and the interpolation of ensemble_quantiles_kernel over v_0 .. v_{M-1}: the output equals mi_tile_blend of
+// every member followed by mi_ensemble_quantiles, bit for bit.  The tile walk is the outer loop and the members the unrolled inner
+// one: the windows are formed once per tile, a tile's M loads are in flight together, and every member still sees its own
+// additions in the same order (den is the same sum for every member).  KP doubles and KP keys per thread, all at constant indices.
+// grid (chunks of 256 elements of a [C][H][W] block, images -- folded over grid.y when B > 65535)
+template <int KP>
+__global__ __launch_bounds__(256)
+void tile_blend_quantiles_kernel(const float* __restrict__ tiles, float* __restrict__ out, int B, int M, TileGeom g, QuantileLevels ql) {
+    const unsigned long long e = (unsigned long long)blockIdx.x * 256 + threadIdx.x;
+    const unsigned long long chw = (unsigned long long)g.C * g.H * g.W;
+    if (e >= chw) return;
+    const int x = (int)(e % (unsigned)g.W);
+    const unsigned long long cy = e / (unsigned)g.W;
+    const int y = (int)(cy % (unsigned)g.H), c = (int)(cy / (unsigned)g.H);
+    int ky0, ky1, kx0, kx1;
+    tile_cover(y, g.H, g.th, g.ny, &ky0, &ky1);
+    tile_cover(x, g.W, g.tw, g.nx, &kx0, &kx1);
+    const size_t tile_plane = (size_t)g.th * g.tw, K = (size_t)g.ny * g.nx;
+    const size_t member_stride = (size_t)B * K * g.C * tile_plane;             // tile block m * B + b: m * member_stride further on
+    for (size_t b = blockIdx.y; b < (size_t)B; b += gridDim.y) {
+        double num[KP], den = 0.0;
+#pragma unroll
+        for (int m = 0; m < KP; ++m) num[m] = 0.0;
+        for (int ky = ky0; ky <= ky1; ++ky) {
+            const int ry = y - tile_origin(ky, g.H, g.th, g.ny);
+            const int wy = tile_window(ry, g.th, g.oy);
+            for (int kx = kx0; kx <= kx1; ++kx) {
+                const int rx = x - tile_origin(kx, g.W, g.tw, g.nx);
+                const double w = (double)(wy * tile_window(rx, g.tw, g.ox));
+                const float* src = tiles + ((b * K + (size_t)ky * g.nx + kx) * g.C + c) * tile_plane + (size_t)ry * g.tw + rx;
+#pragma unroll
+                for (int m = 0; m < KP; ++m)
+                    if (m < M) num[m] = add_rn64(num[m], mul_rn64(w, (double)src[(size_t)m * member_stride]));
+                den = add_rn64(den, w);
+            }
+        }
+        uint32_t key[KP];
+        bool has_nan = false;
+#pragma unroll
+        for (int m = 0; m < KP; ++m) {
+            if (m < M) {
+                const uint32_t bits = __float_as_uint(__double2float_rn(__ddiv_rn(num[m], den)));
+                key[m] = order_key(bits);
+                has_nan = has_nan || is_nan_bits(bits);
+            } else {
+                key[m] = ORDER_KEY_PAD;
+            }
+        }
+        sort_keys<KP>(key);
+        float* dst = out + b * (size_t)ql.nq * chw + e;
+        for (int i = 0; i < ql.nq; ++i) dst[(size_t)i * chw] = quantile_of_sorted<KP>(key, quantile_pos(ql.q[i], M), M, has_nan);
+    }
+}
+
+hipError_t tile_blend_quantiles_launch(const float* tiles, int B, int M, const TileGeom& g, const QuantileLevels& ql, float* out, hipStream_t s) {
+    const unsigned long long chw = (unsigned long long)g.C * g.H * g.W;
+    if (B < 1 || M < 1 || M > QUANTILE_MAX_MEMBERS || g.C < 1 || g.ny < 1 || g.nx < 1 || g.th < 1 || g.tw < 1 || g.th > g.H || g.tw > g.W ||
+        chw >= (1ull << 32) || g.oy < 0 || g.ox < 0 || (long long)g.oy + 1 > 46340 || (long long)g.ox + 1 > 46340 ||      // wy * wx fits an int
+        !tiles || !out || !quantile_levels_ok(ql)) return hipErrorInvalidValue;
+    const long long BK = (long long)B * ((long long)g.ny * g.nx);            // (ny * nx <= H * W < 2^32: no overflow in either product)
+    if (BK > 2147483647ll || BK * M > 2147483647ll) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)((chw + 255) / 256), B < 65535 ? B : 65535);
+#define MIDD_TBQ(N) hipLaunchKernelGGL(tile_blend_quantiles_kernel<N>, grid, dim3(256), 0, s, tiles, out, B, M, g, ql)
+    if (M <= 2) MIDD_TBQ(2);
+    else if (M <= 4) MIDD_TBQ(4);
+    else if (M <= 8) MIDD_TBQ(8);
+    else if (M <= 16) MIDD_TBQ(16);
+    else if (M <= 32) MIDD_TBQ(32);
+    else MIDD_TBQ(64);
+#undef MIDD_TBQ
     return hipGetLastError();
 }
 

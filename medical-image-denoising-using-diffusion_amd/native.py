@@ -75,6 +75,7 @@ SYMBOLS = [
                                       C.c_void_p, C.c_size_t, C.c_void_p]),
     ("mi_ensemble_workspace_bytes", C.c_size_t, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     ("mi_ensemble_reduce", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("mi_ensemble_quantiles", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int64, C.POINTER(C.c_double), C.c_int, C.c_void_p, C.c_void_p]),
     ("mi_tile_geometry", C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int]),
     ("mi_tile_extract", C.c_int, [C.c_void_p] + [C.c_int] * 10 + [C.c_void_p, C.c_void_p]),
     ("mi_tile_blend", C.c_int, [C.c_void_p] + [C.c_int] * 8 + [C.c_void_p, C.c_void_p]),
@@ -87,6 +88,7 @@ SYMBOLS = [
                                             C.c_uint64, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
     ("mi_tiled_ensemble_workspace_bytes", C.c_size_t, [C.c_void_p] + [C.c_int] * 10),
     ("mi_tile_blend_reduce", C.c_int, [C.c_void_p] + [C.c_int] * 9 + [C.c_void_p] * 4),
+    ("mi_tile_blend_quantiles", C.c_int, [C.c_void_p] + [C.c_int] * 9 + [C.POINTER(C.c_double), C.c_int, C.c_void_p, C.c_void_p]),
     ("mi_debug_fetch", C.c_int, [C.c_void_p, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                  C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p]),
     ("mi_status", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]),

@@ -9,6 +9,7 @@ call into libmidd.so.
 from __future__ import annotations
 
 import ctypes as C
+import numbers
 import operator
 from typing import NamedTuple, Optional, Sequence, Tuple
 
@@ -60,6 +61,49 @@ class EnsembleResult(NamedTuple):
     seed: int                             # the seed of the run (drawn when the call had seed=None): pass it to repeat the run
 
 
+class EnsembleQuantileResult(NamedTuple):
+    """What ``DiffusionDenoiser.denoise_ensemble(..., quantiles=levels)`` returns: EnsembleResult's fields, then the maps."""
+    mean: torch.Tensor
+    std: Optional[torch.Tensor]
+    samples: Optional[torch.Tensor]
+    seed: int
+    quantiles: torch.Tensor               # [B, nq, C, H, W]: per-pixel quantile maps of the members, in the order of ``levels``
+    levels: Tuple[float, ...]             # the quantile levels, each in [0, 1]
+
+
+MAX_QUANTILE_MEMBERS = 64                 # include/midd.h: mi_ensemble_quantiles sorts a pixel's members in registers
+MAX_QUANTILE_LEVELS = 8
+
+
+def check_levels(q) -> Tuple[float, ...]:
+    """Argument rules of the quantile levels (include/midd.h: mi_ensemble_quantiles) -> a tuple of floats; raises ValueError
+    before any GPU work.  A single number is one level."""
+    if isinstance(q, numbers.Real) and not isinstance(q, bool):
+        q = (q,)
+    try:
+        levels = tuple(q)
+    except TypeError:
+        raise ValueError(f"quantile levels must be a sequence of numbers in [0, 1] (got {q!r})") from None
+    if not 1 <= len(levels) <= MAX_QUANTILE_LEVELS:
+        raise ValueError(f"between 1 and {MAX_QUANTILE_LEVELS} quantile levels per call (got {len(levels)})")
+    out = []
+    for v in levels:
+        if isinstance(v, bool) or not isinstance(v, numbers.Real) or not 0.0 <= float(v) <= 1.0:      # (NaN fails the comparison)
+            raise ValueError(f"every quantile level must be a number in [0, 1] (got {v!r})")
+        out.append(float(v))
+    return tuple(out)
+
+
+def check_quantile_members(members: int) -> int:
+    if members > MAX_QUANTILE_MEMBERS:
+        raise ValueError(f"quantiles need members <= {MAX_QUANTILE_MEMBERS} (got {members}): the kernel sorts a pixel's members in registers")
+    return members
+
+
+def _levels_arg(levels: Tuple[float, ...]):
+    return (C.c_double * len(levels))(*levels)
+
+
 @torch.no_grad()
 def step_noise(seed: int, n_iters: int, shape: Sequence[int], sample_offset: int = 0, device=None, member: int = 0) -> torch.Tensor:
     """The 0.5-scaled step noise a seeded cddpm run draws, as a tensor [n_iters, B, C, H, W] (mi_step_noise_fill_member).
@@ -106,6 +150,29 @@ def ensemble_reduce(samples: torch.Tensor) -> Tuple[torch.Tensor, Optional[torch
     return mean, std
 
 
+@torch.no_grad()
+def ensemble_quantiles(samples: torch.Tensor, q) -> torch.Tensor:
+    """Per-pixel quantile maps [B, nq, ...] over dim 1 of ``samples`` [B, members, ...] at the levels ``q`` (numbers in [0, 1], at
+    most 8; members <= 64) with the arithmetic of ``denoise_ensemble(..., quantiles=q)`` (mi_ensemble_quantiles: total-order sort,
+    linear interpolation in double precision; a pixel with a NaN member is NaN at every level)."""
+    levels = check_levels(q)
+    if not isinstance(samples, torch.Tensor) or samples.dim() < 3 or samples.shape[0] < 1 or samples.shape[1] < 1:
+        raise ValueError("samples must be a [B, members, ...] tensor with B >= 1 and members >= 1")
+    check_quantile_members(samples.shape[1])
+    if samples.device.type != "cuda":
+        raise RuntimeError(f"ensemble_quantiles runs only on a ROCm GPU (got {samples.device}): there is no CPU fallback")
+    if samples.dtype != torch.float32:
+        raise TypeError(f"samples must be float32 (got {samples.dtype})")
+    src = samples.contiguous()
+    B, K = src.shape[:2]
+    chw = src[0, 0].numel()
+    with torch.cuda.device(src.device):
+        out = torch.empty((B, len(levels)) + tuple(src.shape[2:]), dtype=torch.float32, device=src.device)
+        native.check(native.lib().mi_ensemble_quantiles(src.data_ptr(), B, K, chw, _levels_arg(levels), len(levels), out.data_ptr(),
+                                                        torch.cuda.current_stream(src.device).cuda_stream))
+    return out
+
+
 class TiledResult(NamedTuple):
     """What ``DiffusionDenoiser.denoise_tiled`` returns."""
     image: torch.Tensor                   # [B, C, H, W]: the blended image, at the input's own size
@@ -124,6 +191,19 @@ class TiledEnsembleResult(NamedTuple):
     origins_y: Tuple[int, ...]            # row origin of every tile row
     origins_x: Tuple[int, ...]            # column origin of every tile column
     seed: int                             # the seed of the run (drawn when the call had seed=None): pass it to repeat the run
+
+
+class TiledEnsembleQuantileResult(NamedTuple):
+    """What ``DiffusionDenoiser.denoise_tiled_ensemble(..., quantiles=levels)`` returns: TiledEnsembleResult's fields, then the maps."""
+    mean: torch.Tensor
+    std: Optional[torch.Tensor]
+    samples: Optional[torch.Tensor]
+    tiles: Optional[torch.Tensor]
+    origins_y: Tuple[int, ...]
+    origins_x: Tuple[int, ...]
+    seed: int
+    quantiles: torch.Tensor               # [B, nq, C, H, W]: per-pixel quantile maps of the members' blended images
+    levels: Tuple[float, ...]             # the quantile levels, each in [0, 1]
 
 
 class TilePlan(NamedTuple):
@@ -229,6 +309,31 @@ def tile_blend_reduce(tiles: torch.Tensor, H: int, W: int, overlap=32,
     return mean, std, samples
 
 
+@torch.no_grad()
+def tile_blend_quantiles(tiles: torch.Tensor, H: int, W: int, overlap=32, q=None) -> torch.Tensor:
+    """tiles [members, B, ny * nx, C, th, tw] of an H x W tiling -> the per-pixel quantile maps [B, nq, C, H, W] of the members'
+    blended images at the levels ``q``, in one kernel with the arithmetic of ``denoise_tiled_ensemble(..., quantiles=q)``
+    (mi_tile_blend_quantiles: ``tile_blend`` per member, then ``ensemble_quantiles`` over the members, bit for bit; the blended
+    members are never stored).  members <= 64, at most 8 levels."""
+    if q is None:
+        raise ValueError("tile_blend_quantiles needs the quantile levels: q=(0.05, 0.5, 0.95), say")
+    levels = check_levels(q)
+    if isinstance(tiles, torch.Tensor) and tiles.dim() == 6:
+        check_quantile_members(tiles.shape[0])
+    src = _tile_tensor(tiles, "tiles", 6)
+    M, B, K, Cc, th, tw = src.shape
+    plan = tile_plan(H, W, (th, tw), overlap)
+    if K != len(plan.origins_y) * len(plan.origins_x):
+        raise ValueError(f"tiles has {K} tiles per image; a {H}x{W} image with tile {th}x{tw} and overlap {plan.overlap} has "
+                         f"{len(plan.origins_y)} x {len(plan.origins_x)}")
+    with torch.cuda.device(src.device):
+        out = torch.empty((B, len(levels), Cc, int(H), int(W)), dtype=torch.float32, device=src.device)
+        native.check(native.lib().mi_tile_blend_quantiles(src.data_ptr(), B, M, Cc, int(H), int(W), th, tw, plan.overlap[0], plan.overlap[1],
+                                                          _levels_arg(levels), len(levels), out.data_ptr(),
+                                                          torch.cuda.current_stream(src.device).cuda_stream))
+    return out
+
+
 class DiffusionDenoiser:
     def __init__(self, model, noise_steps=50, beta_start=1e-4, beta_end=0.02):
         self.model = model
@@ -284,7 +389,7 @@ class DiffusionDenoiser:
     @torch.no_grad()
     def denoise_ensemble(self, noisy_img: torch.Tensor, inference_steps: int = 25, members: int = 8, seed: Optional[int] = None,
                          sample_offset: int = 0, member_offset: int = 0, max_batch: int = 16,
-                         return_samples: bool = False) -> EnsembleResult:
+                         return_samples: bool = False, quantiles=None):
         """``members`` stochastic (cddpm) draws per image in one native call: their per-pixel mean -- lower error than any
         single draw -- and unbiased standard deviation -- where the network is guessing.  Not a reference call (the reference
         returns one draw, cddpmModels.py:281-308).
@@ -295,16 +400,29 @@ class DiffusionDenoiser:
         and 12 GB at 512x512; a caller with memory to spare raises it).  ``seed=None`` draws a 64-bit seed from torch's CPU
         generator; the result carries the seed, so the run can be repeated.  ``std`` is None for one member; ``samples``
         ([B, members, C, H, W]) only with ``return_samples=True``.  A DDIM model raises ValueError: a deterministic sampler
-        has no ensemble."""
+        has no ensemble.
+
+        ``quantiles`` (a sequence of at most 8 levels in [0, 1], e.g. ``(0.05, 0.5, 0.95)``; members <= 64): the call also returns
+        the per-pixel quantile maps of the members -- a median and an interval describe outputs clamped to [0, 1] where mean and
+        std do not -- as an ``EnsembleQuantileResult``: the fields above, then ``quantiles`` [B, nq, C, H, W] and ``levels``.  The
+        members are written to a tensor of the call's own instead of the workspace (which shrinks by the same bytes) and one
+        ``ensemble_quantiles`` launch follows on the same stream; mean, std and samples are the bits of the call without it."""
+        levels = None if quantiles is None else check_levels(quantiles)
         if getattr(self.model, "variant", "ddim") != "cddpm":
             raise ValueError("denoise_ensemble needs the stochastic (cddpm) variant: a deterministic sampler has no ensemble")
         seed, _ = check_seed(self._draw_seed() if seed is None else seed, 0)      # (everything else is judged by run_ensemble, before any GPU work)
+        if levels is not None:
+            check_quantile_members(check_member(members, "members", low=1))
         self.model.eval()
         steps = timestep_list(self.noise_steps, inference_steps)
         mean, std, samples = self.model.run_ensemble(noisy_img, steps, self.beta, self.alpha, self.alpha_hat, clamp_eps=False,
                                                      members=members, seed=seed, sample_offset=sample_offset,
-                                                     member_offset=member_offset, max_batch=max_batch, want_samples=return_samples)
-        return EnsembleResult(mean, std, samples, seed)
+                                                     member_offset=member_offset, max_batch=max_batch,
+                                                     want_samples=return_samples or levels is not None)
+        if levels is None:
+            return EnsembleResult(mean, std, samples, seed)
+        maps = ensemble_quantiles(samples, levels)
+        return EnsembleQuantileResult(mean, std, samples if return_samples else None, seed, maps, levels)
 
     @torch.no_grad()
     def denoise_tiled(self, noisy_img: torch.Tensor, inference_steps: int = 25, tile=256, overlap=32, max_batch: int = 16,
@@ -340,7 +458,7 @@ class DiffusionDenoiser:
     def denoise_tiled_ensemble(self, noisy_img: torch.Tensor, inference_steps: int = 25, members: int = 8, tile=256, overlap=32,
                                max_batch: int = 16, seed: Optional[int] = None, sample_offset: int = 0, member_offset: int = 0,
                                return_samples: bool = False, return_tiles: bool = False,
-                               step_noise: None = None) -> TiledEnsembleResult:
+                               step_noise: None = None, quantiles=None):
         """``denoise_ensemble`` for images of ANY size >= the tile: ``members`` stochastic (cddpm) draws of every image as blended
         overlapping tiles in one native call, their per-pixel mean and unbiased standard deviation at the image's own resolution
         (not a reference call; include/midd.h: mi_denoise_tiled_ensemble).
@@ -354,20 +472,32 @@ class DiffusionDenoiser:
         (``samples``: [B, members, C, H, W]).  ``tiles`` ([members, B, ny * nx, C, th, tw], ``return_tiles=True``): ``tiles[m]`` is
         what ``denoise_tiled(..., return_tiles=True).tiles`` is for member m.  ``std`` is None for one member.  ``seed=None`` draws
         a 64-bit seed and returns it.  A DDIM model raises ValueError (a deterministic sampler has no ensemble); a ``step_noise``
-        tensor is not supported (anything but None raises ValueError)."""
+        tensor is not supported (anything but None raises ValueError).
+
+        ``quantiles`` (a sequence of at most 8 levels in [0, 1]; members <= 64): the call also returns the per-pixel quantile maps
+        of the members' blended images as a ``TiledEnsembleQuantileResult``: the fields above, then ``quantiles``
+        [B, nq, C, H, W] and ``levels``.  The tiles are written to a tensor of the call's own instead of the workspace (which
+        shrinks by the same bytes) and one ``tile_blend_quantiles`` launch follows on the same stream: the blended members are
+        still never stored.  The other fields are the bits of the call without it."""
+        levels = None if quantiles is None else check_levels(quantiles)
         if step_noise is not None:
             raise ValueError("denoise_tiled_ensemble does not take a step_noise tensor: its noise is the seeded generator's, indexed by "
                              "image position and member (pass seed; midd_amd.step_noise(seed, n, x.shape, member=m) exports the same values)")
         if getattr(self.model, "variant", "ddim") != "cddpm":
             raise ValueError("denoise_tiled_ensemble needs the stochastic (cddpm) variant: a deterministic sampler has no ensemble")
         seed, _ = check_seed(self._draw_seed() if seed is None else seed, 0)      # (everything else is judged by run_tiled_ensemble, before any GPU work)
+        if levels is not None:
+            check_quantile_members(check_member(members, "members", low=1))
         self.model.eval()
         steps = timestep_list(self.noise_steps, inference_steps)
         mean, std, samples, tiles, plan = self.model.run_tiled_ensemble(
             noisy_img, steps, self.beta, self.alpha, self.alpha_hat, clamp_eps=False, tile=tile, overlap=overlap, members=members,
             seed=seed, sample_offset=sample_offset, member_offset=member_offset, max_batch=max_batch,
-            want_samples=return_samples, want_tiles=return_tiles)
-        return TiledEnsembleResult(mean, std, samples, tiles, plan.origins_y, plan.origins_x, seed)
+            want_samples=return_samples, want_tiles=return_tiles or levels is not None)
+        if levels is None:
+            return TiledEnsembleResult(mean, std, samples, tiles, plan.origins_y, plan.origins_x, seed)
+        maps = tile_blend_quantiles(tiles, noisy_img.shape[2], noisy_img.shape[3], plan.overlap, levels)
+        return TiledEnsembleQuantileResult(mean, std, samples, tiles if return_tiles else None, plan.origins_y, plan.origins_x, seed, maps, levels)
 
     def _draw_seed(self) -> int:
         hi, lo = torch.randint(0, 1 << 32, (2,), dtype=torch.int64).tolist()
