@@ -403,6 +403,79 @@ int mi_tile_blend_reduce(const float* tiles, int B, int members, int C, int H, i
 int mi_tile_blend_quantiles(const float* tiles, int B, int members, int C, int H, int W, int th, int tw, int oy, int ox,
                             const double* q, int nq, float* out, void* stream);
 
+/* GEOMETRIC SELF-ENSEMBLE ("x8 test-time augmentation"): the network runs on flipped and rotated copies of every image, every
+ * output is turned back, and the per-pixel mean and spread over the views are returned -- for BOTH variants: it is the ensemble
+ * of a deterministic (DDIM) sampler, whose std map shows where the output depends on the orientation.  (Not a reference call:
+ * the reference denoises the image as given, DDIMModel.py:268-289.)
+ * THE GEOMETRY (fixed).  A view code is g in 0..7, g = 4*t + 2*fy + fx; it acts on the last two axes of a [C,H,W] image, the same
+ * way on every channel:
+ *   view(x, g):    u = x with H and W swapped (u[i][j] = x[j][i]) if t, else x;
+ *                  if fy: reverse the rows of u;  if fx: reverse the columns of u
+ *   unview(y, g):  if fx: reverse the columns;  if fy: reverse the rows;  if t: swap the axes       (unview(view(x, g), g) == x)
+ * Codes 0..3 are the identity, the left-right mirror, the up-down mirror and the half turn: they keep the shape and work for any
+ * H, W the network takes.  Codes 4..7 are the transpose, the two quarter turns (5: clockwise, numpy.rot90(x, -1); 6: counter-
+ * clockwise, numpy.rot90(x, 1)) and the anti-transpose: they turn H x W into W x H and are accepted ONLY when H == W, because a
+ * pass never mixes image sizes.  A view list is 1 to 8 DISTINCT codes in the caller's order; the order is the order of the
+ * members (samples_out, and the order of the sums of the mean).
+ *
+ * mi_dihedral_views (no plan needed): dst device fp32 [n][C][Hv][Wv] <- view(images[v / n_views], views[v % n_views]) for the
+ *   virtual samples v = v0 .. v0 + n - 1 of images [B][C][H][W] (image-major, v = b * n_views + k, as mi_denoise_ensemble numbers
+ *   them): the fill of a pass on its own.  Bit copies.  n == 0: MI_OK.
+ * mi_dihedral_reduce (no plan needed): views_out device fp32 [B][n_views][C][Hv][Wv], every view's output in ITS frame, ->
+ *   mean_out [B][C][H][W], std_out (or NULL; n_views >= 2) and samples_out [B][n_views][C][H][W] (or NULL), the ALIGNED members
+ *   x_k = unview(views_out[b][k], views[k]).  THE ARITHMETIC (fixed, per pixel) is mi_ensemble_reduce's over x_0 .. x_{n_views-1}
+ *   in list order: the result equals unview per view followed by mi_ensemble_reduce, bit for bit, with or without samples_out.
+ *   The aligned members are never stored unless samples_out is given.  At least one output; views_out and the outputs must not overlap.
+ * mi_dihedral_quantiles (no plan needed): the same gather, then THE ARITHMETIC of mi_ensemble_quantiles over the aligned members:
+ *   out [B][nq][C][H][W] equals mi_ensemble_quantiles of them, bit for bit.
+ * MI_EINVAL of the three, before any GPU work, in this order: C < 1; a bad shape or C*H*W >= 2^32; n_views outside [1, 8]; null
+ *   views; a code outside [0, 7]; a repeated code; a transposing code with H != W; B outside [1, 65535]; then per call -- views:
+ *   v0 < 0, n < 0, n > 65535 or v0 + n > B * n_views; reduce: no output pointer, std_out with one view; quantiles: the level rules of
+ *   mi_ensemble_quantiles -- and last a null data pointer. */
+int mi_dihedral_views(const float* images, int B, int C, int H, int W, const int32_t* views, int n_views,
+                      int v0, int n, float* dst, void* stream);
+int mi_dihedral_reduce(const float* views_out, int B, int C, int H, int W, const int32_t* views, int n_views,
+                       float* mean_out, float* std_out, float* samples_out, void* stream);
+int mi_dihedral_quantiles(const float* views_out, int B, int C, int H, int W, const int32_t* views, int n_views,
+                          const double* q, int nq, float* out, void* stream);
+
+/* mi_denoise_ensemble with the views of an image in the place of its draws.  The B * n_views virtual samples (v = b * n_views + k:
+ * view k of image b) run through mi_denoise's sampler loop in passes of at most pass_samples consecutive virtual samples -- the
+ * fill of a pass is mi_dihedral_views, each pass is split over two streams as a mi_denoise batch of that size is -- and ONE
+ * mi_dihedral_reduce launch follows the last pass.
+ *   noisy        device fp32 [B,C,H,W]; never written
+ *   mean_out     device fp32 [B,C,H,W] or NULL
+ *   std_out      device fp32 [B,C,H,W] or NULL; needs n_views >= 2
+ *   samples_out  device fp32 [B,n_views,C,H,W] or NULL: the ALIGNED members, unview of every view's output
+ *   views        HOST int32[n_views]
+ *   seeded       0: no noise term -- the DDIM variant, or cddpm's noise-free use; nothing is drawn.  != 0: view k of image b draws
+ *                the step noise of (seed, sample_offset + b, member word member_offset + k) with the counter word c0 the pixel's
+ *                index IN THE VIEW'S FRAME: view k is mi_denoise_seeded -- as member member_offset + k, mi_denoise_ensemble's
+ *                single-member form -- of the turned image view(noisy[b], views[k]), bit for bit with a batch-invariant plan
+ *   pass_samples, flags, t_list .. noise_steps   as mi_denoise_ensemble
+ * The view-frame outputs ALWAYS live in the workspace (unview of a transposing view cannot run in place), so the workspace does
+ * not shrink when samples_out is given.  They are its LAST B * n_views * C*H*W * 4 bytes, counted from the size
+ * mi_self_ensemble_workspace_bytes answers, laid out [B][n_views][C][Hv][Wv]: after the call a caller may hand that address to
+ * mi_dihedral_quantiles (or mi_dihedral_reduce) on the same stream.
+ * MI_EINVAL before any GPU work, the rule named in mi_last_error, in this order: null plan; n_views outside [1, 8]; null views; a
+ * code outside [0, 7]; a repeated code; a transposing code with H != W; member_offset < 0; member_offset + n_views > 2^32;
+ * pass_samples < 1; B outside [1, 65535] or B * n_views > 2^31 - 1; sample_offset < 0; C*H*W >= 2^32; no output pointer; std_out
+ * with one view; any two of noisy, mean_out, std_out, samples_out overlapping.  (sample_offset and member_offset are judged when
+ * seeded == 0 too.)  Then, as every batched call: the plan's state, the workspace, null noisy, the schedule, the device.
+ * The status word (mi_status) is cleared once per call and accumulates over the passes.  Allocates nothing; asynchronous. */
+int mi_denoise_self_ensemble(mi_plan* plan, const float* noisy, float* mean_out, float* std_out, float* samples_out,
+                             int B, int H, int W, const int32_t* views, int n_views,
+                             const int32_t* t_list, int n_iters,
+                             const float* beta, const float* alpha, const float* alpha_hat, int noise_steps,
+                             int seeded, uint64_t seed, int64_t sample_offset, int64_t member_offset, int pass_samples, int flags,
+                             void* workspace, size_t workspace_bytes, void* stream);
+
+/* Bytes of workspace mi_denoise_self_ensemble needs: mi_ensemble_workspace_bytes(plan, B, n_views, H, W, pass_samples, 0) -- the
+ * sampler workspace of a pass + the pass's condition views + the view outputs, B * n_views * C*H*W * 4 bytes.  samples_external is
+ * accepted for symmetry with the other queries and IGNORED: the view outputs stay in the workspace whether or not samples_out is
+ * given.  Host only, answered from the planner alone: it works before mi_unet_finalize too.  0 on bad arguments (mi_last_error). */
+size_t mi_self_ensemble_workspace_bytes(mi_plan* plan, int B, int n_views, int H, int W, int pass_samples, int samples_external);
+
 /* Status of the last mi_unet_forward / mi_denoise call that used `workspace` (its first word; the calls clear it when they
  * start).  SYNCHRONISES `stream` (one 4-byte device-to-host copy).  Returns MI_OK with *flags == 0, or MI_ERANGE with the
  * MI_STATUS_* bits in *flags: the kernels never turn a NaN / Inf activation or an operand beyond the split-fp16 range into

@@ -8,6 +8,7 @@ img_size -> sampler -> uint8 -> bicubic resize back -> PNG, with the reference's
                            [--img-size 512] [--inference-steps 25] [--seed N] [--samples K [--std-out std.npy]
                            [--quantiles 0.05,0.5,0.95 --quantiles-out q.npy]]
                            [--tile N [--overlap O]]
+                           [--self-ensemble [auto|flips|d4] [--std-out std.npy] [--quantiles Q,Q --quantiles-out q.npy]]
 
 Without a checkpoint (the trained weights are not distributed with the reference) the network is
 random-init, which exercises the path but does not denoise.  The reference helper has a latent
@@ -33,7 +34,8 @@ def denoise_image_diffusion(model_path: Optional[str], test_image_path: str, dev
                             step_noise: Optional[torch.Tensor] = None, compute: Optional[str] = None,
                             seed: Optional[int] = None, samples: Optional[int] = None,
                             std_out: Optional[str] = None, tile: Optional[int] = None, overlap: int = 32,
-                            quantiles: Optional[Sequence[float]] = None, quantiles_out: Optional[str] = None) -> Image.Image:
+                            quantiles: Optional[Sequence[float]] = None, quantiles_out: Optional[str] = None,
+                            self_ensemble: Optional[str] = None) -> Image.Image:
     """compute (not a reference argument): arithmetic of the network, see UNetDiffusion -- None keeps the default.
     seed (not a reference argument; cddpm): the stochastic sampler's noise is drawn on the device from this seed, so the same
     call gives the same image again (DiffusionDenoiser.denoise); None: torch.randn, as the reference.
@@ -44,17 +46,29 @@ def denoise_image_diffusion(model_path: Optional[str], test_image_path: str, dev
     levels (numbers in [0, 1], at most 8) are written to the .npy file quantiles_out, float32 [len(quantiles), img_size, img_size];
     the two come together.
     tile (not a reference argument): the image is denoised at its OWN size as blended overlapping tile x tile crops with at least
-    `overlap` shared pixels (DiffusionDenoiser.denoise_tiled) -- no resize to img_size and back; both sides must be >= tile."""
+    `overlap` shared pixels (DiffusionDenoiser.denoise_tiled) -- no resize to img_size and back; both sides must be >= tile.
+    self_ensemble (not a reference argument; both variants): "auto", "flips" or "d4" -- the returned image is the MEAN over the
+    flipped and rotated views of the image (DiffusionDenoiser.denoise_self_ensemble); std_out, quantiles and quantiles_out then
+    describe the views instead of seeded draws.  Not together with samples or tile."""
+    if self_ensemble is not None:
+        if samples is not None:
+            raise ValueError("--self-ensemble cannot be combined with --samples")
+        if tile is not None:
+            raise ValueError("--self-ensemble cannot be combined with --tile")
+        if step_noise is not None:
+            raise ValueError("--self-ensemble draws its noise from the seed: step_noise cannot be given as well")
+        if self_ensemble not in ("auto", "flips", "d4"):
+            raise ValueError(f"--self-ensemble takes auto, flips or d4 (got {self_ensemble!r})")
     if tile is not None and (samples is not None or step_noise is not None):
         raise ValueError("--tile cannot be combined with --samples or a step_noise tensor")
     if samples is not None and variant != "cddpm":
         raise ValueError("--samples needs the stochastic (cddpm) variant: a deterministic sampler has no ensemble")
-    if std_out is not None and (samples is None or samples < 2):
+    if std_out is not None and self_ensemble is None and (samples is None or samples < 2):
         raise ValueError("--std-out needs --samples K with K >= 2")
     if (quantiles is None) != (quantiles_out is None):
         raise ValueError("--quantiles and --quantiles-out come together")
     if quantiles is not None:
-        if samples is None or samples > MAX_QUANTILE_MEMBERS:
+        if self_ensemble is None and (samples is None or samples > MAX_QUANTILE_MEMBERS):
             raise ValueError(f"--quantiles needs --samples K with K <= {MAX_QUANTILE_MEMBERS}")
         quantiles = check_levels(quantiles)
     if samples is not None and step_noise is not None:
@@ -96,7 +110,16 @@ def denoise_image_diffusion(model_path: Optional[str], test_image_path: str, dev
     kw = {"step_noise": step_noise} if step_noise is not None else {}
     if seed is not None:
         kw["seed"] = seed
-    if samples is not None:
+    if self_ensemble is not None:
+        ens = diffusion.denoise_self_ensemble(input_tensor, inference_steps=inference_steps, views=self_ensemble,
+                                              seed=seed if variant == "cddpm" else None, quantiles=quantiles)
+        denoised = ens.mean                               # a mean of values in [0, 1]: in [0, 1]
+        print(f"Self-ensemble of {len(ens.views)} views {ens.views}" + (f", seed {ens.seed}" if ens.seed is not None else ""))
+        if std_out is not None:
+            np.save(std_out, ens.std.reshape(img_size, img_size).cpu().numpy())
+        if quantiles is not None:
+            np.save(quantiles_out, ens.quantiles.reshape(len(quantiles), img_size, img_size).cpu().numpy())
+    elif samples is not None:
         ens = diffusion.denoise_ensemble(input_tensor, inference_steps=inference_steps, members=samples, seed=seed, quantiles=quantiles)
         denoised = ens.mean                               # a mean of values in [0, 1]: in [0, 1]
         print(f"Ensemble of {samples} samples, seed {ens.seed}")
@@ -140,18 +163,25 @@ def main(argv=None) -> None:
     ap.add_argument("--tile", type=int, default=None, metavar="N",
                     help="denoise the image at its own size as blended overlapping N x N tiles (N: a multiple of 8) instead of resizing it to --img-size")
     ap.add_argument("--overlap", type=int, default=32, help="with --tile: minimum overlap of neighbouring tiles (<= N / 2)")
+    ap.add_argument("--self-ensemble", nargs="?", const="auto", default=None, choices=["auto", "flips", "d4"],
+                    help="both variants: save the mean over the flipped and rotated views of the image (auto: all 8); --std-out and "
+                         "--quantiles / --quantiles-out then describe the views")
     args = ap.parse_args(argv)
+    if args.self_ensemble is not None and args.samples is not None:
+        ap.error("--self-ensemble cannot be combined with --samples")
+    if args.self_ensemble is not None and args.tile is not None:
+        ap.error("--self-ensemble cannot be combined with --tile")
     if args.tile is not None and (args.tile < 1 or args.samples is not None):
         ap.error("--tile needs N >= 1 and cannot be combined with --samples")
     if args.samples is not None and (args.samples < 1 or args.variant != "cddpm"):
         ap.error("--samples needs K >= 1 and --variant cddpm")
-    if args.std_out is not None and (args.samples is None or args.samples < 2):
+    if args.std_out is not None and args.self_ensemble is None and (args.samples is None or args.samples < 2):
         ap.error("--std-out needs --samples K with K >= 2")
     levels = None
     if (args.quantiles is None) != (args.quantiles_out is None):
         ap.error("--quantiles and --quantiles-out come together")
     if args.quantiles is not None:
-        if args.samples is None or args.samples > MAX_QUANTILE_MEMBERS:
+        if args.self_ensemble is None and (args.samples is None or args.samples > MAX_QUANTILE_MEMBERS):
             ap.error(f"--quantiles needs --samples K with K <= {MAX_QUANTILE_MEMBERS}")
         try:
             levels = check_levels([float(v) for v in args.quantiles.split(",")])
@@ -160,7 +190,7 @@ def main(argv=None) -> None:
     restored = denoise_image_diffusion(args.checkpoint, args.image, device_type=args.device, img_size=args.img_size,
                                        inference_steps=args.inference_steps, variant=args.variant, seed=args.seed,
                                        samples=args.samples, std_out=args.std_out, tile=args.tile, overlap=args.overlap,
-                                       quantiles=levels, quantiles_out=args.quantiles_out)
+                                       quantiles=levels, quantiles_out=args.quantiles_out, self_ensemble=args.self_ensemble)
     restored.save(args.out, quality=95)
     print(f"\nResult saved: {args.out}")
 

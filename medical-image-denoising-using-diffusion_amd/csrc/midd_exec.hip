@@ -819,6 +819,110 @@ extern "C" int mi_denoise_tiled_ensemble(mi_plan* plan, const float* noisy, floa
     return MI_OK;
 }
 
+// ---------------------------------------------------------------------------- geometric self-ensemble: flip / rotate views
+// the view list of a call, host int32 -> the kernel argument (include/midd.h: THE GEOMETRY)
+static int check_views(const int32_t* views, int n_views, int H, int W, DihedralViews* dv) {
+    if (n_views < 1 || n_views > DIHEDRAL_MAX_VIEWS)
+        return fail(MI_EINVAL, "n_views %d outside [1, %d]: a view list holds 1 to 8 distinct view codes (limit: 1 <= n_views <= %d)", n_views,
+                    DIHEDRAL_MAX_VIEWS, DIHEDRAL_MAX_VIEWS);
+    if (!views) return fail(MI_EINVAL, "null argument: views");
+    *dv = DihedralViews{};
+    dv->n = n_views;
+    for (int k = 0; k < n_views; ++k) {
+        if (views[k] < 0 || views[k] > 7)
+            return fail(MI_EINVAL, "views[%d] = %d outside [0, 7]: a view code is 4 * transpose + 2 * flip_rows + flip_columns (limit: 0 <= code <= 7)", k, views[k]);
+        for (int j = 0; j < k; ++j)
+            if (views[j] == views[k]) return fail(MI_EINVAL, "views[%d] = %d repeats views[%d]: the view codes of a list are distinct", k, views[k], j);
+        dv->code[k] = (uint8_t)views[k];
+    }
+    for (int k = 0; k < n_views; ++k)
+        if ((views[k] & 4) && H != W)
+            return fail(MI_EINVAL, "views[%d] = %d transposes a %dx%d image: a pass never mixes image sizes (limit: view codes 4 .. 7 need H == W)", k, views[k], H, W);
+    return MI_OK;
+}
+
+static int check_std_views(const float* std_out, int n_views) {
+    if (std_out && n_views < 2) return fail(MI_EINVAL, "std_out needs at least two views: the unbiased standard deviation of one value is undefined");
+    return MI_OK;
+}
+
+// what the three stand-alone calls share: the image shape, the view list, the batch
+static int check_dihedral_call(int B, int C, int H, int W, const int32_t* views, int n_views, DihedralViews* dv) {
+    if (C < 1) return fail(MI_EINVAL, "C %d must be positive", C);
+    if (int rc = check_step_noise_range(C, H, W, 0)) return rc;
+    if (int rc = check_views(views, n_views, H, W, dv)) return rc;
+    return check_ensemble_size(B, n_views);
+}
+
+extern "C" int mi_dihedral_views(const float* images, int B, int C, int H, int W, const int32_t* views, int n_views,
+                                 int v0, int n, float* dst, void* stream) {
+    DihedralViews dv;
+    if (int rc = check_dihedral_call(B, C, H, W, views, n_views, &dv)) return rc;
+    if (v0 < 0 || n < 0 || n > 65535 || (int64_t)v0 + n > (int64_t)B * n_views)
+        return fail(MI_EINVAL, "views [%d, %d + %d) outside the %d * %d virtual samples of the batch (limit per call: n <= 65535)", v0, v0, n, B, n_views);
+    if (n == 0) return MI_OK;
+    if (!images || !dst) return fail(MI_EINVAL, "null argument");
+    return launched(dihedral_views_launch(images, dst, dv, C, H, W, v0, n, (hipStream_t)stream), "dihedral_views");
+}
+
+extern "C" int mi_dihedral_reduce(const float* views_out, int B, int C, int H, int W, const int32_t* views, int n_views,
+                                  float* mean_out, float* std_out, float* samples_out, void* stream) {
+    DihedralViews dv;
+    if (int rc = check_dihedral_call(B, C, H, W, views, n_views, &dv)) return rc;
+    if (!mean_out && !std_out && !samples_out) return fail(MI_EINVAL, "no output: give at least one of mean_out, std_out, samples_out");
+    if (int rc = check_std_views(std_out, n_views)) return rc;
+    if (!views_out) return fail(MI_EINVAL, "null argument");
+    return launched(dihedral_reduce_launch(views_out, B, dv, C, H, W, mean_out, std_out, samples_out, (hipStream_t)stream), "dihedral_reduce");
+}
+
+extern "C" int mi_dihedral_quantiles(const float* views_out, int B, int C, int H, int W, const int32_t* views, int n_views,
+                                     const double* q, int nq, float* out, void* stream) {
+    DihedralViews dv;
+    if (int rc = check_dihedral_call(B, C, H, W, views, n_views, &dv)) return rc;
+    QuantileLevels ql;
+    if (int rc = check_quantile_levels(q, nq, &ql)) return rc;
+    if (!views_out || !out) return fail(MI_EINVAL, "null argument");
+    return launched(dihedral_quantiles_launch(views_out, B, dv, C, H, W, ql, out, (hipStream_t)stream), "dihedral_quantiles");
+}
+
+// mi_denoise_ensemble with the views of an image in the place of its draws: virtual sample v = b * G + k is view k of image b.
+// The sampler leaves every view's output in the view's own frame, always in the workspace (a transposing unview cannot run in
+// place), and the reduce launch turns them back while it reads them.
+extern "C" int mi_denoise_self_ensemble(mi_plan* plan, const float* noisy, float* mean_out, float* std_out, float* samples_out,
+                                        int B, int H, int W, const int32_t* views, int n_views,
+                                        const int32_t* t_list, int n_iters,
+                                        const float* beta, const float* alpha, const float* alpha_hat, int noise_steps,
+                                        int seeded, uint64_t seed, int64_t sample_offset, int64_t member_offset, int pass_samples, int flags,
+                                        void* workspace, size_t workspace_bytes, void* stream) {
+    DihedralViews dv;
+    if (!plan) return fail(MI_EINVAL, "null plan");
+    if (int rc = check_views(views, n_views, H, W, &dv)) return rc;      // the view list first, then the rules of an ensemble with one member per view
+    if (int rc = check_ensemble_args(plan, B, n_views, H, W, sample_offset, member_offset, pass_samples)) return rc;
+    if (!mean_out && !std_out && !samples_out) return fail(MI_EINVAL, "no output: give at least one of mean_out, std_out, samples_out");
+    if (int rc = check_std_views(std_out, n_views)) return rc;
+    const int Cc = plan->cfg.in_channels;
+    const size_t chw = (size_t)Cc * H * W, img = chw * sizeof(float);
+    const Buf buf[4] = {{noisy, (size_t)B * img, "noisy"}, {mean_out, (size_t)B * img, "mean_out"}, {std_out, (size_t)B * img, "std_out"},
+                        {samples_out, (size_t)B * n_views * img, "samples_out"}};
+    if (int rc = check_no_overlap(buf, 4, "noisy is read by every pass and the reduce writes mean_out, std_out and samples_out in one launch"))
+        return rc;
+    const Schedule sc{t_list, n_iters, beta, alpha, alpha_hat, noise_steps};
+    EnsembleLayout L{};
+    // (evaluated before the state check, reported after it: check_batched_call; host arithmetic only, as in the *_workspace_bytes queries)
+    const int layout_rc = ensemble_layout(plan, B, n_views, H, W, pass_samples, false, &L);
+    if (int rc = check_batched_call(plan, layout_rc, L, workspace, workspace_bytes, {noisy}, sc)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    char* ws = (char*)workspace;
+    float* views_out = reinterpret_cast<float*>(ws + L.samples_off);
+    std::lock_guard<std::mutex> side_lk(plan->side_mu);     // held over all passes: the side streams are per plan
+    HIPCHK(hipMemsetAsync(ws, 0, 256, s));                  // status word: once per call, the passes accumulate into it
+    StepNoise sn;                                           // view k draws as member member_offset + k, at the pixel's place in the VIEW's frame
+    if (seeded) { sn.seeded = true; sn.seed = seed; sn.sample_offset = sample_offset; sn.members = n_views; sn.member_offset = (uint32_t)member_offset; }
+    auto fill = [&](float* cond, int v0, int n) { return launched(dihedral_views_launch(noisy, cond, dv, Cc, H, W, v0, n, s), "dihedral_views"); };
+    if (int rc = run_passes(plan, fill, views_out, (int64_t)B * n_views, 1, H, W, chw, L, sn, sc, flags, ws, stream)) return rc;
+    return launched(dihedral_reduce_launch(views_out, B, dv, Cc, H, W, mean_out, std_out, samples_out, s), "dihedral_reduce");
+}
+
 extern "C" int mi_debug_fetch(mi_plan* plan, const char* module_name, int B, int H, int W, const void* workspace,
                               float* dst, int* C, int* h, int* w, void* stream) {
     if (!plan || !module_name) return fail(MI_EINVAL, "null argument");

@@ -122,6 +122,8 @@ int check_tiled_args(mi_plan* p, int B, int H, int W, int th, int tw, int oy, in
 int check_tiled_ensemble_args(mi_plan* p, int B, int members, int H, int W, int th, int tw, int oy, int ox, int64_t sample_offset,
                               int64_t member_offset, int pass_samples, TileGeom* g);   // midd_exec.hip
 int tiled_ensemble_layout(mi_plan* p, int B, int members, int tiles, int th, int tw, int pass_samples, bool tiles_external, EnsembleLayout* L);   // midd_planner.hip
+// mi_denoise_self_ensemble: its workspace is mi_denoise_ensemble's with members = views and the member outputs ALWAYS inside:
+// [sampler workspace of a pass | condition views of a pass | view outputs [B][views], each in its view's frame]
 }  // namespace midd
 
 struct mi_plan {

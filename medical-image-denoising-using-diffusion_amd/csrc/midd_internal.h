@@ -263,6 +263,21 @@ hipError_t ensemble_quantiles_launch(const float* samples, int B, int K, unsigne
 // per member, then of ensemble_quantiles_launch).  The limits of tile_blend_reduce_launch and of the call above
 hipError_t tile_blend_quantiles_launch(const float* tiles, int B, int M, const TileGeom& g, const QuantileLevels& ql, float* out, hipStream_t s);
 
+// Geometric self-ensemble (include/midd.h: THE GEOMETRY).  A view list is 1 .. 8 distinct codes g = 4 t + 2 fy + fx in the caller's
+// order; it travels as kernel arguments.  Transposing codes (g >= 4) need H == W.
+constexpr int DIHEDRAL_MAX_VIEWS = 8;
+struct DihedralViews { int n; uint8_t code[DIHEDRAL_MAX_VIEWS]; };
+// dst [n][C][Hv][Wv] <- view(images[v / G], code[v % G]) for the virtual samples v = v0 .. v0 + n - 1 (image-major); n <= 65535
+hipError_t dihedral_views_launch(const float* images, float* dst, const DihedralViews& dv, int C, int H, int W, int v0, int n, hipStream_t s);
+// views_out [B][G][C][Hv][Wv] (every view in its own frame) -> mean, unbiased std [B][C][H][W] over the views turned back and those
+// aligned members, samples [B][G][C][H][W]; each of the three may be null (not all; std needs G >= 2).  The arithmetic of
+// ensemble_reduce_launch over unview of every view, in list order.  B <= 65535
+hipError_t dihedral_reduce_launch(const float* views_out, int B, const DihedralViews& dv, int C, int H, int W,
+                                  float* mean, float* std, float* samples, hipStream_t s);
+// views_out as above -> out [B][nq][C][H][W]: the arithmetic of ensemble_quantiles_launch over the aligned members
+hipError_t dihedral_quantiles_launch(const float* views_out, int B, const DihedralViews& dv, int C, int H, int W,
+                                     const QuantileLevels& ql, float* out, hipStream_t s);
+
 // bilinear resize of an activation tensor, either layout (align_corners=False), any size ratio
 hipError_t resize_bilinear_launch(const float* src, float* dst, stat_word* tot, int rep, int bs, int B, int H, int W, int C, int OH, int OW, int blocked, hipStream_t s);
 // ConvTranspose2d(C,C,4,stride=2,padding=1) direct (only used by topologies where it cannot be folded)

@@ -333,6 +333,20 @@ extern "C" size_t mi_ensemble_workspace_bytes(mi_plan* plan, int B, int members,
     return L.bytes;
 }
 
+// (the layout depends on the NUMBER of views alone, so the list itself is not an argument)
+extern "C" size_t mi_self_ensemble_workspace_bytes(mi_plan* plan, int B, int n_views, int H, int W, int pass_samples, int samples_external) {
+    (void)samples_external;                              // the view-frame outputs always live in the workspace (include/midd.h)
+    if (n_views < 1 || n_views > DIHEDRAL_MAX_VIEWS) {
+        fail(MI_EINVAL, "n_views %d outside [1, %d]: a view list holds 1 to 8 distinct view codes (limit: 1 <= n_views <= %d)", n_views,
+             DIHEDRAL_MAX_VIEWS, DIHEDRAL_MAX_VIEWS);
+        return 0;
+    }
+    if (check_ensemble_args(plan, B, n_views, H, W, 0, 0, pass_samples)) return 0;
+    EnsembleLayout L{};
+    if (ensemble_layout(plan, B, n_views, H, W, pass_samples, false, &L)) return 0;
+    return L.bytes;
+}
+
 extern "C" size_t mi_tiled_workspace_bytes(mi_plan* plan, int B, int H, int W, int th, int tw, int oy, int ox, int pass_samples, int tiles_external) {
     TileGeom g{};
     if (check_tiled_args(plan, B, H, W, th, tw, oy, ox, 0, pass_samples, &g)) return 0;

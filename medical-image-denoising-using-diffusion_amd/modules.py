@@ -405,6 +405,65 @@ class UNetDiffusion(nn.Module):
         return mean, std, samples
 
     @torch.no_grad()
+    def run_self_ensemble(self, noisy: torch.Tensor, t_list, beta: torch.Tensor, alpha: torch.Tensor, alpha_hat: torch.Tensor,
+                          clamp_eps: bool, views="auto", seed: Optional[int] = None, sample_offset: int = 0, member_offset: int = 0,
+                          max_batch: int = 16, want_mean: bool = True, want_std: bool = True, want_samples: bool = False,
+                          no_split: bool = False, levels=None):
+        """The flipped and rotated views of every image in one native call (mi_denoise_self_ensemble) -> (mean, std, samples,
+        codes, maps), each tensor None when not asked for.  The B * views (image, view) pairs run through the sampler loop in
+        passes of at most ``max_batch``; samples is [B, views, C, H, W], every member turned back into the image's frame.  seed
+        None: no noise term (DDIM); else view k draws as member ``member_offset + k`` of the seeded generator.  ``levels``
+        (checked quantile levels): one mi_dihedral_quantiles launch follows on the same stream, reading the view outputs where
+        the call left them -- the tail of its workspace (include/midd.h) -- so no member tensor exists for it."""
+        from .sampler import _levels_arg, check_members, check_seed, view_codes
+        if seed is not None:
+            seed, _ = check_seed(seed, 0)
+        _, sample_offset = check_seed(0, sample_offset)
+        if not isinstance(noisy, torch.Tensor) or noisy.dim() != 4:
+            self._check_image(noisy, "noisy_img")                 # (raises)
+        B, Cc, H, W = noisy.shape
+        codes = view_codes(H, W, views)
+        G = len(codes)
+        _, member_offset, max_batch = check_members(G, member_offset, max_batch)
+        self._check_image(noisy, "noisy_img")
+        want_std = want_std and G >= 2
+        if not (want_mean or want_std or want_samples):
+            raise ValueError("nothing to return: ask for the mean, the std or the samples")
+        keep, sched = self._schedule_args(t_list, beta, alpha, alpha_hat)
+        code_arg, maps = (C.c_int32 * G)(*codes), None
+        dev = noisy.device
+        with self._lock, torch.cuda.device(dev):
+            plan = self._ensure_plan(time_rows=sched[-1])
+            src = noisy.contiguous()
+            mean = torch.empty_like(src) if want_mean else None
+            std = torch.empty_like(src) if want_std else None
+            samples = torch.empty((B, G, Cc, H, W), dtype=torch.float32, device=dev) if want_samples else None
+            pass_samples = min(max_batch, max(1, B * G))
+            size = (B, G, H, W, pass_samples)
+            ws = self._resident_workspace("_ensemble_ws", ("self_ensemble",) + size + (dev.index, torch.cuda.current_stream(dev).cuda_stream),
+                                          lambda: native.lib().mi_self_ensemble_workspace_bytes(self._plan, *size, 0), dev)
+            self._invoke(native.lib().mi_denoise_self_ensemble,
+                         (plan, src.data_ptr(), _ptr(mean), _ptr(std), _ptr(samples), B, H, W, code_arg, G) + sched
+                         + (0 if seed is None else 1, C.c_uint64(seed or 0), C.c_int64(sample_offset), C.c_int64(member_offset), pass_samples,
+                            self._call_flags(clamp_eps, no_split)), ws, dev)
+            if levels is not None:
+                maps = torch.empty((B, len(levels), Cc, H, W), dtype=torch.float32, device=dev)
+                wptr, _ = self._aligned_ptr(ws)
+                nbytes = native.lib().mi_self_ensemble_workspace_bytes(self._plan, *size, 0)
+                views_out = wptr + nbytes - B * G * Cc * H * W * 4          # the view outputs: the last bytes of the workspace
+                native.check(native.lib().mi_dihedral_quantiles(views_out, B, Cc, H, W, code_arg, G, _levels_arg(levels), len(levels),
+                                                                maps.data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
+        return mean, std, samples, codes, maps
+
+    def self_ensemble_workspace_bytes(self, B: int, views: int, H: int, W: int, max_batch: int = 16, samples_external: bool = False) -> int:
+        """Workspace of run_self_ensemble for ``views`` views per image (a count): ensemble_workspace_bytes of as many members,
+        whatever ``samples_external`` says -- the view-frame outputs always live in the workspace."""
+        with self._lock, torch.cuda.device(self._device()):
+            self._ensure_plan()
+            return int(native.lib().mi_self_ensemble_workspace_bytes(self._plan, B, views, H, W, min(max_batch, max(1, B * views)),
+                                                                     1 if samples_external else 0))
+
+    @torch.no_grad()
     def run_tiled(self, noisy: torch.Tensor, t_list, beta: torch.Tensor, alpha: torch.Tensor, alpha_hat: torch.Tensor,
                   clamp_eps: bool, tile, overlap, seed: Optional[int] = None, sample_offset: int = 0, max_batch: int = 16,
                   want_tiles: bool = False, no_split: bool = False):

@@ -89,6 +89,14 @@ SYMBOLS = [
     ("mi_tiled_ensemble_workspace_bytes", C.c_size_t, [C.c_void_p] + [C.c_int] * 10),
     ("mi_tile_blend_reduce", C.c_int, [C.c_void_p] + [C.c_int] * 9 + [C.c_void_p] * 4),
     ("mi_tile_blend_quantiles", C.c_int, [C.c_void_p] + [C.c_int] * 9 + [C.POINTER(C.c_double), C.c_int, C.c_void_p, C.c_void_p]),
+    ("mi_dihedral_views", C.c_int, [C.c_void_p] + [C.c_int] * 4 + [C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    ("mi_dihedral_reduce", C.c_int, [C.c_void_p] + [C.c_int] * 4 + [C.POINTER(C.c_int32), C.c_int] + [C.c_void_p] * 4),
+    ("mi_dihedral_quantiles", C.c_int, [C.c_void_p] + [C.c_int] * 4 + [C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_double), C.c_int,
+                                        C.c_void_p, C.c_void_p]),
+    ("mi_denoise_self_ensemble", C.c_int, [C.c_void_p] * 5 + [C.c_int] * 3 + [C.POINTER(C.c_int32), C.c_int] +
+                                          [C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int,
+                                           C.c_int, C.c_uint64, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
+    ("mi_self_ensemble_workspace_bytes", C.c_size_t, [C.c_void_p] + [C.c_int] * 6),
     ("mi_debug_fetch", C.c_int, [C.c_void_p, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                  C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p]),
     ("mi_status", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]),

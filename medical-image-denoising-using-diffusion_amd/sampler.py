@@ -334,6 +334,145 @@ def tile_blend_quantiles(tiles: torch.Tensor, H: int, W: int, overlap=32, q=None
     return out
 
 
+class SelfEnsembleResult(NamedTuple):
+    """What ``DiffusionDenoiser.denoise_self_ensemble`` returns."""
+    mean: torch.Tensor                    # [B, C, H, W]: per-pixel mean over the views, each turned back into the image's frame
+    std: Optional[torch.Tensor]           # [B, C, H, W]: unbiased per-pixel standard deviation over the views; None for one view
+    samples: Optional[torch.Tensor]       # [B, views, C, H, W] with return_samples=True: the aligned members, in the order of ``views``
+    views: Tuple[int, ...]                # the view codes of the run (include/midd.h: THE GEOMETRY), as resolved from the argument
+    seed: Optional[int]                   # cddpm: the seed of the run (drawn when the call had seed=None); None for DDIM
+
+
+class SelfEnsembleQuantileResult(NamedTuple):
+    """What ``DiffusionDenoiser.denoise_self_ensemble(..., quantiles=levels)`` returns: SelfEnsembleResult's fields, then the maps."""
+    mean: torch.Tensor
+    std: Optional[torch.Tensor]
+    samples: Optional[torch.Tensor]
+    views: Tuple[int, ...]
+    seed: Optional[int]
+    quantiles: torch.Tensor               # [B, nq, C, H, W]: per-pixel quantile maps of the aligned members
+    levels: Tuple[float, ...]             # the quantile levels, each in [0, 1]
+
+
+MAX_VIEWS = 8                             # include/midd.h: view codes g = 4 * transpose + 2 * flip_rows + flip_columns, 0 .. 7
+VIEW_SETS = {"flips": (0, 1, 2, 3), "d4": (0, 1, 2, 3, 4, 5, 6, 7)}
+
+
+def view_codes(H: int, W: int, views="auto") -> Tuple[int, ...]:
+    """The view list of a self-ensemble over H x W images (host only): ``"auto"`` is all 8 flips and rotations for a square image
+    and the 4 that keep the shape otherwise, ``"flips"`` codes 0 .. 3, ``"d4"`` codes 0 .. 7, or a sequence of 1 to 8 distinct
+    codes in the order the members are wanted.  Raises ValueError for anything the native call would refuse."""
+    H, W = _integer(H, "H", 1 << 31, 1), _integer(W, "W", 1 << 31, 1)
+    if isinstance(views, str):
+        if views == "auto":
+            views = "d4" if H == W else "flips"
+        if views not in VIEW_SETS:
+            raise ValueError(f"views must be 'auto', 'flips', 'd4' or a sequence of view codes (got {views!r})")
+        codes = VIEW_SETS[views]
+    else:
+        try:
+            codes = tuple(views)
+        except TypeError:
+            raise ValueError(f"views must be 'auto', 'flips', 'd4' or a sequence of view codes (got {views!r})") from None
+        if not 1 <= len(codes) <= MAX_VIEWS:
+            raise ValueError(f"a view list holds between 1 and {MAX_VIEWS} view codes (got {len(codes)})")
+        out = []
+        for v in codes:
+            try:
+                if isinstance(v, bool):
+                    raise TypeError
+                g = operator.index(v)
+            except TypeError:
+                raise ValueError(f"every view code must be an integer in [0, 7] (got {v!r})") from None
+            if not 0 <= g <= 7:
+                raise ValueError(f"every view code must be an integer in [0, 7] (got {v!r})")
+            if g in out:
+                raise ValueError(f"view code {g} is repeated: the view codes of a list are distinct")
+            out.append(g)
+        codes = tuple(out)
+    for g in codes:
+        if g & 4 and H != W:
+            raise ValueError(f"view code {g} transposes the image: codes 4 .. 7 need H == W (got {H}x{W}; use views='flips')")
+    return codes
+
+
+def _views_arg(codes: Tuple[int, ...]):
+    return (C.c_int32 * len(codes))(*codes)
+
+
+def _view_tensor(x, what: str, dims: int) -> torch.Tensor:
+    if not isinstance(x, torch.Tensor) or x.dim() != dims or min(x.shape) < 1:
+        raise ValueError(f"{what} must be a {dims}-dimensional non-empty tensor")
+    if x.device.type != "cuda":
+        raise RuntimeError(f"{what} is on {x.device}: the view kernels run only on a ROCm GPU, there is no CPU fallback")
+    if x.dtype != torch.float32:
+        raise TypeError(f"{what} must be float32 (got {x.dtype})")
+    return x.contiguous()
+
+
+@torch.no_grad()
+def dihedral_views(images: torch.Tensor, views="auto") -> torch.Tensor:
+    """[B, C, H, W] -> its views [B, G, C, Hv, Wv] (mi_dihedral_views): what ``denoise_self_ensemble`` feeds the sampler.  Bit
+    copies; transposing views need H == W, so every view has the image's shape."""
+    if isinstance(images, torch.Tensor) and images.dim() == 4:
+        codes = view_codes(images.shape[2], images.shape[3], views)
+    src = _view_tensor(images, "images", 4)
+    B, Cc, H, W = src.shape
+    G = len(codes)
+    with torch.cuda.device(src.device):
+        out = torch.empty((B, G, Cc, H, W), dtype=torch.float32, device=src.device)
+        stream = torch.cuda.current_stream(src.device).cuda_stream
+        for v0 in range(0, B * G, 65535):
+            n = min(65535, B * G - v0)
+            native.check(native.lib().mi_dihedral_views(src.data_ptr(), B, Cc, H, W, _views_arg(codes), G, v0, n,
+                                                        out.data_ptr() + v0 * Cc * H * W * 4, stream))
+    return out
+
+
+@torch.no_grad()
+def dihedral_reduce(view_outputs: torch.Tensor, views="auto",
+                    return_samples: bool = True) -> Tuple[torch.Tensor, Optional[torch.Tensor], Optional[torch.Tensor]]:
+    """view_outputs [B, G, C, Hv, Wv], view k in its own frame -> (mean, std, samples): per-pixel mean and unbiased std [B, C, H, W]
+    over the views turned back into the image's frame and those aligned members [B, G, C, H, W], in one kernel with the arithmetic
+    of ``denoise_self_ensemble`` (mi_dihedral_reduce: unview per view, then ``ensemble_reduce``, bit for bit).  std is None for
+    one view; samples is None with ``return_samples=False``."""
+    if isinstance(view_outputs, torch.Tensor) and view_outputs.dim() == 5:
+        codes = view_codes(view_outputs.shape[3], view_outputs.shape[4], views)
+        if len(codes) != view_outputs.shape[1]:
+            raise ValueError(f"view_outputs holds {view_outputs.shape[1]} views per image, the view list {len(codes)}")
+    src = _view_tensor(view_outputs, "view_outputs", 5)
+    B, G, Cc, H, W = src.shape
+    with torch.cuda.device(src.device):
+        mean = torch.empty((B, Cc, H, W), dtype=torch.float32, device=src.device)
+        std = torch.empty_like(mean) if G >= 2 else None
+        samples = torch.empty_like(src) if return_samples else None
+        native.check(native.lib().mi_dihedral_reduce(src.data_ptr(), B, Cc, H, W, _views_arg(codes), G, mean.data_ptr(),
+                                                     None if std is None else std.data_ptr(),
+                                                     None if samples is None else samples.data_ptr(),
+                                                     torch.cuda.current_stream(src.device).cuda_stream))
+    return mean, std, samples
+
+
+@torch.no_grad()
+def dihedral_quantiles(view_outputs: torch.Tensor, views="auto", q=None) -> torch.Tensor:
+    """view_outputs [B, G, C, Hv, Wv] -> the per-pixel quantile maps [B, nq, C, H, W] of the aligned members at the levels ``q``
+    (mi_dihedral_quantiles: unview per view, then ``ensemble_quantiles``, bit for bit; the aligned members are never stored)."""
+    if q is None:
+        raise ValueError("dihedral_quantiles needs the quantile levels: q=(0.05, 0.5, 0.95), say")
+    levels = check_levels(q)
+    if isinstance(view_outputs, torch.Tensor) and view_outputs.dim() == 5:
+        codes = view_codes(view_outputs.shape[3], view_outputs.shape[4], views)
+        if len(codes) != view_outputs.shape[1]:
+            raise ValueError(f"view_outputs holds {view_outputs.shape[1]} views per image, the view list {len(codes)}")
+    src = _view_tensor(view_outputs, "view_outputs", 5)
+    B, G, Cc, H, W = src.shape
+    with torch.cuda.device(src.device):
+        out = torch.empty((B, len(levels), Cc, H, W), dtype=torch.float32, device=src.device)
+        native.check(native.lib().mi_dihedral_quantiles(src.data_ptr(), B, Cc, H, W, _views_arg(codes), G, _levels_arg(levels), len(levels),
+                                                        out.data_ptr(), torch.cuda.current_stream(src.device).cuda_stream))
+    return out
+
+
 class DiffusionDenoiser:
     def __init__(self, model, noise_steps=50, beta_start=1e-4, beta_end=0.02):
         self.model = model
@@ -498,6 +637,48 @@ class DiffusionDenoiser:
             return TiledEnsembleResult(mean, std, samples, tiles, plan.origins_y, plan.origins_x, seed)
         maps = tile_blend_quantiles(tiles, noisy_img.shape[2], noisy_img.shape[3], plan.overlap, levels)
         return TiledEnsembleQuantileResult(mean, std, samples, tiles if return_tiles else None, plan.origins_y, plan.origins_x, seed, maps, levels)
+
+    @torch.no_grad()
+    def denoise_self_ensemble(self, noisy_img: torch.Tensor, inference_steps: int = 25, views="auto", seed: Optional[int] = None,
+                              sample_offset: int = 0, member_offset: int = 0, max_batch: int = 16,
+                              return_samples: bool = False, quantiles=None):
+        """The geometric self-ensemble ("x8 test-time augmentation") in one native call, for BOTH variants: the network runs on
+        the flipped and rotated copies of every image, every output is turned back, and the call returns their per-pixel mean --
+        the usual few tenths of a dB over a single run -- and unbiased standard deviation: where the output depends on the
+        orientation.  Not a reference call (the reference denoises the image as given, DDIMModel.py:268-289).
+
+        ``views``: ``"auto"`` (all 8 flips and rotations of a square image, the 4 shape-keeping ones otherwise), ``"flips"``,
+        ``"d4"`` or a sequence of 1 to 8 distinct view codes g = 4 * transpose + 2 * flip_rows + flip_columns (``view_codes``;
+        include/midd.h: THE GEOMETRY); codes 4 .. 7 need H == W.  The B * views (image, view) pairs run as the samples of batches
+        of at most ``max_batch``.  Member k is ``unview(denoise(view(x, g_k)), g_k)`` -- bit for bit with ``batch_invariant=True``
+        -- and ``mean``, ``std`` are ``ensemble_reduce`` of the members in list order, computed by one kernel that never stores
+        them unless ``return_samples=True`` (``samples``: [B, views, C, H, W]).  ``std`` is None for one view.
+
+        DDIM: ``seed`` must be None; the result's ``seed`` is None.  cddpm: always seeded -- view k of image b draws the step
+        noise of (seed, sample_offset + b, member_offset + k) at the pixel's place in the VIEW's frame, i.e. member k is
+        ``denoise(view(x), seed=seed, sample_offset=sample_offset + b, member=member_offset + k)`` turned back; ``seed=None`` draws
+        a 64-bit seed and returns it.
+
+        ``quantiles`` (a sequence of at most 8 levels in [0, 1]): the call also returns the per-pixel quantile maps of the aligned
+        members as a ``SelfEnsembleQuantileResult``: the fields above, then ``quantiles`` [B, nq, C, H, W] and ``levels``.  One
+        ``dihedral_quantiles`` launch follows on the same stream and reads the view outputs from the call's workspace; mean, std
+        and samples are the bits of the call without it."""
+        levels = None if quantiles is None else check_levels(quantiles)
+        stochastic = getattr(self.model, "variant", "ddim") == "cddpm"
+        if not stochastic and seed is not None:
+            raise ValueError("seed selects the step noise of the stochastic (cddpm) variant: the DDIM variant takes seed=None")
+        if isinstance(noisy_img, torch.Tensor) and noisy_img.dim() == 4:
+            views = view_codes(noisy_img.shape[2], noisy_img.shape[3], views)      # (before any GPU work; run_self_ensemble judges the rest)
+        if stochastic:
+            seed, _ = check_seed(self._draw_seed() if seed is None else seed, 0)
+        self.model.eval()
+        steps = timestep_list(self.noise_steps, inference_steps)
+        mean, std, samples, codes, maps = self.model.run_self_ensemble(
+            noisy_img, steps, self.beta, self.alpha, self.alpha_hat, clamp_eps=not stochastic, views=views, seed=seed,
+            sample_offset=sample_offset, member_offset=member_offset, max_batch=max_batch, want_samples=return_samples, levels=levels)
+        if levels is None:
+            return SelfEnsembleResult(mean, std, samples, codes, seed)
+        return SelfEnsembleQuantileResult(mean, std, samples, codes, seed, maps, levels)
 
     def _draw_seed(self) -> int:
         hi, lo = torch.randint(0, 1 << 32, (2,), dtype=torch.int64).tolist()
