@@ -476,6 +476,79 @@ int mi_denoise_self_ensemble(mi_plan* plan, const float* noisy, float* mean_out,
  * given.  Host only, answered from the planner alone: it works before mi_unet_finalize too.  0 on bad arguments (mi_last_error). */
 size_t mi_self_ensemble_workspace_bytes(mi_plan* plan, int B, int n_views, int H, int W, int pass_samples, int samples_external);
 
+/* THE DDIM UPDATE: a stride-aware update rule for the sampler loop (Song, Meng, Ermon: Denoising Diffusion Implicit Models,
+ * eq. 12 and 16), opt-in.  The reference's update, x <- clamp(c1 * (x - c2 * eps) + c3 * noise, 0, 1), is the one-step ancestral mean
+ * for t -> t-1 whatever the list; on a strided list (t, t-6, t-12, ...) every iteration still removes one step's share of the
+ * noise.  This rule predicts x0 from eps, optionally clips it to the image range, and re-noises it to the NEXT timestep of the
+ * list.  Not a reference rule: the default (NULL, or kind MI_UPDATE_REFERENCE) stays the reference's, with the reference's bits.
+ * THE SPECIFICATION (fixed).  The list t_0 > t_1 > ... > t_{n-1} is strictly decreasing.  Iteration i has
+ * A = alpha_hat[t_i] and P = alpha_hat[t_{i+1}], P = 1 for the last iteration; 0 < A < P <= 1.
+ * Host, in double precision from the caller's fp32 table, every operation rounded on its own, each value rounded once to fp32:
+ *   sigma = eta * sqrt((1-P)/(1-A)) * sqrt(1 - A/P)             (products left to right)
+ *   k0 = 1/sqrt(A)    k1 = sqrt(1-A)    r0 = sqrt(A)    r1 = 1/sqrt(1-A)
+ *   a  = sqrt(P)      b  = sqrt(max(0, (1-P) - sigma*sigma))     s = 2*sigma
+ * s carries the factor 2 because the step-noise convention stays what it is: the tensor argument and the seeded generator both
+ * deliver n = 0.5 * z, and neither they nor mi_step_noise_fill change.  The last row is a = 1, b = 0, s = 0; eta = 0 gives s = 0
+ * in every row (the deterministic sampler), eta = 1 on the stride-1 list the ancestral sampler's variance.
+ * Device, per element, fp32, every operation rounded on its own (no fused multiply-add anywhere in this update; fmin / fmax as
+ * C's fminf / fmaxf), in this order:
+ *   e  = flags & MI_CLAMP_EPS ? min(max(eps, -5), 5) : eps
+ *   x0 = k0 * (x - k1*e)
+ *   if clip_x0:  c = min(max(x0, 0), 1);  if c != x0: e = (x - r0*c) * r1;  x0 = c
+ *                (eps re-derived, so that x_prev stays on the trajectory towards the clipped image)
+ *   xn = a*x0 + b*e
+ *   if s > 0 and the call has a noise source:  xn = xn + s*n       (n: step_noise[i] or the seeded draw of iteration i)
+ *   if i == n-1:  xn = min(max(xn, 0), 1)       (the call returns an image in [0, 1] like every other call)
+ * Intermediate x is NOT clamped to [0, 1] under this rule: x_t = sqrt(A) x0 + sqrt(1-A) eps leaves [0, 1] by design, and a clamp
+ * would take it off the trajectory the next iteration's x0 prediction assumes.  Nothing is drawn or read when s == 0 -- every
+ * iteration at eta = 0, always the last one.  tests/ddim_update_reference.py restates host and device in numpy, bit for bit.
+ * The start state stays the noisy image itself, as in the reference. */
+#define MI_UPDATE_REFERENCE 0
+#define MI_UPDATE_DDIM      1
+typedef struct mi_update_rule {
+    int32_t kind;      /* MI_UPDATE_* */
+    double  eta;       /* MI_UPDATE_DDIM: finite, in [0, 1] */
+    int32_t clip_x0;   /* MI_UPDATE_DDIM: != 0 clips the predicted image to [0, 1] */
+} mi_update_rule;
+
+/* The coefficient table of the rule above, host only (no plan, no GPU): out HOST fp32 [n_iters][7] <- (k0, k1, r0, r1, a, b, s) of
+ * every iteration -- the values the *_rule calls below pass to the update kernel.
+ * MI_EINVAL: eta outside [0, 1] or NaN; a null argument; noise_steps < 1; a timestep outside [0, noise_steps); a list that is not
+ * strictly decreasing; a table with alpha_hat[t_i] outside (0, alpha_hat[t_{i+1}]). */
+int mi_ddim_coefficients(const int32_t* t_list, int n_iters, const float* alpha_hat, int noise_steps, double eta, float* out);
+
+/* mi_denoise and mi_denoise_seeded in one signature (step_noise, or seeded != 0 with seed and sample_offset; both: MI_EINVAL), plus
+ * `rule`.  rule == NULL or kind MI_UPDATE_REFERENCE: those two calls, bit for bit.  MI_UPDATE_DDIM: the update above in the place
+ * of the reference's; everything else -- the forward, the two-stream split, the seeded generator's counter words, the workspace
+ * (mi_workspace_bytes: the rule needs no memory) -- is the same.  The rule's own MI_EINVAL cases (mi_ddim_coefficients) are judged
+ * first, before the plan's state and before any GPU work.  With eta > 0 the call takes a noise source for EITHER variant; without
+ * one the term is left out. */
+int mi_denoise_rule(mi_plan* plan, const float* noisy, float* x_out, int B, int H, int W,
+                    const int32_t* t_list, int n_iters,
+                    const float* beta, const float* alpha, const float* alpha_hat, int noise_steps,
+                    const float* step_noise, int seeded, uint64_t seed, int64_t sample_offset, int flags,
+                    const mi_update_rule* rule, void* workspace, size_t workspace_bytes, void* stream);
+
+/* mi_denoise_ensemble plus `rule`: every pass runs the loop under the rule.  NULL / reference: mi_denoise_ensemble bit for bit.
+ * With MI_UPDATE_DDIM and eta > 0 the DDIM variant has an ensemble too (eta == 0 draws nothing: all members are equal; the host
+ * shims refuse it).  Workspace: mi_ensemble_workspace_bytes. */
+int mi_denoise_ensemble_rule(mi_plan* plan, const float* noisy, float* mean_out, float* std_out, float* samples_out,
+                             int B, int members, int H, int W,
+                             const int32_t* t_list, int n_iters,
+                             const float* beta, const float* alpha, const float* alpha_hat, int noise_steps,
+                             uint64_t seed, int64_t sample_offset, int64_t member_offset, int pass_samples, int flags,
+                             const mi_update_rule* rule, void* workspace, size_t workspace_bytes, void* stream);
+
+/* mi_denoise_tiled plus `rule`, likewise.  Workspace: mi_tiled_workspace_bytes.
+ * NOT BUILT: mi_denoise_slots (its per-slot record would have to carry the seven coefficients), mi_denoise_tiled_ensemble and
+ * mi_denoise_self_ensemble (plumbing only) keep the reference's rule. */
+int mi_denoise_tiled_rule(mi_plan* plan, const float* noisy, float* image_out, float* tiles_out,
+                          int B, int H, int W, int th, int tw, int oy, int ox,
+                          const int32_t* t_list, int n_iters,
+                          const float* beta, const float* alpha, const float* alpha_hat, int noise_steps,
+                          int seeded, uint64_t seed, int64_t sample_offset, int pass_samples, int flags,
+                          const mi_update_rule* rule, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Status of the last mi_unet_forward / mi_denoise call that used `workspace` (its first word; the calls clear it when they
  * start).  SYNCHRONISES `stream` (one 4-byte device-to-host copy).  Returns MI_OK with *flags == 0, or MI_ERANGE with the
  * MI_STATUS_* bits in *flags: the kernels never turn a NaN / Inf activation or an operand beyond the split-fp16 range into

@@ -9,6 +9,7 @@ img_size -> sampler -> uint8 -> bicubic resize back -> PNG, with the reference's
                            [--quantiles 0.05,0.5,0.95 --quantiles-out q.npy]]
                            [--tile N [--overlap O]]
                            [--self-ensemble [auto|flips|d4] [--std-out std.npy] [--quantiles Q,Q --quantiles-out q.npy]]
+                           [--update reference|ddim [--eta F] [--no-clip-x0]]
 
 Without a checkpoint (the trained weights are not distributed with the reference) the network is
 random-init, which exercises the path but does not denoise.  The reference helper has a latent
@@ -26,7 +27,7 @@ import torch
 from PIL import Image
 
 from .modules import UNetDiffusion
-from .sampler import MAX_QUANTILE_MEMBERS, DiffusionDenoiser, check_levels
+from .sampler import MAX_QUANTILE_MEMBERS, DiffusionDenoiser, check_levels, check_update
 
 
 def denoise_image_diffusion(model_path: Optional[str], test_image_path: str, device_type: str = "cuda",
@@ -35,7 +36,8 @@ def denoise_image_diffusion(model_path: Optional[str], test_image_path: str, dev
                             seed: Optional[int] = None, samples: Optional[int] = None,
                             std_out: Optional[str] = None, tile: Optional[int] = None, overlap: int = 32,
                             quantiles: Optional[Sequence[float]] = None, quantiles_out: Optional[str] = None,
-                            self_ensemble: Optional[str] = None) -> Image.Image:
+                            self_ensemble: Optional[str] = None, update: str = "reference", eta: float = 0.0,
+                            clip_x0: bool = True) -> Image.Image:
     """compute (not a reference argument): arithmetic of the network, see UNetDiffusion -- None keeps the default.
     seed (not a reference argument; cddpm): the stochastic sampler's noise is drawn on the device from this seed, so the same
     call gives the same image again (DiffusionDenoiser.denoise); None: torch.randn, as the reference.
@@ -49,7 +51,13 @@ def denoise_image_diffusion(model_path: Optional[str], test_image_path: str, dev
     `overlap` shared pixels (DiffusionDenoiser.denoise_tiled) -- no resize to img_size and back; both sides must be >= tile.
     self_ensemble (not a reference argument; both variants): "auto", "flips" or "d4" -- the returned image is the MEAN over the
     flipped and rotated views of the image (DiffusionDenoiser.denoise_self_ensemble); std_out, quantiles and quantiles_out then
-    describe the views instead of seeded draws.  Not together with samples or tile."""
+    describe the views instead of seeded draws.  Not together with samples or tile.
+    update, eta, clip_x0 (not reference arguments; both variants): "ddim" runs the stride-aware DDIM(eta) update
+    (DiffusionDenoiser.denoise) in the place of the reference's; with eta > 0 samples works for the DDIM variant too.  Not together
+    with self_ensemble."""
+    rule = {} if check_update(update, eta, clip_x0) is None else {"update": update, "eta": eta, "clip_x0": clip_x0}
+    if rule and self_ensemble is not None:
+        raise ValueError("--update ddim cannot be combined with --self-ensemble (the self-ensemble runs the reference's update only)")
     if self_ensemble is not None:
         if samples is not None:
             raise ValueError("--self-ensemble cannot be combined with --samples")
@@ -61,7 +69,7 @@ def denoise_image_diffusion(model_path: Optional[str], test_image_path: str, dev
             raise ValueError(f"--self-ensemble takes auto, flips or d4 (got {self_ensemble!r})")
     if tile is not None and (samples is not None or step_noise is not None):
         raise ValueError("--tile cannot be combined with --samples or a step_noise tensor")
-    if samples is not None and variant != "cddpm":
+    if samples is not None and variant != "cddpm" and not (rule and eta > 0):
         raise ValueError("--samples needs the stochastic (cddpm) variant: a deterministic sampler has no ensemble")
     if std_out is not None and self_ensemble is None and (samples is None or samples < 2):
         raise ValueError("--std-out needs --samples K with K >= 2")
@@ -92,7 +100,7 @@ def denoise_image_diffusion(model_path: Optional[str], test_image_path: str, dev
                              "--tile, or leave it out so that the image is resized to img_size")
         input_tensor = torch.from_numpy(np.asarray(img, np.uint8).astype(np.float32) / 255.0)[None, None].to(device)   # ToTensor
         start_time = time.time()
-        res = diffusion.denoise_tiled(input_tensor, inference_steps=inference_steps, tile=tile, overlap=overlap, seed=seed)
+        res = diffusion.denoise_tiled(input_tensor, inference_steps=inference_steps, tile=tile, overlap=overlap, seed=seed, **rule)
         if on_gpu:
             torch.cuda.synchronize(device)
         print(f"Tiled: {len(res.origins_y)} x {len(res.origins_x)} tiles of {tile}" + (f", seed {res.seed}" if res.seed is not None else ""))
@@ -120,7 +128,7 @@ def denoise_image_diffusion(model_path: Optional[str], test_image_path: str, dev
         if quantiles is not None:
             np.save(quantiles_out, ens.quantiles.reshape(len(quantiles), img_size, img_size).cpu().numpy())
     elif samples is not None:
-        ens = diffusion.denoise_ensemble(input_tensor, inference_steps=inference_steps, members=samples, seed=seed, quantiles=quantiles)
+        ens = diffusion.denoise_ensemble(input_tensor, inference_steps=inference_steps, members=samples, seed=seed, quantiles=quantiles, **rule)
         denoised = ens.mean                               # a mean of values in [0, 1]: in [0, 1]
         print(f"Ensemble of {samples} samples, seed {ens.seed}")
         if std_out is not None:
@@ -128,7 +136,7 @@ def denoise_image_diffusion(model_path: Optional[str], test_image_path: str, dev
         if quantiles is not None:
             np.save(quantiles_out, ens.quantiles.reshape(len(quantiles), img_size, img_size).cpu().numpy())
     else:
-        denoised = diffusion.denoise(input_tensor, inference_steps=inference_steps, **kw)
+        denoised = diffusion.denoise(input_tensor, inference_steps=inference_steps, **kw, **rule)
     if device.type == "cuda":
         torch.cuda.synchronize(device)
     print(f"Inference time: {time.time() - start_time:.2f} seconds")
@@ -166,15 +174,25 @@ def main(argv=None) -> None:
     ap.add_argument("--self-ensemble", nargs="?", const="auto", default=None, choices=["auto", "flips", "d4"],
                     help="both variants: save the mean over the flipped and rotated views of the image (auto: all 8); --std-out and "
                          "--quantiles / --quantiles-out then describe the views")
+    ap.add_argument("--update", default="reference", choices=["reference", "ddim"],
+                    help="the sampler's update rule: reference (one-step ancestral, the default) or ddim (stride-aware DDIM(eta) step)")
+    ap.add_argument("--eta", type=float, default=0.0, help="with --update ddim: 0 (deterministic, the default) .. 1 (ancestral)")
+    ap.add_argument("--no-clip-x0", action="store_true", help="with --update ddim: do not clip the predicted image to [0, 1]")
     args = ap.parse_args(argv)
+    if args.update == "reference" and (args.eta != 0.0 or args.no_clip_x0):
+        ap.error("--eta and --no-clip-x0 need --update ddim")
+    if not 0.0 <= args.eta <= 1.0:
+        ap.error("--eta needs a value in [0, 1]")
+    if args.update == "ddim" and args.self_ensemble is not None:
+        ap.error("--update ddim cannot be combined with --self-ensemble")
     if args.self_ensemble is not None and args.samples is not None:
         ap.error("--self-ensemble cannot be combined with --samples")
     if args.self_ensemble is not None and args.tile is not None:
         ap.error("--self-ensemble cannot be combined with --tile")
     if args.tile is not None and (args.tile < 1 or args.samples is not None):
         ap.error("--tile needs N >= 1 and cannot be combined with --samples")
-    if args.samples is not None and (args.samples < 1 or args.variant != "cddpm"):
-        ap.error("--samples needs K >= 1 and --variant cddpm")
+    if args.samples is not None and (args.samples < 1 or (args.variant != "cddpm" and not (args.update == "ddim" and args.eta > 0))):
+        ap.error("--samples needs K >= 1 and --variant cddpm (or --update ddim with --eta > 0)")
     if args.std_out is not None and args.self_ensemble is None and (args.samples is None or args.samples < 2):
         ap.error("--std-out needs --samples K with K >= 2")
     levels = None
@@ -190,7 +208,8 @@ def main(argv=None) -> None:
     restored = denoise_image_diffusion(args.checkpoint, args.image, device_type=args.device, img_size=args.img_size,
                                        inference_steps=args.inference_steps, variant=args.variant, seed=args.seed,
                                        samples=args.samples, std_out=args.std_out, tile=args.tile, overlap=args.overlap,
-                                       quantiles=levels, quantiles_out=args.quantiles_out, self_ensemble=args.self_ensemble)
+                                       quantiles=levels, quantiles_out=args.quantiles_out, self_ensemble=args.self_ensemble,
+                                       update=args.update, eta=args.eta, clip_x0=not args.no_clip_x0)
     restored.save(args.out, quality=95)
     print(f"\nResult saved: {args.out}")
 

@@ -17,11 +17,17 @@ struct StepNoise {
 };
 
 // the sampler's schedule as a caller gives it: the timestep rows (uniform: t[n]; mi_denoise_slots: a table t[n][B]) and the tables
-struct Schedule { const int32_t* t; int n; const float *beta, *alpha, *alpha_hat; int noise_steps; };
+// and the update rule of the uniform calls (include/midd.h: mi_update_rule; ddim == 0: the reference's)
+struct Schedule {
+    const int32_t* t; int n; const float *beta, *alpha, *alpha_hat; int noise_steps;
+    int ddim = 0; double eta = 0.0; int clip_x0 = 1;
+};
 
 struct StepIO {
     const float* x; const float* cond; float* eps_out;
     float* x_update; const float* noise; float c1, c2, c3; int clamp_eps;
+    // ddim != 0: the update is the DDIM(eta) rule with this row of the coefficient table (out_conv_ddim_launch); c1 .. c3 are not read
+    int ddim; DdimCoef coef;
     // sn.seeded: the update draws its noise term (step_noise_common.h) for iteration `iter`, sample 0 of THIS program being virtual
     // sample sn.v0; a step that draws nothing keeps the defaults (sn.tensor is not read: `noise` is this step's slice of it)
     int iter; StepNoise sn;
@@ -138,7 +144,7 @@ static int run_program(mi_plan* p, Program* g, const StepIO& io, char* ws, int* 
                 a.seeded = n.seeded; a.iter = io.iter; a.seed = n.seed; a.sample_offset = n.sample_offset;
                 a.v0 = n.v0; a.members = n.members > 0 ? n.members : 1; a.member_offset = n.member_offset;
                 a.tiles_x = n.tiles_x; a.tiles_y = n.tiles_y; a.img_H = n.img_H; a.img_W = n.img_W;
-                e = io.slots ? out_conv_slots_launch(a, io.slots, s) : out_conv_launch(a, s);
+                e = io.slots ? out_conv_slots_launch(a, io.slots, s) : io.ddim ? out_conv_ddim_launch(a, io.coef, s) : out_conv_launch(a, s);
                 break;
             }
         }
@@ -152,8 +158,9 @@ static int run_program(mi_plan* p, Program* g, const StepIO& io, char* ws, int* 
             mi_plan::Span sp; sp.a = ev_a; sp.b = ev_b;
             op_work(p, g, o, &sp.name, &sp.flops, &sp.bytes);
             const size_t oc_at = sp.name.find("out_conv_kernel");
-            if (o.kind == OP_OUT && (io.sn.seeded || io.slots) && oc_at != std::string::npos)      // the symbol that ran
-                sp.name.replace(oc_at, 15, io.slots ? "out_conv_slots_kernel" : "out_conv_seeded_kernel");
+            if (o.kind == OP_OUT && (io.sn.seeded || io.slots || io.ddim) && oc_at != std::string::npos)      // the symbol that ran
+                sp.name.replace(oc_at, 15, io.slots ? "out_conv_slots_kernel" : io.ddim ? (io.sn.seeded ? "out_conv_ddim_seeded_kernel" : "out_conv_ddim_kernel")
+                                                                             : "out_conv_seeded_kernel");
             static const bool per_op = getenv("MIDD_PROFILE_PER_OP") != nullptr;      // one entry per op instead of per symbol
             if (per_op) {
                 char tag[96];
@@ -191,13 +198,66 @@ static int check_call(mi_plan* plan, int B, int H, int W, void* ws, size_t ws_by
     return check_device(plan);
 }
 
+// every entry of a timestep list indexes the schedule's tables (check_schedule, check_ddim)
+static int check_t_list(const int32_t* t, int n, int noise_steps) {
+    for (int i = 0; i < n; ++i)
+        if (t[i] < 0 || t[i] >= noise_steps) return fail(MI_EINVAL, "t_list[%d]=%d outside [0,%d)", i, t[i], noise_steps);
+    return MI_OK;
+}
+
 // the sampler's host-side arguments (mi_denoise*, and the batched calls before their first pass)
 static int check_schedule(mi_plan* plan, const Schedule& sc) {
     if ((sc.n > 0 && !sc.t) || !sc.beta || !sc.alpha || !sc.alpha_hat) return fail(MI_EINVAL, "null argument");
     if (sc.n < 0 || sc.noise_steps < 1 || sc.noise_steps > plan->time_rows)
         return fail(MI_EINVAL, "noise_steps %d exceeds the precomputed time table (%d rows)", sc.noise_steps, plan->time_rows);
-    for (int i = 0; i < sc.n; ++i)
-        if (sc.t[i] < 0 || sc.t[i] >= sc.noise_steps) return fail(MI_EINVAL, "t_list[%d]=%d outside [0,%d)", i, sc.t[i], sc.noise_steps);
+    return check_t_list(sc.t, sc.n, sc.noise_steps);
+}
+
+// THE DDIM UPDATE, host side (include/midd.h): row i of the coefficient table of a list, in double precision from the caller's
+// fp32 table, every value rounded once to fp32.  A = alpha_hat[t_i], P = alpha_hat[t_{i+1}], 1 after the last entry.  The one
+// place that computes it: mi_ddim_coefficients exports it, enqueue_run passes its rows to the update kernel.
+static void ddim_row(const int32_t* t, int n, const float* alpha_hat, double eta, int i, float out[7]) {
+#pragma clang fp contract(off)
+    const double A = (double)alpha_hat[t[i]], P = i + 1 < n ? (double)alpha_hat[t[i + 1]] : 1.0;
+    const double sigma = eta * std::sqrt((1.0 - P) / (1.0 - A)) * std::sqrt(1.0 - A / P);
+    const double rest = (1.0 - P) - sigma * sigma;
+    out[0] = (float)(1.0 / std::sqrt(A)); out[1] = (float)std::sqrt(1.0 - A); out[2] = (float)std::sqrt(A); out[3] = (float)(1.0 / std::sqrt(1.0 - A));
+    out[4] = (float)std::sqrt(P); out[5] = (float)std::sqrt(rest > 0.0 ? rest : 0.0); out[6] = (float)(2.0 * sigma);
+}
+
+// the rule's own argument rules, host only and before anything else of a call: eta, the list, the table entries the list reads
+static int check_ddim(const int32_t* t, int n, const float* alpha_hat, int noise_steps, double eta) {
+    if (!(eta >= 0.0 && eta <= 1.0)) return fail(MI_EINVAL, "eta %.17g outside [0, 1] (limit: 0 <= eta <= 1, not NaN)", eta);
+    if (n < 0 || (n > 0 && !t) || !alpha_hat) return fail(MI_EINVAL, "null argument");
+    if (noise_steps < 1) return fail(MI_EINVAL, "noise_steps %d: a schedule has at least one step (limit: noise_steps >= 1)", noise_steps);
+    if (int rc = check_t_list(t, n, noise_steps)) return rc;
+    for (int i = 1; i < n; ++i) {
+        if (t[i] >= t[i - 1])
+            return fail(MI_EINVAL, "t_list[%d]=%d after t_list[%d]=%d: the DDIM update jumps from each timestep to the next one of the list "
+                        "(limit: a strictly decreasing list)", i, t[i], i - 1, t[i - 1]);
+    }
+    for (int i = 0; i < n; ++i) {
+        const double A = (double)alpha_hat[t[i]], P = i + 1 < n ? (double)alpha_hat[t[i + 1]] : 1.0;
+        if (!(A > 0.0 && A < P && P <= 1.0))
+            return fail(MI_EINVAL, "alpha_hat[%d]=%.9g, next %.9g: the DDIM update needs 0 < alpha_hat[t_i] < alpha_hat[t_{i+1}] <= 1", t[i], A, P);
+    }
+    return MI_OK;
+}
+
+extern "C" int mi_ddim_coefficients(const int32_t* t_list, int n_iters, const float* alpha_hat, int noise_steps, double eta, float* out) {
+    if (int rc = check_ddim(t_list, n_iters, alpha_hat, noise_steps, eta)) return rc;
+    if (n_iters > 0 && !out) return fail(MI_EINVAL, "null argument");
+    for (int i = 0; i < n_iters; ++i) ddim_row(t_list, n_iters, alpha_hat, eta, i, out + (size_t)i * 7);
+    return MI_OK;
+}
+
+// A call's rule -> its Schedule.  NULL or kind MI_UPDATE_REFERENCE: the schedule stays the reference's.  Judged first in every
+// *_rule call, so a bad rule or list is MI_EINVAL whatever the plan's state.
+static int apply_rule(const mi_update_rule* rule, Schedule* sc) {
+    if (!rule || rule->kind == MI_UPDATE_REFERENCE) return MI_OK;
+    if (rule->kind != MI_UPDATE_DDIM) return fail(MI_EINVAL, "unknown update rule %d (MI_UPDATE_REFERENCE or MI_UPDATE_DDIM)", (int)rule->kind);
+    if (int rc = check_ddim(sc->t, sc->n, sc->alpha_hat, sc->noise_steps, rule->eta)) return rc;
+    sc->ddim = 1; sc->eta = rule->eta; sc->clip_x0 = rule->clip_x0 ? 1 : 0;
     return MI_OK;
 }
 
@@ -330,9 +390,18 @@ static int enqueue_run(mi_plan* plan, Program* g, const float* noisy, float* x_o
                 } else {
                     const int t = sc.t[i];
                     HIPCHK(hipMemsetD32Async((hipDeviceptr_t)(wsh + gh->trow_off), t, Bh, sh));          // t = full((B,), i)
-                    coeffs(t, &io.c1, &io.c2, &io.c3);
-                    io.noise = (sn.tensor && t > 0) ? sn.tensor + (size_t)i * img_elems + h * part : nullptr;      // cddpmModels.py:297-300
-                    if (sn.seeded && t > 0) {                        // nothing is drawn at t == 0
+                    bool draws = t > 0;                              // nothing is drawn at t == 0
+                    if (sc.ddim) {
+                        float r[7];
+                        ddim_row(sc.t, n_iters, alpha_hat, sc.eta, i, r);
+                        io.ddim = 1;
+                        io.coef = DdimCoef{r[0], r[1], r[2], r[3], r[4], r[5], r[6], sc.clip_x0, i == n_iters - 1 ? 1 : 0};
+                        draws = r[6] > 0.0f;                         // nor at s == 0: every row at eta == 0, always the last one
+                    } else {
+                        coeffs(t, &io.c1, &io.c2, &io.c3);
+                    }
+                    io.noise = (sn.tensor && draws) ? sn.tensor + (size_t)i * img_elems + h * part : nullptr;      // cddpmModels.py:297-300
+                    if (sn.seeded && draws) {
                         io.iter = i; io.sn = sn;
                         io.sn.v0 += h * Bh;                          // sub-batch h: its first virtual index
                     }
@@ -402,6 +471,26 @@ extern "C" int mi_denoise_seeded(mi_plan* plan, const float* noisy, float* x_out
     sn.seeded = true; sn.seed = seed; sn.sample_offset = sample_offset;
     return denoise_run(plan, noisy, x_out, B, H, W, Schedule{t_list, n_iters, beta, alpha, alpha_hat, noise_steps}, sn, flags,
                        workspace, workspace_bytes, stream);
+}
+
+// mi_denoise and mi_denoise_seeded in one signature, with an update rule (NULL: the reference's, i.e. those two calls)
+extern "C" int mi_denoise_rule(mi_plan* plan, const float* noisy, float* x_out, int B, int H, int W,
+                               const int32_t* t_list, int n_iters,
+                               const float* beta, const float* alpha, const float* alpha_hat, int noise_steps,
+                               const float* step_noise, int seeded, uint64_t seed, int64_t sample_offset, int flags,
+                               const mi_update_rule* rule, void* workspace, size_t workspace_bytes, void* stream) {
+    Schedule sc{t_list, n_iters, beta, alpha, alpha_hat, noise_steps};
+    if (int rc = apply_rule(rule, &sc)) return rc;
+    StepNoise sn;
+    if (seeded) {
+        if (step_noise) return fail(MI_EINVAL, "seeded together with step_noise: the noise term is drawn or read, not both");
+        if (!plan) return fail(MI_EINVAL, "null plan");      // (as mi_denoise_seeded: the counter range needs the plan; unseeded, check_call answers)
+        if (int rc = check_step_noise_range(plan->cfg.in_channels, H, W, sample_offset)) return rc;
+        sn.seeded = true; sn.seed = seed; sn.sample_offset = sample_offset;
+    } else {
+        sn.tensor = step_noise;
+    }
+    return denoise_run(plan, noisy, x_out, B, H, W, sc, sn, flags, workspace, workspace_bytes, stream);
 }
 
 // ---------------------------------------------------------------------------- per-slot timesteps (continuous batching)
@@ -600,12 +689,14 @@ static int run_passes(mi_plan* plan, Fill fill, float* store, int64_t V, int rou
     return MI_OK;
 }
 
-extern "C" int mi_denoise_ensemble(mi_plan* plan, const float* noisy, float* mean_out, float* std_out, float* samples_out,
-                                   int B, int members, int H, int W,
-                                   const int32_t* t_list, int n_iters,
-                                   const float* beta, const float* alpha, const float* alpha_hat, int noise_steps,
-                                   uint64_t seed, int64_t sample_offset, int64_t member_offset, int pass_samples, int flags,
-                                   void* workspace, size_t workspace_bytes, void* stream) {
+extern "C" int mi_denoise_ensemble_rule(mi_plan* plan, const float* noisy, float* mean_out, float* std_out, float* samples_out,
+                                        int B, int members, int H, int W,
+                                        const int32_t* t_list, int n_iters,
+                                        const float* beta, const float* alpha, const float* alpha_hat, int noise_steps,
+                                        uint64_t seed, int64_t sample_offset, int64_t member_offset, int pass_samples, int flags,
+                                        const mi_update_rule* rule, void* workspace, size_t workspace_bytes, void* stream) {
+    Schedule sc{t_list, n_iters, beta, alpha, alpha_hat, noise_steps};
+    if (int rc = apply_rule(rule, &sc)) return rc;
     if (int rc = check_ensemble_args(plan, B, members, H, W, sample_offset, member_offset, pass_samples)) return rc;
     if (!mean_out && !std_out && !samples_out) return fail(MI_EINVAL, "no output: give at least one of mean_out, std_out, samples_out");
     if (int rc = check_std_members(std_out, members)) return rc;
@@ -614,7 +705,6 @@ extern "C" int mi_denoise_ensemble(mi_plan* plan, const float* noisy, float* mea
                         {samples_out, (size_t)B * members * img, "samples_out"}};
     if (int rc = check_no_overlap(buf, 4, "noisy is read every step and the reduce reads samples_out while it writes mean_out and std_out"))
         return rc;
-    const Schedule sc{t_list, n_iters, beta, alpha, alpha_hat, noise_steps};
     EnsembleLayout L{};
     // (evaluated before the state check, reported after it: check_batched_call; host arithmetic only, as in the *_workspace_bytes queries)
     const int layout_rc = ensemble_layout(plan, B, members, H, W, pass_samples, samples_out != nullptr, &L);
@@ -630,6 +720,16 @@ extern "C" int mi_denoise_ensemble(mi_plan* plan, const float* noisy, float* mea
     if (int rc = run_passes(plan, broadcast, samples, (int64_t)B * members, 1, H, W, chw, L, sn, sc, flags, ws, stream)) return rc;
     if (mean_out || std_out) return launched(ensemble_reduce_launch(samples, B, members, chw, mean_out, std_out, s), "ensemble_reduce");
     return MI_OK;
+}
+
+extern "C" int mi_denoise_ensemble(mi_plan* plan, const float* noisy, float* mean_out, float* std_out, float* samples_out,
+                                   int B, int members, int H, int W,
+                                   const int32_t* t_list, int n_iters,
+                                   const float* beta, const float* alpha, const float* alpha_hat, int noise_steps,
+                                   uint64_t seed, int64_t sample_offset, int64_t member_offset, int pass_samples, int flags,
+                                   void* workspace, size_t workspace_bytes, void* stream) {
+    return mi_denoise_ensemble_rule(plan, noisy, mean_out, std_out, samples_out, B, members, H, W, t_list, n_iters, beta, alpha, alpha_hat,
+                                    noise_steps, seed, sample_offset, member_offset, pass_samples, flags, nullptr, workspace, workspace_bytes, stream);
 }
 
 // ---------------------------------------------------------------------------- tiled denoising of full-resolution images
@@ -698,12 +798,14 @@ extern "C" int mi_tile_blend(const float* tiles, int B, int C, int H, int W, int
     return launched(tile_blend_launch(tiles, out, B, g, (hipStream_t)stream), "tile_blend");
 }
 
-extern "C" int mi_denoise_tiled(mi_plan* plan, const float* noisy, float* image_out, float* tiles_out,
-                                int B, int H, int W, int th, int tw, int oy, int ox,
-                                const int32_t* t_list, int n_iters,
-                                const float* beta, const float* alpha, const float* alpha_hat, int noise_steps,
-                                int seeded, uint64_t seed, int64_t sample_offset, int pass_samples, int flags,
-                                void* workspace, size_t workspace_bytes, void* stream) {
+extern "C" int mi_denoise_tiled_rule(mi_plan* plan, const float* noisy, float* image_out, float* tiles_out,
+                                     int B, int H, int W, int th, int tw, int oy, int ox,
+                                     const int32_t* t_list, int n_iters,
+                                     const float* beta, const float* alpha, const float* alpha_hat, int noise_steps,
+                                     int seeded, uint64_t seed, int64_t sample_offset, int pass_samples, int flags,
+                                     const mi_update_rule* rule, void* workspace, size_t workspace_bytes, void* stream) {
+    Schedule sc{t_list, n_iters, beta, alpha, alpha_hat, noise_steps};
+    if (int rc = apply_rule(rule, &sc)) return rc;
     TileGeom tg{};
     if (int rc = check_tiled_args(plan, B, H, W, th, tw, oy, ox, sample_offset, pass_samples, &tg)) return rc;
     const int K = tg.ny * tg.nx;
@@ -711,7 +813,6 @@ extern "C" int mi_denoise_tiled(mi_plan* plan, const float* noisy, float* image_
     const Buf buf[3] = {{noisy, (size_t)B * img, "noisy"}, {image_out, (size_t)B * img, "image_out"},
                         {tiles_out, (size_t)B * K * chw * sizeof(float), "tiles_out"}};
     if (int rc = check_no_overlap(buf, 3, "noisy is read by every pass and the blend reads the tiles while it writes image_out")) return rc;
-    const Schedule sc{t_list, n_iters, beta, alpha, alpha_hat, noise_steps};
     EnsembleLayout L{};
     // (evaluated before the state check, reported after it: check_batched_call; host arithmetic only, as in the *_workspace_bytes queries)
     const int layout_rc = ensemble_layout(plan, B, K, th, tw, pass_samples, tiles_out != nullptr, &L);
@@ -729,6 +830,16 @@ extern "C" int mi_denoise_tiled(mi_plan* plan, const float* noisy, float* image_
     auto extract = [&](float* cond, int v0, int n) { return launched(tile_extract_launch(noisy, cond, tg, v0, n, s), "tile_extract"); };
     if (int rc = run_passes(plan, extract, tiles, (int64_t)B * K, 1, th, tw, chw, L, sn, sc, flags, ws, stream)) return rc;
     return launched(tile_blend_launch(tiles, image_out, B, tg, s), "tile_blend");
+}
+
+extern "C" int mi_denoise_tiled(mi_plan* plan, const float* noisy, float* image_out, float* tiles_out,
+                                int B, int H, int W, int th, int tw, int oy, int ox,
+                                const int32_t* t_list, int n_iters,
+                                const float* beta, const float* alpha, const float* alpha_hat, int noise_steps,
+                                int seeded, uint64_t seed, int64_t sample_offset, int pass_samples, int flags,
+                                void* workspace, size_t workspace_bytes, void* stream) {
+    return mi_denoise_tiled_rule(plan, noisy, image_out, tiles_out, B, H, W, th, tw, oy, ox, t_list, n_iters, beta, alpha, alpha_hat, noise_steps,
+                                 seeded, seed, sample_offset, pass_samples, flags, nullptr, workspace, workspace_bytes, stream);
 }
 
 // ---------------------------------------------------------------------------- ensembles of tiled runs

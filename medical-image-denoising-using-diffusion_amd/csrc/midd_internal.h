@@ -233,6 +233,17 @@ constexpr int SLOTS_PER_LAUNCH = 32;
 struct SlotRecs { SlotRec v[SLOTS_PER_LAUNCH]; };      // 1 KiB of kernel arguments
 hipError_t slot_fill_launch(int* trow, SlotRec* dst, const SlotRecs& recs, int n, hipStream_t s);
 hipError_t out_conv_slots_launch(const OutConvArgs& a, const SlotRec* slots, hipStream_t s);
+// The DDIM(eta) update (include/midd.h: THE DDIM UPDATE): one row of the host's coefficient table and the launch-uniform switches,
+// a kernel argument of out_conv_ddim_kernel / out_conv_ddim_seeded_kernel alone (scalar loads).  OutConvArgs does not grow:
+// a.c1 .. a.c3 are not read by these kernels, everything else is.
+struct DdimCoef {
+    float k0, k1, r0, r1, a, b, s;  // 1/sqrt(A), sqrt(1-A), sqrt(A), 1/sqrt(1-A), sqrt(P), sqrt(max(0, 1-P-sigma^2)), 2 sigma
+    int clip_x0;                    // clip the predicted image to [0, 1] and re-derive eps
+    int last;                       // last row of the list: the result is clamped to [0, 1]
+};
+// a.seeded != 0 (host: only with k.s > 0): the term s * noise is drawn as out_conv_seeded_kernel draws it; else it is read from
+// a.noise when that is given and k.s > 0
+hipError_t out_conv_ddim_launch(const OutConvArgs& a, const DdimCoef& k, hipStream_t s);
 // dst [n_iters][B][chw] <- the 0.5-scaled seeded step noise of `member` (step_noise_common.h); chw < 2^32, B and n_iters <= 65535
 hipError_t step_noise_fill_launch(float* dst, int n_iters, int B, unsigned long long chw, unsigned long long seed, long long sample_offset,
                                   unsigned member, hipStream_t s);

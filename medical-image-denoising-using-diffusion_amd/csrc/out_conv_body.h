@@ -9,11 +9,17 @@
 // and whether the sample is updated at all come from the sample's SlotRec (midd_internal.h) instead of the arguments -- every
 // sample of the launch is at its own timestep.  b is per workgroup, so the record is read with scalar loads; the workgroups of
 // an idle slot leave at once: nothing is staged, drawn or written.  The other two compiles do not see a token of it.
+// Two more, MIDD_OUT_DDIM 1 = out_conv_ddim_kernel (MIDD_OUT_SEEDED 0) and out_conv_ddim_seeded_kernel (1): the DDIM(eta) update of
+// include/midd.h (THE DDIM UPDATE) in the place of the reference's, its coefficients in a kernel argument of their own (DdimCoef,
+// scalar loads).  The three compiles above do not see a token of it either.
 template <int IC>
 __global__ __launch_bounds__(256)
 void MIDD_OUT_KERNEL(const OutConvArgs a, const float* __restrict__ wglob /* == a.w: a restrict parameter of its own, so that uniform reads become scalar loads */
 #if MIDD_OUT_SLOTS
                      , const SlotRec* __restrict__ slots /* [a.B] */
+#endif
+#if MIDD_OUT_DDIM
+                     , const DdimCoef k
 #endif
                      ) {
     __shared__ __attribute__((aligned(16))) float tile[OC_I * OC_I * OC_PS];
@@ -139,6 +145,40 @@ void MIDD_OUT_KERNEL(const OutConvArgs a, const float* __restrict__ wglob /* == 
                 }
             }
             a.x[o] = fminf(fmaxf(xn, 0.0f), 1.0f);
+        }
+#elif MIDD_OUT_DDIM
+        if (a.x) {
+            // THE DDIM UPDATE (include/midd.h), fp32, every operation rounded on its own: no contraction in this block, so the
+            // seeded and the tensor form round s * noise alike and tests/ddim_update_reference.py restates it bit for bit.
+#pragma clang fp contract(off)
+            if (a.clamp_eps) eps = fminf(fmaxf(eps, -5.0f), 5.0f);
+            const float x = a.x[o];
+            float x0 = k.k0 * (x - k.k1 * eps);
+            if (k.clip_x0) {
+                const float c = fminf(fmaxf(x0, 0.0f), 1.0f);
+                if (c != x0) eps = (x - k.r0 * c) * k.r1;      // eps re-derived: x_prev stays on the trajectory towards the clipped image
+                x0 = c;
+            }
+            float xn = k.a * x0 + k.b * eps;
+            if (k.s > 0.0f) {                                  // (launch-uniform: nothing is drawn or read at s == 0)
+                if constexpr (MIDD_OUT_SEEDED) {
+                    // the virtual sample and the element index of out_conv_seeded_kernel below, word for word
+                    const uint32_t v = (uint32_t)a.v0 + (uint32_t)b, vi = v / (uint32_t)a.members;
+                    uint32_t pitch = (uint32_t)a.W, plane = (uint32_t)a.H * (uint32_t)a.W, origin = 0, member = v - vi * (uint32_t)a.members;
+                    if (a.tiles_x) {
+                        const int ky = (int)member / a.tiles_x, kx = (int)member - ky * a.tiles_x;
+                        pitch = (uint32_t)a.img_W; plane = (uint32_t)a.img_H * (uint32_t)a.img_W;
+                        origin = (uint32_t)tile_origin(ky, a.img_H, a.H, a.tiles_y) * pitch + (uint32_t)tile_origin(kx, a.img_W, a.W, a.tiles_x);
+                        member = 0;
+                    }
+                    const uint32_t elem = (uint32_t)oc * plane + (uint32_t)oy * pitch + (uint32_t)ox + origin;
+                    xn = xn + k.s * step_noise_value(a.seed, a.sample_offset + vi, a.iter, elem, a.member_offset + member);
+                } else {
+                    if (a.noise) xn = xn + k.s * a.noise[o];
+                }
+            }
+            if (k.last) xn = fminf(fmaxf(xn, 0.0f), 1.0f);      // the call returns an image in [0, 1]; intermediate x is not clamped
+            a.x[o] = xn;
         }
 #else
         if (a.x) {

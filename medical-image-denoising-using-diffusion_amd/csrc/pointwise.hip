@@ -5,6 +5,7 @@
 //                      fused with the sampler update of DiffusionDenoiser.denoise
 //                      (DDIMModel.py:278-284; cddpm noise term cddpmModels.py:297-303)
 //   out_conv_seeded_kernel : the same with the noise term drawn in the update (step_noise_common.h)
+//   out_conv_ddim_kernel, out_conv_ddim_seeded_kernel : the same two with the DDIM(eta) update in the place of the reference's
 //   out_conv_slots_kernel  : the same with every sample at its own timestep: coefficients, counter words and the active
 //                      flag from the sample's SlotRec (mi_denoise_slots); slot_fill_kernel writes a row's records
 //   step_noise_fill_kernel : the same noise values as a [n_iters,B,C,H,W] tensor (replay / export)
@@ -359,6 +360,7 @@ constexpr int OC_PS = 20;         // padded pixel stride in floats
 // only known at run time hipcc indexes the accumulators through select chains and splits the 16-byte LDS reads:
 // 7 340 instructions, 989 v_cndmask among them, for a loop of 432 multiply-adds (round 3; tools/isa_count.py).
 #define MIDD_OUT_SLOTS 0
+#define MIDD_OUT_DDIM 0
 #define MIDD_OUT_KERNEL out_conv_kernel
 #define MIDD_OUT_SEEDED 0
 #include "out_conv_body.h"
@@ -378,6 +380,22 @@ constexpr int OC_PS = 20;         // padded pixel stride in floats
 #undef MIDD_OUT_KERNEL
 #undef MIDD_OUT_SEEDED
 #undef MIDD_OUT_SLOTS
+#undef MIDD_OUT_DDIM
+// the DDIM(eta) update (include/midd.h: THE DDIM UPDATE): its tensor-noise and its seeded form, coefficients in a DdimCoef argument
+#define MIDD_OUT_SLOTS 0
+#define MIDD_OUT_DDIM 1
+#define MIDD_OUT_KERNEL out_conv_ddim_kernel
+#define MIDD_OUT_SEEDED 0
+#include "out_conv_body.h"
+#undef MIDD_OUT_KERNEL
+#undef MIDD_OUT_SEEDED
+#define MIDD_OUT_KERNEL out_conv_ddim_seeded_kernel
+#define MIDD_OUT_SEEDED 1
+#include "out_conv_body.h"
+#undef MIDD_OUT_KERNEL
+#undef MIDD_OUT_SEEDED
+#undef MIDD_OUT_SLOTS
+#undef MIDD_OUT_DDIM
 
 hipError_t out_conv_launch(const OutConvArgs& a, hipStream_t s) {
     if (a.ic > 4 || a.C % 16) return hipErrorInvalidValue;
@@ -403,6 +421,22 @@ hipError_t out_conv_slots_launch(const OutConvArgs& a, const SlotRec* slots, hip
     const int tiles = ((a.W + OC_T - 1) / OC_T) * ((a.H + OC_T - 1) / OC_T);
     if (a.ic == 1) hipLaunchKernelGGL(out_conv_slots_kernel<1>, dim3(a.B * tiles), dim3(256), lds, s, a, a.w, slots);
     else hipLaunchKernelGGL(out_conv_slots_kernel<0>, dim3(a.B * tiles), dim3(256), lds, s, a, a.w, slots);
+    return hipGetLastError();
+}
+
+// a.c1 .. a.c3 are not read.  The seeded form is launched only when a term is drawn at all (a.seeded: the host sets it with k.s > 0)
+hipError_t out_conv_ddim_launch(const OutConvArgs& a, const DdimCoef& k, hipStream_t s) {
+    if (a.ic > 4 || a.C % 16 || !a.x) return hipErrorInvalidValue;
+    const size_t lds = ((size_t)a.ic * 9 * a.C + 2 * a.C) * sizeof(float);
+    const int tiles = ((a.W + OC_T - 1) / OC_T) * ((a.H + OC_T - 1) / OC_T);
+    if (a.seeded) {
+        if (a.noise || (unsigned long long)a.ic * a.H * a.W >= (1ull << 32) || a.members < 1 || a.v0 < 0) return hipErrorInvalidValue;
+        if (a.tiles_x && (a.tiles_x < 1 || a.tiles_y < 1 || a.members != a.tiles_x * a.tiles_y || a.img_H < a.H || a.img_W < a.W ||
+                          (unsigned long long)a.ic * a.img_H * a.img_W >= (1ull << 32))) return hipErrorInvalidValue;
+        if (a.ic == 1) hipLaunchKernelGGL(out_conv_ddim_seeded_kernel<1>, dim3(a.B * tiles), dim3(256), lds, s, a, a.w, k);
+        else hipLaunchKernelGGL(out_conv_ddim_seeded_kernel<0>, dim3(a.B * tiles), dim3(256), lds, s, a, a.w, k);
+    } else if (a.ic == 1) hipLaunchKernelGGL(out_conv_ddim_kernel<1>, dim3(a.B * tiles), dim3(256), lds, s, a, a.w, k);
+    else hipLaunchKernelGGL(out_conv_ddim_kernel<0>, dim3(a.B * tiles), dim3(256), lds, s, a, a.w, k);
     return hipGetLastError();
 }
 

@@ -273,14 +273,19 @@ class UNetDiffusion(nn.Module):
     @torch.no_grad()
     def run_sampler(self, noisy: torch.Tensor, t_list, beta: torch.Tensor, alpha: torch.Tensor,
                     alpha_hat: torch.Tensor, clamp_eps: bool, step_noise: Optional[torch.Tensor] = None,
-                    no_split: bool = False, seed: Optional[int] = None, sample_offset: int = 0, member: int = 0) -> torch.Tensor:
+                    no_split: bool = False, seed: Optional[int] = None, sample_offset: int = 0, member: int = 0, *,
+                    update: str = "reference", eta: float = 0.0, clip_x0: bool = True) -> torch.Tensor:
         """The whole reverse loop in one native call (used by DiffusionDenoiser.denoise).
+
+        update, eta, clip_x0: the update rule (sampler.check_update; include/midd.h: THE DDIM UPDATE).  "reference" runs the calls
+        below unchanged; "ddim" runs mi_denoise_rule, whose noise term -- ``step_noise`` or ``seed`` -- is added where s > 0.
 
         seed: the noise term of every t > 0 update is drawn on the device from (seed, sample_offset + b, iteration, element)
         (mi_denoise_seeded) instead of read from ``step_noise``; the two are exclusive.
         member (with seed): which draw of every image; 0 is the plain seeded run, m > 0 is member m of an ensemble, run alone
         through mi_denoise_ensemble's single-member form."""
-        from .sampler import check_member, check_seed
+        from .sampler import check_member, check_seed, check_update
+        rule = check_update(update, eta, clip_x0)
         member = check_member(member)
         if seed is not None:
             if step_noise is not None:
@@ -289,7 +294,8 @@ class UNetDiffusion(nn.Module):
             if member:
                 _, _, samples = self.run_ensemble(noisy, t_list, beta, alpha, alpha_hat, clamp_eps, members=1, seed=seed,
                                                   sample_offset=sample_offset, member_offset=member, max_batch=max(1, noisy.shape[0]),
-                                                  want_mean=False, want_std=False, want_samples=True, no_split=no_split)
+                                                  want_mean=False, want_std=False, want_samples=True, no_split=no_split,
+                                                  update=update, eta=eta, clip_x0=clip_x0)
                 return samples[:, 0]
         elif member:
             raise ValueError("member selects a draw of the seeded generator: pass seed as well")
@@ -302,7 +308,11 @@ class UNetDiffusion(nn.Module):
             out = torch.empty_like(src)
             head = (plan, src.data_ptr(), out.data_ptr(), B, H, W) + sched
             flags = self._call_flags(clamp_eps, no_split)
-            if seed is not None:
+            if rule is not None:
+                step_noise = self._step_noise(step_noise, sched[1], src, "n_iters")
+                fn, head = native.lib().mi_denoise_rule, head + (_ptr(step_noise), 0 if seed is None else 1, C.c_uint64(seed or 0),
+                                                                 C.c_int64(sample_offset if seed is not None else 0), flags, C.byref(rule))
+            elif seed is not None:
                 fn, head = native.lib().mi_denoise_seeded, head + (C.c_uint64(seed), C.c_int64(sample_offset), flags)
             else:
                 step_noise = self._step_noise(step_noise, sched[1], src, "n_iters")
@@ -322,13 +332,15 @@ class UNetDiffusion(nn.Module):
     @torch.no_grad()
     def run_slots(self, cond: torch.Tensor, x: torch.Tensor, t_rows, beta: torch.Tensor, alpha: torch.Tensor, alpha_hat: torch.Tensor,
                   clamp_eps: bool, iter_base=None, sample_index=None, step_noise: Optional[torch.Tensor] = None,
-                  seed: Optional[int] = None, no_split: bool = False, max_slots: Optional[int] = None) -> torch.Tensor:
+                  seed: Optional[int] = None, no_split: bool = False, max_slots: Optional[int] = None, *,
+                  update: str = "reference") -> torch.Tensor:
         """The sampler loop with per-slot timesteps (mi_denoise_slots): ``t_rows`` [n_rows][B] holds every slot's timestep per row,
         -1 = idle.  ``x`` [B,C,H,W] is updated IN PLACE (and returned) and is not initialised: a caller starting a slot copies its
         condition image into it; both tensors must be contiguous.  ``iter_base`` [B]: rows a slot has already run;
         ``sample_index`` [B]: its global image index (seeded noise).  ``max_slots``: the workspace is sized for every batch up to
         this many slots and kept, so that a session whose batch changes from call to call allocates once."""
-        from .sampler import check_seed
+        from .sampler import check_seed, refuse_update
+        refuse_update(update, "run_slots (mi_denoise_slots)")
         if seed is not None:
             if step_noise is not None:
                 raise ValueError("pass either seed or step_noise, not both")
@@ -374,11 +386,12 @@ class UNetDiffusion(nn.Module):
     def run_ensemble(self, noisy: torch.Tensor, t_list, beta: torch.Tensor, alpha: torch.Tensor, alpha_hat: torch.Tensor,
                      clamp_eps: bool, members: int, seed: int, sample_offset: int = 0, member_offset: int = 0,
                      max_batch: int = 16, want_mean: bool = True, want_std: bool = True, want_samples: bool = False,
-                     no_split: bool = False):
+                     no_split: bool = False, *, update: str = "reference", eta: float = 0.0, clip_x0: bool = True):
         """``members`` seeded draws per image in one native call (mi_denoise_ensemble) -> (mean, std, samples), each None when
         not asked for.  The B * members (image, member) pairs run through the sampler loop in passes of at most ``max_batch``;
-        samples is [B, members, C, H, W]."""
-        from .sampler import check_members, check_seed
+        samples is [B, members, C, H, W].  update, eta, clip_x0: the update rule, as in run_sampler (mi_denoise_ensemble_rule)."""
+        from .sampler import check_members, check_seed, check_update
+        rule = check_update(update, eta, clip_x0)
         seed, sample_offset = check_seed(seed, sample_offset)
         members, member_offset, max_batch = check_members(members, member_offset, max_batch)
         want_std = want_std and members >= 2
@@ -398,24 +411,25 @@ class UNetDiffusion(nn.Module):
             size = (B, members, H, W, pass_samples)
             ws = self._resident_workspace("_ensemble_ws", size + (want_samples, dev.index, torch.cuda.current_stream(dev).cuda_stream),
                                           lambda: native.lib().mi_ensemble_workspace_bytes(self._plan, *size, 1 if want_samples else 0), dev)
-            self._invoke(native.lib().mi_denoise_ensemble,
+            self._invoke(native.lib().mi_denoise_ensemble if rule is None else native.lib().mi_denoise_ensemble_rule,
                          (plan, src.data_ptr(), _ptr(mean), _ptr(std), _ptr(samples), B, members, H, W) + sched
                          + (C.c_uint64(seed), C.c_int64(sample_offset), C.c_int64(member_offset), pass_samples,
-                            self._call_flags(clamp_eps, no_split)), ws, dev)
+                            self._call_flags(clamp_eps, no_split)) + (() if rule is None else (C.byref(rule),)), ws, dev)
         return mean, std, samples
 
     @torch.no_grad()
     def run_self_ensemble(self, noisy: torch.Tensor, t_list, beta: torch.Tensor, alpha: torch.Tensor, alpha_hat: torch.Tensor,
                           clamp_eps: bool, views="auto", seed: Optional[int] = None, sample_offset: int = 0, member_offset: int = 0,
                           max_batch: int = 16, want_mean: bool = True, want_std: bool = True, want_samples: bool = False,
-                          no_split: bool = False, levels=None):
+                          no_split: bool = False, levels=None, *, update: str = "reference"):
         """The flipped and rotated views of every image in one native call (mi_denoise_self_ensemble) -> (mean, std, samples,
         codes, maps), each tensor None when not asked for.  The B * views (image, view) pairs run through the sampler loop in
         passes of at most ``max_batch``; samples is [B, views, C, H, W], every member turned back into the image's frame.  seed
         None: no noise term (DDIM); else view k draws as member ``member_offset + k`` of the seeded generator.  ``levels``
         (checked quantile levels): one mi_dihedral_quantiles launch follows on the same stream, reading the view outputs where
         the call left them -- the tail of its workspace (include/midd.h) -- so no member tensor exists for it."""
-        from .sampler import _levels_arg, check_members, check_seed, view_codes
+        from .sampler import _levels_arg, check_members, check_seed, refuse_update, view_codes
+        refuse_update(update, "run_self_ensemble (mi_denoise_self_ensemble)")
         if seed is not None:
             seed, _ = check_seed(seed, 0)
         _, sample_offset = check_seed(0, sample_offset)
@@ -466,10 +480,12 @@ class UNetDiffusion(nn.Module):
     @torch.no_grad()
     def run_tiled(self, noisy: torch.Tensor, t_list, beta: torch.Tensor, alpha: torch.Tensor, alpha_hat: torch.Tensor,
                   clamp_eps: bool, tile, overlap, seed: Optional[int] = None, sample_offset: int = 0, max_batch: int = 16,
-                  want_tiles: bool = False, no_split: bool = False):
+                  want_tiles: bool = False, no_split: bool = False, *, update: str = "reference", eta: float = 0.0, clip_x0: bool = True):
         """Images of any size >= the tile as blended overlapping tiles in one native call (mi_denoise_tiled) ->
-        (image, tiles or None, TilePlan).  seed None: no noise term (DDIM)."""
-        from .sampler import check_member, check_seed, tiling
+        (image, tiles or None, TilePlan).  seed None: no noise term (DDIM).  update, eta, clip_x0: the update rule, as in
+        run_sampler (mi_denoise_tiled_rule)."""
+        from .sampler import check_member, check_seed, check_update, tiling
+        rule = check_update(update, eta, clip_x0)
         if seed is not None:
             seed, sample_offset = check_seed(seed, sample_offset)
         max_batch = check_member(max_batch, "max_batch", low=1)
@@ -485,22 +501,23 @@ class UNetDiffusion(nn.Module):
             tiles = torch.empty((B, K, Cc, th, tw), dtype=torch.float32, device=dev) if want_tiles else None
             pass_samples = min(max_batch, max(1, B * K))
             ws = self._tiled_workspace((B, H, W, th, tw, oy, ox, pass_samples, 1 if want_tiles else 0), dev)
-            self._invoke(native.lib().mi_denoise_tiled,
+            self._invoke(native.lib().mi_denoise_tiled if rule is None else native.lib().mi_denoise_tiled_rule,
                          (plan, src.data_ptr(), image.data_ptr(), _ptr(tiles), B, H, W, th, tw, oy, ox) + sched
                          + (0 if seed is None else 1, C.c_uint64(seed or 0), C.c_int64(sample_offset), pass_samples,
-                            self._call_flags(clamp_eps, no_split)), ws, dev)
+                            self._call_flags(clamp_eps, no_split)) + (() if rule is None else (C.byref(rule),)), ws, dev)
         return image, tiles, plan_t
 
     @torch.no_grad()
     def run_tiled_ensemble(self, noisy: torch.Tensor, t_list, beta: torch.Tensor, alpha: torch.Tensor, alpha_hat: torch.Tensor,
                            clamp_eps: bool, tile, overlap, members: int, seed: int, sample_offset: int = 0, member_offset: int = 0,
                            max_batch: int = 16, want_mean: bool = True, want_std: bool = True, want_samples: bool = False,
-                           want_tiles: bool = False, no_split: bool = False):
+                           want_tiles: bool = False, no_split: bool = False, *, update: str = "reference"):
         """``members`` seeded draws of images of any size >= the tile in one native call (mi_denoise_tiled_ensemble) ->
         (mean, std, samples, tiles, TilePlan), each tensor None when not asked for.  Members are the outer loop; inside a member
         the B * tiles crops run in passes of at most ``max_batch``, as run_tiled runs them.  samples is [B, members, C, H, W],
         tiles [members, B, ny * nx, C, th, tw]."""
-        from .sampler import check_members, check_seed, tiling
+        from .sampler import check_members, check_seed, refuse_update, tiling
+        refuse_update(update, "run_tiled_ensemble (mi_denoise_tiled_ensemble)")
         seed, sample_offset = check_seed(seed, sample_offset)
         members, member_offset, max_batch = check_members(members, member_offset, max_batch)
         want_std = want_std and members >= 2

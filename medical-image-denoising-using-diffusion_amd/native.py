@@ -20,6 +20,7 @@ MI_NO_SPLIT = 2
 MI_COMPUTE = {"f32": 0, "f16x3": 1, "f16": 2}
 MI_STATUS_NONFINITE, MI_STATUS_FP16_RANGE = 1, 2
 MI_COMPUTE_BATCH_INVARIANT = 0x100          # include/midd.h: OR into compute_mode
+MI_UPDATE = {"reference": 0, "ddim": 1}     # include/midd.h: mi_update_rule.kind
 
 
 class NativeLibraryError(RuntimeError):
@@ -37,6 +38,11 @@ class UNetCfg(C.Structure):
                 ("channel_mult", C.c_int32 * MI_MAX_LEVELS), ("num_res_blocks", C.c_int32),
                 ("num_attention_levels", C.c_int32), ("attention_levels", C.c_int32 * MI_MAX_LEVELS),
                 ("time_emb_dim", C.c_int32), ("variant", C.c_int32), ("compute_mode", C.c_int32)]
+
+
+class UpdateRule(C.Structure):
+    """mi_update_rule (include/midd.h: THE DDIM UPDATE)."""
+    _fields_ = [("kind", C.c_int32), ("eta", C.c_double), ("clip_x0", C.c_int32)]
 
 
 class ProfileEntry(C.Structure):
@@ -97,6 +103,18 @@ SYMBOLS = [
                                           [C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int,
                                            C.c_int, C.c_uint64, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
     ("mi_self_ensemble_workspace_bytes", C.c_size_t, [C.c_void_p] + [C.c_int] * 6),
+    ("mi_ddim_coefficients", C.c_int, [C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_float), C.c_int, C.c_double, C.POINTER(C.c_float)]),
+    ("mi_denoise_rule", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                  C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                  C.POINTER(C.c_float), C.c_int, C.c_void_p, C.c_int, C.c_uint64, C.c_int64, C.c_int,
+                                  C.POINTER(UpdateRule), C.c_void_p, C.c_size_t, C.c_void_p]),
+    ("mi_denoise_ensemble_rule", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                           C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                           C.POINTER(C.c_float), C.c_int, C.c_uint64, C.c_int64, C.c_int64, C.c_int, C.c_int,
+                                           C.POINTER(UpdateRule), C.c_void_p, C.c_size_t, C.c_void_p]),
+    ("mi_denoise_tiled_rule", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 7 +
+                                       [C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int,
+                                        C.c_int, C.c_uint64, C.c_int64, C.c_int, C.c_int, C.POINTER(UpdateRule), C.c_void_p, C.c_size_t, C.c_void_p]),
     ("mi_debug_fetch", C.c_int, [C.c_void_p, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                  C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p]),
     ("mi_status", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]),

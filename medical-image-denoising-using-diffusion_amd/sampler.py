@@ -53,6 +53,49 @@ def check_members(members, member_offset, max_batch) -> Tuple[int, int, int]:
     return members, member_offset, max_batch
 
 
+UPDATE_RULES = ("reference", "ddim")
+
+
+def check_update(update="reference", eta=0.0, clip_x0=True):
+    """Argument rules of the update rule (include/midd.h: THE DDIM UPDATE) -> None for ``"reference"`` (the reference's update,
+    the calls and bits of before) or the ``native.UpdateRule`` of ``"ddim"``; raises ValueError before any GPU work.  ``eta`` and
+    ``clip_x0`` belong to ``"ddim"``: anything but their defaults together with ``"reference"`` raises."""
+    if update not in UPDATE_RULES:
+        raise ValueError(f"update must be 'reference' or 'ddim' (got {update!r})")
+    if isinstance(eta, bool) or not isinstance(eta, numbers.Real) or not 0.0 <= float(eta) <= 1.0:      # (NaN fails the comparison)
+        raise ValueError(f"eta must be a number in [0, 1] (got {eta!r})")
+    if not isinstance(clip_x0, (bool, int)):
+        raise ValueError(f"clip_x0 must be a bool (got {clip_x0!r})")
+    if update == "reference":
+        if float(eta) != 0.0 or not clip_x0:
+            raise ValueError("eta and clip_x0 belong to update='ddim': the reference's update has neither")
+        return None
+    return native.UpdateRule(native.MI_UPDATE["ddim"], float(eta), 1 if clip_x0 else 0)
+
+
+def refuse_update(update, what: str) -> None:
+    """The calls the DDIM update is not built for (include/midd.h: NOT BUILT) take ``update`` to say so."""
+    if update not in UPDATE_RULES:
+        raise ValueError(f"update must be 'reference' or 'ddim' (got {update!r})")
+    if update != "reference":
+        raise ValueError(f"{what} runs the reference's update only: update='ddim' is built for denoise, denoise_ensemble and "
+                         "denoise_tiled (the per-slot record and the other two batched calls do not carry the rule yet)")
+
+
+def ddim_coefficients(t_list: Sequence[int], alpha_hat, eta: float = 0.0):
+    """The coefficient table of ``update="ddim"`` for a timestep list (host only; mi_ddim_coefficients): a float32 numpy array
+    [len(t_list), 7] of (k0, k1, r0, r1, a, b, s) per iteration, the values the update kernel receives."""
+    import numpy as np
+    steps = np.ascontiguousarray(np.asarray(list(t_list), dtype=np.int32))
+    tab = np.ascontiguousarray(alpha_hat.detach().to("cpu", torch.float32).numpy() if isinstance(alpha_hat, torch.Tensor)
+                               else np.asarray(alpha_hat, dtype=np.float32))
+    out = np.empty((len(steps), 7), dtype=np.float32)
+    native.check(native.lib().mi_ddim_coefficients(steps.ctypes.data_as(C.POINTER(C.c_int32)), len(steps),
+                                                   tab.ctypes.data_as(C.POINTER(C.c_float)), int(tab.shape[0]), C.c_double(float(eta)),
+                                                   out.ctypes.data_as(C.POINTER(C.c_float))))
+    return out
+
+
 class EnsembleResult(NamedTuple):
     """What ``DiffusionDenoiser.denoise_ensemble`` returns."""
     mean: torch.Tensor                    # [B, C, H, W]: per-pixel mean of the members
@@ -490,7 +533,8 @@ class DiffusionDenoiser:
     @torch.no_grad()
     def denoise(self, noisy_img: torch.Tensor, inference_steps: int = 25,
                 step_noise: Optional[torch.Tensor] = None, seed: Optional[int] = None,
-                sample_offset: int = 0, member: int = 0) -> torch.Tensor:
+                sample_offset: int = 0, member: int = 0, *,
+                update: str = "reference", eta: float = 0.0, clip_x0: bool = True) -> torch.Tensor:
         """x = denoiser.denoise(noisy_img, inference_steps) — DDIMModel.py:268-289.
 
         Starts from the noisy image itself, conditions every step on it, never mutates it and
@@ -508,7 +552,16 @@ class DiffusionDenoiser:
 
         ``member`` (with ``seed``): which draw of every image, 0 being the run described above.  ``denoise(x, seed=s, member=m)``
         is member m of ``denoise_ensemble(x, seed=s)`` run alone (bit for bit with ``batch_invariant=True``).
+
+        ``update="ddim"`` (not a reference argument; include/midd.h: THE DDIM UPDATE): the stride-aware DDIM(eta) step -- predict
+        x0 from eps, clip it to [0, 1] unless ``clip_x0=False``, re-noise it to the NEXT timestep of the list -- in the place of
+        the reference's one-step ancestral update, which on a strided list removes one step's noise per iteration whatever the
+        stride.  ``eta=0`` is the deterministic sampler: ``seed`` and ``step_noise`` are ignored for both variants.  ``eta > 0``
+        (up to 1, ancestral) adds noise, for BOTH variants, from ``seed`` / ``member`` or ``step_noise`` exactly as above (the
+        0.5-scaled convention is kept: the rule's coefficient carries the factor 2); without either, torch.randn up front.
+        ``update="reference"`` (the default) is the call of before, bit for bit; ``eta`` or ``clip_x0`` with it raise ValueError.
         """
+        rule = check_update(update, eta, clip_x0)
         if seed is not None:
             if step_noise is not None:
                 raise ValueError("pass either seed (noise drawn on the device) or step_noise (a noise tensor), not both")
@@ -516,19 +569,23 @@ class DiffusionDenoiser:
         self.model.eval()
         steps = timestep_list(self.noise_steps, inference_steps)
         stochastic = getattr(self.model, "variant", "ddim") == "cddpm"
-        if stochastic and step_noise is None and seed is None and member == 0:      # (a member without a seed: run_sampler refuses)
+        draws = stochastic if rule is None else rule.eta > 0.0      # whether the call has a noise term at all
+        if draws and step_noise is None and seed is None and member == 0:      # (a member without a seed: run_sampler refuses)
             step_noise = 0.5 * torch.randn((len(steps),) + tuple(noisy_img.shape), device=noisy_img.device)
-        if not stochastic:
+        if not draws:
             step_noise = seed = None
             member = 0
         seeded = {"member": member} if seed is None else {"seed": seed, "sample_offset": sample_offset, "member": member}
+        if rule is not None:
+            seeded.update(update=update, eta=eta, clip_x0=clip_x0)
         return self.model.run_sampler(noisy_img, steps, self.beta, self.alpha, self.alpha_hat,
                                       clamp_eps=not stochastic, step_noise=step_noise, **seeded)
 
     @torch.no_grad()
     def denoise_ensemble(self, noisy_img: torch.Tensor, inference_steps: int = 25, members: int = 8, seed: Optional[int] = None,
                          sample_offset: int = 0, member_offset: int = 0, max_batch: int = 16,
-                         return_samples: bool = False, quantiles=None):
+                         return_samples: bool = False, quantiles=None, *,
+                         update: str = "reference", eta: float = 0.0, clip_x0: bool = True):
         """``members`` stochastic (cddpm) draws per image in one native call: their per-pixel mean -- lower error than any
         single draw -- and unbiased standard deviation -- where the network is guessing.  Not a reference call (the reference
         returns one draw, cddpmModels.py:281-308).
@@ -545,19 +602,28 @@ class DiffusionDenoiser:
         the per-pixel quantile maps of the members -- a median and an interval describe outputs clamped to [0, 1] where mean and
         std do not -- as an ``EnsembleQuantileResult``: the fields above, then ``quantiles`` [B, nq, C, H, W] and ``levels``.  The
         members are written to a tensor of the call's own instead of the workspace (which shrinks by the same bytes) and one
-        ``ensemble_quantiles`` launch follows on the same stream; mean, std and samples are the bits of the call without it."""
+        ``ensemble_quantiles`` launch follows on the same stream; mean, std and samples are the bits of the call without it.
+
+        ``update="ddim"`` with ``eta > 0`` (see ``denoise``): the members are draws of the DDIM(eta) sampler, for EITHER variant --
+        member m is ``denoise(x, update="ddim", eta=eta, seed=seed, member=m)``.  ``eta=0`` is deterministic and raises as the
+        DDIM variant does."""
         levels = None if quantiles is None else check_levels(quantiles)
-        if getattr(self.model, "variant", "ddim") != "cddpm":
+        rule = check_update(update, eta, clip_x0)
+        stochastic = getattr(self.model, "variant", "ddim") == "cddpm"
+        if rule is not None and rule.eta == 0.0:
+            raise ValueError("denoise_ensemble with update='ddim' needs eta > 0: a deterministic sampler has no ensemble")
+        if rule is None and not stochastic:
             raise ValueError("denoise_ensemble needs the stochastic (cddpm) variant: a deterministic sampler has no ensemble")
         seed, _ = check_seed(self._draw_seed() if seed is None else seed, 0)      # (everything else is judged by run_ensemble, before any GPU work)
         if levels is not None:
             check_quantile_members(check_member(members, "members", low=1))
         self.model.eval()
         steps = timestep_list(self.noise_steps, inference_steps)
-        mean, std, samples = self.model.run_ensemble(noisy_img, steps, self.beta, self.alpha, self.alpha_hat, clamp_eps=False,
+        rule_kw = {} if rule is None else dict(update=update, eta=eta, clip_x0=clip_x0)
+        mean, std, samples = self.model.run_ensemble(noisy_img, steps, self.beta, self.alpha, self.alpha_hat, clamp_eps=not stochastic,
                                                      members=members, seed=seed, sample_offset=sample_offset,
                                                      member_offset=member_offset, max_batch=max_batch,
-                                                     want_samples=return_samples or levels is not None)
+                                                     want_samples=return_samples or levels is not None, **rule_kw)
         if levels is None:
             return EnsembleResult(mean, std, samples, seed)
         maps = ensemble_quantiles(samples, levels)
@@ -566,7 +632,7 @@ class DiffusionDenoiser:
     @torch.no_grad()
     def denoise_tiled(self, noisy_img: torch.Tensor, inference_steps: int = 25, tile=256, overlap=32, max_batch: int = 16,
                       seed: Optional[int] = None, sample_offset: int = 0, return_tiles: bool = False,
-                      step_noise: None = None) -> TiledResult:
+                      step_noise: None = None, *, update: str = "reference", eta: float = 0.0, clip_x0: bool = True) -> TiledResult:
         """Denoises images of ANY size >= the tile at their own resolution (not a reference call: the reference resizes every
         image to the training size first): every image is cut into overlapping ``tile`` x ``tile`` crops (``tile``: an int or
         (th, tw), a shape the network takes, i.e. multiples of 8; ``overlap``: an int or (oy, ox), at most tile / 2), the
@@ -577,27 +643,35 @@ class DiffusionDenoiser:
         cddpm: the step noise is the seeded generator's, indexed by the pixel's place in the WHOLE image -- the noise field
         belongs to the image, overlapping tiles see the same noise -- so ``tile == image size`` is ``denoise(x, seed=s)`` bit
         for bit; ``seed=None`` draws a seed as ``denoise_ensemble`` does and returns it.  A caller's ``step_noise`` tensor is
-        not supported here (the argument exists to say so: anything but None raises ValueError).  DDIM: ``seed`` must be None."""
+        not supported here (the argument exists to say so: anything but None raises ValueError).  DDIM: ``seed`` must be None.
+
+        ``update="ddim"`` (see ``denoise``): every tile runs the DDIM(eta) update.  ``eta=0``: deterministic for both variants, a
+        ``seed`` is ignored and the result's ``seed`` is None.  ``eta > 0``: seeded as cddpm is above, for BOTH variants."""
+        rule = check_update(update, eta, clip_x0)
         if step_noise is not None:
             raise ValueError("denoise_tiled does not take a step_noise tensor: its noise is the seeded generator's, indexed by "
                              "image position (pass seed; midd_amd.step_noise(seed, n, x.shape) exports the same values)")
         stochastic = getattr(self.model, "variant", "ddim") == "cddpm"
-        if not stochastic and seed is not None:
+        draws = stochastic if rule is None else rule.eta > 0.0
+        if rule is None and not stochastic and seed is not None:
             raise ValueError("seed selects the step noise of the stochastic (cddpm) variant: the DDIM variant takes seed=None")
-        if stochastic:
+        if draws:
             seed, sample_offset = check_seed(self._draw_seed() if seed is None else seed, sample_offset)
+        else:
+            seed = None
         self.model.eval()
         steps = timestep_list(self.noise_steps, inference_steps)
+        rule_kw = {} if rule is None else dict(update=update, eta=eta, clip_x0=clip_x0)
         image, tiles, plan = self.model.run_tiled(noisy_img, steps, self.beta, self.alpha, self.alpha_hat, clamp_eps=not stochastic,
                                                   tile=tile, overlap=overlap, seed=seed, sample_offset=sample_offset,
-                                                  max_batch=max_batch, want_tiles=return_tiles)
+                                                  max_batch=max_batch, want_tiles=return_tiles, **rule_kw)
         return TiledResult(image, tiles, plan.origins_y, plan.origins_x, seed)
 
     @torch.no_grad()
     def denoise_tiled_ensemble(self, noisy_img: torch.Tensor, inference_steps: int = 25, members: int = 8, tile=256, overlap=32,
                                max_batch: int = 16, seed: Optional[int] = None, sample_offset: int = 0, member_offset: int = 0,
                                return_samples: bool = False, return_tiles: bool = False,
-                               step_noise: None = None, quantiles=None):
+                               step_noise: None = None, quantiles=None, *, update: str = "reference"):
         """``denoise_ensemble`` for images of ANY size >= the tile: ``members`` stochastic (cddpm) draws of every image as blended
         overlapping tiles in one native call, their per-pixel mean and unbiased standard deviation at the image's own resolution
         (not a reference call; include/midd.h: mi_denoise_tiled_ensemble).
@@ -618,6 +692,7 @@ class DiffusionDenoiser:
         [B, nq, C, H, W] and ``levels``.  The tiles are written to a tensor of the call's own instead of the workspace (which
         shrinks by the same bytes) and one ``tile_blend_quantiles`` launch follows on the same stream: the blended members are
         still never stored.  The other fields are the bits of the call without it."""
+        refuse_update(update, "denoise_tiled_ensemble")
         levels = None if quantiles is None else check_levels(quantiles)
         if step_noise is not None:
             raise ValueError("denoise_tiled_ensemble does not take a step_noise tensor: its noise is the seeded generator's, indexed by "
@@ -641,7 +716,7 @@ class DiffusionDenoiser:
     @torch.no_grad()
     def denoise_self_ensemble(self, noisy_img: torch.Tensor, inference_steps: int = 25, views="auto", seed: Optional[int] = None,
                               sample_offset: int = 0, member_offset: int = 0, max_batch: int = 16,
-                              return_samples: bool = False, quantiles=None):
+                              return_samples: bool = False, quantiles=None, *, update: str = "reference"):
         """The geometric self-ensemble ("x8 test-time augmentation") in one native call, for BOTH variants: the network runs on
         the flipped and rotated copies of every image, every output is turned back, and the call returns their per-pixel mean --
         the usual few tenths of a dB over a single run -- and unbiased standard deviation: where the output depends on the
@@ -663,6 +738,7 @@ class DiffusionDenoiser:
         members as a ``SelfEnsembleQuantileResult``: the fields above, then ``quantiles`` [B, nq, C, H, W] and ``levels``.  One
         ``dihedral_quantiles`` launch follows on the same stream and reads the view outputs from the call's workspace; mean, std
         and samples are the bits of the call without it."""
+        refuse_update(update, "denoise_self_ensemble")
         levels = None if quantiles is None else check_levels(quantiles)
         stochastic = getattr(self.model, "variant", "ddim") == "cddpm"
         if not stochastic and seed is not None:
@@ -686,12 +762,13 @@ class DiffusionDenoiser:
 
     @torch.no_grad()
     def denoise_ragged(self, noisy_img: torch.Tensor, inference_steps: Sequence[int], seed: Optional[int] = None,
-                       sample_offset: int = 0) -> torch.Tensor:
+                       sample_offset: int = 0, *, update: str = "reference") -> torch.Tensor:
         """Every image of the batch with its OWN step count, in one native call (mi_denoise_slots; not a reference call):
         image b is ``denoise(noisy_img[b:b+1], inference_steps[b], seed=seed, sample_offset=sample_offset + b)`` -- bit for bit
         with ``batch_invariant=True``, within the parity gate otherwise.  The loop runs max(iterations) rows; an image whose
         list has ended idles (its pixels are not touched again).  cddpm: always seeded; ``seed=None`` draws one as
         ``denoise_ensemble`` does (the run then cannot be repeated: pass a seed to keep it).  DDIM ignores ``seed``."""
+        refuse_update(update, "denoise_ragged (mi_denoise_slots)")
         counts = list(inference_steps)
         if not isinstance(noisy_img, torch.Tensor) or noisy_img.dim() != 4 or len(counts) != noisy_img.shape[0]:
             raise ValueError(f"inference_steps must hold one step count per image ({len(counts)} for a batch of "

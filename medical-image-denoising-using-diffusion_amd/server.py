@@ -18,7 +18,9 @@ PIL / numpy recipe, which stays as ``preprocess`` / ``tensor_to_base64`` for CPU
 
 Not in the reference: ``DiffusionService(batch_slots=N)`` (or ``MIDD_BATCH_SLOTS=N``), N > 0, runs the sampler calls of concurrent
 requests as the slots of ONE ``SamplerSession`` owned by one worker thread (continuous batching, session.py) instead of one
-batch-1 call per request.  0, the default, is the path above, unchanged.
+batch-1 call per request.  0, the default, is the path above, unchanged.  ``DiffusionService(update="ddim", eta=F)`` (or
+``MIDD_UPDATE`` / ``MIDD_ETA``) runs the served 9-of-50 list under the stride-aware DDIM(eta) update (include/midd.h: THE DDIM
+UPDATE); the default, "reference", is the reference's update, unchanged.  Not together with batch_slots > 0.
 
 ``python-multipart`` is not available in this image, so the multipart body is parsed with the
 standard library instead of FastAPI's ``UploadFile``; the wire format is the same.
@@ -40,7 +42,7 @@ import torch
 from PIL import Image
 
 from .modules import UNetDiffusion
-from .sampler import DiffusionDenoiser
+from .sampler import DiffusionDenoiser, check_update, refuse_update
 
 SERVE_SIZE = (512, 512)          # run.py:198
 SERVE_INFERENCE_STEPS = 8        # run.py:107 (-> 9 iterations with noise_steps=50)
@@ -105,13 +107,20 @@ class DiffusionService:
 
     def __init__(self, checkpoint: Optional[str] = None, device: Optional[torch.device] = None,
                  denoise_fn: Optional[Callable[[torch.Tensor], torch.Tensor]] = None, compute: Optional[str] = None,
-                 batch_slots: Optional[int] = None, batch_invariant: Optional[bool] = None, session_factory=None):
+                 batch_slots: Optional[int] = None, batch_invariant: Optional[bool] = None, session_factory=None,
+                 update: Optional[str] = None, eta: Optional[float] = None):
+        # the sampler's update rule (DiffusionDenoiser.denoise): None reads MIDD_UPDATE / MIDD_ETA, default the reference's
+        self.update = os.environ.get("MIDD_UPDATE", "reference") if update is None else update
+        self.eta = float(os.environ.get("MIDD_ETA", "0")) if eta is None else float(eta)
+        check_update(self.update, self.eta)
         self.compute = compute                 # arithmetic of the network (UNetDiffusion); None: the default
         self.batch_invariant = batch_invariant # UNetDiffusion's argument; None: its default
         # > 0: concurrent requests share one SamplerSession of this many slots, run by one worker thread; 0: one call per request
         self.batch_slots = int(os.environ.get("MIDD_BATCH_SLOTS", "0")) if batch_slots is None else int(batch_slots)
         if self.batch_slots < 0:
             raise ValueError("batch_slots must be >= 0")
+        if self.batch_slots > 0:
+            refuse_update(self.update, "batch_slots > 0 (SamplerSession)")
         self._session_factory = session_factory    # tests inject a stand-in: (service) -> an object with submit / step / pending / fail_pending
         self._session = None
         self._worker: Optional[threading.Thread] = None
@@ -147,7 +156,8 @@ class DiffusionService:
             elif self.batch_slots > 0:
                 output = self._submit(input_tensor).result()      # raises what the worker met: the route then answers null
             else:
-                output = self.diffusion_denoiser.denoise(input_tensor, inference_steps=SERVE_INFERENCE_STEPS)
+                rule = {} if self.update == "reference" else {"update": self.update, "eta": self.eta}
+                output = self.diffusion_denoiser.denoise(input_tensor, inference_steps=SERVE_INFERENCE_STEPS, **rule)
             output = torch.clamp(output, 0, 1)
             result = (tensor_to_base64_device if output.is_cuda else tensor_to_base64)(output, original_size)
         print(f"  Diffusion: {time.time() - start:.2f}s")

@@ -14,7 +14,7 @@ from typing import List, Optional, Tuple
 import torch
 
 from .config import timestep_list
-from .sampler import _integer, check_seed
+from .sampler import _integer, check_seed, refuse_update
 
 
 class Ticket:
@@ -66,7 +66,9 @@ class SamplerSession:
     slot's end.  It never changes a result.  A cddpm session is always seeded: ``seed=None`` draws one, ``.seed`` holds it.
     """
 
-    def __init__(self, denoiser, H: int, W: int, slots: int = 8, seed: Optional[int] = None, max_rows: Optional[int] = None):
+    def __init__(self, denoiser, H: int, W: int, slots: int = 8, seed: Optional[int] = None, max_rows: Optional[int] = None, *,
+                 update: str = "reference"):
+        refuse_update(update, "SamplerSession (mi_denoise_slots)")      # the per-slot record does not carry the DDIM rule
         self.denoiser = denoiser
         self.model = denoiser.model
         self.H, self.W = _integer(H, "H", 1 << 31, 1), _integer(W, "W", 1 << 31, 1)
