@@ -85,6 +85,21 @@ extern "C" int mi_unet_plan_create(const mi_unet_cfg* cfg, mi_plan** out) {
     if (arith != MI_COMPUTE_F32 && arith != MI_COMPUTE_F16X3 && arith != MI_COMPUTE_F16) return fail(MI_EINVAL, "unknown compute_mode %d", cfg->compute_mode);
     for (int i = 0; i < cfg->num_levels; ++i)
         if (cfg->channel_mult[i] < 1) return fail(MI_EINVAL, "channel_mult[%d] must be >= 1", i);
+    // The two pointwise kernels at the ends of the network keep their weights in LDS: a width whose launch would be refused is
+    // refused here, with the limit named (the sizes are the launches' own: midd_internal.h).  in_conv's width is model_channels,
+    // out_conv's input is the last module of level 0 (build_topology: final_c = model_channels * channel_mult[0])
+    {
+        const int ic = cfg->in_channels, mc = cfg->model_channels;
+        const long long fc = (long long)mc * cfg->channel_mult[0];
+        if (mc > (1 << 20)) return fail(MI_EINVAL, "model_channels %d is out of range", mc);      // (the byte counts below stay inside an int)
+        if (!(ic == 1 && in_conv1_width(mc)) && in_conv_lds_bytes(ic, mc) > POINTWISE_LDS_LIMIT)
+            return fail(MI_EINVAL, "in_channels %d with model_channels %d: in_conv needs %zu bytes of LDS, the limit is %zu bytes",
+                        ic, mc, in_conv_lds_bytes(ic, mc), POINTWISE_LDS_LIMIT);
+        if (fc > (1 << 20) || out_conv_lds_bytes(ic, (int)fc) > POINTWISE_LDS_LIMIT)
+            return fail(MI_EINVAL, "in_channels %d with %lld channels into out_conv (model_channels * channel_mult[0]): out_conv needs more than the "
+                        "limit of %zu bytes of LDS (%zu bytes of tile, %d bytes per channel)",
+                        ic, fc, POINTWISE_LDS_LIMIT, out_conv_static_lds_bytes(), (int)out_conv_dynamic_lds_bytes(ic, 1));
+    }
     for (int i = 0; i < cfg->num_attention_levels; ++i) {
         const int lv = cfg->attention_levels[i];
         if (lv >= 0 && lv < cfg->num_levels) {

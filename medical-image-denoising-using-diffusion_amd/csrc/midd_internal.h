@@ -185,6 +185,27 @@ bool attention_supported(int head_dim);
 // tot != nullptr: also leaves the GroupNorm totals of the output [B][Cout/bs][rep][2][3] (stats_common.h)
 hipError_t in_conv_launch(const float* x, const float* cond, const float* w /*[9][2ic][Cout]*/, const float* bias,
                           float* out, stat_word* tot, int rep, int bs, int B, int ic, int H, int W, int Cout, int blocked, hipStream_t s);
+// LDS of the two kernels at the ends of the network, in bytes.  Neither raises its kernel's limit, so a workgroup has
+// POINTWISE_LDS_LIMIT for its static and dynamic LDS together.  These are the ONE place that says how much a (channels, width)
+// pair takes: the launches allocate by them and mi_unet_plan_create refuses a network that would not fit (the sizes depend on
+// in_channels and the two widths alone, not on B, H, W), so what plans also launches.
+constexpr size_t POINTWISE_LDS_LIMIT = 64 * 1024;
+// in_conv1_kernel (one input channel) is instantiated for these widths and sizes its own LDS (it raises its limit where needed)
+__host__ __device__ constexpr bool in_conv1_width(int Cout) { return Cout == 32 || Cout == 48 || Cout == 64; }
+// in_conv_kernel, all dynamic: weights [9][2ic][Cout] and bias [Cout], the statistics scratch [2][Cout][ppi] of
+// ppi = 256 / (Cout / 16) pixel lanes (+ 2 floats of alignment slack), the publish accumulators (Cout + 2) x STAT_WORDS
+__host__ __device__ inline size_t in_conv_lds_bytes(int ic, int Cout) {
+    const int ppi = 256 / (Cout / 16);
+    return (size_t)(9 * 2 * ic * Cout + Cout + 2 * Cout * ppi + 2) * sizeof(float) + (size_t)(Cout + 2) * STAT_WORDS * sizeof(stat_word);
+}
+// out_conv_*_kernel: a 16 x 16 output tile, its 18 x 18 halo staged 16 channels at a time with a padded pixel stride of 20 floats
+// (static), then the weights [ic][9][C] and the GroupNorm scale / shift [2][C] (dynamic)
+constexpr int OC_T = 16;
+constexpr int OC_I = OC_T + 2;
+constexpr int OC_PS = 20;         // padded pixel stride in floats
+__host__ __device__ constexpr size_t out_conv_static_lds_bytes() { return (size_t)OC_I * OC_I * OC_PS * sizeof(float); }
+__host__ __device__ inline size_t out_conv_dynamic_lds_bytes(int ic, int C) { return ((size_t)ic * 9 * C + 2 * (size_t)C) * sizeof(float); }
+__host__ __device__ inline size_t out_conv_lds_bytes(int ic, int C) { return out_conv_static_lds_bytes() + out_conv_dynamic_lds_bytes(ic, C); }
 
 struct OutConvArgs {
     const float* src;       // [B][H][W][C], or channel-blocked [B][C/16][H][W][16] when `blocked`

@@ -23,7 +23,8 @@ void MIDD_OUT_KERNEL(const OutConvArgs a, const float* __restrict__ wglob /* == 
 #endif
                      ) {
     __shared__ __attribute__((aligned(16))) float tile[OC_I * OC_I * OC_PS];
-    extern __shared__ __attribute__((aligned(16))) float wl[];       // [ic][9][C], then [2][C] GroupNorm scale / shift of this sample
+    static_assert(sizeof(tile) == out_conv_static_lds_bytes(), "out_conv_lds_bytes (midd_internal.h) counts this tile");
+    extern __shared__ __attribute__((aligned(16))) float wl[];       // [ic][9][C], then [2][C] GroupNorm scale / shift of this sample: out_conv_dynamic_lds_bytes
     const int ic = IC ? IC : a.ic;
     const int tid = threadIdx.x;
     const int tx = tid & 15, ty = tid >> 4;

@@ -334,16 +334,17 @@ static hipError_t in_conv1_launch(const float* x, const float* cond, const float
 hipError_t in_conv_launch(const float* x, const float* cond, const float* w, const float* bias, float* out,
                           stat_word* tot, int rep, int bs, int B, int ic, int H, int W, int Cout, int blocked, hipStream_t s) {
     if (Cout % 16 || Cout / 16 > 256) return hipErrorInvalidValue;
-    if (ic == 1) {                          // the grayscale case: in_conv1_kernel for the widths it is instantiated for
+    if (ic == 1 && in_conv1_width(Cout)) {  // the grayscale case: in_conv1_kernel for the widths it is instantiated for
 #define MIDD_IC1(N) if (Cout == N) return blocked ? in_conv1_launch<N, true>(x, cond, w, bias, out, tot, rep, bs, B, H, W, s) \
                                                  : in_conv1_launch<N, false>(x, cond, w, bias, out, tot, rep, bs, B, H, W, s);
         MIDD_IC1(48) MIDD_IC1(32) MIDD_IC1(64)
+        static_assert(in_conv1_width(48) && in_conv1_width(32) && in_conv1_width(64), "in_conv1_width names the instantiations");
 #undef MIDD_IC1
     }
     const int ppi = 256 / (Cout / 16);
     const int rows = pointwise_rows(H * W, ppi);
-    const size_t lds = (size_t)(9 * 2 * ic * Cout + Cout + 2 * Cout * ppi + 2) * sizeof(float) + (size_t)(Cout + 2) * STAT_WORDS * sizeof(stat_word);
-    if (lds > 64 * 1024) return hipErrorInvalidValue;
+    const size_t lds = in_conv_lds_bytes(ic, Cout);
+    if (lds > POINTWISE_LDS_LIMIT) return hipErrorInvalidValue;      // (mi_unet_plan_create refuses such a network: not reached through the C ABI)
     hipLaunchKernelGGL(in_conv_kernel, dim3(rows, B), dim3(256), lds, s, x, cond, w, bias, out, tot, rep, bs, ic, H, W, Cout, rows, blocked);
     return hipGetLastError();
 }
@@ -352,9 +353,7 @@ hipError_t in_conv_launch(const float* x, const float* cond, const float* w, con
 // Workgroup = 16x16 output pixels.  The 18x18 halo is staged through LDS in 16-channel chunks
 // with GroupNorm-apply + SiLU on the way in; pixel stride 20 floats keeps the float4 reads of
 // 16 neighbouring lanes on distinct banks.
-constexpr int OC_T = 16;
-constexpr int OC_I = OC_T + 2;
-constexpr int OC_PS = 20;         // padded pixel stride in floats
+// (OC_T = 16, OC_I = 18, OC_PS = 20 and the LDS the kernels take: midd_internal.h)
 
 // IC: output channels at compile time (1: the reference's grayscale case; 0: a.ic at run time, <= 4).  With the count
 // only known at run time hipcc indexes the accumulators through select chains and splits the 16-byte LDS reads:
@@ -399,7 +398,8 @@ constexpr int OC_PS = 20;         // padded pixel stride in floats
 
 hipError_t out_conv_launch(const OutConvArgs& a, hipStream_t s) {
     if (a.ic > 4 || a.C % 16) return hipErrorInvalidValue;
-    const size_t lds = ((size_t)a.ic * 9 * a.C + 2 * a.C) * sizeof(float);
+    const size_t lds = out_conv_dynamic_lds_bytes(a.ic, a.C);
+    if (out_conv_lds_bytes(a.ic, a.C) > POINTWISE_LDS_LIMIT) return hipErrorInvalidValue;      // (refused at mi_unet_plan_create)
     const int tiles = ((a.W + OC_T - 1) / OC_T) * ((a.H + OC_T - 1) / OC_T);
     if (a.seeded) {
         if (!a.x || (unsigned long long)a.ic * a.H * a.W >= (1ull << 32) || a.members < 1 || a.v0 < 0) return hipErrorInvalidValue;
@@ -417,7 +417,8 @@ hipError_t out_conv_launch(const OutConvArgs& a, hipStream_t s) {
 hipError_t out_conv_slots_launch(const OutConvArgs& a, const SlotRec* slots, hipStream_t s) {
     if (a.ic > 4 || a.C % 16 || !slots || !a.x) return hipErrorInvalidValue;
     if (a.seeded && (a.noise || (unsigned long long)a.ic * a.H * a.W >= (1ull << 32))) return hipErrorInvalidValue;
-    const size_t lds = ((size_t)a.ic * 9 * a.C + 2 * a.C) * sizeof(float);
+    const size_t lds = out_conv_dynamic_lds_bytes(a.ic, a.C);
+    if (out_conv_lds_bytes(a.ic, a.C) > POINTWISE_LDS_LIMIT) return hipErrorInvalidValue;      // (refused at mi_unet_plan_create)
     const int tiles = ((a.W + OC_T - 1) / OC_T) * ((a.H + OC_T - 1) / OC_T);
     if (a.ic == 1) hipLaunchKernelGGL(out_conv_slots_kernel<1>, dim3(a.B * tiles), dim3(256), lds, s, a, a.w, slots);
     else hipLaunchKernelGGL(out_conv_slots_kernel<0>, dim3(a.B * tiles), dim3(256), lds, s, a, a.w, slots);
@@ -427,7 +428,8 @@ hipError_t out_conv_slots_launch(const OutConvArgs& a, const SlotRec* slots, hip
 // a.c1 .. a.c3 are not read.  The seeded form is launched only when a term is drawn at all (a.seeded: the host sets it with k.s > 0)
 hipError_t out_conv_ddim_launch(const OutConvArgs& a, const DdimCoef& k, hipStream_t s) {
     if (a.ic > 4 || a.C % 16 || !a.x) return hipErrorInvalidValue;
-    const size_t lds = ((size_t)a.ic * 9 * a.C + 2 * a.C) * sizeof(float);
+    const size_t lds = out_conv_dynamic_lds_bytes(a.ic, a.C);
+    if (out_conv_lds_bytes(a.ic, a.C) > POINTWISE_LDS_LIMIT) return hipErrorInvalidValue;      // (refused at mi_unet_plan_create)
     const int tiles = ((a.W + OC_T - 1) / OC_T) * ((a.H + OC_T - 1) / OC_T);
     if (a.seeded) {
         if (a.noise || (unsigned long long)a.ic * a.H * a.W >= (1ull << 32) || a.members < 1 || a.v0 < 0) return hipErrorInvalidValue;

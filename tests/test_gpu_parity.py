@@ -265,6 +265,9 @@ CONFIG_SWEEP = [
     # the out_conv instance whose output count is a run-time value
     (dict(in_channels=2, model_channels=32, channel_mult=(1, 2), num_res_blocks=2, attention_resolutions=(1,), time_emb_dim=32), "ddim", 2, 24, 16),
     (dict(in_channels=3, model_channels=32, channel_mult=(1, 2), num_res_blocks=1, attention_resolutions=(1,), time_emb_dim=32), "cddpm", 1, 16, 16),
+    # three channels on the default widths: in_conv_kernel at Cout = 48 -- 3 channel groups, 85 pixel lanes, so thread 255 sits out of
+    # the statistics scratch -- and out_conv_kernel<0> at C = 48; 40 x 24 leaves edge workgroups on both axes
+    (dict(in_channels=3), "ddim", 2, 40, 24),
 ]
 
 
