@@ -636,6 +636,46 @@ size_t mi_metrics_workspace_bytes(int n, int h);
 int mi_image_metrics(const void* target_f32, const void* pred_f32, int n, int h, int w, void* out_f64,
                      void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- THE FLOAT RESIZE AND THE 16-BIT ELEMENT RULES: the high-bit-depth twin of the calls above ------------
+ * The 8-bit calls above are the reference's contract (256 grey levels in and out).  X-ray detectors deliver 12 to 16 bits; these
+ * calls carry such an image to the sampler and back without the 8-bit step (1 / 255 = 3.9e-3, twice the parity gate).
+ *
+ * mi_resize_bicubic_f32: `n` single-channel images [n][sh][sw] of element type `src_type` -> [n][dh][dw] of `dst_type`.
+ *   The arithmetic is Pillow's 32bpc resample, `Image.fromarray(a, mode "F").resize((dw, dh), Image.BICUBIC)`, bit for bit:
+ *     - separable, horizontal pass first; a pass whose size does not change is skipped;
+ *     - bounds and coefficients as the 8-bit resample derives them BEFORE it rounds to fixed point: scale = in / out,
+ *       support = 2 * max(1, scale), center = (xx + .5) * scale, xmin = max(0, (int)(center - support + .5)),
+ *       xmax = min(in, (int)(center + support + .5)), bicubic weights (a = -.5) in double, `w /= ww` when their sum ww != 0;
+ *     - an output value is `(float)ss` with `double ss = 0.0; for x in tap order: ss += (double)pixel[x] * k[x]`: sequential,
+ *       every operation rounded on its own, no fused multiply-add;
+ *     - float32 between the passes, nothing clipped there.
+ *   Pillow's "I;16" resample is NOT reproduced (it wraps the low byte on overshoot: pixels next to a white edge come out below white); resampling
+ *   the unit-float image is the 16-bit route.
+ *   Element types on load and store:
+ *     source MI_PIX_U8: (float)v / 255.0f (as mi_u8_to_unit_f32);  MI_PIX_U16: (float)v / 65535.0f, one correctly rounded fp32
+ *     division;  MI_PIX_F32: as is.
+ *     destination MI_PIX_F32: the value; with clamp01 != 0 min(max(v, 0), 1), applied to the FINAL value only.
+ *     destination MI_PIX_U16: always clamped, then (uint16_t)(v * 65535.0f + 0.5f), the multiply and the add each rounded in
+ *     fp32: round to nearest (there is no reference behaviour to mirror at 16 bits; u16 -> float -> u16 is the identity for all
+ *     65536 values).  A NaN stores 0.
+ *   The fused forms equal the separate steps (convert, resize, convert) bit for bit; with both sizes unchanged the call is the pure
+ *   conversion.  `workspace`: mi_resize_f32_workspace_bytes(n, sw, sh, dw, dh) bytes, 256-byte aligned; it holds the coefficient
+ *   tables (computed on the device: the call is asynchronous) and the float intermediate.
+ *   MI_EINVAL before any GPU work, the rule named in mi_last_error: a null pointer; a non-positive size; an unknown element type or
+ *   a destination of MI_PIX_U8 (the 8-bit destination stays mi_resize_bicubic_u8, whose arithmetic differs); n * height * width of
+ *   the source, the intermediate or the destination >= 2^31; a workspace that is not 256-byte aligned or too small.
+ *   mi_resize_f32_workspace_bytes returns 0 for sizes the call refuses.
+ * mi_u16_to_unit_f32 / mi_unit_f32_to_u16: the two 16-bit element rules on `count` elements (null pointer: MI_EINVAL). */
+#define MI_PIX_U8  0
+#define MI_PIX_U16 1
+#define MI_PIX_F32 2
+size_t mi_resize_f32_workspace_bytes(int n, int sw, int sh, int dw, int dh);
+int mi_resize_bicubic_f32(const void* src, int src_type, int n, int sw, int sh,
+                          void* dst, int dst_type, int dw, int dh, int clamp01,
+                          void* workspace, size_t workspace_bytes, void* stream);
+int mi_u16_to_unit_f32(const uint16_t* src, float* dst, size_t count, void* stream);
+int mi_unit_f32_to_u16(const float* src, uint16_t* dst, size_t count, void* stream);
+
 /* Thread-local, never NULL. */
 const char* mi_last_error(void);
 

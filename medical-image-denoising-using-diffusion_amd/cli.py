@@ -10,6 +10,7 @@ img_size -> sampler -> uint8 -> bicubic resize back -> PNG, with the reference's
                            [--tile N [--overlap O]]
                            [--self-ensemble [auto|flips|d4] [--std-out std.npy] [--quantiles Q,Q --quantiles-out q.npy]]
                            [--update reference|ddim [--eta F] [--no-clip-x0]]
+                           [--bit-depth 8|16]
 
 Without a checkpoint (the trained weights are not distributed with the reference) the network is
 random-init, which exercises the path but does not denoise.  The reference helper has a latent
@@ -26,6 +27,7 @@ import numpy as np
 import torch
 from PIL import Image
 
+from . import image16
 from .modules import UNetDiffusion
 from .sampler import MAX_QUANTILE_MEMBERS, DiffusionDenoiser, check_levels, check_update
 
@@ -37,7 +39,7 @@ def denoise_image_diffusion(model_path: Optional[str], test_image_path: str, dev
                             std_out: Optional[str] = None, tile: Optional[int] = None, overlap: int = 32,
                             quantiles: Optional[Sequence[float]] = None, quantiles_out: Optional[str] = None,
                             self_ensemble: Optional[str] = None, update: str = "reference", eta: float = 0.0,
-                            clip_x0: bool = True) -> Image.Image:
+                            clip_x0: bool = True, bit_depth: int = 8) -> Image.Image:
     """compute (not a reference argument): arithmetic of the network, see UNetDiffusion -- None keeps the default.
     seed (not a reference argument; cddpm): the stochastic sampler's noise is drawn on the device from this seed, so the same
     call gives the same image again (DiffusionDenoiser.denoise); None: torch.randn, as the reference.
@@ -54,7 +56,13 @@ def denoise_image_diffusion(model_path: Optional[str], test_image_path: str, dev
     describe the views instead of seeded draws.  Not together with samples or tile.
     update, eta, clip_x0 (not reference arguments; both variants): "ddim" runs the stride-aware DDIM(eta) update
     (DiffusionDenoiser.denoise) in the place of the reference's; with eta > 0 samples works for the DDIM variant too.  Not together
-    with self_ensemble."""
+    with self_ensemble.
+    bit_depth (not a reference argument): 8 is the reference's recipe, unchanged.  16 keeps a 16-bit file's 65536 levels (image16.py;
+    include/midd.h: THE FLOAT RESIZE): decode to unit float (/ 65535; any other file: `convert("L")` / 255), float bicubic resize to
+    img_size and clip, the sampler, float resize back, clip, and a mode "I;16" image rounded to nearest -- with tile no resize at
+    all.  On the GPU the resizes and conversions are the HIP kernels (prepost), bit-identical to the Pillow mode "F" / numpy recipe
+    that runs around the sampler call on a CPU device."""
+    bit_depth = image16.check_bit_depth(bit_depth)
     rule = {} if check_update(update, eta, clip_x0) is None else {"update": update, "eta": eta, "clip_x0": clip_x0}
     if rule and self_ensemble is not None:
         raise ValueError("--update ddim cannot be combined with --self-ensemble (the self-ensemble runs the reference's update only)")
@@ -92,21 +100,38 @@ def denoise_image_diffusion(model_path: Optional[str], test_image_path: str, dev
     diffusion = DiffusionDenoiser(model, noise_steps=int(checkpoint.get("noise_steps", 50)))
     print(f"Loaded model - PSNR: {checkpoint.get('best_psnr', 'N/A')} dB | SSIM: {checkpoint.get('best_ssim', 'N/A')}")
 
-    img = Image.open(test_image_path).convert("L")
+    img = Image.open(test_image_path)
+    raw16 = image16.decode16(img) if bit_depth == 16 else None          # uint16 [H][W] (uint8 for a file that is not 16-bit)
+    img = img.convert("L") if raw16 is None else img
     on_gpu = device.type == "cuda"
     if tile is not None:
         if min(img.size) < tile:
             raise ValueError(f"the image is {img.size[1]}x{img.size[0]}: a side is shorter than the tile ({tile}); use a smaller "
                              "--tile, or leave it out so that the image is resized to img_size")
-        input_tensor = torch.from_numpy(np.asarray(img, np.uint8).astype(np.float32) / 255.0)[None, None].to(device)   # ToTensor
+        if raw16 is None:
+            input_tensor = torch.from_numpy(np.asarray(img, np.uint8).astype(np.float32) / 255.0)[None, None].to(device)   # ToTensor
+        elif on_gpu:
+            from . import prepost
+            dev_raw = torch.from_numpy(raw16).to(device)
+            input_tensor = (prepost.u16_to_unit_float if raw16.dtype == np.uint16 else prepost.to_unit_float)(dev_raw)[None, None]
+        else:
+            input_tensor = torch.from_numpy(image16.unit_float(raw16))[None, None].to(device)
         start_time = time.time()
         res = diffusion.denoise_tiled(input_tensor, inference_steps=inference_steps, tile=tile, overlap=overlap, seed=seed, **rule)
         if on_gpu:
             torch.cuda.synchronize(device)
         print(f"Tiled: {len(res.origins_y)} x {len(res.origins_x)} tiles of {tile}" + (f", seed {res.seed}" if res.seed is not None else ""))
         print(f"Inference time: {time.time() - start_time:.2f} seconds")
+        if raw16 is not None:
+            out16 = prepost.to_u16(res.image[0, 0].float()).cpu().numpy() if on_gpu else image16.to_u16(res.image[0, 0].cpu().numpy())
+            return image16.image_from_u16(out16)
         return Image.fromarray((res.image[0, 0].cpu().numpy() * 255).astype(np.uint8), mode="L")      # already clamped to [0, 1]
-    if on_gpu:      # resize + ToTensor scaling on the device (prepost: bit-identical to the PIL / numpy recipe below)
+    if raw16 is not None and on_gpu:    # 16-bit recipe on the device: typed load, float resize, clip (one fused call)
+        from . import prepost
+        input_tensor = prepost.resize_bicubic_f32(torch.from_numpy(raw16).to(device), (img_size, img_size), clamp=True)[None, None]
+    elif raw16 is not None:
+        input_tensor = torch.from_numpy(image16.resize_f(image16.unit_float(raw16), (img_size, img_size)))[None, None].to(device)
+    elif on_gpu:      # resize + ToTensor scaling on the device (prepost: bit-identical to the PIL / numpy recipe below)
         from . import prepost
         raw = torch.from_numpy(np.asarray(img, np.uint8).copy()).to(device)
         input_tensor = prepost.to_unit_float(prepost.resize_bicubic_u8(raw, (img_size, img_size)))[None, None]
@@ -141,6 +166,13 @@ def denoise_image_diffusion(model_path: Optional[str], test_image_path: str, dev
         torch.cuda.synchronize(device)
     print(f"Inference time: {time.time() - start_time:.2f} seconds")
 
+    if raw16 is not None:
+        plane = denoised.reshape(img_size, img_size).float()
+        if on_gpu:      # float resize back, clip, round to u16: one fused call
+            back = prepost.resize_bicubic_f32(plane, raw16.shape, clamp=True, out_dtype=torch.uint16).cpu().numpy()
+        else:
+            back = image16.to_u16(image16.resize_f(plane.cpu().numpy(), raw16.shape))
+        return image16.image_from_u16(back)
     if on_gpu:
         u8 = prepost.to_u8(denoised.reshape(img_size, img_size).float())     # denoise() already clamped to [0, 1]
         return Image.fromarray(prepost.resize_bicubic_u8(u8, (img.size[1], img.size[0])).cpu().numpy(), mode="L")
@@ -178,6 +210,8 @@ def main(argv=None) -> None:
                     help="the sampler's update rule: reference (one-step ancestral, the default) or ddim (stride-aware DDIM(eta) step)")
     ap.add_argument("--eta", type=float, default=0.0, help="with --update ddim: 0 (deterministic, the default) .. 1 (ancestral)")
     ap.add_argument("--no-clip-x0", action="store_true", help="with --update ddim: do not clip the predicted image to [0, 1]")
+    ap.add_argument("--bit-depth", type=int, default=8, choices=[8, 16],
+                    help="8 (the default): the reference's 8-bit recipe; 16: keep a 16-bit file's levels -- float resize, 16-bit PNG out")
     args = ap.parse_args(argv)
     if args.update == "reference" and (args.eta != 0.0 or args.no_clip_x0):
         ap.error("--eta and --no-clip-x0 need --update ddim")
@@ -209,7 +243,8 @@ def main(argv=None) -> None:
                                        inference_steps=args.inference_steps, variant=args.variant, seed=args.seed,
                                        samples=args.samples, std_out=args.std_out, tile=args.tile, overlap=args.overlap,
                                        quantiles=levels, quantiles_out=args.quantiles_out, self_ensemble=args.self_ensemble,
-                                       update=args.update, eta=args.eta, clip_x0=not args.no_clip_x0)
+                                       update=args.update, eta=args.eta, clip_x0=not args.no_clip_x0,
+                                       bit_depth=args.bit_depth)
     restored.save(args.out, quality=95)
     print(f"\nResult saved: {args.out}")
 

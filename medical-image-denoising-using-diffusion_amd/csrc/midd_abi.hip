@@ -46,6 +46,44 @@ extern "C" int mi_unit_f32_to_u8(const void* src, void* dst, size_t count, void*
     HIPCHK(unit_to_u8_launch(static_cast<const float*>(src), static_cast<unsigned char*>(dst), count, static_cast<hipStream_t>(stream)));
     return MI_OK;
 }
+// n * h * w of the source, the intermediate and the destination stay below 2^31 (one thread per element, 32-bit grid)
+static bool resize_f32_fits(int n, int sw, int sh, int dw, int dh) {
+    const long long lim = 1LL << 31;
+    return (long long)n * sh * sw < lim && (long long)n * sh * dw < lim && (long long)n * dh * dw < lim;
+}
+extern "C" size_t mi_resize_f32_workspace_bytes(int n, int sw, int sh, int dw, int dh) {
+    if (n < 1 || sw < 1 || sh < 1 || dw < 1 || dh < 1 || !resize_f32_fits(n, sw, sh, dw, dh)) return 0;
+    return resize_f32_workspace_bytes(n, sw, sh, dw, dh);
+}
+extern "C" int mi_resize_bicubic_f32(const void* src, int src_type, int n, int sw, int sh, void* dst, int dst_type, int dw, int dh,
+                                     int clamp01, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!src || !dst || !workspace) return fail(MI_EINVAL, "null argument");
+    if (n < 1 || sw < 1 || sh < 1 || dw < 1 || dh < 1) return fail(MI_EINVAL, "image sizes must be positive");
+    if (src_type != MI_PIX_U8 && src_type != MI_PIX_U16 && src_type != MI_PIX_F32)
+        return fail(MI_EINVAL, "unknown source element type %d (MI_PIX_U8, MI_PIX_U16 or MI_PIX_F32)", src_type);
+    if (dst_type == MI_PIX_U8)
+        return fail(MI_EINVAL, "destination element type MI_PIX_U8: the 8-bit destination is mi_resize_bicubic_u8 (fixed-point arithmetic)");
+    if (dst_type != MI_PIX_U16 && dst_type != MI_PIX_F32)
+        return fail(MI_EINVAL, "unknown destination element type %d (MI_PIX_U16 or MI_PIX_F32)", dst_type);
+    if (!resize_f32_fits(n, sw, sh, dw, dh)) return fail(MI_EINVAL, "too many pixels: n * height * width must stay below 2^31");
+    if (reinterpret_cast<uintptr_t>(workspace) & 255) return fail(MI_EINVAL, "workspace must be 256-byte aligned");
+    if (workspace_bytes < resize_f32_workspace_bytes(n, sw, sh, dw, dh))
+        return fail(MI_EINVAL, "workspace too small: %zu < %zu", workspace_bytes, resize_f32_workspace_bytes(n, sw, sh, dw, dh));
+    HIPCHK(resize_bicubic_f32_launch(src, src_type, n, sw, sh, dst, dst_type, dw, dh, clamp01, workspace, static_cast<hipStream_t>(stream)));
+    return MI_OK;
+}
+extern "C" int mi_u16_to_unit_f32(const uint16_t* src, float* dst, size_t count, void* stream) {
+    if (!src || !dst) return fail(MI_EINVAL, "null argument");
+    if (count >= ((size_t)1 << 40)) return fail(MI_EINVAL, "count must stay below 2^40");
+    HIPCHK(u16_to_unit_launch(src, dst, count, static_cast<hipStream_t>(stream)));
+    return MI_OK;
+}
+extern "C" int mi_unit_f32_to_u16(const float* src, uint16_t* dst, size_t count, void* stream) {
+    if (!src || !dst) return fail(MI_EINVAL, "null argument");
+    if (count >= ((size_t)1 << 40)) return fail(MI_EINVAL, "count must stay below 2^40");
+    HIPCHK(unit_to_u16_launch(src, dst, count, static_cast<hipStream_t>(stream)));
+    return MI_OK;
+}
 extern "C" size_t mi_metrics_workspace_bytes(int n, int h) { return (n < 1 || h < 1) ? 0 : metrics_workspace_bytes(n, h); }
 extern "C" int mi_image_metrics(const void* target, const void* pred, int n, int h, int w, void* out,
                                 void* workspace, size_t workspace_bytes, void* stream) {

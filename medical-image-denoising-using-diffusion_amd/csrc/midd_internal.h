@@ -162,6 +162,12 @@ size_t resize_workspace_bytes(int n, int sw, int sh, int dw, int dh);
 hipError_t resize_bicubic_u8_launch(const unsigned char* src, int n, int sw, int sh, unsigned char* dst, int dw, int dh, void* ws, hipStream_t s);
 hipError_t u8_to_unit_launch(const unsigned char* src, float* dst, size_t count, hipStream_t s);
 hipError_t unit_to_u8_launch(const float* src, unsigned char* dst, size_t count, hipStream_t s);
+// float (Pillow 32bpc) resample with a typed load and store (MI_PIX_*), and the 16-bit element conversions
+size_t resize_f32_workspace_bytes(int n, int sw, int sh, int dw, int dh);
+hipError_t resize_bicubic_f32_launch(const void* src, int src_type, int n, int sw, int sh, void* dst, int dst_type, int dw, int dh,
+                                     int clamp, void* ws, hipStream_t s);
+hipError_t u16_to_unit_launch(const uint16_t* src, float* dst, size_t count, hipStream_t s);
+hipError_t unit_to_u16_launch(const float* src, uint16_t* dst, size_t count, hipStream_t s);
 size_t metrics_workspace_bytes(int n, int h);
 hipError_t metrics_launch(const float* target, const float* pred, int n, int h, int w, double* out, void* ws, hipStream_t s);
 

@@ -8,6 +8,7 @@
 //   * PSNR / SSIM of `compute_metrics` (DDIMModel.py:290-300; skimage defaults: 7x7 uniform window, K1 = .01,
 //     K2 = .03, sample covariance, mean over the interior), fp64, fixed summation order.
 // Checker: oracle/resize_oracle.py (pinned against Pillow itself on the CPU); tests/test_gpu_prepost.py.
+#include "../../include/midd.h"
 #include "midd_internal.h"
 #include <cstdint>
 
@@ -157,8 +158,180 @@ hipError_t unit_to_u8_launch(const float* src, uint8_t* dst, size_t count, hipSt
     return hipGetLastError();
 }
 
+// ------------------------------------------------------------------------------ high bit depth (include/midd.h: THE FLOAT RESIZE)
+// Pillow's 32bpc resample (`Image.resize` on a mode "F" image; src/libImaging/Resample.c, ImagingResample*_32bpc): the bounds
+// and the normalised fp64 coefficients of resize_coeffs_kernel BEFORE its fixed-point rounding, `double ss = 0; ss += pixel * k`
+// in tap order with every operation rounded on its own (contraction off: an FMA would skip the product's rounding), float32
+// between the passes, nothing clipped there.  The element type of the source and of the destination is a template parameter, so
+// u16 -> resize -> u16 is two launches per pass pair and equals convert -> resize -> convert bit for bit.
+// Checker: tests/resize_f32_reference.py (pinned against Pillow on the CPU); tests/test_gpu_prepost16.py.
+__global__ void resize_coeffs_f64_kernel(int in_size, int out_size, int ksize, int* __restrict__ bounds, double* __restrict__ kk) {
+#pragma clang fp contract(off)
+    const int xx = blockIdx.x * blockDim.x + threadIdx.x;
+    if (xx >= out_size) return;
+    const double scale = (double)in_size / (double)out_size;
+    const double filterscale = scale < 1.0 ? 1.0 : scale;
+    const double support = 2.0 * filterscale;
+    const double ss = 1.0 / filterscale;
+    const double center = (xx + 0.5) * scale;
+    int xmin = (int)(center - support + 0.5);
+    if (xmin < 0) xmin = 0;
+    int xmax = (int)(center + support + 0.5);
+    if (xmax > in_size) xmax = in_size;
+    xmax -= xmin;
+    double ww = 0.0;
+    for (int x = 0; x < xmax; ++x) ww += bicubic_w((x + xmin - center + 0.5) * ss);
+    double* k = kk + (size_t)xx * ksize;
+    for (int x = 0; x < ksize; ++x) {
+        double w = 0.0;
+        if (x < xmax) {
+            w = bicubic_w((x + xmin - center + 0.5) * ss);
+            if (ww != 0.0) w /= ww;
+        }
+        k[x] = w;
+    }
+    bounds[2 * xx] = xmin;
+    bounds[2 * xx + 1] = xmax;
+}
+
+__device__ __forceinline__ float pix_load(const uint8_t* p, size_t i) { return __fdiv_rn((float)p[i], 255.0f); }
+__device__ __forceinline__ float pix_load(const uint16_t* p, size_t i) { return __fdiv_rn((float)p[i], 65535.0f); }
+__device__ __forceinline__ float pix_load(const float* p, size_t i) { return p[i]; }
+
+__device__ __forceinline__ void pix_store(float* p, size_t i, float v, int clamp) {
+    if (clamp) v = v < 0.f ? 0.f : (v > 1.f ? 1.f : v);
+    p[i] = v;
+}
+__device__ __forceinline__ void pix_store(uint16_t* p, size_t i, float v, int) {
+    v = !(v > 0.f) ? 0.f : (v > 1.f ? 1.f : v);                         // always clamped; a NaN stores 0
+    p[i] = (uint16_t)__fadd_rn(__fmul_rn(v, 65535.0f), 0.5f);           // round to nearest: two fp32 roundings, truncation
+}
+
+// rows = n * h rows of sw pixels -> rows of dw pixels; consecutive threads: consecutive output x
+template <typename S, typename D>
+__global__ void resample_h_f32_kernel(const S* __restrict__ src, D* __restrict__ dst, long rows, int sw, int dw,
+                                      const int* __restrict__ bounds, const double* __restrict__ kk, int ksize, int clamp) {
+#pragma clang fp contract(off)
+    const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= rows * dw) return;
+    const long row = idx / dw;
+    const int xx = (int)(idx - row * dw);
+    const int xmin = bounds[2 * xx], xmax = bounds[2 * xx + 1];
+    const double* k = kk + (size_t)xx * ksize;
+    const size_t base = (size_t)row * sw + xmin;
+    double ss = 0.0;
+    for (int x = 0; x < xmax; ++x) {
+        const double prod = (double)pix_load(src, base + x) * k[x];
+        ss = ss + prod;
+    }
+    pix_store(dst, (size_t)idx, (float)ss, clamp);
+}
+
+// n images of sh x w -> dh x w; consecutive threads: consecutive x of one output row (loads and stores coalesced)
+template <typename S, typename D>
+__global__ void resample_v_f32_kernel(const S* __restrict__ src, D* __restrict__ dst, int n, int sh, int dh, int w,
+                                      const int* __restrict__ bounds, const double* __restrict__ kk, int ksize, int clamp) {
+#pragma clang fp contract(off)
+    const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= (long)n * dh * w) return;
+    const int x = (int)(idx % w);
+    const long t = idx / w;
+    const int yy = (int)(t % dh);
+    const int img = (int)(t / dh);
+    const int ymin = bounds[2 * yy], ymax = bounds[2 * yy + 1];
+    const double* k = kk + (size_t)yy * ksize;
+    const size_t base = ((size_t)img * sh + ymin) * w + x;
+    double ss = 0.0;
+    for (int y = 0; y < ymax; ++y) {
+        const double prod = (double)pix_load(src, base + (size_t)y * w) * k[y];
+        ss = ss + prod;
+    }
+    pix_store(dst, (size_t)idx, (float)ss, clamp);
+}
+
+// both sizes unchanged: the pure conversion (also mi_u16_to_unit_f32 / mi_unit_f32_to_u16)
+template <typename S, typename D>
+__global__ void pix_convert_kernel(const S* __restrict__ src, D* __restrict__ dst, size_t count, int clamp) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < count) pix_store(dst, i, pix_load(src, i), clamp);
+}
+
+// workspace: [h bounds 2*dw][v bounds 2*dh] ints | [h kk dw*ksize_h][v kk dh*ksize_v] doubles | the n*sh*dw float intermediate
+struct ResizeF32Layout { size_t kk_off, mid_off, total; };
+static ResizeF32Layout resize_f32_layout(int n, int sw, int sh, int dw, int dh) {
+    ResizeF32Layout l;
+    const size_t ints = 2 * (size_t)dw + 2 * (size_t)dh;
+    const size_t dbls = (size_t)dw * resize_ksize(sw, dw) + (size_t)dh * resize_ksize(sh, dh);
+    l.kk_off = (ints * sizeof(int) + 255) & ~(size_t)255;
+    l.mid_off = l.kk_off + ((dbls * sizeof(double) + 255) & ~(size_t)255);
+    l.total = l.mid_off + (size_t)n * sh * dw * sizeof(float) + 256;
+    return l;
+}
+
+size_t resize_f32_workspace_bytes(int n, int sw, int sh, int dw, int dh) { return resize_f32_layout(n, sw, sh, dw, dh).total; }
+
+template <typename S, typename D>
+static hipError_t resize_f32_typed(const S* src, int n, int sw, int sh, D* dst, int dw, int dh, int clamp, void* ws, hipStream_t s) {
+    const ResizeF32Layout l = resize_f32_layout(n, sw, sh, dw, dh);
+    const int kh = resize_ksize(sw, dw), kv = resize_ksize(sh, dh);
+    int* hb = reinterpret_cast<int*>(ws);
+    int* vb = hb + 2 * (size_t)dw;
+    double* hk = reinterpret_cast<double*>(reinterpret_cast<char*>(ws) + l.kk_off);
+    double* vk = hk + (size_t)dw * kh;
+    float* mid = reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + l.mid_off);
+    const bool need_h = dw != sw, need_v = dh != sh;
+    auto blocks = [](long total) { return dim3((unsigned)((total + 255) / 256)); };
+    if (!need_h && !need_v) {
+        const size_t count = (size_t)n * sh * sw;
+        hipLaunchKernelGGL((pix_convert_kernel<S, D>), blocks((long)count), dim3(256), 0, s, src, dst, count, clamp);
+        return hipGetLastError();
+    }
+    if (need_h) hipLaunchKernelGGL(resize_coeffs_f64_kernel, dim3((dw + 127) / 128), dim3(128), 0, s, sw, dw, kh, hb, hk);
+    if (need_v) hipLaunchKernelGGL(resize_coeffs_f64_kernel, dim3((dh + 127) / 128), dim3(128), 0, s, sh, dh, kv, vb, vk);
+    const long htotal = (long)n * sh * dw, vtotal = (long)n * dh * dw;
+    if (need_h && need_v) {
+        hipLaunchKernelGGL((resample_h_f32_kernel<S, float>), blocks(htotal), dim3(256), 0, s, src, mid, (long)n * sh, sw, dw, hb, hk, kh, 0);
+        hipLaunchKernelGGL((resample_v_f32_kernel<float, D>), blocks(vtotal), dim3(256), 0, s, mid, dst, n, sh, dh, dw, vb, vk, kv, clamp);
+    } else if (need_h) {
+        hipLaunchKernelGGL((resample_h_f32_kernel<S, D>), blocks(htotal), dim3(256), 0, s, src, dst, (long)n * sh, sw, dw, hb, hk, kh, clamp);
+    } else {
+        hipLaunchKernelGGL((resample_v_f32_kernel<S, D>), blocks(vtotal), dim3(256), 0, s, src, dst, n, sh, dh, dw, vb, vk, kv, clamp);
+    }
+    return hipGetLastError();
+}
+
+template <typename S>
+static hipError_t resize_f32_src(const S* src, int n, int sw, int sh, void* dst, int dst_type, int dw, int dh, int clamp, void* ws, hipStream_t s) {
+    if (dst_type == MI_PIX_F32) return resize_f32_typed(src, n, sw, sh, static_cast<float*>(dst), dw, dh, clamp, ws, s);
+    if (dst_type == MI_PIX_U16) return resize_f32_typed(src, n, sw, sh, static_cast<uint16_t*>(dst), dw, dh, clamp, ws, s);
+    return hipErrorInvalidValue;
+}
+
+hipError_t resize_bicubic_f32_launch(const void* src, int src_type, int n, int sw, int sh, void* dst, int dst_type, int dw, int dh,
+                                     int clamp, void* ws, hipStream_t s) {
+    if (n < 1 || sw < 1 || sh < 1 || dw < 1 || dh < 1) return hipErrorInvalidValue;
+    switch (src_type) {
+        case MI_PIX_U8:  return resize_f32_src(static_cast<const uint8_t*>(src), n, sw, sh, dst, dst_type, dw, dh, clamp, ws, s);
+        case MI_PIX_U16: return resize_f32_src(static_cast<const uint16_t*>(src), n, sw, sh, dst, dst_type, dw, dh, clamp, ws, s);
+        case MI_PIX_F32: return resize_f32_src(static_cast<const float*>(src), n, sw, sh, dst, dst_type, dw, dh, clamp, ws, s);
+    }
+    return hipErrorInvalidValue;
+}
+
+hipError_t u16_to_unit_launch(const uint16_t* src, float* dst, size_t count, hipStream_t s) {
+    if (count == 0) return hipSuccess;
+    hipLaunchKernelGGL((pix_convert_kernel<uint16_t, float>), dim3((unsigned)((count + 255) / 256)), dim3(256), 0, s, src, dst, count, 0);
+    return hipGetLastError();
+}
+
+hipError_t unit_to_u16_launch(const float* src, uint16_t* dst, size_t count, hipStream_t s) {
+    if (count == 0) return hipSuccess;
+    hipLaunchKernelGGL((pix_convert_kernel<float, uint16_t>), dim3((unsigned)((count + 255) / 256)), dim3(256), 0, s, src, dst, count, 1);
+    return hipGetLastError();
+}
+
 // ------------------------------------------------------------------------------ metrics
-constexpr int MET_ROWS = 4;         // image rows per block
+constexpr int MET_ROWS = 4;        // image rows per block
 constexpr int MET_THREADS = 256;
 
 __device__ __forceinline__ double clamp01(float v) { return (double)(v < 0.f ? 0.f : (v > 1.f ? 1.f : v)); }

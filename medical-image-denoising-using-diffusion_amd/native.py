@@ -21,6 +21,7 @@ MI_COMPUTE = {"f32": 0, "f16x3": 1, "f16": 2}
 MI_STATUS_NONFINITE, MI_STATUS_FP16_RANGE = 1, 2
 MI_COMPUTE_BATCH_INVARIANT = 0x100          # include/midd.h: OR into compute_mode
 MI_UPDATE = {"reference": 0, "ddim": 1}     # include/midd.h: mi_update_rule.kind
+MI_PIX_U8, MI_PIX_U16, MI_PIX_F32 = 0, 1, 2 # include/midd.h: element types of mi_resize_bicubic_f32
 
 
 class NativeLibraryError(RuntimeError):
@@ -131,6 +132,11 @@ SYMBOLS = [
                                        C.c_void_p, C.c_size_t, C.c_void_p]),
     ("mi_u8_to_unit_f32", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     ("mi_unit_f32_to_u8", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    ("mi_resize_f32_workspace_bytes", C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    ("mi_resize_bicubic_f32", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                        C.c_void_p, C.c_size_t, C.c_void_p]),
+    ("mi_u16_to_unit_f32", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    ("mi_unit_f32_to_u16", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     ("mi_metrics_workspace_bytes", C.c_size_t, [C.c_int, C.c_int]),
     ("mi_image_metrics", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                    C.c_void_p, C.c_size_t, C.c_void_p]),

@@ -5,6 +5,9 @@ Host-side mirror of what the reference does around `denoise` with PIL / torchvis
 (Backend/DDIM/DDIMModel.py:290-300), backed by libmidd.so (csrc/prepost.hip).  GPU tensors only: like the sampler
 there is no CPU fallback here -- the reference's own host recipe (`server.preprocess` / `tensor_to_base64`)
 remains the path for CPU tensors.
+
+`resize_bicubic_f32`, `u16_to_unit_float` and `to_u16` are the high-bit-depth twin (not in the reference; include/midd.h: THE FLOAT
+RESIZE AND THE 16-BIT ELEMENT RULES): Pillow's mode "F" resample bit for bit with typed loads and stores; image16.py is the host recipe.
 """
 from typing import Tuple
 
@@ -67,6 +70,57 @@ def to_u8(images: torch.Tensor) -> torch.Tensor:
     out = torch.empty(x.shape, dtype=torch.uint8, device=x.device)
     with torch.cuda.device(x.device):
         native.check(native.lib().mi_unit_f32_to_u8(x.data_ptr(), out.data_ptr(), x.numel(), _stream(x)))
+    return out
+
+
+_PIX = {torch.uint8: native.MI_PIX_U8, torch.uint16: native.MI_PIX_U16, torch.float32: native.MI_PIX_F32}
+
+
+def resize_bicubic_f32(images: torch.Tensor, size: Tuple[int, int], clamp: bool = False,
+                       out_dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """uint8, uint16 or float32 [N,H,W] (or [H,W]) -> float32 (or uint16) [N,size[0],size[1]]: the integer types are scaled to
+    unit float on load (/ 255, / 65535), the resample is bit-identical to
+    `Image.fromarray(img, mode "F").resize((size[1], size[0]), Image.BICUBIC)` per image, `clamp` clips the final value to [0, 1],
+    and out_dtype=torch.uint16 stores clamp(v) * 65535 rounded to nearest (include/midd.h: THE FLOAT RESIZE).  Equal sizes: the pure
+    conversion.  Channels fold into N."""
+    squeeze = images.dim() == 2
+    if images.dtype not in _PIX:
+        raise TypeError(f"resize_bicubic_f32: expected uint8, uint16 or float32, got {images.dtype}")
+    if out_dtype not in (torch.float32, torch.uint16):
+        raise ValueError(f"resize_bicubic_f32: out_dtype is float32 or uint16, got {out_dtype} (8-bit output: resize_bicubic_u8)")
+    x = _need_cuda(images[None] if squeeze else images, images.dtype, "resize_bicubic_f32")
+    if x.dim() != 3:
+        raise ValueError("resize_bicubic_f32: expected [N,H,W] or [H,W]")
+    n, sh, sw = x.shape
+    dh, dw = int(size[0]), int(size[1])
+    lib = native.lib()
+    nbytes = lib.mi_resize_f32_workspace_bytes(n, sw, sh, dw, dh)
+    if nbytes == 0:
+        raise ValueError(f"resize_bicubic_f32: bad sizes {tuple(x.shape)} -> {(dh, dw)}")
+    out = torch.empty((n, dh, dw), dtype=out_dtype, device=x.device)
+    with torch.cuda.device(x.device):
+        ws, wptr = _workspace(nbytes, x.device)
+        native.check(lib.mi_resize_bicubic_f32(x.data_ptr(), _PIX[x.dtype], n, sw, sh, out.data_ptr(), _PIX[out_dtype], dw, dh,
+                                               int(bool(clamp)), wptr, nbytes, _stream(x)))
+        ws.record_stream(torch.cuda.current_stream(x.device))
+    return out[0] if squeeze else out
+
+
+def u16_to_unit_float(images_u16: torch.Tensor) -> torch.Tensor:
+    """uint16 -> float32 / 65535 (same shape): one correctly rounded fp32 division."""
+    x = _need_cuda(images_u16, torch.uint16, "u16_to_unit_float")
+    out = torch.empty(x.shape, dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        native.check(native.lib().mi_u16_to_unit_f32(x.data_ptr(), out.data_ptr(), x.numel(), _stream(x)))
+    return out
+
+
+def to_u16(images: torch.Tensor) -> torch.Tensor:
+    """`(uint16)(clamp(x, 0, 1) * 65535 + 0.5)`, multiply and add in fp32: round to nearest (to_u8 truncates, as the reference)."""
+    x = _need_cuda(images, torch.float32, "to_u16")
+    out = torch.empty(x.shape, dtype=torch.uint16, device=x.device)
+    with torch.cuda.device(x.device):
+        native.check(native.lib().mi_unit_f32_to_u16(x.data_ptr(), out.data_ptr(), x.numel(), _stream(x)))
     return out
 
 

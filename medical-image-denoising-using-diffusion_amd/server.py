@@ -22,6 +22,12 @@ batch-1 call per request.  0, the default, is the path above, unchanged.  ``Diff
 ``MIDD_UPDATE`` / ``MIDD_ETA``) runs the served 9-of-50 list under the stride-aware DDIM(eta) update (include/midd.h: THE DDIM
 UPDATE); the default, "reference", is the reference's update, unchanged.  Not together with batch_slots > 0.
 
+``DiffusionService(bit_depth=16)`` (or ``MIDD_BIT_DEPTH=16``), not in the reference either, keeps a 16-bit upload's 65536 grey levels
+(image16.py; include/midd.h: THE FLOAT RESIZE): ``preprocess16`` / ``tensor_to_base64_16`` and their ``_device`` twins replace the
+four functions above, the ``"diffusion"`` value is a base64 16-bit PNG (mode "I;16") at the upload's size, and ``/health`` reports
+``bit_depth``.  Only pre and post change, so it works with batch_slots > 0 and with update="ddim".  8, the default, is the
+reference's 8-bit contract, unchanged.
+
 ``python-multipart`` is not available in this image, so the multipart body is parsed with the
 standard library instead of FastAPI's ``UploadFile``; the wire format is the same.
 """
@@ -41,6 +47,7 @@ import numpy as np
 import torch
 from PIL import Image
 
+from . import image16
 from .modules import UNetDiffusion
 from .sampler import DiffusionDenoiser, check_update, refuse_update
 
@@ -90,6 +97,39 @@ def tensor_to_base64_device(tensor: torch.Tensor, size: Tuple[int, int]) -> str:
     return base64.b64encode(buffered.getvalue()).decode()
 
 
+def preprocess16(image_bytes: bytes) -> Tuple[torch.Tensor, Tuple[int, int]]:
+    """`preprocess` of the 16-bit recipe: decode to unit float (/ 65535 for a 16-bit file, `convert("L")` / 255 for any other),
+    Pillow mode "F" bicubic resize to 512x512, clip to [0, 1]."""
+    image = Image.open(io.BytesIO(image_bytes))
+    original_size = image.size
+    x = image16.resize_f(image16.unit_float(image16.decode16(image)), SERVE_SIZE)
+    return torch.from_numpy(x)[None, None], original_size
+
+
+def tensor_to_base64_16(tensor: torch.Tensor, size: Tuple[int, int]) -> str:
+    """[1,1,H,W] -> base64 16-bit PNG at the original size: mode "F" resize back, clip, u16 rounded to nearest."""
+    x = tensor.reshape(tensor.shape[-2], tensor.shape[-1]).float().cpu().numpy()
+    return base64.b64encode(image16.png_bytes_u16(image16.to_u16(image16.resize_f(x, (size[1], size[0]))))).decode()
+
+
+def preprocess16_device(image_bytes: bytes, device: torch.device) -> Tuple[torch.Tensor, Tuple[int, int]]:
+    """`preprocess16` with the scaling, the resize and the clip on the GPU (one fused call of csrc/prepost.hip; bit-identical to
+    the host recipe): only the decode stays on the host."""
+    from . import prepost
+    image = Image.open(io.BytesIO(image_bytes))
+    original_size = image.size
+    raw = torch.from_numpy(image16.decode16(image)).to(device, non_blocking=True)
+    return prepost.resize_bicubic_f32(raw, SERVE_SIZE, clamp=True)[None, None], original_size
+
+
+def tensor_to_base64_16_device(tensor: torch.Tensor, size: Tuple[int, int]) -> str:
+    """`tensor_to_base64_16` with the resize back, the clip and the u16 rounding on the GPU; PNG encoding on the host."""
+    from . import prepost
+    plane = tensor.reshape(tensor.shape[-2], tensor.shape[-1]).float()
+    back = prepost.resize_bicubic_f32(plane, (size[1], size[0]), clamp=True, out_dtype=torch.uint16).cpu().numpy()
+    return base64.b64encode(image16.png_bytes_u16(back)).decode()
+
+
 def extract_multipart_file(body: bytes, content_type: str, field: str = "file") -> bytes:
     """Returns the payload of multipart form field ``field`` (stdlib parser)."""
     if "multipart/form-data" not in (content_type or ""):
@@ -108,7 +148,10 @@ class DiffusionService:
     def __init__(self, checkpoint: Optional[str] = None, device: Optional[torch.device] = None,
                  denoise_fn: Optional[Callable[[torch.Tensor], torch.Tensor]] = None, compute: Optional[str] = None,
                  batch_slots: Optional[int] = None, batch_invariant: Optional[bool] = None, session_factory=None,
-                 update: Optional[str] = None, eta: Optional[float] = None):
+                 update: Optional[str] = None, eta: Optional[float] = None, bit_depth: Optional[int] = None):
+        # 8: the reference's 8-bit pre/post-processing; 16: the 16-bit recipe (preprocess16 / tensor_to_base64_16).  None reads
+        # MIDD_BIT_DEPTH, default 8
+        self.bit_depth = image16.check_bit_depth(int(os.environ.get("MIDD_BIT_DEPTH", "8")) if bit_depth is None else bit_depth)
         # the sampler's update rule (DiffusionDenoiser.denoise): None reads MIDD_UPDATE / MIDD_ETA, default the reference's
         self.update = os.environ.get("MIDD_UPDATE", "reference") if update is None else update
         self.eta = float(os.environ.get("MIDD_ETA", "0")) if eta is None else float(eta)
@@ -159,7 +202,10 @@ class DiffusionService:
                 rule = {} if self.update == "reference" else {"update": self.update, "eta": self.eta}
                 output = self.diffusion_denoiser.denoise(input_tensor, inference_steps=SERVE_INFERENCE_STEPS, **rule)
             output = torch.clamp(output, 0, 1)
-            result = (tensor_to_base64_device if output.is_cuda else tensor_to_base64)(output, original_size)
+            if self.bit_depth == 16:
+                result = (tensor_to_base64_16_device if output.is_cuda else tensor_to_base64_16)(output, original_size)
+            else:
+                result = (tensor_to_base64_device if output.is_cuda else tensor_to_base64)(output, original_size)
         print(f"  Diffusion: {time.time() - start:.2f}s")
         return result
 
@@ -229,8 +275,8 @@ class DiffusionService:
     def preprocess(self, image_bytes: bytes) -> Tuple[torch.Tensor, Tuple[int, int]]:
         """Decode + resize + scale; on the GPU when the service runs there (same bytes either way)."""
         if self.device.type == "cuda" and self._denoise_fn is None:
-            return preprocess_device(image_bytes, self.device)
-        x, size = preprocess(image_bytes)
+            return (preprocess16_device if self.bit_depth == 16 else preprocess_device)(image_bytes, self.device)
+        x, size = (preprocess16 if self.bit_depth == 16 else preprocess)(image_bytes)
         return x.to(self.device), size
 
 
@@ -274,7 +320,7 @@ def create_app(service: Optional[DiffusionService] = None, checkpoint: Optional[
 
     @app.get("/health")
     async def health_check():
-        return {"status": "healthy", "device": str(svc.device), "batch_slots": svc.batch_slots,
+        return {"status": "healthy", "device": str(svc.device), "batch_slots": svc.batch_slots, "bit_depth": svc.bit_depth,
                 "models_loaded": {"diffusion": svc.diffusion_model is not None or svc._denoise_fn is not None,
                                   "nafnet": False, "expert": False, "hybrid": False}}
 
