@@ -676,6 +676,47 @@ int mi_resize_bicubic_f32(const void* src, int src_type, int n, int sw, int sh,
 int mi_u16_to_unit_f32(const uint16_t* src, float* dst, size_t count, void* stream);
 int mi_unit_f32_to_u16(const float* src, uint16_t* dst, size_t count, void* stream);
 
+/* ---- THE WINDOW: exact percentile windowing of the 16-bit path ------------------------------------------------
+ * The 16-bit calls above scale by the container (v / 65535).  A 12-bit detector image in a 16-bit file then peaks at 0.0625 and the
+ * network sees an almost black picture.  A window maps the occupied grey range [lo, hi] to [0, 1] before the sampler and back
+ * afterwards (radiology's window/level).  Integer arithmetic or single fp32 roundings throughout: the device, the numpy restatement
+ * (tests/window_reference.py) and the host recipe (image16.py) agree bit for bit.
+ *
+ * Histogram.  h[k], k in [0, 65535], counts the pixels of value k in one image of `count` pixels, 1 <= count <= 2^32 - 1 (uint32
+ *   counts cannot overflow).  mi_histogram_u16: `n` images [n][count] (image i starts at element i * count; src 2-byte aligned) ->
+ *   hist uint32 [n][65536] (16-byte aligned), zeroed by the call itself on the stream.  Counted in on-chip counters per workgroup
+ *   and merged with integer atomics: the result does not depend on the order.
+ * Levels from percentiles.  p_lo, p_hi doubles, finite, 0 <= p_lo < p_hi <= 100;  N = sum of h.
+ *   rank r(p) = (uint64) floor(p * (double)(N - 1) / 100.0), the multiply and the divide in double, each rounded on its own;
+ *   level(p) = the smallest k with h[0] + ... + h[k] > r(p)  ( = np.sort(image.ravel())[r(p)], the 0-based order statistic );
+ *   lo = level(p_lo), hi = level(p_hi);  if hi == lo (a flat image, or both ranks in one bin): hi = lo + 1 when lo < 65535, else
+ *   lo = hi - 1.  So 0 <= lo < hi <= 65535 always.  (A histogram of all zeros, which mi_histogram_u16 never writes, gives (0, 65535).)
+ *   mi_window_levels: hist [n][65536] -> levels int32 [n][2] = (lo, hi) in DEVICE memory.  Every call below reads them there, so
+ *   the recipe histogram -> levels -> load -> sampler -> store stays asynchronous on one stream.  Levels written by the caller
+ *   instead (absolute grey levels) must satisfy 0 <= lo < hi <= 65535; the kernels do not check them.
+ * Element rules under a window (lo, hi), d = (float)(hi - lo):
+ *   load  u16:  x = min(max((float)((int)v - lo) / d, 0.0f), 1.0f) -- the integer difference is exact in fp32, then one correctly
+ *               rounded fp32 division;
+ *   store u16:  v = (uint16_t)(lo + (uint32_t)(min(max(x, 0), 1) * d + 0.5f)), the multiply and the add each rounded in fp32; a NaN
+ *               stores lo.
+ *   store(load(v)) == v for every v in [lo, hi].  THE WINDOW CLIPS: a value below lo comes back as lo, one above hi as hi.
+ *   Percentiles (0, 100) give the min-max window, which clips nothing.  The window (0, 65535) is the unwindowed rule above
+ *   (/ 65535, * 65535 + 0.5) bit for bit, in both directions.
+ *   mi_window_u16_to_f32 / mi_window_f32_to_u16: the two rules on [n][count], image i under levels[i].
+ * mi_resize_bicubic_f32_window: mi_resize_bicubic_f32 with every MI_PIX_U16 side (source, destination or both) taken under the
+ *   window of its image; the other element types and the resample are unchanged, and the fused call equals window load -> float
+ *   resize -> window store done separately, bit for bit.  levels == NULL: mi_resize_bicubic_f32 itself.  With levels, n <= 65535 and
+ *   at least one side is MI_PIX_U16.
+ * MI_EINVAL before any GPU work, the rule named in mi_last_error: a null pointer; n outside [1, 65535]; count outside [1, 2^32);
+ *   percentiles that are not finite or break 0 <= p_lo < p_hi <= 100; a misaligned src or hist; the rules of mi_resize_bicubic_f32. */
+int mi_histogram_u16(const uint16_t* src, int n, size_t count, uint32_t* hist, void* stream);
+int mi_window_levels(const uint32_t* hist, int n, double p_lo, double p_hi, int32_t* levels, void* stream);
+int mi_window_u16_to_f32(const uint16_t* src, const int32_t* levels, int n, size_t count, float* dst, void* stream);
+int mi_window_f32_to_u16(const float* src, const int32_t* levels, int n, size_t count, uint16_t* dst, void* stream);
+int mi_resize_bicubic_f32_window(const void* src, int src_type, int n, int sw, int sh,
+                                 void* dst, int dst_type, int dw, int dh, int clamp01, const int32_t* levels,
+                                 void* workspace, size_t workspace_bytes, void* stream);
+
 /* Thread-local, never NULL. */
 const char* mi_last_error(void);
 

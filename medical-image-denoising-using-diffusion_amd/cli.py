@@ -10,7 +10,7 @@ img_size -> sampler -> uint8 -> bicubic resize back -> PNG, with the reference's
                            [--tile N [--overlap O]]
                            [--self-ensemble [auto|flips|d4] [--std-out std.npy] [--quantiles Q,Q --quantiles-out q.npy]]
                            [--update reference|ddim [--eta F] [--no-clip-x0]]
-                           [--bit-depth 8|16]
+                           [--bit-depth 8|16 [--window P_LO,P_HI | --window-levels LO,HI]]
 
 Without a checkpoint (the trained weights are not distributed with the reference) the network is
 random-init, which exercises the path but does not denoise.  The reference helper has a latent
@@ -39,7 +39,8 @@ def denoise_image_diffusion(model_path: Optional[str], test_image_path: str, dev
                             std_out: Optional[str] = None, tile: Optional[int] = None, overlap: int = 32,
                             quantiles: Optional[Sequence[float]] = None, quantiles_out: Optional[str] = None,
                             self_ensemble: Optional[str] = None, update: str = "reference", eta: float = 0.0,
-                            clip_x0: bool = True, bit_depth: int = 8) -> Image.Image:
+                            clip_x0: bool = True, bit_depth: int = 8, window: Optional[Sequence[float]] = None,
+                            window_levels: Optional[Sequence[int]] = None) -> Image.Image:
     """compute (not a reference argument): arithmetic of the network, see UNetDiffusion -- None keeps the default.
     seed (not a reference argument; cddpm): the stochastic sampler's noise is drawn on the device from this seed, so the same
     call gives the same image again (DiffusionDenoiser.denoise); None: torch.randn, as the reference.
@@ -61,8 +62,22 @@ def denoise_image_diffusion(model_path: Optional[str], test_image_path: str, dev
     include/midd.h: THE FLOAT RESIZE): decode to unit float (/ 65535; any other file: `convert("L")` / 255), float bicubic resize to
     img_size and clip, the sampler, float resize back, clip, and a mode "I;16" image rounded to nearest -- with tile no resize at
     all.  On the GPU the resizes and conversions are the HIP kernels (prepost), bit-identical to the Pillow mode "F" / numpy recipe
-    that runs around the sampler call on a CPU device."""
+    that runs around the sampler call on a CPU device.
+    window, window_levels (not reference arguments; bit_depth 16 and a 16-bit file only; one of the two): the grey range [lo, hi] of
+    the file is mapped to [0, 1] before the sampler and back afterwards (include/midd.h: THE WINDOW) -- window gives two percentiles
+    (p_lo, p_hi) whose levels are read off the image's histogram ((0, 100): its minimum and maximum), window_levels the two levels
+    themselves.  The recipe is decode, histogram, levels, windowed load (+ resize), the sampler call of any kind, (resize +) windowed
+    store; values outside the window come back as lo or hi (the window clips).  With samples / self_ensemble the mean is stored through
+    the window; std_out and quantiles_out stay float, in window units: one unit is hi - lo grey levels.  The levels are printed."""
     bit_depth = image16.check_bit_depth(bit_depth)
+    if window is not None and window_levels is not None:
+        raise ValueError("--window and --window-levels cannot be combined: percentiles or absolute levels, not both")
+    if (window is not None or window_levels is not None) and bit_depth != 16:
+        raise ValueError("--window and --window-levels need --bit-depth 16 (the window acts on 16-bit files)")
+    if window is not None:
+        window = image16.check_percentiles(window)
+    if window_levels is not None:
+        window_levels = image16.check_levels(window_levels)
     rule = {} if check_update(update, eta, clip_x0) is None else {"update": update, "eta": eta, "clip_x0": clip_x0}
     if rule and self_ensemble is not None:
         raise ValueError("--update ddim cannot be combined with --self-ensemble (the self-ensemble runs the reference's update only)")
@@ -104,12 +119,26 @@ def denoise_image_diffusion(model_path: Optional[str], test_image_path: str, dev
     raw16 = image16.decode16(img) if bit_depth == 16 else None          # uint16 [H][W] (uint8 for a file that is not 16-bit)
     img = img.convert("L") if raw16 is None else img
     on_gpu = device.type == "cuda"
+    win = None          # the window's levels: int32 [1,2] on the device (they stay there: no synchronisation), or (lo, hi) on the host
+    if window is not None or window_levels is not None:
+        raw16 = image16.need_u16(raw16, img.mode)
+        if on_gpu:
+            from . import prepost
+            dev_raw16 = torch.from_numpy(raw16).to(device)
+            win = (prepost.window_levels(dev_raw16, window) if window is not None
+                   else torch.tensor([list(window_levels)], dtype=torch.int32, device=device))
+        else:
+            win = image16.window_levels(raw16, window) if window is not None else window_levels
+            print(f"Window: grey levels {win[0]} .. {win[1]}")
     if tile is not None:
         if min(img.size) < tile:
             raise ValueError(f"the image is {img.size[1]}x{img.size[0]}: a side is shorter than the tile ({tile}); use a smaller "
                              "--tile, or leave it out so that the image is resized to img_size")
         if raw16 is None:
             input_tensor = torch.from_numpy(np.asarray(img, np.uint8).astype(np.float32) / 255.0)[None, None].to(device)   # ToTensor
+        elif win is not None:
+            input_tensor = (prepost.window_u16_to_float(dev_raw16, win)[None, None] if on_gpu
+                            else torch.from_numpy(image16.unit_float_window(raw16, win))[None, None].to(device))
         elif on_gpu:
             from . import prepost
             dev_raw = torch.from_numpy(raw16).to(device)
@@ -122,11 +151,22 @@ def denoise_image_diffusion(model_path: Optional[str], test_image_path: str, dev
             torch.cuda.synchronize(device)
         print(f"Tiled: {len(res.origins_y)} x {len(res.origins_x)} tiles of {tile}" + (f", seed {res.seed}" if res.seed is not None else ""))
         print(f"Inference time: {time.time() - start_time:.2f} seconds")
+        if win is not None:
+            if on_gpu:
+                print("Window: grey levels {} .. {}".format(*win[0].tolist()))
+                out16 = prepost.window_to_u16(res.image[0, 0].float(), win).cpu().numpy()
+            else:
+                out16 = image16.to_u16_window(res.image[0, 0].cpu().numpy(), win)
+            return image16.image_from_u16(out16)
         if raw16 is not None:
             out16 = prepost.to_u16(res.image[0, 0].float()).cpu().numpy() if on_gpu else image16.to_u16(res.image[0, 0].cpu().numpy())
             return image16.image_from_u16(out16)
         return Image.fromarray((res.image[0, 0].cpu().numpy() * 255).astype(np.uint8), mode="L")      # already clamped to [0, 1]
-    if raw16 is not None and on_gpu:    # 16-bit recipe on the device: typed load, float resize, clip (one fused call)
+    if win is not None and on_gpu:      # windowed load, float resize, clip: one fused call under the levels on the device
+        input_tensor = prepost.resize_bicubic_f32(dev_raw16, (img_size, img_size), clamp=True, levels=win)[None, None]
+    elif win is not None:
+        input_tensor = torch.from_numpy(image16.resize_f(image16.unit_float_window(raw16, win), (img_size, img_size)))[None, None].to(device)
+    elif raw16 is not None and on_gpu:    # 16-bit recipe on the device: typed load, float resize, clip (one fused call)
         from . import prepost
         input_tensor = prepost.resize_bicubic_f32(torch.from_numpy(raw16).to(device), (img_size, img_size), clamp=True)[None, None]
     elif raw16 is not None:
@@ -166,6 +206,14 @@ def denoise_image_diffusion(model_path: Optional[str], test_image_path: str, dev
         torch.cuda.synchronize(device)
     print(f"Inference time: {time.time() - start_time:.2f} seconds")
 
+    if win is not None:
+        plane = denoised.reshape(img_size, img_size).float()
+        if on_gpu:      # float resize back, clip, windowed store: one fused call
+            print("Window: grey levels {} .. {}".format(*win[0].tolist()))
+            back = prepost.resize_bicubic_f32(plane, raw16.shape, clamp=True, out_dtype=torch.uint16, levels=win).cpu().numpy()
+        else:
+            back = image16.to_u16_window(image16.resize_f(plane.cpu().numpy(), raw16.shape), win)
+        return image16.image_from_u16(back)
     if raw16 is not None:
         plane = denoised.reshape(img_size, img_size).float()
         if on_gpu:      # float resize back, clip, round to u16: one fused call
@@ -212,6 +260,12 @@ def main(argv=None) -> None:
     ap.add_argument("--no-clip-x0", action="store_true", help="with --update ddim: do not clip the predicted image to [0, 1]")
     ap.add_argument("--bit-depth", type=int, default=8, choices=[8, 16],
                     help="8 (the default): the reference's 8-bit recipe; 16: keep a 16-bit file's levels -- float resize, 16-bit PNG out")
+    ap.add_argument("--window", default=None, metavar="P_LO,P_HI",
+                    help="with --bit-depth 16 and a 16-bit file: map the grey range between these two percentiles of the image (0,100: its "
+                         "minimum and maximum) to [0, 1] for the sampler and back afterwards; values outside come back clipped to the "
+                         "range.  --std-out and --quantiles-out stay float in window units: one unit is hi - lo grey levels")
+    ap.add_argument("--window-levels", default=None, metavar="LO,HI",
+                    help="as --window, with the two grey levels given (0 <= LO < HI <= 65535) instead of read off the histogram")
     args = ap.parse_args(argv)
     if args.update == "reference" and (args.eta != 0.0 or args.no_clip_x0):
         ap.error("--eta and --no-clip-x0 need --update ddim")
@@ -239,12 +293,25 @@ def main(argv=None) -> None:
             levels = check_levels([float(v) for v in args.quantiles.split(",")])
         except ValueError as exc:
             ap.error(f"--quantiles needs up to 8 comma-separated levels in [0, 1]: {exc}")
+    window = window_levels = None
+    if args.window is not None and args.window_levels is not None:
+        ap.error("--window and --window-levels cannot be combined")
+    if (args.window is not None or args.window_levels is not None) and args.bit_depth != 16:
+        ap.error("--window and --window-levels need --bit-depth 16")
+    try:
+        if args.window is not None:
+            window = image16.check_percentiles(image16.parse_pair(args.window, "--window"))
+        if args.window_levels is not None:
+            window_levels = image16.check_levels(image16.parse_pair(args.window_levels, "--window-levels"))
+    except ValueError as exc:
+        ap.error(str(exc))
     restored = denoise_image_diffusion(args.checkpoint, args.image, device_type=args.device, img_size=args.img_size,
                                        inference_steps=args.inference_steps, variant=args.variant, seed=args.seed,
                                        samples=args.samples, std_out=args.std_out, tile=args.tile, overlap=args.overlap,
                                        quantiles=levels, quantiles_out=args.quantiles_out, self_ensemble=args.self_ensemble,
                                        update=args.update, eta=args.eta, clip_x0=not args.no_clip_x0,
-                                       bit_depth=args.bit_depth)
+                                       bit_depth=args.bit_depth, **({} if window is None else {"window": window}),
+                                       **({} if window_levels is None else {"window_levels": window_levels}))
     restored.save(args.out, quality=95)
     print(f"\nResult saved: {args.out}")
 

@@ -55,8 +55,9 @@ extern "C" size_t mi_resize_f32_workspace_bytes(int n, int sw, int sh, int dw, i
     if (n < 1 || sw < 1 || sh < 1 || dw < 1 || dh < 1 || !resize_f32_fits(n, sw, sh, dw, dh)) return 0;
     return resize_f32_workspace_bytes(n, sw, sh, dw, dh);
 }
-extern "C" int mi_resize_bicubic_f32(const void* src, int src_type, int n, int sw, int sh, void* dst, int dst_type, int dw, int dh,
-                                     int clamp01, void* workspace, size_t workspace_bytes, void* stream) {
+// the argument rules shared by mi_resize_bicubic_f32 and its windowed form
+static int resize_f32_args(const void* src, int src_type, int n, int sw, int sh, void* dst, int dst_type, int dw, int dh,
+                           void* workspace, size_t workspace_bytes) {
     if (!src || !dst || !workspace) return fail(MI_EINVAL, "null argument");
     if (n < 1 || sw < 1 || sh < 1 || dw < 1 || dh < 1) return fail(MI_EINVAL, "image sizes must be positive");
     if (src_type != MI_PIX_U8 && src_type != MI_PIX_U16 && src_type != MI_PIX_F32)
@@ -69,6 +70,11 @@ extern "C" int mi_resize_bicubic_f32(const void* src, int src_type, int n, int s
     if (reinterpret_cast<uintptr_t>(workspace) & 255) return fail(MI_EINVAL, "workspace must be 256-byte aligned");
     if (workspace_bytes < resize_f32_workspace_bytes(n, sw, sh, dw, dh))
         return fail(MI_EINVAL, "workspace too small: %zu < %zu", workspace_bytes, resize_f32_workspace_bytes(n, sw, sh, dw, dh));
+    return MI_OK;
+}
+extern "C" int mi_resize_bicubic_f32(const void* src, int src_type, int n, int sw, int sh, void* dst, int dst_type, int dw, int dh,
+                                     int clamp01, void* workspace, size_t workspace_bytes, void* stream) {
+    if (const int rc = resize_f32_args(src, src_type, n, sw, sh, dst, dst_type, dw, dh, workspace, workspace_bytes)) return rc;
     HIPCHK(resize_bicubic_f32_launch(src, src_type, n, sw, sh, dst, dst_type, dw, dh, clamp01, workspace, static_cast<hipStream_t>(stream)));
     return MI_OK;
 }
@@ -82,6 +88,53 @@ extern "C" int mi_unit_f32_to_u16(const float* src, uint16_t* dst, size_t count,
     if (!src || !dst) return fail(MI_EINVAL, "null argument");
     if (count >= ((size_t)1 << 40)) return fail(MI_EINVAL, "count must stay below 2^40");
     HIPCHK(unit_to_u16_launch(src, dst, count, static_cast<hipStream_t>(stream)));
+    return MI_OK;
+}
+// ---- the window (include/midd.h: THE WINDOW)
+static int window_counts(int n, size_t count) {
+    if (n < 1 || n > 65535) return fail(MI_EINVAL, "n must be in [1, 65535], got %d", n);
+    if (count < 1 || count > 0xffffffffull) return fail(MI_EINVAL, "count must be in [1, 2^32), got %zu", count);
+    return MI_OK;
+}
+extern "C" int mi_histogram_u16(const uint16_t* src, int n, size_t count, uint32_t* hist, void* stream) {
+    if (!src || !hist) return fail(MI_EINVAL, "null argument");
+    if (const int rc = window_counts(n, count)) return rc;
+    if (reinterpret_cast<uintptr_t>(src) & 1) return fail(MI_EINVAL, "src must be 2-byte aligned");
+    if (reinterpret_cast<uintptr_t>(hist) & 15) return fail(MI_EINVAL, "hist must be 16-byte aligned");
+    HIPCHK(histogram_u16_launch(src, n, count, hist, static_cast<hipStream_t>(stream)));
+    return MI_OK;
+}
+extern "C" int mi_window_levels(const uint32_t* hist, int n, double p_lo, double p_hi, int32_t* levels, void* stream) {
+    if (!hist || !levels) return fail(MI_EINVAL, "null argument");
+    if (n < 1 || n > 65535) return fail(MI_EINVAL, "n must be in [1, 65535], got %d", n);
+    if (!std::isfinite(p_lo) || !std::isfinite(p_hi)) return fail(MI_EINVAL, "percentiles must be finite");
+    if (!(0.0 <= p_lo && p_lo < p_hi && p_hi <= 100.0))
+        return fail(MI_EINVAL, "percentiles must satisfy 0 <= p_lo < p_hi <= 100, got (%g, %g)", p_lo, p_hi);
+    if (reinterpret_cast<uintptr_t>(hist) & 15) return fail(MI_EINVAL, "hist must be 16-byte aligned");
+    HIPCHK(window_levels_launch(hist, n, p_lo, p_hi, levels, static_cast<hipStream_t>(stream)));
+    return MI_OK;
+}
+extern "C" int mi_window_u16_to_f32(const uint16_t* src, const int32_t* levels, int n, size_t count, float* dst, void* stream) {
+    if (!src || !levels || !dst) return fail(MI_EINVAL, "null argument");
+    if (const int rc = window_counts(n, count)) return rc;
+    HIPCHK(window_u16_to_f32_launch(src, levels, n, count, dst, static_cast<hipStream_t>(stream)));
+    return MI_OK;
+}
+extern "C" int mi_window_f32_to_u16(const float* src, const int32_t* levels, int n, size_t count, uint16_t* dst, void* stream) {
+    if (!src || !levels || !dst) return fail(MI_EINVAL, "null argument");
+    if (const int rc = window_counts(n, count)) return rc;
+    HIPCHK(window_f32_to_u16_launch(src, levels, n, count, dst, static_cast<hipStream_t>(stream)));
+    return MI_OK;
+}
+extern "C" int mi_resize_bicubic_f32_window(const void* src, int src_type, int n, int sw, int sh, void* dst, int dst_type, int dw, int dh,
+                                            int clamp01, const int32_t* levels, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!levels) return mi_resize_bicubic_f32(src, src_type, n, sw, sh, dst, dst_type, dw, dh, clamp01, workspace, workspace_bytes, stream);
+    if (const int rc = resize_f32_args(src, src_type, n, sw, sh, dst, dst_type, dw, dh, workspace, workspace_bytes)) return rc;
+    if (n > 65535) return fail(MI_EINVAL, "n must be in [1, 65535] under a window, got %d", n);
+    if (src_type != MI_PIX_U16 && dst_type != MI_PIX_U16)
+        return fail(MI_EINVAL, "levels given, but neither side is MI_PIX_U16: the window acts on 16-bit elements only");
+    HIPCHK(resize_bicubic_f32_window_launch(src, src_type, n, sw, sh, dst, dst_type, dw, dh, clamp01, levels, workspace,
+                                            static_cast<hipStream_t>(stream)));
     return MI_OK;
 }
 extern "C" size_t mi_metrics_workspace_bytes(int n, int h) { return (n < 1 || h < 1) ? 0 : metrics_workspace_bytes(n, h); }

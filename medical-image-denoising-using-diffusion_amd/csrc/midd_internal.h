@@ -168,6 +168,13 @@ hipError_t resize_bicubic_f32_launch(const void* src, int src_type, int n, int s
                                      int clamp, void* ws, hipStream_t s);
 hipError_t u16_to_unit_launch(const uint16_t* src, float* dst, size_t count, hipStream_t s);
 hipError_t unit_to_u16_launch(const float* src, uint16_t* dst, size_t count, hipStream_t s);
+// the window (include/midd.h: THE WINDOW): histogram [n][65536], levels [n][2] from percentiles, the element rules under them
+hipError_t histogram_u16_launch(const uint16_t* src, int n, size_t count, uint32_t* hist, hipStream_t s);
+hipError_t window_levels_launch(const uint32_t* hist, int n, double p_lo, double p_hi, int32_t* levels, hipStream_t s);
+hipError_t window_u16_to_f32_launch(const uint16_t* src, const int32_t* levels, int n, size_t count, float* dst, hipStream_t s);
+hipError_t window_f32_to_u16_launch(const float* src, const int32_t* levels, int n, size_t count, uint16_t* dst, hipStream_t s);
+hipError_t resize_bicubic_f32_window_launch(const void* src, int src_type, int n, int sw, int sh, void* dst, int dst_type, int dw, int dh,
+                                            int clamp, const int32_t* levels, void* ws, hipStream_t s);
 size_t metrics_workspace_bytes(int n, int h);
 hipError_t metrics_launch(const float* target, const float* pred, int n, int h, int w, double* out, void* ws, hipStream_t s);
 

@@ -137,6 +137,12 @@ SYMBOLS = [
                                         C.c_void_p, C.c_size_t, C.c_void_p]),
     ("mi_u16_to_unit_f32", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     ("mi_unit_f32_to_u16", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    ("mi_histogram_u16", C.c_int, [C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_void_p]),
+    ("mi_window_levels", C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_void_p, C.c_void_p]),
+    ("mi_window_u16_to_f32", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_void_p]),
+    ("mi_window_f32_to_u16", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_void_p]),
+    ("mi_resize_bicubic_f32_window", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                               C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     ("mi_metrics_workspace_bytes", C.c_size_t, [C.c_int, C.c_int]),
     ("mi_image_metrics", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                    C.c_void_p, C.c_size_t, C.c_void_p]),

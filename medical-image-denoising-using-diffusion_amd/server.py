@@ -28,6 +28,12 @@ four functions above, the ``"diffusion"`` value is a base64 16-bit PNG (mode "I;
 ``bit_depth``.  Only pre and post change, so it works with batch_slots > 0 and with update="ddim".  8, the default, is the
 reference's 8-bit contract, unchanged.
 
+``DiffusionService(bit_depth=16, window=(p_lo, p_hi))`` (or ``MIDD_WINDOW="0.5,99.5"``) windows every request between these
+percentiles of ITS OWN image (include/midd.h: THE WINDOW): the grey range [lo, hi] goes to the sampler as [0, 1] and comes back at
+the upload's own levels; values outside it come back as lo or hi (the window clips; ``(0, 100)`` clips nothing).  ``/health``
+reports ``window``.  It needs bit_depth=16, changes pre and post only (so it works with batch_slots > 0 and update="ddim"), and
+an upload that is not 16-bit is answered 400 with the file's mode.
+
 ``python-multipart`` is not available in this image, so the multipart body is parsed with the
 standard library instead of FastAPI's ``UploadFile``; the wire format is the same.
 """
@@ -130,6 +136,41 @@ def tensor_to_base64_16_device(tensor: torch.Tensor, size: Tuple[int, int]) -> s
     return base64.b64encode(image16.png_bytes_u16(back)).decode()
 
 
+def preprocess16_window(image_bytes: bytes, percentiles) -> Tuple[torch.Tensor, Tuple[int, int, Tuple[int, int]]]:
+    """`preprocess16` under a window (include/midd.h: THE WINDOW): the levels (lo, hi) at the two percentiles of THIS upload, the
+    windowed load, the mode "F" resize, the clip.  The second value carries the levels to the way back: (width, height, (lo, hi)).
+    An upload that is not 16-bit raises image16.WindowInputError naming its mode (the route answers 400)."""
+    image = Image.open(io.BytesIO(image_bytes))
+    raw = image16.need_u16(image16.decode16(image), image.mode)
+    levels = image16.window_levels(raw, percentiles)
+    x = image16.resize_f(image16.unit_float_window(raw, levels), SERVE_SIZE)
+    return torch.from_numpy(x)[None, None], image.size + (levels,)
+
+
+def tensor_to_base64_16_window(tensor: torch.Tensor, size) -> str:
+    """`tensor_to_base64_16` under the levels that preprocess16_window attached: resize back, clip, windowed store."""
+    x = tensor.reshape(tensor.shape[-2], tensor.shape[-1]).float().cpu().numpy()
+    return base64.b64encode(image16.png_bytes_u16(image16.to_u16_window(image16.resize_f(x, (size[1], size[0])), size[2]))).decode()
+
+
+def preprocess16_window_device(image_bytes: bytes, device: torch.device, percentiles):
+    """`preprocess16_window` on the GPU: histogram, levels, and one fused windowed load + resize + clip (csrc/prepost.hip).  The levels
+    stay on the device, an int32 [1,2] tensor in the place of (lo, hi): nothing waits for them."""
+    from . import prepost
+    image = Image.open(io.BytesIO(image_bytes))
+    raw = torch.from_numpy(image16.need_u16(image16.decode16(image), image.mode)).to(device, non_blocking=True)
+    levels = prepost.window_levels(raw, percentiles)
+    return prepost.resize_bicubic_f32(raw, SERVE_SIZE, clamp=True, levels=levels)[None, None], image.size + (levels,)
+
+
+def tensor_to_base64_16_window_device(tensor: torch.Tensor, size) -> str:
+    """`tensor_to_base64_16_window` with the resize back, the clip and the windowed store on the GPU."""
+    from . import prepost
+    plane = tensor.reshape(tensor.shape[-2], tensor.shape[-1]).float()
+    back = prepost.resize_bicubic_f32(plane, (size[1], size[0]), clamp=True, out_dtype=torch.uint16, levels=size[2]).cpu().numpy()
+    return base64.b64encode(image16.png_bytes_u16(back)).decode()
+
+
 def extract_multipart_file(body: bytes, content_type: str, field: str = "file") -> bytes:
     """Returns the payload of multipart form field ``field`` (stdlib parser)."""
     if "multipart/form-data" not in (content_type or ""):
@@ -148,10 +189,18 @@ class DiffusionService:
     def __init__(self, checkpoint: Optional[str] = None, device: Optional[torch.device] = None,
                  denoise_fn: Optional[Callable[[torch.Tensor], torch.Tensor]] = None, compute: Optional[str] = None,
                  batch_slots: Optional[int] = None, batch_invariant: Optional[bool] = None, session_factory=None,
-                 update: Optional[str] = None, eta: Optional[float] = None, bit_depth: Optional[int] = None):
+                 update: Optional[str] = None, eta: Optional[float] = None, bit_depth: Optional[int] = None,
+                 window: Optional[Tuple[float, float]] = None):
         # 8: the reference's 8-bit pre/post-processing; 16: the 16-bit recipe (preprocess16 / tensor_to_base64_16).  None reads
         # MIDD_BIT_DEPTH, default 8
         self.bit_depth = image16.check_bit_depth(int(os.environ.get("MIDD_BIT_DEPTH", "8")) if bit_depth is None else bit_depth)
+        # (p_lo, p_hi): every request is windowed between these percentiles of its own image (include/midd.h: THE WINDOW); None reads
+        # MIDD_WINDOW ("0.5,99.5"), default no window
+        if window is None and os.environ.get("MIDD_WINDOW"):
+            window = image16.parse_pair(os.environ["MIDD_WINDOW"], "MIDD_WINDOW")
+        self.window = None if window is None else image16.check_percentiles(window)
+        if self.window is not None and self.bit_depth != 16:
+            raise ValueError("a window needs bit_depth=16 (the window acts on 16-bit uploads)")
         # the sampler's update rule (DiffusionDenoiser.denoise): None reads MIDD_UPDATE / MIDD_ETA, default the reference's
         self.update = os.environ.get("MIDD_UPDATE", "reference") if update is None else update
         self.eta = float(os.environ.get("MIDD_ETA", "0")) if eta is None else float(eta)
@@ -202,7 +251,9 @@ class DiffusionService:
                 rule = {} if self.update == "reference" else {"update": self.update, "eta": self.eta}
                 output = self.diffusion_denoiser.denoise(input_tensor, inference_steps=SERVE_INFERENCE_STEPS, **rule)
             output = torch.clamp(output, 0, 1)
-            if self.bit_depth == 16:
+            if len(original_size) == 3:       # a windowed request: (width, height, levels)
+                result = (tensor_to_base64_16_window_device if output.is_cuda else tensor_to_base64_16_window)(output, original_size)
+            elif self.bit_depth == 16:
                 result = (tensor_to_base64_16_device if output.is_cuda else tensor_to_base64_16)(output, original_size)
             else:
                 result = (tensor_to_base64_device if output.is_cuda else tensor_to_base64)(output, original_size)
@@ -274,6 +325,11 @@ class DiffusionService:
 
     def preprocess(self, image_bytes: bytes) -> Tuple[torch.Tensor, Tuple[int, int]]:
         """Decode + resize + scale; on the GPU when the service runs there (same bytes either way)."""
+        if self.window is not None:
+            if self.device.type == "cuda" and self._denoise_fn is None:
+                return preprocess16_window_device(image_bytes, self.device, self.window)
+            x, size = preprocess16_window(image_bytes, self.window)
+            return x.to(self.device), size
         if self.device.type == "cuda" and self._denoise_fn is None:
             return (preprocess16_device if self.bit_depth == 16 else preprocess_device)(image_bytes, self.device)
         x, size = (preprocess16 if self.bit_depth == 16 else preprocess)(image_bytes)
@@ -315,12 +371,15 @@ def create_app(service: Optional[DiffusionService] = None, checkpoint: Optional[
             results = await svc.process_all_models(input_tensor, original_size)
             print(f"Total request time: {time.time() - total_start:.2f}s")
             return JSONResponse(content=results)
+        except image16.WindowInputError as e:                    # a window on an upload that is not 16-bit: the client's error
+            raise HTTPException(status_code=400, detail=str(e))
         except Exception as e:                                   # run.py:210-213
             raise HTTPException(status_code=500, detail=str(e))
 
     @app.get("/health")
     async def health_check():
         return {"status": "healthy", "device": str(svc.device), "batch_slots": svc.batch_slots, "bit_depth": svc.bit_depth,
+                "window": None if svc.window is None else list(svc.window),
                 "models_loaded": {"diffusion": svc.diffusion_model is not None or svc._denoise_fn is not None,
                                   "nafnet": False, "expert": False, "hybrid": False}}
 
