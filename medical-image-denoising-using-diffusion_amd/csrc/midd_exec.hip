@@ -611,7 +611,7 @@ extern "C" int mi_ensemble_reduce(const float* samples, int B, int members, int6
     return launched(ensemble_reduce_launch(samples, B, members, (unsigned long long)chw, mean_out, std_out, (hipStream_t)stream), "ensemble_reduce");
 }
 
-// the members of a pixel are sorted in registers (pointwise.hip: ensemble_quantiles_kernel): at most QUANTILE_MAX_MEMBERS of them
+// the members of a pixel are sorted in registers (ensemble.hip: ensemble_quantiles_kernel): at most QUANTILE_MAX_MEMBERS of them
 static int check_quantile_members(int members) {
     if (members > QUANTILE_MAX_MEMBERS)
         return fail(MI_EINVAL, "members %d: the quantile kernels sort a pixel's members in registers (limit: members <= %d; mean and std have no such limit)",

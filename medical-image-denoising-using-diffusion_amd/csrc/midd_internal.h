@@ -282,7 +282,7 @@ hipError_t out_conv_ddim_launch(const OutConvArgs& a, const DdimCoef& k, hipStre
 hipError_t step_noise_fill_launch(float* dst, int n_iters, int B, unsigned long long chw, unsigned long long seed, long long sample_offset,
                                   unsigned member, hipStream_t s);
 // samples [B][K][chw] -> mean [B][chw] and, when std != null (K >= 2), the unbiased std [B][chw]; fixed double-precision
-// arithmetic per pixel (pointwise.hip: ensemble_reduce_kernel).  B <= 65535, K >= 1
+// arithmetic per pixel (ensemble.hip: ensemble_reduce_kernel).  B <= 65535, K >= 1
 hipError_t ensemble_reduce_launch(const float* samples, int B, int K, unsigned long long chw, float* mean, float* std, hipStream_t s);
 // dst [n][chw] <- noisy[(v0 + j) / K]: the condition image of the n consecutive virtual samples from v0 (one pass of an ensemble)
 hipError_t ensemble_broadcast_launch(const float* noisy, float* dst, int v0, int n, int K, unsigned long long chw, hipStream_t s);

@@ -1,4 +1,4 @@
-// The out_conv kernel's text (pointwise.hip), compiled twice: MIDD_OUT_KERNEL = out_conv_kernel with MIDD_OUT_SEEDED 0 (the
+// The out_conv kernel's text (out_conv.hip), compiled twice: MIDD_OUT_KERNEL = out_conv_kernel with MIDD_OUT_SEEDED 0 (the
 // noise term of the sampler update, if any, is read from a.noise) and out_conv_seeded_kernel with MIDD_OUT_SEEDED 1 (the term is
 // drawn in the update from a.seed / a.sample_offset / a.iter: step_noise_common.h -- no noise tensor exists, 4 bytes per pixel
 // less are read; sample b of the launch is virtual sample a.v0 + b of an ensemble of a.members draws per image, image-major, or
@@ -24,7 +24,12 @@ void MIDD_OUT_KERNEL(const OutConvArgs a, const float* __restrict__ wglob /* == 
                      ) {
     __shared__ __attribute__((aligned(16))) float tile[OC_I * OC_I * OC_PS];
     static_assert(sizeof(tile) == out_conv_static_lds_bytes(), "out_conv_lds_bytes (midd_internal.h) counts this tile");
-    extern __shared__ __attribute__((aligned(16))) float wl[];       // [ic][9][C], then [2][C] GroupNorm scale / shift of this sample: out_conv_dynamic_lds_bytes
+    // No aligned(16) on purpose: it was written here and never took effect.  hipcc fixes the alignment of an `extern __shared__`
+    // array where a function that uses it is first emitted, and while this text shared a translation unit with in_conv_kernel
+    // that was in_conv_kernel's plain `float wl[]`.  The recorded instruction streams (profiles/step_noise_isa.txt;
+    // tests/test_ensemble_cpu.py: 8043 instructions for IC = 0) are those of a 4-byte aligned array, pairs of ds_read2_b32.  With
+    // the attribute in force the five IC = 0 kernels read with ds_read_b128 instead: a change that needs its own measurement.
+    extern __shared__ float wl[];                                    // [ic][9][C], then [2][C] GroupNorm scale / shift of this sample: out_conv_dynamic_lds_bytes
     const int ic = IC ? IC : a.ic;
     const int tid = threadIdx.x;
     const int tx = tid & 15, ty = tid >> 4;

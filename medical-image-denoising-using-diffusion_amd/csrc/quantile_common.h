@@ -1,5 +1,5 @@
-// Order statistics of a pixel's ensemble members in registers (include/midd.h: mi_ensemble_quantiles; pointwise.hip:
-// ensemble_quantiles_kernel, tile_blend_quantiles_kernel); tests/quantile_reference.py restates it in numpy.
+// Order statistics of a pixel's ensemble members in registers (include/midd.h: mi_ensemble_quantiles; ensemble.hip:
+// ensemble_quantiles_kernel, tiles.hip: tile_blend_quantiles_kernel, dihedral.hip: dihedral_quantiles_kernel); tests/quantile_reference.py restates it in numpy.
 //   key:      k = bits ^ (sign ? 0xFFFFFFFF : 0x80000000) -- an unsigned integer whose order is the total order
 //             -inf < ... < -0.0 < +0.0 < ... < +inf of the floats, so a compare-exchange is one unsigned min and one unsigned max:
 //             no NaN case, no signed-zero case; equal keys are equal bits, so the sorted sequence is unique
@@ -11,6 +11,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "pointwise_common.h"
 
 namespace midd {
 
@@ -80,6 +81,36 @@ __host__ __device__ __forceinline__ uint32_t pick_key_from(const uint32_t (&k)[N
 template <int N>
 __host__ __device__ __forceinline__ uint32_t pick_key(const uint32_t (&k)[N], int i) {
     return pick_key_from<N, 1>(k, i, k[0]);
+}
+
+// the interpolation between two order statistics, every operation rounded on its own (pointwise_common.h), and the level rules
+struct QuantilePos { int lo, hi; double g; };
+
+__device__ __forceinline__ QuantilePos quantile_pos(double q, int K) {
+    const double pos = mul_rn64(q, (double)(K - 1));
+    QuantilePos p;
+    p.lo = (int)floor(pos);
+    p.hi = min(p.lo + 1, K - 1);
+    p.g = sub_rn64(pos, (double)p.lo);
+    return p;
+}
+
+template <int KP>
+__device__ __forceinline__ float quantile_of_sorted(const uint32_t (&key)[KP], const QuantilePos& p, int K, bool has_nan) {
+    const float s_lo = __uint_as_float(order_bits(pick_key(key, p.lo)));
+    const float s_hi = __uint_as_float(order_bits(pick_key(key, p.hi)));
+    const float r = __double2float_rn(add_rn64((double)s_lo, mul_rn64(p.g, sub_rn64((double)s_hi, (double)s_lo))));
+    const float v = (K == 1) ? s_lo : r;                    // one member: every quantile is that member, bit for bit
+    return (has_nan || v != v) ? __uint_as_float(0x7FC00000u) : v;
+}
+
+__device__ __forceinline__ bool is_nan_bits(uint32_t bits) { return (bits & 0x7FFFFFFFu) > 0x7F800000u; }
+
+static inline bool quantile_levels_ok(const QuantileLevels& ql) {
+    if (ql.nq < 1 || ql.nq > QUANTILE_MAX_LEVELS) return false;
+    for (int i = 0; i < ql.nq; ++i)
+        if (!(ql.q[i] >= 0.0 && ql.q[i] <= 1.0)) return false;
+    return true;
 }
 
 }  // namespace midd

@@ -12,7 +12,7 @@
 //   one call per element; outputs x0, x1 are used:
 //   u1 = ((x0 >> 8) + 1) * 2^-24  in (0, 1]      u2 = (x1 >> 8) * 2^-24  in [0, 1)      (both exact in fp32)
 //   z  = sqrtf(-2 * logf(u1)) * cospif(2 * u2)   accurate library functions, every product rounded on its own; |z| <= 5.77
-// Used by out_conv_seeded_kernel (the fused sampler update) and step_noise_fill_kernel (replay / export), both in pointwise.hip:
+// Used by out_conv_seeded_kernel (the fused sampler update) and step_noise_fill_kernel (replay / export), both in out_conv.hip:
 // one function, so the two agree bit for bit.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -1,5 +1,5 @@
 // Geometry of tiled denoising (include/midd.h: mi_tile_geometry, mi_denoise_tiled): ONE set of functions for the host checks,
-// the extract / blend kernels and the seeded update (pointwise.hip); tests/tiled_reference.py restates it in numpy.
+// the extract / blend kernels (tiles.hip) and the seeded update (out_conv.hip); tests/tiled_reference.py restates it in numpy.
 // Per axis: an image length L is covered by n tiles of length T whose neighbours overlap by at least O (0 <= O <= T/2, T <= L):
 //   n = 1 if L == T, else max(2, ceil((L - O) / (T - O)))
 //   origin of tile i:  o_i = floor(i * (L - T) / (n - 1))   (o_0 = 0, o_{n-1} = L - T; n == 1: o_0 = 0)

@@ -15,6 +15,7 @@ import torch
 import midd_amd
 from midd_amd import DiffusionDenoiser, UNetDiffusion, native
 from tests import ensemble_reference as ens
+from tests.isa_dump import isa_dump
 from tests import step_noise_reference as ref
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -256,16 +257,8 @@ def test_cli_accepts_samples_and_std_out():
 
 # ------------------------------------------------------------------------------ static: the kernels' ISA
 @pytest.fixture(scope="module")
-def pointwise_isa(tmp_path_factory):
-    import shutil
-    import subprocess
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    assert os.path.exists(hipcc), "hipcc not found: the ISA checks cannot run (they must not be skipped)"
-    out = os.path.join(str(tmp_path_factory.mktemp("isa")), "pointwise.s")
-    src = os.path.join(ROOT, "medical-image-denoising-using-diffusion_amd", "csrc", "pointwise.hip")
-    subprocess.run([hipcc, "-O3", "-std=c++17", "--offload-arch=gfx950", "-S", "--cuda-device-only", src, "-o", out],
-                   check=True, capture_output=True, timeout=1200)
-    text = open(out).read()
+def pointwise_isa():
+    text = isa_dump("out_conv.hip") + isa_dump("ensemble.hip")
     kernels = {}
     for m in re.finditer(r"^(_ZN4midd\w+):", text, re.M):
         end = text.index(".end_amdhsa_kernel", m.start())

@@ -4,7 +4,7 @@ tests/test_gpu_multichannel.py):
   * the widths such a network may have.  in_conv_kernel and the out_conv kernels keep their weights in LDS and neither raises its
     limit, so (in_channels, model_channels) and (in_channels, model_channels * channel_mult[0]) are bounded by 64 KB per workgroup.
     mi_unet_plan_create refuses what the launch would refuse, naming the limit -- the byte counts are restated here from the kernels'
-    LDS layout (pointwise.hip, out_conv_body.h), independently of the library's own functions (midd_internal.h);
+    LDS layout (in_conv.hip, out_conv_body.h), independently of the library's own functions (midd_internal.h);
   * the workspace sizes grow by the documented C * H * W terms;
   * the 2^32 element-index rule of the seeded step noise counts C * H * W, not H * W.
 """

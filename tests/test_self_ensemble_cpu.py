@@ -5,8 +5,6 @@ scratch).  What the device computes is judged in test_gpu_self_ensemble.py."""
 import ctypes as C
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
@@ -15,6 +13,7 @@ import torch
 import midd_amd
 from midd_amd import DiffusionDenoiser, UNetDiffusion, native
 from tests import self_ensemble_reference as sref
+from tests.isa_dump import isa_dump
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SMALL = dict(model_channels=16, time_emb_dim=64)
@@ -341,14 +340,8 @@ def test_cli_refuses_what_is_out_of_scope(capsys):
 
 # ------------------------------------------------------------------------------ 5. static: the kernels' ISA
 @pytest.fixture(scope="module")
-def pointwise_isa(tmp_path_factory):
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    assert os.path.exists(hipcc), "hipcc not found: the ISA checks cannot run (they must not be skipped)"
-    out = os.path.join(str(tmp_path_factory.mktemp("isa")), "pointwise.s")
-    src = os.path.join(ROOT, "medical-image-denoising-using-diffusion_amd", "csrc", "pointwise.hip")
-    subprocess.run([hipcc, "-O3", "-std=c++17", "--offload-arch=gfx950", "-S", "--cuda-device-only", src, "-o", out],
-                   check=True, capture_output=True, timeout=1200)
-    return open(out).read()
+def pointwise_isa():
+    return isa_dump("dihedral.hip")
 
 
 def test_no_dihedral_kernel_touches_scratch_and_only_the_transposing_forms_use_lds(pointwise_isa):

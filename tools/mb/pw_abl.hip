@@ -1,7 +1,9 @@
 // Round-3 ablation harness for the HBM-bound ends (run on the GPU box): which part of in_conv / out_conv / resize costs the time.
 //   for n in 0 1 2 3 4 11 12 13; do hipcc -O3 -std=c++17 --offload-arch=gfx950 -DPW_ABL=$n tools/mb/pw_abl.hip -o tools/mb/pw_abl_$n; done
 // Each binary times the three kernels at B = 4, 256x256 (the sizes of a half-batch program), 20 repetitions.
-#include "../../medical-image-denoising-using-diffusion_amd/csrc/pointwise.hip"
+#include "../../medical-image-denoising-using-diffusion_amd/csrc/in_conv.hip"
+#include "../../medical-image-denoising-using-diffusion_amd/csrc/out_conv.hip"
+#include "../../medical-image-denoising-using-diffusion_amd/csrc/resample.hip"
 #include <cstdio>
 #ifndef PW_BLOCKED
 #define PW_BLOCKED 1      // activation layout of the split-fp16 plans (midd_internal.h)
