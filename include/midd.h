@@ -549,6 +549,57 @@ int mi_denoise_tiled_rule(mi_plan* plan, const float* noisy, float* image_out, f
                           int seeded, uint64_t seed, int64_t sample_offset, int pass_samples, int flags,
                           const mi_update_rule* rule, void* workspace, size_t workspace_bytes, void* stream);
 
+/* THE DPMPP2M UPDATE: a second-order multistep update for the sampler loop (Lu et al. 2022, DPM-Solver++(2M)) with its
+ * extrapolation weight bounded, opt-in.  The DDIM update above is first order and throws away the predicted image x0 that every
+ * iteration computes; this rule keeps the previous iteration's and extrapolates.  It costs no network evaluation and one
+ * image-sized buffer, which the caller owns -- and which, given one slot per iteration, is the trajectory of predicted images.
+ * Since x = sqrt(A) x0 + sqrt(1-A) eps, the 2M step is the DDIM (eta = 0) step plus one term:
+ *   x_next = a*x0 + b*e + g*(x0 - x0_prev)
+ * THE SPECIFICATION (fixed).  List, A and P as under THE DDIM UPDATE.
+ * Host, for the rows 0 < i < n-1, in double precision from the caller's fp32 table, every operation rounded on its own:
+ *   lambda(X) = 0.5 * log(X / (1-X))              (half the log-SNR)
+ *   h_i = lambda(P) - lambda(A)        r = h_{i-1} / h_i
+ *   emh = sqrt(((1-P)/(1-A)) * (A/P))             (= e^{-h_i}, without exp)
+ *   g   = sqrt(P) * (1 - emh) / (2 * max(r, 1))   rounded once to fp32
+ * g = 0 on the first row (no history) and on the last (P = 1: h is infinite).  The textbook weight is 1/(2r); max(r, 1) bounds it
+ * at its uniform-step value 1/2.  The reference's schedule jumps in log-SNR at t = 0 (h = 2.27 after 0.64 on the 9-entry list), r
+ * falls to 0.28 and the unbounded weight 1.8 makes the rule WORSE than DDIM on the short lists; bounded it is better on every one
+ * (the Gaussian check).  k0, k1, r0, r1, a, b are the DDIM table's at eta = 0, bit for bit.
+ * Device, per element, fp32, every operation rounded on its own (no fused multiply-add), in this order: the DDIM update's
+ *   e, x0 (clipped when clip_x0, eps re-derived), xn = a*x0 + b*e            -- the same text
+ *   if g != 0:   xn = xn + g * (x0 - x0_prev)         (x0, x0_prev: the clipped predictions)
+ *   if i == n-1: xn = min(max(xn, 0), 1)
+ *   x0 is stored
+ * g is launch-uniform; nothing of the history is read when g == 0.  Deterministic: there is no eta and no noise term, for either
+ * variant.  Start state and list rules as under THE DDIM UPDATE.  tests/dpm_update_reference.py restates host and device in numpy. */
+#define MI_UPDATE_DPMPP2M   2
+
+/* The coefficient table of the rule above, host only: out HOST fp32 [n_iters][8] <- (k0, k1, r0, r1, a, b, s, g).  The first seven
+ * columns are mi_ddim_coefficients at eta = 0, bit for bit (s is 0).  MI_EINVAL as mi_ddim_coefficients. */
+int mi_dpm_coefficients(const int32_t* t_list, int n_iters, const float* alpha_hat, int noise_steps, float* out);
+
+/* mi_denoise under the rule above.  x0_buf: the caller's DEVICE buffer fp32 [x0_slots, B, C, H, W] of predicted images, overlapping
+ * neither noisy nor x_out.  x0_slots == 1: the history, read and written in place (every thread reads its own element before it
+ * writes it); it ends as the last iteration's prediction.  x0_slots == n_iters: the trajectory -- iteration i reads slot i-1 and
+ * writes slot i.  Any other x0_slots is MI_EINVAL.  x_out is the same bits either way.  The buffer is never read before it is
+ * written: it needs no initialisation.  clip_x0 != 0 clips the predicted image to [0, 1] (then the last slot equals x_out).
+ * Everything else -- the forward, the two-stream split (each sub-batch owns its images of every slot), the workspace
+ * (mi_workspace_bytes: the rule needs none) -- is mi_denoise's.  The rule's MI_EINVAL cases are judged first, as in mi_denoise_rule.
+ * MI_UPDATE_DPMPP2M handed to the *_rule calls above is MI_EINVAL: they have no buffer. */
+int mi_denoise_dpm(mi_plan* plan, const float* noisy, float* x_out, float* x0_buf, int x0_slots, int B, int H, int W,
+                   const int32_t* t_list, int n_iters,
+                   const float* beta, const float* alpha, const float* alpha_hat, int noise_steps,
+                   int flags, int clip_x0, void* workspace, size_t workspace_bytes, void* stream);
+
+/* mi_denoise_tiled under the rule above (no seed: deterministic).  x0_hist: DEVICE fp32 [pass_samples, C, th, tw], the in-place
+ * history of whichever pass runs, reused by every pass; there is no trajectory for tiles.  Workspace: mi_tiled_workspace_bytes.
+ * NOT BUILT under this rule: mi_denoise_slots, ensembles of any kind (nothing is drawn), an SDE (eta > 0) form, a third order. */
+int mi_denoise_tiled_dpm(mi_plan* plan, const float* noisy, float* image_out, float* tiles_out, float* x0_hist,
+                         int B, int H, int W, int th, int tw, int oy, int ox,
+                         const int32_t* t_list, int n_iters,
+                         const float* beta, const float* alpha, const float* alpha_hat, int noise_steps,
+                         int pass_samples, int flags, int clip_x0, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Status of the last mi_unet_forward / mi_denoise call that used `workspace` (its first word; the calls clear it when they
  * start).  SYNCHRONISES `stream` (one 4-byte device-to-host copy).  Returns MI_OK with *flags == 0, or MI_ERANGE with the
  * MI_STATUS_* bits in *flags: the kernels never turn a NaN / Inf activation or an operand beyond the split-fp16 range into

@@ -9,7 +9,7 @@ img_size -> sampler -> uint8 -> bicubic resize back -> PNG, with the reference's
                            [--quantiles 0.05,0.5,0.95 --quantiles-out q.npy]]
                            [--tile N [--overlap O]]
                            [--self-ensemble [auto|flips|d4] [--std-out std.npy] [--quantiles Q,Q --quantiles-out q.npy]]
-                           [--update reference|ddim [--eta F] [--no-clip-x0]]
+                           [--update reference|ddim|dpmpp2m [--eta F] [--no-clip-x0] [--x0-out traj.npy]]
                            [--bit-depth 8|16 [--window P_LO,P_HI | --window-levels LO,HI]]
 
 Without a checkpoint (the trained weights are not distributed with the reference) the network is
@@ -39,7 +39,7 @@ def denoise_image_diffusion(model_path: Optional[str], test_image_path: str, dev
                             std_out: Optional[str] = None, tile: Optional[int] = None, overlap: int = 32,
                             quantiles: Optional[Sequence[float]] = None, quantiles_out: Optional[str] = None,
                             self_ensemble: Optional[str] = None, update: str = "reference", eta: float = 0.0,
-                            clip_x0: bool = True, bit_depth: int = 8, window: Optional[Sequence[float]] = None,
+                            clip_x0: bool = True, x0_out: Optional[str] = None, bit_depth: int = 8, window: Optional[Sequence[float]] = None,
                             window_levels: Optional[Sequence[int]] = None) -> Image.Image:
     """compute (not a reference argument): arithmetic of the network, see UNetDiffusion -- None keeps the default.
     seed (not a reference argument; cddpm): the stochastic sampler's noise is drawn on the device from this seed, so the same
@@ -57,7 +57,9 @@ def denoise_image_diffusion(model_path: Optional[str], test_image_path: str, dev
     describe the views instead of seeded draws.  Not together with samples or tile.
     update, eta, clip_x0 (not reference arguments; both variants): "ddim" runs the stride-aware DDIM(eta) update
     (DiffusionDenoiser.denoise) in the place of the reference's; with eta > 0 samples works for the DDIM variant too.  Not together
-    with self_ensemble.
+    with self_ensemble.  "dpmpp2m" runs the second-order multistep update: deterministic, so not together with eta, seed, samples
+    or step_noise; x0_out (that rule only, not with tile): the predicted image of every iteration is saved there as float32
+    [iterations, img_size, img_size].
     bit_depth (not a reference argument): 8 is the reference's recipe, unchanged.  16 keeps a 16-bit file's 65536 levels (image16.py;
     include/midd.h: THE FLOAT RESIZE): decode to unit float (/ 65535; any other file: `convert("L")` / 255), float bicubic resize to
     img_size and clip, the sampler, float resize back, clip, and a mode "I;16" image rounded to nearest -- with tile no resize at
@@ -80,7 +82,13 @@ def denoise_image_diffusion(model_path: Optional[str], test_image_path: str, dev
         window_levels = image16.check_levels(window_levels)
     rule = {} if check_update(update, eta, clip_x0) is None else {"update": update, "eta": eta, "clip_x0": clip_x0}
     if rule and self_ensemble is not None:
-        raise ValueError("--update ddim cannot be combined with --self-ensemble (the self-ensemble runs the reference's update only)")
+        raise ValueError(f"--update {update} cannot be combined with --self-ensemble (the self-ensemble runs the reference's update only)")
+    if update == "dpmpp2m":
+        if seed is not None or samples is not None or step_noise is not None:
+            raise ValueError("--update dpmpp2m is deterministic: it takes no --seed, --samples or step_noise")
+        rule = {"update": update, "clip_x0": clip_x0}
+    if x0_out is not None and (update != "dpmpp2m" or tile is not None):
+        raise ValueError("--x0-out needs --update dpmpp2m and no --tile: the trajectory of predicted images is that rule's")
     if self_ensemble is not None:
         if samples is not None:
             raise ValueError("--self-ensemble cannot be combined with --samples")
@@ -200,6 +208,9 @@ def denoise_image_diffusion(model_path: Optional[str], test_image_path: str, dev
             np.save(std_out, ens.std.reshape(img_size, img_size).cpu().numpy())
         if quantiles is not None:
             np.save(quantiles_out, ens.quantiles.reshape(len(quantiles), img_size, img_size).cpu().numpy())
+    elif x0_out is not None:
+        denoised, traj = diffusion.denoise(input_tensor, inference_steps=inference_steps, return_x0=True, **rule)
+        np.save(x0_out, traj.reshape(traj.shape[0], img_size, img_size).cpu().numpy())      # float32 [n_iters, H, W], model resolution
     else:
         denoised = diffusion.denoise(input_tensor, inference_steps=inference_steps, **kw, **rule)
     if device.type == "cuda":
@@ -254,10 +265,13 @@ def main(argv=None) -> None:
     ap.add_argument("--self-ensemble", nargs="?", const="auto", default=None, choices=["auto", "flips", "d4"],
                     help="both variants: save the mean over the flipped and rotated views of the image (auto: all 8); --std-out and "
                          "--quantiles / --quantiles-out then describe the views")
-    ap.add_argument("--update", default="reference", choices=["reference", "ddim"],
-                    help="the sampler's update rule: reference (one-step ancestral, the default) or ddim (stride-aware DDIM(eta) step)")
+    ap.add_argument("--update", default="reference", choices=["reference", "ddim", "dpmpp2m"],
+                    help="the sampler's update rule: reference (one-step ancestral, the default), ddim (stride-aware DDIM(eta) step) or "
+                         "dpmpp2m (second-order multistep step, deterministic)")
     ap.add_argument("--eta", type=float, default=0.0, help="with --update ddim: 0 (deterministic, the default) .. 1 (ancestral)")
-    ap.add_argument("--no-clip-x0", action="store_true", help="with --update ddim: do not clip the predicted image to [0, 1]")
+    ap.add_argument("--no-clip-x0", action="store_true", help="with --update ddim or dpmpp2m: do not clip the predicted image to [0, 1]")
+    ap.add_argument("--x0-out", default=None, metavar="PATH.npy",
+                    help="with --update dpmpp2m: write the predicted image of every iteration (float32 [iterations, H, W], model resolution)")
     ap.add_argument("--bit-depth", type=int, default=8, choices=[8, 16],
                     help="8 (the default): the reference's 8-bit recipe; 16: keep a 16-bit file's levels -- float resize, 16-bit PNG out")
     ap.add_argument("--window", default=None, metavar="P_LO,P_HI",
@@ -271,8 +285,12 @@ def main(argv=None) -> None:
         ap.error("--eta and --no-clip-x0 need --update ddim")
     if not 0.0 <= args.eta <= 1.0:
         ap.error("--eta needs a value in [0, 1]")
-    if args.update == "ddim" and args.self_ensemble is not None:
-        ap.error("--update ddim cannot be combined with --self-ensemble")
+    if args.update == "dpmpp2m" and (args.eta != 0.0 or args.seed is not None or args.samples is not None):
+        ap.error("--update dpmpp2m is deterministic: it takes no --eta, --seed or --samples")
+    if args.x0_out is not None and (args.update != "dpmpp2m" or args.tile is not None):
+        ap.error("--x0-out needs --update dpmpp2m and no --tile")
+    if args.update != "reference" and args.self_ensemble is not None:
+        ap.error(f"--update {args.update} cannot be combined with --self-ensemble")
     if args.self_ensemble is not None and args.samples is not None:
         ap.error("--self-ensemble cannot be combined with --samples")
     if args.self_ensemble is not None and args.tile is not None:
@@ -310,6 +328,7 @@ def main(argv=None) -> None:
                                        samples=args.samples, std_out=args.std_out, tile=args.tile, overlap=args.overlap,
                                        quantiles=levels, quantiles_out=args.quantiles_out, self_ensemble=args.self_ensemble,
                                        update=args.update, eta=args.eta, clip_x0=not args.no_clip_x0,
+                                       **({} if args.x0_out is None else {"x0_out": args.x0_out}),
                                        bit_depth=args.bit_depth, **({} if window is None else {"window": window}),
                                        **({} if window_levels is None else {"window_levels": window_levels}))
     restored.save(args.out, quality=95)

@@ -21,6 +21,9 @@ struct StepNoise {
 struct Schedule {
     const int32_t* t; int n; const float *beta, *alpha, *alpha_hat; int noise_steps;
     int ddim = 0; double eta = 0.0; int clip_x0 = 1;
+    // dpm != 0 (include/midd.h: THE DPMPP2M UPDATE; ddim stays 0): the caller's history of predicted images, one run's worth
+    // [slots][B, C, H, W] -- x0_stride 0: one slot, read and written in place; else the elements between two slots of the trajectory
+    int dpm = 0; float* x0 = nullptr; size_t x0_stride = 0;
 };
 
 struct StepIO {
@@ -28,6 +31,9 @@ struct StepIO {
     float* x_update; const float* noise; float c1, c2, c3; int clamp_eps;
     // ddim != 0: the update is the DDIM(eta) rule with this row of the coefficient table (out_conv_ddim_launch); c1 .. c3 are not read
     int ddim; DdimCoef coef;
+    // dpm != 0: the second-order multistep rule instead (out_conv_dpm_launch): its row, the previous predicted image (read when
+    // dcoef.g != 0) and where this iteration's is written; of the fields above the update reads x_update and clamp_eps only
+    int dpm; DpmCoef dcoef; const float* x0_prev; float* x0_out;
     // sn.seeded: the update draws its noise term (step_noise_common.h) for iteration `iter`, sample 0 of THIS program being virtual
     // sample sn.v0; a step that draws nothing keeps the defaults (sn.tensor is not read: `noise` is this step's slice of it)
     int iter; StepNoise sn;
@@ -144,7 +150,8 @@ static int run_program(mi_plan* p, Program* g, const StepIO& io, char* ws, int* 
                 a.seeded = n.seeded; a.iter = io.iter; a.seed = n.seed; a.sample_offset = n.sample_offset;
                 a.v0 = n.v0; a.members = n.members > 0 ? n.members : 1; a.member_offset = n.member_offset;
                 a.tiles_x = n.tiles_x; a.tiles_y = n.tiles_y; a.img_H = n.img_H; a.img_W = n.img_W;
-                e = io.slots ? out_conv_slots_launch(a, io.slots, s) : io.ddim ? out_conv_ddim_launch(a, io.coef, s) : out_conv_launch(a, s);
+                e = io.slots ? out_conv_slots_launch(a, io.slots, s) : io.ddim ? out_conv_ddim_launch(a, io.coef, s)
+                  : io.dpm ? out_conv_dpm_launch(a, io.dcoef, io.x0_prev, io.x0_out, s) : out_conv_launch(a, s);
                 break;
             }
         }
@@ -158,9 +165,9 @@ static int run_program(mi_plan* p, Program* g, const StepIO& io, char* ws, int* 
             mi_plan::Span sp; sp.a = ev_a; sp.b = ev_b;
             op_work(p, g, o, &sp.name, &sp.flops, &sp.bytes);
             const size_t oc_at = sp.name.find("out_conv_kernel");
-            if (o.kind == OP_OUT && (io.sn.seeded || io.slots || io.ddim) && oc_at != std::string::npos)      // the symbol that ran
+            if (o.kind == OP_OUT && (io.sn.seeded || io.slots || io.ddim || io.dpm) && oc_at != std::string::npos)      // the symbol that ran
                 sp.name.replace(oc_at, 15, io.slots ? "out_conv_slots_kernel" : io.ddim ? (io.sn.seeded ? "out_conv_ddim_seeded_kernel" : "out_conv_ddim_kernel")
-                                                                             : "out_conv_seeded_kernel");
+                                                                             : io.dpm ? "out_conv_dpm_kernel" : "out_conv_seeded_kernel");
             static const bool per_op = getenv("MIDD_PROFILE_PER_OP") != nullptr;      // one entry per op instead of per symbol
             if (per_op) {
                 char tag[96];
@@ -251,10 +258,42 @@ extern "C" int mi_ddim_coefficients(const int32_t* t_list, int n_iters, const fl
     return MI_OK;
 }
 
+// THE DPMPP2M UPDATE, host side (include/midd.h): the multistep weight of row i, in double precision from the caller's fp32 table,
+// every operation rounded on its own, rounded once to fp32.  0 on the first row (no history) and on the last (P = 1, h infinite).
+// The one place that computes it: mi_dpm_coefficients exports it, enqueue_run passes it to the update kernel.
+static double dpm_lambda(double X) {
+#pragma clang fp contract(off)
+    return 0.5 * std::log(X / (1.0 - X));
+}
+static float dpm_g(const int32_t* t, int n, const float* alpha_hat, int i) {
+#pragma clang fp contract(off)
+    if (i < 1 || i + 1 >= n) return 0.0f;
+    const double Q = (double)alpha_hat[t[i - 1]], A = (double)alpha_hat[t[i]], P = (double)alpha_hat[t[i + 1]];
+    const double lA = dpm_lambda(A);
+    const double h = dpm_lambda(P) - lA, h_prev = lA - dpm_lambda(Q);
+    const double r = h_prev / h;
+    const double emh = std::sqrt(((1.0 - P) / (1.0 - A)) * (A / P));      // e^{-h} without exp
+    // the extrapolation weight 1 / (2 r) bounded at its uniform-step value 1/2 (why)
+    return (float)(std::sqrt(P) * (1.0 - emh) / (2.0 * (r > 1.0 ? r : 1.0)));
+}
+
+extern "C" int mi_dpm_coefficients(const int32_t* t_list, int n_iters, const float* alpha_hat, int noise_steps, float* out) {
+    if (int rc = check_ddim(t_list, n_iters, alpha_hat, noise_steps, 0.0)) return rc;
+    if (n_iters > 0 && !out) return fail(MI_EINVAL, "null argument");
+    for (int i = 0; i < n_iters; ++i) {
+        ddim_row(t_list, n_iters, alpha_hat, 0.0, i, out + (size_t)i * 8);
+        out[(size_t)i * 8 + 7] = dpm_g(t_list, n_iters, alpha_hat, i);
+    }
+    return MI_OK;
+}
+
 // A call's rule -> its Schedule.  NULL or kind MI_UPDATE_REFERENCE: the schedule stays the reference's.  Judged first in every
 // *_rule call, so a bad rule or list is MI_EINVAL whatever the plan's state.
 static int apply_rule(const mi_update_rule* rule, Schedule* sc) {
     if (!rule || rule->kind == MI_UPDATE_REFERENCE) return MI_OK;
+    if (rule->kind == MI_UPDATE_DPMPP2M)
+        return fail(MI_EINVAL, "update rule MI_UPDATE_DPMPP2M needs a buffer for the predicted images, which this call does not take: "
+                    "call mi_denoise_dpm or mi_denoise_tiled_dpm");
     if (rule->kind != MI_UPDATE_DDIM) return fail(MI_EINVAL, "unknown update rule %d (MI_UPDATE_REFERENCE or MI_UPDATE_DDIM)", (int)rule->kind);
     if (int rc = check_ddim(sc->t, sc->n, sc->alpha_hat, sc->noise_steps, rule->eta)) return rc;
     sc->ddim = 1; sc->eta = rule->eta; sc->clip_x0 = rule->clip_x0 ? 1 : 0;
@@ -397,6 +436,15 @@ static int enqueue_run(mi_plan* plan, Program* g, const float* noisy, float* x_o
                         io.ddim = 1;
                         io.coef = DdimCoef{r[0], r[1], r[2], r[3], r[4], r[5], r[6], sc.clip_x0, i == n_iters - 1 ? 1 : 0};
                         draws = r[6] > 0.0f;                         // nor at s == 0: every row at eta == 0, always the last one
+                    } else if (sc.dpm) {
+                        float r[7];
+                        ddim_row(sc.t, n_iters, alpha_hat, 0.0, i, r);
+                        io.dpm = 1;
+                        io.dcoef = DpmCoef{r[0], r[1], r[2], r[3], r[4], r[5], dpm_g(sc.t, n_iters, alpha_hat, i), sc.clip_x0, i == n_iters - 1 ? 1 : 0};
+                        // iteration i reads slot i - 1 and writes slot i (in place when there is one slot); sub-batch h: its images
+                        io.x0_out = sc.x0 + (size_t)i * sc.x0_stride + h * part;
+                        io.x0_prev = i > 0 ? sc.x0 + (size_t)(i - 1) * sc.x0_stride + h * part : io.x0_out;      // (i == 0: g == 0, not read)
+                        draws = false;                               // deterministic: no noise term
                     } else {
                         coeffs(t, &io.c1, &io.c2, &io.c3);
                     }
@@ -491,6 +539,26 @@ extern "C" int mi_denoise_rule(mi_plan* plan, const float* noisy, float* x_out, 
         sn.tensor = step_noise;
     }
     return denoise_run(plan, noisy, x_out, B, H, W, sc, sn, flags, workspace, workspace_bytes, stream);
+}
+
+// The second-order multistep rule (include/midd.h: THE DPMPP2M UPDATE): mi_denoise plus the caller's buffer of predicted images
+extern "C" int mi_denoise_dpm(mi_plan* plan, const float* noisy, float* x_out, float* x0_buf, int x0_slots, int B, int H, int W,
+                              const int32_t* t_list, int n_iters,
+                              const float* beta, const float* alpha, const float* alpha_hat, int noise_steps,
+                              int flags, int clip_x0, void* workspace, size_t workspace_bytes, void* stream) {
+    Schedule sc{t_list, n_iters, beta, alpha, alpha_hat, noise_steps};
+    if (int rc = check_ddim(t_list, n_iters, alpha_hat, noise_steps, 0.0)) return rc;      // the rule's own cases first, as mi_denoise_rule
+    if (x0_slots != 1 && x0_slots != n_iters)
+        return fail(MI_EINVAL, "x0_slots %d: 1 (the history in place) or n_iters = %d (the trajectory of predicted images)", x0_slots, n_iters);
+    if (!plan) return fail(MI_EINVAL, "null plan");
+    if (n_iters > 0 && !x0_buf) return fail(MI_EINVAL, "null argument");
+    if (B < 1 || H < 1 || W < 1) return fail(MI_EINVAL, "bad image shape %dx%dx%d", B, H, W);
+    const size_t img_elems = (size_t)B * plan->cfg.in_channels * H * W;
+    const Buf buf[3] = {{noisy, img_elems * sizeof(float), "noisy"}, {x_out, img_elems * sizeof(float), "x_out"},
+                        {x0_buf, (size_t)x0_slots * img_elems * sizeof(float), "x0_buf"}};
+    if (int rc = check_no_overlap(buf, 3, "noisy is read every step and x0_buf is written beside x_out")) return rc;
+    sc.dpm = 1; sc.clip_x0 = clip_x0 ? 1 : 0; sc.x0 = x0_buf; sc.x0_stride = x0_slots > 1 ? img_elems : 0;
+    return denoise_run(plan, noisy, x_out, B, H, W, sc, StepNoise{}, flags, workspace, workspace_bytes, stream);
 }
 
 // ---------------------------------------------------------------------------- per-slot timesteps (continuous batching)
@@ -798,21 +866,21 @@ extern "C" int mi_tile_blend(const float* tiles, int B, int C, int H, int W, int
     return launched(tile_blend_launch(tiles, out, B, g, (hipStream_t)stream), "tile_blend");
 }
 
-extern "C" int mi_denoise_tiled_rule(mi_plan* plan, const float* noisy, float* image_out, float* tiles_out,
-                                     int B, int H, int W, int th, int tw, int oy, int ox,
-                                     const int32_t* t_list, int n_iters,
-                                     const float* beta, const float* alpha, const float* alpha_hat, int noise_steps,
-                                     int seeded, uint64_t seed, int64_t sample_offset, int pass_samples, int flags,
-                                     const mi_update_rule* rule, void* workspace, size_t workspace_bytes, void* stream) {
-    Schedule sc{t_list, n_iters, beta, alpha, alpha_hat, noise_steps};
-    if (int rc = apply_rule(rule, &sc)) return rc;
+// mi_denoise_tiled_rule and mi_denoise_tiled_dpm behind their rules: `sc` carries the rule.  sc.dpm: sc.x0 is the call's x0_hist
+// [pass_samples, C, th, tw], the in-place history of whichever pass runs
+static int tiled_run(mi_plan* plan, const float* noisy, float* image_out, float* tiles_out,
+                     int B, int H, int W, int th, int tw, int oy, int ox, const Schedule& sc,
+                     int seeded, uint64_t seed, int64_t sample_offset, int pass_samples, int flags,
+                     void* workspace, size_t workspace_bytes, void* stream) {
     TileGeom tg{};
     if (int rc = check_tiled_args(plan, B, H, W, th, tw, oy, ox, sample_offset, pass_samples, &tg)) return rc;
     const int K = tg.ny * tg.nx;
     const size_t chw = (size_t)tg.C * th * tw, img = (size_t)tg.C * H * W * sizeof(float);
-    const Buf buf[3] = {{noisy, (size_t)B * img, "noisy"}, {image_out, (size_t)B * img, "image_out"},
-                        {tiles_out, (size_t)B * K * chw * sizeof(float), "tiles_out"}};
-    if (int rc = check_no_overlap(buf, 3, "noisy is read by every pass and the blend reads the tiles while it writes image_out")) return rc;
+    if (sc.dpm && sc.n > 0 && !sc.x0) return fail(MI_EINVAL, "null argument");
+    const Buf buf[4] = {{noisy, (size_t)B * img, "noisy"}, {image_out, (size_t)B * img, "image_out"},
+                        {tiles_out, (size_t)B * K * chw * sizeof(float), "tiles_out"},
+                        {sc.dpm ? sc.x0 : nullptr, (size_t)pass_samples * chw * sizeof(float), "x0_hist"}};
+    if (int rc = check_no_overlap(buf, 4, "noisy is read by every pass and the blend reads the tiles while it writes image_out")) return rc;
     EnsembleLayout L{};
     // (evaluated before the state check, reported after it: check_batched_call; host arithmetic only, as in the *_workspace_bytes queries)
     const int layout_rc = ensemble_layout(plan, B, K, th, tw, pass_samples, tiles_out != nullptr, &L);
@@ -830,6 +898,32 @@ extern "C" int mi_denoise_tiled_rule(mi_plan* plan, const float* noisy, float* i
     auto extract = [&](float* cond, int v0, int n) { return launched(tile_extract_launch(noisy, cond, tg, v0, n, s), "tile_extract"); };
     if (int rc = run_passes(plan, extract, tiles, (int64_t)B * K, 1, th, tw, chw, L, sn, sc, flags, ws, stream)) return rc;
     return launched(tile_blend_launch(tiles, image_out, B, tg, s), "tile_blend");
+}
+
+extern "C" int mi_denoise_tiled_rule(mi_plan* plan, const float* noisy, float* image_out, float* tiles_out,
+                                     int B, int H, int W, int th, int tw, int oy, int ox,
+                                     const int32_t* t_list, int n_iters,
+                                     const float* beta, const float* alpha, const float* alpha_hat, int noise_steps,
+                                     int seeded, uint64_t seed, int64_t sample_offset, int pass_samples, int flags,
+                                     const mi_update_rule* rule, void* workspace, size_t workspace_bytes, void* stream) {
+    Schedule sc{t_list, n_iters, beta, alpha, alpha_hat, noise_steps};
+    if (int rc = apply_rule(rule, &sc)) return rc;
+    return tiled_run(plan, noisy, image_out, tiles_out, B, H, W, th, tw, oy, ox, sc, seeded, seed, sample_offset, pass_samples, flags,
+                     workspace, workspace_bytes, stream);
+}
+
+// mi_denoise_tiled under the second-order multistep rule: deterministic, so no seed; the history of a pass lives in x0_hist
+extern "C" int mi_denoise_tiled_dpm(mi_plan* plan, const float* noisy, float* image_out, float* tiles_out, float* x0_hist,
+                                    int B, int H, int W, int th, int tw, int oy, int ox,
+                                    const int32_t* t_list, int n_iters,
+                                    const float* beta, const float* alpha, const float* alpha_hat, int noise_steps,
+                                    int pass_samples, int flags, int clip_x0, void* workspace, size_t workspace_bytes, void* stream) {
+    Schedule sc{t_list, n_iters, beta, alpha, alpha_hat, noise_steps};
+    if (int rc = check_ddim(t_list, n_iters, alpha_hat, noise_steps, 0.0)) return rc;
+    if (n_iters > 0 && !x0_hist) return fail(MI_EINVAL, "null argument");
+    sc.dpm = 1; sc.clip_x0 = clip_x0 ? 1 : 0; sc.x0 = x0_hist; sc.x0_stride = 0;
+    return tiled_run(plan, noisy, image_out, tiles_out, B, H, W, th, tw, oy, ox, sc, 0, 0, 0, pass_samples, flags,
+                     workspace, workspace_bytes, stream);
 }
 
 extern "C" int mi_denoise_tiled(mi_plan* plan, const float* noisy, float* image_out, float* tiles_out,

@@ -278,6 +278,17 @@ struct DdimCoef {
 // a.seeded != 0 (host: only with k.s > 0): the term s * noise is drawn as out_conv_seeded_kernel draws it; else it is read from
 // a.noise when that is given and k.s > 0
 hipError_t out_conv_ddim_launch(const OutConvArgs& a, const DdimCoef& k, hipStream_t s);
+// The second-order multistep update (include/midd.h: THE DPMPP2M UPDATE): the DDIM row at eta = 0 (s == 0 is not carried) and the
+// multistep weight g, a kernel argument of out_conv_dpm_kernel alone (scalar loads).  OutConvArgs does not grow here either.
+struct DpmCoef {
+    float k0, k1, r0, r1, a, b;     // as DdimCoef
+    float g;                        // sqrt(P) (1 - e^-h) / (2 max(r, 1)); 0 on the first and the last row: x0_prev is not read
+    int clip_x0;
+    int last;
+};
+// x0_prev (read when k.g != 0) and x0_out (written) are [a.B, ic, H, W] fp32 and may be the same address: each thread reads its
+// own element before it writes it.  The rule is deterministic: a.seeded or a.noise is refused.
+hipError_t out_conv_dpm_launch(const OutConvArgs& a, const DpmCoef& k, const float* x0_prev, float* x0_out, hipStream_t s);
 // dst [n_iters][B][chw] <- the 0.5-scaled seeded step noise of `member` (step_noise_common.h); chw < 2^32, B and n_iters <= 65535
 hipError_t step_noise_fill_launch(float* dst, int n_iters, int B, unsigned long long chw, unsigned long long seed, long long sample_offset,
                                   unsigned member, hipStream_t s);

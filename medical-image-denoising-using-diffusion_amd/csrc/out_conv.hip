@@ -5,6 +5,7 @@
 //                      (DDIMModel.py:278-284; cddpm noise term cddpmModels.py:297-303)
 //   out_conv_seeded_kernel : the same with the noise term drawn in the update (step_noise_common.h)
 //   out_conv_ddim_kernel, out_conv_ddim_seeded_kernel : the same two with the DDIM(eta) update in the place of the reference's
+//   out_conv_dpm_kernel    : the same with the second-order multistep update (DPM-Solver++(2M), bounded weight); writes x0
 //   out_conv_slots_kernel  : the same with every sample at its own timestep: coefficients, counter words and the active
 //                      flag from the sample's SlotRec (mi_denoise_slots); slot_fill_kernel writes a row's records
 //   step_noise_fill_kernel : the same noise values as a [n_iters,B,C,H,W] tensor (replay / export)
@@ -32,6 +33,7 @@ __device__ __forceinline__ float silu_pw(float v) {
 // 7 340 instructions, 989 v_cndmask among them, for a loop of 432 multiply-adds (round 3; tools/isa_count.py).
 #define MIDD_OUT_SLOTS 0
 #define MIDD_OUT_DDIM 0
+#define MIDD_OUT_DPM 0
 #define MIDD_OUT_KERNEL out_conv_kernel
 #define MIDD_OUT_SEEDED 0
 #include "out_conv_body.h"
@@ -67,6 +69,19 @@ __device__ __forceinline__ float silu_pw(float v) {
 #undef MIDD_OUT_SEEDED
 #undef MIDD_OUT_SLOTS
 #undef MIDD_OUT_DDIM
+#undef MIDD_OUT_DPM
+// the second-order multistep update (include/midd.h: THE DPMPP2M UPDATE): deterministic, so one form; coefficients in a DpmCoef argument
+#define MIDD_OUT_SLOTS 0
+#define MIDD_OUT_DDIM 0
+#define MIDD_OUT_DPM 1
+#define MIDD_OUT_KERNEL out_conv_dpm_kernel
+#define MIDD_OUT_SEEDED 0
+#include "out_conv_body.h"
+#undef MIDD_OUT_KERNEL
+#undef MIDD_OUT_SEEDED
+#undef MIDD_OUT_SLOTS
+#undef MIDD_OUT_DDIM
+#undef MIDD_OUT_DPM
 
 // What every out_conv launch refuses, and what it launches with: the dynamic LDS of (ic, C) and the 16x16 tiles of a sample
 static bool out_conv_shape_ok(const OutConvArgs& a, size_t* lds, int* tiles) {
@@ -120,6 +135,15 @@ hipError_t out_conv_ddim_launch(const OutConvArgs& a, const DdimCoef& k, hipStre
         if (a.noise || !out_conv_seeded_ok(a)) return hipErrorInvalidValue;
         MIDD_OUT_LAUNCH(out_conv_ddim_seeded_kernel, a, a.w, k);
     } else MIDD_OUT_LAUNCH(out_conv_ddim_kernel, a, a.w, k);
+    return hipGetLastError();
+}
+
+// a.c1 .. a.c3, a.noise and the seeded fields are not read: the rule has no noise term.  x0_prev is read only when k.g != 0
+hipError_t out_conv_dpm_launch(const OutConvArgs& a, const DpmCoef& k, const float* x0_prev, float* x0_out, hipStream_t s) {
+    size_t lds; int tiles;
+    if (!out_conv_shape_ok(a, &lds, &tiles) || !a.x || !x0_out || (k.g != 0.0f && !x0_prev)) return hipErrorInvalidValue;
+    if (a.seeded || a.noise) return hipErrorInvalidValue;
+    MIDD_OUT_LAUNCH(out_conv_dpm_kernel, a, a.w, k, x0_prev, x0_out);
     return hipGetLastError();
 }
 #undef MIDD_OUT_LAUNCH

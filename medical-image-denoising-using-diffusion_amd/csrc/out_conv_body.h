@@ -12,6 +12,9 @@
 // Two more, MIDD_OUT_DDIM 1 = out_conv_ddim_kernel (MIDD_OUT_SEEDED 0) and out_conv_ddim_seeded_kernel (1): the DDIM(eta) update of
 // include/midd.h (THE DDIM UPDATE) in the place of the reference's, its coefficients in a kernel argument of their own (DdimCoef,
 // scalar loads).  The three compiles above do not see a token of it either.
+// A sixth, MIDD_OUT_DPM 1 = out_conv_dpm_kernel: the second-order multistep update of include/midd.h (THE DPMPP2M UPDATE) -- the
+// DDIM update at eta = 0 plus g * (x0 - x0_prev) -- its coefficients in a DpmCoef argument (scalar loads) and two more pointers,
+// the previous iteration's predicted image (read) and this one's (written).  The five compiles above do not see a token of it.
 template <int IC>
 __global__ __launch_bounds__(256)
 void MIDD_OUT_KERNEL(const OutConvArgs a, const float* __restrict__ wglob /* == a.w: a restrict parameter of its own, so that uniform reads become scalar loads */
@@ -20,6 +23,9 @@ void MIDD_OUT_KERNEL(const OutConvArgs a, const float* __restrict__ wglob /* == 
 #endif
 #if MIDD_OUT_DDIM
                      , const DdimCoef k
+#endif
+#if MIDD_OUT_DPM
+                     , const DpmCoef k, const float* x0_prev, float* x0_out /* [a.B, ic, H, W]; may be one address: not restrict */
 #endif
                      ) {
     __shared__ __attribute__((aligned(16))) float tile[OC_I * OC_I * OC_PS];
@@ -184,6 +190,26 @@ void MIDD_OUT_KERNEL(const OutConvArgs a, const float* __restrict__ wglob /* == 
                 }
             }
             if (k.last) xn = fminf(fmaxf(xn, 0.0f), 1.0f);      // the call returns an image in [0, 1]; intermediate x is not clamped
+            a.x[o] = xn;
+        }
+#elif MIDD_OUT_DPM
+        if (a.x) {
+            // THE DPMPP2M UPDATE (include/midd.h), fp32, every operation rounded on its own: the DDIM update at eta = 0, word for
+            // word, then the multistep term on the clipped predictions.  tests/dpm_update_reference.py restates it bit for bit.
+#pragma clang fp contract(off)
+            if (a.clamp_eps) eps = fminf(fmaxf(eps, -5.0f), 5.0f);
+            const float x = a.x[o];
+            float x0 = k.k0 * (x - k.k1 * eps);
+            if (k.clip_x0) {
+                const float c = fminf(fmaxf(x0, 0.0f), 1.0f);
+                if (c != x0) eps = (x - k.r0 * c) * k.r1;      // eps re-derived: x_prev stays on the trajectory towards the clipped image
+                x0 = c;
+            }
+            float xn = k.a * x0 + k.b * eps;
+            if (k.g != 0.0f) xn = xn + k.g * (x0 - x0_prev[o]);      // (launch-uniform: the history is not read at g == 0; this
+                                                                     //  thread's own element, read before it is written below)
+            if (k.last) xn = fminf(fmaxf(xn, 0.0f), 1.0f);      // the call returns an image in [0, 1]; intermediate x is not clamped
+            x0_out[o] = x0;
             a.x[o] = xn;
         }
 #else

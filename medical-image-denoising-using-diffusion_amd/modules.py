@@ -274,11 +274,14 @@ class UNetDiffusion(nn.Module):
     def run_sampler(self, noisy: torch.Tensor, t_list, beta: torch.Tensor, alpha: torch.Tensor,
                     alpha_hat: torch.Tensor, clamp_eps: bool, step_noise: Optional[torch.Tensor] = None,
                     no_split: bool = False, seed: Optional[int] = None, sample_offset: int = 0, member: int = 0, *,
-                    update: str = "reference", eta: float = 0.0, clip_x0: bool = True) -> torch.Tensor:
+                    update: str = "reference", eta: float = 0.0, clip_x0: bool = True, return_x0: bool = False):
         """The whole reverse loop in one native call (used by DiffusionDenoiser.denoise).
 
         update, eta, clip_x0: the update rule (sampler.check_update; include/midd.h: THE DDIM UPDATE).  "reference" runs the calls
-        below unchanged; "ddim" runs mi_denoise_rule, whose noise term -- ``step_noise`` or ``seed`` -- is added where s > 0.
+        below unchanged; "ddim" runs mi_denoise_rule, whose noise term -- ``step_noise`` or ``seed`` -- is added where s > 0;
+        "dpmpp2m" (THE DPMPP2M UPDATE) runs mi_denoise_dpm with a history buffer of this call's own: deterministic, so ``seed``,
+        ``step_noise`` and ``member`` raise.  return_x0 (that rule only): -> (image, x0 [n_iters, B, C, H, W]), the trajectory of
+        predicted images, the image being the bits of the call without it.
 
         seed: the noise term of every t > 0 update is drawn on the device from (seed, sample_offset + b, iteration, element)
         (mi_denoise_seeded) instead of read from ``step_noise``; the two are exclusive.
@@ -286,6 +289,11 @@ class UNetDiffusion(nn.Module):
         through mi_denoise_ensemble's single-member form."""
         from .sampler import check_member, check_seed, check_update
         rule = check_update(update, eta, clip_x0)
+        dpm = rule is not None and rule.kind == native.MI_UPDATE["dpmpp2m"]
+        if return_x0 and not dpm:
+            raise ValueError("return_x0 belongs to update='dpmpp2m': the other rules do not store the predicted image")
+        if dpm and (seed is not None or step_noise is not None or member):
+            raise ValueError("update='dpmpp2m' is deterministic: it takes no seed, step_noise or member")
         member = check_member(member)
         if seed is not None:
             if step_noise is not None:
@@ -308,7 +316,16 @@ class UNetDiffusion(nn.Module):
             out = torch.empty_like(src)
             head = (plan, src.data_ptr(), out.data_ptr(), B, H, W) + sched
             flags = self._call_flags(clamp_eps, no_split)
-            if rule is not None:
+            x0 = None
+            if dpm:
+                # the predicted images: one slot (the history, in place) or one per iteration (the trajectory); never read
+                # before it is written, so torch.empty -- poisoned with the workspace when the mirror's switch is on
+                slots = sched[1] if return_x0 else 1
+                x0 = torch.empty((slots,) + tuple(src.shape), dtype=torch.float32, device=src.device)
+                if self.poison_workspace is not None:
+                    x0.view(torch.uint8).fill_(self.poison_workspace)      # (every byte, as the workspace's: 255 is a NaN pattern)
+                fn, head = native.lib().mi_denoise_dpm, head[:3] + (x0.data_ptr(), slots) + head[3:] + (flags, rule.clip_x0)
+            elif rule is not None:
                 step_noise = self._step_noise(step_noise, sched[1], src, "n_iters")
                 fn, head = native.lib().mi_denoise_rule, head + (_ptr(step_noise), 0 if seed is None else 1, C.c_uint64(seed or 0),
                                                                  C.c_int64(sample_offset if seed is not None else 0), flags, C.byref(rule))
@@ -318,7 +335,7 @@ class UNetDiffusion(nn.Module):
                 step_noise = self._step_noise(step_noise, sched[1], src, "n_iters")
                 fn, head = native.lib().mi_denoise, head + (_ptr(step_noise), flags)
             self._invoke(fn, head, self._workspace(B, H, W, noisy.device), noisy.device)
-        return out
+        return (out, x0) if return_x0 else out
 
     @staticmethod
     def _step_noise(step_noise: Optional[torch.Tensor], n: int, images: torch.Tensor, rows: str) -> Optional[torch.Tensor]:
@@ -392,6 +409,8 @@ class UNetDiffusion(nn.Module):
         samples is [B, members, C, H, W].  update, eta, clip_x0: the update rule, as in run_sampler (mi_denoise_ensemble_rule)."""
         from .sampler import check_members, check_seed, check_update
         rule = check_update(update, eta, clip_x0)
+        if rule is not None and rule.kind == native.MI_UPDATE["dpmpp2m"]:
+            raise ValueError("update='dpmpp2m' is deterministic: a deterministic sampler has no ensemble")
         seed, sample_offset = check_seed(seed, sample_offset)
         members, member_offset, max_batch = check_members(members, member_offset, max_batch)
         want_std = want_std and members >= 2
@@ -483,9 +502,12 @@ class UNetDiffusion(nn.Module):
                   want_tiles: bool = False, no_split: bool = False, *, update: str = "reference", eta: float = 0.0, clip_x0: bool = True):
         """Images of any size >= the tile as blended overlapping tiles in one native call (mi_denoise_tiled) ->
         (image, tiles or None, TilePlan).  seed None: no noise term (DDIM).  update, eta, clip_x0: the update rule, as in
-        run_sampler (mi_denoise_tiled_rule)."""
+        run_sampler (mi_denoise_tiled_rule; "dpmpp2m": mi_denoise_tiled_dpm with a history buffer of one pass, no seed)."""
         from .sampler import check_member, check_seed, check_update, tiling
         rule = check_update(update, eta, clip_x0)
+        dpm = rule is not None and rule.kind == native.MI_UPDATE["dpmpp2m"]
+        if dpm and seed is not None:
+            raise ValueError("update='dpmpp2m' is deterministic: it takes no seed")
         if seed is not None:
             seed, sample_offset = check_seed(seed, sample_offset)
         max_batch = check_member(max_batch, "max_batch", low=1)
@@ -501,6 +523,14 @@ class UNetDiffusion(nn.Module):
             tiles = torch.empty((B, K, Cc, th, tw), dtype=torch.float32, device=dev) if want_tiles else None
             pass_samples = min(max_batch, max(1, B * K))
             ws = self._tiled_workspace((B, H, W, th, tw, oy, ox, pass_samples, 1 if want_tiles else 0), dev)
+            if dpm:
+                hist = torch.empty((pass_samples, Cc, th, tw), dtype=torch.float32, device=dev)      # (as in run_sampler)
+                if self.poison_workspace is not None:
+                    hist.view(torch.uint8).fill_(self.poison_workspace)
+                self._invoke(native.lib().mi_denoise_tiled_dpm,
+                             (plan, src.data_ptr(), image.data_ptr(), _ptr(tiles), hist.data_ptr(), B, H, W, th, tw, oy, ox) + sched
+                             + (pass_samples, self._call_flags(clamp_eps, no_split), rule.clip_x0), ws, dev)
+                return image, tiles, plan_t
             self._invoke(native.lib().mi_denoise_tiled if rule is None else native.lib().mi_denoise_tiled_rule,
                          (plan, src.data_ptr(), image.data_ptr(), _ptr(tiles), B, H, W, th, tw, oy, ox) + sched
                          + (0 if seed is None else 1, C.c_uint64(seed or 0), C.c_int64(sample_offset), pass_samples,

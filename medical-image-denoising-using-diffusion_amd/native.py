@@ -20,7 +20,7 @@ MI_NO_SPLIT = 2
 MI_COMPUTE = {"f32": 0, "f16x3": 1, "f16": 2}
 MI_STATUS_NONFINITE, MI_STATUS_FP16_RANGE = 1, 2
 MI_COMPUTE_BATCH_INVARIANT = 0x100          # include/midd.h: OR into compute_mode
-MI_UPDATE = {"reference": 0, "ddim": 1}     # include/midd.h: mi_update_rule.kind
+MI_UPDATE = {"reference": 0, "ddim": 1, "dpmpp2m": 2}     # include/midd.h: mi_update_rule.kind (2: the *_dpm calls, no rule struct)
 MI_PIX_U8, MI_PIX_U16, MI_PIX_F32 = 0, 1, 2 # include/midd.h: element types of mi_resize_bicubic_f32
 
 
@@ -116,6 +116,13 @@ SYMBOLS = [
     ("mi_denoise_tiled_rule", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 7 +
                                        [C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int,
                                         C.c_int, C.c_uint64, C.c_int64, C.c_int, C.c_int, C.POINTER(UpdateRule), C.c_void_p, C.c_size_t, C.c_void_p]),
+    ("mi_dpm_coefficients", C.c_int, [C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_float), C.c_int, C.POINTER(C.c_float)]),
+    ("mi_denoise_dpm", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                 C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                 C.POINTER(C.c_float), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
+    ("mi_denoise_tiled_dpm", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 7 +
+                                      [C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int,
+                                       C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
     ("mi_debug_fetch", C.c_int, [C.c_void_p, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                  C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p]),
     ("mi_status", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]),

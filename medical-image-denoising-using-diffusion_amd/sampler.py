@@ -53,15 +53,17 @@ def check_members(members, member_offset, max_batch) -> Tuple[int, int, int]:
     return members, member_offset, max_batch
 
 
-UPDATE_RULES = ("reference", "ddim")
+UPDATE_RULES = ("reference", "ddim", "dpmpp2m")
 
 
 def check_update(update="reference", eta=0.0, clip_x0=True):
-    """Argument rules of the update rule (include/midd.h: THE DDIM UPDATE) -> None for ``"reference"`` (the reference's update,
-    the calls and bits of before) or the ``native.UpdateRule`` of ``"ddim"``; raises ValueError before any GPU work.  ``eta`` and
-    ``clip_x0`` belong to ``"ddim"``: anything but their defaults together with ``"reference"`` raises."""
+    """Argument rules of the update rule (include/midd.h: THE DDIM UPDATE, THE DPMPP2M UPDATE) -> None for ``"reference"`` (the
+    reference's update, the calls and bits of before) or the ``native.UpdateRule`` of ``"ddim"`` / ``"dpmpp2m"`` (kind and
+    clip_x0; the native *_dpm calls take no rule struct); raises ValueError before any GPU work.  ``eta`` and ``clip_x0`` belong
+    to ``"ddim"``: anything but their defaults together with ``"reference"`` raises; ``"dpmpp2m"`` takes ``clip_x0`` and is
+    deterministic, so ``eta`` must stay 0."""
     if update not in UPDATE_RULES:
-        raise ValueError(f"update must be 'reference' or 'ddim' (got {update!r})")
+        raise ValueError(f"update must be 'reference', 'ddim' or 'dpmpp2m' (got {update!r})")
     if isinstance(eta, bool) or not isinstance(eta, numbers.Real) or not 0.0 <= float(eta) <= 1.0:      # (NaN fails the comparison)
         raise ValueError(f"eta must be a number in [0, 1] (got {eta!r})")
     if not isinstance(clip_x0, (bool, int)):
@@ -70,13 +72,18 @@ def check_update(update="reference", eta=0.0, clip_x0=True):
         if float(eta) != 0.0 or not clip_x0:
             raise ValueError("eta and clip_x0 belong to update='ddim': the reference's update has neither")
         return None
-    return native.UpdateRule(native.MI_UPDATE["ddim"], float(eta), 1 if clip_x0 else 0)
+    if update == "dpmpp2m" and float(eta) != 0.0:
+        raise ValueError("update='dpmpp2m' is deterministic: it has no eta (an SDE form is not built)")
+    return native.UpdateRule(native.MI_UPDATE[update], float(eta), 1 if clip_x0 else 0)
 
 
 def refuse_update(update, what: str) -> None:
-    """The calls the DDIM update is not built for (include/midd.h: NOT BUILT) take ``update`` to say so."""
+    """The calls the DDIM and DPMPP2M updates are not built for (include/midd.h: NOT BUILT) take ``update`` to say so."""
     if update not in UPDATE_RULES:
-        raise ValueError(f"update must be 'reference' or 'ddim' (got {update!r})")
+        raise ValueError(f"update must be 'reference', 'ddim' or 'dpmpp2m' (got {update!r})")
+    if update == "dpmpp2m":
+        raise ValueError(f"{what} runs the reference's update only: update='dpmpp2m' is built for denoise and denoise_tiled "
+                         "(the per-slot record carries neither the rule nor a history of predicted images)")
     if update != "reference":
         raise ValueError(f"{what} runs the reference's update only: update='ddim' is built for denoise, denoise_ensemble and "
                          "denoise_tiled (the per-slot record and the other two batched calls do not carry the rule yet)")
@@ -94,6 +101,26 @@ def ddim_coefficients(t_list: Sequence[int], alpha_hat, eta: float = 0.0):
                                                    tab.ctypes.data_as(C.POINTER(C.c_float)), int(tab.shape[0]), C.c_double(float(eta)),
                                                    out.ctypes.data_as(C.POINTER(C.c_float))))
     return out
+
+
+def dpm_coefficients(t_list: Sequence[int], alpha_hat):
+    """The coefficient table of ``update="dpmpp2m"`` for a timestep list (host only; mi_dpm_coefficients): a float32 numpy array
+    [len(t_list), 8] of (k0, k1, r0, r1, a, b, s, g) per iteration -- ``ddim_coefficients`` at eta = 0, then the multistep weight."""
+    import numpy as np
+    steps = np.ascontiguousarray(np.asarray(list(t_list), dtype=np.int32))
+    tab = np.ascontiguousarray(alpha_hat.detach().to("cpu", torch.float32).numpy() if isinstance(alpha_hat, torch.Tensor)
+                               else np.asarray(alpha_hat, dtype=np.float32))
+    out = np.empty((len(steps), 8), dtype=np.float32)
+    native.check(native.lib().mi_dpm_coefficients(steps.ctypes.data_as(C.POINTER(C.c_int32)), len(steps),
+                                                  tab.ctypes.data_as(C.POINTER(C.c_float)), int(tab.shape[0]),
+                                                  out.ctypes.data_as(C.POINTER(C.c_float))))
+    return out
+
+
+class SamplerTrajectory(NamedTuple):
+    """What ``DiffusionDenoiser.denoise(..., update="dpmpp2m", return_x0=True)`` returns."""
+    image: torch.Tensor                   # [B, C, H, W]: the call's result, the bits of the call without return_x0
+    x0: torch.Tensor                      # [n_iters, B, C, H, W]: the predicted image of every iteration (clipped when clip_x0)
 
 
 class EnsembleResult(NamedTuple):
@@ -534,7 +561,7 @@ class DiffusionDenoiser:
     def denoise(self, noisy_img: torch.Tensor, inference_steps: int = 25,
                 step_noise: Optional[torch.Tensor] = None, seed: Optional[int] = None,
                 sample_offset: int = 0, member: int = 0, *,
-                update: str = "reference", eta: float = 0.0, clip_x0: bool = True) -> torch.Tensor:
+                update: str = "reference", eta: float = 0.0, clip_x0: bool = True, return_x0: bool = False):
         """x = denoiser.denoise(noisy_img, inference_steps) — DDIMModel.py:268-289.
 
         Starts from the noisy image itself, conditions every step on it, never mutates it and
@@ -560,8 +587,27 @@ class DiffusionDenoiser:
         (up to 1, ancestral) adds noise, for BOTH variants, from ``seed`` / ``member`` or ``step_noise`` exactly as above (the
         0.5-scaled convention is kept: the rule's coefficient carries the factor 2); without either, torch.randn up front.
         ``update="reference"`` (the default) is the call of before, bit for bit; ``eta`` or ``clip_x0`` with it raise ValueError.
+
+        ``update="dpmpp2m"`` (not a reference argument; include/midd.h: THE DPMPP2M UPDATE): the second-order multistep step --
+        the DDIM (eta = 0) step plus ``g * (x0 - x0_prev)``, the previous iteration's predicted image reused at no extra network
+        evaluation, the extrapolation weight bounded at its uniform-step value.  Deterministic for both variants: ``eta != 0``,
+        ``seed``, ``step_noise`` or ``member`` raise ValueError.  ``return_x0=True`` (this rule only; any other raises) returns
+        ``SamplerTrajectory(image, x0)`` with ``x0`` [n_iters, B, C, H, W], the predicted image of every iteration; ``image`` is
+        the bits of the call without it.
         """
         rule = check_update(update, eta, clip_x0)
+        dpm = rule is not None and rule.kind == native.MI_UPDATE["dpmpp2m"]
+        if return_x0 and not dpm:
+            raise ValueError("return_x0 belongs to update='dpmpp2m': the other rules do not store the predicted image")
+        if dpm:
+            if seed is not None or step_noise is not None or member != 0:
+                raise ValueError("update='dpmpp2m' is deterministic: it takes no seed, step_noise or member")
+            self.model.eval()
+            steps = timestep_list(self.noise_steps, inference_steps)
+            res = self.model.run_sampler(noisy_img, steps, self.beta, self.alpha, self.alpha_hat,
+                                         clamp_eps=getattr(self.model, "variant", "ddim") != "cddpm",
+                                         update=update, clip_x0=clip_x0, return_x0=return_x0)
+            return SamplerTrajectory(*res) if return_x0 else res
         if seed is not None:
             if step_noise is not None:
                 raise ValueError("pass either seed (noise drawn on the device) or step_noise (a noise tensor), not both")
@@ -610,6 +656,8 @@ class DiffusionDenoiser:
         levels = None if quantiles is None else check_levels(quantiles)
         rule = check_update(update, eta, clip_x0)
         stochastic = getattr(self.model, "variant", "ddim") == "cddpm"
+        if rule is not None and rule.kind == native.MI_UPDATE["dpmpp2m"]:
+            raise ValueError("denoise_ensemble with update='dpmpp2m': a deterministic sampler has no ensemble")
         if rule is not None and rule.eta == 0.0:
             raise ValueError("denoise_ensemble with update='ddim' needs eta > 0: a deterministic sampler has no ensemble")
         if rule is None and not stochastic:
@@ -646,8 +694,12 @@ class DiffusionDenoiser:
         not supported here (the argument exists to say so: anything but None raises ValueError).  DDIM: ``seed`` must be None.
 
         ``update="ddim"`` (see ``denoise``): every tile runs the DDIM(eta) update.  ``eta=0``: deterministic for both variants, a
-        ``seed`` is ignored and the result's ``seed`` is None.  ``eta > 0``: seeded as cddpm is above, for BOTH variants."""
+        ``seed`` is ignored and the result's ``seed`` is None.  ``eta > 0``: seeded as cddpm is above, for BOTH variants.
+        ``update="dpmpp2m"``: every tile runs the second-order multistep update with a history of its own; deterministic, so a
+        ``seed`` raises ValueError and the result's ``seed`` is None.  There is no trajectory for tiles."""
         rule = check_update(update, eta, clip_x0)
+        if rule is not None and rule.kind == native.MI_UPDATE["dpmpp2m"] and seed is not None:
+            raise ValueError("update='dpmpp2m' is deterministic: denoise_tiled takes no seed with it")
         if step_noise is not None:
             raise ValueError("denoise_tiled does not take a step_noise tensor: its noise is the seeded generator's, indexed by "
                              "image position (pass seed; midd_amd.step_noise(seed, n, x.shape) exports the same values)")

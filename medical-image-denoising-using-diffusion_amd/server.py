@@ -20,7 +20,8 @@ Not in the reference: ``DiffusionService(batch_slots=N)`` (or ``MIDD_BATCH_SLOTS
 requests as the slots of ONE ``SamplerSession`` owned by one worker thread (continuous batching, session.py) instead of one
 batch-1 call per request.  0, the default, is the path above, unchanged.  ``DiffusionService(update="ddim", eta=F)`` (or
 ``MIDD_UPDATE`` / ``MIDD_ETA``) runs the served 9-of-50 list under the stride-aware DDIM(eta) update (include/midd.h: THE DDIM
-UPDATE); the default, "reference", is the reference's update, unchanged.  Not together with batch_slots > 0.
+UPDATE); ``update="dpmpp2m"`` runs it under the second-order multistep update (THE DPMPP2M UPDATE; deterministic, no eta); the
+default, "reference", is the reference's update, unchanged.  Not together with batch_slots > 0.  ``/health`` reports ``update``.
 
 ``DiffusionService(bit_depth=16)`` (or ``MIDD_BIT_DEPTH=16``), not in the reference either, keeps a 16-bit upload's 65536 grey levels
 (image16.py; include/midd.h: THE FLOAT RESIZE): ``preprocess16`` / ``tensor_to_base64_16`` and their ``_device`` twins replace the
@@ -248,7 +249,8 @@ class DiffusionService:
             elif self.batch_slots > 0:
                 output = self._submit(input_tensor).result()      # raises what the worker met: the route then answers null
             else:
-                rule = {} if self.update == "reference" else {"update": self.update, "eta": self.eta}
+                rule = {} if self.update == "reference" else {"update": self.update} if self.update == "dpmpp2m" \
+                    else {"update": self.update, "eta": self.eta}
                 output = self.diffusion_denoiser.denoise(input_tensor, inference_steps=SERVE_INFERENCE_STEPS, **rule)
             output = torch.clamp(output, 0, 1)
             if len(original_size) == 3:       # a windowed request: (width, height, levels)
@@ -379,6 +381,7 @@ def create_app(service: Optional[DiffusionService] = None, checkpoint: Optional[
     @app.get("/health")
     async def health_check():
         return {"status": "healthy", "device": str(svc.device), "batch_slots": svc.batch_slots, "bit_depth": svc.bit_depth,
+                "update": svc.update,
                 "window": None if svc.window is None else list(svc.window),
                 "models_loaded": {"diffusion": svc.diffusion_model is not None or svc._denoise_fn is not None,
                                   "nafnet": False, "expert": False, "hybrid": False}}
