@@ -1,0 +1,511 @@
+// The batched sampler calls (virtual samples in passes: ensembles, tiles, tiled ensembles, flip / rotate views), their member /
+// tile / view argument rules, and the stand-alone reduce, quantile, tile and dihedral calls they compose.
+#include "midd_sampler.h"
+#include "tile_geometry.h"
+
+using namespace midd;
+
+// ---------------------------------------------------------------------------- ensembles of the stochastic sampler
+constexpr int64_t MEMBER_WORDS = (int64_t)1 << 32;      // the member index is one 32-bit counter word
+
+static int check_members_min(int members) {
+    return members >= 1 ? MI_OK : fail(MI_EINVAL, "members %d: an ensemble has at least one member (limit: members >= 1)", members);
+}
+
+static int check_std_members(const float* std_out, int members) {
+    if (std_out && members < 2) return fail(MI_EINVAL, "std_out needs members >= 2: the unbiased standard deviation of one value is undefined");
+    return MI_OK;
+}
+
+// B is grid.y of the reduce kernel
+static int check_reduce_batch(int B, const char* why = "limit of the reduce kernel's grid") {
+    return (B >= 1 && B <= 65535) ? MI_OK : fail(MI_EINVAL, "B %d outside [1, 65535] (%s)", B, why);
+}
+
+static int check_members(int members, int64_t member_offset) {
+    if (int rc = check_members_min(members)) return rc;
+    if (member_offset < 0) return fail(MI_EINVAL, "member_offset %lld is negative: member indices start at 0", (long long)member_offset);
+    if (member_offset > MEMBER_WORDS - members)
+        return fail(MI_EINVAL, "member_offset %lld + members %d exceeds 2^32: the member index of the seeded step noise is one 32-bit "
+                    "counter word (limit: member_offset + members <= 4294967296)", (long long)member_offset, members);
+    return MI_OK;
+}
+
+// B images x members draws: what the reduce kernel's grid (B in grid.y) and the 32-bit virtual index can hold
+static int check_ensemble_size(int B, int members) {
+    if (int rc = check_reduce_batch(B)) return rc;
+    if ((int64_t)B * members > 2147483647ll)
+        return fail(MI_EINVAL, "B * members = %d * %d exceeds 2^31 - 1: the virtual sample index is a 32-bit int (limit: B * members <= 2147483647)", B, members);
+    return MI_OK;
+}
+
+int midd::check_ensemble_args(mi_plan* plan, int B, int members, int H, int W, int64_t sample_offset, int64_t member_offset, int pass_samples) {
+    if (!plan) return fail(MI_EINVAL, "null plan");
+    if (int rc = check_members(members, member_offset)) return rc;
+    if (pass_samples < 1) return fail(MI_EINVAL, "pass_samples %d: a pass holds at least one virtual sample (limit: pass_samples >= 1)", pass_samples);
+    if (int rc = check_ensemble_size(B, members)) return rc;
+    return check_step_noise_range(plan->cfg.in_channels, H, W, sample_offset);
+}
+
+// what the two stand-alone ensemble calls open with: the members, the batch, the elements of a sample
+static int check_ensemble_run(int B, int members, int64_t chw) {
+    if (int rc = check_members_min(members)) return rc;
+    if (int rc = check_reduce_batch(B)) return rc;
+    if (chw < 1 || chw >= MEMBER_WORDS) return fail(MI_EINVAL, "chw %lld outside [1, 2^32) (limit: C*H*W < 4294967296)", (long long)chw);
+    return MI_OK;
+}
+
+extern "C" int mi_ensemble_reduce(const float* samples, int B, int members, int64_t chw, float* mean_out, float* std_out, void* stream) {
+    if (int rc = check_ensemble_run(B, members, chw)) return rc;
+    if (int rc = check_std_members(std_out, members)) return rc;
+    if (!samples || !mean_out) return fail(MI_EINVAL, "null argument");
+    return launched(ensemble_reduce_launch(samples, B, members, (unsigned long long)chw, mean_out, std_out, (hipStream_t)stream), "ensemble_reduce");
+}
+
+// the members of a pixel are sorted in registers (ensemble.hip: ensemble_quantiles_kernel): at most QUANTILE_MAX_MEMBERS of them
+static int check_quantile_members(int members) {
+    if (members > QUANTILE_MAX_MEMBERS)
+        return fail(MI_EINVAL, "members %d: the quantile kernels sort a pixel's members in registers (limit: members <= %d; mean and std have no such limit)",
+                    members, QUANTILE_MAX_MEMBERS);
+    return MI_OK;
+}
+
+// the levels of a quantile call, host doubles -> the kernel argument
+static int check_quantile_levels(const double* q, int nq, QuantileLevels* ql) {
+    if (nq < 1 || nq > QUANTILE_MAX_LEVELS)
+        return fail(MI_EINVAL, "nq %d outside [1, %d]: the levels travel as kernel arguments (limit: 1 <= nq <= %d)", nq, QUANTILE_MAX_LEVELS, QUANTILE_MAX_LEVELS);
+    if (!q) return fail(MI_EINVAL, "null argument");
+    *ql = QuantileLevels{};
+    ql->nq = nq;
+    for (int i = 0; i < nq; ++i) {
+        if (!(q[i] >= 0.0 && q[i] <= 1.0)) return fail(MI_EINVAL, "q[%d] = %.17g outside [0, 1] (limit: 0 <= q <= 1, not NaN)", i, q[i]);
+        ql->q[i] = q[i];
+    }
+    return MI_OK;
+}
+
+extern "C" int mi_ensemble_quantiles(const float* samples, int B, int members, int64_t chw, const double* q, int nq, float* out, void* stream) {
+    if (int rc = check_ensemble_run(B, members, chw)) return rc;
+    if (int rc = check_quantile_members(members)) return rc;
+    QuantileLevels ql;
+    if (int rc = check_quantile_levels(q, nq, &ql)) return rc;
+    if (!samples || !out) return fail(MI_EINVAL, "null argument");
+    return launched(ensemble_quantiles_launch(samples, B, members, (unsigned long long)chw, ql, out, (hipStream_t)stream), "ensemble_quantiles");
+}
+
+// ---------------------------------------------------------------------------- the batched calls: virtual samples in passes
+// mi_denoise_ensemble, mi_denoise_tiled and mi_denoise_tiled_ensemble run `rounds` x V virtual samples of h x w each through the
+// sampler loop in passes of L.pass.  Each judges its own argument rules and its table of buffers (check_no_overlap), then shares
+// check_batched_call and run_passes, and ends with its own reduce / blend launch.
+
+// What lies between a batched call's own rules and its first launch, in the order in which it is reported: the plan's state, the
+// workspace layout (the caller's ensemble_layout / tiled_ensemble_layout call: its rc and result), the workspace's size and
+// alignment, the pointers that must not be null, the schedule -- what a pass would refuse is refused here, before anything is
+// enqueued -- and the device.
+static int check_batched_call(mi_plan* plan, int layout_rc, const EnsembleLayout& L, const void* ws, size_t ws_bytes,
+                              std::initializer_list<const void*> required, const Schedule& sc) {
+    if (int rc = check_finalized(plan)) return rc;
+    if (layout_rc) return layout_rc;                     // (mi_last_error holds the planner's message)
+    if (int rc = check_workspace(ws, ws_bytes, L.bytes)) return rc;
+    for (const void* p : required)
+        if (!p) return fail(MI_EINVAL, "null argument");
+    if (int rc = check_schedule(plan, sc)) return rc;
+    return check_device(plan);
+}
+
+// The one pass loop.  Round m (a member of the tiled ensemble, whose member word is a launch constant; else the only round) runs
+// the virtual samples [0, V) in passes: fill(cond, v0, n) writes the pass's condition images, the sampler loop leaves its
+// samples at store[m][v0 ..].  The caller holds plan->side_mu and has cleared the status word, so the word accumulates over the
+// passes; every pass joins its side streams before it returns, on success and on failure (enqueue_run), and the first failing
+// pass ends the call.
+template <class Fill>
+static int run_passes(mi_plan* plan, Fill fill, float* store, int64_t V, int rounds, int h, int w, size_t chw, const EnsembleLayout& L,
+                      StepNoise sn, const Schedule& sc, int flags, char* ws, void* stream) {
+    float* cond = reinterpret_cast<float*>(ws + L.cond_off);
+    const uint32_t member_base = sn.member_offset;
+    for (int m = 0; m < rounds; ++m) {
+        sn.member_offset = member_base + m;
+        for (int64_t v0 = 0; v0 < V; v0 += L.pass) {
+            const int n = (int)(V - v0 < L.pass ? V - v0 : L.pass);
+            if (int rc = fill(cond, (int)v0, n)) return rc;
+            sn.v0 = (int)v0;
+            Program* g = nullptr;
+            float* x = store + ((size_t)m * V + (size_t)v0) * chw;
+            if (int rc = check_run(plan, cond, x, n, h, w, sc, ws, L.run_bytes, &g)) return rc;
+            if (int rc = enqueue_run(plan, g, cond, x, n, h, w, sc, nullptr, sn, flags, ws, L.run_bytes, stream)) return rc;
+        }
+    }
+    return MI_OK;
+}
+
+extern "C" int mi_denoise_ensemble_rule(mi_plan* plan, const float* noisy, float* mean_out, float* std_out, float* samples_out,
+                                        int B, int members, int H, int W,
+                                        const int32_t* t_list, int n_iters,
+                                        const float* beta, const float* alpha, const float* alpha_hat, int noise_steps,
+                                        uint64_t seed, int64_t sample_offset, int64_t member_offset, int pass_samples, int flags,
+                                        const mi_update_rule* rule, void* workspace, size_t workspace_bytes, void* stream) {
+    Schedule sc{t_list, n_iters, beta, alpha, alpha_hat, noise_steps};
+    if (int rc = apply_rule(rule, &sc)) return rc;
+    if (int rc = check_ensemble_args(plan, B, members, H, W, sample_offset, member_offset, pass_samples)) return rc;
+    if (!mean_out && !std_out && !samples_out) return fail(MI_EINVAL, "no output: give at least one of mean_out, std_out, samples_out");
+    if (int rc = check_std_members(std_out, members)) return rc;
+    const size_t chw = (size_t)plan->cfg.in_channels * H * W, img = chw * sizeof(float);
+    const Buf buf[4] = {{noisy, (size_t)B * img, "noisy"}, {mean_out, (size_t)B * img, "mean_out"}, {std_out, (size_t)B * img, "std_out"},
+                        {samples_out, (size_t)B * members * img, "samples_out"}};
+    if (int rc = check_no_overlap(buf, 4, "noisy is read every step and the reduce reads samples_out while it writes mean_out and std_out"))
+        return rc;
+    EnsembleLayout L{};
+    // (evaluated before the state check, reported after it: check_batched_call; host arithmetic only, as in the *_workspace_bytes queries)
+    const int layout_rc = ensemble_layout(plan, B, members, H, W, pass_samples, samples_out != nullptr, &L);
+    if (int rc = check_batched_call(plan, layout_rc, L, workspace, workspace_bytes, {noisy}, sc)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    char* ws = (char*)workspace;
+    float* samples = samples_out ? samples_out : reinterpret_cast<float*>(ws + L.samples_off);
+    std::lock_guard<std::mutex> side_lk(plan->side_mu);     // held over all passes: the side streams are per plan
+    HIPCHK(hipMemsetAsync(ws, 0, 256, s));                  // status word: once per call, the passes accumulate into it
+    StepNoise sn;
+    sn.seeded = true; sn.seed = seed; sn.sample_offset = sample_offset; sn.members = members; sn.member_offset = (uint32_t)member_offset;
+    auto broadcast = [&](float* cond, int v0, int n) { return launched(ensemble_broadcast_launch(noisy, cond, v0, n, members, chw, s), "ensemble_broadcast"); };
+    if (int rc = run_passes(plan, broadcast, samples, (int64_t)B * members, 1, H, W, chw, L, sn, sc, flags, ws, stream)) return rc;
+    if (mean_out || std_out) return launched(ensemble_reduce_launch(samples, B, members, chw, mean_out, std_out, s), "ensemble_reduce");
+    return MI_OK;
+}
+
+extern "C" int mi_denoise_ensemble(mi_plan* plan, const float* noisy, float* mean_out, float* std_out, float* samples_out,
+                                   int B, int members, int H, int W,
+                                   const int32_t* t_list, int n_iters,
+                                   const float* beta, const float* alpha, const float* alpha_hat, int noise_steps,
+                                   uint64_t seed, int64_t sample_offset, int64_t member_offset, int pass_samples, int flags,
+                                   void* workspace, size_t workspace_bytes, void* stream) {
+    return mi_denoise_ensemble_rule(plan, noisy, mean_out, std_out, samples_out, B, members, H, W, t_list, n_iters, beta, alpha, alpha_hat,
+                                    noise_steps, seed, sample_offset, member_offset, pass_samples, flags, nullptr, workspace, workspace_bytes, stream);
+}
+
+// ---------------------------------------------------------------------------- tiled denoising of full-resolution images
+static int check_tile_axis(const char* axis, int L, int T, int O) {
+    if (T < 1) return fail(MI_EINVAL, "tile %s %d must be positive", axis, T);
+    if (T > L) return fail(MI_EINVAL, "tile %s %d exceeds the image %s %d (limit: tile <= image; resize a smaller image up, or use a smaller tile)", axis, T, axis, L);
+    if (O < 0 || O > T / 2) return fail(MI_EINVAL, "overlap %d of tile %s %d outside [0, %d] (limit: 0 <= overlap <= tile / 2)", O, axis, T, T / 2);
+    return MI_OK;
+}
+
+extern "C" int mi_tile_geometry(int L, int T, int O, int* n, int* origins, int cap) {
+    if (int rc = check_tile_axis("length", L, T, O)) return rc;
+    if (!n) return fail(MI_EINVAL, "null argument");
+    *n = tile_count(L, T, O);
+    for (int i = 0; origins && i < *n && i < cap; ++i) origins[i] = tile_origin(i, L, T, *n);
+    return MI_OK;
+}
+
+static int fill_tile_geom(int C, int H, int W, int th, int tw, int oy, int ox, TileGeom* g) {
+    if (int rc = check_tile_axis("height", H, th, oy)) return rc;
+    if (int rc = check_tile_axis("width", W, tw, ox)) return rc;
+    if (oy > 46339 || ox > 46339) return fail(MI_EINVAL, "overlap %dx%d: the window product must fit 32 bits (limit: overlap <= 46339)", oy, ox);
+    *g = TileGeom{C, H, W, th, tw, oy, ox, tile_count(H, th, oy), tile_count(W, tw, ox)};
+    return MI_OK;
+}
+
+static int check_tile_count(int B, const TileGeom& g) {
+    if (B < 1) return fail(MI_EINVAL, "B %d must be positive", B);
+    if ((int64_t)B * g.ny * g.nx > 2147483647ll)
+        return fail(MI_EINVAL, "B * tiles = %d * %d * %d exceeds 2^31 - 1: the virtual sample index is a 32-bit int (limit: B * tiles <= 2147483647)", B, g.ny, g.nx);
+    return MI_OK;
+}
+
+int midd::check_tiled_args(mi_plan* plan, int B, int H, int W, int th, int tw, int oy, int ox, int64_t sample_offset, int pass_samples, TileGeom* g) {
+    if (!plan) return fail(MI_EINVAL, "null plan");
+    const int div = 1 << (plan->levels - 1);
+    if (th < div || tw < div || th % div || tw % div)
+        return fail(MI_EINVAL, "tile %dx%d: the network takes positive multiples of %d only (limit of the plan; the IMAGE may have any size >= the tile)", th, tw, div);
+    if (int rc = fill_tile_geom(plan->cfg.in_channels, H, W, th, tw, oy, ox, g)) return rc;
+    if (pass_samples < 1) return fail(MI_EINVAL, "pass_samples %d: a pass holds at least one tile (limit: pass_samples >= 1)", pass_samples);
+    if (int rc = check_step_noise_range(plan->cfg.in_channels, H, W, sample_offset)) return rc;
+    return check_tile_count(B, *g);
+}
+
+// what the stand-alone tile calls open with: the channels, the geometry, the tiles of the batch (mi_tile_extract: these three) ...
+static int check_tile_shape(int B, int C, int H, int W, int th, int tw, int oy, int ox, TileGeom* g) {
+    if (C < 1) return fail(MI_EINVAL, "C %d must be positive", C);
+    if (int rc = fill_tile_geom(C, H, W, th, tw, oy, ox, g)) return rc;
+    return check_tile_count(B, *g);
+}
+// ... and, where whole images are written, the elements of one (the three blend calls)
+static int check_tile_run(int B, int C, int H, int W, int th, int tw, int oy, int ox, TileGeom* g) {
+    if (int rc = check_tile_shape(B, C, H, W, th, tw, oy, ox, g)) return rc;
+    return check_step_noise_range(C, H, W, 0);
+}
+
+extern "C" int mi_tile_extract(const float* noisy, int B, int C, int H, int W, int th, int tw, int oy, int ox, int v0, int n,
+                               float* dst, void* stream) {
+    TileGeom g{};
+    if (int rc = check_tile_shape(B, C, H, W, th, tw, oy, ox, &g)) return rc;
+    if (v0 < 0 || n < 0 || n > 65535 || (int64_t)v0 + n > (int64_t)B * g.ny * g.nx)
+        return fail(MI_EINVAL, "tiles [%d, %d + %d) outside the %d * %d * %d tiles of the batch (limit per call: n <= 65535)", v0, v0, n, B, g.ny, g.nx);
+    if ((int64_t)C * th * tw > 2147483647ll) return fail(MI_EINVAL, "C*th*tw = %d*%d*%d exceeds 2^31 - 1", C, th, tw);
+    if (n == 0) return MI_OK;
+    if (!noisy || !dst) return fail(MI_EINVAL, "null argument");
+    return launched(tile_extract_launch(noisy, dst, g, v0, n, (hipStream_t)stream), "tile_extract");
+}
+
+extern "C" int mi_tile_blend(const float* tiles, int B, int C, int H, int W, int th, int tw, int oy, int ox, float* out, void* stream) {
+    TileGeom g{};
+    if (int rc = check_tile_run(B, C, H, W, th, tw, oy, ox, &g)) return rc;
+    if (!tiles || !out) return fail(MI_EINVAL, "null argument");
+    return launched(tile_blend_launch(tiles, out, B, g, (hipStream_t)stream), "tile_blend");
+}
+
+// mi_denoise_tiled_rule and mi_denoise_tiled_dpm behind their rules: `sc` carries the rule.  MI_UPDATE_DPMPP2M: sc.x0 is the call's x0_hist
+// [pass_samples, C, th, tw], the in-place history of whichever pass runs
+static int tiled_run(mi_plan* plan, const float* noisy, float* image_out, float* tiles_out,
+                     int B, int H, int W, int th, int tw, int oy, int ox, const Schedule& sc,
+                     int seeded, uint64_t seed, int64_t sample_offset, int pass_samples, int flags,
+                     void* workspace, size_t workspace_bytes, void* stream) {
+    TileGeom tg{};
+    if (int rc = check_tiled_args(plan, B, H, W, th, tw, oy, ox, sample_offset, pass_samples, &tg)) return rc;
+    const int K = tg.ny * tg.nx;
+    const size_t chw = (size_t)tg.C * th * tw, img = (size_t)tg.C * H * W * sizeof(float);
+    const bool dpm = sc.rule == MI_UPDATE_DPMPP2M;
+    if (dpm && sc.n > 0 && !sc.x0) return fail(MI_EINVAL, "null argument");
+    const Buf buf[4] = {{noisy, (size_t)B * img, "noisy"}, {image_out, (size_t)B * img, "image_out"},
+                        {tiles_out, (size_t)B * K * chw * sizeof(float), "tiles_out"},
+                        {dpm ? sc.x0 : nullptr, (size_t)pass_samples * chw * sizeof(float), "x0_hist"}};
+    if (int rc = check_no_overlap(buf, 4, "noisy is read by every pass and the blend reads the tiles while it writes image_out")) return rc;
+    EnsembleLayout L{};
+    // (evaluated before the state check, reported after it: check_batched_call; host arithmetic only, as in the *_workspace_bytes queries)
+    const int layout_rc = ensemble_layout(plan, B, K, th, tw, pass_samples, tiles_out != nullptr, &L);
+    if (int rc = check_batched_call(plan, layout_rc, L, workspace, workspace_bytes, {noisy, image_out}, sc)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    char* ws = (char*)workspace;
+    float* tiles = tiles_out ? tiles_out : reinterpret_cast<float*>(ws + L.samples_off);
+    std::lock_guard<std::mutex> side_lk(plan->side_mu);     // held over all passes: the side streams are per plan
+    HIPCHK(hipMemsetAsync(ws, 0, 256, s));                  // status word: once per call, the passes accumulate into it
+    StepNoise sn;
+    if (seeded) {
+        sn.seeded = true; sn.seed = seed; sn.sample_offset = sample_offset; sn.members = K;
+        sn.tiles_x = tg.nx; sn.tiles_y = tg.ny; sn.img_H = H; sn.img_W = W;
+    }
+    auto extract = [&](float* cond, int v0, int n) { return launched(tile_extract_launch(noisy, cond, tg, v0, n, s), "tile_extract"); };
+    if (int rc = run_passes(plan, extract, tiles, (int64_t)B * K, 1, th, tw, chw, L, sn, sc, flags, ws, stream)) return rc;
+    return launched(tile_blend_launch(tiles, image_out, B, tg, s), "tile_blend");
+}
+
+extern "C" int mi_denoise_tiled_rule(mi_plan* plan, const float* noisy, float* image_out, float* tiles_out,
+                                     int B, int H, int W, int th, int tw, int oy, int ox,
+                                     const int32_t* t_list, int n_iters,
+                                     const float* beta, const float* alpha, const float* alpha_hat, int noise_steps,
+                                     int seeded, uint64_t seed, int64_t sample_offset, int pass_samples, int flags,
+                                     const mi_update_rule* rule, void* workspace, size_t workspace_bytes, void* stream) {
+    Schedule sc{t_list, n_iters, beta, alpha, alpha_hat, noise_steps};
+    if (int rc = apply_rule(rule, &sc)) return rc;
+    return tiled_run(plan, noisy, image_out, tiles_out, B, H, W, th, tw, oy, ox, sc, seeded, seed, sample_offset, pass_samples, flags,
+                     workspace, workspace_bytes, stream);
+}
+
+// mi_denoise_tiled under the second-order multistep rule: deterministic, so no seed; the history of a pass lives in x0_hist
+extern "C" int mi_denoise_tiled_dpm(mi_plan* plan, const float* noisy, float* image_out, float* tiles_out, float* x0_hist,
+                                    int B, int H, int W, int th, int tw, int oy, int ox,
+                                    const int32_t* t_list, int n_iters,
+                                    const float* beta, const float* alpha, const float* alpha_hat, int noise_steps,
+                                    int pass_samples, int flags, int clip_x0, void* workspace, size_t workspace_bytes, void* stream) {
+    Schedule sc{t_list, n_iters, beta, alpha, alpha_hat, noise_steps};
+    if (int rc = apply_dpm(clip_x0, x0_hist, &sc)) return rc;
+    if (n_iters > 0 && !x0_hist) return fail(MI_EINVAL, "null argument");
+    return tiled_run(plan, noisy, image_out, tiles_out, B, H, W, th, tw, oy, ox, sc, 0, 0, 0, pass_samples, flags,
+                     workspace, workspace_bytes, stream);
+}
+
+extern "C" int mi_denoise_tiled(mi_plan* plan, const float* noisy, float* image_out, float* tiles_out,
+                                int B, int H, int W, int th, int tw, int oy, int ox,
+                                const int32_t* t_list, int n_iters,
+                                const float* beta, const float* alpha, const float* alpha_hat, int noise_steps,
+                                int seeded, uint64_t seed, int64_t sample_offset, int pass_samples, int flags,
+                                void* workspace, size_t workspace_bytes, void* stream) {
+    return mi_denoise_tiled_rule(plan, noisy, image_out, tiles_out, B, H, W, th, tw, oy, ox, t_list, n_iters, beta, alpha, alpha_hat, noise_steps,
+                                 seeded, seed, sample_offset, pass_samples, flags, nullptr, workspace, workspace_bytes, stream);
+}
+
+// ---------------------------------------------------------------------------- ensembles of tiled runs
+// members x B images x tiles: the tile storage is indexed by a 32-bit int (check_tile_count has judged B * tiles)
+static int check_tiled_ensemble_size(int B, int members, const TileGeom& g) {
+    if ((int64_t)B * g.ny * g.nx * members > 2147483647ll)
+        return fail(MI_EINVAL, "B * members * tiles = %d * %d * %d * %d exceeds 2^31 - 1: the tile index of the member storage is a 32-bit int "
+                    "(limit: B * members * tiles <= 2147483647)", B, members, g.ny, g.nx);
+    return MI_OK;
+}
+
+int midd::check_tiled_ensemble_args(mi_plan* plan, int B, int members, int H, int W, int th, int tw, int oy, int ox,
+                                    int64_t sample_offset, int64_t member_offset, int pass_samples, TileGeom* g) {
+    if (int rc = check_tiled_args(plan, B, H, W, th, tw, oy, ox, sample_offset, pass_samples, g)) return rc;
+    if (int rc = check_members(members, member_offset)) return rc;
+    return check_tiled_ensemble_size(B, members, *g);
+}
+
+extern "C" int mi_tile_blend_reduce(const float* tiles, int B, int members, int C, int H, int W, int th, int tw, int oy, int ox,
+                                    float* mean_out, float* std_out, float* samples_out, void* stream) {
+    TileGeom g{};
+    if (int rc = check_tile_run(B, C, H, W, th, tw, oy, ox, &g)) return rc;
+    if (int rc = check_members_min(members)) return rc;
+    if (int rc = check_reduce_batch(B, "the limit of mi_ensemble_reduce, whose arithmetic this call composes")) return rc;      // (B >= 1: check_tile_count)
+    if (int rc = check_tiled_ensemble_size(B, members, g)) return rc;
+    if (int rc = check_std_members(std_out, members)) return rc;
+    if (!tiles || !mean_out) return fail(MI_EINVAL, "null argument");
+    return launched(tile_blend_reduce_launch(tiles, B, members, g, mean_out, std_out, samples_out, (hipStream_t)stream), "tile_blend_reduce");
+}
+
+extern "C" int mi_tile_blend_quantiles(const float* tiles, int B, int members, int C, int H, int W, int th, int tw, int oy, int ox,
+                                       const double* q, int nq, float* out, void* stream) {
+    TileGeom g{};
+    if (int rc = check_tile_run(B, C, H, W, th, tw, oy, ox, &g)) return rc;
+    if (int rc = check_members_min(members)) return rc;
+    if (int rc = check_reduce_batch(B, "the limit of mi_ensemble_quantiles, whose arithmetic this call composes")) return rc;      // (B >= 1: check_tile_count)
+    if (int rc = check_tiled_ensemble_size(B, members, g)) return rc;
+    if (int rc = check_quantile_members(members)) return rc;
+    QuantileLevels ql;
+    if (int rc = check_quantile_levels(q, nq, &ql)) return rc;
+    if (!tiles || !out) return fail(MI_EINVAL, "null argument");
+    return launched(tile_blend_quantiles_launch(tiles, B, members, g, ql, out, (hipStream_t)stream), "tile_blend_quantiles");
+}
+
+// Members are the outer loop: member m is mi_denoise_tiled's seeded pass structure with counter word c3 = member_offset + m, a
+// launch constant of the update kernel, so no pass spans two members.  Its tiles are slice m of the storage [members][B][tiles].
+extern "C" int mi_denoise_tiled_ensemble(mi_plan* plan, const float* noisy, float* mean_out, float* std_out, float* samples_out, float* tiles_out,
+                                         int B, int members, int H, int W, int th, int tw, int oy, int ox,
+                                         const int32_t* t_list, int n_iters,
+                                         const float* beta, const float* alpha, const float* alpha_hat, int noise_steps,
+                                         uint64_t seed, int64_t sample_offset, int64_t member_offset, int pass_samples, int flags,
+                                         void* workspace, size_t workspace_bytes, void* stream) {
+    TileGeom tg{};
+    if (int rc = check_tiled_ensemble_args(plan, B, members, H, W, th, tw, oy, ox, sample_offset, member_offset, pass_samples, &tg)) return rc;
+    if (!mean_out && !std_out && !samples_out && !tiles_out)
+        return fail(MI_EINVAL, "no output: give at least one of mean_out, std_out, samples_out, tiles_out");
+    if (int rc = check_std_members(std_out, members)) return rc;
+    const int K = tg.ny * tg.nx;
+    const size_t chw = (size_t)tg.C * th * tw, img = (size_t)tg.C * H * W * sizeof(float);
+    const Buf buf[5] = {{noisy, (size_t)B * img, "noisy"}, {mean_out, (size_t)B * img, "mean_out"}, {std_out, (size_t)B * img, "std_out"},
+                        {samples_out, (size_t)B * members * img, "samples_out"},
+                        {tiles_out, (size_t)members * B * K * chw * sizeof(float), "tiles_out"}};
+    if (int rc = check_no_overlap(buf, 5, "noisy is read by every pass and the reduce reads the tiles while it writes mean_out, std_out and samples_out"))
+        return rc;
+    const Schedule sc{t_list, n_iters, beta, alpha, alpha_hat, noise_steps};
+    EnsembleLayout L{};
+    // (evaluated before the state check, reported after it: check_batched_call; host arithmetic only, as in the *_workspace_bytes queries)
+    const int layout_rc = tiled_ensemble_layout(plan, B, members, K, th, tw, pass_samples, tiles_out != nullptr, &L);
+    if (int rc = check_batched_call(plan, layout_rc, L, workspace, workspace_bytes, {noisy}, sc)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    char* ws = (char*)workspace;
+    float* tiles = tiles_out ? tiles_out : reinterpret_cast<float*>(ws + L.samples_off);
+    std::lock_guard<std::mutex> side_lk(plan->side_mu);     // held over all passes: the side streams are per plan
+    HIPCHK(hipMemsetAsync(ws, 0, 256, s));                  // status word: once per call, the passes of every member accumulate into it
+    StepNoise sn;
+    sn.seeded = true; sn.seed = seed; sn.sample_offset = sample_offset; sn.members = K; sn.member_offset = (uint32_t)member_offset;
+    sn.tiles_x = tg.nx; sn.tiles_y = tg.ny; sn.img_H = H; sn.img_W = W;
+    auto extract = [&](float* cond, int v0, int n) { return launched(tile_extract_launch(noisy, cond, tg, v0, n, s), "tile_extract"); };
+    if (int rc = run_passes(plan, extract, tiles, (int64_t)B * K, members, th, tw, chw, L, sn, sc, flags, ws, stream)) return rc;      // V: ONE member's
+    if (mean_out || std_out || samples_out)
+        return launched(tile_blend_reduce_launch(tiles, B, members, tg, mean_out, std_out, samples_out, s), "tile_blend_reduce");
+    return MI_OK;
+}
+
+// ---------------------------------------------------------------------------- geometric self-ensemble: flip / rotate views
+// the view list of a call, host int32 -> the kernel argument (include/midd.h: THE GEOMETRY)
+static int check_views(const int32_t* views, int n_views, int H, int W, DihedralViews* dv) {
+    if (n_views < 1 || n_views > DIHEDRAL_MAX_VIEWS)
+        return fail(MI_EINVAL, "n_views %d outside [1, %d]: a view list holds 1 to 8 distinct view codes (limit: 1 <= n_views <= %d)", n_views,
+                    DIHEDRAL_MAX_VIEWS, DIHEDRAL_MAX_VIEWS);
+    if (!views) return fail(MI_EINVAL, "null argument: views");
+    *dv = DihedralViews{};
+    dv->n = n_views;
+    for (int k = 0; k < n_views; ++k) {
+        if (views[k] < 0 || views[k] > 7)
+            return fail(MI_EINVAL, "views[%d] = %d outside [0, 7]: a view code is 4 * transpose + 2 * flip_rows + flip_columns (limit: 0 <= code <= 7)", k, views[k]);
+        for (int j = 0; j < k; ++j)
+            if (views[j] == views[k]) return fail(MI_EINVAL, "views[%d] = %d repeats views[%d]: the view codes of a list are distinct", k, views[k], j);
+        dv->code[k] = (uint8_t)views[k];
+    }
+    for (int k = 0; k < n_views; ++k)
+        if ((views[k] & 4) && H != W)
+            return fail(MI_EINVAL, "views[%d] = %d transposes a %dx%d image: a pass never mixes image sizes (limit: view codes 4 .. 7 need H == W)", k, views[k], H, W);
+    return MI_OK;
+}
+
+static int check_std_views(const float* std_out, int n_views) {
+    if (std_out && n_views < 2) return fail(MI_EINVAL, "std_out needs at least two views: the unbiased standard deviation of one value is undefined");
+    return MI_OK;
+}
+
+// what the three stand-alone calls share: the image shape, the view list, the batch
+static int check_dihedral_call(int B, int C, int H, int W, const int32_t* views, int n_views, DihedralViews* dv) {
+    if (C < 1) return fail(MI_EINVAL, "C %d must be positive", C);
+    if (int rc = check_step_noise_range(C, H, W, 0)) return rc;
+    if (int rc = check_views(views, n_views, H, W, dv)) return rc;
+    return check_ensemble_size(B, n_views);
+}
+
+extern "C" int mi_dihedral_views(const float* images, int B, int C, int H, int W, const int32_t* views, int n_views,
+                                 int v0, int n, float* dst, void* stream) {
+    DihedralViews dv;
+    if (int rc = check_dihedral_call(B, C, H, W, views, n_views, &dv)) return rc;
+    if (v0 < 0 || n < 0 || n > 65535 || (int64_t)v0 + n > (int64_t)B * n_views)
+        return fail(MI_EINVAL, "views [%d, %d + %d) outside the %d * %d virtual samples of the batch (limit per call: n <= 65535)", v0, v0, n, B, n_views);
+    if (n == 0) return MI_OK;
+    if (!images || !dst) return fail(MI_EINVAL, "null argument");
+    return launched(dihedral_views_launch(images, dst, dv, C, H, W, v0, n, (hipStream_t)stream), "dihedral_views");
+}
+
+extern "C" int mi_dihedral_reduce(const float* views_out, int B, int C, int H, int W, const int32_t* views, int n_views,
+                                  float* mean_out, float* std_out, float* samples_out, void* stream) {
+    DihedralViews dv;
+    if (int rc = check_dihedral_call(B, C, H, W, views, n_views, &dv)) return rc;
+    if (!mean_out && !std_out && !samples_out) return fail(MI_EINVAL, "no output: give at least one of mean_out, std_out, samples_out");
+    if (int rc = check_std_views(std_out, n_views)) return rc;
+    if (!views_out) return fail(MI_EINVAL, "null argument");
+    return launched(dihedral_reduce_launch(views_out, B, dv, C, H, W, mean_out, std_out, samples_out, (hipStream_t)stream), "dihedral_reduce");
+}
+
+extern "C" int mi_dihedral_quantiles(const float* views_out, int B, int C, int H, int W, const int32_t* views, int n_views,
+                                     const double* q, int nq, float* out, void* stream) {
+    DihedralViews dv;
+    if (int rc = check_dihedral_call(B, C, H, W, views, n_views, &dv)) return rc;
+    QuantileLevels ql;
+    if (int rc = check_quantile_levels(q, nq, &ql)) return rc;
+    if (!views_out || !out) return fail(MI_EINVAL, "null argument");
+    return launched(dihedral_quantiles_launch(views_out, B, dv, C, H, W, ql, out, (hipStream_t)stream), "dihedral_quantiles");
+}
+
+// mi_denoise_ensemble with the views of an image in the place of its draws: virtual sample v = b * G + k is view k of image b.
+// The sampler leaves every view's output in the view's own frame, always in the workspace (a transposing unview cannot run in
+// place), and the reduce launch turns them back while it reads them.
+extern "C" int mi_denoise_self_ensemble(mi_plan* plan, const float* noisy, float* mean_out, float* std_out, float* samples_out,
+                                        int B, int H, int W, const int32_t* views, int n_views,
+                                        const int32_t* t_list, int n_iters,
+                                        const float* beta, const float* alpha, const float* alpha_hat, int noise_steps,
+                                        int seeded, uint64_t seed, int64_t sample_offset, int64_t member_offset, int pass_samples, int flags,
+                                        void* workspace, size_t workspace_bytes, void* stream) {
+    DihedralViews dv;
+    if (!plan) return fail(MI_EINVAL, "null plan");
+    if (int rc = check_views(views, n_views, H, W, &dv)) return rc;      // the view list first, then the rules of an ensemble with one member per view
+    if (int rc = check_ensemble_args(plan, B, n_views, H, W, sample_offset, member_offset, pass_samples)) return rc;
+    if (!mean_out && !std_out && !samples_out) return fail(MI_EINVAL, "no output: give at least one of mean_out, std_out, samples_out");
+    if (int rc = check_std_views(std_out, n_views)) return rc;
+    const int Cc = plan->cfg.in_channels;
+    const size_t chw = (size_t)Cc * H * W, img = chw * sizeof(float);
+    const Buf buf[4] = {{noisy, (size_t)B * img, "noisy"}, {mean_out, (size_t)B * img, "mean_out"}, {std_out, (size_t)B * img, "std_out"},
+                        {samples_out, (size_t)B * n_views * img, "samples_out"}};
+    if (int rc = check_no_overlap(buf, 4, "noisy is read by every pass and the reduce writes mean_out, std_out and samples_out in one launch"))
+        return rc;
+    const Schedule sc{t_list, n_iters, beta, alpha, alpha_hat, noise_steps};
+    EnsembleLayout L{};
+    // (evaluated before the state check, reported after it: check_batched_call; host arithmetic only, as in the *_workspace_bytes queries)
+    const int layout_rc = ensemble_layout(plan, B, n_views, H, W, pass_samples, false, &L);
+    if (int rc = check_batched_call(plan, layout_rc, L, workspace, workspace_bytes, {noisy}, sc)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    char* ws = (char*)workspace;
+    float* views_out = reinterpret_cast<float*>(ws + L.samples_off);
+    std::lock_guard<std::mutex> side_lk(plan->side_mu);     // held over all passes: the side streams are per plan
+    HIPCHK(hipMemsetAsync(ws, 0, 256, s));                  // status word: once per call, the passes accumulate into it
+    StepNoise sn;                                           // view k draws as member member_offset + k, at the pixel's place in the VIEW's frame
+    if (seeded) { sn.seeded = true; sn.seed = seed; sn.sample_offset = sample_offset; sn.members = n_views; sn.member_offset = (uint32_t)member_offset; }
+    auto fill = [&](float* cond, int v0, int n) { return launched(dihedral_views_launch(noisy, cond, dv, Cc, H, W, v0, n, s), "dihedral_views"); };
+    if (int rc = run_passes(plan, fill, views_out, (int64_t)B * n_views, 1, H, W, chw, L, sn, sc, flags, ws, stream)) return rc;
+    return launched(dihedral_reduce_launch(views_out, B, dv, Cc, H, W, mean_out, std_out, samples_out, s), "dihedral_reduce");
+}

@@ -1,5 +1,6 @@
 // Types and functions shared by the host side of libmidd.so: midd_abi.hip (C ABI surface), midd_weights.hip (topology, weight
-// repacking, time table), midd_planner.hip (execution planner) and midd_exec.hip (executor).  No torch, no allocation on the hot path.
+// repacking, time table), midd_planner.hip (execution planner), midd_exec.hip (executor), midd_sampler.hip (sampler calls) and
+// midd_batched.hip (batched calls; the last three share midd_sampler.h).  No torch, no allocation on the hot path.
 #pragma once
 #include "../../include/midd.h"
 #include "midd_internal.h"
@@ -112,15 +113,15 @@ int dump_program(mi_plan* p, int B, int H, int W, bool side_by_side, std::string
 // (unless the caller gives samples_out)]; pass = virtual samples per pass, tail = those of the last pass when it is shorter (else 0)
 struct EnsembleLayout { int pass, tail; size_t run_bytes, cond_off, samples_off, bytes; };
 int ensemble_layout(mi_plan* p, int B, int members, int H, int W, int pass_samples, bool samples_external, EnsembleLayout* L);   // midd_planner.hip
-int check_ensemble_args(mi_plan* p, int B, int members, int H, int W, int64_t sample_offset, int64_t member_offset, int pass_samples);   // midd_exec.hip
+int check_ensemble_args(mi_plan* p, int B, int members, int H, int W, int64_t sample_offset, int64_t member_offset, int pass_samples);   // midd_batched.hip
 // mi_denoise_tiled: its argument rules (no GPU work) -> the geometry; its workspace is an EnsembleLayout with members = tiles per
 // image at the tile's shape: [sampler workspace of a pass | condition tiles of a pass | tile outputs (unless tiles_out is given)]
-int check_tiled_args(mi_plan* p, int B, int H, int W, int th, int tw, int oy, int ox, int64_t sample_offset, int pass_samples, TileGeom* g);   // midd_exec.hip
+int check_tiled_args(mi_plan* p, int B, int H, int W, int th, int tw, int oy, int ox, int64_t sample_offset, int pass_samples, TileGeom* g);   // midd_batched.hip
 // mi_denoise_tiled_ensemble: the rules of mi_denoise_tiled and of an ensemble's members (no GPU work) -> the geometry; its workspace
 // is mi_denoise_tiled's -- a pass never spans two members -- with the tile outputs of every member: [sampler workspace of a pass |
 // condition tiles of a pass | tile outputs [members][B][tiles] (unless tiles_out is given)]
 int check_tiled_ensemble_args(mi_plan* p, int B, int members, int H, int W, int th, int tw, int oy, int ox, int64_t sample_offset,
-                              int64_t member_offset, int pass_samples, TileGeom* g);   // midd_exec.hip
+                              int64_t member_offset, int pass_samples, TileGeom* g);   // midd_batched.hip
 int tiled_ensemble_layout(mi_plan* p, int B, int members, int tiles, int th, int tw, int pass_samples, bool tiles_external, EnsembleLayout* L);   // midd_planner.hip
 // mi_denoise_self_ensemble: its workspace is mi_denoise_ensemble's with members = views and the member outputs ALWAYS inside:
 // [sampler workspace of a pass | condition views of a pass | view outputs [B][views], each in its view's frame]

@@ -251,7 +251,6 @@ struct OutConvArgs {
     // this launch's H, W as the tile): the noise field belongs to the image, not to the tiling.  0: pitch W, plane H*W, origin 0
     int tiles_x, tiles_y, img_H, img_W;
 };
-hipError_t out_conv_launch(const OutConvArgs& a, hipStream_t s);
 // mi_denoise_slots: every sample of a launch is a SLOT at its own timestep.  One record per sample and row of the loop, written
 // by the host for this row (slot_fill_launch) and read by out_conv_slots_kernel through scalar loads (b is per workgroup).
 enum SlotBits { SLOT_ACTIVE = 1, SLOT_NOISE = 2 };      // NOISE: t > 0 and the call has a noise term (seeded or a tensor)
@@ -266,7 +265,6 @@ struct SlotRec {
 constexpr int SLOTS_PER_LAUNCH = 32;
 struct SlotRecs { SlotRec v[SLOTS_PER_LAUNCH]; };      // 1 KiB of kernel arguments
 hipError_t slot_fill_launch(int* trow, SlotRec* dst, const SlotRecs& recs, int n, hipStream_t s);
-hipError_t out_conv_slots_launch(const OutConvArgs& a, const SlotRec* slots, hipStream_t s);
 // The DDIM(eta) update (include/midd.h: THE DDIM UPDATE): one row of the host's coefficient table and the launch-uniform switches,
 // a kernel argument of out_conv_ddim_kernel / out_conv_ddim_seeded_kernel alone (scalar loads).  OutConvArgs does not grow:
 // a.c1 .. a.c3 are not read by these kernels, everything else is.
@@ -275,9 +273,6 @@ struct DdimCoef {
     int clip_x0;                    // clip the predicted image to [0, 1] and re-derive eps
     int last;                       // last row of the list: the result is clamped to [0, 1]
 };
-// a.seeded != 0 (host: only with k.s > 0): the term s * noise is drawn as out_conv_seeded_kernel draws it; else it is read from
-// a.noise when that is given and k.s > 0
-hipError_t out_conv_ddim_launch(const OutConvArgs& a, const DdimCoef& k, hipStream_t s);
 // The second-order multistep update (include/midd.h: THE DPMPP2M UPDATE): the DDIM row at eta = 0 (s == 0 is not carried) and the
 // multistep weight g, a kernel argument of out_conv_dpm_kernel alone (scalar loads).  OutConvArgs does not grow here either.
 struct DpmCoef {
@@ -286,9 +281,24 @@ struct DpmCoef {
     int clip_x0;
     int last;
 };
-// x0_prev (read when k.g != 0) and x0_out (written) are [a.B, ic, H, W] fp32 and may be the same address: each thread reads its
-// own element before it writes it.  The rule is deterministic: a.seeded or a.noise is refused.
-hipError_t out_conv_dpm_launch(const OutConvArgs& a, const DpmCoef& k, const float* x0_prev, float* x0_out, hipStream_t s);
+// The update a step's out_conv launch runs, from the sampler's schedule to the kernel: which rule, and that rule's arguments alone.
+//   OUT_FORWARD   : none -- the network output only (mi_unet_forward; a.x is null)
+//   OUT_REFERENCE : the reference's, a.c1 .. a.c3 <- ref (the other rules do not read them)
+//   OUT_DDIM      : a.seeded != 0 (host: only with k.s > 0): the term s * noise is drawn as out_conv_seeded_kernel draws it; else it
+//                   is read from a.noise when that is given and k.s > 0
+//   OUT_DPM       : x0_prev (read when k.g != 0) and x0_out (written) are [a.B, ic, H, W] fp32 and may be the same address: each thread
+//                   reads its own element before it writes it.  The rule is deterministic: a.seeded or a.noise is refused
+//   OUT_SLOTS     : every sample from its record of this row (device, [a.B])
+enum OutUpdateKind { OUT_FORWARD, OUT_REFERENCE, OUT_DDIM, OUT_DPM, OUT_SLOTS };
+struct RefCoef { float c1, c2, c3; };
+struct DpmStep { DpmCoef k; const float* x0_prev; float* x0_out; };
+struct OutUpdate {
+    OutUpdateKind kind;
+    union { RefCoef ref; DdimCoef ddim; DpmStep dpm; const SlotRec* slots; };
+};
+hipError_t out_conv_launch(const OutConvArgs& a, const OutUpdate& u, hipStream_t s);
+// the kernel symbol that launch runs (without its <1> / <0>): what a profile reports
+const char* out_conv_symbol(const OutUpdate& u, int seeded);
 // dst [n_iters][B][chw] <- the 0.5-scaled seeded step noise of `member` (step_noise_common.h); chw < 2^32, B and n_iters <= 65535
 hipError_t step_noise_fill_launch(float* dst, int n_iters, int B, unsigned long long chw, unsigned long long seed, long long sample_offset,
                                   unsigned member, hipStream_t s);

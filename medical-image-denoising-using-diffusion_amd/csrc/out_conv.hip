@@ -92,7 +92,7 @@ static bool out_conv_shape_ok(const OutConvArgs& a, size_t* lds, int* tiles) {
     return true;
 }
 
-// The arguments of an update that draws its noise term for virtual samples (a.seeded of out_conv_launch and out_conv_ddim_launch)
+// The arguments of an update that draws its noise term for virtual samples (a.seeded of launch_reference and launch_ddim)
 static bool out_conv_seeded_ok(const OutConvArgs& a) {
     if ((unsigned long long)a.ic * a.H * a.W >= (1ull << 32) || a.members < 1 || a.v0 < 0) return false;
     if (a.tiles_x && (a.tiles_x < 1 || a.tiles_y < 1 || a.members != a.tiles_x * a.tiles_y || a.img_H < a.H || a.img_W < a.W ||
@@ -107,7 +107,7 @@ static bool out_conv_seeded_ok(const OutConvArgs& a) {
         else hipLaunchKernelGGL(KERNEL<0>, dim3(a.B * tiles), dim3(256), lds, s, __VA_ARGS__); \
     } while (0)
 
-hipError_t out_conv_launch(const OutConvArgs& a, hipStream_t s) {
+static hipError_t launch_reference(const OutConvArgs& a, hipStream_t s) {
     size_t lds; int tiles;
     if (!out_conv_shape_ok(a, &lds, &tiles)) return hipErrorInvalidValue;
     if (a.seeded) {
@@ -119,7 +119,7 @@ hipError_t out_conv_launch(const OutConvArgs& a, hipStream_t s) {
 
 // a.seeded != 0: the noise term of the slots with SLOT_NOISE is drawn from (a.seed, rec.image, rec.iter, element, member 0); else it
 // is read from a.noise when that is given.  a.c1 .. a.c3, a.iter, a.sample_offset, a.v0, a.members and the tile fields are not read.
-hipError_t out_conv_slots_launch(const OutConvArgs& a, const SlotRec* slots, hipStream_t s) {
+static hipError_t launch_slots(const OutConvArgs& a, const SlotRec* slots, hipStream_t s) {
     size_t lds; int tiles;
     if (!out_conv_shape_ok(a, &lds, &tiles) || !slots || !a.x) return hipErrorInvalidValue;
     if (a.seeded && (a.noise || (unsigned long long)a.ic * a.H * a.W >= (1ull << 32))) return hipErrorInvalidValue;
@@ -128,7 +128,7 @@ hipError_t out_conv_slots_launch(const OutConvArgs& a, const SlotRec* slots, hip
 }
 
 // a.c1 .. a.c3 are not read.  The seeded form is launched only when a term is drawn at all (a.seeded: the host sets it with k.s > 0)
-hipError_t out_conv_ddim_launch(const OutConvArgs& a, const DdimCoef& k, hipStream_t s) {
+static hipError_t launch_ddim(const OutConvArgs& a, const DdimCoef& k, hipStream_t s) {
     size_t lds; int tiles;
     if (!out_conv_shape_ok(a, &lds, &tiles) || !a.x) return hipErrorInvalidValue;
     if (a.seeded) {
@@ -139,7 +139,7 @@ hipError_t out_conv_ddim_launch(const OutConvArgs& a, const DdimCoef& k, hipStre
 }
 
 // a.c1 .. a.c3, a.noise and the seeded fields are not read: the rule has no noise term.  x0_prev is read only when k.g != 0
-hipError_t out_conv_dpm_launch(const OutConvArgs& a, const DpmCoef& k, const float* x0_prev, float* x0_out, hipStream_t s) {
+static hipError_t launch_dpm(const OutConvArgs& a, const DpmCoef& k, const float* x0_prev, float* x0_out, hipStream_t s) {
     size_t lds; int tiles;
     if (!out_conv_shape_ok(a, &lds, &tiles) || !a.x || !x0_out || (k.g != 0.0f && !x0_prev)) return hipErrorInvalidValue;
     if (a.seeded || a.noise) return hipErrorInvalidValue;
@@ -147,6 +147,32 @@ hipError_t out_conv_dpm_launch(const OutConvArgs& a, const DpmCoef& k, const flo
     return hipGetLastError();
 }
 #undef MIDD_OUT_LAUNCH
+
+// The one launcher (midd_internal.h: OutUpdate) and, beside it, the symbol it launches: one switch each over the same kinds
+hipError_t out_conv_launch(const OutConvArgs& a, const OutUpdate& u, hipStream_t s) {
+    switch (u.kind) {
+        case OUT_SLOTS: return launch_slots(a, u.slots, s);
+        case OUT_DDIM: return launch_ddim(a, u.ddim, s);
+        case OUT_DPM: return launch_dpm(a, u.dpm.k, u.dpm.x0_prev, u.dpm.x0_out, s);
+        case OUT_REFERENCE: {
+            OutConvArgs r = a;
+            r.c1 = u.ref.c1; r.c2 = u.ref.c2; r.c3 = u.ref.c3;
+            return launch_reference(r, s);
+        }
+        case OUT_FORWARD: break;
+    }
+    return launch_reference(a, s);
+}
+
+const char* out_conv_symbol(const OutUpdate& u, int seeded) {
+    switch (u.kind) {
+        case OUT_SLOTS: return "out_conv_slots_kernel";
+        case OUT_DDIM: return seeded ? "out_conv_ddim_seeded_kernel" : "out_conv_ddim_kernel";
+        case OUT_DPM: return "out_conv_dpm_kernel";
+        case OUT_REFERENCE: case OUT_FORWARD: break;
+    }
+    return seeded ? "out_conv_seeded_kernel" : "out_conv_kernel";
+}
 
 // One row of mi_denoise_slots for n <= SLOTS_PER_LAUNCH samples: their records travel as kernel arguments (copied when the launch
 // is enqueued: nothing on the device ever reads the caller's host tables) into the program's record region, and every sample's

@@ -38,8 +38,10 @@ int main() {
     if (timeit("in_conv", [&] { return in_conv_launch(x, cond, w, bias, out, tot, 4, 6, B, 1, H, W, C, PW_BLOCKED, 0); }, act * 4.0)) return 1;
     OutConvArgs a{};
     a.src = out; a.gn_tot = tot; a.stat_rep = 4; a.gn_bs = 6; a.gn_gamma = gam; a.gn_beta = bet; a.gn_eps = 1e-5f; a.w = w; a.bias = bias;
-    a.blocked = PW_BLOCKED; a.B = B; a.H = H; a.W = W; a.C = C; a.ic = 1; a.eps_out = nullptr; a.x = img; a.noise = nullptr; a.c1 = 1.f; a.c2 = 0.1f; a.c3 = 0.f; a.clamp_eps = 0;
-    if (timeit("out_conv", [&] { return out_conv_launch(a, 0); }, act * 4.0)) return 1;
+    a.blocked = PW_BLOCKED; a.B = B; a.H = H; a.W = W; a.C = C; a.ic = 1; a.eps_out = nullptr; a.x = img; a.noise = nullptr; a.clamp_eps = 0;
+    OutUpdate u{};
+    u.kind = OUT_REFERENCE; u.ref = RefCoef{1.f, 0.1f, 0.f};
+    if (timeit("out_conv", [&] { return out_conv_launch(a, u, 0); }, act * 4.0)) return 1;
     if (timeit("resize256", [&] { return resize_bilinear_launch(reinterpret_cast<const float*>(lo), out, tot, 4, 6, B, 128, 128, C, 256, 256, PW_BLOCKED, 0); }, act * 5.0)) return 1;
     if (timeit("resize128", [&] { return resize_bilinear_launch(reinterpret_cast<const float*>(lo), out, tot, 4, 12, B, 64, 64, 96, 128, 128, PW_BLOCKED, 0); }, (double)B * 128 * 128 * 96 * 5.0)) return 1;
     return 0;
