@@ -191,6 +191,29 @@ int mi_denoise_slots(mi_plan* plan, const float* cond, float* x, int B, int H, i
                      const float* step_noise, int seeded, uint64_t seed, int flags,
                      void* workspace, size_t workspace_bytes, void* stream);
 
+/* The same loop with every slot a VIRTUAL SAMPLE: slot b carries its own member word and the frame of its element index, the two
+ * things a member of mi_denoise_ensemble and a tile of mi_denoise_tiled differ in from a whole image.  mi_denoise_slots is this
+ * call with member == frame == NULL: same bits, same launches; every rule above holds, in its order.
+ *   member        HOST int64 [B] or NULL (all 0): counter word c3 of slot b, 0 <= member[b] < 2^32
+ *   frame         HOST uint32 [B][3] or NULL: (pitch, plane, origin) of slot b; NULL = (W, H*W, 0).  The element index (counter
+ *                 word c0) of channel c, row y, column x of the slot is  c * plane + y * pitch + x + origin  in uint32 arithmetic
+ * With frame[b] = (Wi, Hi*Wi, y0*Wi + x0) slot b draws what mi_denoise_tiled draws for the tile at origin (y0, x0) of an Hi x Wi
+ * image whose global index is sample_index[b]: the noise field belongs to the image, not to the tiling, so the tiles of one image
+ * may sit in any slots, join at any call and run at different rows.  With member[b] = m it draws what mi_denoise_ensemble draws
+ * for member m (member_offset included) of image sample_index[b].  With a batch-invariant plan a slot's result is therefore the
+ * tile's or the member's bits in those calls, whatever shares the batch.
+ * Both tables are read before the call returns, as the others are (they travel in the per-row records, 48 bytes a slot).
+ * Further MI_EINVAL cases, before any GPU work and after the rules of mi_denoise_slots up to "seeded together with step_noise":
+ * member or frame given without seeded (they are the generator's counter words; a step_noise tensor is already per slot);
+ * member[b] outside [0, 2^32); a frame row with pitch < W; with origin + (H-1)*pitch + W > plane (in 64 bits: the slot would
+ * leave its channel plane); with C*plane >= 2^32. */
+int mi_denoise_slots_virtual(mi_plan* plan, const float* cond, float* x, int B, int H, int W,
+                             const int32_t* t_rows, int n_rows, const int32_t* iter_base, const int64_t* sample_index,
+                             const int64_t* member, const uint32_t* frame,
+                             const float* beta, const float* alpha, const float* alpha_hat, int noise_steps,
+                             const float* step_noise, int seeded, uint64_t seed, int flags,
+                             void* workspace, size_t workspace_bytes, void* stream);
+
 /* The values mi_denoise_seeded draws, as a tensor (no plan needed): dst device fp32 [n_iters,B,C,H,W] <- 0.5 * z of
  * (seed, sample_offset + b, i, element), i.e. already 0.5-scaled as mi_denoise's `step_noise` expects.  Replay and export:
  * mi_denoise with this tensor equals mi_denoise_seeded bit for bit.  Every iteration is filled (the t == 0 entry is ignored

@@ -254,16 +254,24 @@ struct OutConvArgs {
 // mi_denoise_slots: every sample of a launch is a SLOT at its own timestep.  One record per sample and row of the loop, written
 // by the host for this row (slot_fill_launch) and read by out_conv_slots_kernel through scalar loads (b is per workgroup).
 enum SlotBits { SLOT_ACTIVE = 1, SLOT_NOISE = 2 };      // NOISE: t > 0 and the call has a noise term (seeded or a tensor)
-struct SlotRec {
+// A slot is a VIRTUAL sample (mi_denoise_slots_virtual): it carries the member word and the frame that out_conv_seeded_kernel
+// derives from a.members / a.tiles_x for a uniform launch -- element index = oc * plane + y * pitch + x + origin, all uint32.
+// (0, W, H*W, 0) is a whole image, member 0: mi_denoise_slots.  Twelve words, 16-byte aligned: the kernel reads the first quad
+// (which decides whether the workgroup leaves) with one s_load_dwordx4 and, past the idle branch, the counter words with an
+// s_load_dwordx2 and an s_load_dwordx4 (profiles/slot_tickets_isa.txt).
+struct alignas(16) SlotRec {
     float c1, c2, c3;               // x <- clamp(c1 * (x - c2 * eps) + c3 * noise, 0, 1) at the slot's timestep
     int active;                     // SlotBits; 0 = idle: x keeps its bits, nothing is drawn or written
     unsigned iter;                  // noise counter word c2: iter_base + row
     unsigned image;                 // noise counter word c1: low word of the slot's global sample index
     int trow;                       // the slot's time-table row (0 when idle)
+    unsigned member;                // noise counter word c3: the slot's ensemble member
+    unsigned pitch, plane, origin;  // the element index's frame: row pitch, channel plane and first element of the slot in its image
     int pad;
 };
+static_assert(sizeof(SlotRec) == 48, "out_conv_slots_kernel reads a record as 12 words");
 constexpr int SLOTS_PER_LAUNCH = 32;
-struct SlotRecs { SlotRec v[SLOTS_PER_LAUNCH]; };      // 1 KiB of kernel arguments
+struct SlotRecs { SlotRec v[SLOTS_PER_LAUNCH]; };      // 1.5 KiB of kernel arguments (the limit is 4 KiB)
 hipError_t slot_fill_launch(int* trow, SlotRec* dst, const SlotRecs& recs, int n, hipStream_t s);
 // The DDIM(eta) update (include/midd.h: THE DDIM UPDATE): one row of the host's coefficient table and the launch-uniform switches,
 // a kernel argument of out_conv_ddim_kernel / out_conv_ddim_seeded_kernel alone (scalar loads).  OutConvArgs does not grow:

@@ -43,6 +43,9 @@ struct StepIO {
 struct SlotRows {
     const int32_t* iter_base;         // [B] or null (all 0)
     const int64_t* sample_index;      // [B] or null (0 .. B-1)
+    // mi_denoise_slots_virtual: the slot's member word and the frame of its element index (SlotRec, midd_internal.h)
+    const int64_t* member = nullptr;  // [B] or null (all 0)
+    const uint32_t* frame = nullptr;  // [B][3] (pitch, plane, origin) or null: (W, H*W, 0)
 };
 
 // the rc of a launch wrapper's hipError_t

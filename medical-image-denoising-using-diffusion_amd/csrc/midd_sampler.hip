@@ -168,7 +168,7 @@ static OutUpdate uniform_update(const Schedule& sc, int i, size_t at, bool* draw
 
 // Row i of mi_denoise_slots for the Bh columns from col0 of every table: their records leave as kernel arguments, SLOTS_PER_LAUNCH
 // a launch, for recs[Bh], and their time-table rows for trow[Bh]
-static int fill_slot_row(const Schedule& sc, const SlotRows& slots, bool has_noise, int i, int B, int col0, int Bh,
+static int fill_slot_row(const Schedule& sc, const SlotRows& slots, bool has_noise, int i, int B, int H, int W, int col0, int Bh,
                          int* trow, SlotRec* recs, hipStream_t sh) {
     for (int c0 = 0; c0 < Bh; c0 += SLOTS_PER_LAUNCH) {
         SlotRecs r{};
@@ -182,6 +182,9 @@ static int fill_slot_row(const Schedule& sc, const SlotRows& slots, bool has_noi
             q.iter = (unsigned)((slots.iter_base ? slots.iter_base[col] : 0) + i);
             q.image = (unsigned)(uint64_t)(slots.sample_index ? slots.sample_index[col] : (int64_t)col);
             q.trow = t;
+            q.member = (unsigned)(uint64_t)(slots.member ? slots.member[col] : 0);
+            const uint32_t* f = slots.frame ? slots.frame + (size_t)col * 3 : nullptr;
+            q.pitch = f ? f[0] : (unsigned)W; q.plane = f ? f[1] : (unsigned)H * (unsigned)W; q.origin = f ? f[2] : 0u;
         }
         if (int rc = launched(slot_fill_launch(trow + c0, recs + c0, r, m, sh), "slot records")) return rc;
     }
@@ -238,7 +241,7 @@ int midd::enqueue_run(mi_plan* plan, Program* g, const float* noisy, float* x_ou
                 if (slots) {
                     // sub-batch h takes columns [h * Bh, (h + 1) * Bh) of every table
                     SlotRec* recs = reinterpret_cast<SlotRec*>(wsh + gh->slot_off);
-                    if (int rc2 = fill_slot_row(sc, *slots, sn.seeded || sn.tensor, i, B, h * Bh, Bh, trow, recs, sh)) return rc2;
+                    if (int rc2 = fill_slot_row(sc, *slots, sn.seeded || sn.tensor, i, B, H, W, h * Bh, Bh, trow, recs, sh)) return rc2;
                     io.update.kind = OUT_SLOTS; io.update.slots = recs;
                     io.noise = sn.tensor ? sn.tensor + (size_t)i * img_elems + h * part : nullptr;
                     io.sn.seeded = sn.seeded; io.sn.seed = sn.seed;
@@ -354,11 +357,13 @@ extern "C" int mi_denoise_dpm(mi_plan* plan, const float* noisy, float* x_out, f
 }
 
 // ---------------------------------------------------------------------------- per-slot timesteps (continuous batching)
-extern "C" int mi_denoise_slots(mi_plan* plan, const float* cond, float* x, int B, int H, int W,
-                                const int32_t* t_rows, int n_rows, const int32_t* iter_base, const int64_t* sample_index,
-                                const float* beta, const float* alpha, const float* alpha_hat, int noise_steps,
-                                const float* step_noise, int seeded, uint64_t seed, int flags,
-                                void* workspace, size_t workspace_bytes, void* stream) {
+// mi_denoise_slots is this call with member == frame == NULL: one body, so the same rules in the same order and the same launches
+extern "C" int mi_denoise_slots_virtual(mi_plan* plan, const float* cond, float* x, int B, int H, int W,
+                                        const int32_t* t_rows, int n_rows, const int32_t* iter_base, const int64_t* sample_index,
+                                        const int64_t* member, const uint32_t* frame,
+                                        const float* beta, const float* alpha, const float* alpha_hat, int noise_steps,
+                                        const float* step_noise, int seeded, uint64_t seed, int flags,
+                                        void* workspace, size_t workspace_bytes, void* stream) {
     if (!plan) return fail(MI_EINVAL, "null plan");
     if (!cond || !x || !beta || !alpha || !alpha_hat || (n_rows > 0 && !t_rows)) return fail(MI_EINVAL, "null argument");
     if (n_rows < 0) return fail(MI_EINVAL, "n_rows %d is negative (limit: n_rows >= 0)", n_rows);
@@ -384,6 +389,25 @@ extern "C" int mi_denoise_slots(mi_plan* plan, const float* cond, float* x, int 
     if (seeded) {
         if (step_noise) return fail(MI_EINVAL, "seeded together with step_noise: the noise term is drawn or read, not both");
         if (int rc = check_step_noise_range(plan->cfg.in_channels, H, W, 0)) return rc;
+    } else if (member || frame) {
+        return fail(MI_EINVAL, "%s without seeded: the table holds counter words of the seeded generator, a step_noise tensor is already "
+                    "per slot (limit: member and frame need seeded != 0)", member ? "member" : "frame");
+    }
+    for (int b = 0; member && b < B; ++b)
+        if (member[b] < 0 || member[b] >= ((int64_t)1 << 32))
+            return fail(MI_EINVAL, "member[%d]=%lld outside [0, 2^32): the member index is one 32-bit counter word (limit: member < 4294967296)",
+                        b, (long long)member[b]);
+    for (int b = 0; frame && b < B; ++b) {
+        const uint64_t pitch = frame[(size_t)b * 3], plane = frame[(size_t)b * 3 + 1], origin = frame[(size_t)b * 3 + 2];
+        if (pitch < (uint64_t)W)
+            return fail(MI_EINVAL, "frame[%d]: pitch %llu is less than the slot's width %d (limit: pitch >= W)", b, (unsigned long long)pitch, W);
+        if (origin + (uint64_t)(H - 1) * pitch + (uint64_t)W > plane)
+            return fail(MI_EINVAL, "frame[%d]: origin %llu + (H-1)*pitch + W = %llu leaves the plane of %llu elements "
+                        "(limit: origin + (H-1)*pitch + W <= plane)", b, (unsigned long long)origin,
+                        (unsigned long long)(origin + (uint64_t)(H - 1) * pitch + (uint64_t)W), (unsigned long long)plane);
+        if ((uint64_t)plan->cfg.in_channels * plane >= (1ull << 32))
+            return fail(MI_EINVAL, "frame[%d]: C*plane = %d*%llu reaches 2^32: the element index of the seeded step noise is one 32-bit "
+                        "counter word (limit: C*plane < 4294967296)", b, plan->cfg.in_channels, (unsigned long long)plane);
     }
     const size_t batch_bytes = (size_t)B * plan->cfg.in_channels * H * W * sizeof(float);
     const Buf buf[2] = {{x, batch_bytes, "x"}, {cond, batch_bytes, "cond"}};
@@ -396,11 +420,20 @@ extern "C" int mi_denoise_slots(mi_plan* plan, const float* cond, float* x, int 
     if (n_rows == 0) return MI_OK;
     StepNoise sn;
     sn.tensor = step_noise; sn.seeded = seeded != 0; sn.seed = seed;
-    const SlotRows slots{iter_base, sample_index};
+    const SlotRows slots{iter_base, sample_index, member, frame};
     std::lock_guard<std::mutex> side_lk(plan->side_mu);
     HIPCHK(hipMemsetAsync(workspace, 0, 256, (hipStream_t)stream));      // status word: once per call
     return enqueue_run(plan, g, cond, x, B, H, W, Schedule{t_rows, n_rows, beta, alpha, alpha_hat, noise_steps}, &slots, sn, flags,
                        workspace, workspace_bytes, stream);
+}
+
+extern "C" int mi_denoise_slots(mi_plan* plan, const float* cond, float* x, int B, int H, int W,
+                                const int32_t* t_rows, int n_rows, const int32_t* iter_base, const int64_t* sample_index,
+                                const float* beta, const float* alpha, const float* alpha_hat, int noise_steps,
+                                const float* step_noise, int seeded, uint64_t seed, int flags,
+                                void* workspace, size_t workspace_bytes, void* stream) {
+    return mi_denoise_slots_virtual(plan, cond, x, B, H, W, t_rows, n_rows, iter_base, sample_index, nullptr, nullptr, beta, alpha, alpha_hat,
+                                    noise_steps, step_noise, seeded, seed, flags, workspace, workspace_bytes, stream);
 }
 
 extern "C" int mi_step_noise_fill_member(float* dst, int n_iters, int B, int C, int H, int W,

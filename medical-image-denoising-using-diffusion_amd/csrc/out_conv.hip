@@ -117,7 +117,7 @@ static hipError_t launch_reference(const OutConvArgs& a, hipStream_t s) {
     return hipGetLastError();
 }
 
-// a.seeded != 0: the noise term of the slots with SLOT_NOISE is drawn from (a.seed, rec.image, rec.iter, element, member 0); else it
+// a.seeded != 0: the noise term of the slots with SLOT_NOISE is drawn from (a.seed, rec.image, rec.iter, element in the record's frame, rec.member); else it
 // is read from a.noise when that is given.  a.c1 .. a.c3, a.iter, a.sample_offset, a.v0, a.members and the tile fields are not read.
 static hipError_t launch_slots(const OutConvArgs& a, const SlotRec* slots, hipStream_t s) {
     size_t lds; int tiles;

@@ -9,6 +9,8 @@
 // and whether the sample is updated at all come from the sample's SlotRec (midd_internal.h) instead of the arguments -- every
 // sample of the launch is at its own timestep.  b is per workgroup, so the record is read with scalar loads; the workgroups of
 // an idle slot leave at once: nothing is staged, drawn or written.  The other two compiles do not see a token of it.
+// The record also carries the member word and the (pitch, plane, origin) frame of the element index (mi_denoise_slots_virtual):
+// a slot draws what a member of mi_denoise_ensemble or a tile of mi_denoise_tiled draws.
 // Two more, MIDD_OUT_DDIM 1 = out_conv_ddim_kernel (MIDD_OUT_SEEDED 0) and out_conv_ddim_seeded_kernel (1): the DDIM(eta) update of
 // include/midd.h (THE DDIM UPDATE) in the place of the reference's, its coefficients in a kernel argument of their own (DdimCoef,
 // scalar loads).  The three compiles above do not see a token of it either.
@@ -150,8 +152,10 @@ void MIDD_OUT_KERNEL(const OutConvArgs a, const float* __restrict__ wglob /* == 
             float xn = rec.c1 * __builtin_fmaf(-rec.c2, eps, a.x[o]);
             if (rec.active & SLOT_NOISE) {        // (t > 0 and the call has a noise term)
                 if (a.seeded) {
-                    const uint32_t elem = (uint32_t)oc * ((uint32_t)a.H * (uint32_t)a.W) + (uint32_t)oy * (uint32_t)a.W + (uint32_t)ox;
-                    xn = __builtin_fmaf(rec.c3, step_noise_value(a.seed, (long long)rec.image, (int)rec.iter, elem, 0u), xn);
+                    // the slot is a virtual sample: the element index of out_conv_seeded_kernel below with the record's frame -- (W, H*W, 0)
+                    // for a whole image, a tile's place in its image otherwise -- and the record's member word (scalar arithmetic)
+                    const uint32_t elem = (uint32_t)oc * rec.plane + (uint32_t)oy * rec.pitch + (uint32_t)ox + rec.origin;
+                    xn = __builtin_fmaf(rec.c3, step_noise_value(a.seed, (long long)rec.image, (int)rec.iter, elem, rec.member), xn);
                 } else if (a.noise) {
                     xn = __builtin_fmaf(rec.c3, a.noise[o], xn);
                 }

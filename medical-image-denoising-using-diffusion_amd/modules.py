@@ -350,12 +350,15 @@ class UNetDiffusion(nn.Module):
     def run_slots(self, cond: torch.Tensor, x: torch.Tensor, t_rows, beta: torch.Tensor, alpha: torch.Tensor, alpha_hat: torch.Tensor,
                   clamp_eps: bool, iter_base=None, sample_index=None, step_noise: Optional[torch.Tensor] = None,
                   seed: Optional[int] = None, no_split: bool = False, max_slots: Optional[int] = None, *,
-                  update: str = "reference") -> torch.Tensor:
+                  update: str = "reference", member=None, frame=None) -> torch.Tensor:
         """The sampler loop with per-slot timesteps (mi_denoise_slots): ``t_rows`` [n_rows][B] holds every slot's timestep per row,
         -1 = idle.  ``x`` [B,C,H,W] is updated IN PLACE (and returned) and is not initialised: a caller starting a slot copies its
         condition image into it; both tensors must be contiguous.  ``iter_base`` [B]: rows a slot has already run;
         ``sample_index`` [B]: its global image index (seeded noise).  ``max_slots``: the workspace is sized for every batch up to
-        this many slots and kept, so that a session whose batch changes from call to call allocates once."""
+        this many slots and kept, so that a session whose batch changes from call to call allocates once.
+        ``member`` [B] and ``frame`` [B][3] = (pitch, plane, origin) make a slot a virtual sample (mi_denoise_slots_virtual): the
+        member word of its noise and the frame of its element index, what a member of run_ensemble and a tile of run_tiled
+        draw.  Both need ``seed``; with both None the call is mi_denoise_slots."""
         from .sampler import check_seed, refuse_update
         refuse_update(update, "run_slots (mi_denoise_slots)")
         if seed is not None:
@@ -378,16 +381,30 @@ class UNetDiffusion(nn.Module):
             if ib.size and (ib.min() < -(1 << 31) or ib.max() >= 1 << 31):
                 raise ValueError("iter_base must fit 32 bits")
             ib = ib.astype(np.int32)
+        virtual = ()
+        if member is not None or frame is not None:
+            mb = None if member is None else np.ascontiguousarray(np.asarray(member, dtype=np.int64))
+            if mb is not None and mb.shape != (B,):
+                raise ValueError(f"member must have one entry per slot ({B})")
+            fr = None if frame is None else np.asarray(frame, dtype=np.int64)
+            if fr is not None:
+                if fr.shape != (B, 3):
+                    raise ValueError(f"frame must have one (pitch, plane, origin) row per slot ([{B}, 3])")
+                if fr.size and (fr.min() < 0 or fr.max() >= 1 << 32):
+                    raise ValueError("frame entries must fit 32 bits (the element index is one 32-bit counter word)")
+                fr = np.ascontiguousarray(fr.astype(np.uint32))
+            virtual = (None if mb is None else mb.ctypes.data_as(C.POINTER(C.c_int64)),
+                       None if fr is None else fr.ctypes.data_as(C.POINTER(C.c_uint32)))
         keep, tables = self._table_args(beta, alpha, alpha_hat)
         dev = cond.device
         with self._lock, torch.cuda.device(dev):
             plan = self._ensure_plan(time_rows=tables[-1])
             step_noise = self._step_noise(step_noise, n_rows, cond, "n_rows")
             ws = self._workspace(B, H, W, dev) if not max_slots else self._slots_workspace(max(int(max_slots), B), H, W, dev)
-            self._invoke(native.lib().mi_denoise_slots,
+            self._invoke(native.lib().mi_denoise_slots_virtual if virtual else native.lib().mi_denoise_slots,
                          (plan, cond.data_ptr(), x.data_ptr(), B, H, W, rows.ctypes.data_as(C.POINTER(C.c_int32)), n_rows,
                           None if ib is None else ib.ctypes.data_as(C.POINTER(C.c_int32)),
-                          None if si is None else si.ctypes.data_as(C.POINTER(C.c_int64))) + tables
+                          None if si is None else si.ctypes.data_as(C.POINTER(C.c_int64))) + virtual + tables
                          + (_ptr(step_noise), 0 if seed is None else 1, C.c_uint64(seed or 0), self._call_flags(clamp_eps, no_split)), ws, dev)
         return x
 

@@ -72,6 +72,11 @@ SYMBOLS = [
                                    C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int64),
                                    C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int,
                                    C.c_void_p, C.c_int, C.c_uint64, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
+    ("mi_denoise_slots_virtual", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                           C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int64),
+                                           C.POINTER(C.c_int64), C.POINTER(C.c_uint32),
+                                           C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int,
+                                           C.c_void_p, C.c_int, C.c_uint64, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
     ("mi_step_noise_fill", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_int64,
                                      C.c_void_p]),
     ("mi_step_noise_fill_member", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_int64,

@@ -35,6 +35,16 @@ the upload's own levels; values outside it come back as lo or hi (the window cli
 reports ``window``.  It needs bit_depth=16, changes pre and post only (so it works with batch_slots > 0 and update="ddim"), and
 an upload that is not 16-bit is answered 400 with the file's mode.
 
+``DiffusionService(tile=N)`` or ``tile=(TH, TW)`` (or ``MIDD_TILE="N"`` / ``"TH,TW"``, with ``overlap`` / ``MIDD_TILE_OVERLAP``, default 32),
+not in the reference either, serves every upload at its NATIVE size: no resize to 512x512 and back.  The upload is decoded and scaled
+at its own size by whichever recipe is configured (8-bit, 16-bit, windowed), denoised as blended overlapping tiles
+(``DiffusionDenoiser.denoise_tiled``) and answered at its own size; where the sizes are equal no resample runs at all.  An axis
+shorter than the tile is resampled up to the tile length on that axis only, with the recipe's own resize, and back afterwards, so
+every upload is answered.  With ``batch_slots > 0`` the session is built at the tile's shape and requests go in through
+``SamplerSession.submit_tiled``: the tiles of uploads of different sizes share one batch.  ``update="ddim"`` / ``"dpmpp2m"`` pass
+through to ``denoise_tiled`` (batch_slots == 0).  ``/health`` reports ``tile`` and ``overlap``.  None, the default, is no tiling:
+the paths and bytes above.
+
 ``python-multipart`` is not available in this image, so the multipart body is parsed with the
 standard library instead of FastAPI's ``UploadFile``; the wire format is the same.
 """
@@ -62,13 +72,40 @@ SERVE_SIZE = (512, 512)          # run.py:198
 SERVE_INFERENCE_STEPS = 8        # run.py:107 (-> 9 iterations with noise_steps=50)
 
 
+def serve_size(image_size: Tuple[int, int], tile: Optional[Tuple[int, int]] = None) -> Tuple[int, int]:
+    """(H, W) the sampler sees for an upload of PIL size (width, height): SERVE_SIZE, or -- with a tile -- the upload's own size,
+    an axis shorter than the tile raised to the tile's length (the resamplers leave an axis of equal length alone)."""
+    if tile is None:
+        return SERVE_SIZE
+    return max(image_size[1], tile[0]), max(image_size[0], tile[1])
+
+
+def check_tile(tile, overlap) -> Tuple[Tuple[int, int], Tuple[int, int]]:
+    """A service's (tile, overlap) -> ((th, tw), (oy, ox)): a tile is a shape the network takes (multiples of 8), an overlap at most
+    half of it (DiffusionDenoiser.denoise_tiled)."""
+    def pair(v, what):
+        try:
+            a, b = v if isinstance(v, (tuple, list)) else (v, v)
+            if isinstance(a, bool) or isinstance(b, bool) or int(a) != a or int(b) != b:
+                raise ValueError
+            return int(a), int(b)
+        except (TypeError, ValueError):
+            raise ValueError(f"{what} is an integer or a (y, x) pair of integers (got {v!r})") from None
+    (th, tw), (oy, ox) = pair(tile, "tile"), pair(overlap, "overlap")
+    if th < 8 or tw < 8 or th % 8 or tw % 8:
+        raise ValueError(f"tile {th}x{tw} is not a shape the network takes: both sides are positive multiples of 8")
+    if oy < 0 or ox < 0 or 2 * oy > th or 2 * ox > tw:
+        raise ValueError(f"overlap {oy},{ox} must lie in [0, tile / 2] (tile {th}x{tw})")
+    return (th, tw), (oy, ox)
+
+
 # ------------------------------------------------------------------------------ pre / post
-def preprocess(image_bytes: bytes) -> Tuple[torch.Tensor, Tuple[int, int]]:
+def preprocess(image_bytes: bytes, tile=None) -> Tuple[torch.Tensor, Tuple[int, int]]:
     """bytes -> (fp32 [1,1,512,512] in [0,1], original (width, height)) — run.py:193-201.
     ``transforms.Resize`` on a PIL image is ``Image.resize(..., BICUBIC)``; ``ToTensor`` is uint8/255."""
     image = Image.open(io.BytesIO(image_bytes)).convert("L")
     original_size = image.size
-    resized = image.resize(SERVE_SIZE[::-1], Image.BICUBIC)
+    resized = image.resize(serve_size(original_size, tile)[::-1], Image.BICUBIC)      # (equal sizes: a copy, no resample)
     arr = np.asarray(resized, dtype=np.uint8).astype(np.float32) / 255.0
     return torch.from_numpy(arr)[None, None], original_size
 
@@ -83,14 +120,14 @@ def tensor_to_base64(tensor: torch.Tensor, size: Tuple[int, int]) -> str:
     return base64.b64encode(buffered.getvalue()).decode()
 
 
-def preprocess_device(image_bytes: bytes, device: torch.device) -> Tuple[torch.Tensor, Tuple[int, int]]:
+def preprocess_device(image_bytes: bytes, device: torch.device, tile=None) -> Tuple[torch.Tensor, Tuple[int, int]]:
     """`preprocess` with the resize and the ToTensor scaling on the GPU (csrc/prepost.hip; bit-identical to the
     host recipe): only the PNG/JPEG decode stays on the host."""
     from . import prepost
     image = Image.open(io.BytesIO(image_bytes)).convert("L")
     original_size = image.size
     raw = torch.from_numpy(np.asarray(image, dtype=np.uint8).copy()).to(device, non_blocking=True)
-    resized = prepost.resize_bicubic_u8(raw, SERVE_SIZE)
+    resized = prepost.resize_bicubic_u8(raw, serve_size(original_size, tile))
     return prepost.to_unit_float(resized)[None, None], original_size
 
 
@@ -104,12 +141,12 @@ def tensor_to_base64_device(tensor: torch.Tensor, size: Tuple[int, int]) -> str:
     return base64.b64encode(buffered.getvalue()).decode()
 
 
-def preprocess16(image_bytes: bytes) -> Tuple[torch.Tensor, Tuple[int, int]]:
+def preprocess16(image_bytes: bytes, tile=None) -> Tuple[torch.Tensor, Tuple[int, int]]:
     """`preprocess` of the 16-bit recipe: decode to unit float (/ 65535 for a 16-bit file, `convert("L")` / 255 for any other),
     Pillow mode "F" bicubic resize to 512x512, clip to [0, 1]."""
     image = Image.open(io.BytesIO(image_bytes))
     original_size = image.size
-    x = image16.resize_f(image16.unit_float(image16.decode16(image)), SERVE_SIZE)
+    x = image16.resize_f(image16.unit_float(image16.decode16(image)), serve_size(original_size, tile))
     return torch.from_numpy(x)[None, None], original_size
 
 
@@ -119,14 +156,14 @@ def tensor_to_base64_16(tensor: torch.Tensor, size: Tuple[int, int]) -> str:
     return base64.b64encode(image16.png_bytes_u16(image16.to_u16(image16.resize_f(x, (size[1], size[0]))))).decode()
 
 
-def preprocess16_device(image_bytes: bytes, device: torch.device) -> Tuple[torch.Tensor, Tuple[int, int]]:
+def preprocess16_device(image_bytes: bytes, device: torch.device, tile=None) -> Tuple[torch.Tensor, Tuple[int, int]]:
     """`preprocess16` with the scaling, the resize and the clip on the GPU (one fused call of csrc/prepost.hip; bit-identical to
     the host recipe): only the decode stays on the host."""
     from . import prepost
     image = Image.open(io.BytesIO(image_bytes))
     original_size = image.size
     raw = torch.from_numpy(image16.decode16(image)).to(device, non_blocking=True)
-    return prepost.resize_bicubic_f32(raw, SERVE_SIZE, clamp=True)[None, None], original_size
+    return prepost.resize_bicubic_f32(raw, serve_size(original_size, tile), clamp=True)[None, None], original_size
 
 
 def tensor_to_base64_16_device(tensor: torch.Tensor, size: Tuple[int, int]) -> str:
@@ -137,14 +174,14 @@ def tensor_to_base64_16_device(tensor: torch.Tensor, size: Tuple[int, int]) -> s
     return base64.b64encode(image16.png_bytes_u16(back)).decode()
 
 
-def preprocess16_window(image_bytes: bytes, percentiles) -> Tuple[torch.Tensor, Tuple[int, int, Tuple[int, int]]]:
+def preprocess16_window(image_bytes: bytes, percentiles, tile=None) -> Tuple[torch.Tensor, Tuple[int, int, Tuple[int, int]]]:
     """`preprocess16` under a window (include/midd.h: THE WINDOW): the levels (lo, hi) at the two percentiles of THIS upload, the
     windowed load, the mode "F" resize, the clip.  The second value carries the levels to the way back: (width, height, (lo, hi)).
     An upload that is not 16-bit raises image16.WindowInputError naming its mode (the route answers 400)."""
     image = Image.open(io.BytesIO(image_bytes))
     raw = image16.need_u16(image16.decode16(image), image.mode)
     levels = image16.window_levels(raw, percentiles)
-    x = image16.resize_f(image16.unit_float_window(raw, levels), SERVE_SIZE)
+    x = image16.resize_f(image16.unit_float_window(raw, levels), serve_size(image.size, tile))
     return torch.from_numpy(x)[None, None], image.size + (levels,)
 
 
@@ -154,14 +191,14 @@ def tensor_to_base64_16_window(tensor: torch.Tensor, size) -> str:
     return base64.b64encode(image16.png_bytes_u16(image16.to_u16_window(image16.resize_f(x, (size[1], size[0])), size[2]))).decode()
 
 
-def preprocess16_window_device(image_bytes: bytes, device: torch.device, percentiles):
+def preprocess16_window_device(image_bytes: bytes, device: torch.device, percentiles, tile=None):
     """`preprocess16_window` on the GPU: histogram, levels, and one fused windowed load + resize + clip (csrc/prepost.hip).  The levels
     stay on the device, an int32 [1,2] tensor in the place of (lo, hi): nothing waits for them."""
     from . import prepost
     image = Image.open(io.BytesIO(image_bytes))
     raw = torch.from_numpy(image16.need_u16(image16.decode16(image), image.mode)).to(device, non_blocking=True)
     levels = prepost.window_levels(raw, percentiles)
-    return prepost.resize_bicubic_f32(raw, SERVE_SIZE, clamp=True, levels=levels)[None, None], image.size + (levels,)
+    return prepost.resize_bicubic_f32(raw, serve_size(image.size, tile), clamp=True, levels=levels)[None, None], image.size + (levels,)
 
 
 def tensor_to_base64_16_window_device(tensor: torch.Tensor, size) -> str:
@@ -191,7 +228,7 @@ class DiffusionService:
                  denoise_fn: Optional[Callable[[torch.Tensor], torch.Tensor]] = None, compute: Optional[str] = None,
                  batch_slots: Optional[int] = None, batch_invariant: Optional[bool] = None, session_factory=None,
                  update: Optional[str] = None, eta: Optional[float] = None, bit_depth: Optional[int] = None,
-                 window: Optional[Tuple[float, float]] = None):
+                 window: Optional[Tuple[float, float]] = None, tile=None, overlap=None):
         # 8: the reference's 8-bit pre/post-processing; 16: the 16-bit recipe (preprocess16 / tensor_to_base64_16).  None reads
         # MIDD_BIT_DEPTH, default 8
         self.bit_depth = image16.check_bit_depth(int(os.environ.get("MIDD_BIT_DEPTH", "8")) if bit_depth is None else bit_depth)
@@ -202,6 +239,17 @@ class DiffusionService:
         self.window = None if window is None else image16.check_percentiles(window)
         if self.window is not None and self.bit_depth != 16:
             raise ValueError("a window needs bit_depth=16 (the window acts on 16-bit uploads)")
+        # (th, tw): every upload is served at its own size as blended overlapping tiles (DiffusionDenoiser.denoise_tiled); None reads
+        # MIDD_TILE ("N" or "TH,TW") and MIDD_TILE_OVERLAP, default no tiling: the resize to SERVE_SIZE and back
+        if tile is None and os.environ.get("MIDD_TILE"):
+            parts = os.environ["MIDD_TILE"].split(",")
+            try:
+                tile = tuple(int(p) for p in parts) if len(parts) == 2 else int(os.environ["MIDD_TILE"])
+            except ValueError:
+                raise ValueError(f"MIDD_TILE takes N or TH,TW, got {os.environ['MIDD_TILE']!r}") from None
+        if overlap is None:
+            overlap = int(os.environ.get("MIDD_TILE_OVERLAP", "32"))
+        self.tile, self.overlap = (None, None) if tile is None else check_tile(tile, overlap)
         # the sampler's update rule (DiffusionDenoiser.denoise): None reads MIDD_UPDATE / MIDD_ETA, default the reference's
         self.update = os.environ.get("MIDD_UPDATE", "reference") if update is None else update
         self.eta = float(os.environ.get("MIDD_ETA", "0")) if eta is None else float(eta)
@@ -251,7 +299,11 @@ class DiffusionService:
             else:
                 rule = {} if self.update == "reference" else {"update": self.update} if self.update == "dpmpp2m" \
                     else {"update": self.update, "eta": self.eta}
-                output = self.diffusion_denoiser.denoise(input_tensor, inference_steps=SERVE_INFERENCE_STEPS, **rule)
+                if self.tile is not None:
+                    output = self.diffusion_denoiser.denoise_tiled(input_tensor, inference_steps=SERVE_INFERENCE_STEPS, tile=self.tile,
+                                                                   overlap=self.overlap, **rule).image
+                else:
+                    output = self.diffusion_denoiser.denoise(input_tensor, inference_steps=SERVE_INFERENCE_STEPS, **rule)
             output = torch.clamp(output, 0, 1)
             if len(original_size) == 3:       # a windowed request: (width, height, levels)
                 result = (tensor_to_base64_16_window_device if output.is_cuda else tensor_to_base64_16_window)(output, original_size)
@@ -267,7 +319,8 @@ class DiffusionService:
         if self._session_factory is not None:
             return self._session_factory(self)
         from .session import SamplerSession
-        return SamplerSession(self.diffusion_denoiser, SERVE_SIZE[0], SERVE_SIZE[1], slots=self.batch_slots)
+        H, W = SERVE_SIZE if self.tile is None else self.tile      # tiled: the slot is a tile, whatever the uploads' sizes
+        return SamplerSession(self.diffusion_denoiser, H, W, slots=self.batch_slots)
 
     def _submit(self, input_tensor: torch.Tensor):
         with self._wake:
@@ -277,7 +330,10 @@ class DiffusionService:
                 self._stopping = False
                 self._worker = threading.Thread(target=self._work, name="midd-batch-worker", daemon=True)
                 self._worker.start()
-            ticket = self._session.submit(input_tensor, SERVE_INFERENCE_STEPS)
+            if self.tile is not None:
+                ticket = self._session.submit_tiled(input_tensor, SERVE_INFERENCE_STEPS, overlap=self.overlap)
+            else:
+                ticket = self._session.submit(input_tensor, SERVE_INFERENCE_STEPS)
             self._wake.notify()
         return ticket
 
@@ -329,12 +385,12 @@ class DiffusionService:
         """Decode + resize + scale; on the GPU when the service runs there (same bytes either way)."""
         if self.window is not None:
             if self.device.type == "cuda" and self._denoise_fn is None:
-                return preprocess16_window_device(image_bytes, self.device, self.window)
-            x, size = preprocess16_window(image_bytes, self.window)
+                return preprocess16_window_device(image_bytes, self.device, self.window, tile=self.tile)
+            x, size = preprocess16_window(image_bytes, self.window, tile=self.tile)
             return x.to(self.device), size
         if self.device.type == "cuda" and self._denoise_fn is None:
-            return (preprocess16_device if self.bit_depth == 16 else preprocess_device)(image_bytes, self.device)
-        x, size = (preprocess16 if self.bit_depth == 16 else preprocess)(image_bytes)
+            return (preprocess16_device if self.bit_depth == 16 else preprocess_device)(image_bytes, self.device, tile=self.tile)
+        x, size = (preprocess16 if self.bit_depth == 16 else preprocess)(image_bytes, tile=self.tile)
         return x.to(self.device), size
 
 
@@ -382,6 +438,7 @@ def create_app(service: Optional[DiffusionService] = None, checkpoint: Optional[
     async def health_check():
         return {"status": "healthy", "device": str(svc.device), "batch_slots": svc.batch_slots, "bit_depth": svc.bit_depth,
                 "update": svc.update,
+                "tile": None if svc.tile is None else list(svc.tile), "overlap": None if svc.tile is None else list(svc.overlap),
                 "window": None if svc.window is None else list(svc.window),
                 "models_loaded": {"diffusion": svc.diffusion_model is not None or svc._denoise_fn is not None,
                                   "nafnet": False, "expert": False, "hybrid": False}}

@@ -118,6 +118,18 @@ int main() {
     REFUSED(mi_denoise_slots(p, A, B_, 2, 65536, 65536, rows, 3, nullptr, nullptr, tab, tab, ah, 50, nullptr, 1, 5, 0, WS, WSB, nullptr));
     REFUSED(mi_denoise_slots(p, A, A + 4, 2, 32, 32, rows, 3, nullptr, nullptr, tab, tab, ah, 50, nullptr, 1, 5, 0, WS, WSB, nullptr));
     REFUSED(mi_denoise_slots(p, A, B_, 2, 32, 32, rows, 3, nullptr, nullptr, tab, tab, ah, 50, nullptr, 1, 5, 0, WS, WSB, nullptr));
+    // the virtual-sample tables: member words and (pitch, plane, origin) frames, the 64-bit sum at the top of the uint32 range included
+    const int64_t mb_ok[2] = {3, ((int64_t)1 << 32) - 1}, mb_neg[2] = {0, -1}, mb_top[2] = {(int64_t)1 << 32, 0};
+    const uint32_t fr_ok[6] = {88, 88 * 104, 0, 88, 88 * 104, 72 * 88 + 56}, fr_pitch[6] = {32, 1024, 0, 31, 1024, 0};
+    const uint32_t fr_origin[6] = {32, 1024, 0, 40, 1280, 9}, fr_wrap[6] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 32, 1024, 0};
+    REFUSED(mi_denoise_slots_virtual(p, A, B_, 2, 32, 32, rows, 3, nullptr, nullptr, mb_neg, nullptr, tab, tab, ah, 50, nullptr, 1, 5, 0, WS, WSB, nullptr));
+    REFUSED(mi_denoise_slots_virtual(p, A, B_, 2, 32, 32, rows, 3, nullptr, nullptr, mb_top, nullptr, tab, tab, ah, 50, nullptr, 1, 5, 0, WS, WSB, nullptr));
+    REFUSED(mi_denoise_slots_virtual(p, A, B_, 2, 32, 32, rows, 3, nullptr, nullptr, nullptr, fr_pitch, tab, tab, ah, 50, nullptr, 1, 5, 0, WS, WSB, nullptr));
+    REFUSED(mi_denoise_slots_virtual(p, A, B_, 2, 32, 32, rows, 3, nullptr, nullptr, nullptr, fr_origin, tab, tab, ah, 50, nullptr, 1, 5, 0, WS, WSB, nullptr));
+    REFUSED(mi_denoise_slots_virtual(p, A, B_, 2, 32, 32, rows, 3, nullptr, nullptr, nullptr, fr_wrap, tab, tab, ah, 50, nullptr, 1, 5, 0, WS, WSB, nullptr));
+    REFUSED(mi_denoise_slots_virtual(p, A, B_, 2, 32, 32, rows, 3, nullptr, nullptr, mb_ok, nullptr, tab, tab, ah, 50, nullptr, 0, 5, 0, WS, WSB, nullptr));
+    REFUSED(mi_denoise_slots_virtual(p, A, B_, 2, 32, 32, rows, 3, nullptr, nullptr, nullptr, fr_ok, tab, tab, ah, 50, C_, 0, 5, 0, WS, WSB, nullptr));
+    REFUSED(mi_denoise_slots_virtual(p, A, B_, 2, 32, 32, rows, 3, nullptr, nullptr, mb_ok, fr_ok, tab, tab, ah, 50, nullptr, 1, 5, 0, WS, WSB, nullptr));      // valid: the state check
     REFUSED(mi_step_noise_fill(A, 2, 2, 1, 32, 32, 5, -1, nullptr));
     REFUSED(mi_step_noise_fill(A, 2, 2, 1, 65536, 65536, 5, 0, nullptr));
     REFUSED(mi_step_noise_fill(A, 65536, 2, 1, 32, 32, 5, 0, nullptr));
