@@ -563,8 +563,8 @@ int mi_denoise_ensemble_rule(mi_plan* plan, const float* noisy, float* mean_out,
                              const mi_update_rule* rule, void* workspace, size_t workspace_bytes, void* stream);
 
 /* mi_denoise_tiled plus `rule`, likewise.  Workspace: mi_tiled_workspace_bytes.
- * NOT BUILT: mi_denoise_slots (its per-slot record would have to carry the seven coefficients), mi_denoise_tiled_ensemble and
- * mi_denoise_self_ensemble (plumbing only) keep the reference's rule. */
+ * The per-slot loop runs the rule through mi_denoise_slots_rule below (mi_denoise_slots and mi_denoise_slots_virtual themselves keep
+ * the reference's).  NOT BUILT: mi_denoise_tiled_ensemble and mi_denoise_self_ensemble (plumbing only) keep the reference's rule. */
 int mi_denoise_tiled_rule(mi_plan* plan, const float* noisy, float* image_out, float* tiles_out,
                           int B, int H, int W, int th, int tw, int oy, int ox,
                           const int32_t* t_list, int n_iters,
@@ -616,12 +616,52 @@ int mi_denoise_dpm(mi_plan* plan, const float* noisy, float* x_out, float* x0_bu
 
 /* mi_denoise_tiled under the rule above (no seed: deterministic).  x0_hist: DEVICE fp32 [pass_samples, C, th, tw], the in-place
  * history of whichever pass runs, reused by every pass; there is no trajectory for tiles.  Workspace: mi_tiled_workspace_bytes.
- * NOT BUILT under this rule: mi_denoise_slots, ensembles of any kind (nothing is drawn), an SDE (eta > 0) form, a third order. */
+ * The per-slot loop under this rule is mi_denoise_slots_rule below.
+ * NOT BUILT under this rule: ensembles of any kind (nothing is drawn), an SDE (eta > 0) form, a third order. */
 int mi_denoise_tiled_dpm(mi_plan* plan, const float* noisy, float* image_out, float* tiles_out, float* x0_hist,
                          int B, int H, int W, int th, int tw, int oy, int ox,
                          const int32_t* t_list, int n_iters,
                          const float* beta, const float* alpha, const float* alpha_hat, int noise_steps,
                          int pass_samples, int flags, int clip_x0, void* workspace, size_t workspace_bytes, void* stream);
+
+/* One row of both tables from a timestep and its NEIGHBOURS in a list, host only (no plan, no GPU): out HOST fp32 [8] <-
+ * (k0, k1, r0, r1, a, b, s, g) of the iteration at t whose list has t_before in front of it and t_after behind it; -1 = none.
+ * t_before = -1 is a list's first row (g = 0), t_after = -1 its last (P = 1: a = 1, b = 0, s = 0, g = 0).  Columns 0 .. 6 are the
+ * row of mi_ddim_coefficients at `eta`, column 7 the g of mi_dpm_coefficients, bit for bit: the list forms ask this function.
+ * MI_EINVAL as mi_ddim_coefficients, applied to the triple: eta; a null argument; noise_steps < 1; t outside [0, noise_steps),
+ * a neighbour outside [-1, noise_steps); a triple that is not strictly decreasing; alpha_hat outside the rule on either step. */
+int mi_update_row(int32_t t_before, int32_t t, int32_t t_after, const float* alpha_hat, int noise_steps, double eta, float out[8]);
+
+/* CONTINUOUS BATCHING UNDER A RULE: mi_denoise_slots_virtual plus `rule`, every slot at its own place in its own list.
+ * rule == NULL or kind MI_UPDATE_REFERENCE: mi_denoise_slots_virtual, bit for bit, the same launches; t_before, t_after and x0_hist
+ * must then be NULL.  MI_UPDATE_DDIM (x0_hist NULL) and MI_UPDATE_DPMPP2M (x0_hist required; seeded and step_noise refused: the
+ * rule is deterministic) run THE DDIM UPDATE / THE DPMPP2M UPDATE per slot: the row of slot b in row i is mi_update_row of
+ *   previous = t_rows[i-1][b], or t_before[b] in the call's first row
+ *   next     = t_rows[i+1][b], or t_after[b] in the call's last row; -1 there (or an idle row) means the slot's list ends with
+ *              this row: it is the list's LAST row, a = 1, and the result is clamped to [0, 1]
+ * so a list cut into calls anywhere -- a session's call boundaries -- gives the coefficients, and with a batch-invariant plan the
+ * bits, of the list run whole; a uniform table with x preset to the condition gives mi_denoise_rule's / mi_denoise_dpm's bits at
+ * the same B.
+ *   t_before, t_after  HOST int32 [B] or NULL (all -1)
+ *   x0_hist            DEVICE fp32 [B,C,H,W], MI_UPDATE_DPMPP2M only: slot b's previous predicted image, read (where g != 0) and
+ *                      written (every active slot) in place, each thread its own element; an idle slot's keeps its bits.  It
+ *                      travels with the slot: a caller that moves a slot's x moves its x0_hist.  Never read before it is written
+ *                      (a list's first row has g = 0): no initialisation.  Overlaps neither cond nor x
+ * The noise term s * n is added where the row's s > 0 and the call has a noise source, drawn with the slot's counter words exactly
+ * as mi_denoise_slots_virtual draws.  Sub-batches, phase offset, join, status word: as mi_denoise_slots; sub-batch h takes its
+ * columns of x0_hist too.  The records are 64 bytes a slot and live where mi_denoise_slots' 48-byte records live: the region is
+ * sized for the larger, so mi_workspace_bytes grows by 16 bytes per sample (before its 256-byte rounding).
+ * MI_EINVAL, judged before the plan's state and before any GPU work (mi_last_error names the argument): the kinds' rules above,
+ * first; every rule of mi_denoise_slots_virtual; t_before / t_after outside [-1, noise_steps); a column whose sequence
+ * (t_before, active rows, t_after) is not strictly decreasing or breaks mi_ddim_coefficients' alpha_hat rule on a step;
+ * t_after[b] >= 0 for a slot that went idle inside the call; x0_hist overlapping x or cond. */
+int mi_denoise_slots_rule(mi_plan* plan, const float* cond, float* x, int B, int H, int W,
+                          const int32_t* t_rows, int n_rows, const int32_t* iter_base, const int64_t* sample_index,
+                          const int64_t* member, const uint32_t* frame,
+                          const int32_t* t_before, const int32_t* t_after, float* x0_hist,
+                          const float* beta, const float* alpha, const float* alpha_hat, int noise_steps,
+                          const float* step_noise, int seeded, uint64_t seed, int flags,
+                          const mi_update_rule* rule, void* workspace, size_t workspace_bytes, void* stream);
 
 /* Status of the last mi_unet_forward / mi_denoise call that used `workspace` (its first word; the calls clear it when they
  * start).  SYNCHRONISES `stream` (one 4-byte device-to-host copy).  Returns MI_OK with *flags == 0, or MI_ERANGE with the

@@ -10,7 +10,7 @@ the C ABI declared in ``include/midd.h``.  There is no CPU fallback: without the
 from .config import UNetConfig, topology, param_shapes, timestep_list  # noqa: F401
 from .modules import UNetDiffusion  # noqa: F401
 from .sampler import (DiffusionDenoiser, EnsembleQuantileResult, EnsembleResult, SamplerTrajectory, SelfEnsembleQuantileResult,  # noqa: F401
-                      SelfEnsembleResult, dpm_coefficients,
+                      SelfEnsembleResult, SamplerRule, dpm_coefficients,
                       TilePlan, TiledEnsembleQuantileResult, TiledEnsembleResult, TiledResult, ddim_coefficients, device, dihedral_quantiles,
                       dihedral_reduce, dihedral_views, ensemble_quantiles, ensemble_reduce, step_noise, tile_blend,
                       tile_blend_quantiles, tile_blend_reduce, tile_extract, tile_plan, view_codes)

@@ -90,7 +90,7 @@ struct Program {
     bool wide_chunks = false;  // f16x3 3x3 convs may take the wide-chunk variant (conv16_pick_tile): programs that run alone
     std::vector<Op> ops;
     size_t bytes = 0, trow_off = 0;
-    size_t slot_off = 0;                        // SlotRec [B] (midd_internal.h): rewritten before every row of mi_denoise_slots
+    size_t slot_off = 0;                        // SlotRec [B] or SlotRuleRec [B] (midd_internal.h; sized for the larger): rewritten before every row of mi_denoise_slots / mi_denoise_slots_rule
     size_t stats_off = 0, stats_bytes = 0;      // statistics arena: every tensor's totals, zeroed by one memset per forward
     int stat_rep = 1;                           // copies per channel (against same-address atomic serialisation)
     std::map<std::string, TensorRef> outputs;

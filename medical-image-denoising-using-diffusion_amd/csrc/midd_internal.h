@@ -273,6 +273,25 @@ static_assert(sizeof(SlotRec) == 48, "out_conv_slots_kernel reads a record as 12
 constexpr int SLOTS_PER_LAUNCH = 32;
 struct SlotRecs { SlotRec v[SLOTS_PER_LAUNCH]; };      // 1.5 KiB of kernel arguments (the limit is 4 KiB)
 hipError_t slot_fill_launch(int* trow, SlotRec* dst, const SlotRecs& recs, int n, hipStream_t s);
+// mi_denoise_slots_rule: the slot's record under THE DDIM UPDATE / THE DPMPP2M UPDATE (include/midd.h), read by out_conv_slots_rule_kernel
+// alone; SlotRec and out_conv_slots_kernel are what they were.  `active` takes two more bits: LAST, the slot's list ends with this row
+// (the result is clamped to [0, 1]), and HIST, g != 0 (the slot's previous predicted image is read).  Sixteen words, 16-byte aligned,
+// the quad that decides whether the workgroup leaves first: one scalar load before the idle branch (hipcc narrows it to `active`
+// alone), the coefficients and counter words past it as s_load_dwordx8 + s_load_dwordx4 (profiles/slots_rule_isa.txt).  The coefficients are one row of mi_update_row for the slot's (previous, own, next) timesteps.
+enum SlotRuleBits { SLOT_LAST = 4, SLOT_HIST = 8 };
+struct alignas(16) SlotRuleRec {
+    int active;                     // SlotBits | SlotRuleBits; 0 = idle: x and x0_hist keep their bits, nothing is drawn or written
+    int trow;                       // the slot's time-table row (0 when idle)
+    unsigned iter;                  // noise counter word c2: iter_base + row
+    unsigned image;                 // noise counter word c1: low word of the slot's global sample index
+    float k0, k1, r0, r1;           // as DdimCoef
+    float a, b, s, g;               // as DdimCoef / DpmCoef; g == 0 under the DDIM rule
+    unsigned member;                // noise counter word c3: the slot's ensemble member
+    unsigned pitch, plane, origin;  // the element index's frame, as SlotRec's
+};
+static_assert(sizeof(SlotRuleRec) == 64, "out_conv_slots_rule_kernel reads a record as 16 words");
+struct SlotRuleRecs { SlotRuleRec v[SLOTS_PER_LAUNCH]; };      // 2 KiB of kernel arguments (the limit is 4 KiB)
+hipError_t slot_rule_fill_launch(int* trow, SlotRuleRec* dst, const SlotRuleRecs& recs, int n, hipStream_t s);
 // The DDIM(eta) update (include/midd.h: THE DDIM UPDATE): one row of the host's coefficient table and the launch-uniform switches,
 // a kernel argument of out_conv_ddim_kernel / out_conv_ddim_seeded_kernel alone (scalar loads).  OutConvArgs does not grow:
 // a.c1 .. a.c3 are not read by these kernels, everything else is.
@@ -297,12 +316,16 @@ struct DpmCoef {
 //   OUT_DPM       : x0_prev (read when k.g != 0) and x0_out (written) are [a.B, ic, H, W] fp32 and may be the same address: each thread
 //                   reads its own element before it writes it.  The rule is deterministic: a.seeded or a.noise is refused
 //   OUT_SLOTS     : every sample from its record of this row (device, [a.B])
-enum OutUpdateKind { OUT_FORWARD, OUT_REFERENCE, OUT_DDIM, OUT_DPM, OUT_SLOTS };
+//   OUT_SLOTS_RULE: every sample from its SlotRuleRec of this row (device, [a.B]); clip_x0 is launch-uniform.  x0_hist [a.B, ic, H, W]
+//                   is null under the DDIM rule; under the multistep rule it is read where a record has SLOT_HIST, written for every
+//                   active slot, in place (each thread reads its own element before it writes it), and a noise source is refused
+enum OutUpdateKind { OUT_FORWARD, OUT_REFERENCE, OUT_DDIM, OUT_DPM, OUT_SLOTS, OUT_SLOTS_RULE };
 struct RefCoef { float c1, c2, c3; };
 struct DpmStep { DpmCoef k; const float* x0_prev; float* x0_out; };
+struct SlotRuleStep { const SlotRuleRec* recs; int clip_x0; float* x0_hist; };
 struct OutUpdate {
     OutUpdateKind kind;
-    union { RefCoef ref; DdimCoef ddim; DpmStep dpm; const SlotRec* slots; };
+    union { RefCoef ref; DdimCoef ddim; DpmStep dpm; const SlotRec* slots; SlotRuleStep slots_rule; };
 };
 hipError_t out_conv_launch(const OutConvArgs& a, const OutUpdate& u, hipStream_t s);
 // the kernel symbol that launch runs (without its <1> / <0>): what a profile reports

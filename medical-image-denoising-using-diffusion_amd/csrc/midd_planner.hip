@@ -92,7 +92,7 @@ static int build_program(mi_plan* p, int B, int H, int W, Program* g) {
     Builder bld{p, g, B};
     (void)bld.take(256);                      // [0, 256): the call's status word (mi_status); sub-batch programs leave theirs unused
     g->trow_off = bld.take((size_t)B * sizeof(int));
-    g->slot_off = bld.take((size_t)B * sizeof(SlotRec));      // mi_denoise_slots: this row's record of every sample
+    g->slot_off = bld.take((size_t)B * sizeof(SlotRuleRec));  // mi_denoise_slots / mi_denoise_slots_rule: this row's record of every sample, sized for the larger of the two
     int rc;
 
     auto run_rb = [&](const Mod& m, const TensorRef& s0, const TensorRef* s1, TensorRef* out) -> int {

@@ -46,6 +46,10 @@ struct SlotRows {
     // mi_denoise_slots_virtual: the slot's member word and the frame of its element index (SlotRec, midd_internal.h)
     const int64_t* member = nullptr;  // [B] or null (all 0)
     const uint32_t* frame = nullptr;  // [B][3] (pitch, plane, origin) or null: (W, H*W, 0)
+    // mi_denoise_slots_rule (sc.rule != MI_UPDATE_REFERENCE; sc.x0 is the call's x0_hist [B, C, H, W] under the multistep rule): the
+    // slot's timestep before the call's first row and after its last one, -1 = none (SlotRuleRec, midd_internal.h)
+    const int32_t* t_before = nullptr;    // [B] or null (all -1)
+    const int32_t* t_after = nullptr;     // [B] or null (all -1)
 };
 
 // the rc of a launch wrapper's hipError_t

@@ -22,13 +22,18 @@ int midd::check_schedule(mi_plan* plan, const Schedule& sc) {
 // THE DDIM UPDATE, host side (include/midd.h): row i of the coefficient table of a list, in double precision from the caller's
 // fp32 table, every value rounded once to fp32.  A = alpha_hat[t_i], P = alpha_hat[t_{i+1}], 1 after the last entry.  The one
 // place that computes it: mi_ddim_coefficients exports it, enqueue_run passes its rows to the update kernel.
-static void ddim_row(const int32_t* t, int n, const float* alpha_hat, double eta, int i, float out[7]) {
+// A row is a function of the timestep and its neighbours in the list, -1 = none: the list forms below and the per-slot call
+// (mi_denoise_slots_rule, mi_update_row), whose slots carry their neighbours across call boundaries, ask the same function.
+static void ddim_row3(int t, int t_after, const float* alpha_hat, double eta, float out[7]) {
 #pragma clang fp contract(off)
-    const double A = (double)alpha_hat[t[i]], P = i + 1 < n ? (double)alpha_hat[t[i + 1]] : 1.0;
+    const double A = (double)alpha_hat[t], P = t_after >= 0 ? (double)alpha_hat[t_after] : 1.0;
     const double sigma = eta * std::sqrt((1.0 - P) / (1.0 - A)) * std::sqrt(1.0 - A / P);
     const double rest = (1.0 - P) - sigma * sigma;
     out[0] = (float)(1.0 / std::sqrt(A)); out[1] = (float)std::sqrt(1.0 - A); out[2] = (float)std::sqrt(A); out[3] = (float)(1.0 / std::sqrt(1.0 - A));
     out[4] = (float)std::sqrt(P); out[5] = (float)std::sqrt(rest > 0.0 ? rest : 0.0); out[6] = (float)(2.0 * sigma);
+}
+static void ddim_row(const int32_t* t, int n, const float* alpha_hat, double eta, int i, float out[7]) {
+    ddim_row3(t[i], i + 1 < n ? t[i + 1] : -1, alpha_hat, eta, out);
 }
 
 // the rule's own argument rules, host only and before anything else of a call: eta, the list, the table entries the list reads
@@ -64,16 +69,46 @@ static double dpm_lambda(double X) {
 #pragma clang fp contract(off)
     return 0.5 * std::log(X / (1.0 - X));
 }
-static float dpm_g(const int32_t* t, int n, const float* alpha_hat, int i) {
+static float dpm_g3(int t_before, int t, int t_after, const float* alpha_hat) {
 #pragma clang fp contract(off)
-    if (i < 1 || i + 1 >= n) return 0.0f;
-    const double Q = (double)alpha_hat[t[i - 1]], A = (double)alpha_hat[t[i]], P = (double)alpha_hat[t[i + 1]];
+    if (t_before < 0 || t_after < 0) return 0.0f;
+    const double Q = (double)alpha_hat[t_before], A = (double)alpha_hat[t], P = (double)alpha_hat[t_after];
     const double lA = dpm_lambda(A);
     const double h = dpm_lambda(P) - lA, h_prev = lA - dpm_lambda(Q);
     const double r = h_prev / h;
     const double emh = std::sqrt(((1.0 - P) / (1.0 - A)) * (A / P));      // e^{-h} without exp
     // the extrapolation weight 1 / (2 r) bounded at its uniform-step value 1/2 (why)
     return (float)(std::sqrt(P) * (1.0 - emh) / (2.0 * (r > 1.0 ? r : 1.0)));
+}
+static float dpm_g(const int32_t* t, int n, const float* alpha_hat, int i) {
+    return dpm_g3(i > 0 ? t[i - 1] : -1, t[i], i + 1 < n ? t[i + 1] : -1, alpha_hat);
+}
+
+// the pair rule of check_ddim for one step of a list, t -> t_after (-1: the list ends, P = 1)
+static int check_ddim_pair(int t, int t_after, const float* alpha_hat) {
+    const double A = (double)alpha_hat[t], P = t_after >= 0 ? (double)alpha_hat[t_after] : 1.0;
+    if (!(A > 0.0 && A < P && P <= 1.0))
+        return fail(MI_EINVAL, "alpha_hat[%d]=%.9g, next %.9g: the DDIM update needs 0 < alpha_hat[t_i] < alpha_hat[t_{i+1}] <= 1", t, A, P);
+    return MI_OK;
+}
+
+// One row of either table from the timestep and its neighbours (include/midd.h): the per-slot call's rows, for a caller to hold
+extern "C" int mi_update_row(int32_t t_before, int32_t t, int32_t t_after, const float* alpha_hat, int noise_steps, double eta, float out[8]) {
+    if (!(eta >= 0.0 && eta <= 1.0)) return fail(MI_EINVAL, "eta %.17g outside [0, 1] (limit: 0 <= eta <= 1, not NaN)", eta);
+    if (!alpha_hat || !out) return fail(MI_EINVAL, "null argument");
+    if (noise_steps < 1) return fail(MI_EINVAL, "noise_steps %d: a schedule has at least one step (limit: noise_steps >= 1)", noise_steps);
+    if (t < 0 || t >= noise_steps) return fail(MI_EINVAL, "t=%d outside [0,%d)", t, noise_steps);
+    if (t_before < -1 || t_before >= noise_steps || t_after < -1 || t_after >= noise_steps)
+        return fail(MI_EINVAL, "t_before=%d / t_after=%d outside [-1,%d) (-1 = none)", t_before, t_after, noise_steps);
+    if ((t_before >= 0 && t_before <= t) || t_after >= t)
+        return fail(MI_EINVAL, "(t_before, t, t_after) = (%d, %d, %d): the DDIM update jumps from each timestep to the next one of the list "
+                    "(limit: strictly decreasing, -1 = none)", t_before, t, t_after);
+    if (t_before >= 0)
+        if (int rc = check_ddim_pair(t_before, t, alpha_hat)) return rc;
+    if (int rc = check_ddim_pair(t, t_after, alpha_hat)) return rc;
+    ddim_row3(t, t_after, alpha_hat, eta, out);
+    out[7] = dpm_g3(t_before, t, t_after, alpha_hat);
+    return MI_OK;
 }
 
 extern "C" int mi_dpm_coefficients(const int32_t* t_list, int n_iters, const float* alpha_hat, int noise_steps, float* out) {
@@ -191,6 +226,37 @@ static int fill_slot_row(const Schedule& sc, const SlotRows& slots, bool has_noi
     return MI_OK;
 }
 
+// The same row under a rule (mi_denoise_slots_rule): every record is the row of mi_update_row for the slot's own (previous, own, next)
+// timesteps -- the neighbours inside the call from the table, those across its first and last row from t_before / t_after -- so a
+// list cut into calls anywhere gives the coefficients of the list run whole.  g is the multistep rule's; eta is the DDIM rule's
+static int fill_slot_rule_row(const Schedule& sc, const SlotRows& slots, bool has_noise, int i, int B, int H, int W, int col0, int Bh,
+                              int* trow, SlotRuleRec* recs, hipStream_t sh) {
+    for (int c0 = 0; c0 < Bh; c0 += SLOTS_PER_LAUNCH) {
+        SlotRuleRecs r{};
+        const int m = Bh - c0 < SLOTS_PER_LAUNCH ? Bh - c0 : SLOTS_PER_LAUNCH;
+        for (int j = 0; j < m; ++j) {
+            const int col = col0 + c0 + j, t = sc.t[(size_t)i * B + col];
+            if (t < 0) continue;                             // idle: active 0, time row 0
+            const int tb = i > 0 ? sc.t[(size_t)(i - 1) * B + col] : (slots.t_before ? slots.t_before[col] : -1);
+            const int ta = i + 1 < sc.n ? sc.t[(size_t)(i + 1) * B + col] : (slots.t_after ? slots.t_after[col] : -1);
+            SlotRuleRec& q = r.v[j];
+            float k[7];
+            ddim_row3(t, ta, sc.alpha_hat, sc.eta, k);       // (eta is 0 under the multistep rule)
+            q.k0 = k[0]; q.k1 = k[1]; q.r0 = k[2]; q.r1 = k[3]; q.a = k[4]; q.b = k[5]; q.s = k[6];
+            q.g = sc.rule == MI_UPDATE_DPMPP2M ? dpm_g3(tb, t, ta, sc.alpha_hat) : 0.0f;
+            q.active = SLOT_ACTIVE | ((q.s > 0.0f && has_noise) ? SLOT_NOISE : 0) | (ta < 0 ? SLOT_LAST : 0) | (q.g != 0.0f ? SLOT_HIST : 0);
+            q.iter = (unsigned)((slots.iter_base ? slots.iter_base[col] : 0) + i);
+            q.image = (unsigned)(uint64_t)(slots.sample_index ? slots.sample_index[col] : (int64_t)col);
+            q.trow = t;
+            q.member = (unsigned)(uint64_t)(slots.member ? slots.member[col] : 0);
+            const uint32_t* f = slots.frame ? slots.frame + (size_t)col * 3 : nullptr;
+            q.pitch = f ? f[0] : (unsigned)W; q.plane = f ? f[1] : (unsigned)H * (unsigned)W; q.origin = f ? f[2] : 0u;
+        }
+        if (int rc = launched(slot_rule_fill_launch(trow + c0, recs + c0, r, m, sh), "slot rule records")) return rc;
+    }
+    return MI_OK;
+}
+
 // (the caller holds plan->side_mu and has cleared the status word at the head of `workspace`)
 int midd::enqueue_run(mi_plan* plan, Program* g, const float* noisy, float* x_out, int B, int H, int W,
                       const Schedule& sc, const SlotRows* slots, const StepNoise& sn, int flags,
@@ -238,7 +304,15 @@ int midd::enqueue_run(mi_plan* plan, Program* g, const float* noisy, float* x_ou
                 int* trow = reinterpret_cast<int*>(wsh + gh->trow_off);
                 StepIO io{};
                 io.x = x_out + h * part; io.cond = noisy + h * part; io.eps_out = nullptr; io.x_update = x_out + h * part;
-                if (slots) {
+                if (slots && sc.rule != MI_UPDATE_REFERENCE) {
+                    // the same under a rule: the larger records in the same region, and the sub-batch's columns of the history
+                    SlotRuleRec* recs = reinterpret_cast<SlotRuleRec*>(wsh + gh->slot_off);
+                    if (int rc2 = fill_slot_rule_row(sc, *slots, sn.seeded || sn.tensor, i, B, H, W, h * Bh, Bh, trow, recs, sh)) return rc2;
+                    io.update.kind = OUT_SLOTS_RULE;
+                    io.update.slots_rule = SlotRuleStep{recs, sc.clip_x0, sc.x0 ? sc.x0 + h * part : nullptr};
+                    io.noise = sn.tensor ? sn.tensor + (size_t)i * img_elems + h * part : nullptr;
+                    io.sn.seeded = sn.seeded; io.sn.seed = sn.seed;
+                } else if (slots) {
                     // sub-batch h takes columns [h * Bh, (h + 1) * Bh) of every table
                     SlotRec* recs = reinterpret_cast<SlotRec*>(wsh + gh->slot_off);
                     if (int rc2 = fill_slot_row(sc, *slots, sn.seeded || sn.tensor, i, B, H, W, h * Bh, Bh, trow, recs, sh)) return rc2;
@@ -357,13 +431,44 @@ extern "C" int mi_denoise_dpm(mi_plan* plan, const float* noisy, float* x_out, f
 }
 
 // ---------------------------------------------------------------------------- per-slot timesteps (continuous batching)
-// mi_denoise_slots is this call with member == frame == NULL: one body, so the same rules in the same order and the same launches
-extern "C" int mi_denoise_slots_virtual(mi_plan* plan, const float* cond, float* x, int B, int H, int W,
-                                        const int32_t* t_rows, int n_rows, const int32_t* iter_base, const int64_t* sample_index,
-                                        const int64_t* member, const uint32_t* frame,
-                                        const float* beta, const float* alpha, const float* alpha_hat, int noise_steps,
-                                        const float* step_noise, int seeded, uint64_t seed, int flags,
-                                        void* workspace, size_t workspace_bytes, void* stream) {
+// The rule's own column rules (mi_denoise_slots_rule), after the table's entries have been judged: per column, the sequence
+// (t_before, the active rows, t_after) is a piece of a DDIM list -- strictly decreasing, every step within check_ddim's alpha_hat rule
+static int check_rule_columns(const int32_t* t_rows, int n_rows, int B, const int32_t* t_before, const int32_t* t_after,
+                              const float* alpha_hat, int noise_steps) {
+    for (int b = 0; b < B; ++b) {
+        const int tb = t_before ? t_before[b] : -1, ta = t_after ? t_after[b] : -1;
+        if (tb < -1 || tb >= noise_steps) return fail(MI_EINVAL, "t_before[%d]=%d outside [-1,%d) (-1 = none)", b, tb, noise_steps);
+        if (ta < -1 || ta >= noise_steps) return fail(MI_EINVAL, "t_after[%d]=%d outside [-1,%d) (-1 = none)", b, ta, noise_steps);
+        int prev = tb, rows = 0;
+        for (int i = 0; i < n_rows; ++i) {
+            const int t = t_rows[(size_t)i * B + b];
+            if (t < 0) break;                                // (active on a prefix of the rows: judged before)
+            if (prev >= 0 && t >= prev)
+                return fail(MI_EINVAL, "t_rows[%d][%d]=%d after %s=%d: the update jumps from each timestep of a slot to its next one "
+                            "(limit: a strictly decreasing column, t_before and t_after included)", i, b, t, i ? "the row above" : "t_before", prev);
+            if (prev >= 0)
+                if (int rc = check_ddim_pair(prev, t, alpha_hat)) return rc;
+            prev = t; ++rows;
+        }
+        if (ta >= 0 && rows < n_rows)
+            return fail(MI_EINVAL, "t_after[%d]=%d: slot %d went idle inside the call, its list has ended (limit: t_after = -1 after an idle row)", b, ta, b);
+        if (ta >= 0 && prev >= 0 && ta >= prev)
+            return fail(MI_EINVAL, "t_after[%d]=%d after t_rows[%d][%d]=%d: the update jumps from each timestep of a slot to its next one "
+                        "(limit: a strictly decreasing column, t_before and t_after included)", b, ta, n_rows - 1, b, prev);
+        if (rows > 0)
+            if (int rc = check_ddim_pair(prev, ta, alpha_hat)) return rc;
+    }
+    return MI_OK;
+}
+
+// The three slot calls in one body, so the same rules in the same order and the same launches.  rule == null: the reference's
+// update (t_before, t_after and x0_hist are null); else a judged MI_UPDATE_DDIM / MI_UPDATE_DPMPP2M rule of mi_denoise_slots_rule
+static int slots_run(mi_plan* plan, const float* cond, float* x, int B, int H, int W,
+                     const int32_t* t_rows, int n_rows, const int32_t* iter_base, const int64_t* sample_index,
+                     const int64_t* member, const uint32_t* frame, const int32_t* t_before, const int32_t* t_after, float* x0_hist,
+                     const float* beta, const float* alpha, const float* alpha_hat, int noise_steps,
+                     const float* step_noise, int seeded, uint64_t seed, int flags, const mi_update_rule* rule,
+                     void* workspace, size_t workspace_bytes, void* stream) {
     if (!plan) return fail(MI_EINVAL, "null plan");
     if (!cond || !x || !beta || !alpha || !alpha_hat || (n_rows > 0 && !t_rows)) return fail(MI_EINVAL, "null argument");
     if (n_rows < 0) return fail(MI_EINVAL, "n_rows %d is negative (limit: n_rows >= 0)", n_rows);
@@ -409,9 +514,12 @@ extern "C" int mi_denoise_slots_virtual(mi_plan* plan, const float* cond, float*
             return fail(MI_EINVAL, "frame[%d]: C*plane = %d*%llu reaches 2^32: the element index of the seeded step noise is one 32-bit "
                         "counter word (limit: C*plane < 4294967296)", b, plan->cfg.in_channels, (unsigned long long)plane);
     }
+    if (rule)
+        if (int rc = check_rule_columns(t_rows, n_rows, B, t_before, t_after, alpha_hat, noise_steps)) return rc;
     const size_t batch_bytes = (size_t)B * plan->cfg.in_channels * H * W * sizeof(float);
-    const Buf buf[2] = {{x, batch_bytes, "x"}, {cond, batch_bytes, "cond"}};
+    const Buf buf[3] = {{x, batch_bytes, "x"}, {cond, batch_bytes, "cond"}, {x0_hist, batch_bytes, "x0_hist"}};
     if (int rc = check_no_overlap(buf, 2, "the condition images are read by every row while x is updated in place")) return rc;
+    if (int rc = check_no_overlap(buf, 3, "x0_hist is read and written beside x by every row")) return rc;
     if (int rc = check_finalized(plan)) return rc;
     if (noise_steps > plan->time_rows)
         return fail(MI_EINVAL, "noise_steps %d exceeds the precomputed time table (%d rows)", noise_steps, plan->time_rows);
@@ -420,11 +528,54 @@ extern "C" int mi_denoise_slots_virtual(mi_plan* plan, const float* cond, float*
     if (n_rows == 0) return MI_OK;
     StepNoise sn;
     sn.tensor = step_noise; sn.seeded = seeded != 0; sn.seed = seed;
-    const SlotRows slots{iter_base, sample_index, member, frame};
+    const SlotRows slots{iter_base, sample_index, member, frame, t_before, t_after};
+    Schedule sc{t_rows, n_rows, beta, alpha, alpha_hat, noise_steps};
+    if (rule) { sc.rule = rule->kind; sc.eta = rule->kind == MI_UPDATE_DDIM ? rule->eta : 0.0; sc.clip_x0 = rule->clip_x0 ? 1 : 0; sc.x0 = x0_hist; }
     std::lock_guard<std::mutex> side_lk(plan->side_mu);
     HIPCHK(hipMemsetAsync(workspace, 0, 256, (hipStream_t)stream));      // status word: once per call
-    return enqueue_run(plan, g, cond, x, B, H, W, Schedule{t_rows, n_rows, beta, alpha, alpha_hat, noise_steps}, &slots, sn, flags,
-                       workspace, workspace_bytes, stream);
+    return enqueue_run(plan, g, cond, x, B, H, W, sc, &slots, sn, flags, workspace, workspace_bytes, stream);
+}
+
+// mi_denoise_slots is this call with member == frame == NULL
+extern "C" int mi_denoise_slots_virtual(mi_plan* plan, const float* cond, float* x, int B, int H, int W,
+                                        const int32_t* t_rows, int n_rows, const int32_t* iter_base, const int64_t* sample_index,
+                                        const int64_t* member, const uint32_t* frame,
+                                        const float* beta, const float* alpha, const float* alpha_hat, int noise_steps,
+                                        const float* step_noise, int seeded, uint64_t seed, int flags,
+                                        void* workspace, size_t workspace_bytes, void* stream) {
+    return slots_run(plan, cond, x, B, H, W, t_rows, n_rows, iter_base, sample_index, member, frame, nullptr, nullptr, nullptr,
+                     beta, alpha, alpha_hat, noise_steps, step_noise, seeded, seed, flags, nullptr, workspace, workspace_bytes, stream);
+}
+
+// The per-slot call under an update rule (include/midd.h).  What the rule itself refuses is judged first, before the table, the
+// plan's state and any GPU work, as in the other *_rule calls
+extern "C" int mi_denoise_slots_rule(mi_plan* plan, const float* cond, float* x, int B, int H, int W,
+                                     const int32_t* t_rows, int n_rows, const int32_t* iter_base, const int64_t* sample_index,
+                                     const int64_t* member, const uint32_t* frame,
+                                     const int32_t* t_before, const int32_t* t_after, float* x0_hist,
+                                     const float* beta, const float* alpha, const float* alpha_hat, int noise_steps,
+                                     const float* step_noise, int seeded, uint64_t seed, int flags,
+                                     const mi_update_rule* rule, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!rule || rule->kind == MI_UPDATE_REFERENCE) {
+        if (t_before || t_after || x0_hist)
+            return fail(MI_EINVAL, "%s with the reference's update: t_before, t_after and x0_hist belong to MI_UPDATE_DDIM / MI_UPDATE_DPMPP2M "
+                        "(limit: all three NULL under MI_UPDATE_REFERENCE)", t_before ? "t_before" : t_after ? "t_after" : "x0_hist");
+        return slots_run(plan, cond, x, B, H, W, t_rows, n_rows, iter_base, sample_index, member, frame, nullptr, nullptr, nullptr,
+                         beta, alpha, alpha_hat, noise_steps, step_noise, seeded, seed, flags, nullptr, workspace, workspace_bytes, stream);
+    }
+    if (rule->kind == MI_UPDATE_DDIM) {
+        if (!(rule->eta >= 0.0 && rule->eta <= 1.0)) return fail(MI_EINVAL, "eta %.17g outside [0, 1] (limit: 0 <= eta <= 1, not NaN)", rule->eta);
+        if (x0_hist) return fail(MI_EINVAL, "x0_hist with MI_UPDATE_DDIM: the rule keeps no predicted image (limit: x0_hist NULL; MI_UPDATE_DPMPP2M takes it)");
+    } else if (rule->kind == MI_UPDATE_DPMPP2M) {
+        if (!x0_hist) return fail(MI_EINVAL, "MI_UPDATE_DPMPP2M without x0_hist: the rule reads every slot's previous predicted image (limit: x0_hist [B,C,H,W] on the device)");
+        if (seeded || step_noise)
+            return fail(MI_EINVAL, "%s with MI_UPDATE_DPMPP2M: the rule is deterministic, it has no noise term (limit: seeded == 0, step_noise NULL)",
+                        seeded ? "seeded" : "step_noise");
+    } else {
+        return fail(MI_EINVAL, "unknown update rule %d (MI_UPDATE_REFERENCE, MI_UPDATE_DDIM or MI_UPDATE_DPMPP2M)", (int)rule->kind);
+    }
+    return slots_run(plan, cond, x, B, H, W, t_rows, n_rows, iter_base, sample_index, member, frame, t_before, t_after, x0_hist,
+                     beta, alpha, alpha_hat, noise_steps, step_noise, seeded, seed, flags, rule, workspace, workspace_bytes, stream);
 }
 
 extern "C" int mi_denoise_slots(mi_plan* plan, const float* cond, float* x, int B, int H, int W,

@@ -8,6 +8,8 @@
 //   out_conv_dpm_kernel    : the same with the second-order multistep update (DPM-Solver++(2M), bounded weight); writes x0
 //   out_conv_slots_kernel  : the same with every sample at its own timestep: coefficients, counter words and the active
 //                      flag from the sample's SlotRec (mi_denoise_slots); slot_fill_kernel writes a row's records
+//   out_conv_slots_rule_kernel : the per-slot form of the DDIM(eta) and multistep updates: the coefficient row, the counter words
+//                      and the flags from the sample's SlotRuleRec (mi_denoise_slots_rule)
 //   step_noise_fill_kernel : the same noise values as a [n_iters,B,C,H,W] tensor (replay / export)
 // N = 1 is a degenerate GEMM shape: it stays on the vector ALU and is judged against the HBM roofline.
 #include "midd_internal.h"
@@ -34,6 +36,7 @@ __device__ __forceinline__ float silu_pw(float v) {
 #define MIDD_OUT_SLOTS 0
 #define MIDD_OUT_DDIM 0
 #define MIDD_OUT_DPM 0
+#define MIDD_OUT_SLOTS_RULE 0
 #define MIDD_OUT_KERNEL out_conv_kernel
 #define MIDD_OUT_SEEDED 0
 #include "out_conv_body.h"
@@ -82,6 +85,21 @@ __device__ __forceinline__ float silu_pw(float v) {
 #undef MIDD_OUT_SLOTS
 #undef MIDD_OUT_DDIM
 #undef MIDD_OUT_DPM
+#undef MIDD_OUT_SLOTS_RULE
+// the per-slot DDIM(eta) / multistep update (mi_denoise_slots_rule): every per-sample scalar from the sample's SlotRuleRec
+#define MIDD_OUT_SLOTS 0
+#define MIDD_OUT_DDIM 0
+#define MIDD_OUT_DPM 0
+#define MIDD_OUT_SLOTS_RULE 1
+#define MIDD_OUT_KERNEL out_conv_slots_rule_kernel
+#define MIDD_OUT_SEEDED 0
+#include "out_conv_body.h"
+#undef MIDD_OUT_KERNEL
+#undef MIDD_OUT_SEEDED
+#undef MIDD_OUT_SLOTS
+#undef MIDD_OUT_DDIM
+#undef MIDD_OUT_DPM
+#undef MIDD_OUT_SLOTS_RULE
 
 // What every out_conv launch refuses, and what it launches with: the dynamic LDS of (ic, C) and the 16x16 tiles of a sample
 static bool out_conv_shape_ok(const OutConvArgs& a, size_t* lds, int* tiles) {
@@ -146,12 +164,24 @@ static hipError_t launch_dpm(const OutConvArgs& a, const DpmCoef& k, const float
     MIDD_OUT_LAUNCH(out_conv_dpm_kernel, a, a.w, k, x0_prev, x0_out);
     return hipGetLastError();
 }
+
+// The records' flags decide what a slot reads: x0_hist is null under the DDIM rule (no record has SLOT_HIST: the host), and the
+// multistep rule has no noise term
+static hipError_t launch_slots_rule(const OutConvArgs& a, const SlotRuleStep& u, hipStream_t s) {
+    size_t lds; int tiles;
+    if (!out_conv_shape_ok(a, &lds, &tiles) || !u.recs || !a.x) return hipErrorInvalidValue;
+    if (a.seeded && (a.noise || (unsigned long long)a.ic * a.H * a.W >= (1ull << 32))) return hipErrorInvalidValue;
+    if (u.x0_hist && (a.seeded || a.noise)) return hipErrorInvalidValue;
+    MIDD_OUT_LAUNCH(out_conv_slots_rule_kernel, a, a.w, u.recs, u.clip_x0, u.x0_hist);
+    return hipGetLastError();
+}
 #undef MIDD_OUT_LAUNCH
 
 // The one launcher (midd_internal.h: OutUpdate) and, beside it, the symbol it launches: one switch each over the same kinds
 hipError_t out_conv_launch(const OutConvArgs& a, const OutUpdate& u, hipStream_t s) {
     switch (u.kind) {
         case OUT_SLOTS: return launch_slots(a, u.slots, s);
+        case OUT_SLOTS_RULE: return launch_slots_rule(a, u.slots_rule, s);
         case OUT_DDIM: return launch_ddim(a, u.ddim, s);
         case OUT_DPM: return launch_dpm(a, u.dpm.k, u.dpm.x0_prev, u.dpm.x0_out, s);
         case OUT_REFERENCE: {
@@ -167,6 +197,7 @@ hipError_t out_conv_launch(const OutConvArgs& a, const OutUpdate& u, hipStream_t
 const char* out_conv_symbol(const OutUpdate& u, int seeded) {
     switch (u.kind) {
         case OUT_SLOTS: return "out_conv_slots_kernel";
+        case OUT_SLOTS_RULE: return "out_conv_slots_rule_kernel";
         case OUT_DDIM: return seeded ? "out_conv_ddim_seeded_kernel" : "out_conv_ddim_kernel";
         case OUT_DPM: return "out_conv_dpm_kernel";
         case OUT_REFERENCE: case OUT_FORWARD: break;
@@ -184,6 +215,17 @@ __global__ void slot_fill_kernel(int* trow, SlotRec* dst, SlotRecs recs, int n) 
 hipError_t slot_fill_launch(int* trow, SlotRec* dst, const SlotRecs& recs, int n, hipStream_t s) {
     if (n < 1 || n > SLOTS_PER_LAUNCH) return hipErrorInvalidValue;
     hipLaunchKernelGGL(slot_fill_kernel, dim3(1), dim3(SLOTS_PER_LAUNCH), 0, s, trow, dst, recs, n);
+    return hipGetLastError();
+}
+
+// the same for a row of mi_denoise_slots_rule: SlotRuleRec, 64 bytes a slot
+__global__ void slot_rule_fill_kernel(int* trow, SlotRuleRec* dst, SlotRuleRecs recs, int n) {
+    if ((int)threadIdx.x < n) { trow[threadIdx.x] = recs.v[threadIdx.x].trow; dst[threadIdx.x] = recs.v[threadIdx.x]; }
+}
+
+hipError_t slot_rule_fill_launch(int* trow, SlotRuleRec* dst, const SlotRuleRecs& recs, int n, hipStream_t s) {
+    if (n < 1 || n > SLOTS_PER_LAUNCH) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(slot_rule_fill_kernel, dim3(1), dim3(SLOTS_PER_LAUNCH), 0, s, trow, dst, recs, n);
     return hipGetLastError();
 }
 

@@ -17,6 +17,9 @@
 // A sixth, MIDD_OUT_DPM 1 = out_conv_dpm_kernel: the second-order multistep update of include/midd.h (THE DPMPP2M UPDATE) -- the
 // DDIM update at eta = 0 plus g * (x0 - x0_prev) -- its coefficients in a DpmCoef argument (scalar loads) and two more pointers,
 // the previous iteration's predicted image (read) and this one's (written).  The five compiles above do not see a token of it.
+// A seventh, MIDD_OUT_SLOTS_RULE 1 = out_conv_slots_rule_kernel (mi_denoise_slots_rule): the DDIM / DPMPP2M blocks below with every
+// per-sample scalar from the sample's SlotRuleRec (midd_internal.h), the draw of the slots compile, and one history pointer, null
+// under the DDIM rule, read and written in place.  One compile for both rules.  The six compiles above do not see a token of it.
 template <int IC>
 __global__ __launch_bounds__(256)
 void MIDD_OUT_KERNEL(const OutConvArgs a, const float* __restrict__ wglob /* == a.w: a restrict parameter of its own, so that uniform reads become scalar loads */
@@ -28,6 +31,9 @@ void MIDD_OUT_KERNEL(const OutConvArgs a, const float* __restrict__ wglob /* == 
 #endif
 #if MIDD_OUT_DPM
                      , const DpmCoef k, const float* x0_prev, float* x0_out /* [a.B, ic, H, W]; may be one address: not restrict */
+#endif
+#if MIDD_OUT_SLOTS_RULE
+                     , const SlotRuleRec* __restrict__ slots /* [a.B] */, const int clip_x0, float* x0_hist /* [a.B, ic, H, W] or null; read and written: not restrict */
 #endif
                      ) {
     __shared__ __attribute__((aligned(16))) float tile[OC_I * OC_I * OC_PS];
@@ -50,6 +56,10 @@ void MIDD_OUT_KERNEL(const OutConvArgs a, const float* __restrict__ wglob /* == 
 #if MIDD_OUT_SLOTS
     const SlotRec rec = slots[b];
     if (!rec.active) return;                      // idle slot: x[b] keeps its bits (whole workgroup, before any barrier)
+#endif
+#if MIDD_OUT_SLOTS_RULE
+    const SlotRuleRec rec = slots[b];
+    if (!rec.active) return;                      // idle slot: x[b] and x0_hist[b] keep their bits (whole workgroup, before any barrier)
 #endif
     if constexpr (IC == 0) for (int i = tid; i < ic * 9 * C; i += 256) wl[i] = a.w[i];     // (IC > 0 reads the weights through scalar loads)
 
@@ -214,6 +224,36 @@ void MIDD_OUT_KERNEL(const OutConvArgs a, const float* __restrict__ wglob /* == 
                                                                      //  thread's own element, read before it is written below)
             if (k.last) xn = fminf(fmaxf(xn, 0.0f), 1.0f);      // the call returns an image in [0, 1]; intermediate x is not clamped
             x0_out[o] = x0;
+            a.x[o] = xn;
+        }
+#elif MIDD_OUT_SLOTS_RULE
+        if (a.x) {
+            // THE DDIM UPDATE / THE DPMPP2M UPDATE (include/midd.h) of the two blocks above, word for word, every scalar from the slot's
+            // record: fp32, every operation rounded on its own.  A uniform table must give mi_denoise_rule's / mi_denoise_dpm's bits
+            // (tests/test_gpu_slots_rule.py).
+#pragma clang fp contract(off)
+            if (a.clamp_eps) eps = fminf(fmaxf(eps, -5.0f), 5.0f);
+            const float x = a.x[o];
+            float x0 = rec.k0 * (x - rec.k1 * eps);
+            if (clip_x0) {
+                const float c = fminf(fmaxf(x0, 0.0f), 1.0f);
+                if (c != x0) eps = (x - rec.r0 * c) * rec.r1;  // eps re-derived: x_prev stays on the trajectory towards the clipped image
+                x0 = c;
+            }
+            float xn = rec.a * x0 + rec.b * eps;
+            if (rec.s > 0.0f && (rec.active & SLOT_NOISE)) {   // (uniform in the workgroup: nothing is drawn or read otherwise)
+                if (a.seeded) {
+                    // the draw of out_conv_slots_kernel above: the record's frame, member word, image and iteration
+                    const uint32_t elem = (uint32_t)oc * rec.plane + (uint32_t)oy * rec.pitch + (uint32_t)ox + rec.origin;
+                    xn = xn + rec.s * step_noise_value(a.seed, (long long)rec.image, (int)rec.iter, elem, rec.member);
+                } else if (a.noise) {
+                    xn = xn + rec.s * a.noise[o];
+                }
+            }
+            if (rec.active & SLOT_HIST) xn = xn + rec.g * (x0 - x0_hist[o]);      // (g != 0; this thread's own element, read before it is
+                                                                                  //  written below)
+            if (rec.active & SLOT_LAST) xn = fminf(fmaxf(xn, 0.0f), 1.0f);        // the slot's list ends: an image in [0, 1]
+            if (x0_hist) x0_hist[o] = x0;
             a.x[o] = xn;
         }
 #else

@@ -359,8 +359,45 @@ class UNetDiffusion(nn.Module):
         ``member`` [B] and ``frame`` [B][3] = (pitch, plane, origin) make a slot a virtual sample (mi_denoise_slots_virtual): the
         member word of its noise and the frame of its element index, what a member of run_ensemble and a tile of run_tiled
         draw.  Both need ``seed``; with both None the call is mi_denoise_slots."""
-        from .sampler import check_seed, refuse_update
+        from .sampler import refuse_update
         refuse_update(update, "run_slots (mi_denoise_slots)")
+        return self._run_slots(cond, x, t_rows, beta, alpha, alpha_hat, clamp_eps, iter_base, sample_index, step_noise, seed, no_split,
+                               max_slots, member, frame, None)
+
+    @torch.no_grad()
+    def run_slots_rule(self, cond: torch.Tensor, x: torch.Tensor, t_rows, beta: torch.Tensor, alpha: torch.Tensor, alpha_hat: torch.Tensor,
+                       clamp_eps: bool, iter_base=None, sample_index=None, step_noise: Optional[torch.Tensor] = None,
+                       seed: Optional[int] = None, no_split: bool = False, max_slots: Optional[int] = None, *,
+                       rule=None, t_before=None, t_after=None, x0: Optional[torch.Tensor] = None, member=None, frame=None) -> torch.Tensor:
+        """``run_slots`` under an update rule (mi_denoise_slots_rule): every slot runs ``rule`` -- a ``SamplerRule`` -- at its own
+        place in its own list.  A row's coefficients depend on the slot's NEXT timestep and, under "dpmpp2m", on its PREVIOUS one:
+        inside the call they are the rows below and above, across the call's ends ``t_after`` [B] and ``t_before`` [B], -1 (or
+        None: all -1) = none.  -1 after a slot's last active row ends its list: that row returns an image in [0, 1].
+        ``x0`` [B,C,H,W] ("dpmpp2m" only, where it is required): every slot's previous predicted image, read and written in
+        place, not initialised; it travels with the slot as ``x`` does.  "dpmpp2m" is deterministic: ``seed``, ``step_noise``,
+        ``member`` and ``frame`` raise.  ``rule=None``: the reference's update through the same native entry -- ``run_slots``'
+        bits and launches -- with the three new arguments None."""
+        from .sampler import check_rule
+        rule = check_rule(rule)
+        dpm = rule is not None and rule.update == "dpmpp2m"
+        if dpm and (seed is not None or step_noise is not None or member is not None or frame is not None):
+            raise ValueError("rule 'dpmpp2m' is deterministic: it takes no seed, step_noise, member or frame")
+        if dpm != (x0 is not None):
+            raise ValueError("x0 is the history of rule 'dpmpp2m': that rule needs it, no other rule takes it")
+        if rule is None and (t_before is not None or t_after is not None):
+            raise ValueError("t_before and t_after belong to a rule: the reference's update (rule=None) has no neighbours")
+        if x0 is not None:
+            if not isinstance(x0, torch.Tensor) or x0.shape != x.shape or x0.device != x.device or not x0.is_contiguous():
+                raise ValueError("x0 must match x in shape and device and be contiguous (it is updated in place)")
+            self._check_image(x0, "x0")
+        return self._run_slots(cond, x, t_rows, beta, alpha, alpha_hat, clamp_eps, iter_base, sample_index, step_noise, seed, no_split,
+                               max_slots, member, frame, (rule, t_before, t_after, x0))
+
+    def _run_slots(self, cond, x, t_rows, beta, alpha, alpha_hat, clamp_eps, iter_base, sample_index, step_noise, seed, no_split,
+                   max_slots, member, frame, ruled) -> torch.Tensor:
+        """The per-slot native calls: ``ruled`` None is mi_denoise_slots / mi_denoise_slots_virtual, else (rule, t_before, t_after,
+        x0) of mi_denoise_slots_rule, which always takes the two virtual tables (None: NULL)."""
+        from .sampler import check_seed
         if seed is not None:
             if step_noise is not None:
                 raise ValueError("pass either seed or step_noise, not both")
@@ -395,17 +432,30 @@ class UNetDiffusion(nn.Module):
                 fr = np.ascontiguousarray(fr.astype(np.uint32))
             virtual = (None if mb is None else mb.ctypes.data_as(C.POINTER(C.c_int64)),
                        None if fr is None else fr.ctypes.data_as(C.POINTER(C.c_uint32)))
+        fn, tail = native.lib().mi_denoise_slots_virtual if virtual else native.lib().mi_denoise_slots, ()
+        if ruled is not None:
+            rule, t_before, t_after, x0 = ruled
+            nb = []
+            for v, what in ((t_before, "t_before"), (t_after, "t_after")):
+                v = None if v is None else np.asarray(v, dtype=np.int64)
+                if v is not None and (v.shape != (B,) or (v.size and (v.min() < -1 or v.max() >= 1 << 31))):
+                    raise ValueError(f"{what} must have one timestep per slot ({B}), -1 = none")
+                nb.append(None if v is None else np.ascontiguousarray(v.astype(np.int32)))
+            native_rule = None if rule is None else rule.native()
+            fn = native.lib().mi_denoise_slots_rule
+            virtual = (virtual or (None, None)) + tuple(None if v is None else v.ctypes.data_as(C.POINTER(C.c_int32)) for v in nb) + (_ptr(x0),)
+            tail = (None if native_rule is None else C.byref(native_rule),)
         keep, tables = self._table_args(beta, alpha, alpha_hat)
         dev = cond.device
         with self._lock, torch.cuda.device(dev):
             plan = self._ensure_plan(time_rows=tables[-1])
             step_noise = self._step_noise(step_noise, n_rows, cond, "n_rows")
             ws = self._workspace(B, H, W, dev) if not max_slots else self._slots_workspace(max(int(max_slots), B), H, W, dev)
-            self._invoke(native.lib().mi_denoise_slots_virtual if virtual else native.lib().mi_denoise_slots,
+            self._invoke(fn,
                          (plan, cond.data_ptr(), x.data_ptr(), B, H, W, rows.ctypes.data_as(C.POINTER(C.c_int32)), n_rows,
                           None if ib is None else ib.ctypes.data_as(C.POINTER(C.c_int32)),
                           None if si is None else si.ctypes.data_as(C.POINTER(C.c_int64))) + virtual + tables
-                         + (_ptr(step_noise), 0 if seed is None else 1, C.c_uint64(seed or 0), self._call_flags(clamp_eps, no_split)), ws, dev)
+                         + (_ptr(step_noise), 0 if seed is None else 1, C.c_uint64(seed or 0), self._call_flags(clamp_eps, no_split)) + tail, ws, dev)
         return x
 
     def _slots_workspace(self, max_slots: int, H: int, W: int, dev: torch.device) -> torch.Tensor:

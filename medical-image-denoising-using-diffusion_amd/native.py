@@ -128,6 +128,13 @@ SYMBOLS = [
     ("mi_denoise_tiled_dpm", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 7 +
                                       [C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int,
                                        C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
+    ("mi_update_row", C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_float), C.c_int, C.c_double, C.POINTER(C.c_float)]),
+    ("mi_denoise_slots_rule", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                        C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int64),
+                                        C.POINTER(C.c_int64), C.POINTER(C.c_uint32),
+                                        C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p,
+                                        C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int,
+                                        C.c_void_p, C.c_int, C.c_uint64, C.c_int, C.POINTER(UpdateRule), C.c_void_p, C.c_size_t, C.c_void_p]),
     ("mi_debug_fetch", C.c_int, [C.c_void_p, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                  C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p]),
     ("mi_status", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]),

@@ -9,6 +9,7 @@ call into libmidd.so.
 from __future__ import annotations
 
 import ctypes as C
+import dataclasses
 import numbers
 import operator
 from typing import NamedTuple, Optional, Sequence, Tuple
@@ -78,15 +79,52 @@ def check_update(update="reference", eta=0.0, clip_x0=True):
 
 
 def refuse_update(update, what: str) -> None:
-    """The calls the DDIM and DPMPP2M updates are not built for (include/midd.h: NOT BUILT) take ``update`` to say so."""
+    """The calls the DDIM and DPMPP2M updates are not built for (include/midd.h: NOT BUILT) take ``update`` to say so.  The
+    per-slot calls run the rules under another spelling, ``rule=SamplerRule(...)``, which the message names."""
     if update not in UPDATE_RULES:
         raise ValueError(f"update must be 'reference', 'ddim' or 'dpmpp2m' (got {update!r})")
+    slots = "for the per-slot calls pass rule=SamplerRule(...) instead: run_slots_rule, denoise_ragged(rule=), SamplerSession(rule=), " \
+            "DiffusionService(slot_update=)"
     if update == "dpmpp2m":
         raise ValueError(f"{what} runs the reference's update only: update='dpmpp2m' is built for denoise and denoise_tiled "
-                         "(the per-slot record carries neither the rule nor a history of predicted images)")
+                         f"({slots}; ensembles have nothing to draw under it)")
     if update != "reference":
         raise ValueError(f"{what} runs the reference's update only: update='ddim' is built for denoise, denoise_ensemble and "
-                         "denoise_tiled (the per-slot record and the other two batched calls do not carry the rule yet)")
+                         f"denoise_tiled ({slots}; the tiled and the self ensemble do not carry the rule yet)")
+
+
+@dataclasses.dataclass(frozen=True)
+class SamplerRule:
+    """The update rule of the per-slot calls (include/midd.h: mi_denoise_slots_rule) -- ``run_slots_rule``, ``denoise_ragged(rule=)``,
+    ``SamplerSession(rule=)`` -- as one value: ``update`` "ddim" or "dpmpp2m", ``eta`` and ``clip_x0`` as in ``denoise``.  Judged by
+    ``check_update`` when it is made; the reference's update is ``rule=None``, not a SamplerRule."""
+    update: str = "ddim"
+    eta: float = 0.0
+    clip_x0: bool = True
+
+    def __post_init__(self):
+        if check_update(self.update, self.eta, self.clip_x0) is None:
+            raise ValueError("SamplerRule(update='reference'): the reference's update is rule=None")
+        object.__setattr__(self, "eta", float(self.eta))
+        object.__setattr__(self, "clip_x0", bool(self.clip_x0))
+
+    @property
+    def draws(self) -> bool:
+        """Whether the rule has a noise term at all: DDIM with eta > 0."""
+        return self.update == "ddim" and self.eta > 0.0
+
+    def native(self):
+        return check_update(self.update, self.eta, self.clip_x0)
+
+    def kwargs(self) -> dict:
+        """The keywords of ``denoise`` / ``denoise_tiled`` / ``denoise_ensemble`` that name the same rule."""
+        return dict(update=self.update, eta=self.eta, clip_x0=self.clip_x0)
+
+
+def check_rule(rule) -> Optional["SamplerRule"]:
+    if rule is not None and not isinstance(rule, SamplerRule):
+        raise ValueError(f"rule must be None (the reference's update) or a midd_amd.SamplerRule (got {rule!r})")
+    return rule
 
 
 def ddim_coefficients(t_list: Sequence[int], alpha_hat, eta: float = 0.0):
@@ -814,19 +852,25 @@ class DiffusionDenoiser:
 
     @torch.no_grad()
     def denoise_ragged(self, noisy_img: torch.Tensor, inference_steps: Sequence[int], seed: Optional[int] = None,
-                       sample_offset: int = 0, *, update: str = "reference") -> torch.Tensor:
+                       sample_offset: int = 0, *, update: str = "reference", rule: Optional[SamplerRule] = None) -> torch.Tensor:
         """Every image of the batch with its OWN step count, in one native call (mi_denoise_slots; not a reference call):
         image b is ``denoise(noisy_img[b:b+1], inference_steps[b], seed=seed, sample_offset=sample_offset + b)`` -- bit for bit
         with ``batch_invariant=True``, within the parity gate otherwise.  The loop runs max(iterations) rows; an image whose
         list has ended idles (its pixels are not touched again).  cddpm: always seeded; ``seed=None`` draws one as
-        ``denoise_ensemble`` does (the run then cannot be repeated: pass a seed to keep it).  DDIM ignores ``seed``."""
+        ``denoise_ensemble`` does (the run then cannot be repeated: pass a seed to keep it).  DDIM ignores ``seed``.
+
+        ``rule=SamplerRule(...)`` (mi_denoise_slots_rule): every image runs that update over its own list -- image b is
+        ``denoise(noisy_img[b:b+1], inference_steps[b], update=..., eta=..., clip_x0=..., seed=seed, sample_offset=sample_offset + b)``.
+        The rule decides whether anything is drawn, for both variants: seeded as above with ``eta > 0``, ``seed`` ignored at
+        ``eta == 0`` and under "dpmpp2m".  ``update=`` stays the refusal it was and names this spelling."""
         refuse_update(update, "denoise_ragged (mi_denoise_slots)")
+        rule = check_rule(rule)
         counts = list(inference_steps)
         if not isinstance(noisy_img, torch.Tensor) or noisy_img.dim() != 4 or len(counts) != noisy_img.shape[0]:
             raise ValueError(f"inference_steps must hold one step count per image ({len(counts)} for a batch of "
                              f"{noisy_img.shape[0] if isinstance(noisy_img, torch.Tensor) and noisy_img.dim() else '?'})")
         stochastic = getattr(self.model, "variant", "ddim") == "cddpm"
-        if stochastic:
+        if stochastic if rule is None else rule.draws:
             seed, sample_offset = check_seed(self._draw_seed() if seed is None else seed, sample_offset)
         else:
             seed = None
@@ -837,8 +881,13 @@ class DiffusionDenoiser:
         rows = [[t[i] if i < len(t) else -1 for t in lists] for i in range(n_rows)]
         cond = noisy_img.contiguous()
         x = cond.clone()
+        index = [sample_offset + b for b in range(len(counts))]
+        if rule is not None:      # (the whole lists are in the call: no neighbour lies outside it)
+            x0 = torch.empty_like(x) if rule.update == "dpmpp2m" else None
+            return self.model.run_slots_rule(cond, x, rows, self.beta, self.alpha, self.alpha_hat, clamp_eps=not stochastic,
+                                             sample_index=index, seed=seed, rule=rule, x0=x0)
         return self.model.run_slots(cond, x, rows, self.beta, self.alpha, self.alpha_hat, clamp_eps=not stochastic,
-                                    sample_index=[sample_offset + b for b in range(len(counts))], seed=seed)
+                                    sample_index=index, seed=seed)
 
     # north_star's wording for the same call
     ddim_sample = denoise

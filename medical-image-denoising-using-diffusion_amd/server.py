@@ -21,7 +21,11 @@ requests as the slots of ONE ``SamplerSession`` owned by one worker thread (cont
 batch-1 call per request.  0, the default, is the path above, unchanged.  ``DiffusionService(update="ddim", eta=F)`` (or
 ``MIDD_UPDATE`` / ``MIDD_ETA``) runs the served 9-of-50 list under the stride-aware DDIM(eta) update (include/midd.h: THE DDIM
 UPDATE); ``update="dpmpp2m"`` runs it under the second-order multistep update (THE DPMPP2M UPDATE; deterministic, no eta); the
-default, "reference", is the reference's update, unchanged.  Not together with batch_slots > 0.  ``/health`` reports ``update``.
+default, "reference", is the reference's update, unchanged.  ``/health`` reports ``update``.  With batch_slots > 0 the rule is spelled
+``DiffusionService(batch_slots=N, slot_update="ddim" | "dpmpp2m", slot_eta=F)`` (or ``MIDD_SLOT_UPDATE`` / ``MIDD_SLOT_ETA``): the
+session's slots run it (``SamplerSession(rule=SamplerRule(...))``; include/midd.h: mi_denoise_slots_rule), every request answered with
+the bytes the same rule gives without a session under ``batch_invariant=True``.  ``slot_update`` needs batch_slots > 0, ``update=`` with
+batch_slots > 0 stays refused and names it, and ``/health`` reports ``slot_update``.
 
 ``DiffusionService(bit_depth=16)`` (or ``MIDD_BIT_DEPTH=16``), not in the reference either, keeps a 16-bit upload's 65536 grey levels
 (image16.py; include/midd.h: THE FLOAT RESIZE): ``preprocess16`` / ``tensor_to_base64_16`` and their ``_device`` twins replace the
@@ -66,7 +70,7 @@ from PIL import Image
 
 from . import image16
 from .modules import UNetDiffusion
-from .sampler import DiffusionDenoiser, check_update, refuse_update
+from .sampler import DiffusionDenoiser, SamplerRule, check_update, refuse_update
 
 SERVE_SIZE = (512, 512)          # run.py:198
 SERVE_INFERENCE_STEPS = 8        # run.py:107 (-> 9 iterations with noise_steps=50)
@@ -228,7 +232,8 @@ class DiffusionService:
                  denoise_fn: Optional[Callable[[torch.Tensor], torch.Tensor]] = None, compute: Optional[str] = None,
                  batch_slots: Optional[int] = None, batch_invariant: Optional[bool] = None, session_factory=None,
                  update: Optional[str] = None, eta: Optional[float] = None, bit_depth: Optional[int] = None,
-                 window: Optional[Tuple[float, float]] = None, tile=None, overlap=None):
+                 window: Optional[Tuple[float, float]] = None, tile=None, overlap=None,
+                 slot_update: Optional[str] = None, slot_eta: Optional[float] = None):
         # 8: the reference's 8-bit pre/post-processing; 16: the 16-bit recipe (preprocess16 / tensor_to_base64_16).  None reads
         # MIDD_BIT_DEPTH, default 8
         self.bit_depth = image16.check_bit_depth(int(os.environ.get("MIDD_BIT_DEPTH", "8")) if bit_depth is None else bit_depth)
@@ -262,6 +267,14 @@ class DiffusionService:
             raise ValueError("batch_slots must be >= 0")
         if self.batch_slots > 0:
             refuse_update(self.update, "batch_slots > 0 (SamplerSession)")
+        # the update rule of the SESSION's slots (SamplerSession(rule=SamplerRule(...))): None reads MIDD_SLOT_UPDATE / MIDD_SLOT_ETA,
+        # default the reference's.  It is the spelling of update= / eta= for batch_slots > 0, and needs it
+        self.slot_update = os.environ.get("MIDD_SLOT_UPDATE", "reference") if slot_update is None else slot_update
+        self.slot_eta = float(os.environ.get("MIDD_SLOT_ETA", "0")) if slot_eta is None else float(slot_eta)
+        self.slot_rule = None if check_update(self.slot_update, self.slot_eta) is None else SamplerRule(self.slot_update, self.slot_eta)
+        if self.slot_rule is not None and self.batch_slots == 0:
+            raise ValueError(f"slot_update={self.slot_update!r} is the update rule of the session's slots: it needs batch_slots > 0 "
+                             "(without a session, update= and eta= select the rule)")
         self._session_factory = session_factory    # tests inject a stand-in: (service) -> an object with submit / step / pending / fail_pending
         self._session = None
         self._worker: Optional[threading.Thread] = None
@@ -320,7 +333,7 @@ class DiffusionService:
             return self._session_factory(self)
         from .session import SamplerSession
         H, W = SERVE_SIZE if self.tile is None else self.tile      # tiled: the slot is a tile, whatever the uploads' sizes
-        return SamplerSession(self.diffusion_denoiser, H, W, slots=self.batch_slots)
+        return SamplerSession(self.diffusion_denoiser, H, W, slots=self.batch_slots, rule=self.slot_rule)
 
     def _submit(self, input_tensor: torch.Tensor):
         with self._wake:
@@ -437,7 +450,7 @@ def create_app(service: Optional[DiffusionService] = None, checkpoint: Optional[
     @app.get("/health")
     async def health_check():
         return {"status": "healthy", "device": str(svc.device), "batch_slots": svc.batch_slots, "bit_depth": svc.bit_depth,
-                "update": svc.update,
+                "update": svc.update, "slot_update": svc.slot_update,
                 "tile": None if svc.tile is None else list(svc.tile), "overlap": None if svc.tile is None else list(svc.overlap),
                 "window": None if svc.window is None else list(svc.window),
                 "models_loaded": {"diffusion": svc.diffusion_model is not None or svc._denoise_fn is not None,

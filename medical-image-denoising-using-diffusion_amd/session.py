@@ -18,7 +18,8 @@ from typing import List, Optional, Tuple
 import torch
 
 from .config import timestep_list
-from .sampler import EnsembleResult, _integer, check_members, check_seed, ensemble_reduce, refuse_update, tile_blend, tile_plan
+from .sampler import (EnsembleResult, SamplerRule, _integer, check_members, check_rule, check_seed, ensemble_reduce, refuse_update,
+                      tile_blend, tile_plan)
 from . import native
 
 
@@ -83,21 +84,32 @@ class SamplerSession:
     ``submit_tiled`` and ``submit_ensemble`` queue tickets of several jobs; jobs wait in submission order, ticket by ticket, and
     take free slots from the head of the queue, so a ticket larger than the session occupies it for several calls.  The three
     device launches around the sampler -- ``extract``, ``blend``, ``reduce`` -- are attributes, as ``model.run_slots`` is.
+
+    ``rule=SamplerRule(...)`` (include/midd.h: mi_denoise_slots_rule): every ticket runs that update over its own list, through
+    ``model.run_slots_rule``; a ticket's result is the bits of ``denoise`` / ``denoise_tiled`` / ``denoise_ensemble`` with the rule's
+    ``update=, eta=, clip_x0=``.  A row of the rule depends on the slot's next and previous timesteps, so every call carries each
+    active slot's neighbours across the call's ends (``t_before``, ``t_after``) from its ticket's list and position; under
+    "dpmpp2m" the session owns a third buffer, the slots' previous predicted images, which moves with a slot on compaction (a
+    third device copy per hole) and is never initialised.  The rule decides what is drawn, for both variants: with ``eta > 0`` the
+    session is seeded as a cddpm session is, at ``eta == 0`` and under "dpmpp2m" it is deterministic -- a ``seed`` is accepted
+    and nothing is drawn, ``.seed`` is None, ``submit_ensemble`` raises.  ``update=`` stays the refusal it was.
     """
 
     def __init__(self, denoiser, H: int, W: int, slots: int = 8, seed: Optional[int] = None, max_rows: Optional[int] = None, *,
-                 update: str = "reference"):
-        refuse_update(update, "SamplerSession (mi_denoise_slots)")      # the per-slot record does not carry the DDIM rule
+                 update: str = "reference", rule: Optional[SamplerRule] = None):
+        refuse_update(update, "SamplerSession (mi_denoise_slots)")      # (the rules arrive as rule=SamplerRule(...))
+        self.rule = check_rule(rule)
         self.denoiser = denoiser
         self.model = denoiser.model
         self.H, self.W = _integer(H, "H", 1 << 31, 1), _integer(W, "W", 1 << 31, 1)
         self.slots = _integer(slots, "slots", 1 << 16, 1)
         self.max_rows = None if max_rows is None else _integer(max_rows, "max_rows", 1 << 31, 1)
-        self.stochastic = getattr(self.model, "variant", "ddim") == "cddpm"
+        self._clamp_eps = getattr(self.model, "variant", "ddim") != "cddpm"
+        self.stochastic = (not self._clamp_eps) if self.rule is None else self.rule.draws      # whether anything is drawn at all
         if self.stochastic:
             seed, _ = check_seed(denoiser._draw_seed() if seed is None else seed, 0)
         else:
-            seed = None                       # (DDIM has no noise term; denoise ignores a seed too)
+            seed = None                      # (no noise term: the DDIM variant, eta == 0, dpmpp2m; denoise ignores a seed too)
         self.seed = seed
         self.channels = int(self.model.cfg.in_channels)
         self.device = denoiser.beta.device
@@ -107,6 +119,7 @@ class SamplerSession:
         self._active: List[_Slot] = []        # slot i of the buffers, a contiguous prefix
         self._cond: Optional[torch.Tensor] = None
         self._x: Optional[torch.Tensor] = None
+        self._x0: Optional[torch.Tensor] = None      # rule "dpmpp2m": the slots' previous predicted images (never initialised)
         self._submitted = 0
         self._next_index = 0
         self._closed = False
@@ -184,8 +197,11 @@ class SamplerSession:
         """``members`` draws of one slot-shaped image as one ticket, one job per member, ascending.  ``result()`` is an
         ``EnsembleResult(mean, std, None, session.seed)``: with ``batch_invariant=True``, the mean and std of
         ``denoiser.denoise_ensemble(image, inference_steps, members, seed=session.seed, sample_offset=ticket.index,
-        member_offset=member_offset)`` bit for bit.  cddpm only."""
+        member_offset=member_offset)`` bit for bit.  cddpm only -- or, for either variant, a session under the DDIM rule with eta > 0."""
         if not self.stochastic:
+            if self.rule is not None:
+                raise ValueError(f"submit_ensemble under rule {self.rule.update!r}" + (" at eta == 0" if self.rule.update == "ddim" else "")
+                                 + ": a deterministic sampler has no ensemble")
             raise ValueError("submit_ensemble needs the stochastic (cddpm) variant: a deterministic sampler has no ensemble")
         members, member_offset, _ = check_members(members, member_offset, 1)
         want = (self.channels, self.H, self.W)
@@ -230,6 +246,8 @@ class SamplerSession:
                 shape = (self.slots, self.channels, self.H, self.W)
                 self._cond = torch.zeros(shape, dtype=torch.float32, device=self.device)      # (finite: idle rows of a direct
                 self._x = torch.zeros(shape, dtype=torch.float32, device=self.device)         # caller still run the network)
+                if self.rule is not None and self.rule.update == "dpmpp2m":
+                    self._x0 = torch.empty(shape, dtype=torch.float32, device=self.device)    # (a list's first row has g = 0)
             i = len(self._active)
             ticket._started = True
             self._active.extend(_Slot(ticket, j0 + d) for d in range(n))      # (in flight before anything below can fail)
@@ -272,9 +290,16 @@ class SamplerSession:
             whole = (self.W, self.H * self.W, 0)
             virtual = dict(member=[self._member(s) for s in self._active],
                            frame=[self._frame(s) if s.ticket.kind == "tiled" else whole for s in self._active])
-        self.model.run_slots(self._cond[:n], self._x[:n], rows, d.beta, d.alpha, d.alpha_hat, clamp_eps=not self.stochastic,
-                             iter_base=[s.pos for s in self._active], sample_index=[s.ticket.index for s in self._active],
-                             seed=self.seed, max_slots=self.slots, **virtual)
+        if self.rule is not None:
+            # every slot's neighbours across the call's ends, from its ticket's list and position (-1: none)
+            virtual.update(rule=self.rule, t_before=[s.ticket.t_list[s.pos - 1] if s.pos else -1 for s in self._active],
+                           t_after=[s.ticket.t_list[s.pos + k] if s.pos + k < len(s.ticket.t_list) else -1 for s in self._active])
+            if self._x0 is not None:
+                virtual["x0"] = self._x0[:n]
+        (self.model.run_slots if self.rule is None else self.model.run_slots_rule)(
+            self._cond[:n], self._x[:n], rows, d.beta, d.alpha, d.alpha_hat, clamp_eps=self._clamp_eps,
+            iter_base=[s.pos for s in self._active], sample_index=[s.ticket.index for s in self._active],
+            seed=self.seed, max_slots=self.slots, **virtual)
         finished = []                         # (slot, ticket, value or None while the ticket has jobs left)
         for i, s in enumerate(self._active):
             s.pos += k
@@ -286,6 +311,8 @@ class SamplerSession:
             if i != last:
                 self._cond[i].copy_(self._cond[last])
                 self._x[i].copy_(self._x[last])
+                if self._x0 is not None:
+                    self._x0[i].copy_(self._x0[last])
                 self._active[i] = self._active[last]
             self._active.pop()
         done = [(ticket, out) for _, ticket, out in finished if out is not None]
@@ -356,7 +383,7 @@ class SamplerSession:
         with self._qlock:
             self._closed = True
         self.fail_pending(RuntimeError("the session was closed"))
-        self._cond = self._x = None
+        self._cond = self._x = self._x0 = None
 
     def __enter__(self):
         return self
