@@ -440,6 +440,11 @@ int mi_tile_blend_quantiles(const float* tiles, int B, int members, int C, int H
  * clockwise, numpy.rot90(x, 1)) and the anti-transpose: they turn H x W into W x H and are accepted ONLY when H == W, because a
  * pass never mixes image sizes.  A view list is 1 to 8 DISTINCT codes in the caller's order; the order is the order of the
  * members (samples_out, and the order of the sums of the mean).
+ * THE GENERAL FORM of the transposing codes (t = 1), for any H x W plane -- used where a transposed image is acceptable, i.e. by
+ * the TILED self-ensemble below; the calls of this section keep the H == W rule.  view(x, g) is Wv x Hv = W x H with
+ *   view(x)[p][q] = x[fx ? H-1-q : q][fy ? W-1-p : p]
+ * and its inverse is  unview(v)[y][x] = v[p][q]  with  p = fy ? W-1-x : x,  q = fx ? H-1-y : y.
+ * For H == W == N this is the N x N form above (swap, then the reversals), entry for entry; the non-transposing codes are as above.
  *
  * mi_dihedral_views (no plan needed): dst device fp32 [n][C][Hv][Wv] <- view(images[v / n_views], views[v % n_views]) for the
  *   virtual samples v = v0 .. v0 + n - 1 of images [B][C][H][W] (image-major, v = b * n_views + k, as mi_denoise_ensemble numbers
@@ -631,6 +636,92 @@ int mi_denoise_tiled_dpm(mi_plan* plan, const float* noisy, float* image_out, fl
  * MI_EINVAL as mi_ddim_coefficients, applied to the triple: eta; a null argument; noise_steps < 1; t outside [0, noise_steps),
  * a neighbour outside [-1, noise_steps); a triple that is not strictly decreasing; alpha_hat outside the rule on either step. */
 int mi_update_row(int32_t t_before, int32_t t, int32_t t_after, const float* alpha_hat, int noise_steps, double eta, float out[8]);
+
+/* TILED SELF-ENSEMBLE: the flip / rotate views of images of ANY size >= the tile, at their own size -- the cell that was missing
+ * between mi_denoise_self_ensemble (one network-sized image) and mi_denoise_tiled_ensemble (seeded draws, tiled).  It is the
+ * ensemble a deterministic (DDIM) model has for a full-resolution image.
+ * A VIEW'S TILES ARE THE TILES OF THE VIEWED IMAGE.  View k of image b is the Hv x Wv image view(noisy[b], g_k) (THE GEOMETRY
+ * above, general form).  It is cut by THE GEOMETRY of tiled denoising in the view's OWN frame -- the tile counts and origins of
+ * mi_tile_geometry for (Hv, th, oy) and (Wv, tw, ox) -- and its tiles are numbered ky * nx_v + kx there.  This is NOT the view of
+ * every tile of the un-viewed image: the origin formula rounds down, so a mirrored image's tiles sit elsewhere whenever
+ * (L - T) % (n - 1) != 0 (L = 41, T = 16, O = 4: origins 0, 8, 16, 25, whose mirror is 0, 9, 17, 25).  The definition chosen makes
+ * every member the composition of two existing public calls (below).
+ * TRANSPOSING CODES (4 .. 7) are accepted iff th == tw and oy == ox: then the W x H frame has nx * ny tiles of the same shape, the
+ * tile count K = ny * nx is the same in both frames and the storage [n_views][B][K][C][th][tw] is rectangular.  H == W is NOT
+ * required: a transposed image is still cut into th x tw tiles.
+ *
+ * mi_tile_blend_unview_reduce (no plan needed): tiles device fp32 [n_views][B][K][C][th][tw], the tile outputs of every view in
+ *   that view's frame, in run order -> mean_out [B][C][H][W], std_out (or NULL; n_views >= 2) and samples_out
+ *   [B][n_views][C][H][W] (or NULL), the aligned blended members, all in the IMAGE's frame (H, W, th, tw, oy, ox: the un-viewed
+ *   image's).  One kernel.  THE ARITHMETIC (fixed, per output pixel (c, y, x), no atomics, no fused multiply-add, nothing depends
+ *   on the launch geometry) is the composition of two specifications above, bit for bit:
+ *     for k in list order:  v_k = the pixel (c, p_k, q_k) of mi_tile_blend over tiles[k][b] with the geometry (Hv, Wv, th, tw, oy,
+ *       ox) of view k's frame -- (p_k, q_k) = (y, x) mapped by the view (non-transposing: p = fy ? H-1-y : y, q = fx ? W-1-x : x;
+ *       transposing: p = fy ? W-1-x : x, q = fx ? H-1-y : y), the covering tiles walked in ascending (ky, kx) of THAT frame
+ *     (mean, std) = the arithmetic of mi_ensemble_reduce over v_0 .. v_{n_views-1}
+ *   so the outputs equal mi_tile_blend per view, unview, mi_ensemble_reduce, and are the same bits with and without samples_out.
+ * mi_tile_blend_unview_quantiles (no plan needed): the same gather, every v_k formed once, then THE ARITHMETIC of
+ *   mi_ensemble_quantiles over them: out [B][nq][C][H][W].  The aligned members never exist in memory.
+ * MI_EINVAL of the two, before any GPU work, in this order: the cases of mi_tile_blend (C < 1, the geometry rules, overlap > 46339,
+ *   B * tiles > 2^31 - 1, C*H*W >= 2^32); n_views outside [1, 8]; null views; a code outside [0, 7]; a repeated code; a transposing
+ *   code with th != tw or oy != ox; B outside [1, 65535]; B * n_views * tiles > 2^31 - 1; then per call -- reduce: no output pointer,
+ *   std_out with one view; quantiles: the level rules of mi_ensemble_quantiles -- and last a null data pointer.  tiles and the
+ *   outputs must not overlap. */
+int mi_tile_blend_unview_reduce(const float* tiles, int B, int C, int H, int W, int th, int tw, int oy, int ox,
+                                const int32_t* views, int n_views, float* mean_out, float* std_out, float* samples_out, void* stream);
+int mi_tile_blend_unview_quantiles(const float* tiles, int B, int C, int H, int W, int th, int tw, int oy, int ox,
+                                   const int32_t* views, int n_views, const double* q, int nq, float* out, void* stream);
+
+/* mi_denoise_tiled_ensemble with the views of an image in the place of its draws.  Views are the OUTER loop: round k makes
+ * view(noisy, g_k) of the whole batch (a copy in the workspace; the identity is read in place) and runs its B * K (image, tile)
+ * virtual samples exactly as mi_denoise_tiled runs them on that viewed batch -- extract (bit for bit the slices of the viewed
+ * image), then the sampler loop, in passes of at most pass_samples, each pass split over two streams as a mi_denoise batch of
+ * that size is (MI_NO_SPLIT honoured).  A pass never spans two views.  ONE mi_tile_blend_unview_reduce launch follows the last
+ * pass of the last view.
+ *   noisy        device fp32 [B,C,H,W]; never written
+ *   mean_out     device fp32 [B,C,H,W] or NULL
+ *   std_out      device fp32 [B,C,H,W] or NULL; needs n_views >= 2
+ *   samples_out  device fp32 [B,n_views,C,H,W] or NULL: the ALIGNED blended members
+ *   tiles_out    device fp32 [n_views,B,K,C,th,tw] or NULL: the denoised tiles in run order, view k's in ITS frame -- what
+ *                mi_tile_blend_unview_quantiles takes (NULL: they live in the workspace).  At least one of the four is given
+ *   views        HOST int32[n_views]
+ *   seeded       0: nothing is drawn.  != 0: view k draws the member word member_offset + k, with the counter word c0 the pixel's
+ *                index in the WHOLE VIEWED image (mi_denoise_tiled's rule in the view's frame, mi_denoise_self_ensemble's member rule)
+ *   rule         NULL or MI_UPDATE_REFERENCE: the reference's update.  MI_UPDATE_DDIM (any eta; with eta > 0 the term is drawn when
+ *                seeded != 0): as mi_denoise_tiled_rule.  MI_UPDATE_DPMPP2M: refused by name (the call takes no history buffer)
+ *   the rest     as mi_denoise_tiled_ensemble
+ * WHAT THE CALL IS, each statement bit for bit:
+ *   unseeded (DDIM, or any plan with seeded == 0): member k = unview(image_out of mi_denoise_tiled on view(noisy, g_k), g_k) at the
+ *     same pass_samples (under `rule`: of mi_denoise_tiled_rule);
+ *   seeded: member k = the single sample of mi_denoise_tiled_ensemble on view(noisy, g_k) with members = 1 and member_offset =
+ *     member_offset + k, turned back;
+ *   views = [0] at member_offset = 0 IS mi_denoise_tiled / mi_denoise_tiled_rule (mean_out = image_out, tiles_out = tiles_out);
+ *   with a batch-invariant plan every tile of every view is mi_denoise of its crop of view(x) -- with the crop of
+ *     mi_step_noise_fill_member for the viewed shape, image sample_offset + b, member member_offset + k, where seeded -- whatever
+ *     the pass size.
+ * MI_EINVAL before any GPU work, the rule named in mi_last_error, in this order: the update rule's own cases (MI_UPDATE_DPMPP2M by
+ * name, then those of mi_ddim_coefficients); null plan; n_views outside [1, 8]; null views; a code outside [0, 7]; a repeated code;
+ * a transposing code with th != tw or oy != ox; then everything mi_denoise_tiled_ensemble refuses with members = n_views, in its
+ * order; B > 65535; no output pointer; std_out with one view; any two of noisy, mean_out, std_out, samples_out, tiles_out
+ * overlapping.  Then, as every batched call: the plan's state, the workspace, null noisy, the schedule, the device.
+ * The status word (mi_status) is cleared once per call and accumulates over the passes of every view.  Allocates nothing;
+ * asynchronous.  NOT BUILT: a session ticket for this call, MI_UPDATE_DPMPP2M, and the rule for mi_denoise_tiled_ensemble /
+ * mi_denoise_self_ensemble, which keep the reference's update. */
+int mi_denoise_tiled_self_ensemble(mi_plan* plan, const float* noisy, float* mean_out, float* std_out, float* samples_out, float* tiles_out,
+                                   int B, int H, int W, int th, int tw, int oy, int ox, const int32_t* views, int n_views,
+                                   const int32_t* t_list, int n_iters,
+                                   const float* beta, const float* alpha, const float* alpha_hat, int noise_steps,
+                                   int seeded, uint64_t seed, int64_t sample_offset, int64_t member_offset, int pass_samples, int flags,
+                                   const mi_update_rule* rule, void* workspace, size_t workspace_bytes, void* stream);
+
+/* Bytes of workspace mi_denoise_tiled_self_ensemble needs, THE SUM OF: what mi_tiled_workspace_bytes answers for the same pass with
+ * tiles_external != 0 (the sampler workspace of a pass of tiles + the pass's condition tiles); the viewed copy of the batch of the
+ * round that runs, B * C*H*W * 4 bytes rounded up to a multiple of 256 (counted whatever the list, so the size depends on the
+ * NUMBER of views alone); and -- unless tiles_external != 0, i.e. tiles_out is given -- the tile outputs of every view,
+ * n_views * B * K * C*th*tw * 4 bytes, the LAST bytes of the workspace.  Host only, answered from the planner alone: it works
+ * before mi_unet_finalize too.  0 on bad arguments (mi_last_error says which). */
+size_t mi_tiled_self_ensemble_workspace_bytes(mi_plan* plan, int B, int n_views, int H, int W, int th, int tw, int oy, int ox,
+                                              int pass_samples, int tiles_external);
 
 /* CONTINUOUS BATCHING UNDER A RULE: mi_denoise_slots_virtual plus `rule`, every slot at its own place in its own list.
  * rule == NULL or kind MI_UPDATE_REFERENCE: mi_denoise_slots_virtual, bit for bit, the same launches; t_before, t_after and x0_hist

@@ -13,5 +13,7 @@ from .sampler import (DiffusionDenoiser, EnsembleQuantileResult, EnsembleResult,
                       SelfEnsembleResult, SamplerRule, dpm_coefficients,
                       TilePlan, TiledEnsembleQuantileResult, TiledEnsembleResult, TiledResult, ddim_coefficients, device, dihedral_quantiles,
                       dihedral_reduce, dihedral_views, ensemble_quantiles, ensemble_reduce, step_noise, tile_blend,
-                      tile_blend_quantiles, tile_blend_reduce, tile_extract, tile_plan, view_codes)
+                      tile_blend_quantiles, tile_blend_reduce, tile_extract, tile_plan, view_codes,
+                      TiledSelfEnsembleQuantileResult, TiledSelfEnsembleResult, tile_blend_unview_quantiles, tile_blend_unview_reduce,
+                      view_codes_tiled)
 from .session import SamplerSession, Ticket  # noqa: F401

@@ -7,7 +7,8 @@ img_size -> sampler -> uint8 -> bicubic resize back -> PNG, with the reference's
     python -m midd_amd.cli --image in.png --out out.png [--checkpoint ckpt.pth] [--variant cddpm|ddim]
                            [--img-size 512] [--inference-steps 25] [--seed N] [--samples K [--std-out std.npy]
                            [--quantiles 0.05,0.5,0.95 --quantiles-out q.npy]]
-                           [--tile N [--overlap O]]
+                           [--tile N [--overlap O] [--views [auto|flips|d4] | --members K] [--std-out std.npy]
+                            [--quantiles Q,Q --quantiles-out q.npy]]
                            [--self-ensemble [auto|flips|d4] [--std-out std.npy] [--quantiles Q,Q --quantiles-out q.npy]]
                            [--update reference|ddim|dpmpp2m [--eta F] [--no-clip-x0] [--x0-out traj.npy]]
                            [--bit-depth 8|16 [--window P_LO,P_HI | --window-levels LO,HI]]
@@ -40,7 +41,8 @@ def denoise_image_diffusion(model_path: Optional[str], test_image_path: str, dev
                             quantiles: Optional[Sequence[float]] = None, quantiles_out: Optional[str] = None,
                             self_ensemble: Optional[str] = None, update: str = "reference", eta: float = 0.0,
                             clip_x0: bool = True, x0_out: Optional[str] = None, bit_depth: int = 8, window: Optional[Sequence[float]] = None,
-                            window_levels: Optional[Sequence[int]] = None) -> Image.Image:
+                            window_levels: Optional[Sequence[int]] = None, views: Optional[str] = None,
+                            members: Optional[int] = None) -> Image.Image:
     """compute (not a reference argument): arithmetic of the network, see UNetDiffusion -- None keeps the default.
     seed (not a reference argument; cddpm): the stochastic sampler's noise is drawn on the device from this seed, so the same
     call gives the same image again (DiffusionDenoiser.denoise); None: torch.randn, as the reference.
@@ -52,6 +54,13 @@ def denoise_image_diffusion(model_path: Optional[str], test_image_path: str, dev
     the two come together.
     tile (not a reference argument): the image is denoised at its OWN size as blended overlapping tile x tile crops with at least
     `overlap` shared pixels (DiffusionDenoiser.denoise_tiled) -- no resize to img_size and back; both sides must be >= tile.
+    views, members (not reference arguments; with tile only, one of the two): the ensembles of the TILED run, named as the Python
+    calls name them.  views ("auto", "flips" or "d4"; both variants): the returned image is the MEAN over the flipped and rotated
+    views of the image, each denoised as blended tiles at the image's own size (DiffusionDenoiser.denoise_tiled_self_ensemble; "auto"
+    is all 8 views: the tile is square); update "ddim" works with it.  members (cddpm): the MEAN of this many seeded draws of the tiled
+    run (DiffusionDenoiser.denoise_tiled_ensemble; the reference's update only).  std_out, quantiles and quantiles_out then describe
+    the views / the draws, float32 at the image's own size [H, W] / [levels, H, W]; bit_depth 16 and window store the mean as they
+    store the tiled image.  (samples and self_ensemble stay the ensembles of the RESIZED image and are refused together with tile.)
     self_ensemble (not a reference argument; both variants): "auto", "flips" or "d4" -- the returned image is the MEAN over the
     flipped and rotated views of the image (DiffusionDenoiser.denoise_self_ensemble); std_out, quantiles and quantiles_out then
     describe the views instead of seeded draws.  Not together with samples or tile.
@@ -98,16 +107,36 @@ def denoise_image_diffusion(model_path: Optional[str], test_image_path: str, dev
             raise ValueError("--self-ensemble draws its noise from the seed: step_noise cannot be given as well")
         if self_ensemble not in ("auto", "flips", "d4"):
             raise ValueError(f"--self-ensemble takes auto, flips or d4 (got {self_ensemble!r})")
+    if (views is not None or members is not None) and tile is None:
+        raise ValueError("--views and --members are the ensembles of the tiled run: they need --tile N (without it: --self-ensemble, --samples)")
+    if views is not None and members is not None:
+        raise ValueError("--views and --members cannot be combined: flip / rotate views or seeded draws, not both")
+    if views is not None and views not in ("auto", "flips", "d4"):
+        raise ValueError(f"--views takes auto, flips or d4 (got {views!r})")
+    if views is not None and update == "dpmpp2m":
+        raise ValueError("--update dpmpp2m cannot be combined with --views (the tiled self-ensemble runs the reference's update or ddim)")
+    if members is not None:
+        if rule:
+            raise ValueError(f"--update {update} cannot be combined with --members (the tiled ensemble runs the reference's update only)")
+        if variant != "cddpm":
+            raise ValueError("--members needs the stochastic (cddpm) variant: a deterministic sampler has no ensemble (use --views)")
+        if members < 1:
+            raise ValueError("--members needs K >= 1")
+    tiled_ensemble = views is not None or members is not None
     if tile is not None and (samples is not None or step_noise is not None):
         raise ValueError("--tile cannot be combined with --samples or a step_noise tensor")
     if samples is not None and variant != "cddpm" and not (rule and eta > 0):
         raise ValueError("--samples needs the stochastic (cddpm) variant: a deterministic sampler has no ensemble")
-    if std_out is not None and self_ensemble is None and (samples is None or samples < 2):
+    if std_out is not None and members is not None and members < 2:
+        raise ValueError("--std-out needs --members K with K >= 2")
+    if std_out is not None and self_ensemble is None and not tiled_ensemble and (samples is None or samples < 2):
         raise ValueError("--std-out needs --samples K with K >= 2")
     if (quantiles is None) != (quantiles_out is None):
         raise ValueError("--quantiles and --quantiles-out come together")
     if quantiles is not None:
-        if self_ensemble is None and (samples is None or samples > MAX_QUANTILE_MEMBERS):
+        if members is not None and members > MAX_QUANTILE_MEMBERS:
+            raise ValueError(f"--quantiles needs --members K with K <= {MAX_QUANTILE_MEMBERS}")
+        if self_ensemble is None and not tiled_ensemble and (samples is None or samples > MAX_QUANTILE_MEMBERS):
             raise ValueError(f"--quantiles needs --samples K with K <= {MAX_QUANTILE_MEMBERS}")
         quantiles = check_levels(quantiles)
     if samples is not None and step_noise is not None:
@@ -154,22 +183,41 @@ def denoise_image_diffusion(model_path: Optional[str], test_image_path: str, dev
         else:
             input_tensor = torch.from_numpy(image16.unit_float(raw16))[None, None].to(device)
         start_time = time.time()
-        res = diffusion.denoise_tiled(input_tensor, inference_steps=inference_steps, tile=tile, overlap=overlap, seed=seed, **rule)
+        if views is not None:
+            draws = variant == "cddpm" if not rule else eta > 0
+            res = diffusion.denoise_tiled_self_ensemble(input_tensor, inference_steps=inference_steps, views=views, tile=tile, overlap=overlap,
+                                                        seed=seed if draws else None, quantiles=quantiles, **rule)
+            what = f"Self-ensemble of {len(res.views)} views {res.views}, tiled"
+        elif members is not None:
+            res = diffusion.denoise_tiled_ensemble(input_tensor, inference_steps=inference_steps, members=members, tile=tile, overlap=overlap,
+                                                   seed=seed, quantiles=quantiles)
+            what = f"Ensemble of {members} samples, tiled"
+        else:
+            res = diffusion.denoise_tiled(input_tensor, inference_steps=inference_steps, tile=tile, overlap=overlap, seed=seed, **rule)
+            what = "Tiled"
         if on_gpu:
             torch.cuda.synchronize(device)
-        print(f"Tiled: {len(res.origins_y)} x {len(res.origins_x)} tiles of {tile}" + (f", seed {res.seed}" if res.seed is not None else ""))
+        print(f"{what}: {len(res.origins_y)} x {len(res.origins_x)} tiles of {tile}" + (f", seed {res.seed}" if res.seed is not None else ""))
         print(f"Inference time: {time.time() - start_time:.2f} seconds")
+        if tiled_ensemble:      # the mean of values in [0, 1] is in [0, 1]: stored as the tiled image is; the maps stay float, at the image's size
+            if std_out is not None:
+                np.save(std_out, res.std[0, 0].cpu().numpy())
+            if quantiles is not None:
+                np.save(quantiles_out, res.quantiles[0, :, 0].cpu().numpy())
+            image = res.mean
+        else:
+            image = res.image
         if win is not None:
             if on_gpu:
                 print("Window: grey levels {} .. {}".format(*win[0].tolist()))
-                out16 = prepost.window_to_u16(res.image[0, 0].float(), win).cpu().numpy()
+                out16 = prepost.window_to_u16(image[0, 0].float(), win).cpu().numpy()
             else:
-                out16 = image16.to_u16_window(res.image[0, 0].cpu().numpy(), win)
+                out16 = image16.to_u16_window(image[0, 0].cpu().numpy(), win)
             return image16.image_from_u16(out16)
         if raw16 is not None:
-            out16 = prepost.to_u16(res.image[0, 0].float()).cpu().numpy() if on_gpu else image16.to_u16(res.image[0, 0].cpu().numpy())
+            out16 = prepost.to_u16(image[0, 0].float()).cpu().numpy() if on_gpu else image16.to_u16(image[0, 0].cpu().numpy())
             return image16.image_from_u16(out16)
-        return Image.fromarray((res.image[0, 0].cpu().numpy() * 255).astype(np.uint8), mode="L")      # already clamped to [0, 1]
+        return Image.fromarray((image[0, 0].cpu().numpy() * 255).astype(np.uint8), mode="L")      # already clamped to [0, 1]
     if win is not None and on_gpu:      # windowed load, float resize, clip: one fused call under the levels on the device
         input_tensor = prepost.resize_bicubic_f32(dev_raw16, (img_size, img_size), clamp=True, levels=win)[None, None]
     elif win is not None:
@@ -262,6 +310,13 @@ def main(argv=None) -> None:
     ap.add_argument("--tile", type=int, default=None, metavar="N",
                     help="denoise the image at its own size as blended overlapping N x N tiles (N: a multiple of 8) instead of resizing it to --img-size")
     ap.add_argument("--overlap", type=int, default=32, help="with --tile: minimum overlap of neighbouring tiles (<= N / 2)")
+    ap.add_argument("--views", nargs="?", const="auto", default=None, choices=["auto", "flips", "d4"],
+                    help="with --tile, both variants: save the mean over the flipped and rotated views of the image, each denoised as "
+                         "blended tiles at the image's own size (auto: all 8); --std-out and --quantiles / --quantiles-out then describe "
+                         "the views, at the image's size")
+    ap.add_argument("--members", type=int, default=None, metavar="K",
+                    help="with --tile, cddpm: save the mean of this many seeded samples of the tiled run; --std-out (K >= 2) and "
+                         "--quantiles / --quantiles-out (K <= 64) then describe them, at the image's size")
     ap.add_argument("--self-ensemble", nargs="?", const="auto", default=None, choices=["auto", "flips", "d4"],
                     help="both variants: save the mean over the flipped and rotated views of the image (auto: all 8); --std-out and "
                          "--quantiles / --quantiles-out then describe the views")
@@ -297,15 +352,28 @@ def main(argv=None) -> None:
         ap.error("--self-ensemble cannot be combined with --tile")
     if args.tile is not None and (args.tile < 1 or args.samples is not None):
         ap.error("--tile needs N >= 1 and cannot be combined with --samples")
+    if (args.views is not None or args.members is not None) and args.tile is None:
+        ap.error("--views and --members need --tile N (without it: --self-ensemble, --samples)")
+    if args.views is not None and args.members is not None:
+        ap.error("--views and --members cannot be combined")
+    if args.views is not None and args.update == "dpmpp2m":
+        ap.error("--update dpmpp2m cannot be combined with --views")
+    if args.members is not None and (args.members < 1 or args.variant != "cddpm" or args.update != "reference"):
+        ap.error("--members needs K >= 1, --variant cddpm and the reference's update (a deterministic sampler has no ensemble: use --views)")
+    tiled_ensemble = args.views is not None or args.members is not None
+    if args.std_out is not None and args.members is not None and args.members < 2:
+        ap.error("--std-out needs --members K with K >= 2")
+    if args.quantiles is not None and args.members is not None and args.members > MAX_QUANTILE_MEMBERS:
+        ap.error(f"--quantiles needs --members K with K <= {MAX_QUANTILE_MEMBERS}")
     if args.samples is not None and (args.samples < 1 or (args.variant != "cddpm" and not (args.update == "ddim" and args.eta > 0))):
         ap.error("--samples needs K >= 1 and --variant cddpm (or --update ddim with --eta > 0)")
-    if args.std_out is not None and args.self_ensemble is None and (args.samples is None or args.samples < 2):
+    if args.std_out is not None and args.self_ensemble is None and not tiled_ensemble and (args.samples is None or args.samples < 2):
         ap.error("--std-out needs --samples K with K >= 2")
     levels = None
     if (args.quantiles is None) != (args.quantiles_out is None):
         ap.error("--quantiles and --quantiles-out come together")
     if args.quantiles is not None:
-        if args.self_ensemble is None and (args.samples is None or args.samples > MAX_QUANTILE_MEMBERS):
+        if args.self_ensemble is None and not tiled_ensemble and (args.samples is None or args.samples > MAX_QUANTILE_MEMBERS):
             ap.error(f"--quantiles needs --samples K with K <= {MAX_QUANTILE_MEMBERS}")
         try:
             levels = check_levels([float(v) for v in args.quantiles.split(",")])
@@ -330,7 +398,9 @@ def main(argv=None) -> None:
                                        update=args.update, eta=args.eta, clip_x0=not args.no_clip_x0,
                                        **({} if args.x0_out is None else {"x0_out": args.x0_out}),
                                        bit_depth=args.bit_depth, **({} if window is None else {"window": window}),
-                                       **({} if window_levels is None else {"window_levels": window_levels}))
+                                       **({} if window_levels is None else {"window_levels": window_levels}),
+                                       **({} if args.views is None else {"views": args.views}),
+                                       **({} if args.members is None else {"members": args.members}))
     restored.save(args.out, quality=95)
     print(f"\nResult saved: {args.out}")
 

@@ -113,21 +113,21 @@ static int check_batched_call(mi_plan* plan, int layout_rc, const EnsembleLayout
     return check_device(plan);
 }
 
-// The one pass loop.  Round m (a member of the tiled ensemble, whose member word is a launch constant; else the only round) runs
-// the virtual samples [0, V) in passes: fill(cond, v0, n) writes the pass's condition images, the sampler loop leaves its
-// samples at store[m][v0 ..].  The caller holds plan->side_mu and has cleared the status word, so the word accumulates over the
-// passes; every pass joins its side streams before it returns, on success and on failure (enqueue_run), and the first failing
-// pass ends the call.
-template <class Fill>
+// The one pass loop.  Round m (a member of the tiled ensemble or a view of the tiled self-ensemble, whose member word is a launch
+// constant; else the only round) runs the virtual samples [0, V) in passes: fill(cond, m, v0, n) writes the pass's condition
+// images, the sampler loop leaves its samples at store[m][v0 ..].  noise(m) is the round's StepNoise: the member word, and for
+// tiles the whole-image frame, may differ from round to round (member_rounds: the member word alone does).  The caller holds
+// plan->side_mu and has cleared the status word, so the word accumulates over the passes; every pass joins its side streams before
+// it returns, on success and on failure (enqueue_run), and the first failing pass ends the call.
+template <class Fill, class Noise>
 static int run_passes(mi_plan* plan, Fill fill, float* store, int64_t V, int rounds, int h, int w, size_t chw, const EnsembleLayout& L,
-                      StepNoise sn, const Schedule& sc, int flags, char* ws, void* stream) {
+                      Noise noise, const Schedule& sc, int flags, char* ws, void* stream) {
     float* cond = reinterpret_cast<float*>(ws + L.cond_off);
-    const uint32_t member_base = sn.member_offset;
     for (int m = 0; m < rounds; ++m) {
-        sn.member_offset = member_base + m;
+        StepNoise sn = noise(m);
         for (int64_t v0 = 0; v0 < V; v0 += L.pass) {
             const int n = (int)(V - v0 < L.pass ? V - v0 : L.pass);
-            if (int rc = fill(cond, (int)v0, n)) return rc;
+            if (int rc = fill(cond, m, (int)v0, n)) return rc;
             sn.v0 = (int)v0;
             Program* g = nullptr;
             float* x = store + ((size_t)m * V + (size_t)v0) * chw;
@@ -136,6 +136,11 @@ static int run_passes(mi_plan* plan, Fill fill, float* store, int64_t V, int rou
         }
     }
     return MI_OK;
+}
+
+// the rounds of a member-outer call (and the single round of the others): round m draws member word member_offset + m, nothing else changes
+static auto member_rounds(const StepNoise& sn) {
+    return [sn](int m) { StepNoise r = sn; r.member_offset = sn.member_offset + (uint32_t)m; return r; };
 }
 
 extern "C" int mi_denoise_ensemble_rule(mi_plan* plan, const float* noisy, float* mean_out, float* std_out, float* samples_out,
@@ -165,8 +170,8 @@ extern "C" int mi_denoise_ensemble_rule(mi_plan* plan, const float* noisy, float
     HIPCHK(hipMemsetAsync(ws, 0, 256, s));                  // status word: once per call, the passes accumulate into it
     StepNoise sn;
     sn.seeded = true; sn.seed = seed; sn.sample_offset = sample_offset; sn.members = members; sn.member_offset = (uint32_t)member_offset;
-    auto broadcast = [&](float* cond, int v0, int n) { return launched(ensemble_broadcast_launch(noisy, cond, v0, n, members, chw, s), "ensemble_broadcast"); };
-    if (int rc = run_passes(plan, broadcast, samples, (int64_t)B * members, 1, H, W, chw, L, sn, sc, flags, ws, stream)) return rc;
+    auto broadcast = [&](float* cond, int, int v0, int n) { return launched(ensemble_broadcast_launch(noisy, cond, v0, n, members, chw, s), "ensemble_broadcast"); };
+    if (int rc = run_passes(plan, broadcast, samples, (int64_t)B * members, 1, H, W, chw, L, member_rounds(sn), sc, flags, ws, stream)) return rc;
     if (mean_out || std_out) return launched(ensemble_reduce_launch(samples, B, members, chw, mean_out, std_out, s), "ensemble_reduce");
     return MI_OK;
 }
@@ -284,8 +289,8 @@ static int tiled_run(mi_plan* plan, const float* noisy, float* image_out, float*
         sn.seeded = true; sn.seed = seed; sn.sample_offset = sample_offset; sn.members = K;
         sn.tiles_x = tg.nx; sn.tiles_y = tg.ny; sn.img_H = H; sn.img_W = W;
     }
-    auto extract = [&](float* cond, int v0, int n) { return launched(tile_extract_launch(noisy, cond, tg, v0, n, s), "tile_extract"); };
-    if (int rc = run_passes(plan, extract, tiles, (int64_t)B * K, 1, th, tw, chw, L, sn, sc, flags, ws, stream)) return rc;
+    auto extract = [&](float* cond, int, int v0, int n) { return launched(tile_extract_launch(noisy, cond, tg, v0, n, s), "tile_extract"); };
+    if (int rc = run_passes(plan, extract, tiles, (int64_t)B * K, 1, th, tw, chw, L, member_rounds(sn), sc, flags, ws, stream)) return rc;
     return launched(tile_blend_launch(tiles, image_out, B, tg, s), "tile_blend");
 }
 
@@ -399,8 +404,8 @@ extern "C" int mi_denoise_tiled_ensemble(mi_plan* plan, const float* noisy, floa
     StepNoise sn;
     sn.seeded = true; sn.seed = seed; sn.sample_offset = sample_offset; sn.members = K; sn.member_offset = (uint32_t)member_offset;
     sn.tiles_x = tg.nx; sn.tiles_y = tg.ny; sn.img_H = H; sn.img_W = W;
-    auto extract = [&](float* cond, int v0, int n) { return launched(tile_extract_launch(noisy, cond, tg, v0, n, s), "tile_extract"); };
-    if (int rc = run_passes(plan, extract, tiles, (int64_t)B * K, members, th, tw, chw, L, sn, sc, flags, ws, stream)) return rc;      // V: ONE member's
+    auto extract = [&](float* cond, int, int v0, int n) { return launched(tile_extract_launch(noisy, cond, tg, v0, n, s), "tile_extract"); };
+    if (int rc = run_passes(plan, extract, tiles, (int64_t)B * K, members, th, tw, chw, L, member_rounds(sn), sc, flags, ws, stream)) return rc;      // V: ONE member's
     if (mean_out || std_out || samples_out)
         return launched(tile_blend_reduce_launch(tiles, B, members, tg, mean_out, std_out, samples_out, s), "tile_blend_reduce");
     return MI_OK;
@@ -408,7 +413,7 @@ extern "C" int mi_denoise_tiled_ensemble(mi_plan* plan, const float* noisy, floa
 
 // ---------------------------------------------------------------------------- geometric self-ensemble: flip / rotate views
 // the view list of a call, host int32 -> the kernel argument (include/midd.h: THE GEOMETRY)
-static int check_views(const int32_t* views, int n_views, int H, int W, DihedralViews* dv) {
+static int check_view_list(const int32_t* views, int n_views, DihedralViews* dv) {
     if (n_views < 1 || n_views > DIHEDRAL_MAX_VIEWS)
         return fail(MI_EINVAL, "n_views %d outside [1, %d]: a view list holds 1 to 8 distinct view codes (limit: 1 <= n_views <= %d)", n_views,
                     DIHEDRAL_MAX_VIEWS, DIHEDRAL_MAX_VIEWS);
@@ -422,6 +427,12 @@ static int check_views(const int32_t* views, int n_views, int H, int W, Dihedral
             if (views[j] == views[k]) return fail(MI_EINVAL, "views[%d] = %d repeats views[%d]: the view codes of a list are distinct", k, views[k], j);
         dv->code[k] = (uint8_t)views[k];
     }
+    return MI_OK;
+}
+
+// ... and, where every view has the image's shape (the untiled calls), the rule of the transposing codes
+static int check_views(const int32_t* views, int n_views, int H, int W, DihedralViews* dv) {
+    if (int rc = check_view_list(views, n_views, dv)) return rc;
     for (int k = 0; k < n_views; ++k)
         if ((views[k] & 4) && H != W)
             return fail(MI_EINVAL, "views[%d] = %d transposes a %dx%d image: a pass never mixes image sizes (limit: view codes 4 .. 7 need H == W)", k, views[k], H, W);
@@ -505,7 +516,147 @@ extern "C" int mi_denoise_self_ensemble(mi_plan* plan, const float* noisy, float
     HIPCHK(hipMemsetAsync(ws, 0, 256, s));                  // status word: once per call, the passes accumulate into it
     StepNoise sn;                                           // view k draws as member member_offset + k, at the pixel's place in the VIEW's frame
     if (seeded) { sn.seeded = true; sn.seed = seed; sn.sample_offset = sample_offset; sn.members = n_views; sn.member_offset = (uint32_t)member_offset; }
-    auto fill = [&](float* cond, int v0, int n) { return launched(dihedral_views_launch(noisy, cond, dv, Cc, H, W, v0, n, s), "dihedral_views"); };
-    if (int rc = run_passes(plan, fill, views_out, (int64_t)B * n_views, 1, H, W, chw, L, sn, sc, flags, ws, stream)) return rc;
+    auto fill = [&](float* cond, int, int v0, int n) { return launched(dihedral_views_launch(noisy, cond, dv, Cc, H, W, v0, n, s), "dihedral_views"); };
+    if (int rc = run_passes(plan, fill, views_out, (int64_t)B * n_views, 1, H, W, chw, L, member_rounds(sn), sc, flags, ws, stream)) return rc;
     return launched(dihedral_reduce_launch(views_out, B, dv, Cc, H, W, mean_out, std_out, samples_out, s), "dihedral_reduce");
+}
+
+// ---------------------------------------------------------------------------- tiled self-ensemble: flip / rotate views at native size
+// A transposed image is still cut into th x tw tiles, so H == W is not needed here; what a transposing code needs is that the
+// W x H frame has as many tiles of the same shape (include/midd.h: THE GEOMETRY, "a view's tiles are the tiles of the viewed image")
+static int check_view_tiles(const DihedralViews& dv, int th, int tw, int oy, int ox) {
+    for (int k = 0; k < dv.n; ++k)
+        if ((dv.code[k] & 4) && (th != tw || oy != ox))
+            return fail(MI_EINVAL, "views[%d] = %d transposes the image, whose tiles are %dx%d with overlap %dx%d: the storage [views][B][tiles] holds "
+                        "one tile count and shape for every view (limit: view codes 4 .. 7 need th == tw and oy == ox; H == W is not needed)",
+                        k, (int)dv.code[k], th, tw, oy, ox);
+    return MI_OK;
+}
+
+// the geometry of view `code`'s frame: the tiling of the viewed Hv x Wv image (tile_geometry.h)
+static TileGeom view_frame(const TileGeom& g, int code) {
+    return (code & 4) ? TileGeom{g.C, g.W, g.H, g.tw, g.th, g.ox, g.oy, g.nx, g.ny} : g;
+}
+
+// what the two stand-alone calls share: the geometry, the view list, the transposing rule, the batch and the tile blocks
+static int check_unview_call(int B, int C, int H, int W, int th, int tw, int oy, int ox, const int32_t* views, int n_views, TileGeom* g, DihedralViews* dv) {
+    if (int rc = check_tile_run(B, C, H, W, th, tw, oy, ox, g)) return rc;
+    if (int rc = check_view_list(views, n_views, dv)) return rc;
+    if (int rc = check_view_tiles(*dv, th, tw, oy, ox)) return rc;
+    if (int rc = check_reduce_batch(B, "the limit of mi_ensemble_reduce, whose arithmetic this call composes")) return rc;
+    return check_tiled_ensemble_size(B, n_views, *g);
+}
+
+extern "C" int mi_tile_blend_unview_reduce(const float* tiles, int B, int C, int H, int W, int th, int tw, int oy, int ox,
+                                           const int32_t* views, int n_views, float* mean_out, float* std_out, float* samples_out, void* stream) {
+    TileGeom g{};
+    DihedralViews dv;
+    if (int rc = check_unview_call(B, C, H, W, th, tw, oy, ox, views, n_views, &g, &dv)) return rc;
+    if (!mean_out && !std_out && !samples_out) return fail(MI_EINVAL, "no output: give at least one of mean_out, std_out, samples_out");
+    if (int rc = check_std_views(std_out, n_views)) return rc;
+    if (!tiles) return fail(MI_EINVAL, "null argument");
+    return launched(tile_blend_unview_reduce_launch(tiles, B, dv, g, mean_out, std_out, samples_out, (hipStream_t)stream), "tile_blend_unview_reduce");
+}
+
+extern "C" int mi_tile_blend_unview_quantiles(const float* tiles, int B, int C, int H, int W, int th, int tw, int oy, int ox,
+                                              const int32_t* views, int n_views, const double* q, int nq, float* out, void* stream) {
+    TileGeom g{};
+    DihedralViews dv;
+    if (int rc = check_unview_call(B, C, H, W, th, tw, oy, ox, views, n_views, &g, &dv)) return rc;
+    QuantileLevels ql;
+    if (int rc = check_quantile_levels(q, nq, &ql)) return rc;
+    if (!tiles || !out) return fail(MI_EINVAL, "null argument");
+    return launched(tile_blend_unview_quantiles_launch(tiles, B, dv, g, ql, out, (hipStream_t)stream), "tile_blend_unview_quantiles");
+}
+
+// the argument rules of mi_denoise_tiled_self_ensemble and of its workspace query, in the documented order (no GPU work)
+static int check_tiled_self_ensemble_args(mi_plan* plan, int B, int H, int W, int th, int tw, int oy, int ox, const int32_t* views, int n_views,
+                                          int64_t sample_offset, int64_t member_offset, int pass_samples, TileGeom* g, DihedralViews* dv) {
+    if (!plan) return fail(MI_EINVAL, "null plan");
+    if (int rc = check_view_list(views, n_views, dv)) return rc;
+    if (int rc = check_view_tiles(*dv, th, tw, oy, ox)) return rc;
+    if (int rc = check_tiled_ensemble_args(plan, B, n_views, H, W, th, tw, oy, ox, sample_offset, member_offset, pass_samples, g)) return rc;
+    return check_reduce_batch(B, "limit of the view and reduce kernels' grids");
+}
+
+// (the layout depends on the NUMBER of views alone; the list's transposing rule is judged by the call)
+extern "C" size_t mi_tiled_self_ensemble_workspace_bytes(mi_plan* plan, int B, int n_views, int H, int W, int th, int tw, int oy, int ox,
+                                                         int pass_samples, int tiles_external) {
+    if (!plan) { fail(MI_EINVAL, "null plan"); return 0; }
+    if (n_views < 1 || n_views > DIHEDRAL_MAX_VIEWS) {
+        fail(MI_EINVAL, "n_views %d outside [1, %d]: a view list holds 1 to 8 distinct view codes (limit: 1 <= n_views <= %d)", n_views,
+             DIHEDRAL_MAX_VIEWS, DIHEDRAL_MAX_VIEWS);
+        return 0;
+    }
+    TileGeom g{};
+    if (check_tiled_ensemble_args(plan, B, n_views, H, W, th, tw, oy, ox, 0, 0, pass_samples, &g)) return 0;
+    if (check_reduce_batch(B, "limit of the view and reduce kernels' grids")) return 0;
+    EnsembleLayout L{};
+    size_t view_off = 0;
+    if (tiled_self_ensemble_layout(plan, B, n_views, g.ny * g.nx, H, W, th, tw, pass_samples, tiles_external != 0, &L, &view_off)) return 0;
+    return L.bytes;
+}
+
+// Views are the outer loop: round k is mi_denoise_tiled's pass structure over the viewed batch view(noisy, g_k) -- a copy in the
+// workspace (plane_view_launch; the identity is read in place), cut by the extract of the view frame's geometry -- with the member
+// word member_offset + k and that frame as the whole image of the seeded noise.  Its tiles are slice k of the storage
+// [views][B][tiles], in the VIEW's frame; the final launch blends every view there, turns it back and reduces.
+extern "C" int mi_denoise_tiled_self_ensemble(mi_plan* plan, const float* noisy, float* mean_out, float* std_out, float* samples_out, float* tiles_out,
+                                              int B, int H, int W, int th, int tw, int oy, int ox, const int32_t* views, int n_views,
+                                              const int32_t* t_list, int n_iters,
+                                              const float* beta, const float* alpha, const float* alpha_hat, int noise_steps,
+                                              int seeded, uint64_t seed, int64_t sample_offset, int64_t member_offset, int pass_samples, int flags,
+                                              const mi_update_rule* rule, void* workspace, size_t workspace_bytes, void* stream) {
+    Schedule sc{t_list, n_iters, beta, alpha, alpha_hat, noise_steps};
+    if (rule && rule->kind == MI_UPDATE_DPMPP2M)
+        return fail(MI_EINVAL, "update rule MI_UPDATE_DPMPP2M is not built for mi_denoise_tiled_self_ensemble: the call takes no buffer for the "
+                    "predicted images (limit: MI_UPDATE_REFERENCE or MI_UPDATE_DDIM)");
+    if (int rc = apply_rule(rule, &sc)) return rc;
+    TileGeom tg{};
+    DihedralViews dv;
+    if (int rc = check_tiled_self_ensemble_args(plan, B, H, W, th, tw, oy, ox, views, n_views, sample_offset, member_offset, pass_samples, &tg, &dv))
+        return rc;
+    if (!mean_out && !std_out && !samples_out && !tiles_out)
+        return fail(MI_EINVAL, "no output: give at least one of mean_out, std_out, samples_out, tiles_out");
+    if (int rc = check_std_views(std_out, n_views)) return rc;
+    const int K = tg.ny * tg.nx;
+    const size_t chw = (size_t)tg.C * th * tw, img = (size_t)tg.C * H * W * sizeof(float);
+    const Buf buf[5] = {{noisy, (size_t)B * img, "noisy"}, {mean_out, (size_t)B * img, "mean_out"}, {std_out, (size_t)B * img, "std_out"},
+                        {samples_out, (size_t)B * n_views * img, "samples_out"},
+                        {tiles_out, (size_t)n_views * B * K * chw * sizeof(float), "tiles_out"}};
+    if (int rc = check_no_overlap(buf, 5, "noisy is read by every round and the reduce reads the tiles while it writes mean_out, std_out and samples_out"))
+        return rc;
+    EnsembleLayout L{};
+    size_t view_off = 0;
+    // (evaluated before the state check, reported after it: check_batched_call; host arithmetic only, as in the *_workspace_bytes queries)
+    const int layout_rc = tiled_self_ensemble_layout(plan, B, n_views, K, H, W, th, tw, pass_samples, tiles_out != nullptr, &L, &view_off);
+    if (int rc = check_batched_call(plan, layout_rc, L, workspace, workspace_bytes, {noisy}, sc)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    char* ws = (char*)workspace;
+    float* tiles = tiles_out ? tiles_out : reinterpret_cast<float*>(ws + L.samples_off);
+    float* viewed = reinterpret_cast<float*>(ws + view_off);
+    std::lock_guard<std::mutex> side_lk(plan->side_mu);     // held over all passes: the side streams are per plan
+    HIPCHK(hipMemsetAsync(ws, 0, 256, s));                  // status word: once per call, the passes of every view accumulate into it
+    // round k draws as member member_offset + k, at the pixel's place in the whole VIEWED image (its frame: Hv x Wv, ny_v x nx_v tiles)
+    auto noise = [&](int k) {
+        StepNoise sn;
+        if (seeded) {
+            const TileGeom f = view_frame(tg, dv.code[k]);
+            sn.seeded = true; sn.seed = seed; sn.sample_offset = sample_offset; sn.members = K; sn.member_offset = (uint32_t)(member_offset + k);
+            sn.tiles_x = f.nx; sn.tiles_y = f.ny; sn.img_H = f.H; sn.img_W = f.W;
+        }
+        return sn;
+    };
+    // the first pass of a round makes the round's viewed copy (same stream: the passes of the round before have been enqueued and
+    // joined), every pass extracts its tiles from it -- bit for bit the slices of view(noisy, g_k)
+    auto fill = [&](float* cond, int k, int v0, int n) {
+        const int code = dv.code[k];
+        if (code != 0 && v0 == 0)
+            if (int rc = launched(plane_view_launch(noisy, viewed, code, B, tg.C, H, W, s), "plane_view")) return rc;
+        return launched(tile_extract_launch(code ? viewed : noisy, cond, view_frame(tg, code), v0, n, s), "tile_extract");
+    };
+    if (int rc = run_passes(plan, fill, tiles, (int64_t)B * K, n_views, th, tw, chw, L, noise, sc, flags, ws, stream)) return rc;      // V: ONE view's
+    if (mean_out || std_out || samples_out)
+        return launched(tile_blend_unview_reduce_launch(tiles, B, dv, tg, mean_out, std_out, samples_out, s), "tile_blend_unview_reduce");
+    return MI_OK;
 }

@@ -125,6 +125,12 @@ int check_tiled_ensemble_args(mi_plan* p, int B, int members, int H, int W, int 
 int tiled_ensemble_layout(mi_plan* p, int B, int members, int tiles, int th, int tw, int pass_samples, bool tiles_external, EnsembleLayout* L);   // midd_planner.hip
 // mi_denoise_self_ensemble: its workspace is mi_denoise_ensemble's with members = views and the member outputs ALWAYS inside:
 // [sampler workspace of a pass | condition views of a pass | view outputs [B][views], each in its view's frame]
+// mi_denoise_tiled_self_ensemble: its workspace is mi_denoise_tiled's -- a pass never spans two views -- with the viewed copy of the
+// batch of the round that runs and the tile outputs of every view: [sampler workspace of a pass | condition tiles of a pass |
+// view(noisy) of one round, B * C*H*W floats rounded up to 256 bytes, at *view_off | tile outputs [views][B][tiles] (unless
+// tiles_out is given), at L->samples_off]
+int tiled_self_ensemble_layout(mi_plan* p, int B, int n_views, int tiles, int H, int W, int th, int tw, int pass_samples, bool tiles_external,
+                               EnsembleLayout* L, size_t* view_off);   // midd_planner.hip
 }  // namespace midd
 
 struct mi_plan {

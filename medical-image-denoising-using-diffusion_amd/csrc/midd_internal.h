@@ -375,6 +375,19 @@ hipError_t dihedral_reduce_launch(const float* views_out, int B, const DihedralV
 hipError_t dihedral_quantiles_launch(const float* views_out, int B, const DihedralViews& dv, int C, int H, int W,
                                      const QuantileLevels& ql, float* out, hipStream_t s);
 
+// Tiled self-ensemble (tiled_views.hip; include/midd.h: mi_denoise_tiled_self_ensemble).  A transposing view turns H x W into
+// W x H here -- H == W is not needed -- and its tiles are those of the viewed image: with a transposing code th == tw, oy == ox.
+// dst [B][C][Hv][Wv] <- view(images [B][C][H][W], code), one code per launch: the viewed batch of one round.  B <= 65535
+hipError_t plane_view_launch(const float* images, float* dst, int code, int B, int C, int H, int W, hipStream_t s);
+// tiles [G][B][ny*nx][C][th][tw] (view k's tiles in ITS frame; g: the geometry of the un-viewed H x W image) -> mean, unbiased std
+// [B][C][H][W] over the views blended and turned back and those aligned members, samples [B][G][C][H][W]; each of the three may be
+// null (not all; std needs G >= 2).  The arithmetic of tile_blend_launch per view, then of ensemble_reduce_launch.  B <= 65535
+hipError_t tile_blend_unview_reduce_launch(const float* tiles, int B, const DihedralViews& dv, const TileGeom& g,
+                                           float* mean, float* std, float* samples, hipStream_t s);
+// tiles as above -> out [B][nq][C][H][W]: the arithmetic of ensemble_quantiles_launch over the aligned blended members
+hipError_t tile_blend_unview_quantiles_launch(const float* tiles, int B, const DihedralViews& dv, const TileGeom& g,
+                                              const QuantileLevels& ql, float* out, hipStream_t s);
+
 // bilinear resize of an activation tensor, either layout (align_corners=False), any size ratio
 hipError_t resize_bilinear_launch(const float* src, float* dst, stat_word* tot, int rep, int bs, int B, int H, int W, int C, int OH, int OW, int blocked, hipStream_t s);
 // ConvTranspose2d(C,C,4,stride=2,padding=1) direct (only used by topologies where it cannot be folded)

@@ -370,6 +370,16 @@ extern "C" size_t mi_tiled_ensemble_workspace_bytes(mi_plan* plan, int B, int me
     return L.bytes;
 }
 
+int midd::tiled_self_ensemble_layout(mi_plan* p, int B, int n_views, int tiles, int H, int W, int th, int tw, int pass_samples, bool tiles_external,
+                                     EnsembleLayout* L, size_t* view_off) {
+    if (int rc = ensemble_layout(p, B, tiles, th, tw, pass_samples, true, L)) return rc;      // the passes of one view
+    const size_t C = (size_t)p->cfg.in_channels;
+    *view_off = L->samples_off;
+    L->samples_off += ((size_t)B * C * H * W * sizeof(float) + 255) & ~(size_t)255;
+    L->bytes = L->samples_off + (tiles_external ? 0 : (size_t)n_views * B * tiles * C * th * tw * sizeof(float));
+    return MI_OK;
+}
+
 // Kernel symbol + algorithmic work of one op (for mi_profile_*).
 void midd::op_work(mi_plan* p, Program* g, const Op& o, std::string* name, double* flops, double* bytes) {
     const double B = g->B;

@@ -640,6 +640,68 @@ class UNetDiffusion(nn.Module):
                             self._call_flags(clamp_eps, no_split)), ws, dev)
         return mean, std, samples, tiles, plan_t
 
+    @torch.no_grad()
+    def run_tiled_self_ensemble(self, noisy: torch.Tensor, t_list, beta: torch.Tensor, alpha: torch.Tensor, alpha_hat: torch.Tensor,
+                                clamp_eps: bool, tile, overlap, views="auto", seed: Optional[int] = None, sample_offset: int = 0,
+                                member_offset: int = 0, max_batch: int = 16, want_mean: bool = True, want_std: bool = True,
+                                want_samples: bool = False, want_tiles: bool = False, no_split: bool = False, *,
+                                update: str = "reference", eta: float = 0.0, clip_x0: bool = True):
+        """The flip / rotate views of images of any size >= the tile in one native call (mi_denoise_tiled_self_ensemble) ->
+        (mean, std, samples, tiles, codes, TilePlan), each tensor None when not asked for.  Views are the outer loop; inside a view
+        the B * tiles crops of the viewed batch run in passes of at most ``max_batch``, as run_tiled runs them.  samples is
+        [B, views, C, H, W], every member turned back into the image's frame; tiles [views, B, ny * nx, C, th, tw], view k's in its
+        own frame.  seed None: nothing is drawn; else view k draws as member ``member_offset + k``.  update, eta, clip_x0: the
+        update rule, as in run_tiled ("dpmpp2m" is not built for this call)."""
+        from .sampler import check_members, check_seed, check_update, tiling, view_codes_tiled
+        rule = check_update(update, eta, clip_x0)
+        if rule is not None and rule.kind == native.MI_UPDATE["dpmpp2m"]:
+            raise ValueError("run_tiled_self_ensemble (mi_denoise_tiled_self_ensemble) takes no history buffer: update='dpmpp2m' is not built for it")
+        if seed is not None:
+            seed, _ = check_seed(seed, 0)
+        _, sample_offset = check_seed(0, sample_offset)
+        if not isinstance(noisy, torch.Tensor) or noisy.dim() != 4:
+            self._check_image(noisy, "noisy_img")                 # (raises)
+        B, Cc, H, W = noisy.shape
+        codes = view_codes_tiled(H, W, tile, overlap, views)
+        G = len(codes)
+        _, member_offset, max_batch = check_members(G, member_offset, max_batch)
+        self._check_image(noisy, "noisy_img")
+        want_std = want_std and G >= 2
+        if not (want_mean or want_std or want_samples or want_tiles):
+            raise ValueError("nothing to return: ask for the mean, the std, the samples or the tiles")
+        plan_t, th, tw, oy, ox, K = tiling(H, W, tile, overlap)
+        keep, sched = self._schedule_args(t_list, beta, alpha, alpha_hat)
+        code_arg = (C.c_int32 * G)(*codes)
+        dev = noisy.device
+        with self._lock, torch.cuda.device(dev):
+            plan = self._ensure_plan(time_rows=sched[-1])
+            src = noisy.contiguous()
+            mean = torch.empty_like(src) if want_mean else None
+            std = torch.empty_like(src) if want_std else None
+            samples = torch.empty((B, G, Cc, H, W), dtype=torch.float32, device=dev) if want_samples else None
+            tiles = torch.empty((G, B, K, Cc, th, tw), dtype=torch.float32, device=dev) if want_tiles else None
+            pass_samples = min(max_batch, max(1, B * K))
+            size = (B, G, H, W, th, tw, oy, ox, pass_samples, 1 if want_tiles else 0)
+            ws = self._resident_workspace("_ensemble_ws", ("tiled_self_ensemble",) + size + (dev.index, torch.cuda.current_stream(dev).cuda_stream),
+                                          lambda: native.lib().mi_tiled_self_ensemble_workspace_bytes(self._plan, *size), dev)
+            self._invoke(native.lib().mi_denoise_tiled_self_ensemble,
+                         (plan, src.data_ptr(), _ptr(mean), _ptr(std), _ptr(samples), _ptr(tiles), B, H, W, th, tw, oy, ox, code_arg, G) + sched
+                         + (0 if seed is None else 1, C.c_uint64(seed or 0), C.c_int64(sample_offset), C.c_int64(member_offset), pass_samples,
+                            self._call_flags(clamp_eps, no_split), None if rule is None else C.byref(rule)), ws, dev)
+        return mean, std, samples, tiles, codes, plan_t
+
+    def tiled_self_ensemble_workspace_bytes(self, B: int, views: int, H: int, W: int, tile, overlap=32, max_batch: int = 16,
+                                            tiles_external: bool = False) -> int:
+        """Workspace of run_tiled_self_ensemble for ``views`` views per image (a count): tiled_workspace_bytes with the tiles
+        external + the viewed copy of the batch (B * C*H*W * 4 bytes, rounded up to 256) + the tiles of every view unless
+        ``tiles_external``."""
+        from .sampler import tiling
+        _, th, tw, oy, ox, K = tiling(H, W, tile, overlap)
+        with self._lock, torch.cuda.device(self._device()):
+            self._ensure_plan()
+            return int(native.lib().mi_tiled_self_ensemble_workspace_bytes(self._plan, B, views, H, W, th, tw, oy, ox,
+                                                                           min(max_batch, max(1, B * K)), 1 if tiles_external else 0))
+
     def _tiled_workspace(self, args: tuple, dev: torch.device, ensemble: bool = False) -> torch.Tensor:
         """Scratch of one run_tiled (or, ``ensemble``, run_tiled_ensemble) call: the resident entry of the ensemble calls."""
         query = native.lib().mi_tiled_ensemble_workspace_bytes if ensemble else native.lib().mi_tiled_workspace_bytes

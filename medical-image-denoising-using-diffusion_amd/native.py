@@ -109,6 +109,14 @@ SYMBOLS = [
                                           [C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int,
                                            C.c_int, C.c_uint64, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
     ("mi_self_ensemble_workspace_bytes", C.c_size_t, [C.c_void_p] + [C.c_int] * 6),
+    ("mi_tile_blend_unview_reduce", C.c_int, [C.c_void_p] + [C.c_int] * 8 + [C.POINTER(C.c_int32), C.c_int] + [C.c_void_p] * 4),
+    ("mi_tile_blend_unview_quantiles", C.c_int, [C.c_void_p] + [C.c_int] * 8 + [C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_double), C.c_int,
+                                                 C.c_void_p, C.c_void_p]),
+    ("mi_denoise_tiled_self_ensemble", C.c_int, [C.c_void_p] * 6 + [C.c_int] * 7 + [C.POINTER(C.c_int32), C.c_int] +
+                                                [C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int,
+                                                 C.c_int, C.c_uint64, C.c_int64, C.c_int64, C.c_int, C.c_int, C.POINTER(UpdateRule),
+                                                 C.c_void_p, C.c_size_t, C.c_void_p]),
+    ("mi_tiled_self_ensemble_workspace_bytes", C.c_size_t, [C.c_void_p] + [C.c_int] * 10),
     ("mi_ddim_coefficients", C.c_int, [C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_float), C.c_int, C.c_double, C.POINTER(C.c_float)]),
     ("mi_denoise_rule", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                   C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float),

@@ -581,6 +581,106 @@ def dihedral_quantiles(view_outputs: torch.Tensor, views="auto", q=None) -> torc
     return out
 
 
+class TiledSelfEnsembleResult(NamedTuple):
+    """What ``DiffusionDenoiser.denoise_tiled_self_ensemble`` returns."""
+    mean: torch.Tensor                    # [B, C, H, W]: per-pixel mean over the views' blended images, each turned back, at the input's own size
+    std: Optional[torch.Tensor]           # [B, C, H, W]: unbiased per-pixel standard deviation over the views; None for one view
+    samples: Optional[torch.Tensor]       # [B, views, C, H, W] with return_samples=True: the aligned blended members, in the order of ``views``
+    tiles: Optional[torch.Tensor]         # [views, B, ny * nx, C, th, tw] with return_tiles=True: tiles[k] are view k's tiles in ITS frame
+    views: Tuple[int, ...]                # the view codes of the run (include/midd.h: THE GEOMETRY), as resolved from the argument
+    origins_y: Tuple[int, ...]            # row origin of every tile row of the UN-TRANSPOSED frame (H x W); a transposing view is cut
+    origins_x: Tuple[int, ...]            # by the (W, H) plan: tile_plan(W, H, tile, overlap)
+    seed: Optional[int]                   # the seed of the run when it drew noise (drawn when the call had seed=None); else None
+
+
+class TiledSelfEnsembleQuantileResult(NamedTuple):
+    """What ``DiffusionDenoiser.denoise_tiled_self_ensemble(..., quantiles=levels)`` returns: TiledSelfEnsembleResult's fields, then the maps."""
+    mean: torch.Tensor
+    std: Optional[torch.Tensor]
+    samples: Optional[torch.Tensor]
+    tiles: Optional[torch.Tensor]
+    views: Tuple[int, ...]
+    origins_y: Tuple[int, ...]
+    origins_x: Tuple[int, ...]
+    seed: Optional[int]
+    quantiles: torch.Tensor               # [B, nq, C, H, W]: per-pixel quantile maps of the aligned blended members
+    levels: Tuple[float, ...]             # the quantile levels, each in [0, 1]
+
+
+def view_codes_tiled(H: int, W: int, tile, overlap=32, views="auto") -> Tuple[int, ...]:
+    """The view list of a TILED self-ensemble over H x W images (host only).  A transposed image is still cut into tiles, so the
+    transposing codes 4 .. 7 do not need H == W here; they need a square tile and overlap (th == tw and oy == ox), so that the
+    W x H frame has as many tiles of the same shape (include/midd.h: TILED SELF-ENSEMBLE).  ``"auto"`` is ``"d4"`` when the tile
+    and the overlap are square, whatever H and W, else ``"flips"``; ``"flips"``, ``"d4"`` and sequences as in ``view_codes``.
+    Raises ValueError for anything the native call would refuse in the list; the tiling itself is judged by ``tile_plan``."""
+    H, W = _integer(H, "H", 1 << 31, 1), _integer(W, "W", 1 << 31, 1)
+    (th, tw), (oy, ox) = _pair(tile, "tile", 1), _pair(overlap, "overlap", 0)
+    square = th == tw and oy == ox
+    if isinstance(views, str) and views == "auto":
+        views = "d4" if square else "flips"
+    codes = view_codes(1, 1, views)                           # (a 1 x 1 image is square: the list rules without the H == W clause)
+    for g in codes:
+        if g & 4 and not square:
+            raise ValueError(f"view code {g} transposes the image: with tiles, codes 4 .. 7 need a square tile and overlap "
+                             f"(got tile {th}x{tw}, overlap {oy}x{ox}; use views='flips')")
+    return codes
+
+
+def _unview_args(tiles, H, W, overlap, views):
+    """Shared by the two stand-alone calls: (src, codes, geometry) after every host-side rule."""
+    if isinstance(tiles, torch.Tensor) and tiles.dim() == 6:
+        th, tw = int(tiles.shape[4]), int(tiles.shape[5])
+        codes = view_codes_tiled(H, W, (th, tw), overlap, views)
+        if len(codes) != tiles.shape[0]:
+            raise ValueError(f"tiles holds {tiles.shape[0]} views, the view list {len(codes)}")
+    src = _tile_tensor(tiles, "tiles", 6)
+    G, B, K, Cc, th, tw = src.shape
+    plan = tile_plan(H, W, (th, tw), overlap)
+    if K != len(plan.origins_y) * len(plan.origins_x):
+        raise ValueError(f"tiles has {K} tiles per image; a {H}x{W} image with tile {th}x{tw} and overlap {plan.overlap} has "
+                         f"{len(plan.origins_y)} x {len(plan.origins_x)}")
+    return src, codes, plan
+
+
+@torch.no_grad()
+def tile_blend_unview_reduce(tiles: torch.Tensor, H: int, W: int, overlap=32, views="auto",
+                             return_samples: bool = False) -> Tuple[torch.Tensor, Optional[torch.Tensor], Optional[torch.Tensor]]:
+    """tiles [views, B, ny * nx, C, th, tw], view k's tiles in ITS frame (the tiling of the viewed image), of an H x W image ->
+    (mean, std, samples): per-pixel mean and unbiased std [B, C, H, W] over the views' blended images turned back into the image's
+    frame and, with ``return_samples``, those aligned members [B, views, C, H, W], in one kernel with the arithmetic of
+    ``denoise_tiled_self_ensemble`` (mi_tile_blend_unview_reduce: ``tile_blend`` per view in the view's frame, the un-view, then
+    ``ensemble_reduce``, bit for bit).  std is None for one view."""
+    src, codes, plan = _unview_args(tiles, H, W, overlap, views)
+    G, B, K, Cc, th, tw = src.shape
+    with torch.cuda.device(src.device):
+        mean = torch.empty((B, Cc, int(H), int(W)), dtype=torch.float32, device=src.device)
+        std = torch.empty_like(mean) if G >= 2 else None
+        samples = torch.empty((B, G, Cc, int(H), int(W)), dtype=torch.float32, device=src.device) if return_samples else None
+        native.check(native.lib().mi_tile_blend_unview_reduce(src.data_ptr(), B, Cc, int(H), int(W), th, tw, plan.overlap[0], plan.overlap[1],
+                                                              _views_arg(codes), G, mean.data_ptr(), None if std is None else std.data_ptr(),
+                                                              None if samples is None else samples.data_ptr(),
+                                                              torch.cuda.current_stream(src.device).cuda_stream))
+    return mean, std, samples
+
+
+@torch.no_grad()
+def tile_blend_unview_quantiles(tiles: torch.Tensor, H: int, W: int, overlap=32, views="auto", q=None) -> torch.Tensor:
+    """tiles as in ``tile_blend_unview_reduce`` -> the per-pixel quantile maps [B, nq, C, H, W] of the aligned blended members at the
+    levels ``q`` (mi_tile_blend_unview_quantiles: ``tile_blend`` per view, the un-view, then ``ensemble_quantiles``, bit for bit; the
+    members are never stored)."""
+    if q is None:
+        raise ValueError("tile_blend_unview_quantiles needs the quantile levels: q=(0.05, 0.5, 0.95), say")
+    levels = check_levels(q)
+    src, codes, plan = _unview_args(tiles, H, W, overlap, views)
+    G, B, K, Cc, th, tw = src.shape
+    with torch.cuda.device(src.device):
+        out = torch.empty((B, len(levels), Cc, int(H), int(W)), dtype=torch.float32, device=src.device)
+        native.check(native.lib().mi_tile_blend_unview_quantiles(src.data_ptr(), B, Cc, int(H), int(W), th, tw, plan.overlap[0], plan.overlap[1],
+                                                                 _views_arg(codes), G, _levels_arg(levels), len(levels), out.data_ptr(),
+                                                                 torch.cuda.current_stream(src.device).cuda_stream))
+    return out
+
+
 class DiffusionDenoiser:
     def __init__(self, model, noise_steps=50, beta_start=1e-4, beta_end=0.02):
         self.model = model
@@ -845,6 +945,70 @@ class DiffusionDenoiser:
         if levels is None:
             return SelfEnsembleResult(mean, std, samples, codes, seed)
         return SelfEnsembleQuantileResult(mean, std, samples, codes, seed, maps, levels)
+
+    @torch.no_grad()
+    def denoise_tiled_self_ensemble(self, noisy_img: torch.Tensor, inference_steps: int = 25, views="auto", tile=256, overlap=32,
+                                    max_batch: int = 16, seed: Optional[int] = None, sample_offset: int = 0, member_offset: int = 0,
+                                    return_samples: bool = False, return_tiles: bool = False, quantiles=None, *,
+                                    update: str = "reference", eta: float = 0.0, clip_x0: bool = True):
+        """``denoise_self_ensemble`` for images of ANY size >= the tile, for BOTH variants: the flip / rotate views of every image,
+        each denoised as blended overlapping tiles, turned back, and their per-pixel mean and unbiased standard deviation at the
+        image's own resolution, in one native call (not a reference call; include/midd.h: mi_denoise_tiled_self_ensemble).  It is
+        the ensemble a deterministic (DDIM) model has for a full-resolution image.
+
+        ``views`` (``view_codes_tiled``): ``"auto"`` is all 8 flips and rotations when ``tile`` and ``overlap`` are square --
+        whatever H and W: a transposed image is still cut into tiles -- and the 4 flips otherwise; ``"flips"``, ``"d4"`` or a
+        sequence of 1 to 8 distinct codes.  A view's tiles are the tiles of the VIEWED image (a transposing view uses the (W, H)
+        plan, ``tile_plan(W, H, tile, overlap)``), so member k is ``unview(denoise_tiled(view(x, g_k)).image, g_k)`` at the same
+        ``max_batch``, bit for bit.  Views run one after the other; inside a view the B * tiles crops run as batches of at most
+        ``max_batch`` (a batch never mixes views).  ``mean`` and ``std`` are ``ensemble_reduce`` of the members in list order,
+        computed by one kernel that never stores them unless ``return_samples=True`` (``samples``: [B, views, C, H, W]).
+        ``tiles`` ([views, B, ny * nx, C, th, tw], ``return_tiles=True``): ``tiles[k]`` is ``denoise_tiled(view(x, g_k),
+        return_tiles=True).tiles``, in view k's frame.  ``origins_y`` / ``origins_x`` are those of the un-transposed frame.
+        ``std`` is None for one view.
+
+        DDIM: ``seed`` must be None; the result's ``seed`` is None.  cddpm: always seeded -- view k draws the member word
+        ``member_offset + k`` at the pixel's place in the whole VIEWED image, i.e. member k is the single sample of
+        ``denoise_tiled_ensemble(view(x), members=1, seed=seed, member_offset=member_offset + k)`` turned back; ``views=[0]`` is
+        ``denoise_tiled(x, seed=seed)``.  ``seed=None`` draws a 64-bit seed and returns it.
+
+        ``update="ddim"`` (see ``denoise_tiled``): every tile of every view runs the DDIM(eta) update; ``eta=0`` is deterministic
+        for both variants (a ``seed`` is ignored, the result's is None), ``eta > 0`` is seeded as cddpm is above, for BOTH
+        variants.  ``update="dpmpp2m"`` is not built for this call and raises ValueError.
+
+        ``quantiles`` (a sequence of at most 8 levels in [0, 1]): the call also returns the per-pixel quantile maps of the aligned
+        blended members as a ``TiledSelfEnsembleQuantileResult``: the fields above, then ``quantiles`` [B, nq, C, H, W] and
+        ``levels``.  The tiles are written to a tensor of the call's own instead of the workspace and one
+        ``tile_blend_unview_quantiles`` launch follows on the same stream; the other fields are the bits of the call without it.
+
+        Not built: a session ticket (``submit_...``) and a service switch for this call."""
+        rule = check_update(update, eta, clip_x0)
+        if rule is not None and rule.kind == native.MI_UPDATE["dpmpp2m"]:
+            raise ValueError("denoise_tiled_self_ensemble runs the reference's update or update='ddim': update='dpmpp2m' is not built "
+                             "for it (the native call takes no history buffer; denoise and denoise_tiled run it)")
+        levels = None if quantiles is None else check_levels(quantiles)
+        stochastic = getattr(self.model, "variant", "ddim") == "cddpm"
+        draws = stochastic if rule is None else rule.eta > 0.0
+        if rule is None and not stochastic and seed is not None:
+            raise ValueError("seed selects the step noise of the stochastic (cddpm) variant: the DDIM variant takes seed=None")
+        if isinstance(noisy_img, torch.Tensor) and noisy_img.dim() == 4:
+            views = view_codes_tiled(noisy_img.shape[2], noisy_img.shape[3], tile, overlap, views)      # (before any GPU work)
+        if draws:
+            seed, sample_offset = check_seed(self._draw_seed() if seed is None else seed, sample_offset)
+        else:
+            seed = None
+        self.model.eval()
+        steps = timestep_list(self.noise_steps, inference_steps)
+        rule_kw = {} if rule is None else dict(update=update, eta=eta, clip_x0=clip_x0)
+        mean, std, samples, tiles, codes, plan = self.model.run_tiled_self_ensemble(
+            noisy_img, steps, self.beta, self.alpha, self.alpha_hat, clamp_eps=not stochastic, tile=tile, overlap=overlap, views=views,
+            seed=seed, sample_offset=sample_offset, member_offset=member_offset, max_batch=max_batch, want_samples=return_samples,
+            want_tiles=return_tiles or levels is not None, **rule_kw)
+        if levels is None:
+            return TiledSelfEnsembleResult(mean, std, samples, tiles, codes, plan.origins_y, plan.origins_x, seed)
+        maps = tile_blend_unview_quantiles(tiles, noisy_img.shape[2], noisy_img.shape[3], plan.overlap, codes, levels)
+        return TiledSelfEnsembleQuantileResult(mean, std, samples, tiles if return_tiles else None, codes, plan.origins_y, plan.origins_x,
+                                               seed, maps, levels)
 
     def _draw_seed(self) -> int:
         hi, lo = torch.randint(0, 1 << 32, (2,), dtype=torch.int64).tolist()

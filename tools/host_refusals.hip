@@ -207,6 +207,24 @@ int main() {
     REFUSED(mi_dihedral_quantiles(A, 2, 1, 32, 32, v_ok, 2, q_bad, 2, B_, nullptr));
     REFUSED(mi_dihedral_quantiles(A, 2, 1, 32, 32, v_ok, 2, q_ok, 2, nullptr, nullptr));
 
+    const int32_t v_d4[8] = {0, 1, 2, 3, 4, 5, 6, 7};
+    REFUSED(mi_tile_blend_unview_reduce(A, 2, 0, 90, 70, 32, 32, 8, 8, v_ok, 2, B_, C_, D, nullptr));
+    REFUSED(mi_tile_blend_unview_reduce(A, 2, 1, 90, 70, 32, 32, 17, 8, v_ok, 2, B_, C_, D, nullptr));
+    REFUSED(mi_tile_blend_unview_reduce(A, 2, 1, 90, 70, 32, 32, 8, 8, v_ok, 0, B_, C_, D, nullptr));
+    REFUSED(mi_tile_blend_unview_reduce(A, 2, 1, 90, 70, 32, 32, 8, 8, nullptr, 2, B_, C_, D, nullptr));
+    REFUSED(mi_tile_blend_unview_reduce(A, 2, 1, 90, 70, 32, 32, 8, 8, v_rep, 2, B_, C_, D, nullptr));
+    REFUSED(mi_tile_blend_unview_reduce(A, 2, 1, 90, 70, 32, 32, 8, 8, v_code, 2, B_, C_, D, nullptr));
+    REFUSED(mi_tile_blend_unview_reduce(A, 2, 1, 90, 70, 32, 64, 8, 8, v_t, 2, B_, C_, D, nullptr));
+    REFUSED(mi_tile_blend_unview_reduce(A, 2, 1, 90, 70, 32, 32, 8, 4, v_d4, 8, B_, C_, D, nullptr));
+    REFUSED(mi_tile_blend_unview_reduce(A, 65536, 1, 64, 64, 32, 32, 0, 0, v_ok, 2, B_, C_, D, nullptr));
+    REFUSED(mi_tile_blend_unview_reduce(A, 2, 1, 90, 70, 32, 32, 8, 8, v_d4, 8, nullptr, nullptr, nullptr, nullptr));
+    REFUSED(mi_tile_blend_unview_reduce(A, 2, 1, 90, 70, 32, 32, 8, 8, v_t + 1, 1, B_, C_, D, nullptr));
+    REFUSED(mi_tile_blend_unview_reduce(nullptr, 2, 1, 90, 70, 32, 32, 8, 8, v_d4, 8, B_, C_, D, nullptr));
+    REFUSED(mi_tile_blend_unview_quantiles(A, 2, 1, 90, 70, 32, 64, 8, 8, v_t, 2, q_ok, 2, B_, nullptr));
+    REFUSED(mi_tile_blend_unview_quantiles(A, 2, 1, 90, 70, 32, 32, 8, 8, v_d4, 8, q_bad, 2, B_, nullptr));
+    REFUSED(mi_tile_blend_unview_quantiles(A, 2, 1, 90, 70, 32, 32, 8, 8, v_d4, 8, q_ok, 9, B_, nullptr));
+    REFUSED(mi_tile_blend_unview_quantiles(A, 2, 1, 90, 70, 32, 32, 8, 8, v_d4, 8, q_ok, 2, nullptr, nullptr));
+
     // ---- midd_batched.hip: the four batched calls and their rule / dpm forms
     REFUSED(mi_denoise_ensemble(nullptr, A, B_, C_, nullptr, 2, 4, 32, 32, t3, 3, tab, tab, ah, 50, 5, 0, 0, 16, 0, WS, WSB, nullptr));
     REFUSED(mi_denoise_ensemble(p, A, B_, C_, nullptr, 2, 0, 32, 32, t3, 3, tab, tab, ah, 50, 5, 0, 0, 16, 0, WS, WSB, nullptr));
@@ -251,6 +269,27 @@ int main() {
     REFUSED(mi_denoise_self_ensemble(p, A, B_, C_, nullptr, 2, 32, 32, v_ok, 1, t3, 3, tab, tab, ah, 50, 1, 5, 0, 0, 16, 0, WS, WSB, nullptr));
     REFUSED(mi_denoise_self_ensemble(p, A, A + 8, C_, nullptr, 2, 32, 32, v_ok, 2, t3, 3, tab, tab, ah, 50, 1, 5, 0, 0, 16, 0, WS, WSB, nullptr));
     REFUSED(mi_denoise_self_ensemble(p, A, B_, C_, D, 2, 32, 32, v_ok, 2, t3, 3, tab, tab, ah, 50, 1, 5, 0, 0, 16, 0, WS, WSB, nullptr));
+    // the tiled self-ensemble: the rule, the view list, the transposing rule, then the tiled ensemble's rules with members = n_views
+    REFUSED(mi_denoise_tiled_self_ensemble(p, A, B_, C_, nullptr, nullptr, 2, 90, 70, 32, 32, 8, 8, v_d4, 8, t3, 3, tab, tab, ah, 50, 1, 5, 0, 0, 16, 0, &dpm, WS, WSB, nullptr));
+    REFUSED(mi_denoise_tiled_self_ensemble(p, A, B_, C_, nullptr, nullptr, 2, 90, 70, 32, 32, 8, 8, v_d4, 8, t3, 3, tab, tab, ah, 50, 1, 5, 0, 0, 16, 0, &eta_bad, WS, WSB, nullptr));
+    REFUSED(mi_denoise_tiled_self_ensemble(p, A, B_, C_, nullptr, nullptr, 2, 90, 70, 32, 32, 8, 8, v_d4, 8, t_up, 3, tab, tab, ah, 50, 1, 5, 0, 0, 16, 0, &ddim, WS, WSB, nullptr));
+    REFUSED(mi_denoise_tiled_self_ensemble(nullptr, A, B_, C_, nullptr, nullptr, 2, 90, 70, 32, 32, 8, 8, v_d4, 8, t3, 3, tab, tab, ah, 50, 1, 5, 0, 0, 16, 0, nullptr, WS, WSB, nullptr));
+    REFUSED(mi_denoise_tiled_self_ensemble(p, A, B_, C_, nullptr, nullptr, 2, 90, 70, 32, 32, 8, 8, v_d4, 9, t3, 3, tab, tab, ah, 50, 1, 5, 0, 0, 16, 0, nullptr, WS, WSB, nullptr));
+    REFUSED(mi_denoise_tiled_self_ensemble(p, A, B_, C_, nullptr, nullptr, 2, 90, 70, 32, 32, 8, 8, nullptr, 2, t3, 3, tab, tab, ah, 50, 1, 5, 0, 0, 16, 0, nullptr, WS, WSB, nullptr));
+    REFUSED(mi_denoise_tiled_self_ensemble(p, A, B_, C_, nullptr, nullptr, 2, 90, 70, 32, 32, 8, 8, v_rep, 2, t3, 3, tab, tab, ah, 50, 1, 5, 0, 0, 16, 0, nullptr, WS, WSB, nullptr));
+    REFUSED(mi_denoise_tiled_self_ensemble(p, A, B_, C_, nullptr, nullptr, 2, 90, 70, 32, 32, 8, 8, v_code, 2, t3, 3, tab, tab, ah, 50, 1, 5, 0, 0, 16, 0, nullptr, WS, WSB, nullptr));
+    REFUSED(mi_denoise_tiled_self_ensemble(p, A, B_, C_, nullptr, nullptr, 2, 90, 70, 32, 64, 8, 8, v_t, 2, t3, 3, tab, tab, ah, 50, 1, 5, 0, 0, 16, 0, nullptr, WS, WSB, nullptr));
+    REFUSED(mi_denoise_tiled_self_ensemble(p, A, B_, C_, nullptr, nullptr, 2, 90, 70, 32, 32, 8, 4, v_t, 2, t3, 3, tab, tab, ah, 50, 1, 5, 0, 0, 16, 0, nullptr, WS, WSB, nullptr));
+    REFUSED(mi_denoise_tiled_self_ensemble(p, A, B_, C_, nullptr, nullptr, 2, 90, 70, 36, 36, 8, 8, v_d4, 8, t3, 3, tab, tab, ah, 50, 1, 5, 0, 0, 16, 0, nullptr, WS, WSB, nullptr));
+    REFUSED(mi_denoise_tiled_self_ensemble(p, A, B_, C_, nullptr, nullptr, 2, 90, 70, 32, 32, 8, 8, v_d4, 8, t3, 3, tab, tab, ah, 50, 1, 5, -2, 0, 16, 0, nullptr, WS, WSB, nullptr));
+    REFUSED(mi_denoise_tiled_self_ensemble(p, A, B_, C_, nullptr, nullptr, 2, 90, 70, 32, 32, 8, 8, v_d4, 8, t3, 3, tab, tab, ah, 50, 1, 5, 0, ((int64_t)1 << 32) - 7, 16, 0, nullptr, WS, WSB, nullptr));
+    REFUSED(mi_denoise_tiled_self_ensemble(p, A, B_, C_, nullptr, nullptr, 2, 90, 70, 32, 32, 8, 8, v_d4, 8, t3, 3, tab, tab, ah, 50, 1, 5, 0, 0, 0, 0, nullptr, WS, WSB, nullptr));
+    REFUSED(mi_denoise_tiled_self_ensemble(p, A, B_, C_, nullptr, nullptr, 1 << 28, 64, 64, 32, 32, 0, 0, v_d4, 8, t3, 3, tab, tab, ah, 50, 1, 5, 0, 0, 16, 0, nullptr, WS, WSB, nullptr));
+    REFUSED(mi_denoise_tiled_self_ensemble(p, A, B_, C_, nullptr, nullptr, 65536, 64, 64, 32, 32, 0, 0, v_ok, 2, t3, 3, tab, tab, ah, 50, 1, 5, 0, 0, 16, 0, nullptr, WS, WSB, nullptr));
+    REFUSED(mi_denoise_tiled_self_ensemble(p, A, nullptr, nullptr, nullptr, nullptr, 2, 90, 70, 32, 32, 8, 8, v_d4, 8, t3, 3, tab, tab, ah, 50, 1, 5, 0, 0, 16, 0, nullptr, WS, WSB, nullptr));
+    REFUSED(mi_denoise_tiled_self_ensemble(p, A, B_, C_, nullptr, nullptr, 2, 90, 70, 32, 32, 8, 8, v_t + 1, 1, t3, 3, tab, tab, ah, 50, 1, 5, 0, 0, 16, 0, nullptr, WS, WSB, nullptr));
+    REFUSED(mi_denoise_tiled_self_ensemble(p, A, B_, C_, D, D + 8, 2, 90, 70, 32, 32, 8, 8, v_d4, 8, t3, 3, tab, tab, ah, 50, 1, 5, 0, 0, 16, 0, nullptr, WS, WSB, nullptr));
+    REFUSED(mi_denoise_tiled_self_ensemble(p, A, B_, C_, D, E, 2, 41, 27, 16, 16, 4, 4, v_d4, 8, t3, 3, tab, tab, ah, 50, 1, 5, 0, 0, 16, 0, &ddim, WS, WSB, nullptr));      // valid, all 8 views of a non-square image: the state check
 
     mi_plan_destroy(p);
     printf("%d calls, %d unexpected\n", n_calls, bad);
