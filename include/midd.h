@@ -817,6 +817,95 @@ typedef struct mi_profile_entry {
 int mi_profile_begin(mi_plan* plan);
 int mi_profile_end(mi_plan* plan, mi_profile_entry* out, int max_entries, int* n_entries);
 
+/* ---- THE TRAINING OBJECTIVE AS AN EVALUATION: how well a checkpoint fits a (clean, noisy) pair at a timestep ----------------------
+ * The reference trains on: draw t, noise the clean image to x_t (DiffusionDenoiser.noise_images, DDIMModel.py:259-263), predict the
+ * noise with one forward, and compare (DDIMModel.py:351-375; cddpmModels.py:367-374).  These calls evaluate that number -- per sample,
+ * no gradients -- so that a loss-per-timestep curve of a checkpoint needs no sampler run.
+ *
+ * THE FORWARD NOISE (fixed).  z is the standard normal of the generator specified at mi_denoise_seeded: the same Philox4x32-10 call,
+ * the same u1 and u2, the same line  z = sqrtf(-2 * logf(u1)) * cospif(2 * u2), every product rounded once.  There is NO 0.5 factor:
+ * eps = z.  The counter words are
+ *   c0 = element index inside the sample's [C,H,W] block, c * H*W + y * W + x   (C*H*W < 2^32)
+ *   c1 = low 32 bits of sample_offset + b      (the global image index, as there)
+ *   c2 = 0x80000000 | draw,  0 <= draw < 2^31  (a caller numbers the noise draws of one image 0, 1, 2, ...)
+ *   c3 = 0                                      key k0, k1 = low, high word of seed
+ * A sampler iteration index never has the top bit of c2 set (the slot path refuses iter_base + n_rows > 2^31 - 1; the uniform calls
+ * count from 0), so no forward-noise value is a step-noise value of the same seed.
+ *
+ * THE NOISING (fixed).  Per sample b, on the host in fp32, in the reference's order:
+ *   a_b = sqrtf(alpha_hat[t_b])        s_b = sqrtf(1.0f - alpha_hat[t_b])
+ * They reach the device, with the counter words c1 and c2, as kernel arguments (records of 16 bytes a sample, at most 32 a launch): the host tables are not read after
+ * the call returns.  Device, per element, fp32:  x_t = a*x + s*eps  -- two products and one sum, each rounded once, no fused
+ * multiply-add: the bit pattern of the reference's expression in torch eager on a CPU.
+ *
+ * THE DENOISING LOSS (fixed).  Per sample b, per element, fp32, every operation rounded to nearest on its own, no fused multiply-add;
+ * min / max here are torch.clamp's: a NaN stays a NaN.
+ *   e = flags & MI_CLAMP_EPS ? min(max(eps_pred, -5), 5) : eps_pred
+ *   d = e - eps          q = d*d
+ *   p = min(max((x_t - s*e) / a, 0), 1)                 (IEEE division: the predicted clean image)
+ *   Sobel cross-correlation of p and of clean, per channel, zero outside the image; with u[i][j] the 3 x 3 neighbourhood (i the row),
+ *   the six non-zero taps of each kernel in row-major order, summed left to right:
+ *     ex = -u00 + u02 - 2*u10 + 2*u12 - u20 + u22           (kernel [[-1,0,1],[-2,0,2],[-1,0,1]], DDIMModel.py:324)
+ *     ey = -u00 - 2*u01 - u02 + u20 + 2*u21 + u22           (its transpose, DDIMModel.py:325)
+ *   m(u) = sqrtf(ex*ex + ey*ey + 1e-8f)   ((ex*ex + ey*ey) first, then the constant; IEEE square root)
+ *   g = |m(p) - m(clean)|
+ * The sums are in double, every addition rounded on its own, no atomics, in ONE order:
+ *   - a channel plane is cut into 32 x 32 patches from its top-left corner (the last ones partial); pixels outside add nothing;
+ *   - inside a patch, lane j = 0 .. 255 owns column j % 32 of rows j / 32 + 8 k, k = 0, 1, 2, 3, and adds its pixels in that order
+ *     starting from 0; the 256 lane sums are then folded by the tree  for off = 128, 64, .., 1: v[j] += v[j + off]  for j < off;
+ *   - a sample's patch sums are added one by one, starting from 0, in (channel, patch row, patch column) order.
+ *   mse_b = sum(q) / (double)(C*H*W)     edge_b = sum(g) / (double)(C*H*W)     loss_b = mse_b + edge_weight * edge_b   (double)
+ * The reference's scalars are the means of these over the batch (F.mse_loss, F.l1_loss); its DDIM objective is MI_CLAMP_EPS with
+ * edge_weight = 0.2, its cddpm objective no clamp and the plain MSE (edge_weight = 0; the edge term is still reported).  The host
+ * shims default to those.  tests/denoising_loss_reference.py restates the three specifications in numpy.
+ *
+ * Arguments the calls share
+ *   clean        device fp32 [B,C,H,W]
+ *   t            HOST int32 [B], each in [0, noise_steps);  alpha_hat  HOST fp32 [noise_steps]
+ *   eps / seeded the noise source, exactly one: eps device fp32 [B,C,H,W] (the caller's tensor), or seeded != 0 with seed,
+ *                sample_offset (>= 0) and draw: the forward noise above, drawn on the device
+ *   sample_index, draws   HOST int64 [B] or NULL, seeded only: per-sample counter words in the place of sample_offset + b and of draw
+ *                (sample_index[b] >= 0, 0 <= draws[b] < 2^31), so that one call can hold any set of (image, draw) pairs -- a loss
+ *                profile runs image b at its k-th timestep as (sample_offset + b, draw k) whatever shares the pass
+ *   out          device double [B][3] = (mse, edge, loss), 8-byte aligned
+ *   maps         device fp32 [3][B,C,H,W] or NULL: the per-pixel q, g and p
+ *   flags        MI_CLAMP_EPS or 0;  edge_weight: any number but NaN
+ * MI_EINVAL before any GPU work, the rule named in mi_last_error: a null argument; a size below 1, C > 65535, H or W > 2^30; a timestep outside
+ * [0, noise_steps); a draw outside [0, 2^31); a negative sample_offset or sample_index; C*H*W >= 2^32; both a seed and eps; neither
+ * a seed nor eps; sample_index or draws without a seed; a tensor that is not 4-byte aligned.  All calls allocate nothing and are asynchronous on `stream`.
+ *
+ * mi_noise_images (no plan needed): x_t device fp32 [B,C,H,W] <- THE NOISING of clean with eps or with the seeded draw; eps_out
+ *   (device fp32 [B,C,H,W] or NULL, seeded only) receives the drawn eps.  Tensors that share their offset from a 16-byte boundary
+ *   move as 16-byte words with a scalar head and tail per sample, others element by element: the same bits either way.
+ * mi_loss_terms (no plan needed): THE DENOISING LOSS of a given eps_pred.  Explicit form: x_t and eps given.  Seeded form: x_t and eps
+ *   NULL; z and x_t are formed again from the seed -- the same bits as the explicit form on what mi_noise_images exports.
+ *   workspace: mi_loss_workspace_bytes (the patch sums), 8-byte aligned; 0 from the query on sizes the call refuses.
+ * mi_denoising_loss: one enqueue, no host synchronisation: mi_noise_images into the workspace, the unchanged forward of
+ *   mi_unet_forward at the per-sample t with condition cond (device fp32 [B,C,H,W]; C is the plan's in_channels), then mi_loss_terms
+ *   on the same stream -- bit for bit those three calls one after another.  workspace: mi_denoising_loss_workspace_bytes = the
+ *   workspace of the forward's one program (at most mi_workspace_bytes) plus the call's own region (x_t, eps_pred and the patch
+ *   sums), 256-byte aligned; the status word is cleared by
+ *   the call and read with mi_status as after every other call.  Further refusals: the plan's state, the workspace, a timestep
+ *   outside the plan's time table, the device. */
+int mi_noise_images(const float* clean, const int32_t* t, const float* alpha_hat, int noise_steps,
+                    const float* eps, int seeded, uint64_t seed, int64_t sample_offset, int64_t draw,
+                    const int64_t* sample_index, const int64_t* draws,
+                    float* x_t, float* eps_out, int B, int C, int H, int W, void* stream);
+size_t mi_loss_workspace_bytes(int B, int C, int H, int W);
+int mi_loss_terms(const float* clean, const float* x_t, const float* eps, const float* eps_pred,
+                  const int32_t* t, const float* alpha_hat, int noise_steps,
+                  int seeded, uint64_t seed, int64_t sample_offset, int64_t draw,
+                  const int64_t* sample_index, const int64_t* draws, int flags, double edge_weight,
+                  double* out, float* maps, int B, int C, int H, int W,
+                  void* workspace, size_t workspace_bytes, void* stream);
+size_t mi_denoising_loss_workspace_bytes(mi_plan* plan, int B, int H, int W);
+int mi_denoising_loss(mi_plan* plan, const float* clean, const float* cond, const int32_t* t,
+                      const float* alpha_hat, int noise_steps,
+                      const float* eps, int seeded, uint64_t seed, int64_t sample_offset, int64_t draw,
+                      const int64_t* sample_index, const int64_t* draws, int flags, double edge_weight,
+                      double* out, float* maps, int B, int H, int W,
+                      void* workspace, size_t workspace_bytes, void* stream);
+
 void mi_plan_destroy(mi_plan* plan);
 
 /* ---- pre/post-processing either side of the sampler, on the device (no plan needed) -----------------------

@@ -12,6 +12,7 @@ img_size -> sampler -> uint8 -> bicubic resize back -> PNG, with the reference's
                            [--self-ensemble [auto|flips|d4] [--std-out std.npy] [--quantiles Q,Q --quantiles-out q.npy]]
                            [--update reference|ddim|dpmpp2m [--eta F] [--no-clip-x0] [--x0-out traj.npy]]
                            [--bit-depth 8|16 [--window P_LO,P_HI | --window-levels LO,HI]]
+                           [--clean clean.png [--loss-out loss.json]]
 
 Without a checkpoint (the trained weights are not distributed with the reference) the network is
 random-init, which exercises the path but does not denoise.  The reference helper has a latent
@@ -42,7 +43,7 @@ def denoise_image_diffusion(model_path: Optional[str], test_image_path: str, dev
                             self_ensemble: Optional[str] = None, update: str = "reference", eta: float = 0.0,
                             clip_x0: bool = True, x0_out: Optional[str] = None, bit_depth: int = 8, window: Optional[Sequence[float]] = None,
                             window_levels: Optional[Sequence[int]] = None, views: Optional[str] = None,
-                            members: Optional[int] = None) -> Image.Image:
+                            members: Optional[int] = None, clean: Optional[str] = None, loss_out: Optional[str] = None) -> Image.Image:
     """compute (not a reference argument): arithmetic of the network, see UNetDiffusion -- None keeps the default.
     seed (not a reference argument; cddpm): the stochastic sampler's noise is drawn on the device from this seed, so the same
     call gives the same image again (DiffusionDenoiser.denoise); None: torch.randn, as the reference.
@@ -79,7 +80,23 @@ def denoise_image_diffusion(model_path: Optional[str], test_image_path: str, dev
     (p_lo, p_hi) whose levels are read off the image's histogram ((0, 100): its minimum and maximum), window_levels the two levels
     themselves.  The recipe is decode, histogram, levels, windowed load (+ resize), the sampler call of any kind, (resize +) windowed
     store; values outside the window come back as lo or hi (the window clips).  With samples / self_ensemble the mean is stored through
-    the window; std_out and quantiles_out stay float, in window units: one unit is hi - lo grey levels.  The levels are printed."""
+    the window; std_out and quantiles_out stay float, in window units: one unit is hi - lo grey levels.  The levels are printed.
+    clean, loss_out (not reference arguments; both variants): EVALUATION.  clean is the path of the clean counterpart of the image; it
+    is loaded by the same recipe (bit_depth, the resize to img_size, and the noisy image's window if there is one).  The call prints the
+    checkpoint's training objective on the pair at every timestep (DiffusionDenoiser.loss_profile; seed: the forward noise's, drawn
+    and printed when None) and the PSNR / SSIM of the ordinary sampler run against the clean image (prepost.compute_metrics); loss_out
+    is the path of a .json file that receives both.  The sampler run and the returned image are those of the call without clean.
+    Not together with tile, samples, views, members or self_ensemble, and on a GPU only."""
+    if loss_out is not None and clean is None:
+        raise ValueError("--loss-out needs --clean PATH (the evaluation's clean image)")
+    if clean is not None:
+        for flag, given in (("--tile", tile), ("--samples", samples), ("--views", views), ("--members", members), ("--self-ensemble", self_ensemble)):
+            if given is not None:
+                raise ValueError(f"--clean (evaluation) cannot be combined with {flag}: the loss is taken on the resized image, one sampler run")
+        if step_noise is not None or x0_out is not None:
+            raise ValueError("--clean (evaluation) cannot be combined with a step_noise tensor or --x0-out")
+        if torch.device(device_type).type != "cuda":      # (before the sampler run, not after it)
+            raise RuntimeError("--clean (evaluation) runs only on a ROCm GPU: the loss kernels have no CPU fallback")
     bit_depth = image16.check_bit_depth(bit_depth)
     if window is not None and window_levels is not None:
         raise ValueError("--window and --window-levels cannot be combined: percentiles or absolute levels, not both")
@@ -264,6 +281,8 @@ def denoise_image_diffusion(model_path: Optional[str], test_image_path: str, dev
     if device.type == "cuda":
         torch.cuda.synchronize(device)
     print(f"Inference time: {time.time() - start_time:.2f} seconds")
+    if clean is not None:
+        evaluate(diffusion, clean, input_tensor, denoised, img_size, bit_depth, win, seed, loss_out)
 
     if win is not None:
         plane = denoised.reshape(img_size, img_size).float()
@@ -286,6 +305,43 @@ def denoise_image_diffusion(model_path: Optional[str], test_image_path: str, dev
     output_np = denoised.squeeze().cpu().numpy()
     output_img = Image.fromarray((output_np * 255).astype(np.uint8), mode="L")
     return output_img.resize(img.size, Image.BICUBIC)
+
+
+def evaluate(diffusion: DiffusionDenoiser, clean_path: str, noisy: torch.Tensor, denoised: torch.Tensor, img_size: int, bit_depth: int,
+             win, seed: Optional[int], loss_out: Optional[str]) -> dict:
+    """--clean: the loss profile of the (clean, noisy) pair over all timesteps and the PSNR / SSIM of `denoised` against the clean
+    image, printed and, with loss_out, written as JSON.  The clean image goes through the recipe the noisy one went through; a
+    window's levels are the noisy image's."""
+    import json
+
+    from . import prepost
+    device = noisy.device
+    img = Image.open(clean_path)
+    raw16 = image16.decode16(img) if bit_depth == 16 else None
+    if win is not None:
+        dev16 = torch.from_numpy(image16.need_u16(raw16, img.mode)).to(device)
+        clean = prepost.resize_bicubic_f32(dev16, (img_size, img_size), clamp=True, levels=win)[None, None]
+    elif raw16 is not None:
+        clean = prepost.resize_bicubic_f32(torch.from_numpy(raw16).to(device), (img_size, img_size), clamp=True)[None, None]
+    else:
+        raw = torch.from_numpy(np.asarray(img.convert("L"), np.uint8).copy()).to(device)
+        clean = prepost.to_unit_float(prepost.resize_bicubic_u8(raw, (img_size, img_size)))[None, None]
+    prof = diffusion.loss_profile(clean, noisy, seed=seed)
+    psnr, ssim = prepost.compute_metrics(denoised.reshape(1, 1, img_size, img_size).float(), clean)
+    variant = getattr(diffusion.model, "variant", "ddim")
+    result = {"variant": variant, "noise_steps": diffusion.noise_steps, "img_size": img_size, "t": list(prof.t),
+              "loss": prof.loss[:, 0].tolist(), "mse": prof.mse[:, 0].tolist(), "edge": prof.edge[:, 0].tolist(),
+              "psnr": float(psnr), "ssim": float(ssim)}
+    print(f"Denoising loss of the checkpoint on this pair ({variant} objective), per timestep:")
+    print("    t        loss         mse        edge")
+    for k, t in enumerate(prof.t):
+        print(f"  {t:3d}  {result['loss'][k]:10.6f}  {result['mse'][k]:10.6f}  {result['edge'][k]:10.6f}")
+    print(f"Sampler run against the clean image: PSNR {psnr:.2f} dB | SSIM {ssim:.4f}")
+    if loss_out is not None:
+        with open(loss_out, "w") as f:
+            json.dump(result, f, indent=1)
+        print(f"Loss profile saved: {loss_out}")
+    return result
 
 
 def main(argv=None) -> None:
@@ -335,7 +391,18 @@ def main(argv=None) -> None:
                          "range.  --std-out and --quantiles-out stay float in window units: one unit is hi - lo grey levels")
     ap.add_argument("--window-levels", default=None, metavar="LO,HI",
                     help="as --window, with the two grey levels given (0 <= LO < HI <= 65535) instead of read off the histogram")
+    ap.add_argument("--clean", default=None, metavar="PATH",
+                    help="evaluation: the clean counterpart of --image; prints the checkpoint's denoising loss on the pair at every timestep "
+                         "and the PSNR / SSIM of the sampler run against it (not with --tile, --samples, --views, --members, --self-ensemble)")
+    ap.add_argument("--loss-out", default=None, metavar="PATH.json", help="with --clean: write the loss profile and the metrics as JSON")
     args = ap.parse_args(argv)
+    if args.loss_out is not None and args.clean is None:
+        ap.error("--loss-out needs --clean PATH")
+    if args.clean is not None:
+        for flag, given in (("--tile", args.tile), ("--samples", args.samples), ("--views", args.views), ("--members", args.members),
+                            ("--self-ensemble", args.self_ensemble), ("--x0-out", args.x0_out)):
+            if given is not None:
+                ap.error(f"--clean (evaluation) cannot be combined with {flag}")
     if args.update == "reference" and (args.eta != 0.0 or args.no_clip_x0):
         ap.error("--eta and --no-clip-x0 need --update ddim")
     if not 0.0 <= args.eta <= 1.0:
@@ -400,7 +467,8 @@ def main(argv=None) -> None:
                                        bit_depth=args.bit_depth, **({} if window is None else {"window": window}),
                                        **({} if window_levels is None else {"window_levels": window_levels}),
                                        **({} if args.views is None else {"views": args.views}),
-                                       **({} if args.members is None else {"members": args.members}))
+                                       **({} if args.members is None else {"members": args.members}),
+                                       **({} if args.clean is None else {"clean": args.clean, "loss_out": args.loss_out}))
     restored.save(args.out, quality=95)
     print(f"\nResult saved: {args.out}")
 

@@ -333,6 +333,26 @@ const char* out_conv_symbol(const OutUpdate& u, int seeded);
 // dst [n_iters][B][chw] <- the 0.5-scaled seeded step noise of `member` (step_noise_common.h); chw < 2^32, B and n_iters <= 65535
 hipError_t step_noise_fill_launch(float* dst, int n_iters, int B, unsigned long long chw, unsigned long long seed, long long sample_offset,
                                   unsigned member, hipStream_t s);
+// The training objective as an evaluation (diffusion_loss.hip; include/midd.h: THE FORWARD NOISE, THE NOISING, THE DENOISING LOSS).
+// A sample's record: a = sqrtf(alpha_hat[t]), s = sqrtf(1 - alpha_hat[t]) (host, fp32) and the counter words c1 and c2 (without the top bit) of its forward noise.
+// The records of up to LOSS_RECS_PER_LAUNCH consecutive samples travel as kernel arguments: a larger batch takes several launches.
+struct alignas(16) LossRec { float a, s; uint32_t sample; uint32_t draw; };
+constexpr int LOSS_RECS_PER_LAUNCH = 32;
+struct LossRecs { LossRec v[LOSS_RECS_PER_LAUNCH]; };      // 512 bytes of kernel arguments
+constexpr int LOSS_PATCH = 32;                             // a workgroup of the loss kernel owns a LOSS_PATCH x LOSS_PATCH patch of one channel
+constexpr int LOSS_MAX_SIDE = 1 << 30;                     // H, W of the loss calls: (H + 31) stays inside an int; C*H*W < 2^32 bounds the patch count
+inline int loss_tiles(int H, int W) { return ((H + LOSS_PATCH - 1) / LOSS_PATCH) * ((W + LOSS_PATCH - 1) / LOSS_PATCH); }
+// x_t [B][chw] <- a * clean + s * eps, eps read (eps != null) or drawn (seeded; then eps_out, if given, receives it); recs [B] HOST
+hipError_t noise_images_launch(const float* clean, const float* eps, float* x_t, float* eps_out, const LossRec* recs, int B,
+                               unsigned long long chw, int seeded, unsigned long long seed, hipStream_t s);
+// bytes of the partial sums of loss_terms_launch: double [B][C][tiles][2]
+size_t loss_partials_bytes(int B, int C, int H, int W);
+// out double [B][3] <- (mse, edge, mse + edge_weight * edge); maps (or null) float [3][B][C][H][W] <- q, g, p.  Explicit form: x_t and
+// eps given; seeded form: both null, z and x_t are formed again from (seed, recs[b].sample, recs[b].draw).  part: loss_partials_bytes
+hipError_t loss_terms_launch(const float* clean, const float* x_t, const float* eps, const float* eps_pred, const LossRec* recs,
+                             int B, int C, int H, int W, int seeded, unsigned long long seed, int clamp_eps,
+                             double edge_weight, double* out, float* maps, double* part, hipStream_t s);
+
 // samples [B][K][chw] -> mean [B][chw] and, when std != null (K >= 2), the unbiased std [B][chw]; fixed double-precision
 // arithmetic per pixel (ensemble.hip: ensemble_reduce_kernel).  B <= 65535, K >= 1
 hipError_t ensemble_reduce_launch(const float* samples, int B, int K, unsigned long long chw, float* mean, float* std, hipStream_t s);

@@ -46,4 +46,16 @@ __device__ __forceinline__ float step_noise_value(unsigned long long seed, long 
     return __fmul_rn(0.5f, z);
 }
 
+// THE FORWARD NOISE (include/midd.h; diffusion_loss.hip): the standard normal z itself -- no 0.5 -- of (seed, sample, draw, element),
+// 0 <= draw < 2^31.  The same generator with the counter words (element, sample, 0x80000000 | draw, 0): a sampler iteration index
+// never has the top bit of c2 set, so no value here is a step-noise value of the same seed.  A sibling, not a refactoring:
+// step_noise_value above and the kernels that call it are untouched.
+__device__ __forceinline__ float forward_noise_value(unsigned long long seed, uint32_t sample, uint32_t draw, uint32_t elem) {
+    const Philox4 r = philox4x32_10(elem, sample, 0x80000000u | draw, 0u, (uint32_t)seed, (uint32_t)(seed >> 32));
+    constexpr float TWO_M24 = 5.9604644775390625e-08f;
+    const float u1 = __fmul_rn((float)((r.x0 >> 8) + 1u), TWO_M24);
+    const float u2 = __fmul_rn((float)(r.x1 >> 8), TWO_M24);
+    return __fmul_rn(sqrtf(__fmul_rn(-2.0f, logf(u1))), cospif(__fmul_rn(2.0f, u2)));
+}
+
 }  // namespace midd

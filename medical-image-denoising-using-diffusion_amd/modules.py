@@ -96,6 +96,7 @@ class UNetDiffusion(nn.Module):
         self._workspaces: Dict[Tuple[int, int, int, int, int], torch.Tensor] = {}
         self._ensemble_ws: Optional[Tuple[tuple, torch.Tensor]] = None      # the one resident run_ensemble workspace: (key, tensor)
         self._slots_ws: Optional[Tuple[tuple, torch.Tensor]] = None         # the one resident workspace of a session's run_slots calls
+        self._loss_ws: Optional[Tuple[tuple, torch.Tensor]] = None          # the one resident workspace of the run_denoising_loss calls
         # After every native call the status word of its workspace is read back (mi_status: one 4-byte copy, synchronises the
         # stream): NaN / Inf activations or an operand beyond the fp16 range (f16x3, f16) raise MiddError instead of returning garbage.
         # Set to False (env MIDD_CHECK_STATUS=0) to keep forward() / denoise() asynchronous; the output is NaN then, as torch's.
@@ -162,6 +163,7 @@ class UNetDiffusion(nn.Module):
         self._workspaces.clear()
         self._ensemble_ws = None
         self._slots_ws = None
+        self._loss_ws = None
         return self._plan
 
     MAX_WORKSPACES = 4       # resident (shape, stream) workspaces; least recently used is dropped first
@@ -457,6 +459,43 @@ class UNetDiffusion(nn.Module):
                           None if si is None else si.ctypes.data_as(C.POINTER(C.c_int64))) + virtual + tables
                          + (_ptr(step_noise), 0 if seed is None else 1, C.c_uint64(seed or 0), self._call_flags(clamp_eps, no_split)) + tail, ws, dev)
         return x
+
+    @torch.no_grad()
+    def run_denoising_loss(self, clean: torch.Tensor, noisy: torch.Tensor, t, alpha_hat, clamp_eps: bool, edge_weight: float,
+                           noise: Optional[torch.Tensor] = None, seed: Optional[int] = None, sample_offset: int = 0, draw: int = 0,
+                           sample_index=None, draws=None, return_maps: bool = False, workspace_batch: Optional[int] = None):
+        """The training objective of B (clean, noisy) pairs at per-sample timesteps ``t`` in one native call (mi_denoising_loss; used by
+        DiffusionDenoiser.denoising_loss): noising, the forward and the loss kernels on one stream -> (out float64 [B, 3] =
+        (mse, edge, loss), maps float32 [3, B, C, H, W] = (q, g, p) or None).  The noise is ``noise`` or the seeded forward noise of
+        (seed, sample_offset + b, draw) -- ``sample_index`` / ``draws`` ([B] integers) replace those counter words per sample.
+        ``workspace_batch``: the largest batch of a series of calls (loss_profile's passes), so that a shorter last pass keeps the scratch."""
+        from .sampler import check_loss_source, loss_counter_args, loss_table_args
+        self._check_image(clean, "clean")
+        self._check_image(noisy, "noisy")
+        if noisy.shape != clean.shape or noisy.device != clean.device:
+            raise ValueError("noisy must match clean in shape and device")
+        B, _, H, W = clean.shape
+        seed, sample_offset, draw = check_loss_source(seed, noise, sample_offset, draw, clean)
+        keep, tables = loss_table_args(t, alpha_hat, B)
+        keep2, counters = loss_counter_args(seed, sample_index, draws, B)
+        dev = clean.device
+        with self._lock, torch.cuda.device(dev):
+            plan = self._ensure_plan(time_rows=tables[-1])
+            cl, cond = clean.contiguous(), noisy.contiguous()
+            eps = None if noise is None else noise.contiguous()
+            out = torch.empty((B, 3), dtype=torch.float64, device=dev)
+            maps = torch.empty((3,) + tuple(cl.shape), dtype=torch.float32, device=dev) if return_maps else None
+            wb = max(B, int(workspace_batch or B))
+
+            def query_bytes():
+                sizes = [native.lib().mi_denoising_loss_workspace_bytes(self._plan, b, H, W) for b in range(1, wb + 1)]
+                return 0 if min(sizes) == 0 else max(sizes)
+            ws = self._resident_workspace("_loss_ws", (wb, H, W, dev.index, torch.cuda.current_stream(dev).cuda_stream), query_bytes, dev)
+            self._invoke(native.lib().mi_denoising_loss,
+                         (plan, cl.data_ptr(), cond.data_ptr()) + tables
+                         + (_ptr(eps), 0 if seed is None else 1, C.c_uint64(seed or 0), C.c_int64(sample_offset), C.c_int64(draw)) + counters
+                         + (native.MI_CLAMP_EPS if clamp_eps else 0, C.c_double(float(edge_weight)), out.data_ptr(), _ptr(maps), B, H, W), ws, dev)
+        return out, maps
 
     def _slots_workspace(self, max_slots: int, H: int, W: int, dev: torch.device) -> torch.Tensor:
         """Scratch of the run_slots calls of one session: large enough for every batch of 1 .. max_slots slots, so a batch that

@@ -173,6 +173,14 @@ SYMBOLS = [
     ("mi_metrics_workspace_bytes", C.c_size_t, [C.c_int, C.c_int]),
     ("mi_image_metrics", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                    C.c_void_p, C.c_size_t, C.c_void_p]),
+    ("mi_noise_images", C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_float), C.c_int, C.c_void_p, C.c_int, C.c_uint64, C.c_int64,
+                                  C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p]),
+    ("mi_loss_workspace_bytes", C.c_size_t, [C.c_int] * 4),
+    ("mi_loss_terms", C.c_int, [C.c_void_p] * 4 + [C.POINTER(C.c_int32), C.POINTER(C.c_float), C.c_int, C.c_int, C.c_uint64, C.c_int64, C.c_int64,
+                                C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int, C.c_double, C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p, C.c_size_t, C.c_void_p]),
+    ("mi_denoising_loss_workspace_bytes", C.c_size_t, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    ("mi_denoising_loss", C.c_int, [C.c_void_p] * 3 + [C.POINTER(C.c_int32), C.POINTER(C.c_float), C.c_int, C.c_void_p, C.c_int, C.c_uint64, C.c_int64,
+                                    C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int, C.c_double, C.c_void_p, C.c_void_p] + [C.c_int] * 3 + [C.c_void_p, C.c_size_t, C.c_void_p]),
     ("mi_plan_destroy", None, [C.c_void_p]),
     ("mi_last_error", C.c_char_p, []),
     ("mi_version", C.c_char_p, []),
