@@ -58,9 +58,8 @@ int chan_partial_rows(int HW, int C) {
 }
 
 hipError_t chan_total_launch(const float* src, stat_word* tot, int rep, int bs, int B, int HW, int C, int rows, int blocked, hipStream_t s) {
-    if (C % 4 || C / 4 > GN_THREADS) return hipErrorInvalidValue;
-    const int ppi = GN_THREADS / (C / 4);
-    const size_t lds = (size_t)ppi * C * 2 * sizeof(double) + (size_t)(C + 2) * STAT_WORDS * sizeof(stat_word);
+    const size_t lds = chan_total_lds_bytes(C);
+    if (!lds || lds > CHAN_TOTAL_LDS_LIMIT) return hipErrorInvalidValue;      // (the planner refuses such a topology: not reached through the C ABI)
     hipLaunchKernelGGL(chan_total_kernel, dim3(rows, B), dim3(GN_THREADS), lds, s, src, tot, rep, bs, HW, C, rows, blocked);
     return hipGetLastError();
 }

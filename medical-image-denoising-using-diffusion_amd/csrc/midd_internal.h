@@ -156,6 +156,16 @@ constexpr int GN_GROUPS_ = 8;                  // nn.GroupNorm(8, C) everywhere 
 // sample each add their partial sums to tot [B][C/bs][rep][2][3]
 hipError_t chan_total_launch(const float* src, stat_word* tot, int rep, int bs, int B, int HW, int C, int rows, int blocked, hipStream_t s);
 int chan_partial_rows(int HW, int C);
+// chan_total_kernel's dynamic LDS: the fp64 partial sums [ppi][C][2] of ppi = 256 / (C / 4) pixel lanes, then the publish accumulators
+// (C + 2) x STAT_WORDS.  The kernel does not raise its limit (64 KB); 0: no launch for this width (C % 4, or more than 256 quads).
+// The launch allocates by it and the planner refuses a topology whose materialised ConvTranspose would not fit: 1024 channels
+// take 65632 bytes.
+constexpr size_t CHAN_TOTAL_LDS_LIMIT = 64 * 1024;
+inline size_t chan_total_lds_bytes(int C) {
+    if (C < 4 || C % 4 || C / 4 > 256) return 0;
+    const int ppi = 256 / (C / 4);
+    return (size_t)ppi * C * 2 * sizeof(double) + (size_t)(C + 2) * STAT_WORDS * sizeof(stat_word);
+}
 
 // ---------------------------------------------------------------- pre/post-processing (prepost.hip)
 size_t resize_workspace_bytes(int n, int sw, int sh, int dw, int dh);

@@ -177,6 +177,14 @@ static int build_program(mi_plan* p, int B, int H, int W, Program* g) {
     const Mod* pending_up = nullptr;         // a ConvTranspose whose execution is deferred to its consumer
     auto flush_up = [&]() -> int {           // materialise the pending ConvTranspose for real
         if (!pending_up) return MI_OK;
+        // the totals of its output come from chan_total_kernel, whose LDS grows with the width and is not raised past 64 KB
+        const size_t tot_lds = chan_total_lds_bytes(pending_up->out_c);
+        if (!tot_lds)
+            return fail(MI_EINVAL, "%s: an unfolded ConvTranspose of %d channels: chan_total takes a multiple of 4 channels, at most 1024",
+                        pending_up->name.c_str(), pending_up->out_c);
+        if (tot_lds > CHAN_TOTAL_LDS_LIMIT)
+            return fail(MI_EINVAL, "%s: an unfolded ConvTranspose of %d channels: chan_total needs %zu bytes of LDS for its output, the limit is %zu bytes",
+                        pending_up->name.c_str(), pending_up->out_c, tot_lds, CHAN_TOTAL_LDS_LIMIT);
         TensorRef o = bld.alloc(pending_up->out_c, h.H * 2, h.W * 2);
         Op op{}; op.kind = OP_CONVT; op.s0 = h; op.dst = o; op.w = pending_up->wt; op.b = pending_up->bc;
         g->ops.push_back(op);

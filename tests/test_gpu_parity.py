@@ -250,7 +250,12 @@ def test_split_run_matches_oracle(variant):
 # ------------------------------------------------------------------------------ errors
 CONFIG_SWEEP = [
     # (constructor kwargs, variant, B, H, W) -- only topologies whose skip stack closes in the reference itself and
-    # whose output keeps the input resolution (attention at the last level only), with head_dim in {32, 64, 96, 128}
+    # whose output keeps the input resolution (attention at the last level only), with head_dim in {32, 64, 96, 128}.
+    # For these the planner always folds ConvTranspose + bilinear 1/2x into one 3x3 (tests/test_topology_sweep_cpu.py asserts it, and
+    # that every op kind an accepted configuration reaches is reached here or there).  The other topologies the planner accepts --
+    # attention at other levels, where a popped skip already has the doubled size and the ConvTranspose is materialised
+    # (conv_transpose_kernel + chan_total_kernel) -- are tests/topology_cases.py::UNFOLDED_CASES, run by
+    # tests/test_gpu_unfolded_topologies.py.
     (dict(model_channels=32, channel_mult=(1, 2), num_res_blocks=2, attention_resolutions=(1,), time_emb_dim=32), "ddim", 2, 24, 24),
     # 32..256 channels: concat inputs of up to 512 channels (LDS sized at launch beyond the nominal 384), head_dim 128,
     # 2x2 maps at the lowest level
