@@ -301,6 +301,61 @@ int mi_ensemble_reduce(const float* samples, int B, int members, int64_t chw, fl
 int mi_ensemble_quantiles(const float* samples, int B, int members, int64_t chw,
                           const double* q, int nq, float* out, void* stream);
 
+/* ENSEMBLE SCORES against a truth image (no plan needed): do the uncertainty maps of an ensemble mean anything?  samples device fp32
+ * [B,members,chw] and truth device fp32 [B,chw] -> per image the sums behind the CRPS, the error of the mean and the spread, the rank
+ * histogram of the truth among the members and, per quantile level, how often the truth lies below that quantile map -- one pass over
+ * the members, nothing copied to the host but these few numbers.
+ * THE ENSEMBLE SCORES (fixed; independent of the launch geometry, the vector width and the alignment path).  K = members,
+ * 1 <= K <= 64; levels q[0 .. nq-1], host doubles in [0, 1], 0 <= nq <= 8.  A pixel e of image b has x_m = samples[b][m][e] and
+ * y = truth[b][e].
+ *   invalid      a pixel whose y or any x_m is not finite (NaN, +-inf) is INVALID: it adds 1 to invalid[b] and nothing else, and its
+ *                crps_map value is the canonical quiet NaN 0x7FC00000.
+ *   valid        every other pixel; double precision, every operation rounded to nearest on its own, no fused multiply-add:
+ *     mean, var  exactly mi_ensemble_reduce's arithmetic, members in index order:
+ *                  s = 0; s += (double)x_m;  mean64 = s / K;   v = 0; d = (double)x_m - mean64; v += d * d;
+ *                  var = v / (K - 1), or 0 for K == 1;         dm = mean64 - (double)y;  se = dm * dm
+ *     sort       ascending by the order key of mi_ensemble_quantiles: s_0 .. s_{K-1}
+ *     CRPS       a = 0; for i = 0 .. K-1: a += |(double)s_i - (double)y|
+ *                g = 0; for i = 0 .. K-1: g += (double)(2i - K + 1) * (double)s_i     (the product is exact: 7 bits x 24 bits)
+ *                sum_i sum_j |s_i - s_j| = 2 g, so the CRPS of the members' empirical distribution, mean|X - y| - mean|X - X'| / 2, is
+ *                  c = a / (double)K - g / (double)(K*K)            crps_map = (float)c
+ *     rank       float comparisons (so -0.0 == +0.0):  lt = #{m : x_m < y},  eq = #{m : x_m == y};  rank_hist[b][2*lt + eq] += 1.
+ *                That is the mid-rank lt + eq/2 in half steps, bins 0 .. 2K: an exact integer rule with no random tie-break (ties are
+ *                the common case here: every member is clamped to [0, 1]).  A calibrated ensemble without ties fills the even bins
+ *                0, 2, .., 2K evenly; an under-dispersed one piles up in bins 0 and 2K.
+ *     coverage   per level i, Q_i = the quantile of mi_ensemble_quantiles, bit for bit (fp32):
+ *                  counts[b][i][0] += (y < Q_i)        counts[b][i][1] += (y <= Q_i)          (float comparisons)
+ *                so the share of valid pixels inside [Q_lo, Q_hi] is (counts[hi][1] - counts[lo][0]) / valid.
+ *   sums         per image A = sum a, G = sum g, E = sum se, V = sum var over its valid pixels, in double, no atomics, in ONE order:
+ *                - the chw elements of an image are cut into chunks of 1024 consecutive elements (the last one may be partial);
+ *                - in a chunk, lane j = 0 .. 255 owns elements 4j .. 4j+3 and adds them in that order starting from 0; invalid and
+ *                  absent pixels add nothing;
+ *                - the 256 lane sums are folded by the tree  for off = 128, 64, .., 1: v[j] += v[j + off]  for j < off;
+ *                - an image's chunk sums are added one by one, starting from 0, in chunk order.
+ *                The caller composes, with N = chw - invalid[b]:  crps = A/(K N) - G/(K^2 N);  the fair (unbiased in K) form
+ *                crps_fair = A/(K N) - G/(K (K-1) N);  rmse = sqrt(E/N);  spread = sqrt(V/N)  (rmse ~ spread: calibrated).
+ *   integers     invalid, rank_hist and counts are exact integers: their order is free (64-bit integer atomics).
+ * Arguments
+ *   sums         device double [B][4] = (A, G, E, V), 8-byte aligned
+ *   invalid      device uint64 [B];  rank_hist  device uint64 [B][2*members+1];  both 8-byte aligned.  The call zeroes its integer
+ *                outputs itself, on the stream
+ *   counts       device uint64 [B][nq][2], 8-byte aligned; NULL if and only if nq == 0
+ *   crps_map     device fp32 [B][chw] or NULL (skipped)
+ *   workspace    mi_ensemble_scores_workspace_bytes (the chunk sums, double [B][chunks][4]), 8-byte aligned; the query answers 0 on
+ *                sizes the call refuses
+ * Every member is read once, as 16-byte words when chw is a multiple of 4 and samples, truth and crps_map are 16-byte aligned, element
+ * by element otherwise: the same bits either way.  Allocates nothing; asynchronous; needs no plan.
+ * MI_EINVAL before any GPU work, the rule named in mi_last_error, judged in this order: B outside [1, 65535]; members outside
+ * [1, 64]; chw outside [1, 2^32); nq outside [0, 8]; a level that is NaN or outside [0, 1]; a null samples, truth, sums, invalid,
+ * rank_hist or workspace (or q with nq > 0); counts and nq disagreeing; sums, invalid, rank_hist, counts or workspace not 8-byte
+ * aligned, samples, truth or crps_map not 4-byte aligned; workspace_bytes below the query's answer; any output (workspace included)
+ * overlapping an input or another output. */
+size_t mi_ensemble_scores_workspace_bytes(int B, int members, int64_t chw);
+int mi_ensemble_scores(const float* samples, const float* truth, int B, int members, int64_t chw,
+                       const double* q, int nq,
+                       double* sums, uint64_t* invalid, uint64_t* rank_hist, uint64_t* counts, float* crps_map,
+                       void* workspace, size_t workspace_bytes, void* stream);
+
 /* TILED DENOISING: images of any size >= the tile, at their own resolution, as overlapping network-sized tiles (the reference
  * resizes every image to the training size first, Backend/run.py denoise_image_diffusion(..., img_size); nothing there tiles).
  * THE GEOMETRY (fixed), per axis with image length L, tile T, minimum overlap O, T <= L, 0 <= O <= T/2:

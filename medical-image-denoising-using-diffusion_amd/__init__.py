@@ -15,5 +15,6 @@ from .sampler import (DiffusionDenoiser, EnsembleQuantileResult, EnsembleResult,
                       dihedral_reduce, dihedral_views, ensemble_quantiles, ensemble_reduce, step_noise, tile_blend,
                       tile_blend_quantiles, tile_blend_reduce, tile_extract, tile_plan, view_codes,
                       TiledSelfEnsembleQuantileResult, TiledSelfEnsembleResult, tile_blend_unview_quantiles, tile_blend_unview_reduce,
-                      view_codes_tiled, DenoisingLoss, LossMaps, LossProfile, loss_terms, noise_images)
+                      view_codes_tiled, DenoisingLoss, LossMaps, LossProfile, loss_terms, noise_images, EnsembleScores,
+                      ensemble_scores)
 from .session import SamplerSession, Ticket  # noqa: F401

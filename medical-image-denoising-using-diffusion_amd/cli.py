@@ -31,7 +31,7 @@ from PIL import Image
 
 from . import image16
 from .modules import UNetDiffusion
-from .sampler import MAX_QUANTILE_MEMBERS, DiffusionDenoiser, check_levels, check_update
+from .sampler import DEFAULT_SCORE_LEVELS, MAX_QUANTILE_MEMBERS, DiffusionDenoiser, check_levels, check_update, ensemble_scores
 
 
 def denoise_image_diffusion(model_path: Optional[str], test_image_path: str, device_type: str = "cuda",
@@ -43,7 +43,8 @@ def denoise_image_diffusion(model_path: Optional[str], test_image_path: str, dev
                             self_ensemble: Optional[str] = None, update: str = "reference", eta: float = 0.0,
                             clip_x0: bool = True, x0_out: Optional[str] = None, bit_depth: int = 8, window: Optional[Sequence[float]] = None,
                             window_levels: Optional[Sequence[int]] = None, views: Optional[str] = None,
-                            members: Optional[int] = None, clean: Optional[str] = None, loss_out: Optional[str] = None) -> Image.Image:
+                            members: Optional[int] = None, clean: Optional[str] = None, loss_out: Optional[str] = None,
+                            truth: Optional[str] = None, scores_out: Optional[str] = None) -> Image.Image:
     """compute (not a reference argument): arithmetic of the network, see UNetDiffusion -- None keeps the default.
     seed (not a reference argument; cddpm): the stochastic sampler's noise is drawn on the device from this seed, so the same
     call gives the same image again (DiffusionDenoiser.denoise); None: torch.randn, as the reference.
@@ -86,9 +87,24 @@ def denoise_image_diffusion(model_path: Optional[str], test_image_path: str, dev
     checkpoint's training objective on the pair at every timestep (DiffusionDenoiser.loss_profile; seed: the forward noise's, drawn
     and printed when None) and the PSNR / SSIM of the ordinary sampler run against the clean image (prepost.compute_metrics); loss_out
     is the path of a .json file that receives both.  The sampler run and the returned image are those of the call without clean.
-    Not together with tile, samples, views, members or self_ensemble, and on a GPU only."""
+    Not together with tile, samples, views, members or self_ensemble, and on a GPU only.
+    truth, scores_out (not reference arguments; with samples, or with tile and members; on a GPU only): EVALUATION OF THE ENSEMBLE.
+    truth is the path of the clean counterpart of the image, loaded by the recipe of clean (with tile: at its own size, which must be
+    the image's).  The call prints the CRPS, the fair CRPS, the RMSE of the mean beside the spread and the coverage of the outermost
+    pair of levels (quantiles if given, else 0.05, 0.25, 0.5, 0.75, 0.95) of the members against it (sampler.ensemble_scores; K <= 64);
+    scores_out is the path of a .json file that receives everything, rank histogram and level counts included.  The sampler run and
+    the returned image are those of the call without truth."""
     if loss_out is not None and clean is None:
         raise ValueError("--loss-out needs --clean PATH (the evaluation's clean image)")
+    if scores_out is not None and truth is None:
+        raise ValueError("--scores-out needs --truth PATH (the image the ensemble is scored against)")
+    if truth is not None:
+        if samples is None and (tile is None or members is None):
+            raise ValueError("--truth scores an ensemble: it needs --samples K, or --tile N --members K")
+        if (samples if samples is not None else members) > MAX_QUANTILE_MEMBERS:
+            raise ValueError(f"--truth needs K <= {MAX_QUANTILE_MEMBERS} members: the scores kernel sorts a pixel's members in registers")
+        if torch.device(device_type).type != "cuda":
+            raise RuntimeError("--truth (ensemble scores) runs only on a ROCm GPU: the scores kernel has no CPU fallback")
     if clean is not None:
         for flag, given in (("--tile", tile), ("--samples", samples), ("--views", views), ("--members", members), ("--self-ensemble", self_ensemble)):
             if given is not None:
@@ -207,7 +223,7 @@ def denoise_image_diffusion(model_path: Optional[str], test_image_path: str, dev
             what = f"Self-ensemble of {len(res.views)} views {res.views}, tiled"
         elif members is not None:
             res = diffusion.denoise_tiled_ensemble(input_tensor, inference_steps=inference_steps, members=members, tile=tile, overlap=overlap,
-                                                   seed=seed, quantiles=quantiles)
+                                                   seed=seed, quantiles=quantiles, return_samples=truth is not None)
             what = f"Ensemble of {members} samples, tiled"
         else:
             res = diffusion.denoise_tiled(input_tensor, inference_steps=inference_steps, tile=tile, overlap=overlap, seed=seed, **rule)
@@ -216,6 +232,8 @@ def denoise_image_diffusion(model_path: Optional[str], test_image_path: str, dev
             torch.cuda.synchronize(device)
         print(f"{what}: {len(res.origins_y)} x {len(res.origins_x)} tiles of {tile}" + (f", seed {res.seed}" if res.seed is not None else ""))
         print(f"Inference time: {time.time() - start_time:.2f} seconds")
+        if truth is not None:
+            score(res.samples, truth, None, bit_depth, win, quantiles if quantiles is not None else DEFAULT_SCORE_LEVELS, res.seed, scores_out)
         if tiled_ensemble:      # the mean of values in [0, 1] is in [0, 1]: stored as the tiled image is; the maps stay float, at the image's size
             if std_out is not None:
                 np.save(std_out, res.std[0, 0].cpu().numpy())
@@ -266,9 +284,12 @@ def denoise_image_diffusion(model_path: Optional[str], test_image_path: str, dev
         if quantiles is not None:
             np.save(quantiles_out, ens.quantiles.reshape(len(quantiles), img_size, img_size).cpu().numpy())
     elif samples is not None:
-        ens = diffusion.denoise_ensemble(input_tensor, inference_steps=inference_steps, members=samples, seed=seed, quantiles=quantiles, **rule)
+        ens = diffusion.denoise_ensemble(input_tensor, inference_steps=inference_steps, members=samples, seed=seed, quantiles=quantiles,
+                                         return_samples=truth is not None, **rule)
         denoised = ens.mean                               # a mean of values in [0, 1]: in [0, 1]
         print(f"Ensemble of {samples} samples, seed {ens.seed}")
+        if truth is not None:
+            score(ens.samples, truth, img_size, bit_depth, win, quantiles if quantiles is not None else DEFAULT_SCORE_LEVELS, ens.seed, scores_out)
         if std_out is not None:
             np.save(std_out, ens.std.reshape(img_size, img_size).cpu().numpy())
         if quantiles is not None:
@@ -307,6 +328,54 @@ def denoise_image_diffusion(model_path: Optional[str], test_image_path: str, dev
     return output_img.resize(img.size, Image.BICUBIC)
 
 
+def load_counterpart(path: str, device, img_size: Optional[int], bit_depth: int, win) -> torch.Tensor:
+    """The clean counterpart of the noisy image (--clean, --truth) as the [1, 1, H, W] tensor the sampler's input is, on the GPU: the
+    same recipe -- bit_depth, the resize to img_size (None: --tile, the image's own size, no resize) and the NOISY image's window
+    levels `win` (device int32 [1, 2]) if it has a window."""
+    from . import prepost
+    img = Image.open(path)
+    raw16 = image16.decode16(img) if bit_depth == 16 else None
+    if win is not None:
+        dev16 = torch.from_numpy(image16.need_u16(raw16, img.mode)).to(device)
+        if img_size is None:
+            return prepost.window_u16_to_float(dev16, win)[None, None]
+        return prepost.resize_bicubic_f32(dev16, (img_size, img_size), clamp=True, levels=win)[None, None]
+    if raw16 is not None:
+        dev_raw = torch.from_numpy(raw16).to(device)
+        if img_size is None:
+            return (prepost.u16_to_unit_float if raw16.dtype == np.uint16 else prepost.to_unit_float)(dev_raw)[None, None]
+        return prepost.resize_bicubic_f32(dev_raw, (img_size, img_size), clamp=True)[None, None]
+    raw = torch.from_numpy(np.asarray(img.convert("L"), np.uint8).copy()).to(device)
+    if img_size is None:
+        return prepost.to_unit_float(raw)[None, None]
+    return prepost.to_unit_float(prepost.resize_bicubic_u8(raw, (img_size, img_size)))[None, None]
+
+
+def score(samples: torch.Tensor, truth_path: str, img_size: Optional[int], bit_depth: int, win, levels, seed, scores_out: Optional[str]) -> dict:
+    """--truth: the scores of the ensemble `samples` [1, K, 1, H, W] against the truth image (sampler.ensemble_scores), printed and,
+    with scores_out, written as JSON.  The truth goes through the recipe of the noisy image (load_counterpart)."""
+    import json
+    truth = load_counterpart(truth_path, samples.device, img_size, bit_depth, win)
+    if tuple(truth.shape[2:]) != tuple(samples.shape[3:]):
+        raise ValueError(f"--truth is {truth.shape[2]}x{truth.shape[3]}, the ensemble {samples.shape[3]}x{samples.shape[4]}: the truth image "
+                         "must have the size of --image")
+    sc = ensemble_scores(samples, truth.float(), levels)
+    result = {"members": int(samples.shape[1]), "height": int(truth.shape[2]), "width": int(truth.shape[3]), "seed": seed,
+              "crps": float(sc.crps[0]), "crps_fair": float(sc.crps_fair[0]), "rmse": float(sc.rmse[0]), "spread": float(sc.spread[0]),
+              "valid": int(sc.valid[0]), "sums": sc.sums[0].tolist(), "rank_hist": sc.rank_hist[0].tolist(), "levels": list(sc.levels),
+              "count_lt": sc.count_lt[0].tolist(), "count_le": sc.count_le[0].tolist(),
+              "coverage": None if not sc.levels else float(sc.coverage()[0])}
+    print(f"Ensemble of {result['members']} members against the truth image ({result['valid']} valid pixels):")
+    print(f"  CRPS {result['crps']:.6f} | fair CRPS {result['crps_fair']:.6f} | RMSE of the mean {result['rmse']:.6f} | spread {result['spread']:.6f}")
+    if sc.levels:
+        print(f"  coverage of the {sc.levels[0]:g} .. {sc.levels[-1]:g} interval: {result['coverage']:.4f} (nominal {sc.levels[-1] - sc.levels[0]:.4f})")
+    if scores_out is not None:
+        with open(scores_out, "w") as f:
+            json.dump(result, f, indent=1)
+        print(f"Scores saved: {scores_out}")
+    return result
+
+
 def evaluate(diffusion: DiffusionDenoiser, clean_path: str, noisy: torch.Tensor, denoised: torch.Tensor, img_size: int, bit_depth: int,
              win, seed: Optional[int], loss_out: Optional[str]) -> dict:
     """--clean: the loss profile of the (clean, noisy) pair over all timesteps and the PSNR / SSIM of `denoised` against the clean
@@ -315,17 +384,7 @@ def evaluate(diffusion: DiffusionDenoiser, clean_path: str, noisy: torch.Tensor,
     import json
 
     from . import prepost
-    device = noisy.device
-    img = Image.open(clean_path)
-    raw16 = image16.decode16(img) if bit_depth == 16 else None
-    if win is not None:
-        dev16 = torch.from_numpy(image16.need_u16(raw16, img.mode)).to(device)
-        clean = prepost.resize_bicubic_f32(dev16, (img_size, img_size), clamp=True, levels=win)[None, None]
-    elif raw16 is not None:
-        clean = prepost.resize_bicubic_f32(torch.from_numpy(raw16).to(device), (img_size, img_size), clamp=True)[None, None]
-    else:
-        raw = torch.from_numpy(np.asarray(img.convert("L"), np.uint8).copy()).to(device)
-        clean = prepost.to_unit_float(prepost.resize_bicubic_u8(raw, (img_size, img_size)))[None, None]
+    clean = load_counterpart(clean_path, noisy.device, img_size, bit_depth, win)
     prof = diffusion.loss_profile(clean, noisy, seed=seed)
     psnr, ssim = prepost.compute_metrics(denoised.reshape(1, 1, img_size, img_size).float(), clean)
     variant = getattr(diffusion.model, "variant", "ddim")
@@ -395,7 +454,19 @@ def main(argv=None) -> None:
                     help="evaluation: the clean counterpart of --image; prints the checkpoint's denoising loss on the pair at every timestep "
                          "and the PSNR / SSIM of the sampler run against it (not with --tile, --samples, --views, --members, --self-ensemble)")
     ap.add_argument("--loss-out", default=None, metavar="PATH.json", help="with --clean: write the loss profile and the metrics as JSON")
+    ap.add_argument("--truth", default=None, metavar="PATH",
+                    help="with --samples K, or --tile N --members K (K <= 64): the clean counterpart of --image; prints the CRPS, fair CRPS, "
+                         "RMSE, spread and interval coverage of the ensemble against it (levels: --quantiles, else 0.05,0.25,0.5,0.75,0.95)")
+    ap.add_argument("--scores-out", default=None, metavar="PATH.json",
+                    help="with --truth: write the scores, the rank histogram and the level counts as JSON")
     args = ap.parse_args(argv)
+    if args.scores_out is not None and args.truth is None:
+        ap.error("--scores-out needs --truth PATH")
+    if args.truth is not None:
+        if args.samples is None and (args.tile is None or args.members is None):
+            ap.error("--truth scores an ensemble: it needs --samples K, or --tile N --members K")
+        if (args.samples if args.samples is not None else args.members) > MAX_QUANTILE_MEMBERS:
+            ap.error(f"--truth needs K <= {MAX_QUANTILE_MEMBERS} members")
     if args.loss_out is not None and args.clean is None:
         ap.error("--loss-out needs --clean PATH")
     if args.clean is not None:
@@ -468,7 +539,8 @@ def main(argv=None) -> None:
                                        **({} if window_levels is None else {"window_levels": window_levels}),
                                        **({} if args.views is None else {"views": args.views}),
                                        **({} if args.members is None else {"members": args.members}),
-                                       **({} if args.clean is None else {"clean": args.clean, "loss_out": args.loss_out}))
+                                       **({} if args.clean is None else {"clean": args.clean, "loss_out": args.loss_out}),
+                                       **({} if args.truth is None else {"truth": args.truth, "scores_out": args.scores_out}))
     restored.save(args.out, quality=95)
     print(f"\nResult saved: {args.out}")
 

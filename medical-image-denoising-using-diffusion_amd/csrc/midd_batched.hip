@@ -93,6 +93,57 @@ extern "C" int mi_ensemble_quantiles(const float* samples, int B, int members, i
     return launched(ensemble_quantiles_launch(samples, B, members, (unsigned long long)chw, ql, out, (hipStream_t)stream), "ensemble_quantiles");
 }
 
+// The scores of an ensemble against a truth image (ensemble_scores.hip; include/midd.h: THE ENSEMBLE SCORES).  The rules in the
+// documented order; the levels may be none (nq == 0: no coverage counts), which check_quantile_levels does not allow
+static int check_scores_shape(int B, int members, int64_t chw) {
+    if (int rc = check_reduce_batch(B, "limit of the scores kernel's grid")) return rc;
+    if (members < 1 || members > QUANTILE_MAX_MEMBERS)
+        return fail(MI_EINVAL, "members %d outside [1, %d]: the scores kernel sorts a pixel's members in registers (limit: 1 <= members <= %d)",
+                    members, QUANTILE_MAX_MEMBERS, QUANTILE_MAX_MEMBERS);
+    if (chw < 1 || chw >= MEMBER_WORDS) return fail(MI_EINVAL, "chw %lld outside [1, 2^32) (limit: C*H*W < 4294967296)", (long long)chw);
+    return MI_OK;
+}
+
+extern "C" size_t mi_ensemble_scores_workspace_bytes(int B, int members, int64_t chw) {
+    if (check_scores_shape(B, members, chw)) return 0;
+    return ensemble_scores_partials_bytes(B, (unsigned long long)chw);
+}
+
+extern "C" int mi_ensemble_scores(const float* samples, const float* truth, int B, int members, int64_t chw, const double* q, int nq,
+                                  double* sums, uint64_t* invalid, uint64_t* rank_hist, uint64_t* counts, float* crps_map,
+                                  void* workspace, size_t workspace_bytes, void* stream) {
+    if (int rc = check_scores_shape(B, members, chw)) return rc;
+    if (nq < 0 || nq > QUANTILE_MAX_LEVELS)
+        return fail(MI_EINVAL, "nq %d outside [0, %d]: the levels travel as kernel arguments (limit: 0 <= nq <= %d)", nq, QUANTILE_MAX_LEVELS, QUANTILE_MAX_LEVELS);
+    QuantileLevels ql{};
+    ql.nq = nq;
+    for (int i = 0; q && i < nq; ++i) {
+        if (!(q[i] >= 0.0 && q[i] <= 1.0)) return fail(MI_EINVAL, "q[%d] = %.17g outside [0, 1] (limit: 0 <= q <= 1, not NaN)", i, q[i]);
+        ql.q[i] = q[i];
+    }
+    if (!samples || !truth || !sums || !invalid || !rank_hist || !workspace || (nq > 0 && !q)) return fail(MI_EINVAL, "null argument");
+    if ((counts == nullptr) != (nq == 0))
+        return fail(MI_EINVAL, "counts and nq = %d disagree: counts holds [B][nq][2] counters and is NULL if and only if nq == 0", nq);
+    for (const void* p : {(const void*)sums, (const void*)invalid, (const void*)rank_hist, (const void*)counts, (const void*)workspace})
+        if (reinterpret_cast<uintptr_t>(p) & 7) return fail(MI_EINVAL, "sums, invalid, rank_hist, counts and workspace must be 8-byte aligned");
+    for (const void* p : {(const void*)samples, (const void*)truth, (const void*)crps_map})
+        if (reinterpret_cast<uintptr_t>(p) & 3) return fail(MI_EINVAL, "samples, truth and crps_map must be 4-byte aligned");
+    const size_t need = ensemble_scores_partials_bytes(B, (unsigned long long)chw);
+    if (workspace_bytes < need) return fail(MI_EINVAL, "workspace too small: need %zu bytes (mi_ensemble_scores_workspace_bytes), got %zu", need, workspace_bytes);
+    const size_t img = (size_t)chw * sizeof(float);
+    const Buf buf[8] = {{samples, (size_t)B * members * img, "samples"}, {truth, (size_t)B * img, "truth"},
+                        {sums, (size_t)B * 4 * sizeof(double), "sums"}, {invalid, (size_t)B * sizeof(uint64_t), "invalid"},
+                        {rank_hist, (size_t)B * (2 * members + 1) * sizeof(uint64_t), "rank_hist"},
+                        {counts, (size_t)B * nq * 2 * sizeof(uint64_t), "counts"}, {crps_map, (size_t)B * img, "crps_map"},
+                        {workspace, need, "workspace"}};
+    if (int rc = check_no_overlap(buf, 8, "samples and truth are read while every output and the workspace are written")) return rc;
+    static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "the counters are 64-bit");
+    return launched(ensemble_scores_launch(samples, truth, B, members, (unsigned long long)chw, ql, sums,
+                                           reinterpret_cast<unsigned long long*>(invalid), reinterpret_cast<unsigned long long*>(rank_hist),
+                                           reinterpret_cast<unsigned long long*>(counts), crps_map, static_cast<double*>(workspace),
+                                           (hipStream_t)stream), "ensemble_scores");
+}
+
 // ---------------------------------------------------------------------------- the batched calls: virtual samples in passes
 // mi_denoise_ensemble, mi_denoise_tiled and mi_denoise_tiled_ensemble run `rounds` x V virtual samples of h x w each through the
 // sampler loop in passes of L.pass.  Each judges its own argument rules and its table of buffers (check_no_overlap), then shares

@@ -390,6 +390,15 @@ hipError_t ensemble_quantiles_launch(const float* samples, int B, int K, unsigne
 // per member, then of ensemble_quantiles_launch).  The limits of tile_blend_reduce_launch and of the call above
 hipError_t tile_blend_quantiles_launch(const float* tiles, int B, int M, const TileGeom& g, const QuantileLevels& ql, float* out, hipStream_t s);
 
+// Scores of an ensemble against a truth image (ensemble_scores.hip; include/midd.h: THE ENSEMBLE SCORES).  samples [B][K][chw], truth
+// [B][chw] -> sums double [B][4] = (A, G, E, V), invalid [B], rank_hist [B][2K+1], counts [B][nq][2] (null iff nq == 0), crps_map
+// [B][chw] or null; part: ensemble_scores_partials_bytes, the chunk sums.  Zeroes the integer outputs on the stream.  B <= 65535,
+// 1 <= K <= 64, 0 <= nq <= 8, every level in [0, 1]
+size_t ensemble_scores_partials_bytes(int B, unsigned long long chw);
+hipError_t ensemble_scores_launch(const float* samples, const float* truth, int B, int K, unsigned long long chw, const QuantileLevels& ql,
+                                  double* sums, unsigned long long* invalid, unsigned long long* rank_hist, unsigned long long* counts,
+                                  float* crps_map, double* part, hipStream_t s);
+
 // Geometric self-ensemble (include/midd.h: THE GEOMETRY).  A view list is 1 .. 8 distinct codes g = 4 t + 2 fy + fx in the caller's
 // order; it travels as kernel arguments.  Transposing codes (g >= 4) need H == W.
 constexpr int DIHEDRAL_MAX_VIEWS = 8;

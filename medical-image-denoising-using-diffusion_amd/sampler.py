@@ -281,6 +281,97 @@ def ensemble_quantiles(samples: torch.Tensor, q) -> torch.Tensor:
     return out
 
 
+DEFAULT_SCORE_LEVELS = (0.05, 0.25, 0.5, 0.75, 0.95)
+
+
+class EnsembleScores(NamedTuple):
+    """What ``ensemble_scores`` returns (include/midd.h: THE ENSEMBLE SCORES).  Everything but ``crps_map`` lives on the host: the
+    scalars are float64 CPU tensors [B] composed in Python floats from the raw ``sums``, the integers int64 CPU tensors."""
+    crps: torch.Tensor                    # [B]: mean CRPS of the members' empirical distribution, A/(K N) - G/(K^2 N)
+    crps_fair: torch.Tensor               # [B]: the fair (unbiased in K) form, A/(K N) - G/(K (K-1) N); NaN for one member
+    rmse: torch.Tensor                    # [B]: root mean squared error of the ensemble mean, sqrt(E/N)
+    spread: torch.Tensor                  # [B]: root mean unbiased member variance, sqrt(V/N); ~ rmse for a calibrated ensemble
+    rank_hist: torch.Tensor               # int64 [B, 2K+1]: bin 2*lt + eq, the mid-rank of the truth among the members in half steps
+    count_lt: torch.Tensor                # int64 [B, nq]: valid pixels with truth <  the level's quantile map
+    count_le: torch.Tensor                # int64 [B, nq]: valid pixels with truth <= the level's quantile map
+    levels: Tuple[float, ...]             # the quantile levels
+    valid: torch.Tensor                   # int64 [B]: N = chw - invalid, the pixels whose truth and members are all finite
+    sums: torch.Tensor                    # float64 [B, 4]: the raw (A, G, E, V)
+    crps_map: Optional[torch.Tensor]      # float32 [B, ...] on the device with return_map=True: per-pixel CRPS, NaN where invalid
+
+    def coverage(self, lo: int = 0, hi: int = -1) -> torch.Tensor:
+        """float64 [B]: the share of valid pixels whose truth lies inside [Q_lo, Q_hi], the quantile maps of ``levels[lo]`` and
+        ``levels[hi]`` -- (count_le[:, hi] - count_lt[:, lo]) / valid; compare it with ``levels[hi] - levels[lo]``."""
+        return (self.count_le[:, hi] - self.count_lt[:, lo]).to(torch.float64) / self.valid.to(torch.float64)
+
+
+def check_score_levels(quantiles) -> Tuple[float, ...]:
+    """``check_levels``, except that no level at all (None or an empty sequence) is allowed: the scores then carry no coverage."""
+    if quantiles is None or (isinstance(quantiles, (tuple, list)) and len(quantiles) == 0):
+        return ()
+    return check_levels(quantiles)
+
+
+@torch.no_grad()
+def ensemble_scores(samples: torch.Tensor, truth: torch.Tensor, quantiles=DEFAULT_SCORE_LEVELS, return_map: bool = False) -> EnsembleScores:
+    """Proper scores of an ensemble ``samples`` [B, K, ...] against ``truth`` [B, ...] in one launch (mi_ensemble_scores; include/midd.h:
+    THE ENSEMBLE SCORES): CRPS and fair CRPS, the RMSE of the ensemble mean beside the spread, the rank histogram of the truth among
+    the members with exact mid-rank ties, and for every level of ``quantiles`` how many pixels have their truth below that quantile
+    map (``EnsembleScores.coverage``: is the 5-95 % interval a 90 % interval?).  K <= 64, at most 8 levels (none: no coverage).  A
+    pixel whose truth or any member is not finite is left out of everything and counted (``valid`` = pixels - invalid).  The raw
+    outputs are copied to the host once (that waits for the stream); ``return_map=True`` also returns the per-pixel CRPS, which
+    stays on the device."""
+    levels = check_score_levels(quantiles)
+    if not isinstance(samples, torch.Tensor) or samples.dim() < 3 or samples.shape[0] < 1 or samples.shape[1] < 1:
+        raise ValueError("samples must be a [B, members, ...] tensor with B >= 1 and members >= 1")
+    check_quantile_members(samples.shape[1])
+    if not isinstance(truth, torch.Tensor) or tuple(truth.shape) != (samples.shape[0],) + tuple(samples.shape[2:]) or truth.device != samples.device:
+        raise ValueError(f"truth must be a tensor of shape {(samples.shape[0],) + tuple(samples.shape[2:])} on {samples.device}: one image per "
+                         "ensemble, without the member axis")
+    if samples.device.type != "cuda":
+        raise RuntimeError(f"ensemble_scores runs only on a ROCm GPU (got {samples.device}): there is no CPU fallback")
+    if samples.dtype != torch.float32 or truth.dtype != torch.float32:
+        raise TypeError(f"samples and truth must be float32 (got {samples.dtype} and {truth.dtype})")
+    src, tru = samples.contiguous(), truth.contiguous()
+    B, K = src.shape[:2]
+    chw = src[0, 0].numel()
+    nq, bins = len(levels), 2 * K + 1
+    lib = native.lib()
+    dev = src.device
+    with torch.cuda.device(dev):
+        # one 8-byte-word buffer for the raw outputs [sums B*4 | invalid B | rank_hist B*bins | counts B*nq*2]: one copy to the host
+        raw = torch.empty(B * (4 + 1 + bins + 2 * nq), dtype=torch.int64, device=dev)
+        o_inv, o_rank, o_cnt = B * 4, B * 5, B * (5 + bins)
+        cmap = torch.empty_like(tru) if return_map else None
+        nbytes = lib.mi_ensemble_scores_workspace_bytes(B, K, chw)
+        if nbytes == 0:
+            native.check(-1)
+        ws = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
+        base = raw.data_ptr()
+        native.check(lib.mi_ensemble_scores(src.data_ptr(), tru.data_ptr(), B, K, chw, _levels_arg(levels) if nq else None, nq,
+                                            base, base + 8 * o_inv, base + 8 * o_rank, base + 8 * o_cnt if nq else None,
+                                            None if cmap is None else cmap.data_ptr(), ws.data_ptr(), nbytes,
+                                            torch.cuda.current_stream(dev).cuda_stream))
+        host = raw.cpu()
+    sums = host[:o_inv].view(torch.float64).reshape(B, 4).clone()
+    invalid = host[o_inv:o_rank]
+    rank_hist = host[o_rank:o_cnt].reshape(B, bins).clone()
+    counts = host[o_cnt:].reshape(B, nq, 2)
+    valid = chw - invalid
+    crps, fair, rmse, spread = [], [], [], []
+    nan = float("nan")
+    for b in range(B):
+        A, G, E, V = (float(v) for v in sums[b])
+        N = int(valid[b])
+        crps.append(A / (K * N) - G / (K * K * N) if N else nan)
+        fair.append(A / (K * N) - G / (K * (K - 1) * N) if N and K > 1 else nan)
+        rmse.append((E / N) ** 0.5 if N else nan)
+        spread.append((V / N) ** 0.5 if N else nan)
+    f64 = lambda v: torch.tensor(v, dtype=torch.float64)
+    return EnsembleScores(f64(crps), f64(fair), f64(rmse), f64(spread), rank_hist, counts[:, :, 0].clone(), counts[:, :, 1].clone(), levels,
+                          valid.clone(), sums, cmap)
+
+
 class LossMaps(NamedTuple):
     """The per-pixel maps of ``denoising_loss(..., return_maps=True)``, each [B, C, H, W] (include/midd.h: THE DENOISING LOSS)."""
     q: torch.Tensor          # squared error of the predicted noise
@@ -1174,6 +1265,29 @@ class DiffusionDenoiser:
         maps = tile_blend_unview_quantiles(tiles, noisy_img.shape[2], noisy_img.shape[3], plan.overlap, codes, levels)
         return TiledSelfEnsembleQuantileResult(mean, std, samples, tiles if return_tiles else None, codes, plan.origins_y, plan.origins_x,
                                                seed, maps, levels)
+
+    @torch.no_grad()
+    def score_ensemble(self, clean: torch.Tensor, noisy: torch.Tensor, inference_steps: int = 25, members: int = 8, seed: Optional[int] = None,
+                       sample_offset: int = 0, member_offset: int = 0, max_batch: int = 16, quantiles=DEFAULT_SCORE_LEVELS,
+                       tile=None, overlap=32, return_map: bool = False):
+        """An ensemble of ``noisy`` scored against ``clean`` -> ``(result, scores)``: ``denoise_ensemble(noisy, ..., return_samples=True)``
+        -- or, with ``tile``, ``denoise_tiled_ensemble(noisy, ..., tile=tile, overlap=overlap, return_samples=True)``, whose blended
+        members are scored -- followed by ``ensemble_scores(result.samples, clean, quantiles, return_map)``, bit for bit that
+        composition.  ``scores`` answers whether the std and quantile maps of this checkpoint at these ``members``,
+        ``inference_steps`` mean anything: ``scores.rmse`` beside ``scores.spread``, ``scores.coverage()`` beside the levels,
+        ``scores.rank_hist``.  members <= 64."""
+        levels = check_score_levels(quantiles)
+        check_quantile_members(check_member(members, "members", low=1))
+        if not isinstance(clean, torch.Tensor) or not isinstance(noisy, torch.Tensor) or clean.shape != noisy.shape or clean.device != noisy.device:
+            raise ValueError("clean must be a tensor of the noisy images' shape, on their device")
+        if clean.dtype != torch.float32:
+            raise TypeError(f"clean must be float32 (got {clean.dtype})")
+        if tile is None:
+            result = self.denoise_ensemble(noisy, inference_steps, members, seed, sample_offset, member_offset, max_batch, return_samples=True)
+        else:
+            result = self.denoise_tiled_ensemble(noisy, inference_steps, members, tile, overlap, max_batch, seed, sample_offset, member_offset,
+                                                 return_samples=True)
+        return result, ensemble_scores(result.samples, clean, levels, return_map)
 
     # ------------------------------------------------------------------ the training objective as an evaluation
     def sample_timesteps(self, n: int, generator: Optional[torch.Generator] = None) -> torch.Tensor:
