@@ -356,6 +356,72 @@ int mi_ensemble_scores(const float* samples, const float* truth, int B, int memb
                        double* sums, uint64_t* invalid, uint64_t* rank_hist, uint64_t* counts, float* crps_map,
                        void* workspace, size_t workspace_bytes, void* stream);
 
+/* NOISE POWER SPECTRUM (no plan needed): what does the remaining noise look like?  The per-pixel scores above say how large a
+ * residual or an ensemble's spread is; the noise power spectrum (NPS) says at which spatial frequencies it lives.  Welch's method as
+ * in IEC 62220-1: overlapping regions of interest (ROIs) are detrended, windowed, transformed, their periodograms averaged and the
+ * average binned by radial frequency.  a device fp32 [B,K,C,H,W], b device fp32 [B,C,H,W] or NULL (broadcast over K).
+ * THE NOISE POWER SPECTRUM (fixed; independent of the launch geometry, the vector width and the alignment path).
+ *   field        f = a - b, ONE fp32 subtraction (b == NULL: f = a).  A group g = b*C + c is a (b, c) pair; its realisations are
+ *                the K members.
+ *   ROIs         size R = roi in {32, 64, 128}, step S >= 1; origins (iy*S, ix*S), iy < ny = (H-R)/S + 1, ix < nx = (W-R)/S + 1
+ *                (integer divisions); no partial ROIs.  The ROIs of a group are numbered n = (m*ny + iy)*nx + ix, m the member.
+ *   skipped      an ROI holding a NaN or an Inf in f is SKIPPED: it adds 1 to rois_skipped[g] and nothing else.  Every other ROI is
+ *                USED (rois_used[g]).  Only f is judged; a non-finite value is never folded into a sum.
+ *   detrend      0 none: d = f.  1 mean, 2 plane: in double, every operation rounded to nearest on its own, no fused multiply-add,
+ *                with xc = x - (R-1)/2, yc = y - (R-1)/2 (exact):
+ *                  row sums     s0[y] = 0; s0[y] += (double)f[y][x]        s1[y] = 0; s1[y] += xc * (double)f[y][x]     x = 0 .. R-1
+ *                  ROI sums     t0 = 0; t0 += s0[y]     tx = 0; tx += s1[y]     ty = 0; ty += yc * s0[y]                y = 0 .. R-1
+ *                  m = t0 / R^2;   ax = tx / D,  ay = ty / D  with  D = R * (R (R^2 - 1) / 12)  (plane)  or  ax = ay = 0  (mean)
+ *                  d = (float)((double)f - ((m + ax*xc) + ay*yc)), rounded to fp32 once
+ *   window       an optional separable table w[R] (host floats): d = (d * w[y]) * w[x], each fp32 product rounded on its own.
+ *                S_w = (sum_i (double)w[i]^2)^2, the sum in index order from 0; without a window S_w = R^2.
+ *   transform    the 2-D DFT of size R x R in fp32 by radix-2 decimation in time.  Twiddles T[t] = ((float)cos(2 pi t / R),
+ *                (float)(-sin(2 pi t / R))), t < R/2, computed on the host in double with the angle 2.0 * pi * t / R evaluated left
+ *                to right, and rounded to fp32; no device sincos.  The ROI is stored at [bitrev(y)][bitrev(x)] (bit reversal over
+ *                log2 R bits) with imaginary part 0.  A pass over a line z[0 .. R-1] is, for s = 1 .. log2 R, half = 2^(s-1), for
+ *                every k a multiple of 2^s and j < half, with (wr, wi) = T[j * R / 2^s], A = z[k+j], X = z[k+j+half]:
+ *                  tr = wr*X.re - wi*X.im;   ti = wr*X.im + wi*X.re        (4 multiplications, 2 additions, no contraction)
+ *                  z[k+j] = (A.re + tr, A.im + ti);   z[k+j+half] = (A.re - tr, A.im - ti)
+ *                (also for the unit twiddle T[0]).  First every row is passed in full, then the columns u = 0 .. R/2: the rows are
+ *                transforms of real data, so the other columns are taken as the mirror, P[v][u] = P[(R-v) % R][R-u] for u > R/2.
+ *   periodogram  P[v][u] = (double)re * (double)re + (double)im * (double)im  (the products are exact, the sum is rounded once).
+ *   accumulation per group and entry (v, u), in double, no atomics, in ONE order: the ROIs n = 0, 1, .. are cut into chunks of 16
+ *                consecutive ROIs (skipped ones included; they add nothing; the last chunk may be partial); a chunk's used ROIs are
+ *                added in order of n starting from 0; the group's chunk sums are added one by one, starting from 0, in chunk order.
+ *   result       nps[g][v][u] = (scale * sum) / ((double)rois_used[g] * S_w), DFT order (index 0 is DC), double [B,C,R,R].  White
+ *                noise of variance s^2 has a flat NPS of scale * s^2 (unit pixel pitch; frequencies in cycles per pixel), and
+ *                sum(nps) / R^2 is scale times the mean windowed variance (Parseval).  A group with no used ROI is the quiet NaN
+ *                0x7FF8000000000000 in every nps and radial entry.
+ *   radial       fu = u < R/2 ? u : u - R, fv likewise, d2 = fu^2 + fv^2.  Entry (v, u) belongs to the integer bin r with
+ *                (2r-1)^2 <= 4*d2 < (2r+1)^2 (for r = 0 only the upper bound counts): r = floor(sqrt(d2) + 1/2) in integers.
+ *                Bins r = 0 .. R/2; the corners beyond are dropped.  radial[g][r] = the double sum of the bin's nps entries in
+ *                row-major (v, then u) order starting from 0, divided by their number radial_count[r]; an empty bin is the quiet NaN
+ *                above.  Flag MI_NPS_EXCLUDE_AXES leaves out every entry with fu == 0 or fv == 0 (detector fixed-pattern lines
+ *                live on the axes); bin 0 is then empty.
+ * Arguments
+ *   window       HOST fp32 [roi] or NULL; it and the twiddles travel as kernel arguments
+ *   nps          device double [B*C][roi][roi];  radial  device double [B*C][roi/2+1];  radial_count  device int64 [roi/2+1];
+ *   rois_used, rois_skipped  device int64 [B*C];  all 8-byte aligned
+ *   workspace    mi_noise_power_spectrum_workspace_bytes: the chunk sums of the half plane, double [B*C][chunks][roi*(roi/2+1)], and
+ *                the chunks' used counts, int64 [B*C][chunks]; 8-byte aligned; the query answers 0 on sizes the call refuses
+ * An ROI is read as 16-byte words when W is a multiple of 4 and its first element is 16-byte aligned (judged for a and for b on their
+ * own) and element by element otherwise: the same bits.
+ * Three launches on `stream` (the ROIs; the chunk sums, scaling and mirror; the radial bins); allocates nothing; asynchronous.
+ * MI_EINVAL before anything is read, the rule named in mi_last_error, judged in this order: roi outside {32, 64, 128}; step < 1; B,
+ * K or C < 1; B*C > 65535; H < roi or W < roi; ROIs per member or chunks >= 2^31; detrend outside {0, 1, 2}; unknown flags; scale
+ * not finite; a null a, nps, radial, radial_count, rois_used, rois_skipped or workspace; an output or the workspace not 8-byte
+ * aligned, a or b not 4-byte aligned; workspace_bytes below the query's answer; any output (workspace included) overlapping an input
+ * or another output; a window entry that is not finite. */
+#define MI_NPS_DETREND_NONE  0
+#define MI_NPS_DETREND_MEAN  1
+#define MI_NPS_DETREND_PLANE 2
+#define MI_NPS_EXCLUDE_AXES  1
+size_t mi_noise_power_spectrum_workspace_bytes(int B, int K, int C, int H, int W, int roi, int step);
+int mi_noise_power_spectrum(const float* a, const float* b, int B, int K, int C, int H, int W, int roi, int step, int detrend,
+                            const float* window, double scale, int flags,
+                            double* nps, double* radial, int64_t* radial_count, int64_t* rois_used, int64_t* rois_skipped,
+                            void* workspace, size_t workspace_bytes, void* stream);
+
 /* TILED DENOISING: images of any size >= the tile, at their own resolution, as overlapping network-sized tiles (the reference
  * resizes every image to the training size first, Backend/run.py denoise_image_diffusion(..., img_size); nothing there tiles).
  * THE GEOMETRY (fixed), per axis with image length L, tile T, minimum overlap O, T <= L, 0 <= O <= T/2:

@@ -13,6 +13,7 @@ img_size -> sampler -> uint8 -> bicubic resize back -> PNG, with the reference's
                            [--update reference|ddim|dpmpp2m [--eta F] [--no-clip-x0] [--x0-out traj.npy]]
                            [--bit-depth 8|16 [--window P_LO,P_HI | --window-levels LO,HI]]
                            [--clean clean.png [--loss-out loss.json]]
+                           [--nps-out nps.json [--nps-roi 32|64|128] [--nps-step S]]
 
 Without a checkpoint (the trained weights are not distributed with the reference) the network is
 random-init, which exercises the path but does not denoise.  The reference helper has a latent
@@ -31,7 +32,8 @@ from PIL import Image
 
 from . import image16
 from .modules import UNetDiffusion
-from .sampler import DEFAULT_SCORE_LEVELS, MAX_QUANTILE_MEMBERS, DiffusionDenoiser, check_levels, check_update, ensemble_scores
+from .sampler import (DEFAULT_SCORE_LEVELS, MAX_QUANTILE_MEMBERS, NPS_ROIS, DiffusionDenoiser, check_levels, check_nps_args, check_update,
+                      ensemble_scores, noise_power_spectrum)
 
 
 def denoise_image_diffusion(model_path: Optional[str], test_image_path: str, device_type: str = "cuda",
@@ -44,7 +46,8 @@ def denoise_image_diffusion(model_path: Optional[str], test_image_path: str, dev
                             clip_x0: bool = True, x0_out: Optional[str] = None, bit_depth: int = 8, window: Optional[Sequence[float]] = None,
                             window_levels: Optional[Sequence[int]] = None, views: Optional[str] = None,
                             members: Optional[int] = None, clean: Optional[str] = None, loss_out: Optional[str] = None,
-                            truth: Optional[str] = None, scores_out: Optional[str] = None) -> Image.Image:
+                            truth: Optional[str] = None, scores_out: Optional[str] = None, nps_out: Optional[str] = None,
+                            nps_roi: Optional[int] = None, nps_step: Optional[int] = None) -> Image.Image:
     """compute (not a reference argument): arithmetic of the network, see UNetDiffusion -- None keeps the default.
     seed (not a reference argument; cddpm): the stochastic sampler's noise is drawn on the device from this seed, so the same
     call gives the same image again (DiffusionDenoiser.denoise); None: torch.randn, as the reference.
@@ -93,7 +96,28 @@ def denoise_image_diffusion(model_path: Optional[str], test_image_path: str, dev
     the image's).  The call prints the CRPS, the fair CRPS, the RMSE of the mean beside the spread and the coverage of the outermost
     pair of levels (quantiles if given, else 0.05, 0.25, 0.5, 0.75, 0.95) of the members against it (sampler.ensemble_scores; K <= 64);
     scores_out is the path of a .json file that receives everything, rank histogram and level counts included.  The sampler run and
-    the returned image are those of the call without truth."""
+    the returned image are those of the call without truth.
+    nps_out, nps_roi, nps_step (not reference arguments; every kind of run; on a GPU only): THE TEXTURE OF WHAT WAS REMOVED.  nps_out is
+    the path of a .json file that receives radial noise power spectra (sampler.noise_power_spectrum: Welch's method, plane detrend,
+    Hann window, ROIs of nps_roi = 32, 64 (default) or 128 pixels at step nps_step, default nps_roi / 2) taken at the sampler's
+    resolution (img_size, or with tile the image's own): always the method noise, input - output, which is flat if only noise was
+    removed; with samples, or tile and members, K >= 2, also the ensemble's spread, member - mean scaled by K / (K - 1); with truth
+    also the residual, output - truth.  Refused where the sampler's image is smaller than the ROI.  The sampler run and the returned
+    image are those of the call without nps_out."""
+    if (nps_roi is not None or nps_step is not None) and nps_out is None:
+        raise ValueError("--nps-roi and --nps-step need --nps-out PATH.json (the file that receives the spectra)")
+    if nps_out is not None:
+        nps_roi, nps_step = check_nps_args(64 if nps_roi is None else nps_roi, nps_step, "plane")
+        if torch.device(device_type).type != "cuda":
+            raise RuntimeError("--nps-out (noise power spectrum) runs only on a ROCm GPU: the kernel has no CPU fallback")
+        if tile is None and img_size < nps_roi:
+            raise ValueError(f"--nps-out: the sampler's image ({img_size}x{img_size}) is smaller than the ROI ({nps_roi}x{nps_roi}); "
+                             "use a smaller --nps-roi")
+        if tile is not None:      # the tiled run keeps the image's own size
+            with Image.open(test_image_path) as probe:
+                if min(probe.size) < nps_roi:
+                    raise ValueError(f"--nps-out: the image ({probe.size[1]}x{probe.size[0]}) is smaller than the ROI ({nps_roi}x{nps_roi}); "
+                                     "use a smaller --nps-roi")
     if loss_out is not None and clean is None:
         raise ValueError("--loss-out needs --clean PATH (the evaluation's clean image)")
     if scores_out is not None and truth is None:
@@ -223,7 +247,7 @@ def denoise_image_diffusion(model_path: Optional[str], test_image_path: str, dev
             what = f"Self-ensemble of {len(res.views)} views {res.views}, tiled"
         elif members is not None:
             res = diffusion.denoise_tiled_ensemble(input_tensor, inference_steps=inference_steps, members=members, tile=tile, overlap=overlap,
-                                                   seed=seed, quantiles=quantiles, return_samples=truth is not None)
+                                                   seed=seed, quantiles=quantiles, return_samples=truth is not None or nps_out is not None)
             what = f"Ensemble of {members} samples, tiled"
         else:
             res = diffusion.denoise_tiled(input_tensor, inference_steps=inference_steps, tile=tile, overlap=overlap, seed=seed, **rule)
@@ -234,6 +258,9 @@ def denoise_image_diffusion(model_path: Optional[str], test_image_path: str, dev
         print(f"Inference time: {time.time() - start_time:.2f} seconds")
         if truth is not None:
             score(res.samples, truth, None, bit_depth, win, quantiles if quantiles is not None else DEFAULT_SCORE_LEVELS, res.seed, scores_out)
+        if nps_out is not None:
+            write_nps(nps_out, nps_roi, nps_step, input_tensor, res.mean if tiled_ensemble else res.image,
+                      res.samples if members is not None else None, truth, None, bit_depth, win, res.seed)
         if tiled_ensemble:      # the mean of values in [0, 1] is in [0, 1]: stored as the tiled image is; the maps stay float, at the image's size
             if std_out is not None:
                 np.save(std_out, res.std[0, 0].cpu().numpy())
@@ -285,7 +312,7 @@ def denoise_image_diffusion(model_path: Optional[str], test_image_path: str, dev
             np.save(quantiles_out, ens.quantiles.reshape(len(quantiles), img_size, img_size).cpu().numpy())
     elif samples is not None:
         ens = diffusion.denoise_ensemble(input_tensor, inference_steps=inference_steps, members=samples, seed=seed, quantiles=quantiles,
-                                         return_samples=truth is not None, **rule)
+                                         return_samples=truth is not None or nps_out is not None, **rule)
         denoised = ens.mean                               # a mean of values in [0, 1]: in [0, 1]
         print(f"Ensemble of {samples} samples, seed {ens.seed}")
         if truth is not None:
@@ -304,6 +331,9 @@ def denoise_image_diffusion(model_path: Optional[str], test_image_path: str, dev
     print(f"Inference time: {time.time() - start_time:.2f} seconds")
     if clean is not None:
         evaluate(diffusion, clean, input_tensor, denoised, img_size, bit_depth, win, seed, loss_out)
+    if nps_out is not None:
+        write_nps(nps_out, nps_roi, nps_step, input_tensor, denoised.reshape(1, 1, img_size, img_size),
+                  ens.samples if samples is not None else None, truth, img_size, bit_depth, win, ens.seed if samples is not None else seed)
 
     if win is not None:
         plane = denoised.reshape(img_size, img_size).float()
@@ -373,6 +403,41 @@ def score(samples: torch.Tensor, truth_path: str, img_size: Optional[int], bit_d
         with open(scores_out, "w") as f:
             json.dump(result, f, indent=1)
         print(f"Scores saved: {scores_out}")
+    return result
+
+
+def write_nps(nps_out: str, roi: int, step: int, noisy: torch.Tensor, output: torch.Tensor, samples: Optional[torch.Tensor],
+              truth_path: Optional[str], img_size: Optional[int], bit_depth: int, win, seed) -> dict:
+    """--nps-out: the radial noise power spectra of the run at the sampler's resolution, printed in short and written as JSON.  noisy
+    and output are [1, 1, H, W]; samples [1, K, 1, H, W] or None; the truth goes through the recipe of the noisy image."""
+    import json
+
+    def entry(sp, **more):
+        return dict(radial=sp.radial[0, 0].tolist(), radial_count=sp.radial_count.tolist(), rois_used=int(sp.rois_used[0, 0]),
+                    rois_skipped=int(sp.rois_skipped[0, 0]), variance=float(sp.variance()[0, 0]), **more)
+
+    out = output.float().contiguous()
+    first = noise_power_spectrum(noisy.float(), out, roi, step)
+    result = {"roi": roi, "step": step, "detrend": "plane", "window": "hann", "height": int(out.shape[2]), "width": int(out.shape[3]),
+              "seed": seed, "freqs": first.freqs.tolist(), "method_noise": entry(first)}
+    if samples is not None and samples.shape[1] >= 2:
+        K = int(samples.shape[1])
+        result["ensemble_spread"] = entry(noise_power_spectrum(samples, out, roi, step, scale=K / (K - 1)), members=K)
+    if truth_path is not None:
+        truth = load_counterpart(truth_path, out.device, img_size, bit_depth, win)
+        if tuple(truth.shape) != tuple(out.shape):
+            raise ValueError(f"--truth is {truth.shape[2]}x{truth.shape[3]}, the output {out.shape[2]}x{out.shape[3]}: the truth image must have "
+                             "the size of --image")
+        result["residual"] = entry(noise_power_spectrum(out, truth.float(), roi, step))
+    print(f"Noise power spectrum ({roi} x {roi} ROIs at step {step}, plane detrend, Hann window; cycles per pixel):")
+    for name in ("method_noise", "ensemble_spread", "residual"):
+        if name in result:
+            e = result[name]
+            lowf, highf = e["radial"][1], e["radial"][roi // 4]
+            print(f"  {name}: {e['rois_used']} ROIs, variance {e['variance']:.3e}, NPS at f = {1 / roi:.4f}: {lowf:.3e}, at f = 0.25: {highf:.3e}")
+    with open(nps_out, "w") as f:
+        json.dump(result, f, indent=1)
+    print(f"Noise power spectra saved: {nps_out}")
     return result
 
 
@@ -459,7 +524,21 @@ def main(argv=None) -> None:
                          "RMSE, spread and interval coverage of the ensemble against it (levels: --quantiles, else 0.05,0.25,0.5,0.75,0.95)")
     ap.add_argument("--scores-out", default=None, metavar="PATH.json",
                     help="with --truth: write the scores, the rank histogram and the level counts as JSON")
+    ap.add_argument("--nps-out", default=None, metavar="PATH.json",
+                    help="write radial noise power spectra (Welch, plane detrend, Hann window) at the sampler's resolution: the method noise "
+                         "input - output; with --samples K or --tile N --members K (K >= 2) also the ensemble's spread; with --truth also "
+                         "the residual output - truth")
+    ap.add_argument("--nps-roi", type=int, default=None, metavar="R", help="with --nps-out: the ROI size, 32, 64 (default) or 128")
+    ap.add_argument("--nps-step", type=int, default=None, metavar="S", help="with --nps-out: the ROI step (default R / 2)")
     args = ap.parse_args(argv)
+    if (args.nps_roi is not None or args.nps_step is not None) and args.nps_out is None:
+        ap.error("--nps-roi and --nps-step need --nps-out PATH.json")
+    if args.nps_roi is not None and args.nps_roi not in NPS_ROIS:
+        ap.error(f"--nps-roi needs one of {NPS_ROIS}")
+    if args.nps_step is not None and args.nps_step < 1:
+        ap.error("--nps-step needs S >= 1")
+    if args.nps_out is not None and args.tile is None and args.img_size < (args.nps_roi or 64):
+        ap.error(f"--nps-out: the sampler's image ({args.img_size}x{args.img_size}) is smaller than the ROI ({args.nps_roi or 64}); use a smaller --nps-roi")
     if args.scores_out is not None and args.truth is None:
         ap.error("--scores-out needs --truth PATH")
     if args.truth is not None:
@@ -540,7 +619,8 @@ def main(argv=None) -> None:
                                        **({} if args.views is None else {"views": args.views}),
                                        **({} if args.members is None else {"members": args.members}),
                                        **({} if args.clean is None else {"clean": args.clean, "loss_out": args.loss_out}),
-                                       **({} if args.truth is None else {"truth": args.truth, "scores_out": args.scores_out}))
+                                       **({} if args.truth is None else {"truth": args.truth, "scores_out": args.scores_out}),
+                                       **({} if args.nps_out is None else {"nps_out": args.nps_out, "nps_roi": args.nps_roi, "nps_step": args.nps_step}))
     restored.save(args.out, quality=95)
     print(f"\nResult saved: {args.out}")
 

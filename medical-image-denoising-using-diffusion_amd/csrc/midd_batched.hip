@@ -144,6 +144,55 @@ extern "C" int mi_ensemble_scores(const float* samples, const float* truth, int 
                                            (hipStream_t)stream), "ensemble_scores");
 }
 
+// The noise power spectrum (nps.hip; include/midd.h: THE NOISE POWER SPECTRUM).  The rules in the documented order; nothing is read,
+// not even the host window, before every rule has passed
+static int check_nps_shape(int B, int K, int C, int H, int W, int roi, int step) {
+    if (roi != 32 && roi != 64 && roi != 128) return fail(MI_EINVAL, "roi %d outside {32, 64, 128}: the ROI transform is built for these sizes", roi);
+    if (step < 1) return fail(MI_EINVAL, "step %d below 1 (limit: step >= 1)", step);
+    if (B < 1 || K < 1 || C < 1) return fail(MI_EINVAL, "B %d, K %d, C %d: each must be at least 1", B, K, C);
+    if ((long long)B * C > 65535) return fail(MI_EINVAL, "B * C = %lld groups outside [1, 65535] (limit of the kernel's grid)", (long long)B * C);
+    if (H < roi || W < roi) return fail(MI_EINVAL, "image %d x %d smaller than the ROI %d x %d: there are no partial ROIs", H, W, roi, roi);
+    const unsigned long long per_member = (unsigned long long)((H - roi) / step + 1) * (unsigned long long)((W - roi) / step + 1);
+    if (per_member > 0x7FFFFFFFull || nps_chunks(K, H, W, roi, step) > 0x7FFFFFFFull)
+        return fail(MI_EINVAL, "too many ROIs: %llu per member, K %d (limit: ROIs per member < 2^31, chunks of 16 ROIs < 2^31)", per_member, K);
+    return MI_OK;
+}
+
+extern "C" size_t mi_noise_power_spectrum_workspace_bytes(int B, int K, int C, int H, int W, int roi, int step) {
+    if (check_nps_shape(B, K, C, H, W, roi, step)) return 0;
+    return nps_workspace_bytes(B * C, K, H, W, roi, step);
+}
+
+extern "C" int mi_noise_power_spectrum(const float* a, const float* b, int B, int K, int C, int H, int W, int roi, int step, int detrend,
+                                       const float* window, double scale, int flags, double* nps, double* radial, int64_t* radial_count,
+                                       int64_t* rois_used, int64_t* rois_skipped, void* workspace, size_t workspace_bytes, void* stream) {
+    if (int rc = check_nps_shape(B, K, C, H, W, roi, step)) return rc;
+    if (detrend < MI_NPS_DETREND_NONE || detrend > MI_NPS_DETREND_PLANE)
+        return fail(MI_EINVAL, "detrend %d outside {0 none, 1 mean, 2 plane}", detrend);
+    if (flags & ~MI_NPS_EXCLUDE_AXES) return fail(MI_EINVAL, "flags 0x%x: unknown bits (known: MI_NPS_EXCLUDE_AXES = 1)", (unsigned)flags);
+    if (!(scale == scale) || scale - scale != 0.0) return fail(MI_EINVAL, "scale %g is not finite", scale);
+    if (!a || !nps || !radial || !radial_count || !rois_used || !rois_skipped || !workspace) return fail(MI_EINVAL, "null argument");
+    for (const void* p : {(const void*)nps, (const void*)radial, (const void*)radial_count, (const void*)rois_used, (const void*)rois_skipped, (const void*)workspace})
+        if (reinterpret_cast<uintptr_t>(p) & 7) return fail(MI_EINVAL, "nps, radial, radial_count, rois_used, rois_skipped and workspace must be 8-byte aligned");
+    for (const void* p : {(const void*)a, (const void*)b})
+        if (reinterpret_cast<uintptr_t>(p) & 3) return fail(MI_EINVAL, "a and b must be 4-byte aligned");
+    const size_t need = nps_workspace_bytes(B * C, K, H, W, roi, step);
+    if (workspace_bytes < need) return fail(MI_EINVAL, "workspace too small: need %zu bytes (mi_noise_power_spectrum_workspace_bytes), got %zu", need, workspace_bytes);
+    const size_t groups = (size_t)B * C, img = (size_t)H * W * sizeof(float), bins = (size_t)roi / 2 + 1;
+    const Buf buf[8] = {{a, groups * K * img, "a"}, {b, groups * img, "b"}, {nps, groups * roi * roi * sizeof(double), "nps"},
+                        {radial, groups * bins * sizeof(double), "radial"}, {radial_count, bins * sizeof(int64_t), "radial_count"},
+                        {rois_used, groups * sizeof(int64_t), "rois_used"}, {rois_skipped, groups * sizeof(int64_t), "rois_skipped"},
+                        {workspace, need, "workspace"}};
+    if (int rc = check_no_overlap(buf, 8, "a and b are read while every output and the workspace are written")) return rc;
+    if (window)
+        for (int i = 0; i < roi; ++i)
+            if (!(window[i] == window[i]) || window[i] - window[i] != 0.0f) return fail(MI_EINVAL, "window[%d] is not finite", i);
+    static_assert(sizeof(long long) == sizeof(int64_t), "the counters are 64-bit");
+    return launched(nps_launch(a, b, B, K, C, H, W, roi, step, detrend, window, scale, (flags & MI_NPS_EXCLUDE_AXES) ? 1 : 0, nps, radial,
+                               reinterpret_cast<long long*>(radial_count), reinterpret_cast<long long*>(rois_used),
+                               reinterpret_cast<long long*>(rois_skipped), workspace, (hipStream_t)stream), "noise_power_spectrum");
+}
+
 // ---------------------------------------------------------------------------- the batched calls: virtual samples in passes
 // mi_denoise_ensemble, mi_denoise_tiled and mi_denoise_tiled_ensemble run `rounds` x V virtual samples of h x w each through the
 // sampler loop in passes of L.pass.  Each judges its own argument rules and its table of buffers (check_no_overlap), then shares

@@ -399,6 +399,19 @@ hipError_t ensemble_scores_launch(const float* samples, const float* truth, int 
                                   double* sums, unsigned long long* invalid, unsigned long long* rank_hist, unsigned long long* counts,
                                   float* crps_map, double* part, hipStream_t s);
 
+// The noise power spectrum of f = a - b (nps.hip; include/midd.h: THE NOISE POWER SPECTRUM).  a [B][K][C][H][W], b [B][C][H][W] or
+// null; R in {32, 64, 128}, S >= 1, detrend 0 none / 1 mean / 2 plane, window a HOST table of R floats or null -> nps double
+// [B*C][R][R], radial double [B*C][R/2+1], radial_count [R/2+1], rois_used and rois_skipped [B*C]; ws: nps_workspace_bytes (the chunk
+// sums of the half plane, double [B*C][chunks][R*(R/2+1)], then the chunks' used counts).  B*C <= 65535, chunks < 2^31.  The twiddle and
+// window tables travel as a kernel argument
+constexpr int NPS_CHUNK = 16;
+struct NpsTables { float tc[64]; float ts[64]; float w[128]; };
+unsigned long long nps_chunks(int K, int H, int W, int R, int S);
+size_t nps_workspace_bytes(int groups, int K, int H, int W, int R, int S);
+hipError_t nps_launch(const float* a, const float* b, int B, int K, int C, int H, int W, int R, int S, int detrend, const float* window,
+                      double scale, int exclude_axes, double* nps, double* radial, long long* radial_count, long long* rois_used,
+                      long long* rois_skipped, void* ws, hipStream_t s);
+
 // Geometric self-ensemble (include/midd.h: THE GEOMETRY).  A view list is 1 .. 8 distinct codes g = 4 t + 2 fy + fx in the caller's
 // order; it travels as kernel arguments.  Transposing codes (g >= 4) need H == W.
 constexpr int DIHEDRAL_MAX_VIEWS = 8;

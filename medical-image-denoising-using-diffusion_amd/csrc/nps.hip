@@ -1,0 +1,387 @@
+// The noise power spectrum of a field f = a - b (include/midd.h: THE NOISE POWER SPECTRUM; tests/nps_reference.py restates it in
+// numpy): Welch's method over overlapping R x R regions of interest (ROIs) -- detrend, window, 2-D DFT in fp32, |F|^2 in double,
+// averaged over the ROIs of a group (b, c) and binned by radial frequency.
+//   nps_roi_kernel<R>      a workgroup of 256 lanes owns ONE chunk of NPS_CHUNK = 16 consecutive ROIs of one group and walks them in
+//                          order.  Per ROI: the rows are loaded (16-byte loads where W is a multiple of 4 and the ROI's first element
+//                          is 16-byte aligned, elements otherwise: the values are the same) as f = a - b into the lane's registers
+//                          and, for the row sums, into the imaginary slots in natural order, and a non-finite f
+//                          marks the ROI skipped; R lanes add a row each (s0 = sum f, s1 = sum xc f, x from 0), lane 0 adds the rows
+//                          (y from 0) and forms m, ax, ay; every element is detrended in double, rounded once, multiplied by w[y]
+//                          and then by w[x], and written as (d, 0) at [bitrev(y)][bitrev(x)].  Two passes of
+//                          log2 R radix-2 decimation-in-time stages run in place, over all R rows and then over the columns
+//                          0 .. R/2 only (the row transform of real data is Hermitian; the other columns follow by
+//                          P[v][u] = P[(R - v) % R][R - u]).  The lane owns the entries idx = lane + 256 e of the half plane
+//                          [R][R/2 + 1] and adds P = re^2 + im^2 to its double accumulators, ROI after ROI; the chunk's sums and its
+//                          count of used ROIs go to the workspace.  No atomics.
+//                          LDS: ONE complex plane of interleaved (re, im) words, R rows with pitch R + 1 words.  The row pass
+//                          gives consecutive lanes consecutive ROWS at one butterfly index (odd pitch: the 32 lanes of a half wave
+//                          on 32 different bank pairs, the twiddle one broadcast read), the column pass gives them consecutive
+//                          columns.  With the twiddle and window tables and the R + R row sums: 8.7 KiB, 33.7 KiB and 131.7 KiB
+//                          for R = 32, 64, 128.
+//   nps_sum_kernel<R>      one lane per half-plane entry adds the group's chunk sums one by one from 0 in chunk order, scales, and
+//                          writes the entry and its mirror; lane 0 of block 0 leaves rois_used and rois_skipped
+//   nps_radial_kernel<R>   one wave per (group, bin) over the group's plane in LDS: the rows in order, per row one ballot over the
+//                          columns and the bin's entries added in ascending column order, i.e. row-major
+// Contraction is off for the whole unit: a complex multiply is four v_mul_f32 and two v_add/v_sub_f32.
+#include <cmath>
+#include "midd_internal.h"
+#include "pointwise_common.h"
+
+#pragma clang fp contract(off)
+
+namespace midd {
+
+constexpr int NPS_THREADS = 256;
+static_assert(NPS_CHUNK == 16, "THE NOISE POWER SPECTRUM: chunks of 16 consecutive ROIs");
+constexpr unsigned long long NPS_QNAN = 0x7FF8000000000000ull;
+
+__device__ __forceinline__ bool nps_finite(float v) { return (__float_as_uint(v) & 0x7F800000u) != 0x7F800000u; }
+
+template <int R> struct NpsGeom {
+    static constexpr int LOG = R == 32 ? 5 : R == 64 ? 6 : 7;
+    static constexpr int NC = R / 2 + 1;                 // columns kept by the column pass
+    static constexpr int P = R + 1;                      // LDS pitch in floats
+    static constexpr int HALF = R * NC;                  // entries of the half plane
+    static constexpr int NACC = (HALF + NPS_THREADS - 1) / NPS_THREADS;
+};
+
+__device__ __forceinline__ bool nps_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+// a lane's row quads of one ROI plane: 16-byte loads (V = 4) or four element loads each (V = 1), all issued before any is used.  The
+// choice is made once per ROI and is uniform over the workgroup: a choice per quad is a divergent branch around every load, which
+// waits for each load on its own
+template <int R, int NQ, int V>
+__device__ __forceinline__ void nps_load_quads(const float* __restrict__ p, size_t W, int tid, f32x4 (&v)[NQ]) {
+#pragma unroll
+    for (int e = 0; e < NQ; ++e) {
+        const int q = tid + NPS_THREADS * e, y = q / (R / 4), x4 = (q % (R / 4)) * 4;
+        const float* src = p + (size_t)y * W + x4;
+        if constexpr (V == 4) v[e] = *reinterpret_cast<const f32x4*>(src);
+        else v[e] = (f32x4){src[0], src[1], src[2], src[3]};
+    }
+}
+
+// One fp32 product as one v_mul_f32.  Left to the compiler the four products of a butterfly pair up as v_pk_mul_f32 with an op_sel
+// bit (the twiddle component broadcast from the high half of its register pair), the form tools/isa_hazard_audit.py bans
+__device__ __forceinline__ float nps_mul(float a, float b) {
+    float r;
+    asm("v_mul_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
+
+// one radix-2 decimation-in-time butterfly on (ia, ib) with twiddle w: t = w * z[ib] as four products and two sums
+__device__ __forceinline__ void nps_butterfly(float2* z, int ia, int ib, float2 w) {
+    const float2 x = z[ib], u = z[ia];
+    const float tr = nps_mul(w.x, x.x) - nps_mul(w.y, x.y);
+    const float ti = nps_mul(w.x, x.y) + nps_mul(w.y, x.x);
+    z[ia] = make_float2(u.x + tr, u.y + ti);
+    z[ib] = make_float2(u.x - tr, u.y - ti);
+}
+
+// grid (chunks, groups); part [G][chunks][HALF] doubles, used [G][chunks]
+template <int R>
+__global__ __launch_bounds__(NPS_THREADS)
+void nps_roi_kernel(const float* __restrict__ a, const float* __restrict__ b, int K, int C, int H, int W, int S, int ny, int nx,
+                    unsigned long long n_rois, int detrend, int windowed, NpsTables tab, double* __restrict__ part, long long* __restrict__ used) {
+    using G = NpsGeom<R>;
+    constexpr int LOG = G::LOG, NC = G::NC, P = G::P, HALF = G::HALF, NACC = G::NACC;
+    constexpr int COLT = ((NC * (R / 2) + NPS_THREADS - 1) / NPS_THREADS + 1) / 2 * 2;      // column-pass trips per lane, made even: 2, 6, 18
+    constexpr int NQ = R * R / 4 / NPS_THREADS;                          // row quads per lane: 1, 4, 16
+    __shared__ float2 z[R * P];                                          // (re, im), pitch R + 1
+    __shared__ float2 tw[R / 2];
+    __shared__ float win[R];
+    __shared__ double rs0[R], rs1[R];
+    __shared__ double coef[3];
+    __shared__ int bad;
+    const int tid = threadIdx.x;
+    const unsigned chunk = blockIdx.x, chunks = gridDim.x;
+    const size_t g = blockIdx.y;
+    const size_t bi = g / (unsigned)C, c = g % (unsigned)C;
+    const size_t plane = (size_t)H * W;
+    if (tid < R / 2) tw[tid] = make_float2(tab.tc[tid], tab.ts[tid]);
+    if (tid < R) win[tid] = tab.w[tid];
+    double acc[NACC];
+#pragma unroll
+    for (int e = 0; e < NACC; ++e) acc[e] = 0.0;
+    long long n_used = 0;
+    const unsigned long long r0 = (unsigned long long)chunk * NPS_CHUNK;
+    const unsigned long long r1 = r0 + NPS_CHUNK < n_rois ? r0 + NPS_CHUNK : n_rois;
+    const unsigned per_member = (unsigned)ny * (unsigned)nx;            // (< 2^31: nps_launch)
+    size_t m = r0 / per_member;
+    unsigned rem = (unsigned)(r0 % per_member);
+#pragma unroll 1
+    for (unsigned long long r = r0; r < r1; ++r, ++rem) {
+        if (rem == per_member) { rem = 0; ++m; }
+        const size_t oy = (size_t)(rem / (unsigned)nx) * S, ox = (size_t)(rem % (unsigned)nx) * S;
+        const float* pa = a + ((bi * K + m) * C + c) * plane + oy * W + ox;
+        const float* pb = b ? b + (bi * C + c) * plane + oy * W + ox : nullptr;
+        if (tid == 0) bad = 0;
+        __syncthreads();
+        // f = a - b: the lane keeps its quads; with a detrend they also go to the imaginary slots, in natural order, for the row sums
+        f32x4 fq[NQ];
+        {
+            // every row quad of the ROI is 16-byte aligned when W is a multiple of 4 and the ROI's first element is aligned
+            const bool wide = (W & 3) == 0;
+            if (wide && nps_aligned16(pa)) nps_load_quads<R, NQ, 4>(pa, (size_t)W, tid, fq);
+            else nps_load_quads<R, NQ, 1>(pa, (size_t)W, tid, fq);
+            if (pb) {
+                f32x4 sub[NQ];
+                if (wide && nps_aligned16(pb)) nps_load_quads<R, NQ, 4>(pb, (size_t)W, tid, sub);
+                else nps_load_quads<R, NQ, 1>(pb, (size_t)W, tid, sub);
+#pragma unroll
+                for (int e = 0; e < NQ; ++e) fq[e] = (f32x4){fq[e].x - sub[e].x, fq[e].y - sub[e].y, fq[e].z - sub[e].z, fq[e].w - sub[e].w};
+            }
+        }
+        bool nonfinite = false;
+#pragma unroll
+        for (int e = 0; e < NQ; ++e) {
+            const int q = tid + NPS_THREADS * e, y = q / (R / 4), x4 = (q % (R / 4)) * 4;
+            const f32x4 v = fq[e];
+            nonfinite = nonfinite || !nps_finite(v.x) || !nps_finite(v.y) || !nps_finite(v.z) || !nps_finite(v.w);
+            if (detrend != 0) {
+                float2* dst = z + y * P + x4;
+                dst[0].y = v.x; dst[1].y = v.y; dst[2].y = v.z; dst[3].y = v.w;
+            }
+        }
+        if (nonfinite) atomicOr(&bad, 1);
+        __syncthreads();
+        const int skip = bad;
+        if (detrend != 0 && !skip) {
+            if (tid < R) {
+                double s0 = 0.0, s1 = 0.0;
+#pragma unroll 8
+                for (int x = 0; x < R; ++x) {
+                    const double fv = (double)z[tid * P + x].y;
+                    s0 = add_rn64(s0, fv);
+                    s1 = add_rn64(s1, mul_rn64((double)x - 0.5 * (R - 1), fv));
+                }
+                rs0[tid] = s0; rs1[tid] = s1;
+            }
+            __syncthreads();
+            if (tid == 0) {
+                double t0 = 0.0, tx = 0.0, ty = 0.0;
+#pragma unroll 8
+                for (int y = 0; y < R; ++y) {
+                    t0 = add_rn64(t0, rs0[y]);
+                    tx = add_rn64(tx, rs1[y]);
+                    ty = add_rn64(ty, mul_rn64((double)y - 0.5 * (R - 1), rs0[y]));
+                }
+                const double den = (double)R * ((double)R * ((double)R * R - 1.0) / 12.0);      // exact integers
+                coef[0] = __ddiv_rn(t0, (double)(R * R));
+                coef[1] = detrend == 2 ? __ddiv_rn(tx, den) : 0.0;
+                coef[2] = detrend == 2 ? __ddiv_rn(ty, den) : 0.0;
+            }
+        }
+        __syncthreads();                      // (also: every lane has read `bad`, and the row sums have read the imaginary slots)
+        if (skip) continue;
+        {
+            const double m0 = coef[0], ax = coef[1], ay = coef[2];
+#pragma unroll
+            for (int e = 0; e < NQ; ++e) {
+                const int q = tid + NPS_THREADS * e, y = q / (R / 4), x4 = (q % (R / 4)) * 4;
+                const float fs[4] = {fq[e].x, fq[e].y, fq[e].z, fq[e].w};
+                const int yr = (int)(__brev((unsigned)y) >> (32 - LOG)) * P;
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const int x = x4 + i;
+                    float d = fs[i];
+                    if (detrend != 0) {
+                        const double xc = (double)x - 0.5 * (R - 1), yc = (double)y - 0.5 * (R - 1);
+                        const double t = add_rn64(add_rn64(m0, mul_rn64(ax, xc)), mul_rn64(ay, yc));
+                        d = __double2float_rn(sub_rn64((double)fs[i], t));
+                    }
+                    if (windowed) { d = d * win[y]; d = d * win[x]; }
+                    z[yr + (int)(__brev((unsigned)x) >> (32 - LOG))] = make_float2(d, 0.0f);
+                }
+            }
+        }
+        __syncthreads();
+        // the rows: every row, every column.  Consecutive lanes take consecutive ROWS (pitch R + 1: no two lanes of a half wave on
+        // one bank) and share the butterfly index, so the twiddle is one broadcast read
+#pragma unroll 1
+        for (int s = 1; s <= LOG; ++s) {
+            const int half = 1 << (s - 1);
+#pragma unroll 2
+            for (int e = 0; e < R * R / 2 / NPS_THREADS; ++e) {             // (a constant, even trip count: the asm products are convergent)
+                const int q = tid + NPS_THREADS * e, row = q % R, i = q / R;
+                const int j = i & (half - 1), k = (i >> (s - 1)) << s;
+                const int ia = row * P + k + j;
+                nps_butterfly(z, ia, ia + half, tw[j << (LOG - s)]);
+            }
+            __syncthreads();
+        }
+        // the columns 0 .. R/2: consecutive lanes take consecutive columns
+#pragma unroll 1
+        for (int s = 1; s <= LOG; ++s) {
+            const int half = 1 << (s - 1);
+#pragma unroll 2
+            for (int e = 0; e < COLT; ++e) {
+                const int q = tid + NPS_THREADS * e, col = q % NC, i = q / NC;
+                const int j = i & (half - 1), k = (i >> (s - 1)) << s;
+                const int ia = (k + j) * P + col;
+                if (q < NC * (R / 2)) nps_butterfly(z, ia, ia + half * P, tw[j << (LOG - s)]);
+            }
+            __syncthreads();
+        }
+#pragma unroll
+        for (int e = 0; e < NACC; ++e) {
+            const int idx = tid + NPS_THREADS * e;
+            if (idx < HALF) {
+                const float2 v = z[(idx / NC) * P + idx % NC];
+                const double fr = (double)v.x, fi = (double)v.y;
+                acc[e] = add_rn64(acc[e], add_rn64(mul_rn64(fr, fr), mul_rn64(fi, fi)));
+            }
+        }
+        ++n_used;
+        __syncthreads();                      // the plane is written again by the next ROI
+    }
+    double* dst = part + (g * chunks + chunk) * (size_t)HALF;
+#pragma unroll
+    for (int e = 0; e < NACC; ++e) {
+        const int idx = tid + NPS_THREADS * e;
+        if (idx < HALF) dst[idx] = acc[e];
+    }
+    if (tid == 0) used[g * chunks + chunk] = n_used;
+}
+
+// grid (ceil(HALF / 64), groups): the chunk sums of one entry, one by one from 0 in chunk order; NPS_SUM_BATCH independent loads are in
+// flight per step of the dependent chain of adds
+constexpr int NPS_SUM_THREADS = 64;
+constexpr int NPS_SUM_BATCH = 64;
+template <int R>
+__global__ __launch_bounds__(NPS_SUM_THREADS)
+void nps_sum_kernel(const double* __restrict__ part, const long long* __restrict__ used, unsigned chunks, unsigned long long n_rois,
+                    double scale, double sw, double* __restrict__ nps, long long* __restrict__ rois_used, long long* __restrict__ rois_skipped) {
+    using G = NpsGeom<R>;
+    constexpr int NC = G::NC, HALF = G::HALF;
+    const size_t g = blockIdx.y;
+    const int idx = blockIdx.x * NPS_SUM_THREADS + threadIdx.x;
+    // the used ROIs of the group: integers, so the order is free -- a strided share per lane, folded over the wave
+    long long n = 0;
+#pragma unroll 8
+    for (unsigned c = threadIdx.x; c < chunks; c += NPS_SUM_THREADS) n += used[g * chunks + c];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) n += __shfl_xor(n, off);
+    if (idx == 0) { rois_used[g] = n; rois_skipped[g] = (long long)n_rois - n; }
+    if (idx >= HALF) return;
+    const double* p = part + g * chunks * (size_t)HALF + idx;
+    double s = 0.0;
+    unsigned c = 0;
+    for (; c + NPS_SUM_BATCH <= chunks; c += NPS_SUM_BATCH) {
+        double v[NPS_SUM_BATCH];
+#pragma unroll
+        for (int j = 0; j < NPS_SUM_BATCH; ++j) v[j] = p[(size_t)(c + j) * HALF];
+#pragma unroll
+        for (int j = 0; j < NPS_SUM_BATCH; ++j) s = add_rn64(s, v[j]);
+    }
+    for (; c < chunks; ++c) s = add_rn64(s, p[(size_t)c * HALF]);
+    const double val = n > 0 ? __ddiv_rn(mul_rn64(scale, s), mul_rn64((double)n, sw)) : __longlong_as_double((long long)NPS_QNAN);
+    const int v = idx / NC, u = idx % NC;
+    double* out = nps + g * (size_t)(R * R);
+    out[v * R + u] = val;
+    if (u > 0 && u < R / 2) out[((R - v) % R) * R + (R - u)] = val;
+}
+
+// grid (ceil((R/2 + 1) / 4), groups), one wave per bin.  The workgroup first copies the group's plane to LDS (R^2 doubles: 8, 32 and
+// 128 KiB): a bin's entries are added one after the other, and from global memory every one of them was a dependent round trip
+template <int R>
+__global__ __launch_bounds__(NPS_THREADS)
+void nps_radial_kernel(const double* __restrict__ nps, const long long* __restrict__ rois_used, int exclude_axes,
+                       double* __restrict__ radial, long long* __restrict__ radial_count) {
+    __shared__ double plane[R * R];
+    const size_t g = blockIdx.y;
+    const double* src = nps + g * (size_t)(R * R);
+#pragma unroll 4
+    for (int i = threadIdx.x; i < R * R; i += NPS_THREADS) plane[i] = src[i];
+    __syncthreads();
+    const int r = blockIdx.x * (NPS_THREADS / 64) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (r > R / 2) return;
+    const int lo = (2 * r - 1) * (2 * r - 1), hi = (2 * r + 1) * (2 * r + 1);
+    double s = 0.0;
+    long long cnt = 0;
+#pragma unroll 2
+    for (int v = 0; v < R; ++v) {
+        const int fv = v < R / 2 ? v : v - R;
+        for (int ub = 0; ub < R; ub += 64) {
+            const int u = ub + lane;
+            const int fu = u < R / 2 ? u : u - R;
+            const int d4 = 4 * (fu * fu + fv * fv);
+            bool in = u < R && (r == 0 || lo <= d4) && d4 < hi;
+            if (exclude_axes && (fu == 0 || fv == 0)) in = false;
+            const double val = plane[v * R + (u < R ? u : 0)];
+            unsigned long long mask = __ballot(in);
+            while (mask) {                                  // ascending columns: row-major
+                const int bit = __ffsll((long long)mask) - 1;
+                s = add_rn64(s, __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(val), bit), __builtin_amdgcn_readlane(__double2loint(val), bit)));
+                ++cnt;
+                mask &= mask - 1;
+            }
+        }
+    }
+    if (lane == 0) {
+        const bool none = cnt == 0 || rois_used[g] == 0;
+        radial[g * (R / 2 + 1) + r] = none ? __longlong_as_double((long long)NPS_QNAN) : __ddiv_rn(s, (double)cnt);
+        if (g == 0) radial_count[r] = cnt;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------- launches
+static unsigned long long nps_rois(int K, int H, int W, int R, int S) {
+    return (unsigned long long)K * (unsigned long long)((H - R) / S + 1) * (unsigned long long)((W - R) / S + 1);
+}
+
+unsigned long long nps_chunks(int K, int H, int W, int R, int S) { return (nps_rois(K, H, W, R, S) + NPS_CHUNK - 1) / NPS_CHUNK; }
+
+size_t nps_workspace_bytes(int groups, int K, int H, int W, int R, int S) {
+    return (size_t)groups * nps_chunks(K, H, W, R, S) * ((size_t)R * (R / 2 + 1) + 1) * sizeof(double);
+}
+
+template <int R>
+static hipError_t nps_dispatch(const float* a, const float* b, int B, int K, int C, int H, int W, int S, int detrend, int windowed,
+                               const NpsTables& tab, double scale, double sw, int exclude_axes, double* nps, double* radial,
+                               long long* radial_count, long long* rois_used, long long* rois_skipped, void* ws, hipStream_t s) {
+    using G = NpsGeom<R>;
+    const int groups = B * C, ny = (H - R) / S + 1, nx = (W - R) / S + 1;
+    const unsigned long long n_rois = nps_rois(K, H, W, R, S);
+    const unsigned chunks = (unsigned)nps_chunks(K, H, W, R, S);
+    double* part = static_cast<double*>(ws);
+    long long* used = reinterpret_cast<long long*>(part + (size_t)groups * chunks * G::HALF);
+    hipLaunchKernelGGL((nps_roi_kernel<R>), dim3(chunks, groups), dim3(NPS_THREADS), 0, s, a, b, K, C, H, W, S, ny, nx, n_rois, detrend, windowed,
+                       tab, part, used);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL((nps_sum_kernel<R>), dim3((G::HALF + NPS_SUM_THREADS - 1) / NPS_SUM_THREADS, groups), dim3(NPS_SUM_THREADS), 0, s, part, used,
+                       chunks, n_rois, scale, sw, nps, rois_used, rois_skipped);
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL((nps_radial_kernel<R>), dim3((R / 2 + 1 + 3) / 4, groups), dim3(NPS_THREADS), 0, s, nps, rois_used, exclude_axes, radial,
+                       radial_count);
+    return hipGetLastError();
+}
+
+hipError_t nps_launch(const float* a, const float* b, int B, int K, int C, int H, int W, int R, int S, int detrend, const float* window,
+                      double scale, int exclude_axes, double* nps, double* radial, long long* radial_count, long long* rois_used,
+                      long long* rois_skipped, void* ws, hipStream_t s) {
+    if ((R != 32 && R != 64 && R != 128) || S < 1 || B < 1 || K < 1 || C < 1 || H < R || W < R || (long long)B * C > 65535 || detrend < 0 ||
+        detrend > 2 || (unsigned long long)((H - R) / S + 1) * (unsigned long long)((W - R) / S + 1) > 0x7FFFFFFFull || !a || !nps || !radial || !radial_count || !rois_used || !rois_skipped || !ws || nps_chunks(K, H, W, R, S) > 0x7FFFFFFFull)
+        return hipErrorInvalidValue;
+    // the tables: twiddles exp(-2 pi i t / R), t < R/2, and the window, computed in double and rounded to fp32; S_w = (sum w^2)^2
+    NpsTables tab{};
+    for (int t = 0; t < R / 2; ++t) {
+        const double ang = 2.0 * M_PI * (double)t / (double)R;
+        tab.tc[t] = (float)cos(ang);
+        tab.ts[t] = (float)-sin(ang);
+    }
+    double sw = (double)R * (double)R;
+    if (window) {
+        double q = 0.0;
+        for (int i = 0; i < R; ++i) { tab.w[i] = window[i]; q += (double)window[i] * (double)window[i]; }
+        sw = q * q;
+    }
+    const int windowed = window ? 1 : 0;
+    if (R == 32) return nps_dispatch<32>(a, b, B, K, C, H, W, S, detrend, windowed, tab, scale, sw, exclude_axes, nps, radial, radial_count, rois_used, rois_skipped, ws, s);
+    if (R == 64) return nps_dispatch<64>(a, b, B, K, C, H, W, S, detrend, windowed, tab, scale, sw, exclude_axes, nps, radial, radial_count, rois_used, rois_skipped, ws, s);
+    return nps_dispatch<128>(a, b, B, K, C, H, W, S, detrend, windowed, tab, scale, sw, exclude_axes, nps, radial, radial_count, rois_used, rois_skipped, ws, s);
+}
+
+}  // namespace midd
