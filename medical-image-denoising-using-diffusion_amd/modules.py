@@ -25,6 +25,11 @@ import torch.nn as nn
 
 from . import native
 from .config import UNetConfig, param_shapes, topology
+from .loss import check_loss_source, loss_counter_args, loss_table_args
+from .rules import _levels_arg, check_member, check_members, check_rule, check_seed, check_update, refuse_update
+from .tensors import _ptr
+from .tiles import tiling
+from .views import view_codes, view_codes_tiled
 
 DEFAULT_TIME_ROWS = 1000     # rows of the precomputed timestep table (t in [0, rows))
 
@@ -53,10 +58,6 @@ def _default_init(name: str, shape: Tuple[int, ...], all_shapes: Dict[str, Tuple
     fan_in = wshape[1] * (wshape[2] * wshape[3] if len(wshape) == 4 else 1)
     bound = 1.0 / math.sqrt(fan_in)
     return torch.empty(shape).uniform_(-bound, bound)
-
-
-def _ptr(t: Optional[torch.Tensor]):
-    return None if t is None else t.data_ptr()
 
 
 class UNetDiffusion(nn.Module):
@@ -250,6 +251,47 @@ class UNetDiffusion(nn.Module):
         native.check(fn(*head, wptr, wbytes, stream))
         self._raise_on_status(wptr, stream)
 
+    # ------------------------------------------------------------------ what the batched calls share
+    @staticmethod
+    def _wanted(n: int, want_mean: bool, want_std: bool, want_samples: bool, want_tiles: Optional[bool] = None) -> bool:
+        """-> want_std of a call over ``n`` members (one member has no std); raises when nothing is left to return.
+        ``want_tiles`` None: the call has no tiles output."""
+        want_std = want_std and n >= 2
+        if not (want_mean or want_std or want_samples or want_tiles):
+            raise ValueError("nothing to return: ask for the mean, the std" + (" or the samples" if want_tiles is None else ", the samples or the tiles"))
+        return want_std
+
+    @staticmethod
+    def _outputs(src: torch.Tensor, n: int, want_mean: bool, want_std: bool, want_samples: bool):
+        """-> (mean, std, samples [B, n, C, H, W]) of a call over ``n`` members of ``src``, None where not wanted."""
+        B, Cc, H, W = src.shape
+        return (torch.empty_like(src) if want_mean else None, torch.empty_like(src) if want_std else None,
+                torch.empty((B, n, Cc, H, W), dtype=torch.float32, device=src.device) if want_samples else None)
+
+    @staticmethod
+    def _pass_samples(max_batch: int, n: int) -> int:
+        """Samples per pass of a call that runs ``n`` samples in passes of at most ``max_batch``."""
+        return min(max_batch, max(1, n))
+
+    @staticmethod
+    def _seed_args(seed: Optional[int], sample_offset: int, member_offset: Optional[int] = None, flag: bool = True) -> tuple:
+        """The seed words of a batched call as the library takes them: ([seeded,] seed, sample_offset[, member_offset]).  ``flag``
+        False: the call is always seeded and takes no such word."""
+        return ((0 if seed is None else 1,) if flag else ()) + (C.c_uint64(seed or 0), C.c_int64(sample_offset)) \
+            + (() if member_offset is None else (C.c_int64(member_offset),))
+
+    def _batched_workspace(self, query, args: tuple, dev: torch.device, name: Optional[str] = None) -> torch.Tensor:
+        """Scratch of one batched call: the resident ``_ensemble_ws`` entry, keyed by the call (``name``), the arguments ``args`` of
+        its size ``query`` and the device and stream."""
+        key = (() if name is None else (name,)) + args + (dev.index, torch.cuda.current_stream(dev).cuda_stream)
+        return self._resident_workspace("_ensemble_ws", key, lambda: query(self._plan, *args), dev)
+
+    def _query_bytes(self, query: str, *args) -> int:
+        """The body of the ``*_workspace_bytes`` methods: the library's ``query`` for this model's plan."""
+        with self._lock, torch.cuda.device(self._device()):
+            self._ensure_plan()
+            return int(getattr(native.lib(), query)(self._plan, *args))
+
     # ------------------------------------------------------------------ reference interface
     @torch.no_grad()
     def forward(self, x: torch.Tensor, condition: torch.Tensor, t: torch.Tensor) -> torch.Tensor:
@@ -289,7 +331,6 @@ class UNetDiffusion(nn.Module):
         (mi_denoise_seeded) instead of read from ``step_noise``; the two are exclusive.
         member (with seed): which draw of every image; 0 is the plain seeded run, m > 0 is member m of an ensemble, run alone
         through mi_denoise_ensemble's single-member form."""
-        from .sampler import check_member, check_seed, check_update
         rule = check_update(update, eta, clip_x0)
         dpm = rule is not None and rule.kind == native.MI_UPDATE["dpmpp2m"]
         if return_x0 and not dpm:
@@ -361,7 +402,6 @@ class UNetDiffusion(nn.Module):
         ``member`` [B] and ``frame`` [B][3] = (pitch, plane, origin) make a slot a virtual sample (mi_denoise_slots_virtual): the
         member word of its noise and the frame of its element index, what a member of run_ensemble and a tile of run_tiled
         draw.  Both need ``seed``; with both None the call is mi_denoise_slots."""
-        from .sampler import refuse_update
         refuse_update(update, "run_slots (mi_denoise_slots)")
         return self._run_slots(cond, x, t_rows, beta, alpha, alpha_hat, clamp_eps, iter_base, sample_index, step_noise, seed, no_split,
                                max_slots, member, frame, None)
@@ -379,7 +419,6 @@ class UNetDiffusion(nn.Module):
         place, not initialised; it travels with the slot as ``x`` does.  "dpmpp2m" is deterministic: ``seed``, ``step_noise``,
         ``member`` and ``frame`` raise.  ``rule=None``: the reference's update through the same native entry -- ``run_slots``'
         bits and launches -- with the three new arguments None."""
-        from .sampler import check_rule
         rule = check_rule(rule)
         dpm = rule is not None and rule.update == "dpmpp2m"
         if dpm and (seed is not None or step_noise is not None or member is not None or frame is not None):
@@ -399,7 +438,6 @@ class UNetDiffusion(nn.Module):
                    max_slots, member, frame, ruled) -> torch.Tensor:
         """The per-slot native calls: ``ruled`` None is mi_denoise_slots / mi_denoise_slots_virtual, else (rule, t_before, t_after,
         x0) of mi_denoise_slots_rule, which always takes the two virtual tables (None: NULL)."""
-        from .sampler import check_seed
         if seed is not None:
             if step_noise is not None:
                 raise ValueError("pass either seed or step_noise, not both")
@@ -469,7 +507,6 @@ class UNetDiffusion(nn.Module):
         (mse, edge, loss), maps float32 [3, B, C, H, W] = (q, g, p) or None).  The noise is ``noise`` or the seeded forward noise of
         (seed, sample_offset + b, draw) -- ``sample_index`` / ``draws`` ([B] integers) replace those counter words per sample.
         ``workspace_batch``: the largest batch of a series of calls (loss_profile's passes), so that a shorter last pass keeps the scratch."""
-        from .sampler import check_loss_source, loss_counter_args, loss_table_args
         self._check_image(clean, "clean")
         self._check_image(noisy, "noisy")
         if noisy.shape != clean.shape or noisy.device != clean.device:
@@ -513,15 +550,12 @@ class UNetDiffusion(nn.Module):
         """``members`` seeded draws per image in one native call (mi_denoise_ensemble) -> (mean, std, samples), each None when
         not asked for.  The B * members (image, member) pairs run through the sampler loop in passes of at most ``max_batch``;
         samples is [B, members, C, H, W].  update, eta, clip_x0: the update rule, as in run_sampler (mi_denoise_ensemble_rule)."""
-        from .sampler import check_members, check_seed, check_update
         rule = check_update(update, eta, clip_x0)
         if rule is not None and rule.kind == native.MI_UPDATE["dpmpp2m"]:
             raise ValueError("update='dpmpp2m' is deterministic: a deterministic sampler has no ensemble")
         seed, sample_offset = check_seed(seed, sample_offset)
         members, member_offset, max_batch = check_members(members, member_offset, max_batch)
-        want_std = want_std and members >= 2
-        if not (want_mean or want_std or want_samples):
-            raise ValueError("nothing to return: ask for the mean, the std or the samples")
+        want_std = self._wanted(members, want_mean, want_std, want_samples)
         self._check_image(noisy, "noisy_img")
         B, Cc, H, W = noisy.shape
         keep, sched = self._schedule_args(t_list, beta, alpha, alpha_hat)
@@ -529,17 +563,14 @@ class UNetDiffusion(nn.Module):
         with self._lock, torch.cuda.device(dev):
             plan = self._ensure_plan(time_rows=sched[-1])
             src = noisy.contiguous()
-            mean = torch.empty_like(src) if want_mean else None
-            std = torch.empty_like(src) if want_std else None
-            samples = torch.empty((B, members, Cc, H, W), dtype=torch.float32, device=dev) if want_samples else None
-            pass_samples = min(max_batch, max(1, B * members))
-            size = (B, members, H, W, pass_samples)
-            ws = self._resident_workspace("_ensemble_ws", size + (want_samples, dev.index, torch.cuda.current_stream(dev).cuda_stream),
-                                          lambda: native.lib().mi_ensemble_workspace_bytes(self._plan, *size, 1 if want_samples else 0), dev)
+            mean, std, samples = self._outputs(src, members, want_mean, want_std, want_samples)
+            pass_samples = self._pass_samples(max_batch, B * members)
+            ws = self._batched_workspace(native.lib().mi_ensemble_workspace_bytes,
+                                         (B, members, H, W, pass_samples, 1 if want_samples else 0), dev)
             self._invoke(native.lib().mi_denoise_ensemble if rule is None else native.lib().mi_denoise_ensemble_rule,
                          (plan, src.data_ptr(), _ptr(mean), _ptr(std), _ptr(samples), B, members, H, W) + sched
-                         + (C.c_uint64(seed), C.c_int64(sample_offset), C.c_int64(member_offset), pass_samples,
-                            self._call_flags(clamp_eps, no_split)) + (() if rule is None else (C.byref(rule),)), ws, dev)
+                         + self._seed_args(seed, sample_offset, member_offset, flag=False)
+                         + (pass_samples, self._call_flags(clamp_eps, no_split)) + (() if rule is None else (C.byref(rule),)), ws, dev)
         return mean, std, samples
 
     @torch.no_grad()
@@ -553,7 +584,6 @@ class UNetDiffusion(nn.Module):
         None: no noise term (DDIM); else view k draws as member ``member_offset + k`` of the seeded generator.  ``levels``
         (checked quantile levels): one mi_dihedral_quantiles launch follows on the same stream, reading the view outputs where
         the call left them -- the tail of its workspace (include/midd.h) -- so no member tensor exists for it."""
-        from .sampler import _levels_arg, check_members, check_seed, refuse_update, view_codes
         refuse_update(update, "run_self_ensemble (mi_denoise_self_ensemble)")
         if seed is not None:
             seed, _ = check_seed(seed, 0)
@@ -565,30 +595,24 @@ class UNetDiffusion(nn.Module):
         G = len(codes)
         _, member_offset, max_batch = check_members(G, member_offset, max_batch)
         self._check_image(noisy, "noisy_img")
-        want_std = want_std and G >= 2
-        if not (want_mean or want_std or want_samples):
-            raise ValueError("nothing to return: ask for the mean, the std or the samples")
+        want_std = self._wanted(G, want_mean, want_std, want_samples)
         keep, sched = self._schedule_args(t_list, beta, alpha, alpha_hat)
         code_arg, maps = (C.c_int32 * G)(*codes), None
         dev = noisy.device
         with self._lock, torch.cuda.device(dev):
             plan = self._ensure_plan(time_rows=sched[-1])
             src = noisy.contiguous()
-            mean = torch.empty_like(src) if want_mean else None
-            std = torch.empty_like(src) if want_std else None
-            samples = torch.empty((B, G, Cc, H, W), dtype=torch.float32, device=dev) if want_samples else None
-            pass_samples = min(max_batch, max(1, B * G))
-            size = (B, G, H, W, pass_samples)
-            ws = self._resident_workspace("_ensemble_ws", ("self_ensemble",) + size + (dev.index, torch.cuda.current_stream(dev).cuda_stream),
-                                          lambda: native.lib().mi_self_ensemble_workspace_bytes(self._plan, *size, 0), dev)
+            mean, std, samples = self._outputs(src, G, want_mean, want_std, want_samples)
+            pass_samples = self._pass_samples(max_batch, B * G)
+            size = (B, G, H, W, pass_samples, 0)
+            ws = self._batched_workspace(native.lib().mi_self_ensemble_workspace_bytes, size, dev, "self_ensemble")
             self._invoke(native.lib().mi_denoise_self_ensemble,
                          (plan, src.data_ptr(), _ptr(mean), _ptr(std), _ptr(samples), B, H, W, code_arg, G) + sched
-                         + (0 if seed is None else 1, C.c_uint64(seed or 0), C.c_int64(sample_offset), C.c_int64(member_offset), pass_samples,
-                            self._call_flags(clamp_eps, no_split)), ws, dev)
+                         + self._seed_args(seed, sample_offset, member_offset) + (pass_samples, self._call_flags(clamp_eps, no_split)), ws, dev)
             if levels is not None:
                 maps = torch.empty((B, len(levels), Cc, H, W), dtype=torch.float32, device=dev)
                 wptr, _ = self._aligned_ptr(ws)
-                nbytes = native.lib().mi_self_ensemble_workspace_bytes(self._plan, *size, 0)
+                nbytes = native.lib().mi_self_ensemble_workspace_bytes(self._plan, *size)
                 views_out = wptr + nbytes - B * G * Cc * H * W * 4          # the view outputs: the last bytes of the workspace
                 native.check(native.lib().mi_dihedral_quantiles(views_out, B, Cc, H, W, code_arg, G, _levels_arg(levels), len(levels),
                                                                 maps.data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
@@ -597,10 +621,8 @@ class UNetDiffusion(nn.Module):
     def self_ensemble_workspace_bytes(self, B: int, views: int, H: int, W: int, max_batch: int = 16, samples_external: bool = False) -> int:
         """Workspace of run_self_ensemble for ``views`` views per image (a count): ensemble_workspace_bytes of as many members,
         whatever ``samples_external`` says -- the view-frame outputs always live in the workspace."""
-        with self._lock, torch.cuda.device(self._device()):
-            self._ensure_plan()
-            return int(native.lib().mi_self_ensemble_workspace_bytes(self._plan, B, views, H, W, min(max_batch, max(1, B * views)),
-                                                                     1 if samples_external else 0))
+        return self._query_bytes("mi_self_ensemble_workspace_bytes", B, views, H, W, self._pass_samples(max_batch, B * views),
+                                 1 if samples_external else 0)
 
     @torch.no_grad()
     def run_tiled(self, noisy: torch.Tensor, t_list, beta: torch.Tensor, alpha: torch.Tensor, alpha_hat: torch.Tensor,
@@ -609,7 +631,6 @@ class UNetDiffusion(nn.Module):
         """Images of any size >= the tile as blended overlapping tiles in one native call (mi_denoise_tiled) ->
         (image, tiles or None, TilePlan).  seed None: no noise term (DDIM).  update, eta, clip_x0: the update rule, as in
         run_sampler (mi_denoise_tiled_rule; "dpmpp2m": mi_denoise_tiled_dpm with a history buffer of one pass, no seed)."""
-        from .sampler import check_member, check_seed, check_update, tiling
         rule = check_update(update, eta, clip_x0)
         dpm = rule is not None and rule.kind == native.MI_UPDATE["dpmpp2m"]
         if dpm and seed is not None:
@@ -627,8 +648,9 @@ class UNetDiffusion(nn.Module):
             src = noisy.contiguous()
             image = torch.empty_like(src)
             tiles = torch.empty((B, K, Cc, th, tw), dtype=torch.float32, device=dev) if want_tiles else None
-            pass_samples = min(max_batch, max(1, B * K))
-            ws = self._tiled_workspace((B, H, W, th, tw, oy, ox, pass_samples, 1 if want_tiles else 0), dev)
+            pass_samples = self._pass_samples(max_batch, B * K)
+            ws = self._batched_workspace(native.lib().mi_tiled_workspace_bytes,
+                                         (B, H, W, th, tw, oy, ox, pass_samples, 1 if want_tiles else 0), dev, "tiled")
             if dpm:
                 hist = torch.empty((pass_samples, Cc, th, tw), dtype=torch.float32, device=dev)      # (as in run_sampler)
                 if self.poison_workspace is not None:
@@ -639,8 +661,8 @@ class UNetDiffusion(nn.Module):
                 return image, tiles, plan_t
             self._invoke(native.lib().mi_denoise_tiled if rule is None else native.lib().mi_denoise_tiled_rule,
                          (plan, src.data_ptr(), image.data_ptr(), _ptr(tiles), B, H, W, th, tw, oy, ox) + sched
-                         + (0 if seed is None else 1, C.c_uint64(seed or 0), C.c_int64(sample_offset), pass_samples,
-                            self._call_flags(clamp_eps, no_split)) + (() if rule is None else (C.byref(rule),)), ws, dev)
+                         + self._seed_args(seed, sample_offset) + (pass_samples, self._call_flags(clamp_eps, no_split))
+                         + (() if rule is None else (C.byref(rule),)), ws, dev)
         return image, tiles, plan_t
 
     @torch.no_grad()
@@ -652,13 +674,10 @@ class UNetDiffusion(nn.Module):
         (mean, std, samples, tiles, TilePlan), each tensor None when not asked for.  Members are the outer loop; inside a member
         the B * tiles crops run in passes of at most ``max_batch``, as run_tiled runs them.  samples is [B, members, C, H, W],
         tiles [members, B, ny * nx, C, th, tw]."""
-        from .sampler import check_members, check_seed, refuse_update, tiling
         refuse_update(update, "run_tiled_ensemble (mi_denoise_tiled_ensemble)")
         seed, sample_offset = check_seed(seed, sample_offset)
         members, member_offset, max_batch = check_members(members, member_offset, max_batch)
-        want_std = want_std and members >= 2
-        if not (want_mean or want_std or want_samples or want_tiles):
-            raise ValueError("nothing to return: ask for the mean, the std, the samples or the tiles")
+        want_std = self._wanted(members, want_mean, want_std, want_samples, want_tiles)
         self._check_image(noisy, "noisy_img")
         B, Cc, H, W = noisy.shape
         plan_t, th, tw, oy, ox, K = tiling(H, W, tile, overlap)
@@ -667,16 +686,15 @@ class UNetDiffusion(nn.Module):
         with self._lock, torch.cuda.device(dev):
             plan = self._ensure_plan(time_rows=sched[-1])
             src = noisy.contiguous()
-            mean = torch.empty_like(src) if want_mean else None
-            std = torch.empty_like(src) if want_std else None
-            samples = torch.empty((B, members, Cc, H, W), dtype=torch.float32, device=dev) if want_samples else None
+            mean, std, samples = self._outputs(src, members, want_mean, want_std, want_samples)
             tiles = torch.empty((members, B, K, Cc, th, tw), dtype=torch.float32, device=dev) if want_tiles else None
-            pass_samples = min(max_batch, max(1, B * K))
-            ws = self._tiled_workspace((B, members, H, W, th, tw, oy, ox, pass_samples, 1 if want_tiles else 0), dev, ensemble=True)
+            pass_samples = self._pass_samples(max_batch, B * K)
+            ws = self._batched_workspace(native.lib().mi_tiled_ensemble_workspace_bytes,
+                                         (B, members, H, W, th, tw, oy, ox, pass_samples, 1 if want_tiles else 0), dev, "tiled_ensemble")
             self._invoke(native.lib().mi_denoise_tiled_ensemble,
                          (plan, src.data_ptr(), _ptr(mean), _ptr(std), _ptr(samples), _ptr(tiles), B, members, H, W, th, tw, oy, ox) + sched
-                         + (C.c_uint64(seed), C.c_int64(sample_offset), C.c_int64(member_offset), pass_samples,
-                            self._call_flags(clamp_eps, no_split)), ws, dev)
+                         + self._seed_args(seed, sample_offset, member_offset, flag=False)
+                         + (pass_samples, self._call_flags(clamp_eps, no_split)), ws, dev)
         return mean, std, samples, tiles, plan_t
 
     @torch.no_grad()
@@ -691,7 +709,6 @@ class UNetDiffusion(nn.Module):
         [B, views, C, H, W], every member turned back into the image's frame; tiles [views, B, ny * nx, C, th, tw], view k's in its
         own frame.  seed None: nothing is drawn; else view k draws as member ``member_offset + k``.  update, eta, clip_x0: the
         update rule, as in run_tiled ("dpmpp2m" is not built for this call)."""
-        from .sampler import check_members, check_seed, check_update, tiling, view_codes_tiled
         rule = check_update(update, eta, clip_x0)
         if rule is not None and rule.kind == native.MI_UPDATE["dpmpp2m"]:
             raise ValueError("run_tiled_self_ensemble (mi_denoise_tiled_self_ensemble) takes no history buffer: update='dpmpp2m' is not built for it")
@@ -705,9 +722,7 @@ class UNetDiffusion(nn.Module):
         G = len(codes)
         _, member_offset, max_batch = check_members(G, member_offset, max_batch)
         self._check_image(noisy, "noisy_img")
-        want_std = want_std and G >= 2
-        if not (want_mean or want_std or want_samples or want_tiles):
-            raise ValueError("nothing to return: ask for the mean, the std, the samples or the tiles")
+        want_std = self._wanted(G, want_mean, want_std, want_samples, want_tiles)
         plan_t, th, tw, oy, ox, K = tiling(H, W, tile, overlap)
         keep, sched = self._schedule_args(t_list, beta, alpha, alpha_hat)
         code_arg = (C.c_int32 * G)(*codes)
@@ -715,18 +730,15 @@ class UNetDiffusion(nn.Module):
         with self._lock, torch.cuda.device(dev):
             plan = self._ensure_plan(time_rows=sched[-1])
             src = noisy.contiguous()
-            mean = torch.empty_like(src) if want_mean else None
-            std = torch.empty_like(src) if want_std else None
-            samples = torch.empty((B, G, Cc, H, W), dtype=torch.float32, device=dev) if want_samples else None
+            mean, std, samples = self._outputs(src, G, want_mean, want_std, want_samples)
             tiles = torch.empty((G, B, K, Cc, th, tw), dtype=torch.float32, device=dev) if want_tiles else None
-            pass_samples = min(max_batch, max(1, B * K))
-            size = (B, G, H, W, th, tw, oy, ox, pass_samples, 1 if want_tiles else 0)
-            ws = self._resident_workspace("_ensemble_ws", ("tiled_self_ensemble",) + size + (dev.index, torch.cuda.current_stream(dev).cuda_stream),
-                                          lambda: native.lib().mi_tiled_self_ensemble_workspace_bytes(self._plan, *size), dev)
+            pass_samples = self._pass_samples(max_batch, B * K)
+            ws = self._batched_workspace(native.lib().mi_tiled_self_ensemble_workspace_bytes,
+                                         (B, G, H, W, th, tw, oy, ox, pass_samples, 1 if want_tiles else 0), dev, "tiled_self_ensemble")
             self._invoke(native.lib().mi_denoise_tiled_self_ensemble,
                          (plan, src.data_ptr(), _ptr(mean), _ptr(std), _ptr(samples), _ptr(tiles), B, H, W, th, tw, oy, ox, code_arg, G) + sched
-                         + (0 if seed is None else 1, C.c_uint64(seed or 0), C.c_int64(sample_offset), C.c_int64(member_offset), pass_samples,
-                            self._call_flags(clamp_eps, no_split), None if rule is None else C.byref(rule)), ws, dev)
+                         + self._seed_args(seed, sample_offset, member_offset)
+                         + (pass_samples, self._call_flags(clamp_eps, no_split), None if rule is None else C.byref(rule)), ws, dev)
         return mean, std, samples, tiles, codes, plan_t
 
     def tiled_self_ensemble_workspace_bytes(self, B: int, views: int, H: int, W: int, tile, overlap=32, max_batch: int = 16,
@@ -734,41 +746,24 @@ class UNetDiffusion(nn.Module):
         """Workspace of run_tiled_self_ensemble for ``views`` views per image (a count): tiled_workspace_bytes with the tiles
         external + the viewed copy of the batch (B * C*H*W * 4 bytes, rounded up to 256) + the tiles of every view unless
         ``tiles_external``."""
-        from .sampler import tiling
         _, th, tw, oy, ox, K = tiling(H, W, tile, overlap)
-        with self._lock, torch.cuda.device(self._device()):
-            self._ensure_plan()
-            return int(native.lib().mi_tiled_self_ensemble_workspace_bytes(self._plan, B, views, H, W, th, tw, oy, ox,
-                                                                           min(max_batch, max(1, B * K)), 1 if tiles_external else 0))
-
-    def _tiled_workspace(self, args: tuple, dev: torch.device, ensemble: bool = False) -> torch.Tensor:
-        """Scratch of one run_tiled (or, ``ensemble``, run_tiled_ensemble) call: the resident entry of the ensemble calls."""
-        query = native.lib().mi_tiled_ensemble_workspace_bytes if ensemble else native.lib().mi_tiled_workspace_bytes
-        key = ("tiled_ensemble" if ensemble else "tiled",) + args + (dev.index, torch.cuda.current_stream(dev).cuda_stream)
-        return self._resident_workspace("_ensemble_ws", key, lambda: query(self._plan, *args), dev)
+        return self._query_bytes("mi_tiled_self_ensemble_workspace_bytes", B, views, H, W, th, tw, oy, ox,
+                                 self._pass_samples(max_batch, B * K), 1 if tiles_external else 0)
 
     def tiled_workspace_bytes(self, B: int, H: int, W: int, tile, overlap=32, max_batch: int = 16, tiles_external: bool = False) -> int:
-        from .sampler import tiling
         _, th, tw, oy, ox, K = tiling(H, W, tile, overlap)
-        with self._lock, torch.cuda.device(self._device()):
-            self._ensure_plan()
-            return int(native.lib().mi_tiled_workspace_bytes(self._plan, B, H, W, th, tw, oy, ox, min(max_batch, max(1, B * K)),
-                                                             1 if tiles_external else 0))
+        return self._query_bytes("mi_tiled_workspace_bytes", B, H, W, th, tw, oy, ox, self._pass_samples(max_batch, B * K),
+                                 1 if tiles_external else 0)
 
     def tiled_ensemble_workspace_bytes(self, B: int, members: int, H: int, W: int, tile, overlap=32, max_batch: int = 16,
                                        tiles_external: bool = False) -> int:
-        from .sampler import tiling
         _, th, tw, oy, ox, K = tiling(H, W, tile, overlap)
-        with self._lock, torch.cuda.device(self._device()):
-            self._ensure_plan()
-            return int(native.lib().mi_tiled_ensemble_workspace_bytes(self._plan, B, members, H, W, th, tw, oy, ox,
-                                                                      min(max_batch, max(1, B * K)), 1 if tiles_external else 0))
+        return self._query_bytes("mi_tiled_ensemble_workspace_bytes", B, members, H, W, th, tw, oy, ox,
+                                 self._pass_samples(max_batch, B * K), 1 if tiles_external else 0)
 
     def ensemble_workspace_bytes(self, B: int, members: int, H: int, W: int, max_batch: int = 16, samples_external: bool = False) -> int:
-        with self._lock, torch.cuda.device(self._device()):
-            self._ensure_plan()
-            return int(native.lib().mi_ensemble_workspace_bytes(self._plan, B, members, H, W, min(max_batch, max(1, B * members)),
-                                                                1 if samples_external else 0))
+        return self._query_bytes("mi_ensemble_workspace_bytes", B, members, H, W, self._pass_samples(max_batch, B * members),
+                                 1 if samples_external else 0)
 
     @torch.no_grad()
     def debug_fetch(self, module_name: str, B: int, H: int, W: int) -> torch.Tensor:
@@ -804,9 +799,7 @@ class UNetDiffusion(nn.Module):
                          flops=float(buf[i].flops), bytes=float(buf[i].bytes)) for i in range(min(n.value, cap))]
 
     def workspace_bytes(self, B: int, H: int, W: int) -> int:
-        with self._lock, torch.cuda.device(self._device()):
-            self._ensure_plan()
-            return int(native.lib().mi_workspace_bytes(self._plan, B, H, W))
+        return self._query_bytes("mi_workspace_bytes", B, H, W)
 
     def __del__(self):
         plan = getattr(self, "_plan", None)

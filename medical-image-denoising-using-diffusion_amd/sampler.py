@@ -5,1037 +5,40 @@
 The schedule tables are built with the same torch calls as the reference so they are bit
 identical; the loop itself (UNet forward + fused x_{t-1} update per timestep) is a single
 call into libmidd.so.
+
+The argument rules and the stand-alone operators live in ``rules``, ``ensemble``, ``nps``, ``loss``, ``tiles`` and ``views``; every
+name this module has exported is still importable from it.
 """
 from __future__ import annotations
 
-import ctypes as C
-import dataclasses
-import math
-import numbers
-import operator
+import ctypes as C, dataclasses, math, numbers, operator      # noqa: E401,F401  (names this module has always carried)
 from typing import NamedTuple, Optional, Sequence, Tuple
 
 import torch
 
 from . import native
 from .config import timestep_list
+from .ensemble import (DEFAULT_SCORE_LEVELS, EnsembleQuantileResult, EnsembleResult, EnsembleScores, ensemble_quantiles,  # noqa: F401
+                       ensemble_reduce, ensemble_scores, step_noise)
+from .loss import (DenoisingLoss, LossMaps, LossProfile, _loss_tensor, check_loss_source, loss_counter_args, loss_table_args,  # noqa: F401
+                   loss_terms, noise_images)
+from .nps import NoisePowerSpectrum, noise_power_spectrum, nps_window  # noqa: F401
+from .rules import (MAX_QUANTILE_LEVELS, MAX_QUANTILE_MEMBERS, NPS_DETREND, NPS_ROIS, UPDATE_RULES, SamplerRule, _integer,  # noqa: F401
+                    _levels_arg, _pair, check_levels, check_member, check_members, check_nps_args, check_quantile_members, check_rule,
+                    check_score_levels, check_seed, check_update, ddim_coefficients, dpm_coefficients, refuse_update)
+from .tiles import (TiledEnsembleQuantileResult, TiledEnsembleResult, TiledResult, TilePlan, _axis, _tile_tensor, tile_blend,  # noqa: F401
+                    tile_blend_quantiles, tile_blend_reduce, tile_extract, tile_plan, tiling)
+from .views import (MAX_VIEWS, VIEW_SETS, SelfEnsembleQuantileResult, SelfEnsembleResult, TiledSelfEnsembleQuantileResult,  # noqa: F401
+                    TiledSelfEnsembleResult, _unview_args, _view_tensor, _views_arg, dihedral_quantiles, dihedral_reduce, dihedral_views,
+                    tile_blend_unview_quantiles, tile_blend_unview_reduce, view_codes, view_codes_tiled)
 
 device = torch.device("cuda" if torch.cuda.is_available() else "cpu")    # DDIMModel.py:10
-
-
-def _integer(v, what, bound, low=0) -> int:
-    try:
-        if isinstance(v, bool):
-            raise TypeError
-        i = operator.index(v)
-    except TypeError:
-        raise ValueError(f"{what} must be an integer (got {v!r})") from None
-    if not (low <= i < bound):
-        raise ValueError(f"{what} must be in [{low}, 2**{bound.bit_length() - 1}) (got {v!r})")
-    return i
-
-
-def check_seed(seed, sample_offset) -> Tuple[int, int]:
-    """Argument rules of the seeded step noise (include/midd.h: mi_denoise_seeded) -> (seed, sample_offset) as Python ints;
-    raises ValueError before any GPU work."""
-    return _integer(seed, "seed", 1 << 64), _integer(sample_offset, "sample_offset", 1 << 63)
-
-
-def check_member(member, what: str = "member", low: int = 0) -> int:
-    """A member index (or, with low=1, a member count) of the seeded step noise: one 32-bit counter word (include/midd.h)."""
-    return _integer(member, what, 1 << 32 if low == 0 else 1 << 31, low)
-
-
-def check_members(members, member_offset, max_batch) -> Tuple[int, int, int]:
-    """Argument rules of an ensemble call (include/midd.h: mi_denoise_ensemble) -> (members, member_offset, max_batch)."""
-    members, member_offset = check_member(members, "members", low=1), check_member(member_offset, "member_offset")
-    max_batch = check_member(max_batch, "max_batch", low=1)
-    if member_offset + members > 1 << 32:
-        raise ValueError(f"member_offset + members must be <= 2**32 (got {member_offset} + {members})")
-    return members, member_offset, max_batch
-
-
-UPDATE_RULES = ("reference", "ddim", "dpmpp2m")
-
-
-def check_update(update="reference", eta=0.0, clip_x0=True):
-    """Argument rules of the update rule (include/midd.h: THE DDIM UPDATE, THE DPMPP2M UPDATE) -> None for ``"reference"`` (the
-    reference's update, the calls and bits of before) or the ``native.UpdateRule`` of ``"ddim"`` / ``"dpmpp2m"`` (kind and
-    clip_x0; the native *_dpm calls take no rule struct); raises ValueError before any GPU work.  ``eta`` and ``clip_x0`` belong
-    to ``"ddim"``: anything but their defaults together with ``"reference"`` raises; ``"dpmpp2m"`` takes ``clip_x0`` and is
-    deterministic, so ``eta`` must stay 0."""
-    if update not in UPDATE_RULES:
-        raise ValueError(f"update must be 'reference', 'ddim' or 'dpmpp2m' (got {update!r})")
-    if isinstance(eta, bool) or not isinstance(eta, numbers.Real) or not 0.0 <= float(eta) <= 1.0:      # (NaN fails the comparison)
-        raise ValueError(f"eta must be a number in [0, 1] (got {eta!r})")
-    if not isinstance(clip_x0, (bool, int)):
-        raise ValueError(f"clip_x0 must be a bool (got {clip_x0!r})")
-    if update == "reference":
-        if float(eta) != 0.0 or not clip_x0:
-            raise ValueError("eta and clip_x0 belong to update='ddim': the reference's update has neither")
-        return None
-    if update == "dpmpp2m" and float(eta) != 0.0:
-        raise ValueError("update='dpmpp2m' is deterministic: it has no eta (an SDE form is not built)")
-    return native.UpdateRule(native.MI_UPDATE[update], float(eta), 1 if clip_x0 else 0)
-
-
-def refuse_update(update, what: str) -> None:
-    """The calls the DDIM and DPMPP2M updates are not built for (include/midd.h: NOT BUILT) take ``update`` to say so.  The
-    per-slot calls run the rules under another spelling, ``rule=SamplerRule(...)``, which the message names."""
-    if update not in UPDATE_RULES:
-        raise ValueError(f"update must be 'reference', 'ddim' or 'dpmpp2m' (got {update!r})")
-    slots = "for the per-slot calls pass rule=SamplerRule(...) instead: run_slots_rule, denoise_ragged(rule=), SamplerSession(rule=), " \
-            "DiffusionService(slot_update=)"
-    if update == "dpmpp2m":
-        raise ValueError(f"{what} runs the reference's update only: update='dpmpp2m' is built for denoise and denoise_tiled "
-                         f"({slots}; ensembles have nothing to draw under it)")
-    if update != "reference":
-        raise ValueError(f"{what} runs the reference's update only: update='ddim' is built for denoise, denoise_ensemble and "
-                         f"denoise_tiled ({slots}; the tiled and the self ensemble do not carry the rule yet)")
-
-
-@dataclasses.dataclass(frozen=True)
-class SamplerRule:
-    """The update rule of the per-slot calls (include/midd.h: mi_denoise_slots_rule) -- ``run_slots_rule``, ``denoise_ragged(rule=)``,
-    ``SamplerSession(rule=)`` -- as one value: ``update`` "ddim" or "dpmpp2m", ``eta`` and ``clip_x0`` as in ``denoise``.  Judged by
-    ``check_update`` when it is made; the reference's update is ``rule=None``, not a SamplerRule."""
-    update: str = "ddim"
-    eta: float = 0.0
-    clip_x0: bool = True
-
-    def __post_init__(self):
-        if check_update(self.update, self.eta, self.clip_x0) is None:
-            raise ValueError("SamplerRule(update='reference'): the reference's update is rule=None")
-        object.__setattr__(self, "eta", float(self.eta))
-        object.__setattr__(self, "clip_x0", bool(self.clip_x0))
-
-    @property
-    def draws(self) -> bool:
-        """Whether the rule has a noise term at all: DDIM with eta > 0."""
-        return self.update == "ddim" and self.eta > 0.0
-
-    def native(self):
-        return check_update(self.update, self.eta, self.clip_x0)
-
-    def kwargs(self) -> dict:
-        """The keywords of ``denoise`` / ``denoise_tiled`` / ``denoise_ensemble`` that name the same rule."""
-        return dict(update=self.update, eta=self.eta, clip_x0=self.clip_x0)
-
-
-def check_rule(rule) -> Optional["SamplerRule"]:
-    if rule is not None and not isinstance(rule, SamplerRule):
-        raise ValueError(f"rule must be None (the reference's update) or a midd_amd.SamplerRule (got {rule!r})")
-    return rule
-
-
-def ddim_coefficients(t_list: Sequence[int], alpha_hat, eta: float = 0.0):
-    """The coefficient table of ``update="ddim"`` for a timestep list (host only; mi_ddim_coefficients): a float32 numpy array
-    [len(t_list), 7] of (k0, k1, r0, r1, a, b, s) per iteration, the values the update kernel receives."""
-    import numpy as np
-    steps = np.ascontiguousarray(np.asarray(list(t_list), dtype=np.int32))
-    tab = np.ascontiguousarray(alpha_hat.detach().to("cpu", torch.float32).numpy() if isinstance(alpha_hat, torch.Tensor)
-                               else np.asarray(alpha_hat, dtype=np.float32))
-    out = np.empty((len(steps), 7), dtype=np.float32)
-    native.check(native.lib().mi_ddim_coefficients(steps.ctypes.data_as(C.POINTER(C.c_int32)), len(steps),
-                                                   tab.ctypes.data_as(C.POINTER(C.c_float)), int(tab.shape[0]), C.c_double(float(eta)),
-                                                   out.ctypes.data_as(C.POINTER(C.c_float))))
-    return out
-
-
-def dpm_coefficients(t_list: Sequence[int], alpha_hat):
-    """The coefficient table of ``update="dpmpp2m"`` for a timestep list (host only; mi_dpm_coefficients): a float32 numpy array
-    [len(t_list), 8] of (k0, k1, r0, r1, a, b, s, g) per iteration -- ``ddim_coefficients`` at eta = 0, then the multistep weight."""
-    import numpy as np
-    steps = np.ascontiguousarray(np.asarray(list(t_list), dtype=np.int32))
-    tab = np.ascontiguousarray(alpha_hat.detach().to("cpu", torch.float32).numpy() if isinstance(alpha_hat, torch.Tensor)
-                               else np.asarray(alpha_hat, dtype=np.float32))
-    out = np.empty((len(steps), 8), dtype=np.float32)
-    native.check(native.lib().mi_dpm_coefficients(steps.ctypes.data_as(C.POINTER(C.c_int32)), len(steps),
-                                                  tab.ctypes.data_as(C.POINTER(C.c_float)), int(tab.shape[0]),
-                                                  out.ctypes.data_as(C.POINTER(C.c_float))))
-    return out
 
 
 class SamplerTrajectory(NamedTuple):
     """What ``DiffusionDenoiser.denoise(..., update="dpmpp2m", return_x0=True)`` returns."""
     image: torch.Tensor                   # [B, C, H, W]: the call's result, the bits of the call without return_x0
     x0: torch.Tensor                      # [n_iters, B, C, H, W]: the predicted image of every iteration (clipped when clip_x0)
-
-
-class EnsembleResult(NamedTuple):
-    """What ``DiffusionDenoiser.denoise_ensemble`` returns."""
-    mean: torch.Tensor                    # [B, C, H, W]: per-pixel mean of the members
-    std: Optional[torch.Tensor]           # [B, C, H, W]: unbiased per-pixel standard deviation; None for one member
-    samples: Optional[torch.Tensor]       # [B, members, C, H, W] with return_samples=True
-    seed: int                             # the seed of the run (drawn when the call had seed=None): pass it to repeat the run
-
-
-class EnsembleQuantileResult(NamedTuple):
-    """What ``DiffusionDenoiser.denoise_ensemble(..., quantiles=levels)`` returns: EnsembleResult's fields, then the maps."""
-    mean: torch.Tensor
-    std: Optional[torch.Tensor]
-    samples: Optional[torch.Tensor]
-    seed: int
-    quantiles: torch.Tensor               # [B, nq, C, H, W]: per-pixel quantile maps of the members, in the order of ``levels``
-    levels: Tuple[float, ...]             # the quantile levels, each in [0, 1]
-
-
-MAX_QUANTILE_MEMBERS = 64                 # include/midd.h: mi_ensemble_quantiles sorts a pixel's members in registers
-MAX_QUANTILE_LEVELS = 8
-
-
-def check_levels(q) -> Tuple[float, ...]:
-    """Argument rules of the quantile levels (include/midd.h: mi_ensemble_quantiles) -> a tuple of floats; raises ValueError
-    before any GPU work.  A single number is one level."""
-    if isinstance(q, numbers.Real) and not isinstance(q, bool):
-        q = (q,)
-    try:
-        levels = tuple(q)
-    except TypeError:
-        raise ValueError(f"quantile levels must be a sequence of numbers in [0, 1] (got {q!r})") from None
-    if not 1 <= len(levels) <= MAX_QUANTILE_LEVELS:
-        raise ValueError(f"between 1 and {MAX_QUANTILE_LEVELS} quantile levels per call (got {len(levels)})")
-    out = []
-    for v in levels:
-        if isinstance(v, bool) or not isinstance(v, numbers.Real) or not 0.0 <= float(v) <= 1.0:      # (NaN fails the comparison)
-            raise ValueError(f"every quantile level must be a number in [0, 1] (got {v!r})")
-        out.append(float(v))
-    return tuple(out)
-
-
-def check_quantile_members(members: int) -> int:
-    if members > MAX_QUANTILE_MEMBERS:
-        raise ValueError(f"quantiles need members <= {MAX_QUANTILE_MEMBERS} (got {members}): the kernel sorts a pixel's members in registers")
-    return members
-
-
-def _levels_arg(levels: Tuple[float, ...]):
-    return (C.c_double * len(levels))(*levels)
-
-
-@torch.no_grad()
-def step_noise(seed: int, n_iters: int, shape: Sequence[int], sample_offset: int = 0, device=None, member: int = 0) -> torch.Tensor:
-    """The 0.5-scaled step noise a seeded cddpm run draws, as a tensor [n_iters, B, C, H, W] (mi_step_noise_fill_member).
-
-    ``denoise(x, k, step_noise=step_noise(s, n, x.shape))`` equals ``denoise(x, k, seed=s)`` bit for bit: the replay and
-    export path of a seeded run.  Entry ``[i, b]`` is a pure function of (seed, sample_offset + b, i, element index):
-    Philox4x32-10 + Box-Muller, specified in include/midd.h.  ``shape`` is the image batch's (B, C, H, W).  ``member`` m: the
-    noise of ensemble member m of every image (``denoise_ensemble``, ``denoise(..., member=m)``); 0 is the plain seeded run."""
-    seed, sample_offset = check_seed(seed, sample_offset)
-    member = check_member(member)
-    if len(shape) != 4 or n_iters < 0 or min(shape) < 0:
-        raise ValueError("shape must be (B, C, H, W) and n_iters >= 0")
-    B, Cc, H, W = (int(v) for v in shape)
-    dev = torch.device("cuda" if device is None else device)
-    if dev.type != "cuda":
-        raise RuntimeError(f"step_noise runs only on a ROCm GPU (got {dev}): there is no CPU fallback")
-    lib = native.lib()
-    with torch.cuda.device(dev):
-        out = torch.empty((int(n_iters), B, Cc, H, W), dtype=torch.float32, device=dev)
-        native.check(lib.mi_step_noise_fill_member(out.data_ptr(), int(n_iters), B, Cc, H, W, C.c_uint64(seed), C.c_int64(sample_offset),
-                                                   C.c_int64(member), torch.cuda.current_stream(out.device).cuda_stream))
-    return out
-
-
-@torch.no_grad()
-def ensemble_reduce(samples: torch.Tensor) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
-    """(mean, std) over dim 1 of ``samples`` [B, members, ...] with the arithmetic of ``denoise_ensemble`` (mi_ensemble_reduce:
-    double precision, members in index order, unbiased std) -- for members gathered from several calls or GPUs.  std is None
-    for one member."""
-    if not isinstance(samples, torch.Tensor) or samples.dim() < 3 or samples.shape[0] < 1 or samples.shape[1] < 1:
-        raise ValueError("samples must be a [B, members, ...] tensor with B >= 1 and members >= 1")
-    if samples.device.type != "cuda":
-        raise RuntimeError(f"ensemble_reduce runs only on a ROCm GPU (got {samples.device}): there is no CPU fallback")
-    if samples.dtype != torch.float32:
-        raise TypeError(f"samples must be float32 (got {samples.dtype})")
-    src = samples.contiguous()
-    B, K = src.shape[:2]
-    chw = src[0, 0].numel()
-    with torch.cuda.device(src.device):
-        mean = torch.empty((B,) + tuple(src.shape[2:]), dtype=torch.float32, device=src.device)
-        std = torch.empty_like(mean) if K >= 2 else None
-        native.check(native.lib().mi_ensemble_reduce(src.data_ptr(), B, K, chw, mean.data_ptr(), None if std is None else std.data_ptr(),
-                                                     torch.cuda.current_stream(src.device).cuda_stream))
-    return mean, std
-
-
-@torch.no_grad()
-def ensemble_quantiles(samples: torch.Tensor, q) -> torch.Tensor:
-    """Per-pixel quantile maps [B, nq, ...] over dim 1 of ``samples`` [B, members, ...] at the levels ``q`` (numbers in [0, 1], at
-    most 8; members <= 64) with the arithmetic of ``denoise_ensemble(..., quantiles=q)`` (mi_ensemble_quantiles: total-order sort,
-    linear interpolation in double precision; a pixel with a NaN member is NaN at every level)."""
-    levels = check_levels(q)
-    if not isinstance(samples, torch.Tensor) or samples.dim() < 3 or samples.shape[0] < 1 or samples.shape[1] < 1:
-        raise ValueError("samples must be a [B, members, ...] tensor with B >= 1 and members >= 1")
-    check_quantile_members(samples.shape[1])
-    if samples.device.type != "cuda":
-        raise RuntimeError(f"ensemble_quantiles runs only on a ROCm GPU (got {samples.device}): there is no CPU fallback")
-    if samples.dtype != torch.float32:
-        raise TypeError(f"samples must be float32 (got {samples.dtype})")
-    src = samples.contiguous()
-    B, K = src.shape[:2]
-    chw = src[0, 0].numel()
-    with torch.cuda.device(src.device):
-        out = torch.empty((B, len(levels)) + tuple(src.shape[2:]), dtype=torch.float32, device=src.device)
-        native.check(native.lib().mi_ensemble_quantiles(src.data_ptr(), B, K, chw, _levels_arg(levels), len(levels), out.data_ptr(),
-                                                        torch.cuda.current_stream(src.device).cuda_stream))
-    return out
-
-
-DEFAULT_SCORE_LEVELS = (0.05, 0.25, 0.5, 0.75, 0.95)
-
-
-class EnsembleScores(NamedTuple):
-    """What ``ensemble_scores`` returns (include/midd.h: THE ENSEMBLE SCORES).  Everything but ``crps_map`` lives on the host: the
-    scalars are float64 CPU tensors [B] composed in Python floats from the raw ``sums``, the integers int64 CPU tensors."""
-    crps: torch.Tensor                    # [B]: mean CRPS of the members' empirical distribution, A/(K N) - G/(K^2 N)
-    crps_fair: torch.Tensor               # [B]: the fair (unbiased in K) form, A/(K N) - G/(K (K-1) N); NaN for one member
-    rmse: torch.Tensor                    # [B]: root mean squared error of the ensemble mean, sqrt(E/N)
-    spread: torch.Tensor                  # [B]: root mean unbiased member variance, sqrt(V/N); ~ rmse for a calibrated ensemble
-    rank_hist: torch.Tensor               # int64 [B, 2K+1]: bin 2*lt + eq, the mid-rank of the truth among the members in half steps
-    count_lt: torch.Tensor                # int64 [B, nq]: valid pixels with truth <  the level's quantile map
-    count_le: torch.Tensor                # int64 [B, nq]: valid pixels with truth <= the level's quantile map
-    levels: Tuple[float, ...]             # the quantile levels
-    valid: torch.Tensor                   # int64 [B]: N = chw - invalid, the pixels whose truth and members are all finite
-    sums: torch.Tensor                    # float64 [B, 4]: the raw (A, G, E, V)
-    crps_map: Optional[torch.Tensor]      # float32 [B, ...] on the device with return_map=True: per-pixel CRPS, NaN where invalid
-
-    def coverage(self, lo: int = 0, hi: int = -1) -> torch.Tensor:
-        """float64 [B]: the share of valid pixels whose truth lies inside [Q_lo, Q_hi], the quantile maps of ``levels[lo]`` and
-        ``levels[hi]`` -- (count_le[:, hi] - count_lt[:, lo]) / valid; compare it with ``levels[hi] - levels[lo]``."""
-        return (self.count_le[:, hi] - self.count_lt[:, lo]).to(torch.float64) / self.valid.to(torch.float64)
-
-
-def check_score_levels(quantiles) -> Tuple[float, ...]:
-    """``check_levels``, except that no level at all (None or an empty sequence) is allowed: the scores then carry no coverage."""
-    if quantiles is None or (isinstance(quantiles, (tuple, list)) and len(quantiles) == 0):
-        return ()
-    return check_levels(quantiles)
-
-
-@torch.no_grad()
-def ensemble_scores(samples: torch.Tensor, truth: torch.Tensor, quantiles=DEFAULT_SCORE_LEVELS, return_map: bool = False) -> EnsembleScores:
-    """Proper scores of an ensemble ``samples`` [B, K, ...] against ``truth`` [B, ...] in one launch (mi_ensemble_scores; include/midd.h:
-    THE ENSEMBLE SCORES): CRPS and fair CRPS, the RMSE of the ensemble mean beside the spread, the rank histogram of the truth among
-    the members with exact mid-rank ties, and for every level of ``quantiles`` how many pixels have their truth below that quantile
-    map (``EnsembleScores.coverage``: is the 5-95 % interval a 90 % interval?).  K <= 64, at most 8 levels (none: no coverage).  A
-    pixel whose truth or any member is not finite is left out of everything and counted (``valid`` = pixels - invalid).  The raw
-    outputs are copied to the host once (that waits for the stream); ``return_map=True`` also returns the per-pixel CRPS, which
-    stays on the device."""
-    levels = check_score_levels(quantiles)
-    if not isinstance(samples, torch.Tensor) or samples.dim() < 3 or samples.shape[0] < 1 or samples.shape[1] < 1:
-        raise ValueError("samples must be a [B, members, ...] tensor with B >= 1 and members >= 1")
-    check_quantile_members(samples.shape[1])
-    if not isinstance(truth, torch.Tensor) or tuple(truth.shape) != (samples.shape[0],) + tuple(samples.shape[2:]) or truth.device != samples.device:
-        raise ValueError(f"truth must be a tensor of shape {(samples.shape[0],) + tuple(samples.shape[2:])} on {samples.device}: one image per "
-                         "ensemble, without the member axis")
-    if samples.device.type != "cuda":
-        raise RuntimeError(f"ensemble_scores runs only on a ROCm GPU (got {samples.device}): there is no CPU fallback")
-    if samples.dtype != torch.float32 or truth.dtype != torch.float32:
-        raise TypeError(f"samples and truth must be float32 (got {samples.dtype} and {truth.dtype})")
-    src, tru = samples.contiguous(), truth.contiguous()
-    B, K = src.shape[:2]
-    chw = src[0, 0].numel()
-    nq, bins = len(levels), 2 * K + 1
-    lib = native.lib()
-    dev = src.device
-    with torch.cuda.device(dev):
-        # one 8-byte-word buffer for the raw outputs [sums B*4 | invalid B | rank_hist B*bins | counts B*nq*2]: one copy to the host
-        raw = torch.empty(B * (4 + 1 + bins + 2 * nq), dtype=torch.int64, device=dev)
-        o_inv, o_rank, o_cnt = B * 4, B * 5, B * (5 + bins)
-        cmap = torch.empty_like(tru) if return_map else None
-        nbytes = lib.mi_ensemble_scores_workspace_bytes(B, K, chw)
-        if nbytes == 0:
-            native.check(-1)
-        ws = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
-        base = raw.data_ptr()
-        native.check(lib.mi_ensemble_scores(src.data_ptr(), tru.data_ptr(), B, K, chw, _levels_arg(levels) if nq else None, nq,
-                                            base, base + 8 * o_inv, base + 8 * o_rank, base + 8 * o_cnt if nq else None,
-                                            None if cmap is None else cmap.data_ptr(), ws.data_ptr(), nbytes,
-                                            torch.cuda.current_stream(dev).cuda_stream))
-        host = raw.cpu()
-    sums = host[:o_inv].view(torch.float64).reshape(B, 4).clone()
-    invalid = host[o_inv:o_rank]
-    rank_hist = host[o_rank:o_cnt].reshape(B, bins).clone()
-    counts = host[o_cnt:].reshape(B, nq, 2)
-    valid = chw - invalid
-    crps, fair, rmse, spread = [], [], [], []
-    nan = float("nan")
-    for b in range(B):
-        A, G, E, V = (float(v) for v in sums[b])
-        N = int(valid[b])
-        crps.append(A / (K * N) - G / (K * K * N) if N else nan)
-        fair.append(A / (K * N) - G / (K * (K - 1) * N) if N and K > 1 else nan)
-        rmse.append((E / N) ** 0.5 if N else nan)
-        spread.append((V / N) ** 0.5 if N else nan)
-    f64 = lambda v: torch.tensor(v, dtype=torch.float64)
-    return EnsembleScores(f64(crps), f64(fair), f64(rmse), f64(spread), rank_hist, counts[:, :, 0].clone(), counts[:, :, 1].clone(), levels,
-                          valid.clone(), sums, cmap)
-
-
-NPS_ROIS = (32, 64, 128)
-NPS_DETREND = {"none": 0, "mean": 1, "plane": 2}
-
-
-class NoisePowerSpectrum(NamedTuple):
-    """What ``noise_power_spectrum`` returns (include/midd.h: THE NOISE POWER SPECTRUM), on the host.  A group is a (b, c) pair; an input
-    [H, W] drops the two leading axes."""
-    nps: torch.Tensor                     # float64 [B, C, R, R]: DFT order (index 0 is DC), frequencies in cycles per pixel
-    radial: torch.Tensor                  # float64 [B, C, R/2+1]: the mean of the entries of radial bin r; NaN where the bin is empty
-    radial_count: torch.Tensor            # int64 [R/2+1]: entries per bin
-    freqs: torch.Tensor                   # float64 [R/2+1]: r / R, cycles per pixel (0 .. 0.5)
-    rois_used: torch.Tensor               # int64 [B, C]: ROIs averaged
-    rois_skipped: torch.Tensor            # int64 [B, C]: ROIs left out because they hold a NaN or an Inf
-    roi: int
-    step: int
-
-    def variance(self) -> torch.Tensor:
-        """float64 [B, C]: the Parseval integral sum(nps) / R^2 -- ``scale`` times the mean windowed variance of the detrended ROIs."""
-        return self.nps.sum(dim=(-2, -1)) / float(self.roi * self.roi)
-
-
-def nps_window(window, roi: int) -> Optional[torch.Tensor]:
-    """The window table of ``noise_power_spectrum`` as a float32 CPU tensor [roi], or None: "hann" is the periodic
-    0.5 - 0.5 cos(2 pi n / roi), computed in double and rounded to fp32; a sequence or tensor of ``roi`` finite numbers is taken as is."""
-    if window is None:
-        return None
-    if isinstance(window, str):
-        if window != "hann":
-            raise ValueError(f"window must be 'hann', None or a table of {roi} numbers (got {window!r})")
-        return torch.tensor([0.5 - 0.5 * math.cos(2.0 * math.pi * n / roi) for n in range(roi)], dtype=torch.float64).to(torch.float32)
-    w = torch.as_tensor(window).detach().to("cpu", torch.float32).contiguous()
-    if w.dim() != 1 or w.numel() != roi or not bool(torch.isfinite(w).all()):
-        raise ValueError(f"window must be 'hann', None or a table of {roi} finite numbers")
-    return w
-
-
-def check_nps_args(roi, step, detrend):
-    if isinstance(roi, bool) or not isinstance(roi, int) or roi not in NPS_ROIS:
-        raise ValueError(f"roi must be one of {NPS_ROIS} (got {roi!r})")
-    if step is None:
-        step = roi // 2
-    if isinstance(step, bool) or not isinstance(step, int) or step < 1:
-        raise ValueError(f"step must be an integer >= 1 (got {step!r})")
-    if detrend not in NPS_DETREND:
-        raise ValueError(f"detrend must be one of {tuple(NPS_DETREND)} (got {detrend!r})")
-    return roi, step
-
-
-@torch.no_grad()
-def noise_power_spectrum(a: torch.Tensor, b: Optional[torch.Tensor] = None, roi: int = 64, step: Optional[int] = None, detrend: str = "plane",
-                         window="hann", scale: float = 1.0, exclude_axes: bool = False) -> NoisePowerSpectrum:
-    """The noise power spectrum of the field ``a - b`` by Welch's method (mi_noise_power_spectrum; include/midd.h: THE NOISE POWER
-    SPECTRUM): overlapping ``roi`` x ``roi`` regions at ``step`` (default roi / 2) are detrended ("none", "mean", "plane"), windowed
-    ("hann", None or a table), transformed on the device, their periodograms averaged per (b, c) group over the K members and every
-    position, and the average binned by radial frequency.  ``a`` is [B, K, C, H, W], [B, C, H, W] (K = 1) or [H, W]; ``b`` is
-    [B, C, H, W] ([H, W] for an [H, W] field), broadcast over K, subtracted inside the kernel.  White noise of variance s^2 gives a
-    flat spectrum of ``scale`` * s^2.  ROIs holding a NaN or an Inf are left out and counted.  The results are copied to the host
-    once (that waits for the stream)."""
-    roi, step = check_nps_args(roi, step, detrend)
-    w = nps_window(window, roi)
-    scale = float(scale)
-    if not math.isfinite(scale):
-        raise ValueError(f"scale must be finite (got {scale!r})")
-    if not isinstance(a, torch.Tensor) or a.dim() not in (2, 4, 5):
-        raise ValueError("a must be a [B, K, C, H, W], [B, C, H, W] or [H, W] tensor")
-    flat = a.dim() == 2
-    a5 = a[None, None, None] if flat else (a[:, None] if a.dim() == 4 else a)
-    B, K, CH, H, W = a5.shape
-    if min(B, K, CH) < 1:
-        raise ValueError("a must have B >= 1, K >= 1 and C >= 1")
-    b4 = None
-    if b is not None:
-        want = (H, W) if flat else (B, CH, H, W)
-        if not isinstance(b, torch.Tensor) or tuple(b.shape) != want or b.device != a.device:
-            raise ValueError(f"b must be a tensor of shape {want} on {a.device}: one image per (b, c) group, without the member axis")
-        b4 = b[None, None] if flat else b
-    if H < roi or W < roi:
-        raise ValueError(f"the image ({H} x {W}) is smaller than the ROI ({roi} x {roi}): there are no partial ROIs")
-    if a.device.type != "cuda":
-        raise RuntimeError(f"noise_power_spectrum runs only on a ROCm GPU (got {a.device}): there is no CPU fallback")
-    if a.dtype != torch.float32 or (b is not None and b.dtype != torch.float32):
-        raise TypeError(f"a and b must be float32 (got {a.dtype}" + (f" and {b.dtype})" if b is not None else ")"))
-    src = a5.contiguous()
-    sub = None if b4 is None else b4.contiguous()
-    lib = native.lib()
-    dev = src.device
-    G, bins = B * CH, roi // 2 + 1
-    with torch.cuda.device(dev):
-        # one 8-byte-word buffer for the outputs [nps G*R*R | radial G*bins | radial_count bins | used G | skipped G]: one copy to the host
-        o_rad = G * roi * roi
-        o_cnt, o_used, o_skip = o_rad + G * bins, o_rad + G * bins + bins, o_rad + G * bins + bins + G
-        raw = torch.empty(o_skip + G, dtype=torch.int64, device=dev)
-        nbytes = lib.mi_noise_power_spectrum_workspace_bytes(B, K, CH, H, W, roi, step)
-        if nbytes == 0:
-            native.check(-1)
-        ws = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
-        base = raw.data_ptr()
-        warg = None if w is None else (C.c_float * roi)(*w.tolist())
-        native.check(lib.mi_noise_power_spectrum(src.data_ptr(), None if sub is None else sub.data_ptr(), B, K, CH, H, W, roi, step,
-                                                 NPS_DETREND[detrend], warg, scale, 1 if exclude_axes else 0,
-                                                 base, base + 8 * o_rad, base + 8 * o_cnt, base + 8 * o_used, base + 8 * o_skip,
-                                                 ws.data_ptr(), nbytes, torch.cuda.current_stream(dev).cuda_stream))
-        host = raw.cpu()
-    nps = host[:o_rad].view(torch.float64).reshape(B, CH, roi, roi).clone()
-    radial = host[o_rad:o_cnt].view(torch.float64).reshape(B, CH, bins).clone()
-    count = host[o_cnt:o_used].clone()
-    used, skipped = host[o_used:o_skip].reshape(B, CH).clone(), host[o_skip:].reshape(B, CH).clone()
-    if flat:
-        nps, radial, used, skipped = nps[0, 0], radial[0, 0], used[0, 0], skipped[0, 0]
-    freqs = torch.arange(bins, dtype=torch.float64) / float(roi)
-    return NoisePowerSpectrum(nps, radial, count, freqs, used, skipped, roi, step)
-
-
-class LossMaps(NamedTuple):
-    """The per-pixel maps of ``denoising_loss(..., return_maps=True)``, each [B, C, H, W] (include/midd.h: THE DENOISING LOSS)."""
-    q: torch.Tensor          # squared error of the predicted noise
-    g: torch.Tensor          # |Sobel magnitude of the predicted clean image - that of the clean image|
-    p: torch.Tensor          # the predicted clean image, clamped to [0, 1]
-
-
-class DenoisingLoss(NamedTuple):
-    """``DiffusionDenoiser.denoising_loss``: per-sample float64 [B] scalars, the timesteps [B] they were taken at, the seed of the
-    forward noise (None with a caller's ``noise``) and, on request, the per-pixel maps."""
-    loss: torch.Tensor
-    mse: torch.Tensor
-    edge: torch.Tensor
-    t: torch.Tensor
-    seed: Optional[int]
-    maps: Optional[LossMaps]
-
-
-class LossProfile(NamedTuple):
-    """``DiffusionDenoiser.loss_profile``: the timesteps (a tuple of T ints) and float64 CPU tensors [T, B]."""
-    t: Tuple[int, ...]
-    loss: torch.Tensor
-    mse: torch.Tensor
-    edge: torch.Tensor
-
-
-def check_loss_source(seed, noise, sample_offset, draw, like: torch.Tensor) -> Tuple[Optional[int], int, int]:
-    """Argument rules of the forward noise (include/midd.h: THE FORWARD NOISE) -> (seed or None, sample_offset, draw); raises
-    ValueError before any GPU work.  Exactly one of ``seed`` (drawn on the device) and ``noise`` (a tensor like ``like``)."""
-    if seed is not None and noise is not None:
-        raise ValueError("pass either seed (noise drawn on the device) or noise (a tensor), not both")
-    if seed is None and noise is None:
-        raise ValueError("pass a seed (noise drawn on the device) or a noise tensor")
-    _, sample_offset = check_seed(0, sample_offset)
-    draw = _integer(draw, "draw", 1 << 31)
-    if seed is not None:
-        return _integer(seed, "seed", 1 << 64), sample_offset, draw
-    if not isinstance(noise, torch.Tensor) or noise.shape != like.shape or noise.dtype != like.dtype or noise.device != like.device:
-        raise ValueError(f"noise must be a {like.dtype} tensor of shape {tuple(like.shape)} on {like.device}")
-    return None, sample_offset, draw
-
-
-def loss_table_args(t, alpha_hat, B: int):
-    """-> (host arrays to keep alive over the call, (t, alpha_hat, noise_steps) as the loss calls take them); ValueError for a ``t``
-    that has not B entries or leaves [0, noise_steps).  ``alpha_hat``: the schedule tensor (copied to the host here: from a device
-    that waits for its stream) or a float32 host array its owner keeps (``DiffusionDenoiser`` does, per instance)."""
-    import numpy as np
-    if isinstance(alpha_hat, np.ndarray):
-        tab = np.ascontiguousarray(alpha_hat, dtype=np.float32)
-    else:
-        tab = np.ascontiguousarray(alpha_hat.detach().to("cpu", torch.float32).numpy())
-    tt = torch.as_tensor(t).reshape(-1).to("cpu", torch.int64)
-    if tt.numel() != B:
-        raise ValueError(f"t must have {B} entries (got {tt.numel()})")
-    if B and (int(tt.min()) < 0 or int(tt.max()) >= tab.shape[0]):
-        raise ValueError(f"t must be in [0, {tab.shape[0]}) (got {tt.tolist()})")
-    t_host = np.ascontiguousarray(tt.numpy().astype(np.int32))
-    return [tab, t_host], (t_host.ctypes.data_as(C.POINTER(C.c_int32)), tab.ctypes.data_as(C.POINTER(C.c_float)), int(tab.shape[0]))
-
-
-def loss_counter_args(seed, sample_index, draws, B: int):
-    """-> (host arrays to keep alive, (sample_index, draws) as the loss calls take them: int64 [B] or NULL each)."""
-    import numpy as np
-    if seed is None and (sample_index is not None or draws is not None):
-        raise ValueError("sample_index and draws are counter words of the seeded noise: pass seed as well")
-    keep, out = [], []
-    for v, what, bound in ((sample_index, "sample_index", 1 << 63), (draws, "draws", 1 << 31)):
-        if v is None:
-            out.append(None)
-            continue
-        vals = [_integer(i, what, bound) for i in v]
-        if len(vals) != B:
-            raise ValueError(f"{what} must have {B} entries (got {len(vals)})")
-        keep.append(np.ascontiguousarray(np.asarray(vals, dtype=np.int64)))
-        out.append(keep[-1].ctypes.data_as(C.POINTER(C.c_int64)))
-    return keep, tuple(out)
-
-
-def _loss_tensor(x, what: str, like: Optional[torch.Tensor] = None) -> torch.Tensor:
-    if not isinstance(x, torch.Tensor) or x.dim() != 4 or min(x.shape) < 1:
-        raise ValueError(f"{what} must be a [B, C, H, W] tensor")
-    if like is not None and (x.shape != like.shape or x.device != like.device):
-        raise ValueError(f"{what} must match the clean images in shape and device (got {tuple(x.shape)} on {x.device})")
-    if x.dtype != torch.float32:
-        raise TypeError(f"{what} must be float32 (got {x.dtype})")
-    return x
-
-
-@torch.no_grad()
-def noise_images(x: torch.Tensor, t, alpha_hat: torch.Tensor, seed: Optional[int] = None, sample_offset: int = 0, draw: int = 0,
-                 noise: Optional[torch.Tensor] = None, sample_index=None, draws=None) -> Tuple[torch.Tensor, torch.Tensor]:
-    """(x_t, eps) with x_t = sqrt(alpha_hat[t]) * x + sqrt(1 - alpha_hat[t]) * eps per sample (mi_noise_images; include/midd.h: THE
-    NOISING): the bits of the reference's expression in torch eager.  eps is ``noise`` or the seeded forward noise of
-    (seed, sample_offset + b, draw), drawn on the device (THE FORWARD NOISE).  ``alpha_hat``: the schedule tensor, or a float32 host
-    array of it (a device tensor is copied to the host per call, which waits for the stream)."""
-    x = _loss_tensor(x, "x")
-    seed, sample_offset, draw = check_loss_source(seed, noise, sample_offset, draw, x)
-    B, Cc, H, W = x.shape
-    keep, tables = loss_table_args(t, alpha_hat, B)
-    keep2, counters = loss_counter_args(seed, sample_index, draws, B)
-    if x.device.type != "cuda":
-        raise RuntimeError(f"noise_images runs only on a ROCm GPU (got {x.device}): there is no CPU fallback")
-    with torch.cuda.device(x.device):
-        src = x.contiguous()
-        eps = noise.contiguous() if seed is None else torch.empty_like(src)
-        x_t = torch.empty_like(src)
-        native.check(native.lib().mi_noise_images(src.data_ptr(), *tables, eps.data_ptr() if seed is None else None, 0 if seed is None else 1,
-                                                  C.c_uint64(seed or 0), C.c_int64(sample_offset), C.c_int64(draw), *counters,
-                                                  x_t.data_ptr(), None if seed is None else eps.data_ptr(), B, Cc, H, W,
-                                                  torch.cuda.current_stream(x.device).cuda_stream))
-    return x_t, eps
-
-
-@torch.no_grad()
-def loss_terms(clean: torch.Tensor, eps_pred: torch.Tensor, t, alpha_hat: torch.Tensor, x_t: Optional[torch.Tensor] = None,
-               noise: Optional[torch.Tensor] = None, seed: Optional[int] = None, sample_offset: int = 0, draw: int = 0,
-               clamp_eps: bool = True, edge_weight: float = 0.2, return_maps: bool = False, sample_index=None, draws=None):
-    """THE DENOISING LOSS (include/midd.h) of a given predicted noise, no network (mi_loss_terms) -> (out float64 [B, 3] =
-    (mse, edge, loss), maps float32 [3, B, C, H, W] = (q, g, p) or None).  Explicit form: ``x_t`` and ``noise``; seeded form: ``seed``
-    (x_t and the noise are formed again on the device, the bits of the explicit form on what ``noise_images(seed=...)`` returns)."""
-    clean = _loss_tensor(clean, "clean")
-    eps_pred = _loss_tensor(eps_pred, "eps_pred", clean)
-    seed, sample_offset, draw = check_loss_source(seed, noise, sample_offset, draw, clean)
-    if (seed is None) != (x_t is not None):
-        raise ValueError("x_t goes with noise (the explicit form); the seeded form takes neither")
-    if x_t is not None:
-        x_t = _loss_tensor(x_t, "x_t", clean)
-    B, Cc, H, W = clean.shape
-    keep, tables = loss_table_args(t, alpha_hat, B)
-    keep2, counters = loss_counter_args(seed, sample_index, draws, B)
-    if clean.device.type != "cuda":
-        raise RuntimeError(f"loss_terms runs only on a ROCm GPU (got {clean.device}): there is no CPU fallback")
-    dev = clean.device
-    lib = native.lib()
-    with torch.cuda.device(dev):
-        cl, pred = clean.contiguous(), eps_pred.contiguous()
-        xt = None if x_t is None else x_t.contiguous()
-        eps = None if noise is None else noise.contiguous()
-        out = torch.empty((B, 3), dtype=torch.float64, device=dev)
-        maps = torch.empty((3,) + tuple(cl.shape), dtype=torch.float32, device=dev) if return_maps else None
-        nbytes = lib.mi_loss_workspace_bytes(B, Cc, H, W)
-        if nbytes == 0:
-            native.check(-1)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        native.check(lib.mi_loss_terms(cl.data_ptr(), None if xt is None else xt.data_ptr(), None if eps is None else eps.data_ptr(),
-                                       pred.data_ptr(), *tables, 0 if seed is None else 1, C.c_uint64(seed or 0), C.c_int64(sample_offset),
-                                       C.c_int64(draw), *counters, native.MI_CLAMP_EPS if clamp_eps else 0, C.c_double(float(edge_weight)),
-                                       out.data_ptr(), None if maps is None else maps.data_ptr(), B, Cc, H, W, ws.data_ptr(), ws.numel(),
-                                       torch.cuda.current_stream(dev).cuda_stream))
-    return out, maps
-
-
-class TiledResult(NamedTuple):
-    """What ``DiffusionDenoiser.denoise_tiled`` returns."""
-    image: torch.Tensor                   # [B, C, H, W]: the blended image, at the input's own size
-    tiles: Optional[torch.Tensor]         # [B, ny * nx, C, th, tw] with return_tiles=True: the denoised tiles, k = ky * nx + kx
-    origins_y: Tuple[int, ...]            # row origin of every tile row
-    origins_x: Tuple[int, ...]            # column origin of every tile column
-    seed: Optional[int]                   # cddpm: the seed of the run (drawn when the call had seed=None); None for DDIM
-
-
-class TiledEnsembleResult(NamedTuple):
-    """What ``DiffusionDenoiser.denoise_tiled_ensemble`` returns."""
-    mean: torch.Tensor                    # [B, C, H, W]: per-pixel mean of the members' blended images, at the input's own size
-    std: Optional[torch.Tensor]           # [B, C, H, W]: unbiased per-pixel standard deviation; None for one member
-    samples: Optional[torch.Tensor]       # [B, members, C, H, W] with return_samples=True: every member's blended image
-    tiles: Optional[torch.Tensor]         # [members, B, ny * nx, C, th, tw] with return_tiles=True: tiles[m] is a TiledResult.tiles
-    origins_y: Tuple[int, ...]            # row origin of every tile row
-    origins_x: Tuple[int, ...]            # column origin of every tile column
-    seed: int                             # the seed of the run (drawn when the call had seed=None): pass it to repeat the run
-
-
-class TiledEnsembleQuantileResult(NamedTuple):
-    """What ``DiffusionDenoiser.denoise_tiled_ensemble(..., quantiles=levels)`` returns: TiledEnsembleResult's fields, then the maps."""
-    mean: torch.Tensor
-    std: Optional[torch.Tensor]
-    samples: Optional[torch.Tensor]
-    tiles: Optional[torch.Tensor]
-    origins_y: Tuple[int, ...]
-    origins_x: Tuple[int, ...]
-    seed: int
-    quantiles: torch.Tensor               # [B, nq, C, H, W]: per-pixel quantile maps of the members' blended images
-    levels: Tuple[float, ...]             # the quantile levels, each in [0, 1]
-
-
-class TilePlan(NamedTuple):
-    """What ``tile_plan`` returns: the tiling of an H x W image (include/midd.h: mi_tile_geometry)."""
-    tile: Tuple[int, int]                 # (th, tw)
-    overlap: Tuple[int, int]              # (oy, ox): the minimum overlap of neighbouring tiles
-    origins_y: Tuple[int, ...]
-    origins_x: Tuple[int, ...]
-
-
-def _pair(v, what: str, low: int) -> Tuple[int, int]:
-    a, b = (v if isinstance(v, (tuple, list)) and len(v) == 2 else (v, v))
-    return _integer(a, what, 1 << 31, low), _integer(b, what, 1 << 31, low)
-
-
-def _axis(L: int, T: int, O: int) -> Tuple[int, ...]:
-    lib = native.lib()
-    n = C.c_int()
-    native.check(lib.mi_tile_geometry(L, T, O, C.byref(n), None, 0))
-    origins = (C.c_int * n.value)()
-    native.check(lib.mi_tile_geometry(L, T, O, C.byref(n), origins, n.value))
-    return tuple(origins)
-
-
-def tile_plan(H: int, W: int, tile, overlap=32) -> TilePlan:
-    """The tiling ``denoise_tiled`` uses for an H x W image (host only): ``tile`` and ``overlap`` are ints or (y, x) pairs.
-    Raises MiddError for a tile larger than the image or an overlap outside [0, tile / 2]."""
-    (th, tw), (oy, ox) = _pair(tile, "tile", 1), _pair(overlap, "overlap", 0)
-    H, W = _integer(H, "H", 1 << 31, 1), _integer(W, "W", 1 << 31, 1)
-    return TilePlan((th, tw), (oy, ox), _axis(H, th, oy), _axis(W, tw, ox))
-
-
-def tiling(H: int, W: int, tile, overlap=32) -> Tuple[TilePlan, int, int, int, int, int]:
-    """``tile_plan`` with what the native calls take: (plan, th, tw, oy, ox, tiles per image)."""
-    plan = tile_plan(H, W, tile, overlap)
-    return (plan,) + plan.tile + plan.overlap + (len(plan.origins_y) * len(plan.origins_x),)
-
-
-def _tile_tensor(x, what: str, dims: int) -> torch.Tensor:
-    if not isinstance(x, torch.Tensor) or x.dim() != dims or min(x.shape) < 1:
-        raise ValueError(f"{what} must be a {dims}-dimensional non-empty tensor")
-    if x.device.type != "cuda":
-        raise RuntimeError(f"{what} is on {x.device}: tiling runs only on a ROCm GPU, there is no CPU fallback")
-    if x.dtype != torch.float32:
-        raise TypeError(f"{what} must be float32 (got {x.dtype})")
-    return x.contiguous()
-
-
-@torch.no_grad()
-def tile_extract(images: torch.Tensor, tile, overlap=32) -> torch.Tensor:
-    """[B, C, H, W] -> its tiles [B, ny * nx, C, th, tw] (mi_tile_extract): what ``denoise_tiled`` feeds the sampler."""
-    src = _tile_tensor(images, "images", 4)
-    B, Cc, H, W = src.shape
-    _, th, tw, oy, ox, K = tiling(H, W, tile, overlap)
-    with torch.cuda.device(src.device):
-        out = torch.empty((B, K, Cc, th, tw), dtype=torch.float32, device=src.device)
-        stream = torch.cuda.current_stream(src.device).cuda_stream
-        for v0 in range(0, B * K, 65535):
-            n = min(65535, B * K - v0)
-            native.check(native.lib().mi_tile_extract(src.data_ptr(), B, Cc, H, W, th, tw, oy, ox, v0, n,
-                                                      out.data_ptr() + v0 * Cc * th * tw * 4, stream))
-    return out
-
-
-@torch.no_grad()
-def tile_blend(tiles: torch.Tensor, H: int, W: int, overlap=32) -> torch.Tensor:
-    """tiles [B, ny * nx, C, th, tw] of an H x W tiling -> the blended images [B, C, H, W] with the arithmetic of
-    ``denoise_tiled`` (mi_tile_blend: integer ramp windows, double precision, tiles in index order)."""
-    src = _tile_tensor(tiles, "tiles", 5)
-    B, K, Cc, th, tw = src.shape
-    plan = tile_plan(H, W, (th, tw), overlap)
-    if K != len(plan.origins_y) * len(plan.origins_x):
-        raise ValueError(f"tiles has {K} tiles per image; a {H}x{W} image with tile {th}x{tw} and overlap {plan.overlap} has "
-                         f"{len(plan.origins_y)} x {len(plan.origins_x)}")
-    with torch.cuda.device(src.device):
-        out = torch.empty((B, Cc, int(H), int(W)), dtype=torch.float32, device=src.device)
-        native.check(native.lib().mi_tile_blend(src.data_ptr(), B, Cc, int(H), int(W), th, tw, plan.overlap[0], plan.overlap[1],
-                                                out.data_ptr(), torch.cuda.current_stream(src.device).cuda_stream))
-    return out
-
-
-@torch.no_grad()
-def tile_blend_reduce(tiles: torch.Tensor, H: int, W: int, overlap=32,
-                      return_samples: bool = False) -> Tuple[torch.Tensor, Optional[torch.Tensor], Optional[torch.Tensor]]:
-    """tiles [members, B, ny * nx, C, th, tw] of an H x W tiling -> (mean, std, samples): per-pixel mean and unbiased std
-    [B, C, H, W] over the members' blended images and, with ``return_samples``, those images [B, members, C, H, W], in one kernel
-    with the arithmetic of ``denoise_tiled_ensemble`` (mi_tile_blend_reduce: ``tile_blend`` per member, then ``ensemble_reduce``
-    over the members, bit for bit).  std is None for one member."""
-    src = _tile_tensor(tiles, "tiles", 6)
-    M, B, K, Cc, th, tw = src.shape
-    plan = tile_plan(H, W, (th, tw), overlap)
-    if K != len(plan.origins_y) * len(plan.origins_x):
-        raise ValueError(f"tiles has {K} tiles per image; a {H}x{W} image with tile {th}x{tw} and overlap {plan.overlap} has "
-                         f"{len(plan.origins_y)} x {len(plan.origins_x)}")
-    with torch.cuda.device(src.device):
-        mean = torch.empty((B, Cc, int(H), int(W)), dtype=torch.float32, device=src.device)
-        std = torch.empty_like(mean) if M >= 2 else None
-        samples = torch.empty((B, M, Cc, int(H), int(W)), dtype=torch.float32, device=src.device) if return_samples else None
-        native.check(native.lib().mi_tile_blend_reduce(src.data_ptr(), B, M, Cc, int(H), int(W), th, tw, plan.overlap[0], plan.overlap[1],
-                                                       mean.data_ptr(), None if std is None else std.data_ptr(),
-                                                       None if samples is None else samples.data_ptr(),
-                                                       torch.cuda.current_stream(src.device).cuda_stream))
-    return mean, std, samples
-
-
-@torch.no_grad()
-def tile_blend_quantiles(tiles: torch.Tensor, H: int, W: int, overlap=32, q=None) -> torch.Tensor:
-    """tiles [members, B, ny * nx, C, th, tw] of an H x W tiling -> the per-pixel quantile maps [B, nq, C, H, W] of the members'
-    blended images at the levels ``q``, in one kernel with the arithmetic of ``denoise_tiled_ensemble(..., quantiles=q)``
-    (mi_tile_blend_quantiles: ``tile_blend`` per member, then ``ensemble_quantiles`` over the members, bit for bit; the blended
-    members are never stored).  members <= 64, at most 8 levels."""
-    if q is None:
-        raise ValueError("tile_blend_quantiles needs the quantile levels: q=(0.05, 0.5, 0.95), say")
-    levels = check_levels(q)
-    if isinstance(tiles, torch.Tensor) and tiles.dim() == 6:
-        check_quantile_members(tiles.shape[0])
-    src = _tile_tensor(tiles, "tiles", 6)
-    M, B, K, Cc, th, tw = src.shape
-    plan = tile_plan(H, W, (th, tw), overlap)
-    if K != len(plan.origins_y) * len(plan.origins_x):
-        raise ValueError(f"tiles has {K} tiles per image; a {H}x{W} image with tile {th}x{tw} and overlap {plan.overlap} has "
-                         f"{len(plan.origins_y)} x {len(plan.origins_x)}")
-    with torch.cuda.device(src.device):
-        out = torch.empty((B, len(levels), Cc, int(H), int(W)), dtype=torch.float32, device=src.device)
-        native.check(native.lib().mi_tile_blend_quantiles(src.data_ptr(), B, M, Cc, int(H), int(W), th, tw, plan.overlap[0], plan.overlap[1],
-                                                          _levels_arg(levels), len(levels), out.data_ptr(),
-                                                          torch.cuda.current_stream(src.device).cuda_stream))
-    return out
-
-
-class SelfEnsembleResult(NamedTuple):
-    """What ``DiffusionDenoiser.denoise_self_ensemble`` returns."""
-    mean: torch.Tensor                    # [B, C, H, W]: per-pixel mean over the views, each turned back into the image's frame
-    std: Optional[torch.Tensor]           # [B, C, H, W]: unbiased per-pixel standard deviation over the views; None for one view
-    samples: Optional[torch.Tensor]       # [B, views, C, H, W] with return_samples=True: the aligned members, in the order of ``views``
-    views: Tuple[int, ...]                # the view codes of the run (include/midd.h: THE GEOMETRY), as resolved from the argument
-    seed: Optional[int]                   # cddpm: the seed of the run (drawn when the call had seed=None); None for DDIM
-
-
-class SelfEnsembleQuantileResult(NamedTuple):
-    """What ``DiffusionDenoiser.denoise_self_ensemble(..., quantiles=levels)`` returns: SelfEnsembleResult's fields, then the maps."""
-    mean: torch.Tensor
-    std: Optional[torch.Tensor]
-    samples: Optional[torch.Tensor]
-    views: Tuple[int, ...]
-    seed: Optional[int]
-    quantiles: torch.Tensor               # [B, nq, C, H, W]: per-pixel quantile maps of the aligned members
-    levels: Tuple[float, ...]             # the quantile levels, each in [0, 1]
-
-
-MAX_VIEWS = 8                             # include/midd.h: view codes g = 4 * transpose + 2 * flip_rows + flip_columns, 0 .. 7
-VIEW_SETS = {"flips": (0, 1, 2, 3), "d4": (0, 1, 2, 3, 4, 5, 6, 7)}
-
-
-def view_codes(H: int, W: int, views="auto") -> Tuple[int, ...]:
-    """The view list of a self-ensemble over H x W images (host only): ``"auto"`` is all 8 flips and rotations for a square image
-    and the 4 that keep the shape otherwise, ``"flips"`` codes 0 .. 3, ``"d4"`` codes 0 .. 7, or a sequence of 1 to 8 distinct
-    codes in the order the members are wanted.  Raises ValueError for anything the native call would refuse."""
-    H, W = _integer(H, "H", 1 << 31, 1), _integer(W, "W", 1 << 31, 1)
-    if isinstance(views, str):
-        if views == "auto":
-            views = "d4" if H == W else "flips"
-        if views not in VIEW_SETS:
-            raise ValueError(f"views must be 'auto', 'flips', 'd4' or a sequence of view codes (got {views!r})")
-        codes = VIEW_SETS[views]
-    else:
-        try:
-            codes = tuple(views)
-        except TypeError:
-            raise ValueError(f"views must be 'auto', 'flips', 'd4' or a sequence of view codes (got {views!r})") from None
-        if not 1 <= len(codes) <= MAX_VIEWS:
-            raise ValueError(f"a view list holds between 1 and {MAX_VIEWS} view codes (got {len(codes)})")
-        out = []
-        for v in codes:
-            try:
-                if isinstance(v, bool):
-                    raise TypeError
-                g = operator.index(v)
-            except TypeError:
-                raise ValueError(f"every view code must be an integer in [0, 7] (got {v!r})") from None
-            if not 0 <= g <= 7:
-                raise ValueError(f"every view code must be an integer in [0, 7] (got {v!r})")
-            if g in out:
-                raise ValueError(f"view code {g} is repeated: the view codes of a list are distinct")
-            out.append(g)
-        codes = tuple(out)
-    for g in codes:
-        if g & 4 and H != W:
-            raise ValueError(f"view code {g} transposes the image: codes 4 .. 7 need H == W (got {H}x{W}; use views='flips')")
-    return codes
-
-
-def _views_arg(codes: Tuple[int, ...]):
-    return (C.c_int32 * len(codes))(*codes)
-
-
-def _view_tensor(x, what: str, dims: int) -> torch.Tensor:
-    if not isinstance(x, torch.Tensor) or x.dim() != dims or min(x.shape) < 1:
-        raise ValueError(f"{what} must be a {dims}-dimensional non-empty tensor")
-    if x.device.type != "cuda":
-        raise RuntimeError(f"{what} is on {x.device}: the view kernels run only on a ROCm GPU, there is no CPU fallback")
-    if x.dtype != torch.float32:
-        raise TypeError(f"{what} must be float32 (got {x.dtype})")
-    return x.contiguous()
-
-
-@torch.no_grad()
-def dihedral_views(images: torch.Tensor, views="auto") -> torch.Tensor:
-    """[B, C, H, W] -> its views [B, G, C, Hv, Wv] (mi_dihedral_views): what ``denoise_self_ensemble`` feeds the sampler.  Bit
-    copies; transposing views need H == W, so every view has the image's shape."""
-    if isinstance(images, torch.Tensor) and images.dim() == 4:
-        codes = view_codes(images.shape[2], images.shape[3], views)
-    src = _view_tensor(images, "images", 4)
-    B, Cc, H, W = src.shape
-    G = len(codes)
-    with torch.cuda.device(src.device):
-        out = torch.empty((B, G, Cc, H, W), dtype=torch.float32, device=src.device)
-        stream = torch.cuda.current_stream(src.device).cuda_stream
-        for v0 in range(0, B * G, 65535):
-            n = min(65535, B * G - v0)
-            native.check(native.lib().mi_dihedral_views(src.data_ptr(), B, Cc, H, W, _views_arg(codes), G, v0, n,
-                                                        out.data_ptr() + v0 * Cc * H * W * 4, stream))
-    return out
-
-
-@torch.no_grad()
-def dihedral_reduce(view_outputs: torch.Tensor, views="auto",
-                    return_samples: bool = True) -> Tuple[torch.Tensor, Optional[torch.Tensor], Optional[torch.Tensor]]:
-    """view_outputs [B, G, C, Hv, Wv], view k in its own frame -> (mean, std, samples): per-pixel mean and unbiased std [B, C, H, W]
-    over the views turned back into the image's frame and those aligned members [B, G, C, H, W], in one kernel with the arithmetic
-    of ``denoise_self_ensemble`` (mi_dihedral_reduce: unview per view, then ``ensemble_reduce``, bit for bit).  std is None for
-    one view; samples is None with ``return_samples=False``."""
-    if isinstance(view_outputs, torch.Tensor) and view_outputs.dim() == 5:
-        codes = view_codes(view_outputs.shape[3], view_outputs.shape[4], views)
-        if len(codes) != view_outputs.shape[1]:
-            raise ValueError(f"view_outputs holds {view_outputs.shape[1]} views per image, the view list {len(codes)}")
-    src = _view_tensor(view_outputs, "view_outputs", 5)
-    B, G, Cc, H, W = src.shape
-    with torch.cuda.device(src.device):
-        mean = torch.empty((B, Cc, H, W), dtype=torch.float32, device=src.device)
-        std = torch.empty_like(mean) if G >= 2 else None
-        samples = torch.empty_like(src) if return_samples else None
-        native.check(native.lib().mi_dihedral_reduce(src.data_ptr(), B, Cc, H, W, _views_arg(codes), G, mean.data_ptr(),
-                                                     None if std is None else std.data_ptr(),
-                                                     None if samples is None else samples.data_ptr(),
-                                                     torch.cuda.current_stream(src.device).cuda_stream))
-    return mean, std, samples
-
-
-@torch.no_grad()
-def dihedral_quantiles(view_outputs: torch.Tensor, views="auto", q=None) -> torch.Tensor:
-    """view_outputs [B, G, C, Hv, Wv] -> the per-pixel quantile maps [B, nq, C, H, W] of the aligned members at the levels ``q``
-    (mi_dihedral_quantiles: unview per view, then ``ensemble_quantiles``, bit for bit; the aligned members are never stored)."""
-    if q is None:
-        raise ValueError("dihedral_quantiles needs the quantile levels: q=(0.05, 0.5, 0.95), say")
-    levels = check_levels(q)
-    if isinstance(view_outputs, torch.Tensor) and view_outputs.dim() == 5:
-        codes = view_codes(view_outputs.shape[3], view_outputs.shape[4], views)
-        if len(codes) != view_outputs.shape[1]:
-            raise ValueError(f"view_outputs holds {view_outputs.shape[1]} views per image, the view list {len(codes)}")
-    src = _view_tensor(view_outputs, "view_outputs", 5)
-    B, G, Cc, H, W = src.shape
-    with torch.cuda.device(src.device):
-        out = torch.empty((B, len(levels), Cc, H, W), dtype=torch.float32, device=src.device)
-        native.check(native.lib().mi_dihedral_quantiles(src.data_ptr(), B, Cc, H, W, _views_arg(codes), G, _levels_arg(levels), len(levels),
-                                                        out.data_ptr(), torch.cuda.current_stream(src.device).cuda_stream))
-    return out
-
-
-class TiledSelfEnsembleResult(NamedTuple):
-    """What ``DiffusionDenoiser.denoise_tiled_self_ensemble`` returns."""
-    mean: torch.Tensor                    # [B, C, H, W]: per-pixel mean over the views' blended images, each turned back, at the input's own size
-    std: Optional[torch.Tensor]           # [B, C, H, W]: unbiased per-pixel standard deviation over the views; None for one view
-    samples: Optional[torch.Tensor]       # [B, views, C, H, W] with return_samples=True: the aligned blended members, in the order of ``views``
-    tiles: Optional[torch.Tensor]         # [views, B, ny * nx, C, th, tw] with return_tiles=True: tiles[k] are view k's tiles in ITS frame
-    views: Tuple[int, ...]                # the view codes of the run (include/midd.h: THE GEOMETRY), as resolved from the argument
-    origins_y: Tuple[int, ...]            # row origin of every tile row of the UN-TRANSPOSED frame (H x W); a transposing view is cut
-    origins_x: Tuple[int, ...]            # by the (W, H) plan: tile_plan(W, H, tile, overlap)
-    seed: Optional[int]                   # the seed of the run when it drew noise (drawn when the call had seed=None); else None
-
-
-class TiledSelfEnsembleQuantileResult(NamedTuple):
-    """What ``DiffusionDenoiser.denoise_tiled_self_ensemble(..., quantiles=levels)`` returns: TiledSelfEnsembleResult's fields, then the maps."""
-    mean: torch.Tensor
-    std: Optional[torch.Tensor]
-    samples: Optional[torch.Tensor]
-    tiles: Optional[torch.Tensor]
-    views: Tuple[int, ...]
-    origins_y: Tuple[int, ...]
-    origins_x: Tuple[int, ...]
-    seed: Optional[int]
-    quantiles: torch.Tensor               # [B, nq, C, H, W]: per-pixel quantile maps of the aligned blended members
-    levels: Tuple[float, ...]             # the quantile levels, each in [0, 1]
-
-
-def view_codes_tiled(H: int, W: int, tile, overlap=32, views="auto") -> Tuple[int, ...]:
-    """The view list of a TILED self-ensemble over H x W images (host only).  A transposed image is still cut into tiles, so the
-    transposing codes 4 .. 7 do not need H == W here; they need a square tile and overlap (th == tw and oy == ox), so that the
-    W x H frame has as many tiles of the same shape (include/midd.h: TILED SELF-ENSEMBLE).  ``"auto"`` is ``"d4"`` when the tile
-    and the overlap are square, whatever H and W, else ``"flips"``; ``"flips"``, ``"d4"`` and sequences as in ``view_codes``.
-    Raises ValueError for anything the native call would refuse in the list; the tiling itself is judged by ``tile_plan``."""
-    H, W = _integer(H, "H", 1 << 31, 1), _integer(W, "W", 1 << 31, 1)
-    (th, tw), (oy, ox) = _pair(tile, "tile", 1), _pair(overlap, "overlap", 0)
-    square = th == tw and oy == ox
-    if isinstance(views, str) and views == "auto":
-        views = "d4" if square else "flips"
-    codes = view_codes(1, 1, views)                           # (a 1 x 1 image is square: the list rules without the H == W clause)
-    for g in codes:
-        if g & 4 and not square:
-            raise ValueError(f"view code {g} transposes the image: with tiles, codes 4 .. 7 need a square tile and overlap "
-                             f"(got tile {th}x{tw}, overlap {oy}x{ox}; use views='flips')")
-    return codes
-
-
-def _unview_args(tiles, H, W, overlap, views):
-    """Shared by the two stand-alone calls: (src, codes, geometry) after every host-side rule."""
-    if isinstance(tiles, torch.Tensor) and tiles.dim() == 6:
-        th, tw = int(tiles.shape[4]), int(tiles.shape[5])
-        codes = view_codes_tiled(H, W, (th, tw), overlap, views)
-        if len(codes) != tiles.shape[0]:
-            raise ValueError(f"tiles holds {tiles.shape[0]} views, the view list {len(codes)}")
-    src = _tile_tensor(tiles, "tiles", 6)
-    G, B, K, Cc, th, tw = src.shape
-    plan = tile_plan(H, W, (th, tw), overlap)
-    if K != len(plan.origins_y) * len(plan.origins_x):
-        raise ValueError(f"tiles has {K} tiles per image; a {H}x{W} image with tile {th}x{tw} and overlap {plan.overlap} has "
-                         f"{len(plan.origins_y)} x {len(plan.origins_x)}")
-    return src, codes, plan
-
-
-@torch.no_grad()
-def tile_blend_unview_reduce(tiles: torch.Tensor, H: int, W: int, overlap=32, views="auto",
-                             return_samples: bool = False) -> Tuple[torch.Tensor, Optional[torch.Tensor], Optional[torch.Tensor]]:
-    """tiles [views, B, ny * nx, C, th, tw], view k's tiles in ITS frame (the tiling of the viewed image), of an H x W image ->
-    (mean, std, samples): per-pixel mean and unbiased std [B, C, H, W] over the views' blended images turned back into the image's
-    frame and, with ``return_samples``, those aligned members [B, views, C, H, W], in one kernel with the arithmetic of
-    ``denoise_tiled_self_ensemble`` (mi_tile_blend_unview_reduce: ``tile_blend`` per view in the view's frame, the un-view, then
-    ``ensemble_reduce``, bit for bit).  std is None for one view."""
-    src, codes, plan = _unview_args(tiles, H, W, overlap, views)
-    G, B, K, Cc, th, tw = src.shape
-    with torch.cuda.device(src.device):
-        mean = torch.empty((B, Cc, int(H), int(W)), dtype=torch.float32, device=src.device)
-        std = torch.empty_like(mean) if G >= 2 else None
-        samples = torch.empty((B, G, Cc, int(H), int(W)), dtype=torch.float32, device=src.device) if return_samples else None
-        native.check(native.lib().mi_tile_blend_unview_reduce(src.data_ptr(), B, Cc, int(H), int(W), th, tw, plan.overlap[0], plan.overlap[1],
-                                                              _views_arg(codes), G, mean.data_ptr(), None if std is None else std.data_ptr(),
-                                                              None if samples is None else samples.data_ptr(),
-                                                              torch.cuda.current_stream(src.device).cuda_stream))
-    return mean, std, samples
-
-
-@torch.no_grad()
-def tile_blend_unview_quantiles(tiles: torch.Tensor, H: int, W: int, overlap=32, views="auto", q=None) -> torch.Tensor:
-    """tiles as in ``tile_blend_unview_reduce`` -> the per-pixel quantile maps [B, nq, C, H, W] of the aligned blended members at the
-    levels ``q`` (mi_tile_blend_unview_quantiles: ``tile_blend`` per view, the un-view, then ``ensemble_quantiles``, bit for bit; the
-    members are never stored)."""
-    if q is None:
-        raise ValueError("tile_blend_unview_quantiles needs the quantile levels: q=(0.05, 0.5, 0.95), say")
-    levels = check_levels(q)
-    src, codes, plan = _unview_args(tiles, H, W, overlap, views)
-    G, B, K, Cc, th, tw = src.shape
-    with torch.cuda.device(src.device):
-        out = torch.empty((B, len(levels), Cc, int(H), int(W)), dtype=torch.float32, device=src.device)
-        native.check(native.lib().mi_tile_blend_unview_quantiles(src.data_ptr(), B, Cc, int(H), int(W), th, tw, plan.overlap[0], plan.overlap[1],
-                                                                 _views_arg(codes), G, _levels_arg(levels), len(levels), out.data_ptr(),
-                                                                 torch.cuda.current_stream(src.device).cuda_stream))
-    return out
 
 
 class DiffusionDenoiser:
@@ -1064,6 +67,40 @@ class DiffusionDenoiser:
             held = (ah, ah._version, np.array(ah.detach().to("cpu", torch.float32).numpy(), dtype=np.float32, copy=True))
             self._alpha_hat_held = held
         return held[2]
+
+    # ------------------------------------------------------------------ what the entries share
+    @property
+    def _stochastic(self) -> bool:
+        return getattr(self.model, "variant", "ddim") == "cddpm"
+
+    def _draws(self, rule, seed=None) -> bool:
+        """Does a call under ``rule`` (None: the reference's update) draw noise?  cddpm does under the reference's update, a rule
+        with eta > 0 does for both variants.  A ``seed`` given to the DDIM variant under the reference's update is refused."""
+        if rule is None and not self._stochastic and seed is not None:
+            raise ValueError("seed selects the step noise of the stochastic (cddpm) variant: the DDIM variant takes seed=None")
+        return self._stochastic if rule is None else rule.eta > 0.0
+
+    def _seed(self, draws: bool, seed, sample_offset=0) -> Tuple[Optional[int], int]:
+        """From which seed?  -> ``check_seed`` of (the caller's seed or a fresh one, sample_offset) where the call draws, else
+        (None, sample_offset as given)."""
+        if not draws:
+            return None, sample_offset
+        return check_seed(self._draw_seed() if seed is None else seed, sample_offset)
+
+    @staticmethod
+    def _rule_kw(rule, update, eta, clip_x0) -> dict:
+        """The rule's keywords for a ``run_*`` call; none for the reference's update, so that call is the call of before."""
+        return {} if rule is None else dict(update=update, eta=eta, clip_x0=clip_x0)
+
+    def _steps(self, inference_steps):
+        self.model.eval()
+        return timestep_list(self.noise_steps, inference_steps)
+
+    def _ensemble_with_samples(self, noisy, tile, overlap, **kw):
+        """``denoise_ensemble`` or, with ``tile``, ``denoise_tiled_ensemble``, with the members returned."""
+        if tile is None:
+            return self.denoise_ensemble(noisy, return_samples=True, **kw)
+        return self.denoise_tiled_ensemble(noisy, tile=tile, overlap=overlap, return_samples=True, **kw)
 
     @torch.no_grad()
     def denoise(self, noisy_img: torch.Tensor, inference_steps: int = 25,
@@ -1110,30 +147,24 @@ class DiffusionDenoiser:
         if dpm:
             if seed is not None or step_noise is not None or member != 0:
                 raise ValueError("update='dpmpp2m' is deterministic: it takes no seed, step_noise or member")
-            self.model.eval()
-            steps = timestep_list(self.noise_steps, inference_steps)
-            res = self.model.run_sampler(noisy_img, steps, self.beta, self.alpha, self.alpha_hat,
-                                         clamp_eps=getattr(self.model, "variant", "ddim") != "cddpm",
-                                         update=update, clip_x0=clip_x0, return_x0=return_x0)
+            res = self.model.run_sampler(noisy_img, self._steps(inference_steps), self.beta, self.alpha, self.alpha_hat,
+                                         clamp_eps=not self._stochastic, update=update, clip_x0=clip_x0, return_x0=return_x0)
             return SamplerTrajectory(*res) if return_x0 else res
         if seed is not None:
             if step_noise is not None:
                 raise ValueError("pass either seed (noise drawn on the device) or step_noise (a noise tensor), not both")
             seed, sample_offset = check_seed(seed, sample_offset)
-        self.model.eval()
-        steps = timestep_list(self.noise_steps, inference_steps)
-        stochastic = getattr(self.model, "variant", "ddim") == "cddpm"
-        draws = stochastic if rule is None else rule.eta > 0.0      # whether the call has a noise term at all
+        steps = self._steps(inference_steps)
+        stochastic = self._stochastic
+        draws = self._draws(rule)                                   # whether the call has a noise term at all
         if draws and step_noise is None and seed is None and member == 0:      # (a member without a seed: run_sampler refuses)
             step_noise = 0.5 * torch.randn((len(steps),) + tuple(noisy_img.shape), device=noisy_img.device)
         if not draws:
             step_noise = seed = None
             member = 0
         seeded = {"member": member} if seed is None else {"seed": seed, "sample_offset": sample_offset, "member": member}
-        if rule is not None:
-            seeded.update(update=update, eta=eta, clip_x0=clip_x0)
-        return self.model.run_sampler(noisy_img, steps, self.beta, self.alpha, self.alpha_hat,
-                                      clamp_eps=not stochastic, step_noise=step_noise, **seeded)
+        return self.model.run_sampler(noisy_img, steps, self.beta, self.alpha, self.alpha_hat, clamp_eps=not stochastic,
+                                      step_noise=step_noise, **seeded, **self._rule_kw(rule, update, eta, clip_x0))
 
     @torch.no_grad()
     def denoise_ensemble(self, noisy_img: torch.Tensor, inference_steps: int = 25, members: int = 8, seed: Optional[int] = None,
@@ -1163,23 +194,21 @@ class DiffusionDenoiser:
         DDIM variant does."""
         levels = None if quantiles is None else check_levels(quantiles)
         rule = check_update(update, eta, clip_x0)
-        stochastic = getattr(self.model, "variant", "ddim") == "cddpm"
+        stochastic = self._stochastic
         if rule is not None and rule.kind == native.MI_UPDATE["dpmpp2m"]:
             raise ValueError("denoise_ensemble with update='dpmpp2m': a deterministic sampler has no ensemble")
         if rule is not None and rule.eta == 0.0:
             raise ValueError("denoise_ensemble with update='ddim' needs eta > 0: a deterministic sampler has no ensemble")
         if rule is None and not stochastic:
             raise ValueError("denoise_ensemble needs the stochastic (cddpm) variant: a deterministic sampler has no ensemble")
-        seed, _ = check_seed(self._draw_seed() if seed is None else seed, 0)      # (everything else is judged by run_ensemble, before any GPU work)
+        seed, _ = self._seed(True, seed)      # (everything else is judged by run_ensemble, before any GPU work)
         if levels is not None:
             check_quantile_members(check_member(members, "members", low=1))
-        self.model.eval()
-        steps = timestep_list(self.noise_steps, inference_steps)
-        rule_kw = {} if rule is None else dict(update=update, eta=eta, clip_x0=clip_x0)
-        mean, std, samples = self.model.run_ensemble(noisy_img, steps, self.beta, self.alpha, self.alpha_hat, clamp_eps=not stochastic,
-                                                     members=members, seed=seed, sample_offset=sample_offset,
+        mean, std, samples = self.model.run_ensemble(noisy_img, self._steps(inference_steps), self.beta, self.alpha, self.alpha_hat,
+                                                     clamp_eps=not stochastic, members=members, seed=seed, sample_offset=sample_offset,
                                                      member_offset=member_offset, max_batch=max_batch,
-                                                     want_samples=return_samples or levels is not None, **rule_kw)
+                                                     want_samples=return_samples or levels is not None,
+                                                     **self._rule_kw(rule, update, eta, clip_x0))
         if levels is None:
             return EnsembleResult(mean, std, samples, seed)
         maps = ensemble_quantiles(samples, levels)
@@ -1211,20 +240,11 @@ class DiffusionDenoiser:
         if step_noise is not None:
             raise ValueError("denoise_tiled does not take a step_noise tensor: its noise is the seeded generator's, indexed by "
                              "image position (pass seed; midd_amd.step_noise(seed, n, x.shape) exports the same values)")
-        stochastic = getattr(self.model, "variant", "ddim") == "cddpm"
-        draws = stochastic if rule is None else rule.eta > 0.0
-        if rule is None and not stochastic and seed is not None:
-            raise ValueError("seed selects the step noise of the stochastic (cddpm) variant: the DDIM variant takes seed=None")
-        if draws:
-            seed, sample_offset = check_seed(self._draw_seed() if seed is None else seed, sample_offset)
-        else:
-            seed = None
-        self.model.eval()
-        steps = timestep_list(self.noise_steps, inference_steps)
-        rule_kw = {} if rule is None else dict(update=update, eta=eta, clip_x0=clip_x0)
-        image, tiles, plan = self.model.run_tiled(noisy_img, steps, self.beta, self.alpha, self.alpha_hat, clamp_eps=not stochastic,
-                                                  tile=tile, overlap=overlap, seed=seed, sample_offset=sample_offset,
-                                                  max_batch=max_batch, want_tiles=return_tiles, **rule_kw)
+        seed, sample_offset = self._seed(self._draws(rule, seed), seed, sample_offset)
+        image, tiles, plan = self.model.run_tiled(noisy_img, self._steps(inference_steps), self.beta, self.alpha, self.alpha_hat,
+                                                  clamp_eps=not self._stochastic, tile=tile, overlap=overlap, seed=seed,
+                                                  sample_offset=sample_offset, max_batch=max_batch, want_tiles=return_tiles,
+                                                  **self._rule_kw(rule, update, eta, clip_x0))
         return TiledResult(image, tiles, plan.origins_y, plan.origins_x, seed)
 
     @torch.no_grad()
@@ -1257,15 +277,13 @@ class DiffusionDenoiser:
         if step_noise is not None:
             raise ValueError("denoise_tiled_ensemble does not take a step_noise tensor: its noise is the seeded generator's, indexed by "
                              "image position and member (pass seed; midd_amd.step_noise(seed, n, x.shape, member=m) exports the same values)")
-        if getattr(self.model, "variant", "ddim") != "cddpm":
+        if not self._stochastic:
             raise ValueError("denoise_tiled_ensemble needs the stochastic (cddpm) variant: a deterministic sampler has no ensemble")
-        seed, _ = check_seed(self._draw_seed() if seed is None else seed, 0)      # (everything else is judged by run_tiled_ensemble, before any GPU work)
+        seed, _ = self._seed(True, seed)      # (everything else is judged by run_tiled_ensemble, before any GPU work)
         if levels is not None:
             check_quantile_members(check_member(members, "members", low=1))
-        self.model.eval()
-        steps = timestep_list(self.noise_steps, inference_steps)
         mean, std, samples, tiles, plan = self.model.run_tiled_ensemble(
-            noisy_img, steps, self.beta, self.alpha, self.alpha_hat, clamp_eps=False, tile=tile, overlap=overlap, members=members,
+            noisy_img, self._steps(inference_steps), self.beta, self.alpha, self.alpha_hat, clamp_eps=False, tile=tile, overlap=overlap, members=members,
             seed=seed, sample_offset=sample_offset, member_offset=member_offset, max_batch=max_batch,
             want_samples=return_samples, want_tiles=return_tiles or levels is not None)
         if levels is None:
@@ -1300,17 +318,12 @@ class DiffusionDenoiser:
         and samples are the bits of the call without it."""
         refuse_update(update, "denoise_self_ensemble")
         levels = None if quantiles is None else check_levels(quantiles)
-        stochastic = getattr(self.model, "variant", "ddim") == "cddpm"
-        if not stochastic and seed is not None:
-            raise ValueError("seed selects the step noise of the stochastic (cddpm) variant: the DDIM variant takes seed=None")
+        draws = self._draws(None, seed)
         if isinstance(noisy_img, torch.Tensor) and noisy_img.dim() == 4:
             views = view_codes(noisy_img.shape[2], noisy_img.shape[3], views)      # (before any GPU work; run_self_ensemble judges the rest)
-        if stochastic:
-            seed, _ = check_seed(self._draw_seed() if seed is None else seed, 0)
-        self.model.eval()
-        steps = timestep_list(self.noise_steps, inference_steps)
+        seed, _ = self._seed(draws, seed)
         mean, std, samples, codes, maps = self.model.run_self_ensemble(
-            noisy_img, steps, self.beta, self.alpha, self.alpha_hat, clamp_eps=not stochastic, views=views, seed=seed,
+            noisy_img, self._steps(inference_steps), self.beta, self.alpha, self.alpha_hat, clamp_eps=not draws, views=views, seed=seed,
             sample_offset=sample_offset, member_offset=member_offset, max_batch=max_batch, want_samples=return_samples, levels=levels)
         if levels is None:
             return SelfEnsembleResult(mean, std, samples, codes, seed)
@@ -1357,23 +370,14 @@ class DiffusionDenoiser:
             raise ValueError("denoise_tiled_self_ensemble runs the reference's update or update='ddim': update='dpmpp2m' is not built "
                              "for it (the native call takes no history buffer; denoise and denoise_tiled run it)")
         levels = None if quantiles is None else check_levels(quantiles)
-        stochastic = getattr(self.model, "variant", "ddim") == "cddpm"
-        draws = stochastic if rule is None else rule.eta > 0.0
-        if rule is None and not stochastic and seed is not None:
-            raise ValueError("seed selects the step noise of the stochastic (cddpm) variant: the DDIM variant takes seed=None")
+        draws = self._draws(rule, seed)
         if isinstance(noisy_img, torch.Tensor) and noisy_img.dim() == 4:
             views = view_codes_tiled(noisy_img.shape[2], noisy_img.shape[3], tile, overlap, views)      # (before any GPU work)
-        if draws:
-            seed, sample_offset = check_seed(self._draw_seed() if seed is None else seed, sample_offset)
-        else:
-            seed = None
-        self.model.eval()
-        steps = timestep_list(self.noise_steps, inference_steps)
-        rule_kw = {} if rule is None else dict(update=update, eta=eta, clip_x0=clip_x0)
+        seed, sample_offset = self._seed(draws, seed, sample_offset)
         mean, std, samples, tiles, codes, plan = self.model.run_tiled_self_ensemble(
-            noisy_img, steps, self.beta, self.alpha, self.alpha_hat, clamp_eps=not stochastic, tile=tile, overlap=overlap, views=views,
-            seed=seed, sample_offset=sample_offset, member_offset=member_offset, max_batch=max_batch, want_samples=return_samples,
-            want_tiles=return_tiles or levels is not None, **rule_kw)
+            noisy_img, self._steps(inference_steps), self.beta, self.alpha, self.alpha_hat, clamp_eps=not self._stochastic, tile=tile,
+            overlap=overlap, views=views, seed=seed, sample_offset=sample_offset, member_offset=member_offset, max_batch=max_batch,
+            want_samples=return_samples, want_tiles=return_tiles or levels is not None, **self._rule_kw(rule, update, eta, clip_x0))
         if levels is None:
             return TiledSelfEnsembleResult(mean, std, samples, tiles, codes, plan.origins_y, plan.origins_x, seed)
         maps = tile_blend_unview_quantiles(tiles, noisy_img.shape[2], noisy_img.shape[3], plan.overlap, codes, levels)
@@ -1396,11 +400,8 @@ class DiffusionDenoiser:
             raise ValueError("clean must be a tensor of the noisy images' shape, on their device")
         if clean.dtype != torch.float32:
             raise TypeError(f"clean must be float32 (got {clean.dtype})")
-        if tile is None:
-            result = self.denoise_ensemble(noisy, inference_steps, members, seed, sample_offset, member_offset, max_batch, return_samples=True)
-        else:
-            result = self.denoise_tiled_ensemble(noisy, inference_steps, members, tile, overlap, max_batch, seed, sample_offset, member_offset,
-                                                 return_samples=True)
+        result = self._ensemble_with_samples(noisy, tile, overlap, inference_steps=inference_steps, members=members, seed=seed,
+                                             sample_offset=sample_offset, member_offset=member_offset, max_batch=max_batch)
         return result, ensemble_scores(result.samples, clean, levels, return_map)
 
     @torch.no_grad()
@@ -1417,11 +418,8 @@ class DiffusionDenoiser:
             raise ValueError("ensemble_nps needs members >= 2: one member has no spread around its own mean")
         check_nps_args(roi, step, detrend)
         nps_window(window, roi)
-        if tile is None:
-            result = self.denoise_ensemble(noisy, inference_steps, members, seed, sample_offset, member_offset, max_batch, return_samples=True)
-        else:
-            result = self.denoise_tiled_ensemble(noisy, inference_steps, members, tile, overlap, max_batch, seed, sample_offset, member_offset,
-                                                 return_samples=True)
+        result = self._ensemble_with_samples(noisy, tile, overlap, inference_steps=inference_steps, members=members, seed=seed,
+                                             sample_offset=sample_offset, member_offset=member_offset, max_batch=max_batch)
         return result, noise_power_spectrum(result.samples, result.mean, roi, step, detrend, window, members / (members - 1), exclude_axes)
 
     # ------------------------------------------------------------------ the training objective as an evaluation
@@ -1447,7 +445,7 @@ class DiffusionDenoiser:
 
     def _objective(self, edge_weight) -> Tuple[bool, float]:
         """(clamp_eps, edge_weight) of the variant's training objective: DDIMModel.py:358,375 / cddpmModels.py:374."""
-        ddim = getattr(self.model, "variant", "ddim") != "cddpm"
+        ddim = not self._stochastic
         if edge_weight is None:
             return ddim, 0.2 if ddim else 0.0
         w = float(edge_weight)
@@ -1497,7 +495,7 @@ class DiffusionDenoiser:
             raise ValueError("clean must be a [B, C, H, W] tensor")
         steps = tuple(range(self.noise_steps)) if timesteps is None else tuple(_integer(v, "timesteps", self.noise_steps) for v in timesteps)
         max_batch = check_member(max_batch, "max_batch", low=1)
-        seed, sample_offset = check_seed(self._draw_seed() if seed is None else seed, sample_offset)
+        seed, sample_offset = self._seed(True, seed, sample_offset)
         clamp, weight = self._objective(edge_weight)
         B, T = clean.shape[0], len(steps)
         pairs = [(b, k) for k in range(T) for b in range(B)]
@@ -1537,12 +535,9 @@ class DiffusionDenoiser:
         if not isinstance(noisy_img, torch.Tensor) or noisy_img.dim() != 4 or len(counts) != noisy_img.shape[0]:
             raise ValueError(f"inference_steps must hold one step count per image ({len(counts)} for a batch of "
                              f"{noisy_img.shape[0] if isinstance(noisy_img, torch.Tensor) and noisy_img.dim() else '?'})")
-        stochastic = getattr(self.model, "variant", "ddim") == "cddpm"
-        if stochastic if rule is None else rule.draws:
-            seed, sample_offset = check_seed(self._draw_seed() if seed is None else seed, sample_offset)
-        else:
-            seed = None
-            _, sample_offset = check_seed(0, sample_offset)
+        stochastic = self._stochastic
+        seed, sample_offset = self._seed(self._draws(rule), seed, sample_offset)      # (DDIM ignores ``seed``: nothing to refuse)
+        _, sample_offset = check_seed(0, sample_offset)                               # (judged whether the call draws or not)
         self.model.eval()
         lists = [timestep_list(self.noise_steps, _integer(k, "inference_steps", 1 << 31)) for k in counts]
         n_rows = max((len(t) for t in lists), default=0)
