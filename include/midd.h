@@ -422,6 +422,64 @@ int mi_noise_power_spectrum(const float* a, const float* b, int B, int K, int C,
                             double* nps, double* radial, int64_t* radial_count, int64_t* rois_used, int64_t* rois_skipped,
                             void* workspace, size_t workspace_bytes, void* stream);
 
+/* CROSS SPECTRUM (no plan needed): at which spatial frequencies does the signal survive?  The NPS above is the spectrum of ONE
+ * field; resolution needs two: the Welch cross-spectrum S_xy of a truth x and an output y (or of two independent draws of an
+ * ensemble) beside their auto-spectra S_xx, S_yy.  From the radial averages follow, on the host, the signal transfer
+ * Re S_xy / S_xx (how much of x's amplitude at a frequency is in y: the MTF-like curve of a nonlinear, content-adaptive denoiser,
+ * for which an edge-phantom MTF is not defined) and the Fourier ring correlation Re S_xy / sqrt(S_xx S_yy).
+ * x device fp32 [B,Kx,C,H,W], y device fp32 [B,Ky,C,H,W] with Kx, Ky in {K, 1}, K = max(Kx, Ky).
+ * THE CROSS SPECTRUM (fixed; independent of the launch geometry, the vector width and the alignment path).  Everything not named
+ * here -- ROIs and their numbering, detrend, window and S_w, twiddles, storage order, the butterfly, chunks, radial bins -- is THE
+ * NOISE POWER SPECTRUM's, applied to x and to y each on its own.
+ *   fields       x and y as given: there is no subtraction.  A field with one realisation (Kx or Ky == 1 < K) is broadcast over the
+ *                K members.  A group g = b*C + c is a (b, c) pair; ROI n = (m*ny + iy)*nx + ix pairs member m of x (or its only one)
+ *                with member m of y at the same position.
+ *   skipped      an ROI is SKIPPED when x OR y holds a NaN or an Inf inside it; it is counted once in rois_skipped[g].
+ *   detrend, window   the NPS's operations on the ROI of x -> dx and, with its own sums and coefficients, on that of y -> dy.
+ *   transform    ONE complex transform per ROI of z = (dx, dy): dx is the real part, dy the imaginary part, stored at
+ *                [bitrev(y)][bitrev(x)].  The NPS pass over all R rows, then over ALL R columns (the row transforms of a complex
+ *                field are not Hermitian: there is no half-column shortcut).  Z[v][u] is the result in DFT order.
+ *   separation   per entry (v, u) of the half plane u <= R/2, in double: Z1 = Z[v][u], Z2 = Z[(R-v)%R][(R-u)%R], (x1, y1) and
+ *                (x2, y2) their fp32 components converted to double.  Every product of two of them is exact; every sum is rounded
+ *                on its own; no fused multiply-add; the factors 2, 1/2 and 1/4 are exact:
+ *                  n1 = x1*x1 + y1*y1        n2 = x2*x2 + y2*y2
+ *                  c  = x1*x2 - y1*y2        s  = x1*y2 + y1*x2                     (Z1 * Z2)
+ *                  Sxx = ((n1 + n2) + 2c) / 4        Syy = ((n1 + n2) - 2c) / 4
+ *                  Re Sxy = s / 2                    Im Sxy = (n1 - n2) / 4         (Sxy = X * conj Y)
+ *                (from X = (Z1 + conj Z2) / 2 and Y = (Z1 - conj Z2) / (2i), the transforms of the two real fields).
+ *   accumulation four double sums per group and entry, each in the NPS's ONE order (chunks of 16 ROIs; a chunk's used ROIs in order of
+ *                n from 0; the chunk sums one by one from 0 in chunk order; no atomics).
+ *   result       plane[q][g][v][u] = sum / ((double)rois_used[g] * S_w), q = 0 Sxx, 1 Syy, 2 Re Sxy, 3 Im Sxy, DFT order.  For
+ *                0 < u < R/2 the entry ((R-v)%R, R-u) is the copy of (v, u) for Sxx, Syy and Re Sxy and its negation for Im Sxy
+ *                (Sxy(-f) = conj Sxy(f)).  A group with no used ROI is the quiet NaN 0x7FF8000000000000 in every plane and radial
+ *                entry.
+ *   radial       the NPS's bins and order, MI_NPS_EXCLUDE_AXES included, over each of the four planes: radial[q][g][r].
+ * Accuracy: the fp32 transform's rounding error is relative to the COMBINED energy of the two fields, sum (Sxx + Syy): against
+ * float64 arithmetic on the same detrended, windowed ROIs, sum |S - S*| / sum (Sxx* + Syy*) <= 2 rho + rho^2 for each of the four
+ * quantities (rho: Higham, Theorem 24.2, as for the NPS; 8.3e-6, 9.9e-6, 1.15e-5 for R = 32, 64, 128; measured: about 1e-7).  A
+ * field much weaker than its partner therefore inherits the partner's rounding error, about 1e-7 of the STRONGER amplitude: scale
+ * such a pair to comparable size first (the curves are ratios).
+ * Arguments
+ *   window       HOST fp32 [roi] or NULL, as for the NPS
+ *   planes       device double [4][B*C][roi][roi];  radial  device double [4][B*C][roi/2+1];  radial_count  device int64 [roi/2+1];
+ *   rois_used, rois_skipped  device int64 [B*C];  all 8-byte aligned
+ *   workspace    mi_cross_spectrum_workspace_bytes: the chunk sums, double [B*C][chunks][4][roi*(roi/2+1)], and the chunks' used
+ *                counts, int64 [B*C][chunks]; 8-byte aligned; the query answers 0 on sizes the call refuses
+ * An ROI is read as 16-byte words when W is a multiple of 4 and its first element is 16-byte aligned (judged for x and for y on their
+ * own) and element by element otherwise: the same bits.  x and y may overlap each other (y == x is the auto-spectrum twice).
+ * Six launches on `stream` (the ROIs; the chunk sums, division and mirror; the radial bins of each plane); allocates nothing;
+ * asynchronous.
+ * MI_EINVAL before anything is read, the rule named in mi_last_error, judged in this order: Kx or Ky < 1; Kx != Ky with neither
+ * equal to 1; then, with K = max(Kx, Ky), mi_noise_power_spectrum's rules from "roi outside {32, 64, 128}" to "unknown flags"; a null
+ * x, y, planes, radial, radial_count, rois_used, rois_skipped or workspace; an output or the workspace not 8-byte aligned, x or y
+ * not 4-byte aligned; workspace_bytes below the query's answer; any output (workspace included) overlapping an input or another
+ * output; a window entry that is not finite. */
+size_t mi_cross_spectrum_workspace_bytes(int B, int Kx, int Ky, int C, int H, int W, int roi, int step);
+int mi_cross_spectrum(const float* x, const float* y, int B, int Kx, int Ky, int C, int H, int W, int roi, int step, int detrend,
+                      const float* window, int flags,
+                      double* planes, double* radial, int64_t* radial_count, int64_t* rois_used, int64_t* rois_skipped,
+                      void* workspace, size_t workspace_bytes, void* stream);
+
 /* TILED DENOISING: images of any size >= the tile, at their own resolution, as overlapping network-sized tiles (the reference
  * resizes every image to the training size first, Backend/run.py denoise_image_diffusion(..., img_size); nothing there tiles).
  * THE GEOMETRY (fixed), per axis with image length L, tile T, minimum overlap O, T <= L, 0 <= O <= T/2:

@@ -14,6 +14,7 @@ img_size -> sampler -> uint8 -> bicubic resize back -> PNG, with the reference's
                            [--bit-depth 8|16 [--window P_LO,P_HI | --window-levels LO,HI]]
                            [--clean clean.png [--loss-out loss.json]]
                            [--nps-out nps.json [--nps-roi 32|64|128] [--nps-step S]]
+                           [--fidelity-out fidelity.json [--fidelity-roi 32|64|128] [--fidelity-step S]]
 
 Without a checkpoint (the trained weights are not distributed with the reference) the network is
 random-init, which exercises the path but does not denoise.  The reference helper has a latent
@@ -33,7 +34,7 @@ from PIL import Image
 from . import image16
 from .modules import UNetDiffusion
 from .sampler import (DEFAULT_SCORE_LEVELS, MAX_QUANTILE_MEMBERS, NPS_ROIS, DiffusionDenoiser, check_levels, check_nps_args, check_update,
-                      ensemble_scores, noise_power_spectrum)
+                      cross_spectrum, ensemble_scores, noise_power_spectrum)
 
 
 def denoise_image_diffusion(model_path: Optional[str], test_image_path: str, device_type: str = "cuda",
@@ -47,7 +48,8 @@ def denoise_image_diffusion(model_path: Optional[str], test_image_path: str, dev
                             window_levels: Optional[Sequence[int]] = None, views: Optional[str] = None,
                             members: Optional[int] = None, clean: Optional[str] = None, loss_out: Optional[str] = None,
                             truth: Optional[str] = None, scores_out: Optional[str] = None, nps_out: Optional[str] = None,
-                            nps_roi: Optional[int] = None, nps_step: Optional[int] = None) -> Image.Image:
+                            nps_roi: Optional[int] = None, nps_step: Optional[int] = None, fidelity_out: Optional[str] = None,
+                            fidelity_roi: Optional[int] = None, fidelity_step: Optional[int] = None) -> Image.Image:
     """compute (not a reference argument): arithmetic of the network, see UNetDiffusion -- None keeps the default.
     seed (not a reference argument; cddpm): the stochastic sampler's noise is drawn on the device from this seed, so the same
     call gives the same image again (DiffusionDenoiser.denoise); None: torch.randn, as the reference.
@@ -103,7 +105,31 @@ def denoise_image_diffusion(model_path: Optional[str], test_image_path: str, dev
     resolution (img_size, or with tile the image's own): always the method noise, input - output, which is flat if only noise was
     removed; with samples, or tile and members, K >= 2, also the ensemble's spread, member - mean scaled by K / (K - 1); with truth
     also the residual, output - truth.  Refused where the sampler's image is smaller than the ROI.  The sampler run and the returned
-    image are those of the call without nps_out."""
+    image are those of the call without nps_out.
+    fidelity_out, fidelity_roi, fidelity_step (not reference arguments; with samples, or with tile and members; on a GPU only): AT WHICH
+    FREQUENCIES THE SIGNAL SURVIVES.  fidelity_out is the path of a .json file that receives, per radial frequency, the signal transfer
+    and the Fourier ring correlation of Welch cross-spectra (sampler.cross_spectrum; plane detrend, Hann window, ROIs as for nps_out)
+    and the frequency at which the FRC falls below 1/7: with truth, of (truth, output) and of (truth, noisy input); with an even
+    K >= 2, between the draws 0, 2, .. and 1, 3, .., which needs no truth.  Refused with neither, and where the sampler's image is
+    smaller than the ROI.  The sampler run and the returned image are those of the call without fidelity_out."""
+    if (fidelity_roi is not None or fidelity_step is not None) and fidelity_out is None:
+        raise ValueError("--fidelity-roi and --fidelity-step need --fidelity-out PATH.json (the file that receives the curves)")
+    if fidelity_out is not None:
+        fidelity_roi, fidelity_step = check_nps_args(64 if fidelity_roi is None else fidelity_roi, fidelity_step, "plane")
+        n_draws = samples if samples is not None else (members if tile is not None else None)
+        if n_draws is None or (truth is None and (n_draws < 2 or n_draws % 2)):
+            raise ValueError("--fidelity-out needs --truth PATH beside --samples K or --tile N --members K (transfer and FRC against the "
+                             "truth), or an even K >= 2 of them (the FRC between the draws, which needs no truth)")
+        if torch.device(device_type).type != "cuda":
+            raise RuntimeError("--fidelity-out (cross-spectrum) runs only on a ROCm GPU: the kernel has no CPU fallback")
+        if tile is None and img_size < fidelity_roi:
+            raise ValueError(f"--fidelity-out: the sampler's image ({img_size}x{img_size}) is smaller than the ROI ({fidelity_roi}x{fidelity_roi}); "
+                             "use a smaller --fidelity-roi")
+        if tile is not None:      # the tiled run keeps the image's own size
+            with Image.open(test_image_path) as probe:
+                if min(probe.size) < fidelity_roi:
+                    raise ValueError(f"--fidelity-out: the image ({probe.size[1]}x{probe.size[0]}) is smaller than the ROI "
+                                     f"({fidelity_roi}x{fidelity_roi}); use a smaller --fidelity-roi")
     if (nps_roi is not None or nps_step is not None) and nps_out is None:
         raise ValueError("--nps-roi and --nps-step need --nps-out PATH.json (the file that receives the spectra)")
     if nps_out is not None:
@@ -247,7 +273,7 @@ def denoise_image_diffusion(model_path: Optional[str], test_image_path: str, dev
             what = f"Self-ensemble of {len(res.views)} views {res.views}, tiled"
         elif members is not None:
             res = diffusion.denoise_tiled_ensemble(input_tensor, inference_steps=inference_steps, members=members, tile=tile, overlap=overlap,
-                                                   seed=seed, quantiles=quantiles, return_samples=truth is not None or nps_out is not None)
+                                                   seed=seed, quantiles=quantiles, return_samples=truth is not None or nps_out is not None or fidelity_out is not None)
             what = f"Ensemble of {members} samples, tiled"
         else:
             res = diffusion.denoise_tiled(input_tensor, inference_steps=inference_steps, tile=tile, overlap=overlap, seed=seed, **rule)
@@ -261,6 +287,8 @@ def denoise_image_diffusion(model_path: Optional[str], test_image_path: str, dev
         if nps_out is not None:
             write_nps(nps_out, nps_roi, nps_step, input_tensor, res.mean if tiled_ensemble else res.image,
                       res.samples if members is not None else None, truth, None, bit_depth, win, res.seed)
+        if fidelity_out is not None:
+            write_fidelity(fidelity_out, fidelity_roi, fidelity_step, input_tensor, res.mean, res.samples, truth, None, bit_depth, win, res.seed)
         if tiled_ensemble:      # the mean of values in [0, 1] is in [0, 1]: stored as the tiled image is; the maps stay float, at the image's size
             if std_out is not None:
                 np.save(std_out, res.std[0, 0].cpu().numpy())
@@ -312,7 +340,7 @@ def denoise_image_diffusion(model_path: Optional[str], test_image_path: str, dev
             np.save(quantiles_out, ens.quantiles.reshape(len(quantiles), img_size, img_size).cpu().numpy())
     elif samples is not None:
         ens = diffusion.denoise_ensemble(input_tensor, inference_steps=inference_steps, members=samples, seed=seed, quantiles=quantiles,
-                                         return_samples=truth is not None or nps_out is not None, **rule)
+                                         return_samples=truth is not None or nps_out is not None or fidelity_out is not None, **rule)
         denoised = ens.mean                               # a mean of values in [0, 1]: in [0, 1]
         print(f"Ensemble of {samples} samples, seed {ens.seed}")
         if truth is not None:
@@ -334,6 +362,9 @@ def denoise_image_diffusion(model_path: Optional[str], test_image_path: str, dev
     if nps_out is not None:
         write_nps(nps_out, nps_roi, nps_step, input_tensor, denoised.reshape(1, 1, img_size, img_size),
                   ens.samples if samples is not None else None, truth, img_size, bit_depth, win, ens.seed if samples is not None else seed)
+    if fidelity_out is not None:
+        write_fidelity(fidelity_out, fidelity_roi, fidelity_step, input_tensor, denoised.reshape(1, 1, img_size, img_size), ens.samples, truth,
+                       img_size, bit_depth, win, ens.seed)
 
     if win is not None:
         plane = denoised.reshape(img_size, img_size).float()
@@ -441,6 +472,43 @@ def write_nps(nps_out: str, roi: int, step: int, noisy: torch.Tensor, output: to
     return result
 
 
+def write_fidelity(fidelity_out: str, roi: int, step: int, noisy: torch.Tensor, output: torch.Tensor, samples: torch.Tensor,
+                   truth_path: Optional[str], img_size: Optional[int], bit_depth: int, win, seed) -> dict:
+    """--fidelity-out: at which spatial frequencies the signal survives the run (sampler.cross_spectrum), printed in short and written
+    as JSON.  noisy and output are [1, 1, H, W], samples [1, K, 1, H, W].  With a truth (loaded by the recipe of the noisy image): the
+    transfer, the FRC and the resolution of (truth, output) and of (truth, noisy).  With an even K >= 2: the FRC between the draws
+    samples[:, 0::2] and samples[:, 1::2], which needs no truth."""
+    import json
+
+    def entry(sp, **more):
+        return dict(transfer=sp.transfer()[0, 0].tolist(), frc=sp.frc()[0, 0].tolist(), resolution=float(sp.resolution()[0, 0]),
+                    rois_used=int(sp.rois_used[0, 0]), rois_skipped=int(sp.rois_skipped[0, 0]), **more)
+
+    out = output.float().contiguous()
+    K = int(samples.shape[1])
+    result = {"roi": roi, "step": step, "detrend": "plane", "window": "hann", "height": int(out.shape[2]), "width": int(out.shape[3]),
+              "seed": seed, "freqs": [r / roi for r in range(roi // 2 + 1)]}
+    if truth_path is not None:
+        truth = load_counterpart(truth_path, out.device, img_size, bit_depth, win).float()
+        if tuple(truth.shape) != tuple(out.shape):
+            raise ValueError(f"--truth is {truth.shape[2]}x{truth.shape[3]}, the output {out.shape[2]}x{out.shape[3]}: the truth image must have "
+                             "the size of --image")
+        result["truth_output"] = entry(cross_spectrum(truth, out, roi, step))
+        result["truth_noisy"] = entry(cross_spectrum(truth, noisy.float(), roi, step))
+    if K >= 2 and K % 2 == 0:
+        result["draws"] = entry(cross_spectrum(samples[:, 0::2], samples[:, 1::2], roi, step), members=K)
+    print(f"Spectral fidelity ({roi} x {roi} ROIs at step {step}, plane detrend, Hann window; cycles per pixel):")
+    for name in ("truth_output", "truth_noisy", "draws"):
+        if name in result:
+            e = result[name]
+            print(f"  {name}: {e['rois_used']} ROIs, FRC at f = 0.25: {e['frc'][roi // 4]:.3f}, transfer at f = 0.25: {e['transfer'][roi // 4]:.3f}, "
+                  f"FRC below 1/7 at f = {e['resolution']:.4f}")
+    with open(fidelity_out, "w") as f:
+        json.dump(result, f, indent=1)
+    print(f"Spectral fidelity saved: {fidelity_out}")
+    return result
+
+
 def evaluate(diffusion: DiffusionDenoiser, clean_path: str, noisy: torch.Tensor, denoised: torch.Tensor, img_size: int, bit_depth: int,
              win, seed: Optional[int], loss_out: Optional[str]) -> dict:
     """--clean: the loss profile of the (clean, noisy) pair over all timesteps and the PSNR / SSIM of `denoised` against the clean
@@ -530,9 +598,29 @@ def main(argv=None) -> None:
                          "the residual output - truth")
     ap.add_argument("--nps-roi", type=int, default=None, metavar="R", help="with --nps-out: the ROI size, 32, 64 (default) or 128")
     ap.add_argument("--nps-step", type=int, default=None, metavar="S", help="with --nps-out: the ROI step (default R / 2)")
+    ap.add_argument("--fidelity-out", default=None, metavar="PATH.json",
+                    help="write the signal transfer and the Fourier ring correlation per radial frequency as JSON: with --truth (beside "
+                         "--samples K or --tile N --members K) of (truth, output) and (truth, noisy input); with an even K also between the "
+                         "draws, which needs no truth")
+    ap.add_argument("--fidelity-roi", type=int, default=None, metavar="R", help="with --fidelity-out: the ROI size, 32, 64 (default) or 128")
+    ap.add_argument("--fidelity-step", type=int, default=None, metavar="S", help="with --fidelity-out: the ROI step (default R / 2)")
     args = ap.parse_args(argv)
     if (args.nps_roi is not None or args.nps_step is not None) and args.nps_out is None:
         ap.error("--nps-roi and --nps-step need --nps-out PATH.json")
+    if (args.fidelity_roi is not None or args.fidelity_step is not None) and args.fidelity_out is None:
+        ap.error("--fidelity-roi and --fidelity-step need --fidelity-out PATH.json")
+    if args.fidelity_roi is not None and args.fidelity_roi not in NPS_ROIS:
+        ap.error(f"--fidelity-roi needs one of {NPS_ROIS}")
+    if args.fidelity_step is not None and args.fidelity_step < 1:
+        ap.error("--fidelity-step needs S >= 1")
+    if args.fidelity_out is not None:
+        n_draws = args.samples if args.samples is not None else (args.members if args.tile is not None else None)
+        if n_draws is None or (args.truth is None and (n_draws < 2 or n_draws % 2)):
+            ap.error("--fidelity-out needs --truth PATH beside --samples K or --tile N --members K, or an even K >= 2 of them (the FRC between "
+                     "the draws needs no truth)")
+        if args.tile is None and args.img_size < (args.fidelity_roi or 64):
+            ap.error(f"--fidelity-out: the sampler's image ({args.img_size}x{args.img_size}) is smaller than the ROI ({args.fidelity_roi or 64}); "
+                     "use a smaller --fidelity-roi")
     if args.nps_roi is not None and args.nps_roi not in NPS_ROIS:
         ap.error(f"--nps-roi needs one of {NPS_ROIS}")
     if args.nps_step is not None and args.nps_step < 1:
@@ -620,7 +708,9 @@ def main(argv=None) -> None:
                                        **({} if args.members is None else {"members": args.members}),
                                        **({} if args.clean is None else {"clean": args.clean, "loss_out": args.loss_out}),
                                        **({} if args.truth is None else {"truth": args.truth, "scores_out": args.scores_out}),
-                                       **({} if args.nps_out is None else {"nps_out": args.nps_out, "nps_roi": args.nps_roi, "nps_step": args.nps_step}))
+                                       **({} if args.nps_out is None else {"nps_out": args.nps_out, "nps_roi": args.nps_roi, "nps_step": args.nps_step}),
+                                       **({} if args.fidelity_out is None else {"fidelity_out": args.fidelity_out, "fidelity_roi": args.fidelity_roi,
+                                                                                "fidelity_step": args.fidelity_step}))
     restored.save(args.out, quality=95)
     print(f"\nResult saved: {args.out}")
 

@@ -193,6 +193,52 @@ extern "C" int mi_noise_power_spectrum(const float* a, const float* b, int B, in
                                reinterpret_cast<long long*>(rois_skipped), workspace, (hipStream_t)stream), "noise_power_spectrum");
 }
 
+// The cross-spectrum of two fields (cross_spectrum.hip; include/midd.h: THE CROSS SPECTRUM).  The member rule, then the shape rules of
+// the noise power spectrum with K = max(Kx, Ky), then the rest in the documented order
+static int check_xs_shape(int B, int Kx, int Ky, int C, int H, int W, int roi, int step) {
+    if (Kx < 1 || Ky < 1) return fail(MI_EINVAL, "Kx %d, Ky %d: each field has at least one realisation", Kx, Ky);
+    if (Kx != Ky && Kx != 1 && Ky != 1)
+        return fail(MI_EINVAL, "Kx %d, Ky %d: the fields have K = max(Kx, Ky) members each, or one that is broadcast (limit: Kx, Ky in {K, 1})", Kx, Ky);
+    return check_nps_shape(B, Kx > Ky ? Kx : Ky, C, H, W, roi, step);
+}
+
+extern "C" size_t mi_cross_spectrum_workspace_bytes(int B, int Kx, int Ky, int C, int H, int W, int roi, int step) {
+    if (check_xs_shape(B, Kx, Ky, C, H, W, roi, step)) return 0;
+    return xs_workspace_bytes(B * C, Kx > Ky ? Kx : Ky, H, W, roi, step);
+}
+
+extern "C" int mi_cross_spectrum(const float* x, const float* y, int B, int Kx, int Ky, int C, int H, int W, int roi, int step, int detrend,
+                                 const float* window, int flags, double* planes, double* radial, int64_t* radial_count,
+                                 int64_t* rois_used, int64_t* rois_skipped, void* workspace, size_t workspace_bytes, void* stream) {
+    if (int rc = check_xs_shape(B, Kx, Ky, C, H, W, roi, step)) return rc;
+    if (detrend < MI_NPS_DETREND_NONE || detrend > MI_NPS_DETREND_PLANE)
+        return fail(MI_EINVAL, "detrend %d outside {0 none, 1 mean, 2 plane}", detrend);
+    if (flags & ~MI_NPS_EXCLUDE_AXES) return fail(MI_EINVAL, "flags 0x%x: unknown bits (known: MI_NPS_EXCLUDE_AXES = 1)", (unsigned)flags);
+    if (!x || !y || !planes || !radial || !radial_count || !rois_used || !rois_skipped || !workspace) return fail(MI_EINVAL, "null argument");
+    for (const void* p : {(const void*)planes, (const void*)radial, (const void*)radial_count, (const void*)rois_used, (const void*)rois_skipped, (const void*)workspace})
+        if (reinterpret_cast<uintptr_t>(p) & 7) return fail(MI_EINVAL, "planes, radial, radial_count, rois_used, rois_skipped and workspace must be 8-byte aligned");
+    for (const void* p : {(const void*)x, (const void*)y})
+        if (reinterpret_cast<uintptr_t>(p) & 3) return fail(MI_EINVAL, "x and y must be 4-byte aligned");
+    const int K = Kx > Ky ? Kx : Ky;
+    const size_t need = xs_workspace_bytes(B * C, K, H, W, roi, step);
+    if (workspace_bytes < need) return fail(MI_EINVAL, "workspace too small: need %zu bytes (mi_cross_spectrum_workspace_bytes), got %zu", need, workspace_bytes);
+    const size_t groups = (size_t)B * C, img = (size_t)H * W * sizeof(float), bins = (size_t)roi / 2 + 1;
+    // (x and y are both only read: they may overlap each other, or be the same field)
+    const Buf outs[6] = {{planes, 4 * groups * roi * roi * sizeof(double), "planes"}, {radial, 4 * groups * bins * sizeof(double), "radial"},
+                         {radial_count, bins * sizeof(int64_t), "radial_count"}, {rois_used, groups * sizeof(int64_t), "rois_used"},
+                         {rois_skipped, groups * sizeof(int64_t), "rois_skipped"}, {workspace, need, "workspace"}};
+    for (const Buf& in : {Buf{x, groups * Kx * img, "x"}, Buf{y, groups * Ky * img, "y"}}) {
+        const Buf buf[7] = {in, outs[0], outs[1], outs[2], outs[3], outs[4], outs[5]};
+        if (int rc = check_no_overlap(buf, 7, "x and y are read while every output and the workspace are written")) return rc;
+    }
+    if (window)
+        for (int i = 0; i < roi; ++i)
+            if (!(window[i] == window[i]) || window[i] - window[i] != 0.0f) return fail(MI_EINVAL, "window[%d] is not finite", i);
+    return launched(xs_launch(x, y, B, Kx, Ky, C, H, W, roi, step, detrend, window, (flags & MI_NPS_EXCLUDE_AXES) ? 1 : 0, planes, radial,
+                              reinterpret_cast<long long*>(radial_count), reinterpret_cast<long long*>(rois_used),
+                              reinterpret_cast<long long*>(rois_skipped), workspace, (hipStream_t)stream), "cross_spectrum");
+}
+
 // ---------------------------------------------------------------------------- the batched calls: virtual samples in passes
 // mi_denoise_ensemble, mi_denoise_tiled and mi_denoise_tiled_ensemble run `rounds` x V virtual samples of h x w each through the
 // sampler loop in passes of L.pass.  Each judges its own argument rules and its table of buffers (check_no_overlap), then shares

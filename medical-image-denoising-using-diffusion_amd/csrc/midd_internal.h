@@ -411,6 +411,15 @@ size_t nps_workspace_bytes(int groups, int K, int H, int W, int R, int S);
 hipError_t nps_launch(const float* a, const float* b, int B, int K, int C, int H, int W, int R, int S, int detrend, const float* window,
                       double scale, int exclude_axes, double* nps, double* radial, long long* radial_count, long long* rois_used,
                       long long* rois_skipped, void* ws, hipStream_t s);
+void nps_tables(int R, const float* window, NpsTables* tab, double* sw);
+
+// The Welch cross-spectrum of x [B][Kx][C][H][W] and y [B][Ky][C][H][W], Kx, Ky in {K, 1} (cross_spectrum.hip; include/midd.h: THE
+// CROSS SPECTRUM): ROIs, detrend, window and bins as above -> planes double [4][B*C][R][R] (Sxx, Syy, Re Sxy, Im Sxy), radial double
+// [4][B*C][R/2+1], radial_count, rois_used, rois_skipped as above; ws: xs_workspace_bytes (four chunk sums per half-plane entry)
+size_t xs_workspace_bytes(int groups, int K, int H, int W, int R, int S);
+hipError_t xs_launch(const float* x, const float* y, int B, int Kx, int Ky, int C, int H, int W, int R, int S, int detrend, const float* window,
+                     int exclude_axes, double* planes, double* radial, long long* radial_count, long long* rois_used, long long* rois_skipped,
+                     void* ws, hipStream_t s);
 
 // Geometric self-ensemble (include/midd.h: THE GEOMETRY).  A view list is 1 .. 8 distinct codes g = 4 t + 2 fy + fx in the caller's
 // order; it travels as kernel arguments.  Transposing codes (g >= 4) need H == W.

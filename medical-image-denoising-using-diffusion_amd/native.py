@@ -94,6 +94,9 @@ SYMBOLS = [
     ("mi_noise_power_spectrum_workspace_bytes", C.c_size_t, [C.c_int] * 7),
     ("mi_noise_power_spectrum", C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 8 + [C.POINTER(C.c_float), C.c_double, C.c_int] +
                                          [C.c_void_p] * 5 + [C.c_void_p, C.c_size_t, C.c_void_p]),
+    ("mi_cross_spectrum_workspace_bytes", C.c_size_t, [C.c_int] * 8),
+    ("mi_cross_spectrum", C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 9 + [C.POINTER(C.c_float), C.c_int] +
+                                   [C.c_void_p] * 5 + [C.c_void_p, C.c_size_t, C.c_void_p]),
     ("mi_tile_geometry", C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int]),
     ("mi_tile_extract", C.c_int, [C.c_void_p] + [C.c_int] * 10 + [C.c_void_p, C.c_void_p]),
     ("mi_tile_blend", C.c_int, [C.c_void_p] + [C.c_int] * 8 + [C.c_void_p, C.c_void_p]),

@@ -23,6 +23,7 @@ from .ensemble import (DEFAULT_SCORE_LEVELS, EnsembleQuantileResult, EnsembleRes
 from .loss import (DenoisingLoss, LossMaps, LossProfile, _loss_tensor, check_loss_source, loss_counter_args, loss_table_args,  # noqa: F401
                    loss_terms, noise_images)
 from .nps import NoisePowerSpectrum, noise_power_spectrum, nps_window  # noqa: F401
+from .spectral import CrossSpectrum, cross_spectrum  # noqa: F401
 from .rules import (MAX_QUANTILE_LEVELS, MAX_QUANTILE_MEMBERS, NPS_DETREND, NPS_ROIS, UPDATE_RULES, SamplerRule, _integer,  # noqa: F401
                     _levels_arg, _pair, check_levels, check_member, check_members, check_nps_args, check_quantile_members, check_rule,
                     check_score_levels, check_seed, check_update, ddim_coefficients, dpm_coefficients, refuse_update)
@@ -421,6 +422,55 @@ class DiffusionDenoiser:
         result = self._ensemble_with_samples(noisy, tile, overlap, inference_steps=inference_steps, members=members, seed=seed,
                                              sample_offset=sample_offset, member_offset=member_offset, max_batch=max_batch)
         return result, noise_power_spectrum(result.samples, result.mean, roi, step, detrend, window, members / (members - 1), exclude_axes)
+
+    @torch.no_grad()
+    def spectral_fidelity(self, clean: torch.Tensor, noisy: torch.Tensor, inference_steps: int = 25, members: Optional[int] = None,
+                          seed: Optional[int] = None, sample_offset: int = 0, member_offset: int = 0, max_batch: int = 16, tile=None,
+                          overlap=32, roi: int = 64, step: Optional[int] = None, detrend: str = "plane", window="hann",
+                          exclude_axes: bool = False, return_planes: bool = False):
+        """A run on ``noisy`` and, against ``clean``, at which spatial frequencies the signal survives it ->
+        ``(result, fidelity, baseline)``.  The run: ``denoise(noisy, inference_steps, seed=seed, sample_offset=sample_offset)``, with
+        ``tile`` ``denoise_tiled(..., tile=tile, overlap=overlap, max_batch=max_batch)``, with ``members`` ``denoise_ensemble(...,
+        return_samples=True)`` or ``denoise_tiled_ensemble(..., return_samples=True)``.  ``fidelity = cross_spectrum(clean, output,
+        roi, step, detrend, window, exclude_axes, return_planes)``, output being the image or, with ``members``, the samples
+        [B, K, C, H, W] beside the broadcast truth; ``baseline = cross_spectrum(clean, noisy, ...)`` with the same arguments: bit for
+        bit those compositions.  ``fidelity.transfer()`` and ``fidelity.frc()`` beside the baseline's give the per-frequency gain of
+        the run."""
+        check_nps_args(roi, step, detrend)
+        nps_window(window, roi)
+        if not isinstance(clean, torch.Tensor) or not isinstance(noisy, torch.Tensor) or clean.shape != noisy.shape or clean.device != noisy.device:
+            raise ValueError("clean must be a tensor of the noisy images' shape, on their device")
+        if clean.dtype != torch.float32:
+            raise TypeError(f"clean must be float32 (got {clean.dtype})")
+        if members is not None:
+            result = self._ensemble_with_samples(noisy, tile, overlap, inference_steps=inference_steps, members=members, seed=seed,
+                                                 sample_offset=sample_offset, member_offset=member_offset, max_batch=max_batch)
+            output = result.samples
+        elif tile is not None:
+            result = self.denoise_tiled(noisy, inference_steps, tile=tile, overlap=overlap, max_batch=max_batch, seed=seed, sample_offset=sample_offset)
+            output = result.image
+        else:
+            result = output = self.denoise(noisy, inference_steps, seed=seed, sample_offset=sample_offset)
+        spec = dict(roi=roi, step=step, detrend=detrend, window=window, exclude_axes=exclude_axes, return_planes=return_planes)
+        return result, cross_spectrum(clean, output, **spec), cross_spectrum(clean, noisy, **spec)
+
+    @torch.no_grad()
+    def ensemble_frc(self, noisy: torch.Tensor, inference_steps: int = 25, members: int = 8, seed: Optional[int] = None, sample_offset: int = 0,
+                     member_offset: int = 0, max_batch: int = 16, tile=None, overlap=32, roi: int = 64, step: Optional[int] = None,
+                     detrend: str = "plane", window="hann", exclude_axes: bool = False, return_planes: bool = False):
+        """An ensemble of ``noisy`` and the Fourier ring correlation between its independent draws, which needs no truth ->
+        ``(result, spectrum)``: ``denoise_ensemble(noisy, ..., return_samples=True)`` -- or, with ``tile``,
+        ``denoise_tiled_ensemble(noisy, ..., tile=tile, overlap=overlap, return_samples=True)`` -- followed by
+        ``cross_spectrum(result.samples[:, 0::2], result.samples[:, 1::2], roi, step, detrend, window, exclude_axes, return_planes)``,
+        bit for bit that composition: the draws are paired two by two.  ``spectrum.frc()`` says up to which frequency two draws
+        agree, ``spectrum.resolution()`` where it falls below 1/7.  cddpm only; ``members`` even and >= 2."""
+        if check_member(members, "members", low=1) < 2 or members % 2:
+            raise ValueError(f"ensemble_frc needs an even members >= 2 (got {members}): the draws are paired two by two")
+        check_nps_args(roi, step, detrend)
+        nps_window(window, roi)
+        result = self._ensemble_with_samples(noisy, tile, overlap, inference_steps=inference_steps, members=members, seed=seed,
+                                             sample_offset=sample_offset, member_offset=member_offset, max_batch=max_batch)
+        return result, cross_spectrum(result.samples[:, 0::2], result.samples[:, 1::2], roi, step, detrend, window, exclude_axes, return_planes)
 
     # ------------------------------------------------------------------ the training objective as an evaluation
     def sample_timesteps(self, n: int, generator: Optional[torch.Generator] = None) -> torch.Tensor:
