@@ -25,16 +25,142 @@ from __future__ import annotations
 
 import argparse
 import time
-from typing import Optional, Sequence
+from typing import NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 from PIL import Image
 
-from . import image16
+from . import image16, prepost
 from .modules import UNetDiffusion
+from .recipe import ImageRecipe
 from .sampler import (DEFAULT_SCORE_LEVELS, MAX_QUANTILE_MEMBERS, NPS_ROIS, DiffusionDenoiser, check_levels, check_nps_args, check_update,
                       cross_spectrum, ensemble_scores, noise_power_spectrum)
+
+
+class Options(NamedTuple):
+    """What check_options makes of the options it judged."""
+    rule: dict                                  # the update rule as keywords of the sampler calls; {} for the reference's
+    quantiles: Optional[Tuple[float, ...]]      # the checked quantile levels
+    recipe: ImageRecipe                         # bit_depth and the window
+    nps_roi: Optional[int]                      # ROI and step with their defaults (64, ROI / 2); as given without --nps-out
+    nps_step: Optional[int]
+    fidelity_roi: Optional[int]
+    fidelity_step: Optional[int]
+    tiled_ensemble: bool                        # --views or --members
+
+
+def check_options(device_type: str = "cuda", img_size: int = 512, variant: str = "cddpm", step_noise=None, seed=None, samples=None,
+                  std_out=None, tile=None, quantiles=None, quantiles_out=None, self_ensemble=None, update: str = "reference",
+                  eta: float = 0.0, clip_x0: bool = True, x0_out=None, bit_depth: int = 8, window=None, window_levels=None, views=None,
+                  members=None, clean=None, loss_out=None, truth=None, scores_out=None, nps_out=None, nps_roi=None, nps_step=None,
+                  fidelity_out=None, fidelity_roi=None, fidelity_step=None) -> Options:
+    """The rules of denoise_image_diffusion's options (its docstring says what each option is), all of them and nowhere else: the
+    function and main both call this.  Opens no file and touches no device; the two rules that compare an ROI with the image file
+    itself follow the call in denoise_image_diffusion.  Raises ValueError, and RuntimeError for what runs only on a GPU."""
+    on_gpu = torch.device(device_type).type == "cuda"
+
+    def spectrum(flag, kernel, receives, out, roi, step, missing=None):
+        """--nps-out and --fidelity-out: one rule list under two flag names."""
+        if (roi is not None or step is not None) and out is None:
+            raise ValueError(f"--{flag}-roi and --{flag}-step need --{flag}-out PATH.json (the file that receives the {receives})")
+        if out is None:
+            return roi, step
+        roi, step = check_nps_args(64 if roi is None else roi, step, "plane")
+        if missing is not None:
+            raise ValueError(missing)
+        if not on_gpu:
+            raise RuntimeError(f"--{flag}-out ({kernel}) runs only on a ROCm GPU: the kernel has no CPU fallback")
+        if tile is None and img_size < roi:
+            raise ValueError(f"--{flag}-out: the sampler's image ({img_size}x{img_size}) is smaller than the ROI ({roi}x{roi}); "
+                             f"use a smaller --{flag}-roi")
+        return roi, step
+
+    n_draws = samples if samples is not None else (members if tile is not None else None)
+    fidelity_roi, fidelity_step = spectrum(
+        "fidelity", "cross-spectrum", "curves", fidelity_out, fidelity_roi, fidelity_step,
+        None if n_draws is not None and (truth is not None or (n_draws >= 2 and n_draws % 2 == 0)) else
+        "--fidelity-out needs --truth PATH beside --samples K or --tile N --members K (transfer and FRC against the "
+        "truth), or an even K >= 2 of them (the FRC between the draws, which needs no truth)")
+    nps_roi, nps_step = spectrum("nps", "noise power spectrum", "spectra", nps_out, nps_roi, nps_step)
+    if loss_out is not None and clean is None:
+        raise ValueError("--loss-out needs --clean PATH (the evaluation's clean image)")
+    if scores_out is not None and truth is None:
+        raise ValueError("--scores-out needs --truth PATH (the image the ensemble is scored against)")
+    if truth is not None:
+        if samples is None and (tile is None or members is None):
+            raise ValueError("--truth scores an ensemble: it needs --samples K, or --tile N --members K")
+        if (samples if samples is not None else members) > MAX_QUANTILE_MEMBERS:
+            raise ValueError(f"--truth needs K <= {MAX_QUANTILE_MEMBERS} members: the scores kernel sorts a pixel's members in registers")
+        if not on_gpu:
+            raise RuntimeError("--truth (ensemble scores) runs only on a ROCm GPU: the scores kernel has no CPU fallback")
+    if clean is not None:
+        for flag, given in (("--tile", tile), ("--samples", samples), ("--views", views), ("--members", members), ("--self-ensemble", self_ensemble)):
+            if given is not None:
+                raise ValueError(f"--clean (evaluation) cannot be combined with {flag}: the loss is taken on the resized image, one sampler run")
+        if step_noise is not None or x0_out is not None:
+            raise ValueError("--clean (evaluation) cannot be combined with a step_noise tensor or --x0-out")
+        if not on_gpu:      # (before the sampler run, not after it)
+            raise RuntimeError("--clean (evaluation) runs only on a ROCm GPU: the loss kernels have no CPU fallback")
+    bit_depth = image16.check_bit_depth(bit_depth)
+    if window is not None and window_levels is not None:
+        raise ValueError("--window and --window-levels cannot be combined: percentiles or absolute levels, not both")
+    if (window is not None or window_levels is not None) and bit_depth != 16:
+        raise ValueError("--window and --window-levels need --bit-depth 16 (the window acts on 16-bit files)")
+    recipe = ImageRecipe(bit_depth, window=window, window_levels=window_levels)
+    rule = {} if check_update(update, eta, clip_x0) is None else {"update": update, "eta": eta, "clip_x0": clip_x0}
+    if rule and self_ensemble is not None:
+        raise ValueError(f"--update {update} cannot be combined with --self-ensemble (the self-ensemble runs the reference's update only)")
+    if update == "dpmpp2m":
+        if seed is not None or samples is not None or step_noise is not None:
+            raise ValueError("--update dpmpp2m is deterministic: it takes no --seed, --samples or step_noise")
+        rule = {"update": update, "clip_x0": clip_x0}
+    if x0_out is not None and (update != "dpmpp2m" or tile is not None):
+        raise ValueError("--x0-out needs --update dpmpp2m and no --tile: the trajectory of predicted images is that rule's")
+    if self_ensemble is not None:
+        if samples is not None:
+            raise ValueError("--self-ensemble cannot be combined with --samples")
+        if tile is not None:
+            raise ValueError("--self-ensemble cannot be combined with --tile")
+        if step_noise is not None:
+            raise ValueError("--self-ensemble draws its noise from the seed: step_noise cannot be given as well")
+        if self_ensemble not in ("auto", "flips", "d4"):
+            raise ValueError(f"--self-ensemble takes auto, flips or d4 (got {self_ensemble!r})")
+    if (views is not None or members is not None) and tile is None:
+        raise ValueError("--views and --members are the ensembles of the tiled run: they need --tile N (without it: --self-ensemble, --samples)")
+    if views is not None and members is not None:
+        raise ValueError("--views and --members cannot be combined: flip / rotate views or seeded draws, not both")
+    if views is not None and views not in ("auto", "flips", "d4"):
+        raise ValueError(f"--views takes auto, flips or d4 (got {views!r})")
+    if views is not None and update == "dpmpp2m":
+        raise ValueError("--update dpmpp2m cannot be combined with --views (the tiled self-ensemble runs the reference's update or ddim)")
+    if members is not None:
+        if rule:
+            raise ValueError(f"--update {update} cannot be combined with --members (the tiled ensemble runs the reference's update only)")
+        if variant != "cddpm":
+            raise ValueError("--members needs the stochastic (cddpm) variant: a deterministic sampler has no ensemble (use --views)")
+        if members < 1:
+            raise ValueError("--members needs K >= 1")
+    tiled_ensemble = views is not None or members is not None
+    if tile is not None and (samples is not None or step_noise is not None):
+        raise ValueError("--tile cannot be combined with --samples or a step_noise tensor")
+    if samples is not None and variant != "cddpm" and not (rule and eta > 0):
+        raise ValueError("--samples needs the stochastic (cddpm) variant: a deterministic sampler has no ensemble")
+    if std_out is not None and members is not None and members < 2:
+        raise ValueError("--std-out needs --members K with K >= 2")
+    if std_out is not None and self_ensemble is None and not tiled_ensemble and (samples is None or samples < 2):
+        raise ValueError("--std-out needs --samples K with K >= 2")
+    if (quantiles is None) != (quantiles_out is None):
+        raise ValueError("--quantiles and --quantiles-out come together")
+    if quantiles is not None:
+        if members is not None and members > MAX_QUANTILE_MEMBERS:
+            raise ValueError(f"--quantiles needs --members K with K <= {MAX_QUANTILE_MEMBERS}")
+        if self_ensemble is None and not tiled_ensemble and (samples is None or samples > MAX_QUANTILE_MEMBERS):
+            raise ValueError(f"--quantiles needs --samples K with K <= {MAX_QUANTILE_MEMBERS}")
+        quantiles = check_levels(quantiles)
+    if samples is not None and step_noise is not None:
+        raise ValueError("samples draws its noise from the seed: step_noise cannot be given as well")
+    return Options(rule, quantiles, recipe, nps_roi, nps_step, fidelity_roi, fidelity_step, tiled_ensemble)
 
 
 def denoise_image_diffusion(model_path: Optional[str], test_image_path: str, device_type: str = "cuda",
@@ -112,118 +238,20 @@ def denoise_image_diffusion(model_path: Optional[str], test_image_path: str, dev
     and the frequency at which the FRC falls below 1/7: with truth, of (truth, output) and of (truth, noisy input); with an even
     K >= 2, between the draws 0, 2, .. and 1, 3, .., which needs no truth.  Refused with neither, and where the sampler's image is
     smaller than the ROI.  The sampler run and the returned image are those of the call without fidelity_out."""
-    if (fidelity_roi is not None or fidelity_step is not None) and fidelity_out is None:
-        raise ValueError("--fidelity-roi and --fidelity-step need --fidelity-out PATH.json (the file that receives the curves)")
-    if fidelity_out is not None:
-        fidelity_roi, fidelity_step = check_nps_args(64 if fidelity_roi is None else fidelity_roi, fidelity_step, "plane")
-        n_draws = samples if samples is not None else (members if tile is not None else None)
-        if n_draws is None or (truth is None and (n_draws < 2 or n_draws % 2)):
-            raise ValueError("--fidelity-out needs --truth PATH beside --samples K or --tile N --members K (transfer and FRC against the "
-                             "truth), or an even K >= 2 of them (the FRC between the draws, which needs no truth)")
-        if torch.device(device_type).type != "cuda":
-            raise RuntimeError("--fidelity-out (cross-spectrum) runs only on a ROCm GPU: the kernel has no CPU fallback")
-        if tile is None and img_size < fidelity_roi:
-            raise ValueError(f"--fidelity-out: the sampler's image ({img_size}x{img_size}) is smaller than the ROI ({fidelity_roi}x{fidelity_roi}); "
-                             "use a smaller --fidelity-roi")
-        if tile is not None:      # the tiled run keeps the image's own size
+    opt = check_options(device_type=device_type, img_size=img_size, variant=variant, step_noise=step_noise, seed=seed, samples=samples,
+                        std_out=std_out, tile=tile, quantiles=quantiles, quantiles_out=quantiles_out, self_ensemble=self_ensemble,
+                        update=update, eta=eta, clip_x0=clip_x0, x0_out=x0_out, bit_depth=bit_depth, window=window,
+                        window_levels=window_levels, views=views, members=members, clean=clean, loss_out=loss_out, truth=truth,
+                        scores_out=scores_out, nps_out=nps_out, nps_roi=nps_roi, nps_step=nps_step, fidelity_out=fidelity_out,
+                        fidelity_roi=fidelity_roi, fidelity_step=fidelity_step)
+    rule, quantiles, recipe, tiled_ensemble = opt.rule, opt.quantiles, opt.recipe, opt.tiled_ensemble
+    nps_roi, nps_step, fidelity_roi, fidelity_step = opt.nps_roi, opt.nps_step, opt.fidelity_roi, opt.fidelity_step
+    for flag, out, roi in (("fidelity", fidelity_out, fidelity_roi), ("nps", nps_out, nps_roi)):
+        if out is not None and tile is not None:      # the tiled run keeps the image's own size
             with Image.open(test_image_path) as probe:
-                if min(probe.size) < fidelity_roi:
-                    raise ValueError(f"--fidelity-out: the image ({probe.size[1]}x{probe.size[0]}) is smaller than the ROI "
-                                     f"({fidelity_roi}x{fidelity_roi}); use a smaller --fidelity-roi")
-    if (nps_roi is not None or nps_step is not None) and nps_out is None:
-        raise ValueError("--nps-roi and --nps-step need --nps-out PATH.json (the file that receives the spectra)")
-    if nps_out is not None:
-        nps_roi, nps_step = check_nps_args(64 if nps_roi is None else nps_roi, nps_step, "plane")
-        if torch.device(device_type).type != "cuda":
-            raise RuntimeError("--nps-out (noise power spectrum) runs only on a ROCm GPU: the kernel has no CPU fallback")
-        if tile is None and img_size < nps_roi:
-            raise ValueError(f"--nps-out: the sampler's image ({img_size}x{img_size}) is smaller than the ROI ({nps_roi}x{nps_roi}); "
-                             "use a smaller --nps-roi")
-        if tile is not None:      # the tiled run keeps the image's own size
-            with Image.open(test_image_path) as probe:
-                if min(probe.size) < nps_roi:
-                    raise ValueError(f"--nps-out: the image ({probe.size[1]}x{probe.size[0]}) is smaller than the ROI ({nps_roi}x{nps_roi}); "
-                                     "use a smaller --nps-roi")
-    if loss_out is not None and clean is None:
-        raise ValueError("--loss-out needs --clean PATH (the evaluation's clean image)")
-    if scores_out is not None and truth is None:
-        raise ValueError("--scores-out needs --truth PATH (the image the ensemble is scored against)")
-    if truth is not None:
-        if samples is None and (tile is None or members is None):
-            raise ValueError("--truth scores an ensemble: it needs --samples K, or --tile N --members K")
-        if (samples if samples is not None else members) > MAX_QUANTILE_MEMBERS:
-            raise ValueError(f"--truth needs K <= {MAX_QUANTILE_MEMBERS} members: the scores kernel sorts a pixel's members in registers")
-        if torch.device(device_type).type != "cuda":
-            raise RuntimeError("--truth (ensemble scores) runs only on a ROCm GPU: the scores kernel has no CPU fallback")
-    if clean is not None:
-        for flag, given in (("--tile", tile), ("--samples", samples), ("--views", views), ("--members", members), ("--self-ensemble", self_ensemble)):
-            if given is not None:
-                raise ValueError(f"--clean (evaluation) cannot be combined with {flag}: the loss is taken on the resized image, one sampler run")
-        if step_noise is not None or x0_out is not None:
-            raise ValueError("--clean (evaluation) cannot be combined with a step_noise tensor or --x0-out")
-        if torch.device(device_type).type != "cuda":      # (before the sampler run, not after it)
-            raise RuntimeError("--clean (evaluation) runs only on a ROCm GPU: the loss kernels have no CPU fallback")
-    bit_depth = image16.check_bit_depth(bit_depth)
-    if window is not None and window_levels is not None:
-        raise ValueError("--window and --window-levels cannot be combined: percentiles or absolute levels, not both")
-    if (window is not None or window_levels is not None) and bit_depth != 16:
-        raise ValueError("--window and --window-levels need --bit-depth 16 (the window acts on 16-bit files)")
-    if window is not None:
-        window = image16.check_percentiles(window)
-    if window_levels is not None:
-        window_levels = image16.check_levels(window_levels)
-    rule = {} if check_update(update, eta, clip_x0) is None else {"update": update, "eta": eta, "clip_x0": clip_x0}
-    if rule and self_ensemble is not None:
-        raise ValueError(f"--update {update} cannot be combined with --self-ensemble (the self-ensemble runs the reference's update only)")
-    if update == "dpmpp2m":
-        if seed is not None or samples is not None or step_noise is not None:
-            raise ValueError("--update dpmpp2m is deterministic: it takes no --seed, --samples or step_noise")
-        rule = {"update": update, "clip_x0": clip_x0}
-    if x0_out is not None and (update != "dpmpp2m" or tile is not None):
-        raise ValueError("--x0-out needs --update dpmpp2m and no --tile: the trajectory of predicted images is that rule's")
-    if self_ensemble is not None:
-        if samples is not None:
-            raise ValueError("--self-ensemble cannot be combined with --samples")
-        if tile is not None:
-            raise ValueError("--self-ensemble cannot be combined with --tile")
-        if step_noise is not None:
-            raise ValueError("--self-ensemble draws its noise from the seed: step_noise cannot be given as well")
-        if self_ensemble not in ("auto", "flips", "d4"):
-            raise ValueError(f"--self-ensemble takes auto, flips or d4 (got {self_ensemble!r})")
-    if (views is not None or members is not None) and tile is None:
-        raise ValueError("--views and --members are the ensembles of the tiled run: they need --tile N (without it: --self-ensemble, --samples)")
-    if views is not None and members is not None:
-        raise ValueError("--views and --members cannot be combined: flip / rotate views or seeded draws, not both")
-    if views is not None and views not in ("auto", "flips", "d4"):
-        raise ValueError(f"--views takes auto, flips or d4 (got {views!r})")
-    if views is not None and update == "dpmpp2m":
-        raise ValueError("--update dpmpp2m cannot be combined with --views (the tiled self-ensemble runs the reference's update or ddim)")
-    if members is not None:
-        if rule:
-            raise ValueError(f"--update {update} cannot be combined with --members (the tiled ensemble runs the reference's update only)")
-        if variant != "cddpm":
-            raise ValueError("--members needs the stochastic (cddpm) variant: a deterministic sampler has no ensemble (use --views)")
-        if members < 1:
-            raise ValueError("--members needs K >= 1")
-    tiled_ensemble = views is not None or members is not None
-    if tile is not None and (samples is not None or step_noise is not None):
-        raise ValueError("--tile cannot be combined with --samples or a step_noise tensor")
-    if samples is not None and variant != "cddpm" and not (rule and eta > 0):
-        raise ValueError("--samples needs the stochastic (cddpm) variant: a deterministic sampler has no ensemble")
-    if std_out is not None and members is not None and members < 2:
-        raise ValueError("--std-out needs --members K with K >= 2")
-    if std_out is not None and self_ensemble is None and not tiled_ensemble and (samples is None or samples < 2):
-        raise ValueError("--std-out needs --samples K with K >= 2")
-    if (quantiles is None) != (quantiles_out is None):
-        raise ValueError("--quantiles and --quantiles-out come together")
-    if quantiles is not None:
-        if members is not None and members > MAX_QUANTILE_MEMBERS:
-            raise ValueError(f"--quantiles needs --members K with K <= {MAX_QUANTILE_MEMBERS}")
-        if self_ensemble is None and not tiled_ensemble and (samples is None or samples > MAX_QUANTILE_MEMBERS):
-            raise ValueError(f"--quantiles needs --samples K with K <= {MAX_QUANTILE_MEMBERS}")
-        quantiles = check_levels(quantiles)
-    if samples is not None and step_noise is not None:
-        raise ValueError("samples draws its noise from the seed: step_noise cannot be given as well")
+                if min(probe.size) < roi:
+                    raise ValueError(f"--{flag}-out: the image ({probe.size[1]}x{probe.size[0]}) is smaller than the ROI ({roi}x{roi}); "
+                                     f"use a smaller --{flag}-roi")
     device = torch.device(device_type)
     model = UNetDiffusion(in_channels=1, model_channels=48, channel_mult=(1, 2, 3, 4), num_res_blocks=2,
                           attention_resolutions=(3,), dropout=0.0, time_emb_dim=192, variant=variant, compute=compute)
@@ -236,35 +264,24 @@ def denoise_image_diffusion(model_path: Optional[str], test_image_path: str, dev
     print(f"Loaded model - PSNR: {checkpoint.get('best_psnr', 'N/A')} dB | SSIM: {checkpoint.get('best_ssim', 'N/A')}")
 
     img = Image.open(test_image_path)
-    raw16 = image16.decode16(img) if bit_depth == 16 else None          # uint16 [H][W] (uint8 for a file that is not 16-bit)
-    img = img.convert("L") if raw16 is None else img
     on_gpu = device.type == "cuda"
-    win = None          # the window's levels: int32 [1,2] on the device (they stay there: no synchronisation), or (lo, hi) on the host
-    if window is not None or window_levels is not None:
-        raw16 = image16.need_u16(raw16, img.mode)
-        if on_gpu:
-            from . import prepost
-            dev_raw16 = torch.from_numpy(raw16).to(device)
-            win = (prepost.window_levels(dev_raw16, window) if window is not None
-                   else torch.tensor([list(window_levels)], dtype=torch.int32, device=device))
-        else:
-            win = image16.window_levels(raw16, window) if window is not None else window_levels
-            print(f"Window: grey levels {win[0]} .. {win[1]}")
+    size = None if tile is not None else img_size      # the sampler's resolution: img_size, or with tile the image's own (no resize)
+    input_tensor, source = recipe.load(img, None if size is None else (size, size), device)
+    win = source.levels       # the window's levels: int32 [1,2] on the device (they stay there: no synchronisation), or (lo, hi) on the host
+    if win is not None and not on_gpu:
+        print(f"Window: grey levels {win[0]} .. {win[1]}")
+
+    def restored(image: torch.Tensor) -> Image.Image:
+        if win is not None and on_gpu:
+            print("Window: grey levels {} .. {}".format(*win[0].tolist()))
+        return Image.fromarray(recipe.store(image, source))
+
+    keep = truth is not None or nps_out is not None or fidelity_out is not None      # the members are needed after the run
+    truth_img = None
     if tile is not None:
         if min(img.size) < tile:
             raise ValueError(f"the image is {img.size[1]}x{img.size[0]}: a side is shorter than the tile ({tile}); use a smaller "
                              "--tile, or leave it out so that the image is resized to img_size")
-        if raw16 is None:
-            input_tensor = torch.from_numpy(np.asarray(img, np.uint8).astype(np.float32) / 255.0)[None, None].to(device)   # ToTensor
-        elif win is not None:
-            input_tensor = (prepost.window_u16_to_float(dev_raw16, win)[None, None] if on_gpu
-                            else torch.from_numpy(image16.unit_float_window(raw16, win))[None, None].to(device))
-        elif on_gpu:
-            from . import prepost
-            dev_raw = torch.from_numpy(raw16).to(device)
-            input_tensor = (prepost.u16_to_unit_float if raw16.dtype == np.uint16 else prepost.to_unit_float)(dev_raw)[None, None]
-        else:
-            input_tensor = torch.from_numpy(image16.unit_float(raw16))[None, None].to(device)
         start_time = time.time()
         if views is not None:
             draws = variant == "cddpm" if not rule else eta > 0
@@ -273,7 +290,7 @@ def denoise_image_diffusion(model_path: Optional[str], test_image_path: str, dev
             what = f"Self-ensemble of {len(res.views)} views {res.views}, tiled"
         elif members is not None:
             res = diffusion.denoise_tiled_ensemble(input_tensor, inference_steps=inference_steps, members=members, tile=tile, overlap=overlap,
-                                                   seed=seed, quantiles=quantiles, return_samples=truth is not None or nps_out is not None or fidelity_out is not None)
+                                                   seed=seed, quantiles=quantiles, return_samples=keep)
             what = f"Ensemble of {members} samples, tiled"
         else:
             res = diffusion.denoise_tiled(input_tensor, inference_steps=inference_steps, tile=tile, overlap=overlap, seed=seed, **rule)
@@ -282,48 +299,20 @@ def denoise_image_diffusion(model_path: Optional[str], test_image_path: str, dev
             torch.cuda.synchronize(device)
         print(f"{what}: {len(res.origins_y)} x {len(res.origins_x)} tiles of {tile}" + (f", seed {res.seed}" if res.seed is not None else ""))
         print(f"Inference time: {time.time() - start_time:.2f} seconds")
+        image = res.mean if tiled_ensemble else res.image      # the mean of values in [0, 1] is in [0, 1]: stored as the tiled image is
         if truth is not None:
-            score(res.samples, truth, None, bit_depth, win, quantiles if quantiles is not None else DEFAULT_SCORE_LEVELS, res.seed, scores_out)
+            truth_img = load_truth(truth, res.samples, size, recipe, win)
+            score(res.samples, truth_img, quantiles if quantiles is not None else DEFAULT_SCORE_LEVELS, res.seed, scores_out)
         if nps_out is not None:
-            write_nps(nps_out, nps_roi, nps_step, input_tensor, res.mean if tiled_ensemble else res.image,
-                      res.samples if members is not None else None, truth, None, bit_depth, win, res.seed)
+            write_nps(nps_out, nps_roi, nps_step, input_tensor, image, res.samples if members is not None else None, truth_img, res.seed)
         if fidelity_out is not None:
-            write_fidelity(fidelity_out, fidelity_roi, fidelity_step, input_tensor, res.mean, res.samples, truth, None, bit_depth, win, res.seed)
-        if tiled_ensemble:      # the mean of values in [0, 1] is in [0, 1]: stored as the tiled image is; the maps stay float, at the image's size
+            write_fidelity(fidelity_out, fidelity_roi, fidelity_step, input_tensor, image, res.samples, truth_img, res.seed)
+        if tiled_ensemble:      # the maps stay float, at the image's size
             if std_out is not None:
                 np.save(std_out, res.std[0, 0].cpu().numpy())
             if quantiles is not None:
                 np.save(quantiles_out, res.quantiles[0, :, 0].cpu().numpy())
-            image = res.mean
-        else:
-            image = res.image
-        if win is not None:
-            if on_gpu:
-                print("Window: grey levels {} .. {}".format(*win[0].tolist()))
-                out16 = prepost.window_to_u16(image[0, 0].float(), win).cpu().numpy()
-            else:
-                out16 = image16.to_u16_window(image[0, 0].cpu().numpy(), win)
-            return image16.image_from_u16(out16)
-        if raw16 is not None:
-            out16 = prepost.to_u16(image[0, 0].float()).cpu().numpy() if on_gpu else image16.to_u16(image[0, 0].cpu().numpy())
-            return image16.image_from_u16(out16)
-        return Image.fromarray((image[0, 0].cpu().numpy() * 255).astype(np.uint8), mode="L")      # already clamped to [0, 1]
-    if win is not None and on_gpu:      # windowed load, float resize, clip: one fused call under the levels on the device
-        input_tensor = prepost.resize_bicubic_f32(dev_raw16, (img_size, img_size), clamp=True, levels=win)[None, None]
-    elif win is not None:
-        input_tensor = torch.from_numpy(image16.resize_f(image16.unit_float_window(raw16, win), (img_size, img_size)))[None, None].to(device)
-    elif raw16 is not None and on_gpu:    # 16-bit recipe on the device: typed load, float resize, clip (one fused call)
-        from . import prepost
-        input_tensor = prepost.resize_bicubic_f32(torch.from_numpy(raw16).to(device), (img_size, img_size), clamp=True)[None, None]
-    elif raw16 is not None:
-        input_tensor = torch.from_numpy(image16.resize_f(image16.unit_float(raw16), (img_size, img_size)))[None, None].to(device)
-    elif on_gpu:      # resize + ToTensor scaling on the device (prepost: bit-identical to the PIL / numpy recipe below)
-        from . import prepost
-        raw = torch.from_numpy(np.asarray(img, np.uint8).copy()).to(device)
-        input_tensor = prepost.to_unit_float(prepost.resize_bicubic_u8(raw, (img_size, img_size)))[None, None]
-    else:
-        resized = img.resize((img_size, img_size), Image.BICUBIC)       # transforms.Resize on a PIL image
-        input_tensor = torch.from_numpy(np.asarray(resized, np.uint8).astype(np.float32) / 255.0)[None, None].to(device)
+        return restored(image)
 
     start_time = time.time()
     kw = {"step_noise": step_noise} if step_noise is not None else {}
@@ -334,93 +323,59 @@ def denoise_image_diffusion(model_path: Optional[str], test_image_path: str, dev
                                               seed=seed if variant == "cddpm" else None, quantiles=quantiles)
         denoised = ens.mean                               # a mean of values in [0, 1]: in [0, 1]
         print(f"Self-ensemble of {len(ens.views)} views {ens.views}" + (f", seed {ens.seed}" if ens.seed is not None else ""))
-        if std_out is not None:
-            np.save(std_out, ens.std.reshape(img_size, img_size).cpu().numpy())
-        if quantiles is not None:
-            np.save(quantiles_out, ens.quantiles.reshape(len(quantiles), img_size, img_size).cpu().numpy())
     elif samples is not None:
         ens = diffusion.denoise_ensemble(input_tensor, inference_steps=inference_steps, members=samples, seed=seed, quantiles=quantiles,
-                                         return_samples=truth is not None or nps_out is not None or fidelity_out is not None, **rule)
+                                         return_samples=keep, **rule)
         denoised = ens.mean                               # a mean of values in [0, 1]: in [0, 1]
         print(f"Ensemble of {samples} samples, seed {ens.seed}")
         if truth is not None:
-            score(ens.samples, truth, img_size, bit_depth, win, quantiles if quantiles is not None else DEFAULT_SCORE_LEVELS, ens.seed, scores_out)
-        if std_out is not None:
-            np.save(std_out, ens.std.reshape(img_size, img_size).cpu().numpy())
-        if quantiles is not None:
-            np.save(quantiles_out, ens.quantiles.reshape(len(quantiles), img_size, img_size).cpu().numpy())
+            truth_img = load_truth(truth, ens.samples, size, recipe, win)
+            score(ens.samples, truth_img, quantiles if quantiles is not None else DEFAULT_SCORE_LEVELS, ens.seed, scores_out)
     elif x0_out is not None:
         denoised, traj = diffusion.denoise(input_tensor, inference_steps=inference_steps, return_x0=True, **rule)
         np.save(x0_out, traj.reshape(traj.shape[0], img_size, img_size).cpu().numpy())      # float32 [n_iters, H, W], model resolution
     else:
         denoised = diffusion.denoise(input_tensor, inference_steps=inference_steps, **kw, **rule)
-    if device.type == "cuda":
+    if self_ensemble is not None or samples is not None:
+        if std_out is not None:
+            np.save(std_out, ens.std.reshape(img_size, img_size).cpu().numpy())
+        if quantiles is not None:
+            np.save(quantiles_out, ens.quantiles.reshape(len(quantiles), img_size, img_size).cpu().numpy())
+    if on_gpu:
         torch.cuda.synchronize(device)
     print(f"Inference time: {time.time() - start_time:.2f} seconds")
+    denoised = denoised.reshape(1, 1, img_size, img_size)
     if clean is not None:
-        evaluate(diffusion, clean, input_tensor, denoised, img_size, bit_depth, win, seed, loss_out)
+        evaluate(diffusion, clean, input_tensor, denoised, img_size, recipe, win, seed, loss_out)
     if nps_out is not None:
-        write_nps(nps_out, nps_roi, nps_step, input_tensor, denoised.reshape(1, 1, img_size, img_size),
-                  ens.samples if samples is not None else None, truth, img_size, bit_depth, win, ens.seed if samples is not None else seed)
+        write_nps(nps_out, nps_roi, nps_step, input_tensor, denoised, ens.samples if samples is not None else None, truth_img,
+                  ens.seed if samples is not None else seed)
     if fidelity_out is not None:
-        write_fidelity(fidelity_out, fidelity_roi, fidelity_step, input_tensor, denoised.reshape(1, 1, img_size, img_size), ens.samples, truth,
-                       img_size, bit_depth, win, ens.seed)
-
-    if win is not None:
-        plane = denoised.reshape(img_size, img_size).float()
-        if on_gpu:      # float resize back, clip, windowed store: one fused call
-            print("Window: grey levels {} .. {}".format(*win[0].tolist()))
-            back = prepost.resize_bicubic_f32(plane, raw16.shape, clamp=True, out_dtype=torch.uint16, levels=win).cpu().numpy()
-        else:
-            back = image16.to_u16_window(image16.resize_f(plane.cpu().numpy(), raw16.shape), win)
-        return image16.image_from_u16(back)
-    if raw16 is not None:
-        plane = denoised.reshape(img_size, img_size).float()
-        if on_gpu:      # float resize back, clip, round to u16: one fused call
-            back = prepost.resize_bicubic_f32(plane, raw16.shape, clamp=True, out_dtype=torch.uint16).cpu().numpy()
-        else:
-            back = image16.to_u16(image16.resize_f(plane.cpu().numpy(), raw16.shape))
-        return image16.image_from_u16(back)
-    if on_gpu:
-        u8 = prepost.to_u8(denoised.reshape(img_size, img_size).float())     # denoise() already clamped to [0, 1]
-        return Image.fromarray(prepost.resize_bicubic_u8(u8, (img.size[1], img.size[0])).cpu().numpy(), mode="L")
-    output_np = denoised.squeeze().cpu().numpy()
-    output_img = Image.fromarray((output_np * 255).astype(np.uint8), mode="L")
-    return output_img.resize(img.size, Image.BICUBIC)
+        write_fidelity(fidelity_out, fidelity_roi, fidelity_step, input_tensor, denoised, ens.samples, truth_img, ens.seed)
+    return restored(denoised)
 
 
-def load_counterpart(path: str, device, img_size: Optional[int], bit_depth: int, win) -> torch.Tensor:
-    """The clean counterpart of the noisy image (--clean, --truth) as the [1, 1, H, W] tensor the sampler's input is, on the GPU: the
-    same recipe -- bit_depth, the resize to img_size (None: --tile, the image's own size, no resize) and the NOISY image's window
-    levels `win` (device int32 [1, 2]) if it has a window."""
-    from . import prepost
-    img = Image.open(path)
-    raw16 = image16.decode16(img) if bit_depth == 16 else None
-    if win is not None:
-        dev16 = torch.from_numpy(image16.need_u16(raw16, img.mode)).to(device)
-        if img_size is None:
-            return prepost.window_u16_to_float(dev16, win)[None, None]
-        return prepost.resize_bicubic_f32(dev16, (img_size, img_size), clamp=True, levels=win)[None, None]
-    if raw16 is not None:
-        dev_raw = torch.from_numpy(raw16).to(device)
-        if img_size is None:
-            return (prepost.u16_to_unit_float if raw16.dtype == np.uint16 else prepost.to_unit_float)(dev_raw)[None, None]
-        return prepost.resize_bicubic_f32(dev_raw, (img_size, img_size), clamp=True)[None, None]
-    raw = torch.from_numpy(np.asarray(img.convert("L"), np.uint8).copy()).to(device)
-    if img_size is None:
-        return prepost.to_unit_float(raw)[None, None]
-    return prepost.to_unit_float(prepost.resize_bicubic_u8(raw, (img_size, img_size)))[None, None]
+def load_counterpart(path: str, device, img_size: Optional[int], recipe: ImageRecipe, win) -> torch.Tensor:
+    """The clean counterpart of the noisy image (--clean, --truth) as the [1, 1, H, W] tensor the sampler's input is: the same
+    recipe -- bit_depth, the resize to img_size (None: --tile, the image's own size, no resize) and the NOISY image's window levels
+    `win` (on the GPU a device int32 [1, 2]) if it has a window."""
+    return recipe.load(Image.open(path), None if img_size is None else (img_size, img_size), device, levels=win)[0]
 
 
-def score(samples: torch.Tensor, truth_path: str, img_size: Optional[int], bit_depth: int, win, levels, seed, scores_out: Optional[str]) -> dict:
-    """--truth: the scores of the ensemble `samples` [1, K, 1, H, W] against the truth image (sampler.ensemble_scores), printed and,
-    with scores_out, written as JSON.  The truth goes through the recipe of the noisy image (load_counterpart)."""
-    import json
-    truth = load_counterpart(truth_path, samples.device, img_size, bit_depth, win)
+def load_truth(path: str, samples: torch.Tensor, img_size: Optional[int], recipe: ImageRecipe, win) -> torch.Tensor:
+    """--truth for the ensemble `samples` [1, K, 1, H, W]: load_counterpart, float32 [1, 1, H, W], refused at another size."""
+    truth = load_counterpart(path, samples.device, img_size, recipe, win).float()
     if tuple(truth.shape[2:]) != tuple(samples.shape[3:]):
         raise ValueError(f"--truth is {truth.shape[2]}x{truth.shape[3]}, the ensemble {samples.shape[3]}x{samples.shape[4]}: the truth image "
                          "must have the size of --image")
-    sc = ensemble_scores(samples, truth.float(), levels)
+    return truth
+
+
+def score(samples: torch.Tensor, truth: torch.Tensor, levels, seed, scores_out: Optional[str]) -> dict:
+    """--truth: the scores of the ensemble `samples` [1, K, 1, H, W] against the truth image (sampler.ensemble_scores), printed and,
+    with scores_out, written as JSON.  The truth went through the recipe of the noisy image (load_truth)."""
+    import json
+    sc = ensemble_scores(samples, truth, levels)
     result = {"members": int(samples.shape[1]), "height": int(truth.shape[2]), "width": int(truth.shape[3]), "seed": seed,
               "crps": float(sc.crps[0]), "crps_fair": float(sc.crps_fair[0]), "rmse": float(sc.rmse[0]), "spread": float(sc.spread[0]),
               "valid": int(sc.valid[0]), "sums": sc.sums[0].tolist(), "rank_hist": sc.rank_hist[0].tolist(), "levels": list(sc.levels),
@@ -438,9 +393,9 @@ def score(samples: torch.Tensor, truth_path: str, img_size: Optional[int], bit_d
 
 
 def write_nps(nps_out: str, roi: int, step: int, noisy: torch.Tensor, output: torch.Tensor, samples: Optional[torch.Tensor],
-              truth_path: Optional[str], img_size: Optional[int], bit_depth: int, win, seed) -> dict:
-    """--nps-out: the radial noise power spectra of the run at the sampler's resolution, printed in short and written as JSON.  noisy
-    and output are [1, 1, H, W]; samples [1, K, 1, H, W] or None; the truth goes through the recipe of the noisy image."""
+              truth: Optional[torch.Tensor], seed) -> dict:
+    """--nps-out: the radial noise power spectra of the run at the sampler's resolution, printed in short and written as JSON.  noisy,
+    output and the truth (load_truth, or None) are [1, 1, H, W]; samples [1, K, 1, H, W] or None."""
     import json
 
     def entry(sp, **more):
@@ -454,12 +409,8 @@ def write_nps(nps_out: str, roi: int, step: int, noisy: torch.Tensor, output: to
     if samples is not None and samples.shape[1] >= 2:
         K = int(samples.shape[1])
         result["ensemble_spread"] = entry(noise_power_spectrum(samples, out, roi, step, scale=K / (K - 1)), members=K)
-    if truth_path is not None:
-        truth = load_counterpart(truth_path, out.device, img_size, bit_depth, win)
-        if tuple(truth.shape) != tuple(out.shape):
-            raise ValueError(f"--truth is {truth.shape[2]}x{truth.shape[3]}, the output {out.shape[2]}x{out.shape[3]}: the truth image must have "
-                             "the size of --image")
-        result["residual"] = entry(noise_power_spectrum(out, truth.float(), roi, step))
+    if truth is not None:
+        result["residual"] = entry(noise_power_spectrum(out, truth, roi, step))
     print(f"Noise power spectrum ({roi} x {roi} ROIs at step {step}, plane detrend, Hann window; cycles per pixel):")
     for name in ("method_noise", "ensemble_spread", "residual"):
         if name in result:
@@ -473,9 +424,9 @@ def write_nps(nps_out: str, roi: int, step: int, noisy: torch.Tensor, output: to
 
 
 def write_fidelity(fidelity_out: str, roi: int, step: int, noisy: torch.Tensor, output: torch.Tensor, samples: torch.Tensor,
-                   truth_path: Optional[str], img_size: Optional[int], bit_depth: int, win, seed) -> dict:
+                   truth: Optional[torch.Tensor], seed) -> dict:
     """--fidelity-out: at which spatial frequencies the signal survives the run (sampler.cross_spectrum), printed in short and written
-    as JSON.  noisy and output are [1, 1, H, W], samples [1, K, 1, H, W].  With a truth (loaded by the recipe of the noisy image): the
+    as JSON.  noisy and output are [1, 1, H, W], samples [1, K, 1, H, W].  With a truth ([1, 1, H, W], load_truth): the
     transfer, the FRC and the resolution of (truth, output) and of (truth, noisy).  With an even K >= 2: the FRC between the draws
     samples[:, 0::2] and samples[:, 1::2], which needs no truth."""
     import json
@@ -488,11 +439,7 @@ def write_fidelity(fidelity_out: str, roi: int, step: int, noisy: torch.Tensor, 
     K = int(samples.shape[1])
     result = {"roi": roi, "step": step, "detrend": "plane", "window": "hann", "height": int(out.shape[2]), "width": int(out.shape[3]),
               "seed": seed, "freqs": [r / roi for r in range(roi // 2 + 1)]}
-    if truth_path is not None:
-        truth = load_counterpart(truth_path, out.device, img_size, bit_depth, win).float()
-        if tuple(truth.shape) != tuple(out.shape):
-            raise ValueError(f"--truth is {truth.shape[2]}x{truth.shape[3]}, the output {out.shape[2]}x{out.shape[3]}: the truth image must have "
-                             "the size of --image")
+    if truth is not None:
         result["truth_output"] = entry(cross_spectrum(truth, out, roi, step))
         result["truth_noisy"] = entry(cross_spectrum(truth, noisy.float(), roi, step))
     if K >= 2 and K % 2 == 0:
@@ -509,17 +456,15 @@ def write_fidelity(fidelity_out: str, roi: int, step: int, noisy: torch.Tensor, 
     return result
 
 
-def evaluate(diffusion: DiffusionDenoiser, clean_path: str, noisy: torch.Tensor, denoised: torch.Tensor, img_size: int, bit_depth: int,
+def evaluate(diffusion: DiffusionDenoiser, clean_path: str, noisy: torch.Tensor, denoised: torch.Tensor, img_size: int, recipe: ImageRecipe,
              win, seed: Optional[int], loss_out: Optional[str]) -> dict:
     """--clean: the loss profile of the (clean, noisy) pair over all timesteps and the PSNR / SSIM of `denoised` against the clean
     image, printed and, with loss_out, written as JSON.  The clean image goes through the recipe the noisy one went through; a
     window's levels are the noisy image's."""
     import json
-
-    from . import prepost
-    clean = load_counterpart(clean_path, noisy.device, img_size, bit_depth, win)
+    clean = load_counterpart(clean_path, noisy.device, img_size, recipe, win)
     prof = diffusion.loss_profile(clean, noisy, seed=seed)
-    psnr, ssim = prepost.compute_metrics(denoised.reshape(1, 1, img_size, img_size).float(), clean)
+    psnr, ssim = prepost.compute_metrics(denoised.float(), clean)
     variant = getattr(diffusion.model, "variant", "ddim")
     result = {"variant": variant, "noise_steps": diffusion.noise_steps, "img_size": img_size, "t": list(prof.t),
               "loss": prof.loss[:, 0].tolist(), "mse": prof.mse[:, 0].tolist(), "edge": prof.edge[:, 0].tolist(),
@@ -605,112 +550,45 @@ def main(argv=None) -> None:
     ap.add_argument("--fidelity-roi", type=int, default=None, metavar="R", help="with --fidelity-out: the ROI size, 32, 64 (default) or 128")
     ap.add_argument("--fidelity-step", type=int, default=None, metavar="S", help="with --fidelity-out: the ROI step (default R / 2)")
     args = ap.parse_args(argv)
-    if (args.nps_roi is not None or args.nps_step is not None) and args.nps_out is None:
-        ap.error("--nps-roi and --nps-step need --nps-out PATH.json")
-    if (args.fidelity_roi is not None or args.fidelity_step is not None) and args.fidelity_out is None:
-        ap.error("--fidelity-roi and --fidelity-step need --fidelity-out PATH.json")
-    if args.fidelity_roi is not None and args.fidelity_roi not in NPS_ROIS:
-        ap.error(f"--fidelity-roi needs one of {NPS_ROIS}")
-    if args.fidelity_step is not None and args.fidelity_step < 1:
-        ap.error("--fidelity-step needs S >= 1")
-    if args.fidelity_out is not None:
-        n_draws = args.samples if args.samples is not None else (args.members if args.tile is not None else None)
-        if n_draws is None or (args.truth is None and (n_draws < 2 or n_draws % 2)):
-            ap.error("--fidelity-out needs --truth PATH beside --samples K or --tile N --members K, or an even K >= 2 of them (the FRC between "
-                     "the draws needs no truth)")
-        if args.tile is None and args.img_size < (args.fidelity_roi or 64):
-            ap.error(f"--fidelity-out: the sampler's image ({args.img_size}x{args.img_size}) is smaller than the ROI ({args.fidelity_roi or 64}); "
-                     "use a smaller --fidelity-roi")
-    if args.nps_roi is not None and args.nps_roi not in NPS_ROIS:
-        ap.error(f"--nps-roi needs one of {NPS_ROIS}")
-    if args.nps_step is not None and args.nps_step < 1:
-        ap.error("--nps-step needs S >= 1")
-    if args.nps_out is not None and args.tile is None and args.img_size < (args.nps_roi or 64):
-        ap.error(f"--nps-out: the sampler's image ({args.img_size}x{args.img_size}) is smaller than the ROI ({args.nps_roi or 64}); use a smaller --nps-roi")
-    if args.scores_out is not None and args.truth is None:
-        ap.error("--scores-out needs --truth PATH")
-    if args.truth is not None:
-        if args.samples is None and (args.tile is None or args.members is None):
-            ap.error("--truth scores an ensemble: it needs --samples K, or --tile N --members K")
-        if (args.samples if args.samples is not None else args.members) > MAX_QUANTILE_MEMBERS:
-            ap.error(f"--truth needs K <= {MAX_QUANTILE_MEMBERS} members")
-    if args.loss_out is not None and args.clean is None:
-        ap.error("--loss-out needs --clean PATH")
-    if args.clean is not None:
-        for flag, given in (("--tile", args.tile), ("--samples", args.samples), ("--views", args.views), ("--members", args.members),
-                            ("--self-ensemble", args.self_ensemble), ("--x0-out", args.x0_out)):
-            if given is not None:
-                ap.error(f"--clean (evaluation) cannot be combined with {flag}")
+    # the rules that are main's own: the text arguments and the ranges argv words; every other rule is check_options'
+    for flag, roi, step in (("fidelity", args.fidelity_roi, args.fidelity_step), ("nps", args.nps_roi, args.nps_step)):
+        if roi is not None and roi not in NPS_ROIS:
+            ap.error(f"--{flag}-roi needs one of {NPS_ROIS}")
+        if step is not None and step < 1:
+            ap.error(f"--{flag}-step needs S >= 1")
     if args.update == "reference" and (args.eta != 0.0 or args.no_clip_x0):
         ap.error("--eta and --no-clip-x0 need --update ddim")
     if not 0.0 <= args.eta <= 1.0:
         ap.error("--eta needs a value in [0, 1]")
-    if args.update == "dpmpp2m" and (args.eta != 0.0 or args.seed is not None or args.samples is not None):
+    if args.update == "dpmpp2m" and args.eta != 0.0:
         ap.error("--update dpmpp2m is deterministic: it takes no --eta, --seed or --samples")
-    if args.x0_out is not None and (args.update != "dpmpp2m" or args.tile is not None):
-        ap.error("--x0-out needs --update dpmpp2m and no --tile")
-    if args.update != "reference" and args.self_ensemble is not None:
-        ap.error(f"--update {args.update} cannot be combined with --self-ensemble")
-    if args.self_ensemble is not None and args.samples is not None:
-        ap.error("--self-ensemble cannot be combined with --samples")
-    if args.self_ensemble is not None and args.tile is not None:
-        ap.error("--self-ensemble cannot be combined with --tile")
-    if args.tile is not None and (args.tile < 1 or args.samples is not None):
-        ap.error("--tile needs N >= 1 and cannot be combined with --samples")
-    if (args.views is not None or args.members is not None) and args.tile is None:
-        ap.error("--views and --members need --tile N (without it: --self-ensemble, --samples)")
-    if args.views is not None and args.members is not None:
-        ap.error("--views and --members cannot be combined")
-    if args.views is not None and args.update == "dpmpp2m":
-        ap.error("--update dpmpp2m cannot be combined with --views")
-    if args.members is not None and (args.members < 1 or args.variant != "cddpm" or args.update != "reference"):
-        ap.error("--members needs K >= 1, --variant cddpm and the reference's update (a deterministic sampler has no ensemble: use --views)")
-    tiled_ensemble = args.views is not None or args.members is not None
-    if args.std_out is not None and args.members is not None and args.members < 2:
-        ap.error("--std-out needs --members K with K >= 2")
-    if args.quantiles is not None and args.members is not None and args.members > MAX_QUANTILE_MEMBERS:
-        ap.error(f"--quantiles needs --members K with K <= {MAX_QUANTILE_MEMBERS}")
-    if args.samples is not None and (args.samples < 1 or (args.variant != "cddpm" and not (args.update == "ddim" and args.eta > 0))):
-        ap.error("--samples needs K >= 1 and --variant cddpm (or --update ddim with --eta > 0)")
-    if args.std_out is not None and args.self_ensemble is None and not tiled_ensemble and (args.samples is None or args.samples < 2):
-        ap.error("--std-out needs --samples K with K >= 2")
-    levels = None
-    if (args.quantiles is None) != (args.quantiles_out is None):
-        ap.error("--quantiles and --quantiles-out come together")
-    if args.quantiles is not None:
-        if args.self_ensemble is None and not tiled_ensemble and (args.samples is None or args.samples > MAX_QUANTILE_MEMBERS):
-            ap.error(f"--quantiles needs --samples K with K <= {MAX_QUANTILE_MEMBERS}")
-        try:
-            levels = check_levels([float(v) for v in args.quantiles.split(",")])
-        except ValueError as exc:
-            ap.error(f"--quantiles needs up to 8 comma-separated levels in [0, 1]: {exc}")
-    window = window_levels = None
-    if args.window is not None and args.window_levels is not None:
-        ap.error("--window and --window-levels cannot be combined")
-    if (args.window is not None or args.window_levels is not None) and args.bit_depth != 16:
-        ap.error("--window and --window-levels need --bit-depth 16")
+    if args.tile is not None and args.tile < 1:
+        ap.error("--tile needs N >= 1")
+    if args.samples is not None and args.samples < 1:
+        ap.error("--samples needs K >= 1")
+    options = dict(device_type=args.device, img_size=args.img_size, variant=args.variant, seed=args.seed, samples=args.samples,
+                   std_out=args.std_out, tile=args.tile, quantiles=None, quantiles_out=args.quantiles_out, self_ensemble=args.self_ensemble,
+                   update=args.update, eta=args.eta, clip_x0=not args.no_clip_x0, bit_depth=args.bit_depth)
+    later = dict(x0_out=args.x0_out, window=None, window_levels=None, views=args.views, members=args.members, clean=args.clean,
+                 loss_out=args.loss_out, truth=args.truth, scores_out=args.scores_out, nps_out=args.nps_out, nps_roi=args.nps_roi,
+                 nps_step=args.nps_step, fidelity_out=args.fidelity_out, fidelity_roi=args.fidelity_roi, fidelity_step=args.fidelity_step)
+    try:
+        if args.quantiles is not None:
+            options["quantiles"] = check_levels([float(v) for v in args.quantiles.split(",")])
+    except ValueError as exc:
+        ap.error(f"--quantiles needs up to 8 comma-separated levels in [0, 1]: {exc}")
     try:
         if args.window is not None:
-            window = image16.check_percentiles(image16.parse_pair(args.window, "--window"))
+            later["window"] = image16.parse_pair(args.window, "--window")
         if args.window_levels is not None:
-            window_levels = image16.check_levels(image16.parse_pair(args.window_levels, "--window-levels"))
+            later["window_levels"] = image16.parse_pair(args.window_levels, "--window-levels")
+        options.update({k: v for k, v in later.items() if v is not None})      # the later options are passed on only where given
+        opt = check_options(**options)
     except ValueError as exc:
         ap.error(str(exc))
-    restored = denoise_image_diffusion(args.checkpoint, args.image, device_type=args.device, img_size=args.img_size,
-                                       inference_steps=args.inference_steps, variant=args.variant, seed=args.seed,
-                                       samples=args.samples, std_out=args.std_out, tile=args.tile, overlap=args.overlap,
-                                       quantiles=levels, quantiles_out=args.quantiles_out, self_ensemble=args.self_ensemble,
-                                       update=args.update, eta=args.eta, clip_x0=not args.no_clip_x0,
-                                       **({} if args.x0_out is None else {"x0_out": args.x0_out}),
-                                       bit_depth=args.bit_depth, **({} if window is None else {"window": window}),
-                                       **({} if window_levels is None else {"window_levels": window_levels}),
-                                       **({} if args.views is None else {"views": args.views}),
-                                       **({} if args.members is None else {"members": args.members}),
-                                       **({} if args.clean is None else {"clean": args.clean, "loss_out": args.loss_out}),
-                                       **({} if args.truth is None else {"truth": args.truth, "scores_out": args.scores_out}),
-                                       **({} if args.nps_out is None else {"nps_out": args.nps_out, "nps_roi": args.nps_roi, "nps_step": args.nps_step}),
-                                       **({} if args.fidelity_out is None else {"fidelity_out": args.fidelity_out, "fidelity_roi": args.fidelity_roi,
-                                                                                "fidelity_step": args.fidelity_step}))
+    options.update(quantiles=opt.quantiles, **{k: v for k, v in (("window", opt.recipe.window), ("window_levels", opt.recipe.window_levels))
+                                              if v is not None})
+    restored = denoise_image_diffusion(args.checkpoint, args.image, inference_steps=args.inference_steps, overlap=args.overlap, **options)
     restored.save(args.out, quality=95)
     print(f"\nResult saved: {args.out}")
 

@@ -4,7 +4,7 @@ Not in the reference, whose every path squeezes an image through 256 grey levels
 out): a 16-bit PNG is decoded to its 65536 levels, scaled to unit float, resampled by Pillow in mode "F" (its 32bpc resample, not
 its "I;16" one, which wraps the low byte on overshoot), clipped, and stored back as u16 rounded to nearest.  These functions are the
 recipe with Pillow and numpy; `prepost.resize_bicubic_f32` / `u16_to_unit_float` / `to_u16` are the same arithmetic on the GPU, bit
-for bit.  cli.py and server.py use whichever side their tensors live on.
+for bit.  recipe.py picks the side its tensors live on, for cli.py and server.py alike.
 
 `window_levels` / `unit_float_window` / `to_u16_window` are the host twins of the window (include/midd.h: THE WINDOW;
 `prepost.window_levels` / `window_u16_to_float` / `window_to_u16` on the GPU): the grey range [lo, hi] between two percentiles of the

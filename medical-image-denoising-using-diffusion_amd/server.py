@@ -64,12 +64,12 @@ from email.parser import BytesParser
 from email.policy import HTTP
 from typing import Callable, Optional, Tuple
 
-import numpy as np
 import torch
 from PIL import Image
 
 from . import image16
 from .modules import UNetDiffusion
+from .recipe import ImageRecipe, Source
 from .sampler import DiffusionDenoiser, SamplerRule, check_update, refuse_update
 
 SERVE_SIZE = (512, 512)          # run.py:198
@@ -103,114 +103,86 @@ def check_tile(tile, overlap) -> Tuple[Tuple[int, int], Tuple[int, int]]:
     return (th, tw), (oy, ox)
 
 
-# ------------------------------------------------------------------------------ pre / post
+# ------------------------------------------------------------------------------ pre / post: recipe.py, under the names of its kinds
+def _load(recipe: ImageRecipe, image_bytes: bytes, device, tile):
+    """bytes -> (float32 [1,1,H,W] in [0,1] on `device`, (width, height) or, under a window, (width, height, levels))."""
+    image = Image.open(io.BytesIO(image_bytes))
+    x, source = recipe.load(image, serve_size(image.size, tile), device)
+    return x, source.as_tuple()
+
+
+def _store(recipe: ImageRecipe, tensor: torch.Tensor, size) -> str:
+    """[1,1,H,W] in [0,1] -> base64 PNG (8-bit "L" or 16-bit "I;16") at the original size; `size` is what _load returned."""
+    buffered = io.BytesIO()
+    Image.fromarray(recipe.store(tensor, Source.of(size))).save(buffered, format="PNG")
+    return base64.b64encode(buffered.getvalue()).decode()
+
+
 def preprocess(image_bytes: bytes, tile=None) -> Tuple[torch.Tensor, Tuple[int, int]]:
     """bytes -> (fp32 [1,1,512,512] in [0,1], original (width, height)) — run.py:193-201.
     ``transforms.Resize`` on a PIL image is ``Image.resize(..., BICUBIC)``; ``ToTensor`` is uint8/255."""
-    image = Image.open(io.BytesIO(image_bytes)).convert("L")
-    original_size = image.size
-    resized = image.resize(serve_size(original_size, tile)[::-1], Image.BICUBIC)      # (equal sizes: a copy, no resample)
-    arr = np.asarray(resized, dtype=np.uint8).astype(np.float32) / 255.0
-    return torch.from_numpy(arr)[None, None], original_size
+    return _load(ImageRecipe(8), image_bytes, "cpu", tile)
 
 
 def tensor_to_base64(tensor: torch.Tensor, size: Tuple[int, int]) -> str:
     """[1,1,H,W] in [0,1] -> base64 PNG at the original size — run.py:143-149."""
-    output_np = tensor.squeeze(0).squeeze(0).cpu().numpy()
-    output_img = Image.fromarray((output_np * 255).astype("uint8"), mode="L")
-    output_img = output_img.resize(size, Image.BICUBIC)
-    buffered = io.BytesIO()
-    output_img.save(buffered, format="PNG")
-    return base64.b64encode(buffered.getvalue()).decode()
+    return _store(ImageRecipe(8), tensor, size)
 
 
 def preprocess_device(image_bytes: bytes, device: torch.device, tile=None) -> Tuple[torch.Tensor, Tuple[int, int]]:
     """`preprocess` with the resize and the ToTensor scaling on the GPU (csrc/prepost.hip; bit-identical to the
     host recipe): only the PNG/JPEG decode stays on the host."""
-    from . import prepost
-    image = Image.open(io.BytesIO(image_bytes)).convert("L")
-    original_size = image.size
-    raw = torch.from_numpy(np.asarray(image, dtype=np.uint8).copy()).to(device, non_blocking=True)
-    resized = prepost.resize_bicubic_u8(raw, serve_size(original_size, tile))
-    return prepost.to_unit_float(resized)[None, None], original_size
+    return _load(ImageRecipe(8), image_bytes, device, tile)
 
 
 def tensor_to_base64_device(tensor: torch.Tensor, size: Tuple[int, int]) -> str:
     """`tensor_to_base64` with clamp / x255 truncation / resize-back on the GPU; PNG encoding on the host."""
-    from . import prepost
-    u8 = prepost.to_u8(tensor.reshape(tensor.shape[-2], tensor.shape[-1]).float())
-    back = prepost.resize_bicubic_u8(u8, (size[1], size[0])).cpu().numpy()      # PIL size is (width, height)
-    buffered = io.BytesIO()
-    Image.fromarray(back, mode="L").save(buffered, format="PNG")
-    return base64.b64encode(buffered.getvalue()).decode()
+    return _store(ImageRecipe(8), tensor, size)
 
 
 def preprocess16(image_bytes: bytes, tile=None) -> Tuple[torch.Tensor, Tuple[int, int]]:
     """`preprocess` of the 16-bit recipe: decode to unit float (/ 65535 for a 16-bit file, `convert("L")` / 255 for any other),
     Pillow mode "F" bicubic resize to 512x512, clip to [0, 1]."""
-    image = Image.open(io.BytesIO(image_bytes))
-    original_size = image.size
-    x = image16.resize_f(image16.unit_float(image16.decode16(image)), serve_size(original_size, tile))
-    return torch.from_numpy(x)[None, None], original_size
+    return _load(ImageRecipe(16), image_bytes, "cpu", tile)
 
 
 def tensor_to_base64_16(tensor: torch.Tensor, size: Tuple[int, int]) -> str:
     """[1,1,H,W] -> base64 16-bit PNG at the original size: mode "F" resize back, clip, u16 rounded to nearest."""
-    x = tensor.reshape(tensor.shape[-2], tensor.shape[-1]).float().cpu().numpy()
-    return base64.b64encode(image16.png_bytes_u16(image16.to_u16(image16.resize_f(x, (size[1], size[0]))))).decode()
+    return _store(ImageRecipe(16), tensor, size)
 
 
 def preprocess16_device(image_bytes: bytes, device: torch.device, tile=None) -> Tuple[torch.Tensor, Tuple[int, int]]:
     """`preprocess16` with the scaling, the resize and the clip on the GPU (one fused call of csrc/prepost.hip; bit-identical to
     the host recipe): only the decode stays on the host."""
-    from . import prepost
-    image = Image.open(io.BytesIO(image_bytes))
-    original_size = image.size
-    raw = torch.from_numpy(image16.decode16(image)).to(device, non_blocking=True)
-    return prepost.resize_bicubic_f32(raw, serve_size(original_size, tile), clamp=True)[None, None], original_size
+    return _load(ImageRecipe(16), image_bytes, device, tile)
 
 
 def tensor_to_base64_16_device(tensor: torch.Tensor, size: Tuple[int, int]) -> str:
     """`tensor_to_base64_16` with the resize back, the clip and the u16 rounding on the GPU; PNG encoding on the host."""
-    from . import prepost
-    plane = tensor.reshape(tensor.shape[-2], tensor.shape[-1]).float()
-    back = prepost.resize_bicubic_f32(plane, (size[1], size[0]), clamp=True, out_dtype=torch.uint16).cpu().numpy()
-    return base64.b64encode(image16.png_bytes_u16(back)).decode()
+    return _store(ImageRecipe(16), tensor, size)
 
 
 def preprocess16_window(image_bytes: bytes, percentiles, tile=None) -> Tuple[torch.Tensor, Tuple[int, int, Tuple[int, int]]]:
     """`preprocess16` under a window (include/midd.h: THE WINDOW): the levels (lo, hi) at the two percentiles of THIS upload, the
     windowed load, the mode "F" resize, the clip.  The second value carries the levels to the way back: (width, height, (lo, hi)).
     An upload that is not 16-bit raises image16.WindowInputError naming its mode (the route answers 400)."""
-    image = Image.open(io.BytesIO(image_bytes))
-    raw = image16.need_u16(image16.decode16(image), image.mode)
-    levels = image16.window_levels(raw, percentiles)
-    x = image16.resize_f(image16.unit_float_window(raw, levels), serve_size(image.size, tile))
-    return torch.from_numpy(x)[None, None], image.size + (levels,)
+    return _load(ImageRecipe(16, window=percentiles), image_bytes, "cpu", tile)
 
 
 def tensor_to_base64_16_window(tensor: torch.Tensor, size) -> str:
     """`tensor_to_base64_16` under the levels that preprocess16_window attached: resize back, clip, windowed store."""
-    x = tensor.reshape(tensor.shape[-2], tensor.shape[-1]).float().cpu().numpy()
-    return base64.b64encode(image16.png_bytes_u16(image16.to_u16_window(image16.resize_f(x, (size[1], size[0])), size[2]))).decode()
+    return _store(ImageRecipe(16), tensor, size)
 
 
 def preprocess16_window_device(image_bytes: bytes, device: torch.device, percentiles, tile=None):
     """`preprocess16_window` on the GPU: histogram, levels, and one fused windowed load + resize + clip (csrc/prepost.hip).  The levels
     stay on the device, an int32 [1,2] tensor in the place of (lo, hi): nothing waits for them."""
-    from . import prepost
-    image = Image.open(io.BytesIO(image_bytes))
-    raw = torch.from_numpy(image16.need_u16(image16.decode16(image), image.mode)).to(device, non_blocking=True)
-    levels = prepost.window_levels(raw, percentiles)
-    return prepost.resize_bicubic_f32(raw, serve_size(image.size, tile), clamp=True, levels=levels)[None, None], image.size + (levels,)
+    return _load(ImageRecipe(16, window=percentiles), image_bytes, device, tile)
 
 
 def tensor_to_base64_16_window_device(tensor: torch.Tensor, size) -> str:
     """`tensor_to_base64_16_window` with the resize back, the clip and the windowed store on the GPU."""
-    from . import prepost
-    plane = tensor.reshape(tensor.shape[-2], tensor.shape[-1]).float()
-    back = prepost.resize_bicubic_f32(plane, (size[1], size[0]), clamp=True, out_dtype=torch.uint16, levels=size[2]).cpu().numpy()
-    return base64.b64encode(image16.png_bytes_u16(back)).decode()
+    return _store(ImageRecipe(16), tensor, size)
 
 
 def extract_multipart_file(body: bytes, content_type: str, field: str = "file") -> bytes:
@@ -236,14 +208,13 @@ class DiffusionService:
                  slot_update: Optional[str] = None, slot_eta: Optional[float] = None):
         # 8: the reference's 8-bit pre/post-processing; 16: the 16-bit recipe (preprocess16 / tensor_to_base64_16).  None reads
         # MIDD_BIT_DEPTH, default 8
-        self.bit_depth = image16.check_bit_depth(int(os.environ.get("MIDD_BIT_DEPTH", "8")) if bit_depth is None else bit_depth)
+        bit_depth = image16.check_bit_depth(int(os.environ.get("MIDD_BIT_DEPTH", "8")) if bit_depth is None else bit_depth)
         # (p_lo, p_hi): every request is windowed between these percentiles of its own image (include/midd.h: THE WINDOW); None reads
         # MIDD_WINDOW ("0.5,99.5"), default no window
         if window is None and os.environ.get("MIDD_WINDOW"):
             window = image16.parse_pair(os.environ["MIDD_WINDOW"], "MIDD_WINDOW")
-        self.window = None if window is None else image16.check_percentiles(window)
-        if self.window is not None and self.bit_depth != 16:
-            raise ValueError("a window needs bit_depth=16 (the window acts on 16-bit uploads)")
+        self.recipe = ImageRecipe(bit_depth, window=window)
+        self.bit_depth, self.window = self.recipe.bit_depth, self.recipe.window
         # (th, tw): every upload is served at its own size as blended overlapping tiles (DiffusionDenoiser.denoise_tiled); None reads
         # MIDD_TILE ("N" or "TH,TW") and MIDD_TILE_OVERLAP, default no tiling: the resize to SERVE_SIZE and back
         if tile is None and os.environ.get("MIDD_TILE"):
@@ -317,13 +288,7 @@ class DiffusionService:
                                                                    overlap=self.overlap, **rule).image
                 else:
                     output = self.diffusion_denoiser.denoise(input_tensor, inference_steps=SERVE_INFERENCE_STEPS, **rule)
-            output = torch.clamp(output, 0, 1)
-            if len(original_size) == 3:       # a windowed request: (width, height, levels)
-                result = (tensor_to_base64_16_window_device if output.is_cuda else tensor_to_base64_16_window)(output, original_size)
-            elif self.bit_depth == 16:
-                result = (tensor_to_base64_16_device if output.is_cuda else tensor_to_base64_16)(output, original_size)
-            else:
-                result = (tensor_to_base64_device if output.is_cuda else tensor_to_base64)(output, original_size)
+            result = _store(self.recipe, torch.clamp(output, 0, 1), original_size)
         print(f"  Diffusion: {time.time() - start:.2f}s")
         return result
 
@@ -396,14 +361,7 @@ class DiffusionService:
 
     def preprocess(self, image_bytes: bytes) -> Tuple[torch.Tensor, Tuple[int, int]]:
         """Decode + resize + scale; on the GPU when the service runs there (same bytes either way)."""
-        if self.window is not None:
-            if self.device.type == "cuda" and self._denoise_fn is None:
-                return preprocess16_window_device(image_bytes, self.device, self.window, tile=self.tile)
-            x, size = preprocess16_window(image_bytes, self.window, tile=self.tile)
-            return x.to(self.device), size
-        if self.device.type == "cuda" and self._denoise_fn is None:
-            return (preprocess16_device if self.bit_depth == 16 else preprocess_device)(image_bytes, self.device, tile=self.tile)
-        x, size = (preprocess16 if self.bit_depth == 16 else preprocess)(image_bytes, tile=self.tile)
+        x, size = _load(self.recipe, image_bytes, self.device if self._denoise_fn is None else "cpu", self.tile)
         return x.to(self.device), size
 
 
