@@ -356,6 +356,58 @@ int mi_ensemble_scores(const float* samples, const float* truth, int B, int memb
                        double* sums, uint64_t* invalid, uint64_t* rank_hist, uint64_t* counts, float* crps_map,
                        void* workspace, size_t workspace_bytes, void* stream);
 
+/* ENSEMBLE MODES (no plan needed): what varies TOGETHER?  The std and quantile maps say how much a pixel varies, the scores whether
+ * that amount is calibrated; neither tells a global brightness shift from an edge that moves or a structure that comes and goes.
+ * The principal components of the members do: the leading eigenvectors of their covariance, each shown as an image in grey-level
+ * units.  With K <= 64 members the covariance never exists: the K x K Gram matrix of the centred members is a reduction over the
+ * pixels (mi_ensemble_gram), its eigenvectors are a host matter (C callers bring their own symmetric eigensolver), and the modes
+ * are one projection of the centred members onto the scaled eigenvectors (mi_ensemble_project).  Channels are pooled: an element
+ * is one of the chw values of an image.
+ * THE ENSEMBLE MODES (fixed; independent of the launch geometry, the vector width and the alignment path).  K = members,
+ * 2 <= K <= 64.  An element e of image b has x_m = samples[b][m][e].  Double precision, every operation rounded to nearest on its
+ * own, no fused multiply-add.
+ *   invalid      an element with a member that is not finite (NaN, +-inf) is INVALID: it adds 1 to invalid[b] and nothing to the Gram
+ *                matrix, and its projected value is the canonical quiet NaN 0x7FC00000 in every mode.
+ *   centring     every other element, exactly mi_ensemble_reduce's mean, members in index order:
+ *                  s = 0; s += (double)x_m;  mean64 = s / K;      d_m = (double)x_m - mean64
+ *   Gram         G[i][j] = sum over the valid elements of d_i * d_j for i <= j: the product is rounded, then added.  G[j][i] = G[i][j].
+ *   sums         per image and entry (i, j), no atomics, in ONE order:
+ *                - the chw elements of an image are cut into chunks of 4096 consecutive elements (the last one may be partial);
+ *                - a chunk is 16 rounds of 256 elements; lane l = 0 .. 63 owns elements 256 r + 4 l .. 256 r + 4 l + 3 of round
+ *                  r = 0 .. 15 and adds its 64 products in increasing element order starting from 0; invalid and absent elements
+ *                  add nothing;
+ *                - the 64 lane sums are folded by the tree  for off = 32, 16, .., 1: v[l] += v[l + off]  for l < off;
+ *                - an image's chunk sums are added one by one, starting from 0, in chunk order.
+ *                (A chunk four times that of the scores: the tree runs over up to 2080 accumulators per chunk and is paid for by 64
+ *                elements a lane.)
+ *   projection   weights w[b][j][k], device doubles, j < M = n_modes, 1 <= M <= 8:
+ *                  a = 0; for k = 0 .. K-1: a += w[b][j][k] * d_k;      out[b][j][e] = (float)a
+ *                the product rounded, then added.  The weights are the caller's and should be finite.
+ * With mu_j, v_j the eigenpairs of G (v_j of unit length) and w[j][k] = v_j[k] / sqrt(K - 1), out[b][j] is mode j in image units:
+ * mean +- out[b][j] is a one-standard-deviation excursion along the j-th pattern, its variance is mu_j / (K - 1), and over all K - 1
+ * modes sum_j out[b][j]^2 is the unbiased per-pixel variance.  Eigenvectors of (nearly) equal eigenvalues are not unique: any
+ * rotation within their span is as good, so only the span of such modes is reproducible between solvers.
+ * Arguments
+ *   gram         device double [B][K][K], 8-byte aligned, written symmetric
+ *   invalid      device uint64 [B], 8-byte aligned; the call zeroes it itself, on the stream
+ *   workspace    mi_ensemble_gram_workspace_bytes, 8-byte aligned: the chunk sums of the upper triangle, double
+ *                [B][chunks][K (K + 1) / 2], and for K > 8 the double mean of every element, double [B][chw] (K <= 8: one launch
+ *                holds all members and computes the mean itself; above, the members are tiled in blocks of 8 and a pre-pass
+ *                stores the mean once).  The query answers 0 on sizes the call refuses
+ *   out          device fp32 [B][M][chw]
+ * The members are read as 16-byte words when chw is a multiple of 4 and samples (and out) are 16-byte aligned, element by element
+ * otherwise: the same bits either way.  Both calls allocate nothing, are asynchronous and need no plan.
+ * MI_EINVAL before any GPU work, the rule named in mi_last_error, judged in this order.  mi_ensemble_gram: B outside [1, 65535];
+ * members outside [2, 64]; chw outside [1, 2^32); a null samples, gram, invalid or workspace; gram, invalid or workspace not 8-byte
+ * aligned, samples not 4-byte aligned; workspace_bytes below the query's answer; gram, invalid or the workspace overlapping samples
+ * or each other.  mi_ensemble_project: B, members and chw as above; n_modes outside [1, 8]; a null samples, weights or out; weights
+ * not 8-byte aligned, samples or out not 4-byte aligned; any two of samples, weights and out overlapping. */
+size_t mi_ensemble_gram_workspace_bytes(int B, int members, int64_t chw);
+int mi_ensemble_gram(const float* samples, int B, int members, int64_t chw, double* gram, uint64_t* invalid,
+                     void* workspace, size_t workspace_bytes, void* stream);
+int mi_ensemble_project(const float* samples, int B, int members, int64_t chw, const double* weights, int n_modes,
+                        float* out, void* stream);
+
 /* NOISE POWER SPECTRUM (no plan needed): what does the remaining noise look like?  The per-pixel scores above say how large a
  * residual or an ensemble's spread is; the noise power spectrum (NPS) says at which spatial frequencies it lives.  Welch's method as
  * in IEC 62220-1: overlapping regions of interest (ROIs) are detrended, windowed, transformed, their periodograms averaged and the

@@ -16,5 +16,6 @@ from .sampler import (DiffusionDenoiser, EnsembleQuantileResult, EnsembleResult,
                       tile_blend_quantiles, tile_blend_reduce, tile_extract, tile_plan, view_codes,
                       TiledSelfEnsembleQuantileResult, TiledSelfEnsembleResult, tile_blend_unview_quantiles, tile_blend_unview_reduce,
                       view_codes_tiled, DenoisingLoss, LossMaps, LossProfile, loss_terms, noise_images, EnsembleScores,
-                      ensemble_scores, NoisePowerSpectrum, noise_power_spectrum, nps_window, CrossSpectrum, cross_spectrum)
+                      ensemble_scores, NoisePowerSpectrum, noise_power_spectrum, nps_window, CrossSpectrum, cross_spectrum,
+                      EnsembleModes, ensemble_modes)
 from .session import SamplerSession, Ticket  # noqa: F401

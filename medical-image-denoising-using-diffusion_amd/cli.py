@@ -35,7 +35,7 @@ from . import image16, prepost
 from .modules import UNetDiffusion
 from .recipe import ImageRecipe
 from .sampler import (DEFAULT_SCORE_LEVELS, MAX_QUANTILE_MEMBERS, NPS_ROIS, DiffusionDenoiser, check_levels, check_nps_args, check_update,
-                      cross_spectrum, ensemble_scores, noise_power_spectrum)
+                      check_modes, cross_spectrum, ensemble_modes, ensemble_scores, noise_power_spectrum)
 
 
 class Options(NamedTuple):
@@ -54,7 +54,7 @@ def check_options(device_type: str = "cuda", img_size: int = 512, variant: str =
                   std_out=None, tile=None, quantiles=None, quantiles_out=None, self_ensemble=None, update: str = "reference",
                   eta: float = 0.0, clip_x0: bool = True, x0_out=None, bit_depth: int = 8, window=None, window_levels=None, views=None,
                   members=None, clean=None, loss_out=None, truth=None, scores_out=None, nps_out=None, nps_roi=None, nps_step=None,
-                  fidelity_out=None, fidelity_roi=None, fidelity_step=None) -> Options:
+                  fidelity_out=None, fidelity_roi=None, fidelity_step=None, modes=None, modes_out=None, modes_json=None) -> Options:
     """The rules of denoise_image_diffusion's options (its docstring says what each option is), all of them and nowhere else: the
     function and main both call this.  Opens no file and touches no device; the two rules that compare an ROI with the image file
     itself follow the call in denoise_image_diffusion.  Raises ValueError, and RuntimeError for what runs only on a GPU."""
@@ -94,6 +94,14 @@ def check_options(device_type: str = "cuda", img_size: int = 512, variant: str =
             raise ValueError(f"--truth needs K <= {MAX_QUANTILE_MEMBERS} members: the scores kernel sorts a pixel's members in registers")
         if not on_gpu:
             raise RuntimeError("--truth (ensemble scores) runs only on a ROCm GPU: the scores kernel has no CPU fallback")
+    if modes is not None or modes_out is not None or modes_json is not None:
+        if modes is None or modes_out is None:
+            raise ValueError(f"--modes M and --modes-out PATH.npy come together{'' if modes_json is None else ', and --modes-json needs both'}")
+        if n_draws is None:
+            raise ValueError(f"--modes {modes} takes the principal modes of an ensemble: it needs --samples K, or --tile N --members K")
+        check_modes(modes, n_draws)
+        if not on_gpu:
+            raise RuntimeError(f"--modes {modes} (ensemble modes) runs only on a ROCm GPU: the Gram kernel has no CPU fallback")
     if clean is not None:
         for flag, given in (("--tile", tile), ("--samples", samples), ("--views", views), ("--members", members), ("--self-ensemble", self_ensemble)):
             if given is not None:
@@ -175,7 +183,8 @@ def denoise_image_diffusion(model_path: Optional[str], test_image_path: str, dev
                             members: Optional[int] = None, clean: Optional[str] = None, loss_out: Optional[str] = None,
                             truth: Optional[str] = None, scores_out: Optional[str] = None, nps_out: Optional[str] = None,
                             nps_roi: Optional[int] = None, nps_step: Optional[int] = None, fidelity_out: Optional[str] = None,
-                            fidelity_roi: Optional[int] = None, fidelity_step: Optional[int] = None) -> Image.Image:
+                            fidelity_roi: Optional[int] = None, fidelity_step: Optional[int] = None, modes: Optional[int] = None,
+                            modes_out: Optional[str] = None, modes_json: Optional[str] = None) -> Image.Image:
     """compute (not a reference argument): arithmetic of the network, see UNetDiffusion -- None keeps the default.
     seed (not a reference argument; cddpm): the stochastic sampler's noise is drawn on the device from this seed, so the same
     call gives the same image again (DiffusionDenoiser.denoise); None: torch.randn, as the reference.
@@ -237,13 +246,19 @@ def denoise_image_diffusion(model_path: Optional[str], test_image_path: str, dev
     and the Fourier ring correlation of Welch cross-spectra (sampler.cross_spectrum; plane detrend, Hann window, ROIs as for nps_out)
     and the frequency at which the FRC falls below 1/7: with truth, of (truth, output) and of (truth, noisy input); with an even
     K >= 2, between the draws 0, 2, .. and 1, 3, .., which needs no truth.  Refused with neither, and where the sampler's image is
-    smaller than the ROI.  The sampler run and the returned image are those of the call without fidelity_out."""
+    smaller than the ROI.  The sampler run and the returned image are those of the call without fidelity_out.
+    modes, modes_out, modes_json (not reference arguments; with samples, or with tile and members, 2 <= K <= 64; on a GPU only): WHAT
+    VARIES TOGETHER.  The modes leading principal modes of the draws (sampler.ensemble_modes; modes <= min(8, K - 1)) are written to
+    the .npy file modes_out, float32 [modes, 1, H, W] at the sampler's resolution, in window units under window: mean +- mode j is a
+    one-standard-deviation excursion along the j-th coherent pattern.  modes and modes_out come together; modes_json is the path of
+    a .json file that receives the variance along each mode, its explained share, every draw's coefficients and the valid element
+    count.  The sampler run and the returned image are those of the call without modes."""
     opt = check_options(device_type=device_type, img_size=img_size, variant=variant, step_noise=step_noise, seed=seed, samples=samples,
                         std_out=std_out, tile=tile, quantiles=quantiles, quantiles_out=quantiles_out, self_ensemble=self_ensemble,
                         update=update, eta=eta, clip_x0=clip_x0, x0_out=x0_out, bit_depth=bit_depth, window=window,
                         window_levels=window_levels, views=views, members=members, clean=clean, loss_out=loss_out, truth=truth,
                         scores_out=scores_out, nps_out=nps_out, nps_roi=nps_roi, nps_step=nps_step, fidelity_out=fidelity_out,
-                        fidelity_roi=fidelity_roi, fidelity_step=fidelity_step)
+                        fidelity_roi=fidelity_roi, fidelity_step=fidelity_step, modes=modes, modes_out=modes_out, modes_json=modes_json)
     rule, quantiles, recipe, tiled_ensemble = opt.rule, opt.quantiles, opt.recipe, opt.tiled_ensemble
     nps_roi, nps_step, fidelity_roi, fidelity_step = opt.nps_roi, opt.nps_step, opt.fidelity_roi, opt.fidelity_step
     for flag, out, roi in (("fidelity", fidelity_out, fidelity_roi), ("nps", nps_out, nps_roi)):
@@ -276,7 +291,7 @@ def denoise_image_diffusion(model_path: Optional[str], test_image_path: str, dev
             print("Window: grey levels {} .. {}".format(*win[0].tolist()))
         return Image.fromarray(recipe.store(image, source))
 
-    keep = truth is not None or nps_out is not None or fidelity_out is not None      # the members are needed after the run
+    keep = truth is not None or nps_out is not None or fidelity_out is not None or modes is not None      # the members are needed after the run
     truth_img = None
     if tile is not None:
         if min(img.size) < tile:
@@ -307,6 +322,8 @@ def denoise_image_diffusion(model_path: Optional[str], test_image_path: str, dev
             write_nps(nps_out, nps_roi, nps_step, input_tensor, image, res.samples if members is not None else None, truth_img, res.seed)
         if fidelity_out is not None:
             write_fidelity(fidelity_out, fidelity_roi, fidelity_step, input_tensor, image, res.samples, truth_img, res.seed)
+        if modes is not None:
+            write_modes(modes, modes_out, modes_json, res.samples, res.seed)
         if tiled_ensemble:      # the maps stay float, at the image's size
             if std_out is not None:
                 np.save(std_out, res.std[0, 0].cpu().numpy())
@@ -352,6 +369,8 @@ def denoise_image_diffusion(model_path: Optional[str], test_image_path: str, dev
                   ens.seed if samples is not None else seed)
     if fidelity_out is not None:
         write_fidelity(fidelity_out, fidelity_roi, fidelity_step, input_tensor, denoised, ens.samples, truth_img, ens.seed)
+    if modes is not None:
+        write_modes(modes, modes_out, modes_json, ens.samples, ens.seed)
     return restored(denoised)
 
 
@@ -389,6 +408,25 @@ def score(samples: torch.Tensor, truth: torch.Tensor, levels, seed, scores_out: 
         with open(scores_out, "w") as f:
             json.dump(result, f, indent=1)
         print(f"Scores saved: {scores_out}")
+    return result
+
+
+def write_modes(modes: int, modes_out: str, modes_json: Optional[str], samples: torch.Tensor, seed) -> dict:
+    """--modes: the leading principal modes of the ensemble `samples` [1, K, 1, H, W] (sampler.ensemble_modes), saved as float32
+    [modes, 1, H, W] in the sampler's units (window units under --window), their figures printed and, with modes_json, written as JSON."""
+    import json
+    pm = ensemble_modes(samples, modes)
+    np.save(modes_out, pm.modes[0].cpu().numpy())
+    result = {"members": int(samples.shape[1]), "modes": modes, "height": int(samples.shape[3]), "width": int(samples.shape[4]), "seed": seed,
+              "variance": pm.variance[0].tolist(), "explained": pm.explained[0].tolist(), "coefficients": pm.coefficients[0].tolist(),
+              "total_variance": float(pm.total_variance[0]), "valid": int(pm.valid[0])}
+    print(f"Principal modes of {result['members']} members ({result['valid']} valid elements): explained " +
+          ", ".join(f"{v:.4f}" for v in result["explained"]))
+    print(f"Modes saved: {modes_out}")
+    if modes_json is not None:
+        with open(modes_json, "w") as f:
+            json.dump(result, f, indent=1)
+        print(f"Mode figures saved: {modes_json}")
     return result
 
 
@@ -549,6 +587,13 @@ def main(argv=None) -> None:
                          "draws, which needs no truth")
     ap.add_argument("--fidelity-roi", type=int, default=None, metavar="R", help="with --fidelity-out: the ROI size, 32, 64 (default) or 128")
     ap.add_argument("--fidelity-step", type=int, default=None, metavar="S", help="with --fidelity-out: the ROI step (default R / 2)")
+    ap.add_argument("--modes", type=int, default=None, metavar="M",
+                    help="with --samples K, or --tile N --members K (2 <= K <= 64), and --modes-out: the M <= min(8, K - 1) leading principal "
+                         "modes of the draws, what varies together; mean +- a mode is a one-standard-deviation excursion along it")
+    ap.add_argument("--modes-out", default=None, metavar="PATH.npy",
+                    help="with --modes: the modes as float32 [M, 1, H, W] at the sampler's resolution (window units under --window)")
+    ap.add_argument("--modes-json", default=None, metavar="PATH.json",
+                    help="with --modes: write the variance along each mode, its explained share, the draws' coefficients and the valid count")
     args = ap.parse_args(argv)
     # the rules that are main's own: the text arguments and the ranges argv words; every other rule is check_options'
     for flag, roi, step in (("fidelity", args.fidelity_roi, args.fidelity_step), ("nps", args.nps_roi, args.nps_step)):
@@ -571,7 +616,8 @@ def main(argv=None) -> None:
                    update=args.update, eta=args.eta, clip_x0=not args.no_clip_x0, bit_depth=args.bit_depth)
     later = dict(x0_out=args.x0_out, window=None, window_levels=None, views=args.views, members=args.members, clean=args.clean,
                  loss_out=args.loss_out, truth=args.truth, scores_out=args.scores_out, nps_out=args.nps_out, nps_roi=args.nps_roi,
-                 nps_step=args.nps_step, fidelity_out=args.fidelity_out, fidelity_roi=args.fidelity_roi, fidelity_step=args.fidelity_step)
+                 nps_step=args.nps_step, fidelity_out=args.fidelity_out, fidelity_roi=args.fidelity_roi, fidelity_step=args.fidelity_step,
+                 modes=args.modes, modes_out=args.modes_out, modes_json=args.modes_json)
     try:
         if args.quantiles is not None:
             options["quantiles"] = check_levels([float(v) for v in args.quantiles.split(",")])

@@ -144,6 +144,56 @@ extern "C" int mi_ensemble_scores(const float* samples, const float* truth, int 
                                            (hipStream_t)stream), "ensemble_scores");
 }
 
+// The principal modes of an ensemble's spread (ensemble_modes.hip; include/midd.h: THE ENSEMBLE MODES): the Gram matrix of the
+// centred members and the projection onto the caller's weight rows.  The rules in the documented order
+static int check_modes_shape(int B, int members, int64_t chw) {
+    if (int rc = check_reduce_batch(B, "limit of the modes kernels' grid")) return rc;
+    if (members < 2 || members > MODES_MAX_MEMBERS)
+        return fail(MI_EINVAL, "members %d outside [2, %d]: one member has no spread, and the Gram kernel tiles at most %d members (limit: 2 <= members <= %d)",
+                    members, MODES_MAX_MEMBERS, MODES_MAX_MEMBERS, MODES_MAX_MEMBERS);
+    if (chw < 1 || chw >= MEMBER_WORDS) return fail(MI_EINVAL, "chw %lld outside [1, 2^32) (limit: C*H*W < 4294967296)", (long long)chw);
+    return MI_OK;
+}
+
+extern "C" size_t mi_ensemble_gram_workspace_bytes(int B, int members, int64_t chw) {
+    if (check_modes_shape(B, members, chw)) return 0;
+    return ensemble_gram_workspace_bytes(B, members, (unsigned long long)chw);
+}
+
+extern "C" int mi_ensemble_gram(const float* samples, int B, int members, int64_t chw, double* gram, uint64_t* invalid,
+                                void* workspace, size_t workspace_bytes, void* stream) {
+    if (int rc = check_modes_shape(B, members, chw)) return rc;
+    if (!samples || !gram || !invalid || !workspace) return fail(MI_EINVAL, "null argument");
+    for (const void* p : {(const void*)gram, (const void*)invalid, (const void*)workspace})
+        if (reinterpret_cast<uintptr_t>(p) & 7) return fail(MI_EINVAL, "gram, invalid and workspace must be 8-byte aligned");
+    if (reinterpret_cast<uintptr_t>(samples) & 3) return fail(MI_EINVAL, "samples must be 4-byte aligned");
+    const size_t need = ensemble_gram_workspace_bytes(B, members, (unsigned long long)chw);
+    if (workspace_bytes < need) return fail(MI_EINVAL, "workspace too small: need %zu bytes (mi_ensemble_gram_workspace_bytes), got %zu", need, workspace_bytes);
+    const Buf buf[4] = {{samples, (size_t)B * members * (size_t)chw * sizeof(float), "samples"},
+                        {gram, (size_t)B * members * members * sizeof(double), "gram"}, {invalid, (size_t)B * sizeof(uint64_t), "invalid"},
+                        {workspace, need, "workspace"}};
+    if (int rc = check_no_overlap(buf, 4, "samples is read while gram, invalid and the workspace are written")) return rc;
+    static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "the counters are 64-bit");
+    return launched(ensemble_gram_launch(samples, B, members, (unsigned long long)chw, gram, reinterpret_cast<unsigned long long*>(invalid),
+                                         static_cast<double*>(workspace), (hipStream_t)stream), "ensemble_gram");
+}
+
+extern "C" int mi_ensemble_project(const float* samples, int B, int members, int64_t chw, const double* weights, int n_modes, float* out, void* stream) {
+    if (int rc = check_modes_shape(B, members, chw)) return rc;
+    if (n_modes < 1 || n_modes > MODES_MAX_MODES)
+        return fail(MI_EINVAL, "n_modes %d outside [1, %d]: a projection launch holds at most %d accumulators per element (limit: 1 <= n_modes <= %d)",
+                    n_modes, MODES_MAX_MODES, MODES_MAX_MODES, MODES_MAX_MODES);
+    if (!samples || !weights || !out) return fail(MI_EINVAL, "null argument");
+    if (reinterpret_cast<uintptr_t>(weights) & 7) return fail(MI_EINVAL, "weights must be 8-byte aligned");
+    for (const void* p : {(const void*)samples, (const void*)out})
+        if (reinterpret_cast<uintptr_t>(p) & 3) return fail(MI_EINVAL, "samples and out must be 4-byte aligned");
+    const size_t img = (size_t)chw * sizeof(float);
+    const Buf buf[3] = {{samples, (size_t)B * members * img, "samples"}, {weights, (size_t)B * n_modes * members * sizeof(double), "weights"},
+                        {out, (size_t)B * n_modes * img, "out"}};
+    if (int rc = check_no_overlap(buf, 3, "samples and weights are read while out is written")) return rc;
+    return launched(ensemble_project_launch(samples, B, members, (unsigned long long)chw, weights, n_modes, out, (hipStream_t)stream), "ensemble_project");
+}
+
 // The noise power spectrum (nps.hip; include/midd.h: THE NOISE POWER SPECTRUM).  The rules in the documented order; nothing is read,
 // not even the host window, before every rule has passed
 static int check_nps_shape(int B, int K, int C, int H, int W, int roi, int step) {

@@ -399,6 +399,17 @@ hipError_t ensemble_scores_launch(const float* samples, const float* truth, int 
                                   double* sums, unsigned long long* invalid, unsigned long long* rank_hist, unsigned long long* counts,
                                   float* crps_map, double* part, hipStream_t s);
 
+// Principal modes of an ensemble's spread (ensemble_modes.hip; include/midd.h: THE ENSEMBLE MODES).  samples [B][K][chw] -> gram
+// double [B][K][K], symmetric, and invalid [B] (zeroed on the stream); ws: ensemble_gram_workspace_bytes (the chunk sums of the
+// packed upper triangle and, for K > 8, the double means).  weights double [B][M][K] on the device -> out [B][M][chw].  B <= 65535,
+// 2 <= K <= 64, 1 <= M <= 8
+constexpr int MODES_MAX_MEMBERS = 64, MODES_MAX_MODES = 8;
+unsigned long long ensemble_gram_chunks(unsigned long long chw);
+size_t ensemble_gram_workspace_bytes(int B, int K, unsigned long long chw);
+hipError_t ensemble_gram_launch(const float* samples, int B, int K, unsigned long long chw, double* gram, unsigned long long* invalid,
+                                double* ws, hipStream_t s);
+hipError_t ensemble_project_launch(const float* samples, int B, int K, unsigned long long chw, const double* weights, int M, float* out, hipStream_t s);
+
 // The noise power spectrum of f = a - b (nps.hip; include/midd.h: THE NOISE POWER SPECTRUM).  a [B][K][C][H][W], b [B][C][H][W] or
 // null; R in {32, 64, 128}, S >= 1, detrend 0 none / 1 mean / 2 plane, window a HOST table of R floats or null -> nps double
 // [B*C][R][R], radial double [B*C][R/2+1], radial_count [R/2+1], rois_used and rois_skipped [B*C]; ws: nps_workspace_bytes (the chunk

@@ -1,6 +1,6 @@
-"""The ensemble operators: the seeded step noise as a tensor, mean / std, quantile maps and proper scores over the members of an
-ensemble (include/midd.h: mi_step_noise_fill_member, mi_ensemble_reduce, mi_ensemble_quantiles, THE ENSEMBLE SCORES), and what
-``DiffusionDenoiser.denoise_ensemble`` returns."""
+"""The ensemble operators: the seeded step noise as a tensor, mean / std, quantile maps, proper scores and principal modes over the
+members of an ensemble (include/midd.h: mi_step_noise_fill_member, mi_ensemble_reduce, mi_ensemble_quantiles, THE ENSEMBLE SCORES,
+THE ENSEMBLE MODES), and what ``DiffusionDenoiser.denoise_ensemble`` returns."""
 from __future__ import annotations
 
 import ctypes as C
@@ -169,3 +169,95 @@ def ensemble_scores(samples: torch.Tensor, truth: torch.Tensor, quantiles=DEFAUL
     f64 = lambda v: torch.tensor(v, dtype=torch.float64)
     return EnsembleScores(f64(crps), f64(fair), f64(rmse), f64(spread), rank_hist, counts[:, :, 0].clone(), counts[:, :, 1].clone(), levels,
                           valid.clone(), sums, cmap)
+
+
+MAX_MODES, MAX_MODE_MEMBERS = 8, 64
+
+
+class EnsembleModes(NamedTuple):
+    """What ``ensemble_modes`` returns (include/midd.h: THE ENSEMBLE MODES).  Only ``modes`` lives on the device; the rest are float64
+    (``valid``: int64) CPU tensors.  Modes of (nearly) equal ``variance`` are not unique: any rotation within their span is as good."""
+    modes: torch.Tensor                   # float32 [B, M, C, H, W] on the device: mode j in image units; mean +- modes[:, j] is one std along it
+    variance: torch.Tensor                # [B, M]: the variance along mode j, mu_j / (K - 1), descending
+    explained: torch.Tensor               # [B, M]: its share of the total, mu_j / sum(mu)
+    coefficients: torch.Tensor            # [B, K, M]: member k's position along mode j in standard deviations, v_j[k] * sqrt(K - 1)
+    gram: torch.Tensor                    # [B, K, K]: the raw Gram matrix of the centred members
+    total_variance: torch.Tensor          # [B]: sum(mu) / (K - 1), the unbiased member variance summed over the valid elements
+    valid: torch.Tensor                   # int64 [B]: the elements whose members are all finite; the others are NaN in every mode
+
+
+def check_modes(modes, members: int) -> int:
+    """The ``modes`` argument of ``ensemble_modes`` beside the member count: an int in [1, min(8, members - 1)], members in [2, 64]."""
+    if isinstance(members, bool) or not isinstance(members, int) or not 2 <= members <= MAX_MODE_MEMBERS:
+        raise ValueError(f"ensemble_modes needs 2 <= members <= {MAX_MODE_MEMBERS} (got {members}): one member has no spread, and the Gram "
+                         "kernel tiles at most 64 members")
+    if isinstance(modes, bool) or not isinstance(modes, int) or not 1 <= modes <= min(MAX_MODES, members - 1):
+        raise ValueError(f"modes must be an int in [1, min({MAX_MODES}, members - 1)] = [1, {min(MAX_MODES, members - 1)}] (got {modes!r}): "
+                         f"{members} centred members span at most {members - 1} modes")
+    return modes
+
+
+def gram_eigen(gram, modes: int, eigh=None):
+    """The host step of ``ensemble_modes`` in float64 numpy: ``gram`` [B, K, K] -> (mu [B, K], v [B, K, K], weights [B, modes, K]).
+    ``numpy.linalg.eigh``; eigenvalues clipped at 0 and sorted descending; each eigenvector (column ``v[b, :, j]``) signed so that
+    its component of largest magnitude -- the first of them on ties -- is positive; weights[b, j, k] = v[b, k, j] / sqrt(K - 1)."""
+    import numpy as np
+    g = np.asarray(gram, dtype=np.float64)
+    K = g.shape[-1]
+    mu, v = (eigh or np.linalg.eigh)(g)
+    mu = np.clip(mu, 0.0, None)[:, ::-1]
+    v = v[:, :, ::-1]
+    lead = np.argmax(np.abs(v), axis=1)                                     # [B, K]: the first component of largest magnitude
+    sign = np.where(np.take_along_axis(v, lead[:, None, :], axis=1) < 0.0, -1.0, 1.0)
+    v = np.ascontiguousarray(v * sign)
+    weights = np.ascontiguousarray(np.swapaxes(v[:, :, :modes], 1, 2) / np.sqrt(np.float64(K - 1)))
+    return np.ascontiguousarray(mu), v, weights
+
+
+@torch.no_grad()
+def ensemble_modes(samples: torch.Tensor, modes: int = 3) -> EnsembleModes:
+    """The principal modes of an ensemble's spread: what varies together (mi_ensemble_gram, mi_ensemble_project; include/midd.h:
+    THE ENSEMBLE MODES).  ``samples`` is [B, K, C, H, W] or [K, C, H, W] (then every output lacks the batch axis), float32 on the GPU,
+    2 <= K <= 64; ``modes`` <= min(8, K - 1).  The K x K Gram matrix of the centred members is reduced on the device, its
+    eigenproblem solved on the host in float64 (``gram_eigen``), and the centred members are projected onto the scaled leading
+    eigenvectors in one launch: ``modes[:, j]`` is the j-th coherent pattern in grey-level units, so that mean +- mode is a
+    one-standard-deviation excursion along it, and with all K - 1 modes the squares add up to the per-pixel variance.  Channels
+    are pooled.  An element with a member that is not finite is left out, counted (``valid``) and NaN in every mode.  Modes that
+    belong to (nearly) equal eigenvalues are not unique: only their span is.  The Gram matrix is copied to the host (that waits
+    for the stream); the members never are."""
+    import numpy as np
+    if not isinstance(samples, torch.Tensor) or samples.dim() not in (4, 5) or min(samples.shape) < 1:
+        raise ValueError("samples must be a [B, members, C, H, W] or [members, C, H, W] tensor without an empty axis")
+    batched = samples.dim() == 5
+    src = samples if batched else samples.unsqueeze(0)
+    B, K = int(src.shape[0]), int(src.shape[1])
+    M = check_modes(modes, K)
+    if src.device.type != "cuda":
+        raise RuntimeError(f"ensemble_modes runs only on a ROCm GPU (got {src.device}): there is no CPU fallback")
+    if src.dtype != torch.float32:
+        raise TypeError(f"samples must be float32 (got {src.dtype})")
+    src = src.contiguous()
+    chw = src[0, 0].numel()
+    lib = native.lib()
+    dev = src.device
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        raw = torch.empty(B * (K * K + 1), dtype=torch.int64, device=dev)       # [gram B*K*K | invalid B]: one copy to the host
+        nbytes = lib.mi_ensemble_gram_workspace_bytes(B, K, chw)
+        if nbytes == 0:
+            native.check(-1)
+        ws = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
+        native.check(lib.mi_ensemble_gram(src.data_ptr(), B, K, chw, raw.data_ptr(), raw.data_ptr() + 8 * B * K * K, ws.data_ptr(), nbytes, stream))
+        host = raw.cpu()
+        gram = host[:B * K * K].view(torch.float64).reshape(B, K, K).clone()
+        valid = chw - host[B * K * K:]
+        mu, v, weights = gram_eigen(gram.numpy(), M)
+        w_dev = torch.from_numpy(weights).to(dev)
+        out = torch.empty((B, M) + tuple(src.shape[2:]), dtype=torch.float32, device=dev)
+        native.check(lib.mi_ensemble_project(src.data_ptr(), B, K, chw, w_dev.data_ptr(), M, out.data_ptr(), stream))
+    total = mu.sum(axis=1)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        explained = mu[:, :M] / total[:, None]
+    fields = (out, torch.from_numpy(mu[:, :M] / (K - 1)), torch.from_numpy(explained),
+              torch.from_numpy(np.ascontiguousarray(v[:, :, :M] * np.sqrt(np.float64(K - 1)))), gram, torch.from_numpy(total / (K - 1)), valid.clone())
+    return EnsembleModes(*(fields if batched else (t[0] for t in fields)))

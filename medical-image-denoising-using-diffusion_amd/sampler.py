@@ -18,8 +18,8 @@ import torch
 
 from . import native
 from .config import timestep_list
-from .ensemble import (DEFAULT_SCORE_LEVELS, EnsembleQuantileResult, EnsembleResult, EnsembleScores, ensemble_quantiles,  # noqa: F401
-                       ensemble_reduce, ensemble_scores, step_noise)
+from .ensemble import (DEFAULT_SCORE_LEVELS, EnsembleModes, EnsembleQuantileResult, EnsembleResult, EnsembleScores, check_modes,  # noqa: F401
+                       ensemble_modes, ensemble_quantiles, ensemble_reduce, ensemble_scores, gram_eigen, step_noise)
 from .loss import (DenoisingLoss, LossMaps, LossProfile, _loss_tensor, check_loss_source, loss_counter_args, loss_table_args,  # noqa: F401
                    loss_terms, noise_images)
 from .nps import NoisePowerSpectrum, noise_power_spectrum, nps_window  # noqa: F401
@@ -422,6 +422,19 @@ class DiffusionDenoiser:
         result = self._ensemble_with_samples(noisy, tile, overlap, inference_steps=inference_steps, members=members, seed=seed,
                                              sample_offset=sample_offset, member_offset=member_offset, max_batch=max_batch)
         return result, noise_power_spectrum(result.samples, result.mean, roi, step, detrend, window, members / (members - 1), exclude_axes)
+
+    @torch.no_grad()
+    def ensemble_modes(self, noisy: torch.Tensor, inference_steps: int = 25, members: int = 16, modes: int = 3, seed: Optional[int] = None,
+                       sample_offset: int = 0, member_offset: int = 0, max_batch: int = 16, tile=None, overlap=32):
+        """An ensemble of ``noisy`` and the principal modes of its spread -> ``(result, modes)``: ``denoise_ensemble(noisy, ...,
+        return_samples=True)`` -- or, with ``tile``, ``denoise_tiled_ensemble(noisy, ..., tile=tile, overlap=overlap,
+        return_samples=True)`` -- followed by ``ensemble_modes(result.samples, modes)``, bit for bit that composition.  The std map
+        says how much each pixel varies between members; ``modes.modes`` says what varies together: mean +- mode j is a
+        one-standard-deviation excursion along the j-th coherent pattern.  2 <= members <= 64, modes <= min(8, members - 1)."""
+        check_modes(modes, check_member(members, "members", low=1))
+        result = self._ensemble_with_samples(noisy, tile, overlap, inference_steps=inference_steps, members=members, seed=seed,
+                                             sample_offset=sample_offset, member_offset=member_offset, max_batch=max_batch)
+        return result, ensemble_modes(result.samples, modes)
 
     @torch.no_grad()
     def spectral_fidelity(self, clean: torch.Tensor, noisy: torch.Tensor, inference_steps: int = 25, members: Optional[int] = None,
