@@ -40,7 +40,18 @@ extern "C" {
 #define MI_ERANGE       -5   /* mi_status: the last call met values outside what its arithmetic represents */
 
 /* bits of the status word (mi_status) */
-#define MI_STATUS_NONFINITE   1   /* NaN / Inf activations reached a GroupNorm statistic or a raw conv operand */
+#define MI_STATUS_NONFINITE   1   /* NaN / Inf activations reached a GroupNorm statistic or a raw conv operand -- or FINITE ones
+                                   * beyond the statistics range.  SUPPORTED ACTIVATION RANGE: the GroupNorm totals are fixed point
+                                   * with range +-2^59 (csrc/stats_common.h), and a producer workgroup's fp32 partial sum of squares
+                                   * of one channel of one sample that reaches 2^59 counts as not a number: the group is NaN in the
+                                   * output and the call reports MI_ERANGE with this bit.  A workgroup covers between one tile (16 ..
+                                   * 128 pixels) and one sample's whole map, so
+                                   *   never reported:   rms of every channel of every activation map < 2^29.5 / sqrt(H * W) of that map
+                                   *                     (2.4e7 at 24 x 40, 3.0e6 at 256 x 256, 1.5e6 at 512 x 512),
+                                   *   always reported:  any |activation| >= 2^29.5 = 7.6e8,
+                                   * and between the two it depends on the launch's tiles.  Below, partials under 2^-37 lose low bits
+                                   * and nothing else.  fp32 torch has no such limit: the reference is finite and right until fp32
+                                   * itself overflows (squares of 1.8e19). */
 #define MI_STATUS_FP16_RANGE  2   /* fp16-MFMA modes (f16x3, f16): an attention operand (q, k, v) beyond +-4094 */
 
 #define MI_MAX_LEVELS    8

@@ -152,7 +152,7 @@ void conv_mfma_f32_kernel(const ConvArgs a) {
     for (int nt = 0; nt < NT; ++nt) wcur[nt] = wp[nt * 64];
 
     if (a.prologue != PRO_RAW) {
-        gn_prologue_lds(a.gn_tot0, a.C0, a.gn_bs0, a.gn_tot1, a.C1, a.gn_bs1, a.stat_rep, a.gn_gamma, a.gn_beta, a.gn_eps, a.gn_inv_n, b, 1.0f, gnp, tid, NTHREADS);
+        gn_prologue_lds(a.gn_tot0, a.C0, a.gn_bs0, a.gn_tot1, a.C1, a.gn_bs1, a.stat_rep, a.gn_gamma, a.gn_beta, a.gn_eps, a.gn_inv_n, b, 1.0f, gnp, tid, NTHREADS, a.status);
         __syncthreads();
     }
     stage_load(0);

@@ -246,8 +246,11 @@ extern "C" int mi_status(const void* workspace, void* stream, int* flags) {
     // the range flag first: an operand beyond fp16 turns into Inf / NaN downstream, so both bits are usually set then
     if (host & MI_STATUS_FP16_RANGE)
         return fail(MI_ERANGE, "an attention operand exceeds the split-fp16 range (|q|, |k| or |v| >= 4094, or not finite): use compute=\"f32\"%s",
-                    (host & MI_STATUS_NONFINITE) ? "; non-finite values reached later statistics" : "");
-    if (host & MI_STATUS_NONFINITE) return fail(MI_ERANGE, "non-finite activations (NaN / Inf) reached a GroupNorm statistic or a raw operand");
+                    (host & MI_STATUS_NONFINITE) ? "; non-finite values, or finite ones beyond the statistics range, reached GroupNorm statistics" : "");
+    // (the same bit for both: a finite partial sum of squares >= 2^59 adds the sentinel an Inf / NaN partial adds, stats_common.h)
+    if (host & MI_STATUS_NONFINITE)
+        return fail(MI_ERANGE, "non-finite activations (NaN / Inf), or finite ones beyond the statistics range (a workgroup's sum of squares of one "
+                               "channel >= 2^59; midd.h: MI_STATUS_NONFINITE), reached a GroupNorm statistic or a raw operand");
     return MI_OK;
 }
 
