@@ -1,21 +1,14 @@
 // The Welch cross-spectrum of two fields x and y (include/midd.h: THE CROSS SPECTRUM; tests/cross_spectrum_reference.py restates it
-// in numpy).  ROIs, detrend, window, butterflies, summation order and radial bins are those of nps.hip (nps_common.h); here ONE
-// complex transform per ROI carries both fields, z = (dx, dy), and four double spectra follow from Z[v][u] and Z[-v][-u].
-//   xs_roi_kernel<R>       a workgroup of T = 256 lanes (512 at R = 128, where four accumulators per entry and two fields' quads at
-//                          256 lanes would pass the register file) walks one chunk of NPS_CHUNK = 16 ROIs.  Per ROI: both fields'
-//                          row quads are loaded (16-byte or element loads, judged per field: the same bits), a non-finite value in
-//                          either marks the ROI skipped; with a detrend (x, y) go to the plane in natural order, lanes 0 .. R-1 add
-//                          the rows of x while lanes R .. 2R-1 add those of y, and lanes 0 and 64 form the two sets of
-//                          coefficients, behind the same barriers; every element pair is detrended in double, rounded once, windowed
-//                          and written as (dx, dy) at [bitrev(y)][bitrev(x)].  log2 R stages over all R rows, then over all R
-//                          columns (the rows of a complex field are not Hermitian).  The lane owns the half-plane entries
-//                          (XsGeom), reads Z1 = Z[v][u] and Z2 = Z[(R-v)%R][(R-u)%R] and adds Sxx, Syy, Re Sxy, Im Sxy to
-//                          its double accumulators.  At R = 128 the quads are not kept across the detrend sums but loaded again,
-//                          four per field at a time.  LDS as nps_roi_kernel<R> with two sets of row sums.
-//   xs_sum_kernel<R>       one lane per (quantity, half-plane entry): the chunk sums one by one in chunk order, the division, the
-//                          entry and its mirror (Im Sxy with the opposite sign)
-//   nps_radial_kernel<R>   (nps_common.h) once per quantity
-// Contraction is off for the whole unit.
+// in numpy).  The stages are those of nps_common.h; here ONE complex transform per ROI carries both fields, z = (dx, dy), and four
+// double spectra follow from Z[v][u] and Z[-v][-u].  What is this unit's:
+//   xs_roi_kernel<R>   T = 256 lanes (512 at R = 128, where four accumulators per entry and two fields' quads at 256 lanes would pass
+//                      the register file).  A non-finite value in either field skips the ROI; lanes 0 .. R-1 add the rows of x while
+//                      lanes R .. 2R-1 add those of y, lanes 0 and 64 form the two sets of coefficients, behind the same barriers.
+//                      The column pass covers all R columns (the rows of a complex field are not Hermitian).  The lane owns the
+//                      half-plane entries of XsGeom, reads Z1 = Z[v][u] and Z2 = Z[(R-v)%R][(R-u)%R] and adds Sxx, Syy, Re Sxy,
+//                      Im Sxy.  At R = 128 the quads are not kept across the detrend sums but loaded again, four per field at a time
+//   xs_sum_kernel<R>   one lane per (quantity, entry): 32 loads in flight, the division, the mirror (Im Sxy with the opposite sign)
+//   nps_radial_kernel<R>   once per quantity
 #include <cmath>
 #include "nps_common.h"
 
@@ -64,20 +57,15 @@ void xs_roi_kernel(const float* __restrict__ x, const float* __restrict__ y, int
 #pragma unroll
     for (int e = 0; e < NACC; ++e) { axx[e] = 0.0; ayy[e] = 0.0; are[e] = 0.0; aim[e] = 0.0; }
     long long n_used = 0;
-    const unsigned long long r0 = (unsigned long long)chunk * NPS_CHUNK;
-    const unsigned long long r1 = r0 + NPS_CHUNK < n_rois ? r0 + NPS_CHUNK : n_rois;
-    const unsigned per_member = (unsigned)ny * (unsigned)nx;            // (< 2^31: xs_launch)
-    size_t m = r0 / per_member;
-    unsigned rem = (unsigned)(r0 % per_member);
+    NpsWalk w = nps_walk(chunk, n_rois, ny, nx);
 #pragma unroll 1
-    for (unsigned long long r = r0; r < r1; ++r, ++rem) {
-        if (rem == per_member) { rem = 0; ++m; }
-        const size_t oy = (size_t)(rem / (unsigned)nx) * S, ox = (size_t)(rem % (unsigned)nx) * S;
-        const float* px = x + ((bi * Kx + m * sx) * C + c) * plane + oy * W + ox;
-        const float* py = y + ((bi * Ky + m * sy) * C + c) * plane + oy * W + ox;
+    for (unsigned long long r = w.r0; r < w.r1; ++r, ++w.rem) {
+        size_t oy, ox;
+        nps_walk_roi(w, nx, S, oy, ox);
+        const float* px = x + ((bi * Kx + w.m * sx) * C + c) * plane + oy * W + ox;
+        const float* py = y + ((bi * Ky + w.m * sy) * C + c) * plane + oy * W + ox;
         if (tid == 0) bad = 0;
         __syncthreads();
-        // every row quad of the ROI is 16-byte aligned when W is a multiple of 4 and the ROI's first element is aligned
         const bool wide = (W & 3) == 0;
         const bool widex = wide && nps_aligned16(px), widey = wide && nps_aligned16(py);
         // batch e0 of a lane's quads, NB per field.  KEEP: one batch, which stays in registers until it is detrended; otherwise the
@@ -135,7 +123,7 @@ void xs_roi_kernel(const float* __restrict__ x, const float* __restrict__ y, int
                     tx = add_rn64(tx, rs1[f][yy]);
                     ty = add_rn64(ty, mul_rn64((double)yy - 0.5 * (R - 1), rs0[f][yy]));
                 }
-                const double den = (double)R * ((double)R * ((double)R * R - 1.0) / 12.0);      // exact integers
+                const double den = NPS_SLOPE_DEN<R>;
                 coef[f][0] = __ddiv_rn(t0, (double)(R * R));
                 coef[f][1] = detrend == 2 ? __ddiv_rn(tx, den) : 0.0;
                 coef[f][2] = detrend == 2 ? __ddiv_rn(ty, den) : 0.0;
@@ -174,7 +162,7 @@ void xs_roi_kernel(const float* __restrict__ x, const float* __restrict__ y, int
             }
         }
         __syncthreads();
-        // the rows: consecutive lanes take consecutive ROWS (pitch R + 1) and share the butterfly index: the twiddle is one broadcast
+        // the rows
 #pragma unroll 1
         for (int s = 1; s <= LOG; ++s) {
             const int half = 1 << (s - 1);
@@ -244,7 +232,7 @@ __global__ __launch_bounds__(XS_SUM_THREADS)
 void xs_sum_kernel(const double* __restrict__ part, const long long* __restrict__ used, unsigned chunks, unsigned long long n_rois,
                    double sw, double* __restrict__ planes, long long* __restrict__ rois_used, long long* __restrict__ rois_skipped) {
     using G = NpsGeom<R>;
-    constexpr int NC = G::NC, HALF = G::HALF;
+    constexpr int HALF = G::HALF;
     const size_t g = blockIdx.y, groups = gridDim.y, qty = blockIdx.z;
     const int idx = blockIdx.x * XS_SUM_THREADS + threadIdx.x;
     long long n = 0;
@@ -254,24 +242,10 @@ void xs_sum_kernel(const double* __restrict__ part, const long long* __restrict_
     for (int off = 32; off > 0; off >>= 1) n += __shfl_xor(n, off);
     if (idx == 0 && qty == 0) { rois_used[g] = n; rois_skipped[g] = (long long)n_rois - n; }
     if (idx >= HALF) return;
-    const double* p = part + (g * chunks * 4 + qty) * (size_t)HALF + idx;
-    const size_t pitch = (size_t)4 * HALF;
-    double s = 0.0;
-    unsigned c = 0;
-    for (; c + XS_SUM_BATCH <= chunks; c += XS_SUM_BATCH) {
-        double v[XS_SUM_BATCH];
-#pragma unroll
-        for (int j = 0; j < XS_SUM_BATCH; ++j) v[j] = p[(size_t)(c + j) * pitch];
-#pragma unroll
-        for (int j = 0; j < XS_SUM_BATCH; ++j) s = add_rn64(s, v[j]);
-    }
-    for (; c < chunks; ++c) s = add_rn64(s, p[(size_t)c * pitch]);
+    const double s = nps_chunk_sum<XS_SUM_BATCH, (size_t)4 * HALF>(part + (g * chunks * 4 + qty) * (size_t)HALF + idx, chunks);
     const double qnan = __longlong_as_double((long long)NPS_QNAN);
     const double val = n > 0 ? __ddiv_rn(s, mul_rn64((double)n, sw)) : qnan;
-    const int v = idx / NC, u = idx % NC;
-    double* out = planes + (qty * groups + g) * (size_t)(R * R);
-    out[v * R + u] = val;
-    if (u > 0 && u < R / 2) out[((R - v) % R) * R + (R - u)] = (qty == 3 && n > 0) ? -val : val;     // Sxy(-f) = conj Sxy(f)
+    nps_store_mirrored<R>(planes, qty, groups, g, idx, val, (qty == 3 && n > 0) ? -val : val);      // Sxy(-f) = conj Sxy(f)
 }
 
 // ---------------------------------------------------------------------------------------------------------------- launches
@@ -279,49 +253,37 @@ size_t xs_workspace_bytes(int groups, int K, int H, int W, int R, int S) {
     return (size_t)groups * nps_chunks(K, H, W, R, S) * (4 * (size_t)R * (R / 2 + 1) + 1) * sizeof(double);
 }
 
-template <int R>
-static hipError_t xs_dispatch(const float* x, const float* y, int B, int Kx, int Ky, int C, int H, int W, int S, int detrend, int windowed,
-                              const NpsTables& tab, double sw, int exclude_axes, double* planes, double* radial, long long* radial_count,
-                              long long* rois_used, long long* rois_skipped, void* ws, hipStream_t s) {
-    using G = NpsGeom<R>;
-    const int groups = B * C, ny = (H - R) / S + 1, nx = (W - R) / S + 1, K = Kx > Ky ? Kx : Ky;
-    const unsigned long long n_rois = (unsigned long long)K * (unsigned long long)ny * (unsigned long long)nx;
-    const unsigned chunks = (unsigned)nps_chunks(K, H, W, R, S);
-    double* part = static_cast<double*>(ws);
-    long long* used = reinterpret_cast<long long*>(part + (size_t)groups * chunks * 4 * G::HALF);
-    hipLaunchKernelGGL((xs_roi_kernel<R>), dim3(chunks, groups), dim3(XsGeom<R>::T), 0, s, x, y, Kx, Ky, C, H, W, S, ny, nx, n_rois, detrend, windowed,
-                       tab, part, used);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((xs_sum_kernel<R>), dim3((G::HALF + XS_SUM_THREADS - 1) / XS_SUM_THREADS, groups, 4), dim3(XS_SUM_THREADS), 0, s, part, used,
-                       chunks, n_rois, sw, planes, rois_used, rois_skipped);
-    e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    for (int q = 0; q < 4; ++q) {
-        hipLaunchKernelGGL((nps_radial_kernel<R>), dim3((R / 2 + 1 + 3) / 4, groups), dim3(NPS_THREADS), 0, s, planes + (size_t)q * groups * R * R,
-                           rois_used, exclude_axes, radial + (size_t)q * groups * (R / 2 + 1), radial_count);
-        e = hipGetLastError();
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
-}
-
+// (every argument has been judged by the entry, mi_cross_spectrum, with a message)
 hipError_t xs_launch(const float* x, const float* y, int B, int Kx, int Ky, int C, int H, int W, int R, int S, int detrend, const float* window,
                      int exclude_axes, double* planes, double* radial, long long* radial_count, long long* rois_used, long long* rois_skipped,
                      void* ws, hipStream_t s) {
-    const int K = Kx > Ky ? Kx : Ky;
-    if ((R != 32 && R != 64 && R != 128) || S < 1 || B < 1 || Kx < 1 || Ky < 1 || (Kx != K && Kx != 1) || (Ky != K && Ky != 1) || C < 1 || H < R ||
-        W < R || (long long)B * C > 65535 || detrend < 0 || detrend > 2 ||
-        (unsigned long long)((H - R) / S + 1) * (unsigned long long)((W - R) / S + 1) > 0x7FFFFFFFull || !x || !y || !planes || !radial ||
-        !radial_count || !rois_used || !rois_skipped || !ws || nps_chunks(K, H, W, R, S) > 0x7FFFFFFFull)
-        return hipErrorInvalidValue;
     NpsTables tab{};
     double sw;
     nps_tables(R, window, &tab, &sw);
-    const int windowed = window ? 1 : 0;
-    if (R == 32) return xs_dispatch<32>(x, y, B, Kx, Ky, C, H, W, S, detrend, windowed, tab, sw, exclude_axes, planes, radial, radial_count, rois_used, rois_skipped, ws, s);
-    if (R == 64) return xs_dispatch<64>(x, y, B, Kx, Ky, C, H, W, S, detrend, windowed, tab, sw, exclude_axes, planes, radial, radial_count, rois_used, rois_skipped, ws, s);
-    return xs_dispatch<128>(x, y, B, Kx, Ky, C, H, W, S, detrend, windowed, tab, sw, exclude_axes, planes, radial, radial_count, rois_used, rois_skipped, ws, s);
+    const int groups = B * C, windowed = window ? 1 : 0;
+    const NpsCounts n = nps_counts(Kx > Ky ? Kx : Ky, H, W, R, S);
+    const unsigned chunks = (unsigned)n.chunks;
+    double* part = static_cast<double*>(ws);
+    return nps_for_roi_size(R, [&](auto size) {
+        constexpr int N = decltype(size)::value;
+        using G = NpsGeom<N>;
+        long long* used = reinterpret_cast<long long*>(part + (size_t)groups * chunks * 4 * G::HALF);
+        hipLaunchKernelGGL((xs_roi_kernel<N>), dim3(chunks, groups), dim3(XsGeom<N>::T), 0, s, x, y, Kx, Ky, C, H, W, S, n.ny, n.nx, n.n_rois, detrend,
+                           windowed, tab, part, used);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL((xs_sum_kernel<N>), dim3((G::HALF + XS_SUM_THREADS - 1) / XS_SUM_THREADS, groups, 4), dim3(XS_SUM_THREADS), 0, s, part,
+                           used, chunks, n.n_rois, sw, planes, rois_used, rois_skipped);
+        e = hipGetLastError();
+        if (e != hipSuccess) return e;
+        for (int q = 0; q < 4; ++q) {
+            hipLaunchKernelGGL((nps_radial_kernel<N>), dim3((N / 2 + 1 + 3) / 4, groups), dim3(NPS_THREADS), 0, s, planes + (size_t)q * groups * N * N,
+                               rois_used, exclude_axes, radial + (size_t)q * groups * (N / 2 + 1), radial_count);
+            e = hipGetLastError();
+            if (e != hipSuccess) return e;
+        }
+        return hipSuccess;
+    });
 }
 
 }  // namespace midd

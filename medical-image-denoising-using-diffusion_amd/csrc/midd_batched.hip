@@ -1,27 +1,11 @@
 // The batched sampler calls (virtual samples in passes: ensembles, tiles, tiled ensembles, flip / rotate views), their member /
-// tile / view argument rules, and the stand-alone reduce, quantile, tile and dihedral calls they compose.
+// tile / view argument rules, and the stand-alone tile and dihedral calls they compose (reduce and quantiles: midd_analysis.hip).
 #include "midd_sampler.h"
 #include "tile_geometry.h"
 
 using namespace midd;
 
 // ---------------------------------------------------------------------------- ensembles of the stochastic sampler
-constexpr int64_t MEMBER_WORDS = (int64_t)1 << 32;      // the member index is one 32-bit counter word
-
-static int check_members_min(int members) {
-    return members >= 1 ? MI_OK : fail(MI_EINVAL, "members %d: an ensemble has at least one member (limit: members >= 1)", members);
-}
-
-static int check_std_members(const float* std_out, int members) {
-    if (std_out && members < 2) return fail(MI_EINVAL, "std_out needs members >= 2: the unbiased standard deviation of one value is undefined");
-    return MI_OK;
-}
-
-// B is grid.y of the reduce kernel
-static int check_reduce_batch(int B, const char* why = "limit of the reduce kernel's grid") {
-    return (B >= 1 && B <= 65535) ? MI_OK : fail(MI_EINVAL, "B %d outside [1, 65535] (%s)", B, why);
-}
-
 static int check_members(int members, int64_t member_offset) {
     if (int rc = check_members_min(members)) return rc;
     if (member_offset < 0) return fail(MI_EINVAL, "member_offset %lld is negative: member indices start at 0", (long long)member_offset);
@@ -45,248 +29,6 @@ int midd::check_ensemble_args(mi_plan* plan, int B, int members, int H, int W, i
     if (pass_samples < 1) return fail(MI_EINVAL, "pass_samples %d: a pass holds at least one virtual sample (limit: pass_samples >= 1)", pass_samples);
     if (int rc = check_ensemble_size(B, members)) return rc;
     return check_step_noise_range(plan->cfg.in_channels, H, W, sample_offset);
-}
-
-// what the two stand-alone ensemble calls open with: the members, the batch, the elements of a sample
-static int check_ensemble_run(int B, int members, int64_t chw) {
-    if (int rc = check_members_min(members)) return rc;
-    if (int rc = check_reduce_batch(B)) return rc;
-    if (chw < 1 || chw >= MEMBER_WORDS) return fail(MI_EINVAL, "chw %lld outside [1, 2^32) (limit: C*H*W < 4294967296)", (long long)chw);
-    return MI_OK;
-}
-
-extern "C" int mi_ensemble_reduce(const float* samples, int B, int members, int64_t chw, float* mean_out, float* std_out, void* stream) {
-    if (int rc = check_ensemble_run(B, members, chw)) return rc;
-    if (int rc = check_std_members(std_out, members)) return rc;
-    if (!samples || !mean_out) return fail(MI_EINVAL, "null argument");
-    return launched(ensemble_reduce_launch(samples, B, members, (unsigned long long)chw, mean_out, std_out, (hipStream_t)stream), "ensemble_reduce");
-}
-
-// the members of a pixel are sorted in registers (ensemble.hip: ensemble_quantiles_kernel): at most QUANTILE_MAX_MEMBERS of them
-static int check_quantile_members(int members) {
-    if (members > QUANTILE_MAX_MEMBERS)
-        return fail(MI_EINVAL, "members %d: the quantile kernels sort a pixel's members in registers (limit: members <= %d; mean and std have no such limit)",
-                    members, QUANTILE_MAX_MEMBERS);
-    return MI_OK;
-}
-
-// the levels of a quantile call, host doubles -> the kernel argument
-static int check_quantile_levels(const double* q, int nq, QuantileLevels* ql) {
-    if (nq < 1 || nq > QUANTILE_MAX_LEVELS)
-        return fail(MI_EINVAL, "nq %d outside [1, %d]: the levels travel as kernel arguments (limit: 1 <= nq <= %d)", nq, QUANTILE_MAX_LEVELS, QUANTILE_MAX_LEVELS);
-    if (!q) return fail(MI_EINVAL, "null argument");
-    *ql = QuantileLevels{};
-    ql->nq = nq;
-    for (int i = 0; i < nq; ++i) {
-        if (!(q[i] >= 0.0 && q[i] <= 1.0)) return fail(MI_EINVAL, "q[%d] = %.17g outside [0, 1] (limit: 0 <= q <= 1, not NaN)", i, q[i]);
-        ql->q[i] = q[i];
-    }
-    return MI_OK;
-}
-
-extern "C" int mi_ensemble_quantiles(const float* samples, int B, int members, int64_t chw, const double* q, int nq, float* out, void* stream) {
-    if (int rc = check_ensemble_run(B, members, chw)) return rc;
-    if (int rc = check_quantile_members(members)) return rc;
-    QuantileLevels ql;
-    if (int rc = check_quantile_levels(q, nq, &ql)) return rc;
-    if (!samples || !out) return fail(MI_EINVAL, "null argument");
-    return launched(ensemble_quantiles_launch(samples, B, members, (unsigned long long)chw, ql, out, (hipStream_t)stream), "ensemble_quantiles");
-}
-
-// The scores of an ensemble against a truth image (ensemble_scores.hip; include/midd.h: THE ENSEMBLE SCORES).  The rules in the
-// documented order; the levels may be none (nq == 0: no coverage counts), which check_quantile_levels does not allow
-static int check_scores_shape(int B, int members, int64_t chw) {
-    if (int rc = check_reduce_batch(B, "limit of the scores kernel's grid")) return rc;
-    if (members < 1 || members > QUANTILE_MAX_MEMBERS)
-        return fail(MI_EINVAL, "members %d outside [1, %d]: the scores kernel sorts a pixel's members in registers (limit: 1 <= members <= %d)",
-                    members, QUANTILE_MAX_MEMBERS, QUANTILE_MAX_MEMBERS);
-    if (chw < 1 || chw >= MEMBER_WORDS) return fail(MI_EINVAL, "chw %lld outside [1, 2^32) (limit: C*H*W < 4294967296)", (long long)chw);
-    return MI_OK;
-}
-
-extern "C" size_t mi_ensemble_scores_workspace_bytes(int B, int members, int64_t chw) {
-    if (check_scores_shape(B, members, chw)) return 0;
-    return ensemble_scores_partials_bytes(B, (unsigned long long)chw);
-}
-
-extern "C" int mi_ensemble_scores(const float* samples, const float* truth, int B, int members, int64_t chw, const double* q, int nq,
-                                  double* sums, uint64_t* invalid, uint64_t* rank_hist, uint64_t* counts, float* crps_map,
-                                  void* workspace, size_t workspace_bytes, void* stream) {
-    if (int rc = check_scores_shape(B, members, chw)) return rc;
-    if (nq < 0 || nq > QUANTILE_MAX_LEVELS)
-        return fail(MI_EINVAL, "nq %d outside [0, %d]: the levels travel as kernel arguments (limit: 0 <= nq <= %d)", nq, QUANTILE_MAX_LEVELS, QUANTILE_MAX_LEVELS);
-    QuantileLevels ql{};
-    ql.nq = nq;
-    for (int i = 0; q && i < nq; ++i) {
-        if (!(q[i] >= 0.0 && q[i] <= 1.0)) return fail(MI_EINVAL, "q[%d] = %.17g outside [0, 1] (limit: 0 <= q <= 1, not NaN)", i, q[i]);
-        ql.q[i] = q[i];
-    }
-    if (!samples || !truth || !sums || !invalid || !rank_hist || !workspace || (nq > 0 && !q)) return fail(MI_EINVAL, "null argument");
-    if ((counts == nullptr) != (nq == 0))
-        return fail(MI_EINVAL, "counts and nq = %d disagree: counts holds [B][nq][2] counters and is NULL if and only if nq == 0", nq);
-    for (const void* p : {(const void*)sums, (const void*)invalid, (const void*)rank_hist, (const void*)counts, (const void*)workspace})
-        if (reinterpret_cast<uintptr_t>(p) & 7) return fail(MI_EINVAL, "sums, invalid, rank_hist, counts and workspace must be 8-byte aligned");
-    for (const void* p : {(const void*)samples, (const void*)truth, (const void*)crps_map})
-        if (reinterpret_cast<uintptr_t>(p) & 3) return fail(MI_EINVAL, "samples, truth and crps_map must be 4-byte aligned");
-    const size_t need = ensemble_scores_partials_bytes(B, (unsigned long long)chw);
-    if (workspace_bytes < need) return fail(MI_EINVAL, "workspace too small: need %zu bytes (mi_ensemble_scores_workspace_bytes), got %zu", need, workspace_bytes);
-    const size_t img = (size_t)chw * sizeof(float);
-    const Buf buf[8] = {{samples, (size_t)B * members * img, "samples"}, {truth, (size_t)B * img, "truth"},
-                        {sums, (size_t)B * 4 * sizeof(double), "sums"}, {invalid, (size_t)B * sizeof(uint64_t), "invalid"},
-                        {rank_hist, (size_t)B * (2 * members + 1) * sizeof(uint64_t), "rank_hist"},
-                        {counts, (size_t)B * nq * 2 * sizeof(uint64_t), "counts"}, {crps_map, (size_t)B * img, "crps_map"},
-                        {workspace, need, "workspace"}};
-    if (int rc = check_no_overlap(buf, 8, "samples and truth are read while every output and the workspace are written")) return rc;
-    static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "the counters are 64-bit");
-    return launched(ensemble_scores_launch(samples, truth, B, members, (unsigned long long)chw, ql, sums,
-                                           reinterpret_cast<unsigned long long*>(invalid), reinterpret_cast<unsigned long long*>(rank_hist),
-                                           reinterpret_cast<unsigned long long*>(counts), crps_map, static_cast<double*>(workspace),
-                                           (hipStream_t)stream), "ensemble_scores");
-}
-
-// The principal modes of an ensemble's spread (ensemble_modes.hip; include/midd.h: THE ENSEMBLE MODES): the Gram matrix of the
-// centred members and the projection onto the caller's weight rows.  The rules in the documented order
-static int check_modes_shape(int B, int members, int64_t chw) {
-    if (int rc = check_reduce_batch(B, "limit of the modes kernels' grid")) return rc;
-    if (members < 2 || members > MODES_MAX_MEMBERS)
-        return fail(MI_EINVAL, "members %d outside [2, %d]: one member has no spread, and the Gram kernel tiles at most %d members (limit: 2 <= members <= %d)",
-                    members, MODES_MAX_MEMBERS, MODES_MAX_MEMBERS, MODES_MAX_MEMBERS);
-    if (chw < 1 || chw >= MEMBER_WORDS) return fail(MI_EINVAL, "chw %lld outside [1, 2^32) (limit: C*H*W < 4294967296)", (long long)chw);
-    return MI_OK;
-}
-
-extern "C" size_t mi_ensemble_gram_workspace_bytes(int B, int members, int64_t chw) {
-    if (check_modes_shape(B, members, chw)) return 0;
-    return ensemble_gram_workspace_bytes(B, members, (unsigned long long)chw);
-}
-
-extern "C" int mi_ensemble_gram(const float* samples, int B, int members, int64_t chw, double* gram, uint64_t* invalid,
-                                void* workspace, size_t workspace_bytes, void* stream) {
-    if (int rc = check_modes_shape(B, members, chw)) return rc;
-    if (!samples || !gram || !invalid || !workspace) return fail(MI_EINVAL, "null argument");
-    for (const void* p : {(const void*)gram, (const void*)invalid, (const void*)workspace})
-        if (reinterpret_cast<uintptr_t>(p) & 7) return fail(MI_EINVAL, "gram, invalid and workspace must be 8-byte aligned");
-    if (reinterpret_cast<uintptr_t>(samples) & 3) return fail(MI_EINVAL, "samples must be 4-byte aligned");
-    const size_t need = ensemble_gram_workspace_bytes(B, members, (unsigned long long)chw);
-    if (workspace_bytes < need) return fail(MI_EINVAL, "workspace too small: need %zu bytes (mi_ensemble_gram_workspace_bytes), got %zu", need, workspace_bytes);
-    const Buf buf[4] = {{samples, (size_t)B * members * (size_t)chw * sizeof(float), "samples"},
-                        {gram, (size_t)B * members * members * sizeof(double), "gram"}, {invalid, (size_t)B * sizeof(uint64_t), "invalid"},
-                        {workspace, need, "workspace"}};
-    if (int rc = check_no_overlap(buf, 4, "samples is read while gram, invalid and the workspace are written")) return rc;
-    static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "the counters are 64-bit");
-    return launched(ensemble_gram_launch(samples, B, members, (unsigned long long)chw, gram, reinterpret_cast<unsigned long long*>(invalid),
-                                         static_cast<double*>(workspace), (hipStream_t)stream), "ensemble_gram");
-}
-
-extern "C" int mi_ensemble_project(const float* samples, int B, int members, int64_t chw, const double* weights, int n_modes, float* out, void* stream) {
-    if (int rc = check_modes_shape(B, members, chw)) return rc;
-    if (n_modes < 1 || n_modes > MODES_MAX_MODES)
-        return fail(MI_EINVAL, "n_modes %d outside [1, %d]: a projection launch holds at most %d accumulators per element (limit: 1 <= n_modes <= %d)",
-                    n_modes, MODES_MAX_MODES, MODES_MAX_MODES, MODES_MAX_MODES);
-    if (!samples || !weights || !out) return fail(MI_EINVAL, "null argument");
-    if (reinterpret_cast<uintptr_t>(weights) & 7) return fail(MI_EINVAL, "weights must be 8-byte aligned");
-    for (const void* p : {(const void*)samples, (const void*)out})
-        if (reinterpret_cast<uintptr_t>(p) & 3) return fail(MI_EINVAL, "samples and out must be 4-byte aligned");
-    const size_t img = (size_t)chw * sizeof(float);
-    const Buf buf[3] = {{samples, (size_t)B * members * img, "samples"}, {weights, (size_t)B * n_modes * members * sizeof(double), "weights"},
-                        {out, (size_t)B * n_modes * img, "out"}};
-    if (int rc = check_no_overlap(buf, 3, "samples and weights are read while out is written")) return rc;
-    return launched(ensemble_project_launch(samples, B, members, (unsigned long long)chw, weights, n_modes, out, (hipStream_t)stream), "ensemble_project");
-}
-
-// The noise power spectrum (nps.hip; include/midd.h: THE NOISE POWER SPECTRUM).  The rules in the documented order; nothing is read,
-// not even the host window, before every rule has passed
-static int check_nps_shape(int B, int K, int C, int H, int W, int roi, int step) {
-    if (roi != 32 && roi != 64 && roi != 128) return fail(MI_EINVAL, "roi %d outside {32, 64, 128}: the ROI transform is built for these sizes", roi);
-    if (step < 1) return fail(MI_EINVAL, "step %d below 1 (limit: step >= 1)", step);
-    if (B < 1 || K < 1 || C < 1) return fail(MI_EINVAL, "B %d, K %d, C %d: each must be at least 1", B, K, C);
-    if ((long long)B * C > 65535) return fail(MI_EINVAL, "B * C = %lld groups outside [1, 65535] (limit of the kernel's grid)", (long long)B * C);
-    if (H < roi || W < roi) return fail(MI_EINVAL, "image %d x %d smaller than the ROI %d x %d: there are no partial ROIs", H, W, roi, roi);
-    const unsigned long long per_member = (unsigned long long)((H - roi) / step + 1) * (unsigned long long)((W - roi) / step + 1);
-    if (per_member > 0x7FFFFFFFull || nps_chunks(K, H, W, roi, step) > 0x7FFFFFFFull)
-        return fail(MI_EINVAL, "too many ROIs: %llu per member, K %d (limit: ROIs per member < 2^31, chunks of 16 ROIs < 2^31)", per_member, K);
-    return MI_OK;
-}
-
-extern "C" size_t mi_noise_power_spectrum_workspace_bytes(int B, int K, int C, int H, int W, int roi, int step) {
-    if (check_nps_shape(B, K, C, H, W, roi, step)) return 0;
-    return nps_workspace_bytes(B * C, K, H, W, roi, step);
-}
-
-extern "C" int mi_noise_power_spectrum(const float* a, const float* b, int B, int K, int C, int H, int W, int roi, int step, int detrend,
-                                       const float* window, double scale, int flags, double* nps, double* radial, int64_t* radial_count,
-                                       int64_t* rois_used, int64_t* rois_skipped, void* workspace, size_t workspace_bytes, void* stream) {
-    if (int rc = check_nps_shape(B, K, C, H, W, roi, step)) return rc;
-    if (detrend < MI_NPS_DETREND_NONE || detrend > MI_NPS_DETREND_PLANE)
-        return fail(MI_EINVAL, "detrend %d outside {0 none, 1 mean, 2 plane}", detrend);
-    if (flags & ~MI_NPS_EXCLUDE_AXES) return fail(MI_EINVAL, "flags 0x%x: unknown bits (known: MI_NPS_EXCLUDE_AXES = 1)", (unsigned)flags);
-    if (!(scale == scale) || scale - scale != 0.0) return fail(MI_EINVAL, "scale %g is not finite", scale);
-    if (!a || !nps || !radial || !radial_count || !rois_used || !rois_skipped || !workspace) return fail(MI_EINVAL, "null argument");
-    for (const void* p : {(const void*)nps, (const void*)radial, (const void*)radial_count, (const void*)rois_used, (const void*)rois_skipped, (const void*)workspace})
-        if (reinterpret_cast<uintptr_t>(p) & 7) return fail(MI_EINVAL, "nps, radial, radial_count, rois_used, rois_skipped and workspace must be 8-byte aligned");
-    for (const void* p : {(const void*)a, (const void*)b})
-        if (reinterpret_cast<uintptr_t>(p) & 3) return fail(MI_EINVAL, "a and b must be 4-byte aligned");
-    const size_t need = nps_workspace_bytes(B * C, K, H, W, roi, step);
-    if (workspace_bytes < need) return fail(MI_EINVAL, "workspace too small: need %zu bytes (mi_noise_power_spectrum_workspace_bytes), got %zu", need, workspace_bytes);
-    const size_t groups = (size_t)B * C, img = (size_t)H * W * sizeof(float), bins = (size_t)roi / 2 + 1;
-    const Buf buf[8] = {{a, groups * K * img, "a"}, {b, groups * img, "b"}, {nps, groups * roi * roi * sizeof(double), "nps"},
-                        {radial, groups * bins * sizeof(double), "radial"}, {radial_count, bins * sizeof(int64_t), "radial_count"},
-                        {rois_used, groups * sizeof(int64_t), "rois_used"}, {rois_skipped, groups * sizeof(int64_t), "rois_skipped"},
-                        {workspace, need, "workspace"}};
-    if (int rc = check_no_overlap(buf, 8, "a and b are read while every output and the workspace are written")) return rc;
-    if (window)
-        for (int i = 0; i < roi; ++i)
-            if (!(window[i] == window[i]) || window[i] - window[i] != 0.0f) return fail(MI_EINVAL, "window[%d] is not finite", i);
-    static_assert(sizeof(long long) == sizeof(int64_t), "the counters are 64-bit");
-    return launched(nps_launch(a, b, B, K, C, H, W, roi, step, detrend, window, scale, (flags & MI_NPS_EXCLUDE_AXES) ? 1 : 0, nps, radial,
-                               reinterpret_cast<long long*>(radial_count), reinterpret_cast<long long*>(rois_used),
-                               reinterpret_cast<long long*>(rois_skipped), workspace, (hipStream_t)stream), "noise_power_spectrum");
-}
-
-// The cross-spectrum of two fields (cross_spectrum.hip; include/midd.h: THE CROSS SPECTRUM).  The member rule, then the shape rules of
-// the noise power spectrum with K = max(Kx, Ky), then the rest in the documented order
-static int check_xs_shape(int B, int Kx, int Ky, int C, int H, int W, int roi, int step) {
-    if (Kx < 1 || Ky < 1) return fail(MI_EINVAL, "Kx %d, Ky %d: each field has at least one realisation", Kx, Ky);
-    if (Kx != Ky && Kx != 1 && Ky != 1)
-        return fail(MI_EINVAL, "Kx %d, Ky %d: the fields have K = max(Kx, Ky) members each, or one that is broadcast (limit: Kx, Ky in {K, 1})", Kx, Ky);
-    return check_nps_shape(B, Kx > Ky ? Kx : Ky, C, H, W, roi, step);
-}
-
-extern "C" size_t mi_cross_spectrum_workspace_bytes(int B, int Kx, int Ky, int C, int H, int W, int roi, int step) {
-    if (check_xs_shape(B, Kx, Ky, C, H, W, roi, step)) return 0;
-    return xs_workspace_bytes(B * C, Kx > Ky ? Kx : Ky, H, W, roi, step);
-}
-
-extern "C" int mi_cross_spectrum(const float* x, const float* y, int B, int Kx, int Ky, int C, int H, int W, int roi, int step, int detrend,
-                                 const float* window, int flags, double* planes, double* radial, int64_t* radial_count,
-                                 int64_t* rois_used, int64_t* rois_skipped, void* workspace, size_t workspace_bytes, void* stream) {
-    if (int rc = check_xs_shape(B, Kx, Ky, C, H, W, roi, step)) return rc;
-    if (detrend < MI_NPS_DETREND_NONE || detrend > MI_NPS_DETREND_PLANE)
-        return fail(MI_EINVAL, "detrend %d outside {0 none, 1 mean, 2 plane}", detrend);
-    if (flags & ~MI_NPS_EXCLUDE_AXES) return fail(MI_EINVAL, "flags 0x%x: unknown bits (known: MI_NPS_EXCLUDE_AXES = 1)", (unsigned)flags);
-    if (!x || !y || !planes || !radial || !radial_count || !rois_used || !rois_skipped || !workspace) return fail(MI_EINVAL, "null argument");
-    for (const void* p : {(const void*)planes, (const void*)radial, (const void*)radial_count, (const void*)rois_used, (const void*)rois_skipped, (const void*)workspace})
-        if (reinterpret_cast<uintptr_t>(p) & 7) return fail(MI_EINVAL, "planes, radial, radial_count, rois_used, rois_skipped and workspace must be 8-byte aligned");
-    for (const void* p : {(const void*)x, (const void*)y})
-        if (reinterpret_cast<uintptr_t>(p) & 3) return fail(MI_EINVAL, "x and y must be 4-byte aligned");
-    const int K = Kx > Ky ? Kx : Ky;
-    const size_t need = xs_workspace_bytes(B * C, K, H, W, roi, step);
-    if (workspace_bytes < need) return fail(MI_EINVAL, "workspace too small: need %zu bytes (mi_cross_spectrum_workspace_bytes), got %zu", need, workspace_bytes);
-    const size_t groups = (size_t)B * C, img = (size_t)H * W * sizeof(float), bins = (size_t)roi / 2 + 1;
-    // (x and y are both only read: they may overlap each other, or be the same field)
-    const Buf outs[6] = {{planes, 4 * groups * roi * roi * sizeof(double), "planes"}, {radial, 4 * groups * bins * sizeof(double), "radial"},
-                         {radial_count, bins * sizeof(int64_t), "radial_count"}, {rois_used, groups * sizeof(int64_t), "rois_used"},
-                         {rois_skipped, groups * sizeof(int64_t), "rois_skipped"}, {workspace, need, "workspace"}};
-    for (const Buf& in : {Buf{x, groups * Kx * img, "x"}, Buf{y, groups * Ky * img, "y"}}) {
-        const Buf buf[7] = {in, outs[0], outs[1], outs[2], outs[3], outs[4], outs[5]};
-        if (int rc = check_no_overlap(buf, 7, "x and y are read while every output and the workspace are written")) return rc;
-    }
-    if (window)
-        for (int i = 0; i < roi; ++i)
-            if (!(window[i] == window[i]) || window[i] - window[i] != 0.0f) return fail(MI_EINVAL, "window[%d] is not finite", i);
-    return launched(xs_launch(x, y, B, Kx, Ky, C, H, W, roi, step, detrend, window, (flags & MI_NPS_EXCLUDE_AXES) ? 1 : 0, planes, radial,
-                              reinterpret_cast<long long*>(radial_count), reinterpret_cast<long long*>(rois_used),
-                              reinterpret_cast<long long*>(rois_skipped), workspace, (hipStream_t)stream), "cross_spectrum");
 }
 
 // ---------------------------------------------------------------------------- the batched calls: virtual samples in passes

@@ -1,7 +1,7 @@
 // Types and functions shared by the host side of libmidd.so: midd_abi.hip (C ABI surface), midd_weights.hip (topology, weight
 // repacking, time table), midd_planner.hip (execution planner), midd_exec.hip (executor), midd_sampler.hip (sampler calls),
-// midd_batched.hip (batched calls) and midd_loss.hip (the denoising-loss calls; the last four share midd_sampler.h).  No torch,
-// no allocation on the hot path.
+// midd_batched.hip (batched calls), midd_analysis.hip (stand-alone analysis calls) and midd_loss.hip (the denoising-loss calls; the
+// last five share midd_sampler.h).  No torch, no allocation on the hot path.
 #pragma once
 #include "../../include/midd.h"
 #include "midd_internal.h"

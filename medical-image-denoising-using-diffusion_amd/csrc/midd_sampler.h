@@ -1,4 +1,5 @@
-// What the executor (midd_exec.hip), the sampler calls (midd_sampler.hip) and the batched calls (midd_batched.hip) share.
+// What the executor (midd_exec.hip), the sampler calls (midd_sampler.hip), the batched calls (midd_batched.hip) and the stand-alone
+// analysis calls (midd_analysis.hip) share.
 #pragma once
 #include "midd_host.h"
 
@@ -60,6 +61,14 @@ inline int launched(hipError_t e, const char* what) {
 // no two of the n buffers may overlap (a null one is absent); `why` is the call's sentence on who reads and who writes
 struct Buf { const void* p; size_t bytes; const char* name; };
 int check_no_overlap(const Buf* b, int n, const char* why);                                             // midd_sampler.hip
+
+// midd_analysis.hip: the member, batch and level rules of the reduce and quantile calls, which the batched calls compose
+constexpr int64_t MEMBER_WORDS = (int64_t)1 << 32;      // the member index is one 32-bit counter word
+int check_members_min(int members);
+int check_std_members(const float* std_out, int members);
+int check_reduce_batch(int B, const char* why = "limit of the reduce kernel's grid");
+int check_quantile_members(int members);
+int check_quantile_levels(const double* q, int nq, QuantileLevels* ql, int nq_min = 1);
 
 // midd_exec.hip.  status: the call's status word (first word of the CALLER's workspace, whichever sub-batch program runs)
 int run_program(mi_plan* p, Program* g, const StepIO& io, char* ws, int* status, hipStream_t s, hipEvent_t mid_event = nullptr, int mid_div = 2);

@@ -1,28 +1,12 @@
 // The noise power spectrum of a field f = a - b (include/midd.h: THE NOISE POWER SPECTRUM; tests/nps_reference.py restates it in
 // numpy): Welch's method over overlapping R x R regions of interest (ROIs) -- detrend, window, 2-D DFT in fp32, |F|^2 in double,
-// averaged over the ROIs of a group (b, c) and binned by radial frequency.
-//   nps_roi_kernel<R>      a workgroup of 256 lanes owns ONE chunk of NPS_CHUNK = 16 consecutive ROIs of one group and walks them in
-//                          order.  Per ROI: the rows are loaded (16-byte loads where W is a multiple of 4 and the ROI's first element
-//                          is 16-byte aligned, elements otherwise: the values are the same) as f = a - b into the lane's registers
-//                          and, for the row sums, into the imaginary slots in natural order, and a non-finite f
-//                          marks the ROI skipped; R lanes add a row each (s0 = sum f, s1 = sum xc f, x from 0), lane 0 adds the rows
-//                          (y from 0) and forms m, ax, ay; every element is detrended in double, rounded once, multiplied by w[y]
-//                          and then by w[x], and written as (d, 0) at [bitrev(y)][bitrev(x)].  Two passes of
-//                          log2 R radix-2 decimation-in-time stages run in place, over all R rows and then over the columns
-//                          0 .. R/2 only (the row transform of real data is Hermitian; the other columns follow by
-//                          P[v][u] = P[(R - v) % R][R - u]).  The lane owns the entries idx = lane + 256 e of the half plane
-//                          [R][R/2 + 1] and adds P = re^2 + im^2 to its double accumulators, ROI after ROI; the chunk's sums and its
-//                          count of used ROIs go to the workspace.  No atomics.
-//                          LDS: ONE complex plane of interleaved (re, im) words, R rows with pitch R + 1 words.  The row pass
-//                          gives consecutive lanes consecutive ROWS at one butterfly index (odd pitch: the 32 lanes of a half wave
-//                          on 32 different bank pairs, the twiddle one broadcast read), the column pass gives them consecutive
-//                          columns.  With the twiddle and window tables and the R + R row sums: 8.7 KiB, 33.7 KiB and 131.7 KiB
-//                          for R = 32, 64, 128.
-//   nps_sum_kernel<R>      one lane per half-plane entry adds the group's chunk sums one by one from 0 in chunk order, scales, and
-//                          writes the entry and its mirror; lane 0 of block 0 leaves rois_used and rois_skipped
-//   nps_radial_kernel<R>   one wave per (group, bin) over the group's plane in LDS: the rows in order, per row one ballot over the
-//                          columns and the bin's entries added in ascending column order, i.e. row-major
-// Contraction is off for the whole unit: a complex multiply is four v_mul_f32 and two v_add/v_sub_f32.
+// averaged over the ROIs of a group (b, c) and binned by radial frequency.  The stages are those of nps_common.h; what is this unit's:
+//   nps_roi_kernel<R>  256 lanes.  f = a - b is ONE real field: the lane keeps its row quads and, for the row sums, puts them into the
+//                      imaginary slots in natural order; R lanes add a row each, lane 0 forms m, ax, ay; the element is written as
+//                      (d, 0).  The column pass covers the columns 0 .. R/2 only (the row transform of real data is Hermitian; the
+//                      other columns follow by P[v][u] = P[(R - v) % R][R - u]).  The lane owns the entries idx = lane + 256 e of the
+//                      half plane [R][R/2 + 1] and adds P = re^2 + im^2.  LDS: 8.7 KiB, 33.7 KiB and 131.7 KiB for R = 32, 64, 128
+//   nps_sum_kernel<R>  64 loads in flight, the scale, the entry and its mirror
 #include <cmath>
 #include "nps_common.h"
 
@@ -56,23 +40,18 @@ void nps_roi_kernel(const float* __restrict__ a, const float* __restrict__ b, in
 #pragma unroll
     for (int e = 0; e < NACC; ++e) acc[e] = 0.0;
     long long n_used = 0;
-    const unsigned long long r0 = (unsigned long long)chunk * NPS_CHUNK;
-    const unsigned long long r1 = r0 + NPS_CHUNK < n_rois ? r0 + NPS_CHUNK : n_rois;
-    const unsigned per_member = (unsigned)ny * (unsigned)nx;            // (< 2^31: nps_launch)
-    size_t m = r0 / per_member;
-    unsigned rem = (unsigned)(r0 % per_member);
+    NpsWalk w = nps_walk(chunk, n_rois, ny, nx);
 #pragma unroll 1
-    for (unsigned long long r = r0; r < r1; ++r, ++rem) {
-        if (rem == per_member) { rem = 0; ++m; }
-        const size_t oy = (size_t)(rem / (unsigned)nx) * S, ox = (size_t)(rem % (unsigned)nx) * S;
-        const float* pa = a + ((bi * K + m) * C + c) * plane + oy * W + ox;
+    for (unsigned long long r = w.r0; r < w.r1; ++r, ++w.rem) {
+        size_t oy, ox;
+        nps_walk_roi(w, nx, S, oy, ox);
+        const float* pa = a + ((bi * K + w.m) * C + c) * plane + oy * W + ox;
         const float* pb = b ? b + (bi * C + c) * plane + oy * W + ox : nullptr;
         if (tid == 0) bad = 0;
         __syncthreads();
         // f = a - b: the lane keeps its quads; with a detrend they also go to the imaginary slots, in natural order, for the row sums
         f32x4 fq[NQ];
         {
-            // every row quad of the ROI is 16-byte aligned when W is a multiple of 4 and the ROI's first element is aligned
             const bool wide = (W & 3) == 0;
             if (wide && nps_aligned16(pa)) nps_load_quads<R, NQ, 4>(pa, (size_t)W, tid, fq);
             else nps_load_quads<R, NQ, 1>(pa, (size_t)W, tid, fq);
@@ -118,7 +97,7 @@ void nps_roi_kernel(const float* __restrict__ a, const float* __restrict__ b, in
                     tx = add_rn64(tx, rs1[y]);
                     ty = add_rn64(ty, mul_rn64((double)y - 0.5 * (R - 1), rs0[y]));
                 }
-                const double den = (double)R * ((double)R * ((double)R * R - 1.0) / 12.0);      // exact integers
+                const double den = NPS_SLOPE_DEN<R>;
                 coef[0] = __ddiv_rn(t0, (double)(R * R));
                 coef[1] = detrend == 2 ? __ddiv_rn(tx, den) : 0.0;
                 coef[2] = detrend == 2 ? __ddiv_rn(ty, den) : 0.0;
@@ -148,8 +127,7 @@ void nps_roi_kernel(const float* __restrict__ a, const float* __restrict__ b, in
             }
         }
         __syncthreads();
-        // the rows: every row, every column.  Consecutive lanes take consecutive ROWS (pitch R + 1: no two lanes of a half wave on
-        // one bank) and share the butterfly index, so the twiddle is one broadcast read
+        // the rows: every row, every column
 #pragma unroll 1
         for (int s = 1; s <= LOG; ++s) {
             const int half = 1 << (s - 1);
@@ -196,16 +174,14 @@ void nps_roi_kernel(const float* __restrict__ a, const float* __restrict__ b, in
     if (tid == 0) used[g * chunks + chunk] = n_used;
 }
 
-// grid (ceil(HALF / 64), groups): the chunk sums of one entry, one by one from 0 in chunk order; NPS_SUM_BATCH independent loads are in
-// flight per step of the dependent chain of adds
+// grid (ceil(HALF / 64), groups): the chunk sums of one entry (nps_chunk_sum), scaled
 constexpr int NPS_SUM_THREADS = 64;
 constexpr int NPS_SUM_BATCH = 64;
 template <int R>
 __global__ __launch_bounds__(NPS_SUM_THREADS)
 void nps_sum_kernel(const double* __restrict__ part, const long long* __restrict__ used, unsigned chunks, unsigned long long n_rois,
                     double scale, double sw, double* __restrict__ nps, long long* __restrict__ rois_used, long long* __restrict__ rois_skipped) {
-    using G = NpsGeom<R>;
-    constexpr int NC = G::NC, HALF = G::HALF;
+    constexpr int HALF = NpsGeom<R>::HALF;
     const size_t g = blockIdx.y;
     const int idx = blockIdx.x * NPS_SUM_THREADS + threadIdx.x;
     // the used ROIs of the group: integers, so the order is free -- a strided share per lane, folded over the wave
@@ -216,56 +192,16 @@ void nps_sum_kernel(const double* __restrict__ part, const long long* __restrict
     for (int off = 32; off > 0; off >>= 1) n += __shfl_xor(n, off);
     if (idx == 0) { rois_used[g] = n; rois_skipped[g] = (long long)n_rois - n; }
     if (idx >= HALF) return;
-    const double* p = part + g * chunks * (size_t)HALF + idx;
-    double s = 0.0;
-    unsigned c = 0;
-    for (; c + NPS_SUM_BATCH <= chunks; c += NPS_SUM_BATCH) {
-        double v[NPS_SUM_BATCH];
-#pragma unroll
-        for (int j = 0; j < NPS_SUM_BATCH; ++j) v[j] = p[(size_t)(c + j) * HALF];
-#pragma unroll
-        for (int j = 0; j < NPS_SUM_BATCH; ++j) s = add_rn64(s, v[j]);
-    }
-    for (; c < chunks; ++c) s = add_rn64(s, p[(size_t)c * HALF]);
+    const double s = nps_chunk_sum<NPS_SUM_BATCH, HALF>(part + g * chunks * (size_t)HALF + idx, chunks);
     const double val = n > 0 ? __ddiv_rn(mul_rn64(scale, s), mul_rn64((double)n, sw)) : __longlong_as_double((long long)NPS_QNAN);
-    const int v = idx / NC, u = idx % NC;
-    double* out = nps + g * (size_t)(R * R);
-    out[v * R + u] = val;
-    if (u > 0 && u < R / 2) out[((R - v) % R) * R + (R - u)] = val;
+    nps_store_mirrored<R>(nps, 0, 0, g, idx, val, val);
 }
 
 // ---------------------------------------------------------------------------------------------------------------- launches
-static unsigned long long nps_rois(int K, int H, int W, int R, int S) {
-    return (unsigned long long)K * (unsigned long long)((H - R) / S + 1) * (unsigned long long)((W - R) / S + 1);
-}
-
-unsigned long long nps_chunks(int K, int H, int W, int R, int S) { return (nps_rois(K, H, W, R, S) + NPS_CHUNK - 1) / NPS_CHUNK; }
+unsigned long long nps_chunks(int K, int H, int W, int R, int S) { return nps_counts(K, H, W, R, S).chunks; }
 
 size_t nps_workspace_bytes(int groups, int K, int H, int W, int R, int S) {
     return (size_t)groups * nps_chunks(K, H, W, R, S) * ((size_t)R * (R / 2 + 1) + 1) * sizeof(double);
-}
-
-template <int R>
-static hipError_t nps_dispatch(const float* a, const float* b, int B, int K, int C, int H, int W, int S, int detrend, int windowed,
-                               const NpsTables& tab, double scale, double sw, int exclude_axes, double* nps, double* radial,
-                               long long* radial_count, long long* rois_used, long long* rois_skipped, void* ws, hipStream_t s) {
-    using G = NpsGeom<R>;
-    const int groups = B * C, ny = (H - R) / S + 1, nx = (W - R) / S + 1;
-    const unsigned long long n_rois = nps_rois(K, H, W, R, S);
-    const unsigned chunks = (unsigned)nps_chunks(K, H, W, R, S);
-    double* part = static_cast<double*>(ws);
-    long long* used = reinterpret_cast<long long*>(part + (size_t)groups * chunks * G::HALF);
-    hipLaunchKernelGGL((nps_roi_kernel<R>), dim3(chunks, groups), dim3(NPS_THREADS), 0, s, a, b, K, C, H, W, S, ny, nx, n_rois, detrend, windowed,
-                       tab, part, used);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((nps_sum_kernel<R>), dim3((G::HALF + NPS_SUM_THREADS - 1) / NPS_SUM_THREADS, groups), dim3(NPS_SUM_THREADS), 0, s, part, used,
-                       chunks, n_rois, scale, sw, nps, rois_used, rois_skipped);
-    e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((nps_radial_kernel<R>), dim3((R / 2 + 1 + 3) / 4, groups), dim3(NPS_THREADS), 0, s, nps, rois_used, exclude_axes, radial,
-                       radial_count);
-    return hipGetLastError();
 }
 
 // the tables: twiddles exp(-2 pi i t / R), t < R/2, and the window, computed in double and rounded to fp32; S_w = (sum w^2)^2
@@ -283,19 +219,33 @@ void nps_tables(int R, const float* window, NpsTables* tab, double* sw) {
     }
 }
 
+// (every argument has been judged by the entry, mi_noise_power_spectrum, with a message)
 hipError_t nps_launch(const float* a, const float* b, int B, int K, int C, int H, int W, int R, int S, int detrend, const float* window,
                       double scale, int exclude_axes, double* nps, double* radial, long long* radial_count, long long* rois_used,
                       long long* rois_skipped, void* ws, hipStream_t s) {
-    if ((R != 32 && R != 64 && R != 128) || S < 1 || B < 1 || K < 1 || C < 1 || H < R || W < R || (long long)B * C > 65535 || detrend < 0 ||
-        detrend > 2 || (unsigned long long)((H - R) / S + 1) * (unsigned long long)((W - R) / S + 1) > 0x7FFFFFFFull || !a || !nps || !radial || !radial_count || !rois_used || !rois_skipped || !ws || nps_chunks(K, H, W, R, S) > 0x7FFFFFFFull)
-        return hipErrorInvalidValue;
     NpsTables tab{};
     double sw;
     nps_tables(R, window, &tab, &sw);
-    const int windowed = window ? 1 : 0;
-    if (R == 32) return nps_dispatch<32>(a, b, B, K, C, H, W, S, detrend, windowed, tab, scale, sw, exclude_axes, nps, radial, radial_count, rois_used, rois_skipped, ws, s);
-    if (R == 64) return nps_dispatch<64>(a, b, B, K, C, H, W, S, detrend, windowed, tab, scale, sw, exclude_axes, nps, radial, radial_count, rois_used, rois_skipped, ws, s);
-    return nps_dispatch<128>(a, b, B, K, C, H, W, S, detrend, windowed, tab, scale, sw, exclude_axes, nps, radial, radial_count, rois_used, rois_skipped, ws, s);
+    const int groups = B * C, windowed = window ? 1 : 0;
+    const NpsCounts n = nps_counts(K, H, W, R, S);
+    const unsigned chunks = (unsigned)n.chunks;
+    double* part = static_cast<double*>(ws);
+    return nps_for_roi_size(R, [&](auto size) {
+        constexpr int N = decltype(size)::value;
+        using G = NpsGeom<N>;
+        long long* used = reinterpret_cast<long long*>(part + (size_t)groups * chunks * G::HALF);
+        hipLaunchKernelGGL((nps_roi_kernel<N>), dim3(chunks, groups), dim3(NPS_THREADS), 0, s, a, b, K, C, H, W, S, n.ny, n.nx, n.n_rois, detrend,
+                           windowed, tab, part, used);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL((nps_sum_kernel<N>), dim3((G::HALF + NPS_SUM_THREADS - 1) / NPS_SUM_THREADS, groups), dim3(NPS_SUM_THREADS), 0, s, part,
+                           used, chunks, n.n_rois, scale, sw, nps, rois_used, rois_skipped);
+        e = hipGetLastError();
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL((nps_radial_kernel<N>), dim3((N / 2 + 1 + 3) / 4, groups), dim3(NPS_THREADS), 0, s, nps, rois_used, exclude_axes, radial,
+                           radial_count);
+        return hipGetLastError();
+    });
 }
 
 }  // namespace midd

@@ -45,6 +45,51 @@ def nps_window(window, roi: int) -> Optional[torch.Tensor]:
     return w
 
 
+# ------------------------------------------------------------------------------ the preamble of a Welch call (spectral.py shares it)
+def _as5(t: torch.Tensor, name: str) -> torch.Tensor:
+    if not isinstance(t, torch.Tensor) or t.dim() not in (2, 4, 5):
+        raise ValueError(f"{name} must be a [B, K, C, H, W], [B, C, H, W] or [H, W] tensor")
+    return t[None, None, None] if t.dim() == 2 else (t[:, None] if t.dim() == 4 else t)
+
+
+def _check_fields(call: str, names: str, fields, H: int, W: int, roi: int) -> None:      # the ROI fits; one CUDA device; float32
+    if H < roi or W < roi:
+        raise ValueError(f"the image ({H} x {W}) is smaller than the ROI ({roi} x {roi}): there are no partial ROIs")
+    if len({f.device for f in fields}) > 1:
+        raise ValueError(f"{names} must be on one device (got {' and '.join(str(f.device) for f in fields)})")
+    if fields[0].device.type != "cuda":
+        raise RuntimeError(f"{call} runs only on a ROCm GPU (got {fields[0].device}): there is no CPU fallback")
+    if any(f.dtype != torch.float32 for f in fields):
+        raise TypeError(f"{names} must be float32 (got {' and '.join(str(f.dtype) for f in fields)})")
+
+
+def _packed(segments, device):
+    """The outputs of a call in ONE device buffer of 8-byte words; ``segments``: the ordered (name, words, dtype, shape).  Returns
+    ({name: device address}, host): ``host(until)`` copies the segments before the one named ``until`` (default: all) to the host
+    once -- that waits for the stream -- and returns {name: cloned host tensor of its shape}."""
+    offset, words = {}, 0
+    for name, n, _, _ in segments:
+        offset[name], words = words, words + n
+    raw = torch.empty(words, dtype=torch.int64, device=device)
+
+    def host(until=None):
+        end = words if until is None else offset[until]
+        h = raw[:end].cpu()
+        return {name: h[offset[name]:offset[name] + n].view(dtype).reshape(shape).clone() for name, n, dtype, shape in segments if offset[name] < end}
+    return {name: raw.data_ptr() + 8 * o for name, o in offset.items()}, host
+
+
+def _workspace(query, *shape, device):      # (the workspace, its bytes); a query that answers 0 raises the library's message
+    nbytes = query(*shape)
+    if nbytes == 0:
+        native.check(-1)
+    return torch.empty(nbytes // 8, dtype=torch.float64, device=device), nbytes
+
+
+def _window_arg(w: Optional[torch.Tensor]):
+    return None if w is None else (C.c_float * w.numel())(*w.tolist())
+
+
 @torch.no_grad()
 def noise_power_spectrum(a: torch.Tensor, b: Optional[torch.Tensor] = None, roi: int = 64, step: Optional[int] = None, detrend: str = "plane",
                          window="hann", scale: float = 1.0, exclude_axes: bool = False) -> NoisePowerSpectrum:
@@ -60,10 +105,8 @@ def noise_power_spectrum(a: torch.Tensor, b: Optional[torch.Tensor] = None, roi:
     scale = float(scale)
     if not math.isfinite(scale):
         raise ValueError(f"scale must be finite (got {scale!r})")
-    if not isinstance(a, torch.Tensor) or a.dim() not in (2, 4, 5):
-        raise ValueError("a must be a [B, K, C, H, W], [B, C, H, W] or [H, W] tensor")
+    a5 = _as5(a, "a")
     flat = a.dim() == 2
-    a5 = a[None, None, None] if flat else (a[:, None] if a.dim() == 4 else a)
     B, K, CH, H, W = a5.shape
     if min(B, K, CH) < 1:
         raise ValueError("a must have B >= 1, K >= 1 and C >= 1")
@@ -73,38 +116,19 @@ def noise_power_spectrum(a: torch.Tensor, b: Optional[torch.Tensor] = None, roi:
         if not isinstance(b, torch.Tensor) or tuple(b.shape) != want or b.device != a.device:
             raise ValueError(f"b must be a tensor of shape {want} on {a.device}: one image per (b, c) group, without the member axis")
         b4 = b[None, None] if flat else b
-    if H < roi or W < roi:
-        raise ValueError(f"the image ({H} x {W}) is smaller than the ROI ({roi} x {roi}): there are no partial ROIs")
-    if a.device.type != "cuda":
-        raise RuntimeError(f"noise_power_spectrum runs only on a ROCm GPU (got {a.device}): there is no CPU fallback")
-    if a.dtype != torch.float32 or (b is not None and b.dtype != torch.float32):
-        raise TypeError(f"a and b must be float32 (got {a.dtype}" + (f" and {b.dtype})" if b is not None else ")"))
-    src = a5.contiguous()
-    sub = None if b4 is None else b4.contiguous()
-    lib = native.lib()
-    dev = src.device
+    _check_fields("noise_power_spectrum", "a and b", [a] if b is None else [a, b], H, W, roi)
+    src, sub = a5.contiguous(), None if b4 is None else b4.contiguous()
+    lib, dev = native.lib(), src.device
     G, bins = B * CH, roi // 2 + 1
     with torch.cuda.device(dev):
-        # one 8-byte-word buffer for the outputs [nps G*R*R | radial G*bins | radial_count bins | used G | skipped G]: one copy to the host
-        o_rad = G * roi * roi
-        o_cnt, o_used, o_skip = o_rad + G * bins, o_rad + G * bins + bins, o_rad + G * bins + bins + G
-        raw = torch.empty(o_skip + G, dtype=torch.int64, device=dev)
-        nbytes = lib.mi_noise_power_spectrum_workspace_bytes(B, K, CH, H, W, roi, step)
-        if nbytes == 0:
-            native.check(-1)
-        ws = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
-        base = raw.data_ptr()
-        warg = None if w is None else (C.c_float * roi)(*w.tolist())
-        native.check(lib.mi_noise_power_spectrum(src.data_ptr(), _ptr(sub), B, K, CH, H, W, roi, step,
-                                                 NPS_DETREND[detrend], warg, scale, 1 if exclude_axes else 0,
-                                                 base, base + 8 * o_rad, base + 8 * o_cnt, base + 8 * o_used, base + 8 * o_skip,
-                                                 ws.data_ptr(), nbytes, torch.cuda.current_stream(dev).cuda_stream))
-        host = raw.cpu()
-    nps = host[:o_rad].view(torch.float64).reshape(B, CH, roi, roi).clone()
-    radial = host[o_rad:o_cnt].view(torch.float64).reshape(B, CH, bins).clone()
-    count = host[o_cnt:o_used].clone()
-    used, skipped = host[o_used:o_skip].reshape(B, CH).clone(), host[o_skip:].reshape(B, CH).clone()
-    if flat:
-        nps, radial, used, skipped = nps[0, 0], radial[0, 0], used[0, 0], skipped[0, 0]
-    freqs = torch.arange(bins, dtype=torch.float64) / float(roi)
-    return NoisePowerSpectrum(nps, radial, count, freqs, used, skipped, roi, step)
+        ptr, host = _packed([("nps", G * roi * roi, torch.float64, (B, CH, roi, roi)), ("radial", G * bins, torch.float64, (B, CH, bins)),
+                             ("radial_count", bins, torch.int64, (bins,)), ("rois_used", G, torch.int64, (B, CH)),
+                             ("rois_skipped", G, torch.int64, (B, CH))], dev)
+        ws, nbytes = _workspace(lib.mi_noise_power_spectrum_workspace_bytes, B, K, CH, H, W, roi, step, device=dev)
+        native.check(lib.mi_noise_power_spectrum(src.data_ptr(), _ptr(sub), B, K, CH, H, W, roi, step, NPS_DETREND[detrend], _window_arg(w), scale,
+                                                 1 if exclude_axes else 0, ptr["nps"], ptr["radial"], ptr["radial_count"], ptr["rois_used"],
+                                                 ptr["rois_skipped"], ws.data_ptr(), nbytes,
+                                                 torch.cuda.current_stream(dev).cuda_stream))
+        got = host()
+    nps, radial, used, skipped = (got[k][0, 0] if flat else got[k] for k in ("nps", "radial", "rois_used", "rois_skipped"))
+    return NoisePowerSpectrum(nps, radial, got["radial_count"], torch.arange(bins, dtype=torch.float64) / float(roi), used, skipped, roi, step)

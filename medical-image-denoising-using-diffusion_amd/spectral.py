@@ -2,14 +2,13 @@
 (include/midd.h: THE CROSS SPECTRUM)."""
 from __future__ import annotations
 
-import ctypes as C
 import math
 from typing import NamedTuple, Optional
 
 import torch
 
 from . import native
-from .nps import nps_window
+from .nps import _as5, _check_fields, _packed, _window_arg, _workspace, nps_window
 from .rules import NPS_DETREND, check_nps_args
 
 
@@ -63,12 +62,6 @@ def _first_crossing(frc, freqs, threshold):
     return 0.5
 
 
-def _as5(t: torch.Tensor, name: str):
-    if not isinstance(t, torch.Tensor) or t.dim() not in (2, 4, 5):
-        raise ValueError(f"{name} must be a [B, K, C, H, W], [B, C, H, W] or [H, W] tensor")
-    return t[None, None, None] if t.dim() == 2 else (t[:, None] if t.dim() == 4 else t)
-
-
 @torch.no_grad()
 def cross_spectrum(x: torch.Tensor, y: torch.Tensor, roi: int = 64, step: Optional[int] = None, detrend: str = "plane", window="hann",
                    exclude_axes: bool = False, return_planes: bool = False) -> CrossSpectrum:
@@ -91,45 +84,27 @@ def cross_spectrum(x: torch.Tensor, y: torch.Tensor, roi: int = 64, step: Option
                              "K; B, C, H and W must agree")
     elif tuple(x.shape) != tuple(y.shape):
         raise ValueError(f"x {tuple(x.shape)} and y {tuple(y.shape)} must have the same shape (or one [B, C, H, W] beside one [B, K, C, H, W])")
-    B, Kx, CH, H, W = x5.shape
-    Ky = y5.shape[1]
+    (B, Kx, CH, H, W), Ky = x5.shape, y5.shape[1]
     if min(B, Kx, Ky, CH) < 1:
         raise ValueError("x and y must have B >= 1, K >= 1 and C >= 1")
-    if H < roi or W < roi:
-        raise ValueError(f"the image ({H} x {W}) is smaller than the ROI ({roi} x {roi}): there are no partial ROIs")
-    if x.device != y.device:
-        raise ValueError(f"x and y must be on one device (got {x.device} and {y.device})")
-    if x.device.type != "cuda":
-        raise RuntimeError(f"cross_spectrum runs only on a ROCm GPU (got {x.device}): there is no CPU fallback")
-    if x.dtype != torch.float32 or y.dtype != torch.float32:
-        raise TypeError(f"x and y must be float32 (got {x.dtype} and {y.dtype})")
+    _check_fields("cross_spectrum", "x and y", [x, y], H, W, roi)
     xs, ys = x5.contiguous(), y5.contiguous()
-    lib = native.lib()
-    dev = xs.device
+    lib, dev = native.lib(), xs.device
     G, bins = B * CH, roi // 2 + 1
     with torch.cuda.device(dev):
-        # one 8-byte-word buffer for the outputs [radial 4*G*bins | radial_count bins | used G | skipped G | planes 4*G*R*R]: one
-        # copy to the host, without the planes unless they are asked for
-        o_cnt = 4 * G * bins
-        o_used, o_skip, o_pl = o_cnt + bins, o_cnt + bins + G, o_cnt + bins + 2 * G
-        raw = torch.empty(o_pl + 4 * G * roi * roi, dtype=torch.int64, device=dev)
-        nbytes = lib.mi_cross_spectrum_workspace_bytes(B, Kx, Ky, CH, H, W, roi, step)
-        if nbytes == 0:
-            native.check(-1)
-        ws = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
-        base = raw.data_ptr()
-        warg = None if w is None else (C.c_float * roi)(*w.tolist())
-        native.check(lib.mi_cross_spectrum(xs.data_ptr(), ys.data_ptr(), B, Kx, Ky, CH, H, W, roi, step, NPS_DETREND[detrend], warg,
-                                           1 if exclude_axes else 0, base + 8 * o_pl, base, base + 8 * o_cnt, base + 8 * o_used,
-                                           base + 8 * o_skip, ws.data_ptr(), nbytes, torch.cuda.current_stream(dev).cuda_stream))
-        host = (raw if return_planes else raw[:o_pl]).cpu()
-    radial = host[:o_cnt].view(torch.float64).reshape(4, B, CH, bins).clone()
-    count = host[o_cnt:o_used].clone()
-    used, skipped = host[o_used:o_skip].reshape(B, CH).clone(), host[o_skip:o_pl].reshape(B, CH).clone()
-    planes = host[o_pl:].view(torch.float64).reshape(4, B, CH, roi, roi).clone() if return_planes else None
+        # the planes last: they are copied to the host only if they are asked for
+        ptr, host = _packed([("radial", 4 * G * bins, torch.float64, (4, B, CH, bins)), ("radial_count", bins, torch.int64, (bins,)),
+                             ("rois_used", G, torch.int64, (B, CH)), ("rois_skipped", G, torch.int64, (B, CH)),
+                             ("planes", 4 * G * roi * roi, torch.float64, (4, B, CH, roi, roi))], dev)
+        ws, nbytes = _workspace(lib.mi_cross_spectrum_workspace_bytes, B, Kx, Ky, CH, H, W, roi, step, device=dev)
+        native.check(lib.mi_cross_spectrum(xs.data_ptr(), ys.data_ptr(), B, Kx, Ky, CH, H, W, roi, step, NPS_DETREND[detrend], _window_arg(w),
+                                           1 if exclude_axes else 0, ptr["planes"], ptr["radial"], ptr["radial_count"], ptr["rois_used"],
+                                           ptr["rois_skipped"], ws.data_ptr(), nbytes, torch.cuda.current_stream(dev).cuda_stream))
+        got = host(None if return_planes else "planes")
+    radial, used, skipped, planes = got["radial"], got["rois_used"], got["rois_skipped"], got.get("planes")
     if flat:
         radial, used, skipped = radial[:, 0, 0], used[0, 0], skipped[0, 0]
         planes = None if planes is None else planes[:, 0, 0]
     freqs = torch.arange(bins, dtype=torch.float64) / float(roi)
     pl = (None,) * 4 if planes is None else tuple(planes)
-    return CrossSpectrum(*pl, *tuple(radial), count, freqs, used, skipped, roi, step)
+    return CrossSpectrum(*pl, *tuple(radial), got["radial_count"], freqs, used, skipped, roi, step)

@@ -1,14 +1,15 @@
-// Host-side sanitizer harness for the executor, sampler and batched units (midd_exec.hip, midd_sampler.hip, midd_batched.hip): a
-// stand-alone program that drives every mi_* entry of the three down a refusal path on an unfinalized plan -- null, negative,
-// overflowing and aliasing arguments -- and the two coefficient tables on 1-, 2- and 9-entry lists.  Nothing reaches a GPU: every
-// call must return before its first launch, so it runs on a machine without one.  Build the six host units with the sanitizers on
-// the host side only and link them with the kernel units of an ordinary build (make -C .../csrc):
+// Host-side sanitizer harness for the executor, sampler, batched and analysis units (midd_exec.hip, midd_sampler.hip, midd_batched.hip,
+// midd_analysis.hip): a stand-alone program that drives every mi_* entry of the four down a refusal path -- on an unfinalized plan
+// where there is one -- with null, negative, overflowing, misaligned and aliasing arguments, and the two coefficient tables on 1-, 2-
+// and 9-entry lists.  Nothing reaches a GPU: every call must return before its first launch, so it runs on a machine without one.
+// Build the seven host units with the sanitizers on the host side only and link them with the kernel units of an ordinary build
+// (make -C .../csrc):
 //   C=medical-image-denoising-using-diffusion_amd/csrc; S="-Xarch_host -fsanitize=address,undefined -Xarch_host -fno-omit-frame-pointer"
-//   for u in midd_abi midd_weights midd_planner midd_exec midd_sampler midd_batched; do
-//     hipcc -O1 -g -std=c++17 -fPIC --offload-arch=gfx950 $S -c $C/$u.hip -o /tmp/san_$u.o; done
+//   U="midd_abi midd_weights midd_planner midd_exec midd_sampler midd_batched midd_analysis"
+//   for u in $U; do hipcc -O1 -g -std=c++17 -fPIC --offload-arch=gfx950 $S -c $C/$u.hip -o /tmp/san_$u.o; done
 //   hipcc -O1 -g -std=c++17 --offload-arch=gfx950 $S -c tools/host_refusals.hip -o /tmp/san_main.o
 //   hipcc --offload-arch=gfx950 -fsanitize=address,undefined /tmp/san_*.o \
-//     $(ls $C/build/*.o | grep -v -e midd_abi -e midd_weights -e midd_planner -e midd_exec -e midd_sampler -e midd_batched) -o /tmp/host_refusals
+//     $(ls $C/build/*.o | grep -v $(printf -- "-e %s.o " $U)) -o /tmp/host_refusals
 //   /tmp/host_refusals        # prints the number of calls checked; exit status 1 on a call that did not answer as expected
 #include "../include/midd.h"
 #include <cstdio>
@@ -138,7 +139,7 @@ int main() {
     REFUSED(mi_step_noise_fill_member(A, 2, 2, 1, 32, 32, 5, 0, (int64_t)1 << 32, nullptr));
     ACCEPTED(mi_step_noise_fill_member(nullptr, 0, 2, 1, 32, 32, 5, 0, 0, nullptr));
 
-    // ---- midd_batched.hip: the stand-alone reduce, quantile, tile and view calls
+    // ---- midd_analysis.hip: the stand-alone reduce, quantile, scores, modes and spectrum calls
     const double q_ok[2] = {0.1, 0.9}, q_bad[2] = {0.1, 1.5};
     REFUSED(mi_ensemble_reduce(A, 2, 0, 1024, B_, C_, nullptr));
     REFUSED(mi_ensemble_reduce(A, 65536, 4, 1024, B_, C_, nullptr));
@@ -153,6 +154,80 @@ int main() {
     REFUSED(mi_ensemble_quantiles(A, 2, 4, 1024, nullptr, 2, B_, nullptr));
     REFUSED(mi_ensemble_quantiles(A, 2, 4, 1024, q_bad, 2, B_, nullptr));
     REFUSED(mi_ensemble_quantiles(A, 2, 4, 1024, q_ok, 2, nullptr, nullptr));
+    // (8-byte aligned outputs at 1 MiB steps: doubles F, G; the unsigned counters U1 .. U3 of the scores and modes; the signed counts
+    // I1 .. I3 of the spectra)
+    double *F = (double*)0x700000, *G = (double*)0x800000;
+    uint64_t *U1 = (uint64_t*)0x900000, *U2 = (uint64_t*)0xA00000, *U3 = (uint64_t*)0xB00000;
+    int64_t *I1 = (int64_t*)0xC00000, *I2 = (int64_t*)0xD00000, *I3 = (int64_t*)0xE00000;
+    REFUSED(mi_ensemble_scores_workspace_bytes(0, 4, 1024) == 0);
+    REFUSED(mi_ensemble_scores_workspace_bytes(2, 65, 1024) == 0);
+    ACCEPTED(mi_ensemble_scores_workspace_bytes(2, 4, 1024) == 0);
+    REFUSED(mi_ensemble_scores(A, B_, 0, 4, 1024, q_ok, 2, F, U1, U2, U3, C_, WS, WSB, nullptr));
+    REFUSED(mi_ensemble_scores(A, B_, 2, 65, 1024, q_ok, 2, F, U1, U2, U3, C_, WS, WSB, nullptr));
+    REFUSED(mi_ensemble_scores(A, B_, 2, 4, (int64_t)1 << 32, q_ok, 2, F, U1, U2, U3, C_, WS, WSB, nullptr));
+    REFUSED(mi_ensemble_scores(A, B_, 2, 4, 1024, q_ok, 9, F, U1, U2, U3, C_, WS, WSB, nullptr));
+    REFUSED(mi_ensemble_scores(A, B_, 2, 4, 1024, q_bad, 2, F, U1, U2, U3, C_, WS, WSB, nullptr));
+    REFUSED(mi_ensemble_scores(A, B_, 2, 4, 1024, nullptr, 2, F, U1, U2, U3, C_, WS, WSB, nullptr));
+    REFUSED(mi_ensemble_scores(A, B_, 2, 4, 1024, q_ok, 2, nullptr, U1, U2, U3, C_, WS, WSB, nullptr));
+    REFUSED(mi_ensemble_scores(A, B_, 2, 4, 1024, q_ok, 2, F, U1, U2, nullptr, C_, WS, WSB, nullptr));
+    REFUSED(mi_ensemble_scores(A, B_, 2, 4, 1024, nullptr, 0, F, U1, U2, U3, C_, WS, WSB, nullptr));
+    REFUSED(mi_ensemble_scores(A, B_, 2, 4, 1024, q_ok, 2, F, (uint64_t*)((char*)U1 + 4), U2, U3, C_, WS, WSB, nullptr));
+    REFUSED(mi_ensemble_scores(A, (float*)((char*)B_ + 2), 2, 4, 1024, q_ok, 2, F, U1, U2, U3, C_, WS, WSB, nullptr));
+    REFUSED(mi_ensemble_scores(A, B_, 2, 4, 1024, q_ok, 2, F, U1, U2, U3, C_, WS, 8, nullptr));
+    REFUSED(mi_ensemble_scores(A, B_, 2, 4, 1024, q_ok, 2, F, U1, (uint64_t*)(F + 1), U3, C_, WS, WSB, nullptr));
+    REFUSED(mi_ensemble_gram_workspace_bytes(2, 1, 1024) == 0);
+    ACCEPTED(mi_ensemble_gram_workspace_bytes(2, 12, 5000) == 0);
+    REFUSED(mi_ensemble_gram(A, 65536, 4, 1024, F, U1, WS, WSB, nullptr));
+    REFUSED(mi_ensemble_gram(A, 2, 1, 1024, F, U1, WS, WSB, nullptr));
+    REFUSED(mi_ensemble_gram(A, 2, 4, 0, F, U1, WS, WSB, nullptr));
+    REFUSED(mi_ensemble_gram(A, 2, 4, 1024, nullptr, U1, WS, WSB, nullptr));
+    REFUSED(mi_ensemble_gram(A, 2, 4, 1024, (double*)((char*)F + 4), U1, WS, WSB, nullptr));
+    REFUSED(mi_ensemble_gram((float*)((char*)A + 1), 2, 4, 1024, F, U1, WS, WSB, nullptr));
+    REFUSED(mi_ensemble_gram(A, 2, 4, 1024, F, U1, WS, 8, nullptr));
+    REFUSED(mi_ensemble_gram(A, 2, 4, 1024, F, (uint64_t*)(F + 2), WS, WSB, nullptr));
+    REFUSED(mi_ensemble_project(A, 2, 65, 1024, F, 2, B_, nullptr));
+    REFUSED(mi_ensemble_project(A, 2, 4, 1024, F, 9, B_, nullptr));
+    REFUSED(mi_ensemble_project(A, 2, 4, 1024, nullptr, 2, B_, nullptr));
+    REFUSED(mi_ensemble_project(A, 2, 4, 1024, (double*)((char*)F + 4), 2, B_, nullptr));
+    REFUSED(mi_ensemble_project(A, 2, 4, 1024, F, 2, (float*)((char*)B_ + 2), nullptr));
+    REFUSED(mi_ensemble_project(A, 2, 4, 1024, F, 2, A + 8, nullptr));
+    // the spectra: the host window is the one thing a refusal path reads, and only after every other rule (32 entries, the last not finite)
+    float win[32];
+    for (int i = 0; i < 32; ++i) win[i] = 0.5f;
+    win[31] = win[31] / 0.0f;
+    const size_t nps_ws = mi_noise_power_spectrum_workspace_bytes(2, 3, 1, 70, 83, 32, 16), xs_ws = mi_cross_spectrum_workspace_bytes(2, 3, 3, 1, 70, 83, 32, 16);
+    ACCEPTED(nps_ws == 0 || xs_ws == 0);
+    REFUSED(mi_noise_power_spectrum_workspace_bytes(2, 3, 1, 70, 83, 48, 16) == 0);
+    REFUSED(mi_noise_power_spectrum_workspace_bytes(1, 17, 1, 46371, 46371, 32, 1) == 0);
+    REFUSED(mi_cross_spectrum_workspace_bytes(2, 2, 3, 1, 70, 83, 32, 16) == 0);
+    REFUSED(mi_noise_power_spectrum(A, B_, 2, 3, 1, 70, 83, 48, 16, 2, win, 1.0, 0, F, G, I1, I2, I3, WS, nps_ws, nullptr));
+    REFUSED(mi_noise_power_spectrum(A, B_, 2, 3, 1, 70, 83, 32, 0, 2, win, 1.0, 0, F, G, I1, I2, I3, WS, nps_ws, nullptr));
+    REFUSED(mi_noise_power_spectrum(A, B_, 65536, 3, 1, 70, 83, 32, 16, 2, win, 1.0, 0, F, G, I1, I2, I3, WS, nps_ws, nullptr));
+    REFUSED(mi_noise_power_spectrum(A, B_, 2, 3, 1, 31, 83, 32, 16, 2, win, 1.0, 0, F, G, I1, I2, I3, WS, nps_ws, nullptr));
+    REFUSED(mi_noise_power_spectrum(A, B_, 2, 3, 1, 70000, 70000, 32, 1, 2, win, 1.0, 0, F, G, I1, I2, I3, WS, nps_ws, nullptr));
+    REFUSED(mi_noise_power_spectrum(A, B_, 2, 3, 1, 70, 83, 32, 16, 3, win, 1.0, 0, F, G, I1, I2, I3, WS, nps_ws, nullptr));
+    REFUSED(mi_noise_power_spectrum(A, B_, 2, 3, 1, 70, 83, 32, 16, 2, win, 1.0, 2, F, G, I1, I2, I3, WS, nps_ws, nullptr));
+    REFUSED(mi_noise_power_spectrum(A, B_, 2, 3, 1, 70, 83, 32, 16, 2, win, 1.0 / 0.0, 0, F, G, I1, I2, I3, WS, nps_ws, nullptr));
+    REFUSED(mi_noise_power_spectrum(A, nullptr, 2, 3, 1, 70, 83, 32, 16, 2, win, 1.0, 0, nullptr, G, I1, I2, I3, WS, nps_ws, nullptr));
+    REFUSED(mi_noise_power_spectrum(A, B_, 2, 3, 1, 70, 83, 32, 16, 2, win, 1.0, 0, F, (double*)((char*)G + 4), I1, I2, I3, WS, nps_ws, nullptr));
+    REFUSED(mi_noise_power_spectrum(A, (float*)((char*)B_ + 1), 2, 3, 1, 70, 83, 32, 16, 2, win, 1.0, 0, F, G, I1, I2, I3, WS, nps_ws, nullptr));
+    REFUSED(mi_noise_power_spectrum(A, B_, 2, 3, 1, 70, 83, 32, 16, 2, win, 1.0, 0, F, G, I1, I2, I3, WS, nps_ws - 1, nullptr));
+    REFUSED(mi_noise_power_spectrum(A, A + 70 * 83, 2, 3, 1, 70, 83, 32, 16, 2, win, 1.0, 0, F, G, I1, I2, I3, WS, nps_ws, nullptr));
+    REFUSED(mi_noise_power_spectrum(A, B_, 2, 3, 1, 70, 83, 32, 16, 2, win, 1.0, 0, F, G, I1, (int64_t*)(F + 1), I3, WS, nps_ws, nullptr));
+    REFUSED(mi_noise_power_spectrum(A, nullptr, 2, 3, 1, 70, 83, 32, 16, 2, win, 1.0, 0, F, G, I1, I2, I3, WS, nps_ws, nullptr));      // valid but for the window
+    REFUSED(mi_cross_spectrum(A, B_, 2, 3, 0, 1, 70, 83, 32, 16, 2, win, 0, F, G, I1, I2, I3, WS, xs_ws, nullptr));
+    REFUSED(mi_cross_spectrum(A, B_, 2, 2, 3, 1, 70, 83, 32, 16, 2, win, 0, F, G, I1, I2, I3, WS, xs_ws, nullptr));
+    REFUSED(mi_cross_spectrum(A, B_, 2, 3, 3, 1, 70, 83, 64, 16, 2, win, 0, F, G, I1, I2, I3, WS, xs_ws, nullptr));      // (roi 64: a valid shape, the workspace of roi 32)
+    REFUSED(mi_cross_spectrum(A, B_, 2, 3, 3, 1, 70, 83, 32, 16, -1, win, 0, F, G, I1, I2, I3, WS, xs_ws, nullptr));
+    REFUSED(mi_cross_spectrum(A, B_, 2, 3, 3, 1, 70, 83, 32, 16, 2, win, -1, F, G, I1, I2, I3, WS, xs_ws, nullptr));
+    REFUSED(mi_cross_spectrum(A, nullptr, 2, 3, 3, 1, 70, 83, 32, 16, 2, win, 0, F, G, I1, I2, I3, WS, xs_ws, nullptr));
+    REFUSED(mi_cross_spectrum(A, B_, 2, 3, 3, 1, 70, 83, 32, 16, 2, win, 0, F, G, I1, I2, (int64_t*)((char*)I3 + 2), WS, xs_ws, nullptr));
+    REFUSED(mi_cross_spectrum((float*)((char*)A + 2), B_, 2, 3, 3, 1, 70, 83, 32, 16, 2, win, 0, F, G, I1, I2, I3, WS, xs_ws, nullptr));
+    REFUSED(mi_cross_spectrum(A, B_, 2, 3, 3, 1, 70, 83, 32, 16, 2, win, 0, F, G, I1, I2, I3, WS, 0, nullptr));
+    REFUSED(mi_cross_spectrum(A, B_, 2, 3, 3, 1, 70, 83, 32, 16, 2, win, 0, (double*)(B_ + 2), G, I1, I2, I3, WS, xs_ws, nullptr));
+    REFUSED(mi_cross_spectrum(A, B_, 2, 3, 3, 1, 70, 83, 32, 16, 2, win, 0, F, F + 4 * 2 * 32 * 32 - 1, I1, I2, I3, WS, xs_ws, nullptr));
+    REFUSED(mi_cross_spectrum(A, A, 2, 3, 3, 1, 70, 83, 32, 16, 2, win, 0, F, G, I1, I2, I3, WS, xs_ws, nullptr));      // x == y is allowed: the window
+    // ---- midd_batched.hip: the stand-alone tile and view calls
     int n_tiles = 0, origins[8];
     ACCEPTED(mi_tile_geometry(90, 32, 8, &n_tiles, origins, 8));
     ACCEPTED(mi_tile_geometry(90, 32, 8, &n_tiles, origins, 1));      // more tiles than `cap`: only cap origins are written
