@@ -419,6 +419,42 @@ int mi_ensemble_gram(const float* samples, int B, int members, int64_t chw, doub
 int mi_ensemble_project(const float* samples, int B, int members, int64_t chw, const double* weights, int n_modes,
                         float* out, void* stream);
 
+/* CHANNEL RESPONSES (no plan needed): is a faint signal easier or harder to see after the run?  The task-based answer is a model
+ * observer: many noisy realisations with and without a known signal go through the system, and a channelized Hotelling observer is
+ * asked how well it separates the two classes.  Its statistics are a host matter on [rows][C] doubles; its hot path is this call: the
+ * responses of N planes at L locations to C channel templates, i.e. N * L * C dot products over R x R regions of interest (ROIs), in
+ * one fixed order.
+ * THE CHANNEL RESPONSES (fixed; independent of the launch geometry, the load width and the alignment).  The ROI of the centre
+ * (cy, cx) = centres[l] has its origin at y0 = cy - R / 2, x0 = cx - R / 2 (integer division) and covers rows y0 .. y0 + R - 1 and
+ * columns x0 .. x0 + R - 1: the centre pixel has ROI index (R / 2, R / 2), R odd or even.  With p = y R + x, u_c[p] =
+ * channels[c][y][x] and g_p = (double)x[n][y0 + y][x0 + x]; double precision, every operation rounded to nearest on its own, no
+ * fused multiply-add:
+ *   lanes        lane j = 0 .. 63 starts from 0 and adds u_c[p] * g_p (the product rounded, then added) for p = j, j + 64, j + 128, ..
+ *                below R * R, in increasing order;
+ *   tree         the 64 lane sums are folded by  for off = 32, 16, .., 1: v[j] += v[j + off]  for j < off;
+ *   response     out[n][l][c] is the root v[0].
+ *   invalid      an ROI that holds a pixel that is not finite (NaN, +-inf) is INVALID: invalid[n][l] = 1 and its C responses are the
+ *                canonical quiet NaN 0x7FF8000000000000.  Every other ROI has invalid[n][l] = 0.  A pixel outside every ROI is never
+ *                read and has no effect.  The channels are the caller's and should be finite.
+ * ROIs may overlap or repeat; each is computed on its own.
+ * Arguments
+ *   x            device fp32 [N][H][W], contiguous planes, 4-byte aligned
+ *   centres      HOST int32 [L][2] as (cy, cx), as the timestep lists of the sampler calls are host arrays: read and judged before
+ *                any GPU work and not needed after the call returns.  The origins travel as kernel arguments, 512 locations a
+ *                launch, so the call needs no workspace
+ *   channels     device double [C][R][R], 8-byte aligned
+ *   out          device double [N][L][C], 8-byte aligned
+ *   invalid      device uint32 [N][L], 4-byte aligned; every entry is written
+ * The planes are read element by element whatever the alignment: there is one load path.  The call allocates nothing, is
+ * asynchronous and needs no plan.
+ * MI_EINVAL before any GPU work, the rule named in mi_last_error, judged in this order: N outside [1, 65535]; H outside [1, 32768];
+ * W outside [1, 32768]; R outside [4, 128]; L outside [1, 4096]; C outside [1, 32]; an ROI that leaves the image -- y0 < 0, x0 < 0,
+ * y0 + R > H or x0 + R > W: refused, not clipped, the first such centre named (a null centres is "null argument" here: the rule
+ * reads it); a null x, channels, out or invalid; channels or out not 8-byte aligned; x or invalid not 4-byte aligned; any two of x,
+ * channels, out and invalid overlapping. */
+int mi_channel_responses(const float* x, int N, int H, int W, const int32_t* centres, int L, int R, const double* channels, int C,
+                         double* out, uint32_t* invalid, void* stream);
+
 /* NOISE POWER SPECTRUM (no plan needed): what does the remaining noise look like?  The per-pixel scores above say how large a
  * residual or an ensemble's spread is; the noise power spectrum (NPS) says at which spatial frequencies it lives.  Welch's method as
  * in IEC 62220-1: overlapping regions of interest (ROIs) are detrended, windowed, transformed, their periodograms averaged and the

@@ -17,5 +17,6 @@ from .sampler import (DiffusionDenoiser, EnsembleQuantileResult, EnsembleResult,
                       TiledSelfEnsembleQuantileResult, TiledSelfEnsembleResult, tile_blend_unview_quantiles, tile_blend_unview_reduce,
                       view_codes_tiled, DenoisingLoss, LossMaps, LossProfile, loss_terms, noise_images, EnsembleScores,
                       ensemble_scores, NoisePowerSpectrum, noise_power_spectrum, nps_window, CrossSpectrum, cross_spectrum,
-                      EnsembleModes, ensemble_modes)
+                      EnsembleModes, ensemble_modes, ChannelResponses, Detectability, DetectabilityStudy, channel_responses, hotelling,
+                      insert_signal, laguerre_gauss_channels, roi_grid)
 from .session import SamplerSession, Ticket  # noqa: F401

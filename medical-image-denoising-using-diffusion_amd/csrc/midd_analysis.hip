@@ -1,5 +1,5 @@
 // The stand-alone analysis calls (no plan, no schedule, no pass): the reduce and quantile maps of an ensemble, its scores against a
-// truth, its principal modes, the noise power spectrum and the cross-spectrum.  Each judges its rules in the order include/midd.h
+// truth, its principal modes, the channel responses of a model observer, the noise power spectrum and the cross-spectrum.  Each judges its rules in the order include/midd.h
 // documents, before anything is read, and ends in one launch wrapper.  The member / batch / level rules that the batched calls
 // (midd_batched.hip) compose are defined here and declared in midd_sampler.h.
 #include <algorithm>
@@ -176,6 +176,38 @@ extern "C" int mi_ensemble_project(const float* samples, int B, int members, int
                         {out, (size_t)B * n_modes * img, "out"}};
     if (int rc = check_no_overlap(buf, 3, "samples and weights are read while out is written")) return rc;
     return launched(ensemble_project_launch(samples, B, members, (unsigned long long)chw, weights, n_modes, out, (hipStream_t)stream), "ensemble_project");
+}
+
+// ---------------------------------------------------------------------------- the channel responses of a model observer
+// (channel_responses.hip; include/midd.h: THE CHANNEL RESPONSES).  centres is a HOST table, as the timestep lists of the sampler calls
+// are: its rule is judged here, before any GPU work
+static int check_range(const char* name, int v, int lo, int hi, const char* why) {
+    return (v >= lo && v <= hi) ? MI_OK : fail(MI_EINVAL, "%s %d outside [%d, %d] (%s)", name, v, lo, hi, why);
+}
+
+extern "C" int mi_channel_responses(const float* x, int N, int H, int W, const int32_t* centres, int L, int R, const double* channels, int C,
+                                    double* out, uint32_t* invalid, void* stream) {
+    if (int rc = check_range("N", N, 1, CR_MAX_PLANES, "limit of the kernel's grid")) return rc;
+    if (int rc = check_range("H", H, 1, CR_MAX_SIDE, "an ROI origin travels as two 16-bit kernel arguments")) return rc;
+    if (int rc = check_range("W", W, 1, CR_MAX_SIDE, "an ROI origin travels as two 16-bit kernel arguments")) return rc;
+    if (int rc = check_range("R", R, CR_MIN_ROI, CR_MAX_ROI, "the side of an ROI, odd or even")) return rc;
+    if (int rc = check_range("L", L, 1, CR_MAX_LOCATIONS, "the locations of a call")) return rc;
+    if (int rc = check_range("C", C, 1, CR_MAX_CHANNELS, "the channels of a call")) return rc;
+    if (!centres) return fail(MI_EINVAL, "null argument");                    // (the next rule reads it)
+    for (int l = 0; l < L; ++l) {
+        const int cy = centres[2 * l], cx = centres[2 * l + 1];
+        const long long y0 = (long long)cy - R / 2, x0 = (long long)cx - R / 2;
+        if (y0 < 0 || x0 < 0 || y0 + R > H || x0 + R > W)
+            return fail(MI_EINVAL, "centre %d = (%d, %d): its ROI of side %d, rows %lld .. %lld and columns %lld .. %lld, leaves the %d x %d image "
+                        "(an ROI is refused, not clipped)", l, cy, cx, R, y0, y0 + R - 1, x0, x0 + R - 1, H, W);
+    }
+    if (!x || !channels || !out || !invalid) return fail(MI_EINVAL, "null argument");
+    if (int rc = check_aligned({channels, out}, 8, "channels and out must be 8-byte aligned")) return rc;
+    if (int rc = check_aligned({x, invalid}, 4, "x and invalid must be 4-byte aligned")) return rc;
+    const Buf buf[4] = {{x, (size_t)N * H * W * sizeof(float), "x"}, {channels, (size_t)C * R * R * sizeof(double), "channels"},
+                        {out, (size_t)N * L * C * sizeof(double), "out"}, {invalid, (size_t)N * L * sizeof(uint32_t), "invalid"}};
+    if (int rc = check_no_overlap(buf, 4, "x and channels are read while out and invalid are written")) return rc;
+    return launched(channel_responses_launch(x, N, H, W, centres, L, R, channels, C, out, invalid, (hipStream_t)stream), "channel_responses");
 }
 
 // ---------------------------------------------------------------------------- the Welch spectra

@@ -410,6 +410,13 @@ hipError_t ensemble_gram_launch(const float* samples, int B, int K, unsigned lon
                                 double* ws, hipStream_t s);
 hipError_t ensemble_project_launch(const float* samples, int B, int K, unsigned long long chw, const double* weights, int M, float* out, hipStream_t s);
 
+// The responses of planes to channel templates (channel_responses.hip; include/midd.h: THE CHANNEL RESPONSES).  x [N][H][W], centres a
+// HOST table [L][2] of (cy, cx) whose ROIs of side R all lie inside the image, channels double [C][R][R] on the device -> out double
+// [N][L][C], invalid uint32 [N][L].  The origins travel as kernel arguments, 512 locations a launch
+constexpr int CR_MAX_PLANES = 65535, CR_MAX_SIDE = 32768, CR_MIN_ROI = 4, CR_MAX_ROI = 128, CR_MAX_LOCATIONS = 4096, CR_MAX_CHANNELS = 32;
+hipError_t channel_responses_launch(const float* x, int N, int H, int W, const int32_t* centres, int L, int R, const double* channels, int C,
+                                    double* out, uint32_t* invalid, hipStream_t s);
+
 // The noise power spectrum of f = a - b (nps.hip; include/midd.h: THE NOISE POWER SPECTRUM).  a [B][K][C][H][W], b [B][C][H][W] or
 // null; R in {32, 64, 128}, S >= 1, detrend 0 none / 1 mean / 2 plane, window a HOST table of R floats or null -> nps double
 // [B*C][R][R], radial double [B*C][R/2+1], radial_count [R/2+1], rois_used and rois_skipped [B*C]; ws: nps_workspace_bytes (the chunk

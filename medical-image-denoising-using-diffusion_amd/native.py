@@ -94,6 +94,8 @@ SYMBOLS = [
     ("mi_ensemble_gram_workspace_bytes", C.c_size_t, [C.c_int, C.c_int, C.c_int64]),
     ("mi_ensemble_gram", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     ("mi_ensemble_project", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    ("mi_channel_responses", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_void_p, C.c_int,
+                                      C.c_void_p, C.c_void_p, C.c_void_p]),
     ("mi_noise_power_spectrum_workspace_bytes", C.c_size_t, [C.c_int] * 7),
     ("mi_noise_power_spectrum", C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 8 + [C.POINTER(C.c_float), C.c_double, C.c_int] +
                                          [C.c_void_p] * 5 + [C.c_void_p, C.c_size_t, C.c_void_p]),

@@ -23,6 +23,8 @@ from .ensemble import (DEFAULT_SCORE_LEVELS, EnsembleModes, EnsembleQuantileResu
 from .loss import (DenoisingLoss, LossMaps, LossProfile, _loss_tensor, check_loss_source, loss_counter_args, loss_table_args,  # noqa: F401
                    loss_terms, noise_images)
 from .nps import NoisePowerSpectrum, noise_power_spectrum, nps_window  # noqa: F401
+from .observer import (ChannelResponses, Detectability, DetectabilityStudy, channel_responses, detectability_study, hotelling,  # noqa: F401
+                       insert_signal, laguerre_gauss_channels, roi_grid)
 from .spectral import CrossSpectrum, cross_spectrum  # noqa: F401
 from .rules import (MAX_QUANTILE_LEVELS, MAX_QUANTILE_MEMBERS, NPS_DETREND, NPS_ROIS, UPDATE_RULES, SamplerRule, _integer,  # noqa: F401
                     _levels_arg, _pair, check_levels, check_member, check_members, check_nps_args, check_quantile_members, check_rule,
@@ -484,6 +486,41 @@ class DiffusionDenoiser:
         result = self._ensemble_with_samples(noisy, tile, overlap, inference_steps=inference_steps, members=members, seed=seed,
                                              sample_offset=sample_offset, member_offset=member_offset, max_batch=max_batch)
         return result, cross_spectrum(result.samples[:, 0::2], result.samples[:, 1::2], roi, step, detrend, window, exclude_axes, return_planes)
+
+    @torch.no_grad()
+    def detectability(self, background: torch.Tensor, signal, inference_steps: int = 25, trials: int = 64, centres=None,
+                      amplitude: float = 1.0, sigma: float = 0.05, seed: Optional[int] = None, channels=None, n_channels: int = 6,
+                      width: Optional[float] = None, roi: Optional[int] = None, train: Optional[int] = None, max_batch: int = 16,
+                      degrade=None, return_images: bool = False) -> DetectabilityStudy:
+        """Is a faint signal easier or harder to see after the run?  A signal-known-exactly, location-known detection study with a
+        channelized Hotelling observer -> ``DetectabilityStudy(denoised, noisy, responses_denoised, responses_noisy, centres,
+        channels, seed, images)``: the observer's d' and AUC on the sampler's outputs beside the same observer on its noisy inputs.
+        Not a reference call.
+
+        ``background``: one clean single-channel image, [H, W] or [1, 1, H, W] (anything else, or a model with more than one image
+        channel, is refused by name).  ``signal``: [h, w], added with ``insert_signal(background, signal, centres, amplitude)`` on
+        every centre.  ``roi`` defaults to the signal's larger side rounded up to a multiple of 8 and to at least 16, ``centres`` to
+        ``roi_grid(H, W, roi)``, ``channels`` to ``laguerre_gauss_channels(roi, n_channels, width)``; ``seed=None`` draws a seed as
+        ``denoise_ensemble`` does and the result carries it.
+
+        Trial j = 0 .. 2 * trials - 1 is signal-absent for j < trials and signal-present otherwise.  Its noisy image is
+        clamp(bg_k + float32(sigma) * eps_j, 0, 1) with bg_0 the background, bg_1 the background with the signal, and eps_j the eps
+        that ``noise_images(bg, t, seed=seed, sample_offset=j, draw=0)`` returns: THE FORWARD NOISE words (include/midd.h), which
+        no sampler step draws, so the measurement noise is independent of the cddpm step noise of the same seed.
+        ``degrade(clean_batch, first_index) -> noisy_batch`` replaces that rule when given.  The trials run in index order, in
+        passes of ``max_batch``, through the unchanged ``denoise``: cddpm with ``seed=seed, sample_offset=j`` -- trial j is that
+        image's plain seeded run --, DDIM unseeded.  One ``channel_responses`` launch then runs over the 2 * trials outputs and one
+        over the noisy inputs, and ``hotelling(absent rows, present rows, train)`` is applied to each with the L locations of an
+        image pooled as rows in (trial, location) order.  The call is exactly that chain, bit for bit; with
+        ``batch_invariant=True`` it does not depend on ``max_batch``.
+
+        Pooling treats the locations of one image as independent samples.  They share the image's noise realisation only through
+        the network's receptive field and the background differs between them, so the pooled d' is an average over locations and
+        its rows are less independent than their count suggests.  ``train=None`` scores the rows the template was built from
+        (resubstitution, biased upwards); ``train=k`` holds out all but the first k pooled rows of each class (``hotelling``)."""
+        return detectability_study(self, background, signal, inference_steps=inference_steps, trials=trials, centres=centres,
+                                   amplitude=amplitude, sigma=sigma, seed=seed, channels=channels, n_channels=n_channels, width=width,
+                                   roi=roi, train=train, max_batch=max_batch, degrade=degrade, return_images=return_images)
 
     # ------------------------------------------------------------------ the training objective as an evaluation
     def sample_timesteps(self, n: int, generator: Optional[torch.Generator] = None) -> torch.Tensor:
