@@ -1032,6 +1032,66 @@ int mi_denoise_slots_rule(mi_plan* plan, const float* cond, float* x, int B, int
                           const float* step_noise, int seeded, uint64_t seed, int flags,
                           const mi_update_rule* rule, void* workspace, size_t workspace_bytes, void* stream);
 
+/* TILED DENOISING, FUSED: the overlapping tiles agree after EVERY step.  mi_denoise_tiled runs the whole sampler loop on each tile
+ * alone and cross-fades what the tiles ended up with; the network has attention, so two tiles make different global decisions about
+ * the strip they share, and the ramp only hides it.  Here the steps are the outer loop and the overlapping STATES are fused after
+ * each one (MultiDiffusion / Mixture of Diffusers), so every tile enters the next forward with the same values wherever it shares
+ * pixels with a neighbour.  The seeded step noise belongs to the image (mi_denoise_tiled: `seeded`), so overlapping tiles draw the
+ * same noise at the same pixel and averaging their states does not shrink the noise variance in the overlaps.
+ *
+ * THE CONSENSUS (fixed; no plan needed).  tiles device fp32 [B][ny*nx][C][th][tw], IN PLACE; image_out device fp32 [B][C][H][W] or
+ * NULL.  For every image pixel
+ *   v = the value of mi_tile_blend over the tiles that cover it: the same walk in ascending (ky, kx), the same double arithmetic
+ *       with every operation rounded on its own and no fused multiply-add, one rounding to fp32 (THE ARITHMETIC above)
+ *   v is written to that pixel's element in EVERY covering tile, and to image_out if one is given.
+ * By definition the tiles afterwards are mi_tile_extract(mi_tile_blend(tiles)) and image_out is mi_tile_blend(tiles), bit for bit,
+ * whatever the launch geometry, the alignment of the pointers or the load width the kernel picks; the call is idempotent.  A pixel
+ * under one tile keeps its value as mi_tile_blend keeps it.  One launch, one pass, no image-sized temporary: per pixel `cover`
+ * reads and `cover` (+ 1) writes.  In place is safe because a tile element lies over exactly one pixel and the thread that owns a
+ * pixel reads all of its covering elements before it writes any.  No atomics.
+ * MI_EINVAL before any GPU work: everything mi_tile_blend refuses (the geometry rules, C*H*W >= 2^32, B * tiles > 2^31 - 1,
+ * overlap > 46339, null tiles), and an image_out that overlaps tiles. */
+int mi_tile_consensus(float* tiles, int B, int C, int H, int W, int th, int tw, int oy, int ox, float* image_out /* or NULL */, void* stream);
+
+/* The step-outer tiled sampler.  Arguments as mi_denoise_tiled_rule, plus x0_hist: DEVICE fp32 [B*ny*nx, C, th, tw], every tile's own
+ * previous predicted image -- required under MI_UPDATE_DPMPP2M (which this call takes, with seeded == 0), NULL under every other rule.
+ * THE SPECIFICATION is this composition of public calls, which the call equals BIT FOR BIT at the same pass_samples and flags:
+ *   cond[v] = tile v of noisy (mi_tile_extract);  x[v] = cond[v]                      v = b * (ny*nx) + k
+ *   for i in 0 .. n_iters-1:
+ *       for each pass of pass_samples consecutive v (the last one may be shorter):
+ *           ONE ROW of mi_denoise_slots_rule on (cond[pass], x[pass]):
+ *               t_rows = t_list[i] in every column, iter_base = i, sample_index = sample_offset + b(v), member = 0,
+ *               frame = (W, H*W, y0*W + x0) of the tile when seeded != 0 (else NULL),
+ *               t_before = t_list[i-1] or -1, t_after = t_list[i+1] or -1 (NULL under the reference's update),
+ *               x0_hist[pass] under MI_UPDATE_DPMPP2M, the caller's rule and flags
+ *       mi_tile_consensus(x, ...)          -- the one after the last step also writes image_out
+ *   tiles_out = x
+ * With a batch-invariant plan the result does not depend on pass_samples at all.  Only x is fused: the x0 history is a tile's own
+ * prediction.  Under the reference's update x is the clamped image state, under MI_UPDATE_DDIM and MI_UPDATE_DPMPP2M the unclamped
+ * x_t; the consensus is linear and convex either way, so a fused state stays inside the range of the states it fuses.  One tile that
+ * is the image is mi_denoise_rule / mi_denoise_dpm of it.  n_iters == 0 behaves as mi_denoise_tiled does (the tiles are the crops,
+ * image_out their blend).
+ * As mi_denoise_tiled: every rule is judged before the first launch; the plan's side streams are held over the call; the status
+ * word (mi_status) is cleared once and accumulates over all (step, pass) runs; every run joins its side streams -- once per
+ * (step, pass), where mi_denoise_tiled joins once per pass --; no device memory is allocated; the host never waits.
+ * MI_EINVAL before any GPU work: everything mi_denoise_tiled_rule refuses; MI_UPDATE_DPMPP2M with seeded != 0 or without x0_hist;
+ * x0_hist under any other rule; any two of noisy, image_out, tiles_out, x0_hist overlapping.
+ * NOT BUILT: fused tiled ensembles and self-ensembles, fused tickets of a session, fusing every n-th step or a range of steps,
+ * fusing the x0 history, a trajectory. */
+int mi_denoise_tiled_fused(mi_plan* plan, const float* noisy, float* image_out, float* tiles_out, float* x0_hist,
+                           int B, int H, int W, int th, int tw, int oy, int ox,
+                           const int32_t* t_list, int n_iters,
+                           const float* beta, const float* alpha, const float* alpha_hat, int noise_steps,
+                           int seeded, uint64_t seed, int64_t sample_offset, int pass_samples, int flags,
+                           const mi_update_rule* rule, void* workspace, size_t workspace_bytes, void* stream);
+
+/* Bytes of workspace mi_denoise_tiled_fused needs, THE SUM OF: the sampler workspace of a pass of tiles (as mi_tiled_workspace_bytes
+ * counts it); the condition tiles of ALL B * ny*nx virtual samples, rounded up to 256 bytes -- they are extracted once and kept for
+ * the whole call, since every step reads them again; and -- unless tiles_external != 0, i.e. tiles_out is given -- the tile states,
+ * B * ny*nx * C*th*tw * 4 bytes.  Host only, answered from the planner alone (it works before mi_unet_finalize); 0 + mi_last_error
+ * for arguments the call would refuse. */
+size_t mi_tiled_fused_workspace_bytes(mi_plan* plan, int B, int H, int W, int th, int tw, int oy, int ox, int pass_samples, int tiles_external);
+
 /* Status of the last mi_unet_forward / mi_denoise call that used `workspace` (its first word; the calls clear it when they
  * start).  SYNCHRONISES `stream` (one 4-byte device-to-host copy).  Returns MI_OK with *flags == 0, or MI_ERANGE with the
  * MI_STATUS_* bits in *flags: the kernels never turn a NaN / Inf activation or an operand beyond the split-fp16 range into

@@ -18,5 +18,5 @@ from .sampler import (DiffusionDenoiser, EnsembleQuantileResult, EnsembleResult,
                       view_codes_tiled, DenoisingLoss, LossMaps, LossProfile, loss_terms, noise_images, EnsembleScores,
                       ensemble_scores, NoisePowerSpectrum, noise_power_spectrum, nps_window, CrossSpectrum, cross_spectrum,
                       EnsembleModes, ensemble_modes, ChannelResponses, Detectability, DetectabilityStudy, channel_responses, hotelling,
-                      insert_signal, laguerre_gauss_channels, roi_grid)
+                      insert_signal, laguerre_gauss_channels, roi_grid, tile_consensus)
 from .session import SamplerSession, Ticket  # noqa: F401

@@ -7,7 +7,7 @@ img_size -> sampler -> uint8 -> bicubic resize back -> PNG, with the reference's
     python -m midd_amd.cli --image in.png --out out.png [--checkpoint ckpt.pth] [--variant cddpm|ddim]
                            [--img-size 512] [--inference-steps 25] [--seed N] [--samples K [--std-out std.npy]
                            [--quantiles 0.05,0.5,0.95 --quantiles-out q.npy]]
-                           [--tile N [--overlap O] [--views [auto|flips|d4] | --members K] [--std-out std.npy]
+                           [--tile N [--overlap O] [--tile-fuse end|step] [--views [auto|flips|d4] | --members K] [--std-out std.npy]
                             [--quantiles Q,Q --quantiles-out q.npy]]
                            [--self-ensemble [auto|flips|d4] [--std-out std.npy] [--quantiles Q,Q --quantiles-out q.npy]]
                            [--update reference|ddim|dpmpp2m [--eta F] [--no-clip-x0] [--x0-out traj.npy]]
@@ -54,11 +54,21 @@ def check_options(device_type: str = "cuda", img_size: int = 512, variant: str =
                   std_out=None, tile=None, quantiles=None, quantiles_out=None, self_ensemble=None, update: str = "reference",
                   eta: float = 0.0, clip_x0: bool = True, x0_out=None, bit_depth: int = 8, window=None, window_levels=None, views=None,
                   members=None, clean=None, loss_out=None, truth=None, scores_out=None, nps_out=None, nps_roi=None, nps_step=None,
-                  fidelity_out=None, fidelity_roi=None, fidelity_step=None, modes=None, modes_out=None, modes_json=None) -> Options:
+                  fidelity_out=None, fidelity_roi=None, fidelity_step=None, modes=None, modes_out=None, modes_json=None,
+                  tile_fuse: str = "end") -> Options:
     """The rules of denoise_image_diffusion's options (its docstring says what each option is), all of them and nowhere else: the
     function and main both call this.  Opens no file and touches no device; the two rules that compare an ROI with the image file
     itself follow the call in denoise_image_diffusion.  Raises ValueError, and RuntimeError for what runs only on a GPU."""
     on_gpu = torch.device(device_type).type == "cuda"
+    if tile_fuse not in ("end", "step"):
+        raise ValueError(f"--tile-fuse takes end or step (got {tile_fuse!r})")
+    if tile_fuse == "step":
+        if tile is None:
+            raise ValueError(f"--tile-fuse {tile_fuse} fuses the tiles of the tiled run after every step: it needs --tile N")
+        for flag, given in (("--members", members), ("--views", views), ("--samples", samples), ("--self-ensemble", self_ensemble)):
+            if given is not None:
+                raise ValueError(f"--tile-fuse {tile_fuse} cannot be combined with {flag}: the fused tiled run is one run of the image "
+                                 "(fused ensembles are not built)")
 
     def spectrum(flag, kernel, receives, out, roi, step, missing=None):
         """--nps-out and --fidelity-out: one rule list under two flag names."""
@@ -184,7 +194,7 @@ def denoise_image_diffusion(model_path: Optional[str], test_image_path: str, dev
                             truth: Optional[str] = None, scores_out: Optional[str] = None, nps_out: Optional[str] = None,
                             nps_roi: Optional[int] = None, nps_step: Optional[int] = None, fidelity_out: Optional[str] = None,
                             fidelity_roi: Optional[int] = None, fidelity_step: Optional[int] = None, modes: Optional[int] = None,
-                            modes_out: Optional[str] = None, modes_json: Optional[str] = None) -> Image.Image:
+                            modes_out: Optional[str] = None, modes_json: Optional[str] = None, tile_fuse: str = "end") -> Image.Image:
     """compute (not a reference argument): arithmetic of the network, see UNetDiffusion -- None keeps the default.
     seed (not a reference argument; cddpm): the stochastic sampler's noise is drawn on the device from this seed, so the same
     call gives the same image again (DiffusionDenoiser.denoise); None: torch.randn, as the reference.
@@ -203,6 +213,10 @@ def denoise_image_diffusion(model_path: Optional[str], test_image_path: str, dev
     run (DiffusionDenoiser.denoise_tiled_ensemble; the reference's update only).  std_out, quantiles and quantiles_out then describe
     the views / the draws, float32 at the image's own size [H, W] / [levels, H, W]; bit_depth 16 and window store the mean as they
     store the tiled image.  (samples and self_ensemble stay the ensembles of the RESIZED image and are refused together with tile.)
+    tile_fuse (not a reference argument; with tile only): "end" (the default) blends the tiles once, after each has run the whole
+    sampler loop alone (denoise_tiled); "step" makes the overlapping tiles agree after EVERY step (DiffusionDenoiser.denoise_tiled_fused),
+    so that no tile carries its own version of a shared strip into the blend.  update, bit_depth and window work with it as with tile;
+    not together with views, members, samples or self_ensemble.
     self_ensemble (not a reference argument; both variants): "auto", "flips" or "d4" -- the returned image is the MEAN over the
     flipped and rotated views of the image (DiffusionDenoiser.denoise_self_ensemble); std_out, quantiles and quantiles_out then
     describe the views instead of seeded draws.  Not together with samples or tile.
@@ -258,7 +272,8 @@ def denoise_image_diffusion(model_path: Optional[str], test_image_path: str, dev
                         update=update, eta=eta, clip_x0=clip_x0, x0_out=x0_out, bit_depth=bit_depth, window=window,
                         window_levels=window_levels, views=views, members=members, clean=clean, loss_out=loss_out, truth=truth,
                         scores_out=scores_out, nps_out=nps_out, nps_roi=nps_roi, nps_step=nps_step, fidelity_out=fidelity_out,
-                        fidelity_roi=fidelity_roi, fidelity_step=fidelity_step, modes=modes, modes_out=modes_out, modes_json=modes_json)
+                        fidelity_roi=fidelity_roi, fidelity_step=fidelity_step, modes=modes, modes_out=modes_out, modes_json=modes_json,
+                        tile_fuse=tile_fuse)
     rule, quantiles, recipe, tiled_ensemble = opt.rule, opt.quantiles, opt.recipe, opt.tiled_ensemble
     nps_roi, nps_step, fidelity_roi, fidelity_step = opt.nps_roi, opt.nps_step, opt.fidelity_roi, opt.fidelity_step
     for flag, out, roi in (("fidelity", fidelity_out, fidelity_roi), ("nps", nps_out, nps_roi)):
@@ -308,8 +323,9 @@ def denoise_image_diffusion(model_path: Optional[str], test_image_path: str, dev
                                                    seed=seed, quantiles=quantiles, return_samples=keep)
             what = f"Ensemble of {members} samples, tiled"
         else:
-            res = diffusion.denoise_tiled(input_tensor, inference_steps=inference_steps, tile=tile, overlap=overlap, seed=seed, **rule)
-            what = "Tiled"
+            run = diffusion.denoise_tiled_fused if tile_fuse == "step" else diffusion.denoise_tiled
+            res = run(input_tensor, inference_steps=inference_steps, tile=tile, overlap=overlap, seed=seed, **rule)
+            what = "Tiled, fused after every step" if tile_fuse == "step" else "Tiled"
         if on_gpu:
             torch.cuda.synchronize(device)
         print(f"{what}: {len(res.origins_y)} x {len(res.origins_x)} tiles of {tile}" + (f", seed {res.seed}" if res.seed is not None else ""))
@@ -541,6 +557,9 @@ def main(argv=None) -> None:
     ap.add_argument("--tile", type=int, default=None, metavar="N",
                     help="denoise the image at its own size as blended overlapping N x N tiles (N: a multiple of 8) instead of resizing it to --img-size")
     ap.add_argument("--overlap", type=int, default=32, help="with --tile: minimum overlap of neighbouring tiles (<= N / 2)")
+    ap.add_argument("--tile-fuse", default="end", choices=["end", "step"],
+                    help="with --tile: end (the default) blends the tiles once, after the last step; step makes the overlapping tiles "
+                         "agree after every sampler step (not with --views, --members, --samples or --self-ensemble)")
     ap.add_argument("--views", nargs="?", const="auto", default=None, choices=["auto", "flips", "d4"],
                     help="with --tile, both variants: save the mean over the flipped and rotated views of the image, each denoised as "
                          "blended tiles at the image's own size (auto: all 8); --std-out and --quantiles / --quantiles-out then describe "
@@ -617,7 +636,8 @@ def main(argv=None) -> None:
     later = dict(x0_out=args.x0_out, window=None, window_levels=None, views=args.views, members=args.members, clean=args.clean,
                  loss_out=args.loss_out, truth=args.truth, scores_out=args.scores_out, nps_out=args.nps_out, nps_roi=args.nps_roi,
                  nps_step=args.nps_step, fidelity_out=args.fidelity_out, fidelity_roi=args.fidelity_roi, fidelity_step=args.fidelity_step,
-                 modes=args.modes, modes_out=args.modes_out, modes_json=args.modes_json)
+                 modes=args.modes, modes_out=args.modes_out, modes_json=args.modes_json,
+                 tile_fuse=None if args.tile_fuse == "end" else args.tile_fuse)
     try:
         if args.quantiles is not None:
             options["quantiles"] = check_levels([float(v) for v in args.quantiles.split(",")])

@@ -267,6 +267,107 @@ extern "C" int mi_denoise_tiled(mi_plan* plan, const float* noisy, float* image_
                                  seeded, seed, sample_offset, pass_samples, flags, nullptr, workspace, workspace_bytes, stream);
 }
 
+// ---------------------------------------------------------------------------- tiled denoising, the tiles fused after every step
+extern "C" int mi_tile_consensus(float* tiles, int B, int C, int H, int W, int th, int tw, int oy, int ox, float* image_out, void* stream) {
+    TileGeom g{};
+    if (int rc = check_tile_run(B, C, H, W, th, tw, oy, ox, &g)) return rc;
+    if (!tiles) return fail(MI_EINVAL, "null argument");
+    const Buf buf[2] = {{tiles, (size_t)B * g.ny * g.nx * C * th * tw * sizeof(float), "tiles"},
+                        {image_out, (size_t)B * C * H * W * sizeof(float), "image_out"}};
+    if (int rc = check_no_overlap(buf, 2, "every pixel's value is written to its tile elements and to image_out in one launch")) return rc;
+    return launched(tile_consensus_launch(tiles, image_out, B, g, (hipStream_t)stream), "tile_consensus");
+}
+
+// mi_denoise_tiled_fused behind its rule (include/midd.h: the composition it equals).  The steps are the OUTER loop: step i runs
+// every pass as ONE ROW of the per-slot path -- the row mi_denoise_slots_rule would run for the pass: enqueue_run with the pass's
+// slot tables -- and one consensus launch over all the tile states follows.  The condition tiles of every pass stay in the
+// workspace for the whole call (tiled_fused_layout); x, the tile states, is tiles_out or the workspace.  As tiled_run: every rule
+// is judged before the first launch, plan->side_mu is held over the call, the status word is cleared once and accumulates over
+// all (step, pass) runs, every run joins its side streams (enqueue_run), no device memory is allocated and the host never waits.
+static int tiled_fused_run(mi_plan* plan, const float* noisy, float* image_out, float* tiles_out, float* x0_hist,
+                           int B, int H, int W, int th, int tw, int oy, int ox, const Schedule& sc,
+                           int seeded, uint64_t seed, int64_t sample_offset, int pass_samples, int flags,
+                           void* workspace, size_t workspace_bytes, void* stream) {
+    TileGeom tg{};
+    if (int rc = check_tiled_args(plan, B, H, W, th, tw, oy, ox, sample_offset, pass_samples, &tg)) return rc;
+    const int K = tg.ny * tg.nx;
+    const int64_t V = (int64_t)B * K;
+    const size_t chw = (size_t)tg.C * th * tw, img = (size_t)tg.C * H * W * sizeof(float), all = (size_t)V * chw * sizeof(float);
+    const bool dpm = sc.rule == MI_UPDATE_DPMPP2M, ruled = sc.rule != MI_UPDATE_REFERENCE;
+    const Buf buf[4] = {{noisy, (size_t)B * img, "noisy"}, {image_out, (size_t)B * img, "image_out"}, {tiles_out, all, "tiles_out"},
+                        {dpm ? x0_hist : nullptr, all, "x0_hist"}};
+    if (int rc = check_no_overlap(buf, 4, "noisy is read into the condition tiles, x0_hist beside the tiles by every step, and the consensus "
+                                          "writes the tiles and image_out in one launch")) return rc;
+    EnsembleLayout L{};
+    // (evaluated before the state check, reported after it: check_batched_call; host arithmetic only, as in the *_workspace_bytes queries)
+    const int layout_rc = tiled_fused_layout(plan, B, K, th, tw, pass_samples, tiles_out != nullptr, &L);
+    if (int rc = check_batched_call(plan, layout_rc, L, workspace, workspace_bytes, {noisy, image_out}, sc)) return rc;
+    Program *g_pass = nullptr, *g_tail = nullptr;            // the programs of a whole pass and of the shorter last one
+    if (int rc = check_call(plan, L.pass, th, tw, workspace, L.run_bytes, &g_pass)) return rc;
+    if (L.tail)
+        if (int rc = check_call(plan, L.tail, th, tw, workspace, L.run_bytes, &g_tail)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    char* ws = (char*)workspace;
+    float* cond = reinterpret_cast<float*>(ws + L.cond_off);
+    float* x = tiles_out ? tiles_out : reinterpret_cast<float*>(ws + L.samples_off);
+    std::lock_guard<std::mutex> side_lk(plan->side_mu);     // held over all steps: the side streams are per plan
+    HIPCHK(hipMemsetAsync(ws, 0, 256, s));                  // status word: once per call, the (step, pass) runs accumulate into it
+    for (int64_t v0 = 0; v0 < V; v0 += 65535) {             // cond[v] = tile v of noisy; x[v] = cond[v]
+        const int n = (int)(V - v0 < 65535 ? V - v0 : 65535);
+        if (int rc = launched(tile_extract_launch(noisy, cond + (size_t)v0 * chw, tg, (int)v0, n, s), "tile_extract")) return rc;
+    }
+    HIPCHK(hipMemcpyAsync(x, cond, all, hipMemcpyDeviceToDevice, s));
+    if (sc.n == 0) return launched(tile_blend_launch(x, image_out, B, tg, s), "tile_blend");      // no step: as mi_denoise_tiled
+    // the slot tables of one row of one pass (host memory: enqueue_run reads them while it enqueues)
+    std::vector<int32_t> t_row(L.pass), iter_base(L.pass), t_before(L.pass), t_after(L.pass);
+    std::vector<int64_t> sample_index(L.pass);
+    std::vector<uint32_t> frame((size_t)L.pass * 3);
+    StepNoise sn;
+    sn.seeded = seeded != 0; sn.seed = seed;
+    for (int i = 0; i < sc.n; ++i) {
+        for (int64_t v0 = 0; v0 < V; v0 += L.pass) {
+            const int n = (int)(V - v0 < L.pass ? V - v0 : L.pass);
+            for (int j = 0; j < n; ++j) {
+                const int64_t v = v0 + j, b = v / K;
+                const int k = (int)(v - b * K), ky = k / tg.nx, kx = k - ky * tg.nx;
+                t_row[j] = sc.t[i]; iter_base[j] = i;
+                t_before[j] = i > 0 ? sc.t[i - 1] : -1; t_after[j] = i + 1 < sc.n ? sc.t[i + 1] : -1;
+                sample_index[j] = sample_offset + b;
+                frame[(size_t)j * 3] = (uint32_t)W; frame[(size_t)j * 3 + 1] = (uint32_t)H * (uint32_t)W;
+                frame[(size_t)j * 3 + 2] = (uint32_t)tile_origin(ky, H, th, tg.ny) * (uint32_t)W + (uint32_t)tile_origin(kx, W, tw, tg.nx);
+            }
+            Schedule row = sc;                               // the caller's tables and rule; one row, this pass's columns
+            row.t = t_row.data(); row.n = 1; row.x0 = dpm ? x0_hist + (size_t)v0 * chw : nullptr; row.x0_stride = 0;
+            const SlotRows slots{iter_base.data(), sample_index.data(), nullptr, seeded ? frame.data() : nullptr,
+                                 ruled ? t_before.data() : nullptr, ruled ? t_after.data() : nullptr};
+            if (int rc = enqueue_run(plan, n == L.pass ? g_pass : g_tail, cond + (size_t)v0 * chw, x + (size_t)v0 * chw, n, th, tw, row, &slots,
+                                     sn, flags, ws, L.run_bytes, stream)) return rc;
+        }
+        if (int rc = launched(tile_consensus_launch(x, i == sc.n - 1 ? image_out : nullptr, B, tg, s), "tile_consensus")) return rc;
+    }
+    return MI_OK;
+}
+
+extern "C" int mi_denoise_tiled_fused(mi_plan* plan, const float* noisy, float* image_out, float* tiles_out, float* x0_hist,
+                                      int B, int H, int W, int th, int tw, int oy, int ox,
+                                      const int32_t* t_list, int n_iters,
+                                      const float* beta, const float* alpha, const float* alpha_hat, int noise_steps,
+                                      int seeded, uint64_t seed, int64_t sample_offset, int pass_samples, int flags,
+                                      const mi_update_rule* rule, void* workspace, size_t workspace_bytes, void* stream) {
+    Schedule sc{t_list, n_iters, beta, alpha, alpha_hat, noise_steps};
+    if (rule && rule->kind == MI_UPDATE_DPMPP2M) {
+        if (seeded) return fail(MI_EINVAL, "seeded with MI_UPDATE_DPMPP2M: the rule is deterministic, it has no noise term (limit: seeded == 0)");
+        if (int rc = apply_dpm(rule->clip_x0, x0_hist, &sc)) return rc;
+        if (!x0_hist) return fail(MI_EINVAL, "MI_UPDATE_DPMPP2M without x0_hist: the rule reads every tile's previous predicted image (limit: x0_hist [B*tiles,C,th,tw] on the device)");
+    } else {
+        if (int rc = apply_rule(rule, &sc)) return rc;
+        if (x0_hist) return fail(MI_EINVAL, "x0_hist with %s: the rule keeps no predicted image (limit: x0_hist NULL; MI_UPDATE_DPMPP2M takes it)",
+                                 sc.rule == MI_UPDATE_DDIM ? "MI_UPDATE_DDIM" : "the reference's update");
+    }
+    return tiled_fused_run(plan, noisy, image_out, tiles_out, x0_hist, B, H, W, th, tw, oy, ox, sc, seeded, seed, sample_offset, pass_samples,
+                           flags, workspace, workspace_bytes, stream);
+}
+
 // ---------------------------------------------------------------------------- ensembles of tiled runs
 // members x B images x tiles: the tile storage is indexed by a 32-bit int (check_tile_count has judged B * tiles)
 static int check_tiled_ensemble_size(int B, int members, const TileGeom& g) {

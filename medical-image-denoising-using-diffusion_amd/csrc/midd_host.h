@@ -132,6 +132,10 @@ int tiled_ensemble_layout(mi_plan* p, int B, int members, int tiles, int th, int
 // tiles_out is given), at L->samples_off]
 int tiled_self_ensemble_layout(mi_plan* p, int B, int n_views, int tiles, int H, int W, int th, int tw, int pass_samples, bool tiles_external,
                                EnsembleLayout* L, size_t* view_off);   // midd_planner.hip
+// mi_denoise_tiled_fused: the steps are the outer loop, so the condition tiles of EVERY pass are kept for the whole call:
+// [sampler workspace of a pass | condition tiles of all B * tiles virtual samples, at L->cond_off | the tile states (unless tiles_out
+// is given), at L->samples_off]
+int tiled_fused_layout(mi_plan* p, int B, int tiles, int th, int tw, int pass_samples, bool tiles_external, EnsembleLayout* L);   // midd_planner.hip
 }  // namespace midd
 
 struct mi_plan {

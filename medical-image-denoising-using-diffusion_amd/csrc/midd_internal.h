@@ -379,6 +379,9 @@ hipError_t tile_blend_launch(const float* tiles, float* out, int B, const TileGe
 // samples [B][M][C][H][W]; each of the three may be null (not all; std needs M >= 2).  The arithmetic of tile_blend_launch per
 // member, then of ensemble_reduce_launch over the members.  B * M * ny*nx <= 2^31 - 1
 hipError_t tile_blend_reduce_launch(const float* tiles, int B, int M, const TileGeom& g, float* mean, float* std, float* samples, hipStream_t s);
+// tiles [B][ny*nx][C][th][tw], IN PLACE: every element <- tile_blend_launch's value of the pixel it lies over; image [B][C][H][W] or
+// null <- those values (tile_consensus.hip; include/midd.h: THE CONSENSUS).  One launch, no temporary
+hipError_t tile_consensus_launch(float* tiles, float* image, int B, const TileGeom& g, hipStream_t s);
 
 // Per-pixel quantile maps over the members (quantile_common.h; include/midd.h: mi_ensemble_quantiles).  The levels travel as kernel
 // arguments; the members of a pixel are sorted in registers, hence the member limit.

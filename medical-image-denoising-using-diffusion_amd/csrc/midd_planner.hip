@@ -388,6 +388,22 @@ int midd::tiled_self_ensemble_layout(mi_plan* p, int B, int n_views, int tiles, 
     return MI_OK;
 }
 
+int midd::tiled_fused_layout(mi_plan* p, int B, int tiles, int th, int tw, int pass_samples, bool tiles_external, EnsembleLayout* L) {
+    if (int rc = ensemble_layout(p, B, tiles, th, tw, pass_samples, true, L)) return rc;      // the passes of one step
+    const size_t all = (size_t)B * tiles * p->cfg.in_channels * th * tw * sizeof(float);
+    L->samples_off = L->cond_off + ((all + 255) & ~(size_t)255);                              // the condition tiles of every pass stay
+    L->bytes = L->samples_off + (tiles_external ? 0 : all);
+    return MI_OK;
+}
+
+extern "C" size_t mi_tiled_fused_workspace_bytes(mi_plan* plan, int B, int H, int W, int th, int tw, int oy, int ox, int pass_samples, int tiles_external) {
+    TileGeom g{};
+    if (check_tiled_args(plan, B, H, W, th, tw, oy, ox, 0, pass_samples, &g)) return 0;
+    EnsembleLayout L{};
+    if (tiled_fused_layout(plan, B, g.ny * g.nx, th, tw, pass_samples, tiles_external != 0, &L)) return 0;
+    return L.bytes;
+}
+
 // Kernel symbol + algorithmic work of one op (for mi_profile_*).
 void midd::op_work(mi_plan* p, Program* g, const Op& o, std::string* name, double* flops, double* bytes) {
     const double B = g->B;

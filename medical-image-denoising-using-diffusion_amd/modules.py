@@ -666,6 +666,54 @@ class UNetDiffusion(nn.Module):
         return image, tiles, plan_t
 
     @torch.no_grad()
+    def run_tiled_fused(self, noisy: torch.Tensor, t_list, beta: torch.Tensor, alpha: torch.Tensor, alpha_hat: torch.Tensor,
+                        clamp_eps: bool, tile, overlap, seed: Optional[int] = None, sample_offset: int = 0, max_batch: int = 16,
+                        want_tiles: bool = False, no_split: bool = False, *, update: str = "reference", eta: float = 0.0,
+                        clip_x0: bool = True):
+        """``run_tiled`` with the steps as the outer loop and the overlapping tile states fused after every step, in one native
+        call (mi_denoise_tiled_fused) -> (image, tiles or None, TilePlan).  Every step runs the B * tiles crops in passes of at most
+        ``max_batch`` as one row of the per-slot path each, then one ``tile_consensus`` launch makes the tiles agree; the call
+        equals that composition of ``run_slots_rule`` and ``tile_consensus`` bit for bit.  seed None: no noise term.  update, eta,
+        clip_x0: the update rule, as in run_tiled ("dpmpp2m": a history buffer of every tile's own prediction, no seed)."""
+        rule = check_update(update, eta, clip_x0)
+        dpm = rule is not None and rule.kind == native.MI_UPDATE["dpmpp2m"]
+        if dpm and seed is not None:
+            raise ValueError("update='dpmpp2m' is deterministic: it takes no seed")
+        if seed is not None:
+            seed, sample_offset = check_seed(seed, sample_offset)
+        max_batch = check_member(max_batch, "max_batch", low=1)
+        self._check_image(noisy, "noisy_img")
+        B, Cc, H, W = noisy.shape
+        plan_t, th, tw, oy, ox, K = tiling(H, W, tile, overlap)
+        keep, sched = self._schedule_args(t_list, beta, alpha, alpha_hat)
+        dev = noisy.device
+        with self._lock, torch.cuda.device(dev):
+            plan = self._ensure_plan(time_rows=sched[-1])
+            src = noisy.contiguous()
+            image = torch.empty_like(src)
+            tiles = torch.empty((B, K, Cc, th, tw), dtype=torch.float32, device=dev) if want_tiles else None
+            pass_samples = self._pass_samples(max_batch, B * K)
+            ws = self._batched_workspace(native.lib().mi_tiled_fused_workspace_bytes,
+                                         (B, H, W, th, tw, oy, ox, pass_samples, 1 if want_tiles else 0), dev, "tiled_fused")
+            hist = None
+            if dpm:
+                hist = torch.empty((B * K, Cc, th, tw), dtype=torch.float32, device=dev)      # (as in run_sampler)
+                if self.poison_workspace is not None:
+                    hist.view(torch.uint8).fill_(self.poison_workspace)
+            self._invoke(native.lib().mi_denoise_tiled_fused,
+                         (plan, src.data_ptr(), image.data_ptr(), _ptr(tiles), _ptr(hist), B, H, W, th, tw, oy, ox) + sched
+                         + self._seed_args(seed, sample_offset) + (pass_samples, self._call_flags(clamp_eps, no_split))
+                         + (None if rule is None else C.byref(rule),), ws, dev)
+        return image, tiles, plan_t
+
+    def tiled_fused_workspace_bytes(self, B: int, H: int, W: int, tile, overlap=32, max_batch: int = 16, tiles_external: bool = False) -> int:
+        """Workspace of run_tiled_fused: the sampler workspace of a pass of tiles + the condition tiles of ALL B * tiles crops (kept
+        for the whole call, rounded up to 256 bytes) + the tile states unless ``tiles_external``."""
+        _, th, tw, oy, ox, K = tiling(H, W, tile, overlap)
+        return self._query_bytes("mi_tiled_fused_workspace_bytes", B, H, W, th, tw, oy, ox, self._pass_samples(max_batch, B * K),
+                                 1 if tiles_external else 0)
+
+    @torch.no_grad()
     def run_tiled_ensemble(self, noisy: torch.Tensor, t_list, beta: torch.Tensor, alpha: torch.Tensor, alpha_hat: torch.Tensor,
                            clamp_eps: bool, tile, overlap, members: int, seed: int, sample_offset: int = 0, member_offset: int = 0,
                            max_batch: int = 16, want_mean: bool = True, want_std: bool = True, want_samples: bool = False,

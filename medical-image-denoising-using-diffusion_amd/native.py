@@ -157,6 +157,11 @@ SYMBOLS = [
                                         C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p,
                                         C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int,
                                         C.c_void_p, C.c_int, C.c_uint64, C.c_int, C.POINTER(UpdateRule), C.c_void_p, C.c_size_t, C.c_void_p]),
+    ("mi_tile_consensus", C.c_int, [C.c_void_p] + [C.c_int] * 8 + [C.c_void_p, C.c_void_p]),
+    ("mi_denoise_tiled_fused", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 7 +
+                                        [C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int,
+                                         C.c_int, C.c_uint64, C.c_int64, C.c_int, C.c_int, C.POINTER(UpdateRule), C.c_void_p, C.c_size_t, C.c_void_p]),
+    ("mi_tiled_fused_workspace_bytes", C.c_size_t, [C.c_void_p] + [C.c_int] * 9),
     ("mi_debug_fetch", C.c_int, [C.c_void_p, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                  C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p]),
     ("mi_status", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]),

@@ -30,7 +30,7 @@ from .rules import (MAX_QUANTILE_LEVELS, MAX_QUANTILE_MEMBERS, NPS_DETREND, NPS_
                     _levels_arg, _pair, check_levels, check_member, check_members, check_nps_args, check_quantile_members, check_rule,
                     check_score_levels, check_seed, check_update, ddim_coefficients, dpm_coefficients, refuse_update)
 from .tiles import (TiledEnsembleQuantileResult, TiledEnsembleResult, TiledResult, TilePlan, _axis, _tile_tensor, tile_blend,  # noqa: F401
-                    tile_blend_quantiles, tile_blend_reduce, tile_extract, tile_plan, tiling)
+                    tile_blend_quantiles, tile_blend_reduce, tile_consensus, tile_extract, tile_plan, tiling)
 from .views import (MAX_VIEWS, VIEW_SETS, SelfEnsembleQuantileResult, SelfEnsembleResult, TiledSelfEnsembleQuantileResult,  # noqa: F401
                     TiledSelfEnsembleResult, _unview_args, _view_tensor, _views_arg, dihedral_quantiles, dihedral_reduce, dihedral_views,
                     tile_blend_unview_quantiles, tile_blend_unview_reduce, view_codes, view_codes_tiled)
@@ -248,6 +248,35 @@ class DiffusionDenoiser:
                                                   clamp_eps=not self._stochastic, tile=tile, overlap=overlap, seed=seed,
                                                   sample_offset=sample_offset, max_batch=max_batch, want_tiles=return_tiles,
                                                   **self._rule_kw(rule, update, eta, clip_x0))
+        return TiledResult(image, tiles, plan.origins_y, plan.origins_x, seed)
+
+    @torch.no_grad()
+    def denoise_tiled_fused(self, noisy_img: torch.Tensor, inference_steps: int = 25, tile=256, overlap=32, max_batch: int = 16,
+                            seed: Optional[int] = None, sample_offset: int = 0, return_tiles: bool = False,
+                            *, update: str = "reference", eta: float = 0.0, clip_x0: bool = True) -> TiledResult:
+        """``denoise_tiled`` whose overlapping tiles AGREE AFTER EVERY STEP (not a reference call; include/midd.h:
+        mi_denoise_tiled_fused).  ``denoise_tiled`` runs the whole sampler loop on every tile alone and cross-fades what the tiles
+        ended up with; the network has attention, so two tiles decide differently about the strip they share and the ramp only
+        hides it.  Here the steps are the outer loop: after each one a single ``tile_consensus`` launch replaces every tile element
+        by the blend of all the elements over its pixel (the usual per-step fusion of tiled diffusion), so every tile enters the
+        next forward with the same values wherever it shares pixels with a neighbour, and the result's ``tiles`` are exactly
+        ``tile_extract(image)``.  Same tiling, same arguments and the same ``TiledResult`` as ``denoise_tiled``; ``tile == image
+        size`` is ``denoise`` bit for bit.  The call equals, bit for bit, the composition of ``run_slots_rule`` rows and
+        ``tile_consensus`` at the same ``max_batch``; with ``batch_invariant=True`` it does not depend on ``max_batch`` at all.
+
+        The seed rules are ``denoise_tiled``'s: cddpm and ``update="ddim"`` with ``eta > 0`` are always seeded -- the noise field
+        belongs to the image, overlapping tiles draw the same noise, so fusing does not shrink it -- and ``seed=None`` draws a seed
+        and returns it; DDIM takes ``seed=None``; ``update="ddim"`` with ``eta=0`` ignores a seed; ``update="dpmpp2m"`` raises
+        ValueError on one (its ``x0`` history is every tile's own and is not fused).  There is no ``step_noise`` tensor.  The
+        workspace keeps the condition tiles of the whole batch (``UNetDiffusion.tiled_fused_workspace_bytes``)."""
+        rule = check_update(update, eta, clip_x0)
+        if rule is not None and rule.kind == native.MI_UPDATE["dpmpp2m"] and seed is not None:
+            raise ValueError("update='dpmpp2m' is deterministic: denoise_tiled_fused takes no seed with it")
+        seed, sample_offset = self._seed(self._draws(rule, seed), seed, sample_offset)
+        image, tiles, plan = self.model.run_tiled_fused(noisy_img, self._steps(inference_steps), self.beta, self.alpha, self.alpha_hat,
+                                                        clamp_eps=not self._stochastic, tile=tile, overlap=overlap, seed=seed,
+                                                        sample_offset=sample_offset, max_batch=max_batch, want_tiles=return_tiles,
+                                                        **self._rule_kw(rule, update, eta, clip_x0))
         return TiledResult(image, tiles, plan.origins_y, plan.origins_x, seed)
 
     @torch.no_grad()

@@ -120,6 +120,27 @@ def tile_blend(tiles: torch.Tensor, H: int, W: int, overlap=32) -> torch.Tensor:
 
 
 @torch.no_grad()
+def tile_consensus(tiles: torch.Tensor, H: int, W: int, overlap=32, inplace: bool = False, return_image: bool = False):
+    """tiles [B, ny * nx, C, th, tw] of an H x W tiling -> the tiles made to agree: every element becomes ``tile_blend``'s value of
+    the image pixel it lies over, in ONE kernel and one pass (mi_tile_consensus; include/midd.h: THE CONSENSUS) -- bit for bit
+    ``tile_extract(tile_blend(tiles, H, W, overlap), tile, overlap)`` without the image in between.  It is what
+    ``denoise_tiled_fused`` runs after every sampler step.  ``inplace=True`` works on ``tiles`` itself, which must then be a
+    contiguous float32 tensor (it is returned); else on a copy.  ``return_image=True``: -> (tiles, image) with image [B, C, H, W]
+    = ``tile_blend(tiles)`` of the input, written by the same launch."""
+    if inplace and isinstance(tiles, torch.Tensor) and tiles.dim() == 5 and not tiles.is_contiguous():
+        raise ValueError("tiles must be contiguous for inplace=True (the kernel writes the tensor it is given)")
+    src = _tile_tensor(tiles, "tiles", 5)
+    B, K, Cc, th, tw = src.shape
+    plan = check_tile_count(K, H, W, th, tw, overlap)
+    with torch.cuda.device(src.device):
+        out = src if inplace else src.clone()
+        image = torch.empty((B, Cc, int(H), int(W)), dtype=torch.float32, device=src.device) if return_image else None
+        native.check(native.lib().mi_tile_consensus(out.data_ptr(), B, Cc, int(H), int(W), th, tw, plan.overlap[0], plan.overlap[1],
+                                                    _ptr(image), torch.cuda.current_stream(src.device).cuda_stream))
+    return (out, image) if return_image else out
+
+
+@torch.no_grad()
 def tile_blend_reduce(tiles: torch.Tensor, H: int, W: int, overlap=32,
                       return_samples: bool = False) -> Tuple[torch.Tensor, Optional[torch.Tensor], Optional[torch.Tensor]]:
     """tiles [members, B, ny * nx, C, th, tw] of an H x W tiling -> (mean, std, samples): per-pixel mean and unbiased std
